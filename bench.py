@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- attention-forward TFLOP/s of the HIP path on MI355X, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one forward launch over the whole per-GPU batch (B=8,H=16,N=4096,d=64 fp16 in,
 fp32 out: the configuration BASELINE.json's metric is quoted on), inputs resident in HBM.
@@ -10,8 +10,15 @@ per-GPU workload on its own (b,h) shard of a global batch of 8*N (weak scaling, 
 collective -- SURVEY.md 8(e)); the barrier-bracketed wall time is max-reduced over ranks.
 
 Rank 0 prints ONE JSON line with the contract keys plus `roofline` (dominant kernel, HIP events
-on the launch stream) and `cpu_baseline` (the oracle's naive 3-loop fp32 port, timed on this
-host's cores over a bounded sample of the same workload).
+on the launch stream of the timed steps).  A plain run does only that: set up, warm up, time the
+steps, dump the outputs if asked, print.  `--full` adds what takes runs of its own: `cpu_baseline`
+(the oracle's naive 3-loop fp32 port, timed on this host's cores over a bounded sample of the same
+workload), `sustained` (launches after the timed region) and, for N>1, `cfg5_per_gpu`.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/out.npy (float32): the whole
+output when it fits in 48 MB, else a fixed seeded sample of whole output rows (sorted (b,h,n)
+row indices), shape [rows, d].  With N>1, rank r > 0 writes DIR/out_rank<r>.npy.  The inputs are
+seeded, so equal arguments give equal inputs from run to run.
 """
 import argparse
 import json
@@ -41,12 +48,18 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
                     help="BASELINE.json shorthand: cfg3 (B4 H8 N1024 d64 fp16), cfg4 (B8 H16 N4096 d64 fp16, the metric config), "
                          "cfg4bf16 (config 4 as written), cfg5 (one GPU's shard of B64 H16 N8192 d128 fp16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/out.npy (float32; a fixed seeded row sample if large)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras that take runs of their own: cpu_baseline, sustained and (N>1) cfg5_per_gpu")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: cpu_baseline's time budget")
     ap.add_argument("--sustained", type=int, default=300,
-                    help="launches run AFTER the timed region and reported under `sustained` (the first ~30 ms after idle run "
-                         "slower while the clocks settle; never part of `value`); 0 disables")
+                    help="with --full: launches run AFTER the timed region and reported under `sustained` (the first ~30 ms "
+                         "after idle run slower while the clocks settle; never part of `value`); 0 disables")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config:
         args.B, args.H, args.N, args.d, args.dtype = CONFIGS[args.config]
 
@@ -103,9 +116,12 @@ def main():
     value = total_flops / wall / 1e12
     achieved = flops_per_gpu / (kern_ms * 1e-3) / 1e12
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, o, ranks.rank, world)
+
     # after the timed region, outside `value`: the same launch back to back until the clocks have settled
     sustained = None
-    if args.sustained > 0:
+    if args.full and args.sustained > 0:
         sv0, sv1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(args.sustained // 3):
             step()
@@ -120,7 +136,7 @@ def main():
                      "frac": round(flops_per_gpu / (s_ms * 1e-3) / 1e12 / PEAK_TFLOPS, 4)}
     # N > 1: BASELINE config 5's per-GPU shard (B8 H16 N8192 d128) as an extra figure, a few launches
     cfg5 = None
-    if world > 1 and (B, H, N, d) != (8, 16, 8192, 128):
+    if args.full and world > 1 and (B, H, N, d) != (8, 16, 8192, 128):
         q5, k5, v5 = (torch.randn(8, 16, 8192, 128, generator=g, device=dev, dtype=torch.float32).to(dt) for _ in range(3))
         o5 = torch.empty(8, 16, 8192, 128, device=dev, dtype=odt)
         # (run behind the sustained block, 12 + 30 launches of 3.7 ms: the post-idle clock clamp -- the first ~30 ms of a
@@ -144,7 +160,7 @@ def main():
         del q5, k5, v5, o5
 
     cpu = None
-    if ranks.rank == 0 and not args.no_cpu_baseline:
+    if args.full and ranks.rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(q, k, v, o, N, d, args.cpu_seconds)
 
     if ranks.rank == 0:
@@ -181,6 +197,27 @@ def main():
             line["cfg5_per_gpu"] = cfg5
         print(json.dumps(line), flush=True)
     ranks.close()
+
+
+DUMP_BYTES = 48 << 20     # per run, under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, o, rank, world):
+    """DIR/out.npy (rank 0) or DIR/out_rank<r>.npy: the output as float32, whole if it fits in DUMP_BYTES / world, else
+    the rows at a fixed seeded set of sorted (b,h,n) indices (numpy's default_rng(1234)), shape [rows, d]."""
+    import numpy as np
+    import torch
+    d = o.shape[-1]
+    flat = o.reshape(-1, d)
+    rows_cap = max(1, DUMP_BYTES // world // (4 * d))
+    if flat.shape[0] > rows_cap:
+        idx = np.sort(np.random.default_rng(1234).choice(flat.shape[0], size=rows_cap, replace=False))
+        sample = flat.index_select(0, torch.from_numpy(idx).to(o.device))
+    else:
+        sample = o
+    os.makedirs(out_dir, exist_ok=True)
+    name = "out.npy" if rank == 0 else f"out_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), np.ascontiguousarray(sample.float().cpu().numpy(), dtype=np.float32))
 
 
 def cpu_threads():

@@ -35,8 +35,10 @@ GENERAL = [
     ("bh1_n77_d128_bf16_normal", 1, 77, 128, o.BF16, 14, o.NORMAL),
     ("bh2_n64_d16_f16_normal", 2, 64, 16, o.F16, 15, o.NORMAL),             # generic-kernel head dims
     ("bh2_n50_d32_f16_uniform", 2, 50, 32, o.F16, 16, o.UNIFORM),
-    ("memprofile_bh4_n512_d64_f16_normal", 4, 512, 64, o.F16, 17, o.NORMAL),  # memprofile.cu:409-411 shape
+    ("memprofile_bh3_n512_d64_f16_normal", 4, 512, 64, o.F16, 17, o.NORMAL),  # memprofile.cu:409-411 shape
 ]
+# heads kept of a case's BH (each head is an independent problem): a committed file stays under 1 MiB
+KEEP_HEADS = {"memprofile_bh3_n512_d64_f16_normal": 3}
 
 # 16x16 streaming family: name, B, L, seed (reference driver: B=1024, L=128, N(0,1) seed 42,
 # flashattn_streaming_16x16_mw.cu:322-349; a B=8 slice is committed)
@@ -46,12 +48,19 @@ STREAM16 = [
     ("s16_b3_l80_normal", 3, 80, 44),
 ]
 
+# fp32 N(0,1) problems (numpy default_rng(0), drawn q, k, v per case in this order) and the reference's own outputs on
+# them, for tests/test_oracle.py::test_oracle_matches_reference_build where oracle/_ref cannot be built.  Kept in a
+# sub-directory: the *.npz at the top are the 16-bit fixtures every parity test walks.
+REF_BUILD = ("ref_build/random_normal_f32", [(1, 1, 16), (2, 33, 48), (1, 130, 64), (3, 64, 128)])
+
 
 def main():
     o.build()
     assert o.have_ref(), "oracle/_ref/libref_cpu.so missing: /root/reference not available?"
     for name, bh, n, d, fmt, seed, dist in GENERAL:
         (q, k, v), (qb, kb, vb) = o.make_qkv(bh, n, d, fmt, seed, dist)
+        h = KEEP_HEADS.get(name, bh)
+        q, k, v, qb, kb, vb = q[:h], k[:h], v[:h], qb[:h], kb[:h], vb[:h]
         expected = o.reference_forward(q, k, v)   # the reference's own function
         np.savez_compressed(os.path.join(HERE, name + ".npz"), q=qb, k=kb, v=vb,
                             fmt=np.int32(fmt), expected=expected, kind="general")
@@ -79,6 +88,15 @@ def main():
         np.savez_compressed(os.path.join(HERE, name + ".npz"), q=qb, k=kb, v=vb,
                             fmt=np.int32(o.F16), expected=expected, kind="stream16")
         print(name, expected.shape)
+    name, shapes = REF_BUILD
+    rng = np.random.default_rng(0)
+    arrays = {}
+    for i, (bh, n, d) in enumerate(shapes):
+        q, k, v = (rng.standard_normal((bh, n, d)).astype(np.float32) for _ in range(3))
+        arrays.update({f"q{i}": q, f"k{i}": k, f"v{i}": v, f"expected{i}": o.reference_forward(q, k, v)})
+    os.makedirs(os.path.join(HERE, os.path.dirname(name)), exist_ok=True)
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrays)
+    print(name, len(shapes), "cases")
 
 
 if __name__ == "__main__":

@@ -853,7 +853,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, FA_BENCH_BACKEND="gloo", FA_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--sustained", "0"]
+           "--full", "--no-cpu-baseline", "--sustained", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,6 @@ import glob
 import os
 
 import numpy as np
-import pytest
 
 
 def _load(path):
@@ -35,15 +34,18 @@ def test_oracle_matches_golden_general(oracle, golden_dir):
         assert oracle.max_abs(got32, exp) <= 5e-6, path
 
 
-def test_oracle_matches_reference_build(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    rng = np.random.default_rng(0)
-    for bh, n, d in [(1, 1, 16), (2, 33, 48), (1, 130, 64), (3, 64, 128)]:
-        q, k, v = (rng.standard_normal((bh, n, d)).astype(np.float32) for _ in range(3))
-        ref = oracle.reference_forward(q, k, v)
-        assert oracle.max_abs(oracle.forward(q, k, v, accum=1), ref) <= 1e-7
-        assert oracle.max_abs(oracle.forward(q, k, v, accum=0), ref) <= 5e-6
+def test_oracle_matches_reference_build(oracle, golden_dir):
+    """fp32 N(0,1) problems against the reference's own oracle: its recorded outputs (tests/golden/ref_build/), and
+    oracle/_ref itself when it is built here."""
+    z = _load(os.path.join(golden_dir, "ref_build", "random_normal_f32.npz"))
+    shapes = [(1, 1, 16), (2, 33, 48), (1, 130, 64), (3, 64, 128)]
+    for i, (bh, n, d) in enumerate(shapes):
+        q, k, v = (z[f"{x}{i}"] for x in "qkv")
+        assert q.shape == k.shape == v.shape == (bh, n, d)
+        refs = [z[f"expected{i}"]] + ([oracle.reference_forward(q, k, v)] if oracle.have_ref() else [])
+        for ref in refs:
+            assert oracle.max_abs(oracle.forward(q, k, v, accum=1), ref) <= 1e-7
+            assert oracle.max_abs(oracle.forward(q, k, v, accum=0), ref) <= 5e-6
 
 
 def test_oracle_rows_subset_and_threads(oracle):

@@ -15,7 +15,7 @@ cd /tmp; export TMPDIR=/tmp
 CMD=(python3 "$R/bench.py" --config "$cfg" --steps 20 --warmup 5 --no-cpu-baseline --sustained 0)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- "${CMD[@]}" > "$O/kt.log" 2>&1
 # per-dispatch durations of an un-profiled-counter run with the sustained tail (the post-idle transient): kernel trace only
-rocprofv3 --kernel-trace --output-format csv -d "$O/kt_long" -- python3 "$R/bench.py" --config "$cfg" --steps 20 --warmup 5 --no-cpu-baseline --sustained 150 > "$O/kt_long.log" 2>&1 || true
+rocprofv3 --kernel-trace --output-format csv -d "$O/kt_long" -- python3 "$R/bench.py" --config "$cfg" --steps 20 --warmup 5 --full --no-cpu-baseline --sustained 150 > "$O/kt_long.log" 2>&1 || true
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU \
     --output-format csv -d "$O/pmc_sq" -- "${CMD[@]}" > "$O/pmc_sq.log" 2>&1
 rocprofv3 --pmc SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES GRBM_GUI_ACTIVE \
