@@ -64,7 +64,7 @@ FA_EXPORT int fa_debug_il_times(const void* Q, const void* K, const void* V, voi
 
 #endif  // FA_EXPERIMENTS
 
-// 1 when this build carries the experimental A/B kernels (explicit algo ids 3, 4, 7-12, 14, 15), else 0.
+// 1 when this build carries the experimental A/B kernels (explicit algo ids 7, 8, 13, 14, 16-22, 25), else 0.
 FA_EXPORT int fa_mi355_has_experiments(void)
 {
 #ifdef FA_EXPERIMENTS

@@ -20,10 +20,11 @@
 // (rare, wave-uniform branch at the end of the iteration) rescales O, l and the packed P(t) that
 // has not been multiplied into O yet.
 //
-// The vector pipe is the bottleneck at d=64 (rocprofv3: VALU-active 64-72 % of SIMD time, MFMA 41 %), so
-// vector instructions are traded for matrix ones where possible: the row sums l = sum_k P come out
-// of four extra MFMAs per tile against an all-ones A fragment (no LDS traffic; every lane then holds
-// the complete row sum of its query, no cross-half exchange), and c*S - m is a packed v_pk_fma_f32.
+// The vector pipe is the bottleneck at d=64 (rocprofv3: VALU-active 64-72 % of SIMD time, MFMA 41 %), but
+// the two trades of vector instructions for others that were tried both lost and are not in the stream:
+// the row sums l = sum_k P stay v_adds on the fp32 p (the kernel is POWER-limited, and four extra MFMAs
+// per tile against an all-ones A fragment cost more energy than 34 v_add: -4.9 % wall for the v_adds),
+// and c*S - m stays two v_fma_f32 (see fma_pair).
 //
 // K(t+2) and V(t) are fetched HBM/L2 -> registers at the top of iteration t and written to LDS at
 // its end (2-deep rings for K and V, one barrier per iteration): the role of the reference's
@@ -46,34 +47,7 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
-#ifndef FA_IL_READ_AHEAD
-#define FA_IL_READ_AHEAD 4
-#endif
-#ifndef FA_IL_SETPRIO
-#define FA_IL_SETPRIO 1
-#endif
-#ifndef FA_IL_NO_MAX
-#define FA_IL_NO_MAX 0   // experiment: skip the per-tile row max (UNSAFE: no overflow protection)
-#endif
-#ifndef FA_IL_SLOT_FENCE
-#define FA_IL_SLOT_FENCE 1
-#endif
-#ifndef FA_IL_STAGE_NUM
-#define FA_IL_STAGE_NUM 3
-#endif
-#ifndef FA_IL_FRONT_STEPS
-#define FA_IL_FRONT_STEPS 0   // VALU pair-steps issued right after the barrier, under the first LDS reads' latency
-#endif
-#ifndef FA_IL_OCC
-#define FA_IL_OCC 2   // waves per SIMD the register budget is held to (experiments: 3 forces spills)
-#endif
-#ifndef FA_IL_MFMA_SUM
-#define FA_IL_MFMA_SUM 0   // 0: row sums by v_add on the fp32 p (default: the kernel is POWER-limited and 4 extra MFMAs per tile cost more energy than 34 v_add; -4.9 % wall); 1: by 4 MFMAs against an all-ones fragment
-#endif
-#ifndef FA_IL_MFMA_ORDER
-#define FA_IL_MFMA_ORDER 0
-#endif
-constexpr int kReadAhead = FA_IL_READ_AHEAD;             // LDS operand reads run this many MFMAs ahead
+constexpr int kReadAhead = 4;                            // LDS operand reads run this many MFMAs ahead
 constexpr int kFragRing  = kReadAhead + 1;
 
 // kDiag: diagnostic build only (never the shipped path): per-wave s_memtime sums of the time spent
@@ -85,7 +59,7 @@ constexpr int kFragRing  = kReadAhead + 1;
 // tile in ~1360 cycles, the younger in ~2180, and the older then idles at the workgroup barrier);
 // across workgroups nobody waits for the slower wave, so the unfairness costs nothing.
 template <typename T, int D, bool kOutF32, int W, bool kDiag = false, int kAblate = 0>
-__global__ __launch_bounds__(64 * W, FA_IL_OCC)
+__global__ __launch_bounds__(64 * W, 2)   // two waves per SIMD: the register budget
 void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restrict__ Kg,
                       const uint16_t* __restrict__ Vg, void* __restrict__ Og,
                       int N, int nqb, float scale_log2e, unsigned long long* __restrict__ diag = nullptr,
@@ -199,15 +173,13 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) zero16[i] = 0.0f;
     float m_ref = 0.0f;    // reference max of this lane's query row, log2 units (c*S)
-    float l_part = 0.0f;   // FA_IL_MFMA_SUM == 0: this half-wave's share of the row sum (fp32 p, v_add)
-    f32x16 o_l = zero16;   // row sums: accumulator of ones(32x16).P^T, every register = l of this lane's row
-    const u32x4 ones = {T::kOnes2, T::kOnes2, T::kOnes2, T::kOnes2};
+    float l_part = 0.0f;   // this half-wave's share of the row sum (fp32 p, v_add)
 
     const int ntiles = (N + kBlockN - 1) / kBlockN;
     const bool partial = (N % kBlockN) != 0;
 
     constexpr int nQK = 2 * G::kKSteps;   // MFMAs of S(t+1) = K.Q^T
-    constexpr int nPV = 4 * (G::kDBlocks + FA_IL_MFMA_SUM);  // MFMAs of O^T += V^T.P^T (plus the row-sum block, A = ones)
+    constexpr int nPV = 4 * G::kDBlocks;  // MFMAs of O^T += V^T.P^T
 
     auto keep_alive = [&](u32x4& v) { asm volatile("" : "+v"(v)); };
     auto mask_tail = [&](int tile, f32x16 (&s)[2]) {   // keys >= N -> -inf (p = 0)
@@ -228,8 +200,6 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         for (int db = 0; db < G::kDBlocks; ++db)
 #pragma unroll
             for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o_l[i] *= alpha;
         l_part *= alpha;
 #pragma unroll
         for (int k4 = 0; k4 < 4; ++k4)   // P(t) is still waiting for its PV: bring it to the new scale too
@@ -246,10 +216,9 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         constexpr bool kHasPrev = decltype(has_prev_c)::value;
         constexpr bool kHasNext = decltype(has_next_c)::value;
         constexpr int nQ = kHasNext ? nQK : 0, nP = kHasPrev ? nPV : 0, nAll = nQ + nP;
-        // slot -> MFMA index: QK^T first (order 0) or PV first (order 1); indices < nQ are QK^T MFMAs
-        auto mfma_of = [](int slot) constexpr { return FA_IL_MFMA_ORDER == 1 ? (slot < nP ? nQ + slot : slot - nP) : slot; };
+        // slot i holds MFMA i: the QK^T MFMAs first (i < nQ), then PV
         constexpr int kSteps = 16;   // VALU pair-steps (2 scores each)
-        constexpr int kStageSlot = nAll > 0 ? (FA_IL_STAGE_NUM * nAll) / 4 : -1;   // slot in front of which the staged tiles are written
+        constexpr int kStageSlot = nAll > 0 ? (3 * nAll) / 4 : -1;   // slot in front of which the staged tiles are written
 
         if constexpr (!(kAblate & 8)) {
             load_k(st_fetch, t + 3);   // requested now, landed in LDS during iteration t+1
@@ -260,17 +229,16 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         constexpr int kPar = decltype(par_c)::value;
         const unsigned kbuf = kPar >= 0 ? (unsigned)kPar : ((unsigned)(t + 1) & 1u), vbuf = kbuf;
         u32x4 frag[kFragRing];
-        auto issue_reads = [&](auto slot_c) {   // LDS operand reads of the MFMA in slot `slot`
-            constexpr int slot = decltype(slot_c)::value;
-            constexpr int i = slot < nAll ? mfma_of(slot) : nAll;
+        auto issue_reads = [&](auto slot_c) {   // LDS operand reads of the MFMA in slot i (may lie past the end)
+            constexpr int i = decltype(slot_c)::value;
             if constexpr ((kAblate & 1) != 0) {   // timing ablation: no LDS operand reads
-                if constexpr (i < nAll) frag[slot % kFragRing] = qf[i % G::kKSteps];
+                if constexpr (i < nAll) frag[i % kFragRing] = qf[i % G::kKSteps];
             } else if constexpr (i < nAll) {
                 if constexpr (i < nQ) {
                     constexpr int kb = i / G::kKSteps, ks = i % G::kKSteps;
-                    frag[slot % kFragRing] = lds_read16(smem, kbuf * G::kTileBytes + kb * 32u * G::kRowBytes + k_rd_row +
+                    frag[i % kFragRing] = lds_read16(smem, kbuf * G::kTileBytes + kb * 32u * G::kRowBytes + k_rd_row +
                                                                (((2u * ks + h) ^ k_rd_swz) << 4));
-                } else if constexpr ((i - nQ) / 4 < G::kDBlocks) {
+                } else {
                     constexpr int j = i - nQ, db = j / 4, ks = j % 4;
                     u32x4 vf;
 #pragma unroll
@@ -280,24 +248,21 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
                         vf[2 * jj] = half[0];
                         vf[2 * jj + 1] = half[1];
                     }
-                    frag[slot % kFragRing] = vf;
+                    frag[i % kFragRing] = vf;
                 }
             }
         };
         auto issue_mfma = [&](auto slot_c) {
-            constexpr int slot = decltype(slot_c)::value;
-            constexpr int i = mfma_of(slot);
+            constexpr int i = decltype(slot_c)::value;
             if constexpr ((kAblate & 2) != 0) {   // timing ablation: no MFMA (operands kept alive)
-                keep_alive(frag[slot % kFragRing]);
+                keep_alive(frag[i % kFragRing]);
             } else if constexpr ((kAblate & 32) != 0) {   // timing ablation: reads issued, MFMA does not wait for them
                 if constexpr (i < nQ) {
                     constexpr int kb = i / G::kKSteps, ks = i % G::kKSteps;
                     s_nxt[kb] = T::mfma32(qf[(ks + 1) % G::kKSteps], qf[ks], ks == 0 ? zero16 : s_nxt[kb]);
-                } else if constexpr ((i - nQ) / 4 < G::kDBlocks) {
+                } else {
                     constexpr int j = i - nQ, db = j / 4, ks = j % 4;
                     o[db] = T::mfma32(qf[ks], pk_prev[ks], o[db]);
-                } else {
-                    o_l = T::mfma32(ones, pk_prev[(i - nQ) % 4], o_l);
                 }
                 if constexpr (i + 1 == nAll) {
 #pragma unroll
@@ -305,12 +270,10 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
                 }
             } else if constexpr (i < nQ) {
                 constexpr int kb = i / G::kKSteps, ks = i % G::kKSteps;
-                s_nxt[kb] = T::mfma32(frag[slot % kFragRing], qf[ks], ks == 0 ? zero16 : s_nxt[kb]);
-            } else if constexpr ((i - nQ) / 4 < G::kDBlocks) {
-                constexpr int j = i - nQ, db = j / 4, ks = j % 4;
-                o[db] = T::mfma32(frag[slot % kFragRing], pk_prev[ks], o[db]);
+                s_nxt[kb] = T::mfma32(frag[i % kFragRing], qf[ks], ks == 0 ? zero16 : s_nxt[kb]);
             } else {
-                o_l = T::mfma32(ones, pk_prev[(i - nQ) % 4], o_l);   // row sums: no LDS operand
+                constexpr int j = i - nQ, db = j / 4, ks = j % 4;
+                o[db] = T::mfma32(frag[i % kFragRing], pk_prev[ks], o[db]);
             }
         };
 
@@ -319,22 +282,12 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         //            and (last six steps) three max chains over S(t+1).
         const float neg_m = -m_ref;
         float mx0 = -INFINITY, mx1 = -INFINITY, mx2 = -INFINITY, ls0 = 0.0f, ls1 = 0.0f;
-#ifndef FA_IL_PKFMA
-#define FA_IL_PKFMA 0   // 1: one v_pk_fma_f32 per pair (round 1).  Packed fp32 stalls behind the matrix pipe when it is issued
-                        // between MFMAs (slot model: 81 vs 45.5 cycles per slot), so the interleaved stream uses two v_fma_f32
-#endif
+        // Two v_fma_f32, not one v_pk_fma_f32 per pair: packed fp32 stalls behind the matrix pipe when it is issued between
+        // MFMAs (slot model: 81 vs 45.5 cycles per slot).
         auto fma_pair = [&](auto jc) {
             constexpr int e0 = 2 * decltype(jc)::value, e1 = e0 + 1;
-            if constexpr (FA_IL_PKFMA) {
-                const f32x2 c2 = {c, c}, neg_m2 = {neg_m, neg_m};
-                f32x2 x = {s_cur[e0 >> 4][e0 & 15], s_cur[e1 >> 4][e1 & 15]};
-                x = __builtin_elementwise_fma(x, c2, neg_m2);
-                s_cur[e0 >> 4][e0 & 15] = x[0];
-                s_cur[e1 >> 4][e1 & 15] = x[1];
-            } else {
-                s_cur[e0 >> 4][e0 & 15] = __builtin_fmaf(s_cur[e0 >> 4][e0 & 15], c, neg_m);
-                s_cur[e1 >> 4][e1 & 15] = __builtin_fmaf(s_cur[e1 >> 4][e1 & 15], c, neg_m);
-            }
+            s_cur[e0 >> 4][e0 & 15] = __builtin_fmaf(s_cur[e0 >> 4][e0 & 15], c, neg_m);
+            s_cur[e1 >> 4][e1 & 15] = __builtin_fmaf(s_cur[e1 >> 4][e1 & 15], c, neg_m);
         };
         auto exp_pair = [&](auto jc) {
             constexpr int e0 = 2 * decltype(jc)::value, e1 = e0 + 1;
@@ -344,19 +297,17 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         auto fin_pair = [&](auto jc) {
             constexpr int j = decltype(jc)::value, e0 = 2 * j, e1 = e0 + 1;
             pk_cur[j >> 2][j & 3] = T::pack2(s_cur[e0 >> 4][e0 & 15], s_cur[e1 >> 4][e1 & 15]);
-            if constexpr (!FA_IL_MFMA_SUM) {
-                if constexpr (T::kSumRounded) {
-                    if constexpr ((j & 1) == 0) ls0 = T::sum2(pk_cur[j >> 2][j & 3], ls0);
-                    else ls1 = T::sum2(pk_cur[j >> 2][j & 3], ls1);
-                } else {
-                    ls0 += s_cur[e0 >> 4][e0 & 15];
-                    ls1 += s_cur[e1 >> 4][e1 & 15];
-                }
+            if constexpr (T::kSumRounded) {
+                if constexpr ((j & 1) == 0) ls0 = T::sum2(pk_cur[j >> 2][j & 3], ls0);
+                else ls1 = T::sum2(pk_cur[j >> 2][j & 3], ls1);
+            } else {
+                ls0 += s_cur[e0 >> 4][e0 & 15];
+                ls1 += s_cur[e1 >> 4][e1 & 15];
             }
         };
         // The max chains read S(t+1) inside the slot sequence only when every QK^T MFMA has been
         // issued before the first of those steps (steady iterations); otherwise after the slots.
-        constexpr bool kMaxInSlots = kTrack && FA_IL_MFMA_ORDER == 0 && kHasNext && kHasPrev && ((kSteps - 6) * nAll / kSteps >= nQ);
+        constexpr bool kMaxInSlots = kTrack && kHasNext && kHasPrev && ((kSteps - 6) * nAll / kSteps >= nQ);
         auto max_step = [&](auto kc) {   // 6 scores of S(t+1), three independent chains
             constexpr int e0 = 6 * decltype(kc)::value;
             constexpr int a0 = e0 < 32 ? e0 : 31, a1 = e0 + 1 < 32 ? e0 + 1 : 31, a2 = e0 + 2 < 32 ? e0 + 2 : 31;
@@ -382,19 +333,12 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
         fma_pair(std::integral_constant<int, 0>{});
         fma_pair(std::integral_constant<int, 1>{});
         exp_pair(std::integral_constant<int, 0>{});
-        constexpr int kFront = (nAll > 0 && !kMaxInSlots) ? FA_IL_FRONT_STEPS : 0;
-        if constexpr (kFront > 0) {
-            // Every LDS read of this iteration is of data that became visible at the barrier just
-            // passed, so the first MFMA cannot issue for one LDS round trip: fill it with VALU work.
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<kFront>([&](auto jc) { valu_step(jc); });
-        }
         if constexpr (nAll == 0) {
             static_for<kSteps>([&](auto jc) { valu_step(jc); });
         } else {
             static_for<nAll>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
-                if constexpr (FA_IL_SLOT_FENCE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);   // program order IS issue order
                 if constexpr (i == kStageSlot && !(kAblate & 8)) {
                     // land the staged tiles mid-iteration: the loads were issued at the top, and the
                     // LDS writes are long complete when the iteration reaches its barrier
@@ -404,17 +348,17 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
                 // The SIMD arbitrates between its two waves by age; raising the priority around the
                 // short MFMA + LDS-read issue lets the younger wave feed the long-latency units as
                 // soon as it gets there instead of queueing behind the older wave's VALU stream.
-                if constexpr (FA_IL_SETPRIO) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
                 issue_mfma(ic);
                 issue_reads(std::integral_constant<int, i + kReadAhead>{});
-                if constexpr (FA_IL_SETPRIO) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
                 // VALU steps [i*kSteps/nAll, (i+1)*kSteps/nAll)
-                constexpr int j0 = kFront + i * (kSteps - kFront) / nAll, j1 = kFront + (i + 1) * (kSteps - kFront) / nAll;
+                constexpr int j0 = i * kSteps / nAll, j1 = (i + 1) * kSteps / nAll;
                 static_for<j1 - j0>([&](auto dj) { valu_step(std::integral_constant<int, j0 + decltype(dj)::value>{}); });
             });
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!FA_IL_MFMA_SUM) l_part += ls0 + ls1;
+        l_part += ls0 + ls1;
 
         if constexpr (kHasNext && !kTrack) {
             if (mask_next) mask_tail(t + 1, s_nxt);   // only ever true in a peeled iteration
@@ -446,8 +390,8 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
     // tile 0 plus kHeadroom) and never looks at a row max again: the 18 v_max3 + compare + branch
     // per tile are pure cost on a vector-issue-bound loop (-4.6 % measured).  It is exact unless a
     // later score exceeds the reference by more than the 16-bit format can hold (p = 2^(x-m) > 65504
-    // for fp16, > 3e38 for bf16): then p becomes inf, the row sum -- accumulated by MFMA from the very
-    // same packed P -- becomes inf/NaN, and that is tested once per row at the end.  If any row of the
+    // for fp16, > 3e38 for bf16): then p becomes inf, which the fp32 row sum shows (it reaches the
+    // format's range), and that is tested once per row at the end.  If any row of the
     // workgroup overflowed, the whole workgroup (staging is cooperative) re-runs in the tracking mode
     // with the lazy running max.  Underflow is harmless: the reference is an actual score of the row,
     // so one term has weight 2^-kHeadroom and anything that underflows is < 2^-24 of it.
@@ -460,7 +404,6 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
     auto run = [&](auto track_c) {
 #pragma unroll
         for (int db = 0; db < G::kDBlocks; ++db) o[db] = zero16;
-        o_l = zero16;
         l_part = 0.0f;
         // ---- prologue: K(0), K(1) into LDS; S(0) and the exact row max of tile 0 ---------------------
         load_k(stA, 0);
@@ -535,17 +478,13 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
                     }
                     o[db] = T::mfma32(vf, pkA[ks], o[db]);
                 }
-    #pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                if constexpr (FA_IL_MFMA_SUM) o_l = T::mfma32(ones, pkA[ks], o_l);
         }
-
     };
     run(no);
     {
-        // without the MFMA row sum: a packed p can only have overflowed if the fp32 row sum reached the format's range
-        const float l_chk = FA_IL_MFMA_SUM ? o_l[0] : l_part + swap_halves(l_part);
-        const bool bad = !(__builtin_fabsf(l_chk) < (FA_IL_MFMA_SUM || T::id == 1 ? 0x1p+96f : 60000.0f));
+        // a packed p can only have overflowed if the fp32 row sum reached the format's range
+        const float l_chk = l_part + swap_halves(l_part);
+        const bool bad = !(__builtin_fabsf(l_chk) < (T::id == 1 ? 0x1p+96f : 60000.0f));
         if (__syncthreads_or(bad ? 1 : 0)) {
             __syncthreads();   // everybody is out of the first pass's LDS reads
             run(yes);
@@ -553,7 +492,7 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
     }
 
     // ---- normalise and store: lane holds O[q_row][db*32 + 8g + 4h + 0..3] in o[db][4g..4g+3] ---
-    const float inv = 1.0f / (FA_IL_MFMA_SUM ? o_l[0] : l_part + swap_halves(l_part));   // every register of o_l holds the full row sum
+    const float inv = 1.0f / (l_part + swap_halves(l_part));
     constexpr unsigned es = kOutF32 ? 4u : 2u;
     const __amdgpu_buffer_rsrc_t ro =
         make_rsrc(reinterpret_cast<char*>(Og) + (size_t)bh * head_elems * es, (unsigned)(head_elems * es));

@@ -472,7 +472,7 @@ hipError_t rp16_causal_dispatch(const void* Q, const void* K, const void* V, voi
 hipError_t rp16_causal_dispatch_1w(const void* Q, const void* K, const void* V, void* O,
                                 int BH, int N, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 hipError_t rp16_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, int fold,
+                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, bool fold, Rp16Family family,
                          hipStream_t stream);
 hipError_t rp_dispatch(const void* Q, const void* K, const void* V, void* O,
                        int BH, int N, int D, float scale, int in_dtype, int out_dtype, int fold,
@@ -545,8 +545,9 @@ const char* algo_kernel_name(int algo, int D)
     }
 }
 
-// algo: 0 auto, 1 generic single-fragment kernel, 2 tiled kernel (D in {64,128} only),
-//       3 software-pipelined tiled kernel (D = 64 only), 4 ping-pong tiled kernel (D in {64,128})
+// algo: 0 auto, 1 generic single-fragment kernel, 2 tiled kernel (D in {64,128} only), 5 / 6 the interleaved kernel
+//       (fa_fwd_il.hip, D = 64), 23-29 the rolling pipeline (fa_fwd_rp16.hip); the other ids are A/B kernels of the
+//       experimental build or removed (include/fa_mi355.h has the list)
 hipError_t forward_dispatch(const void* Q, const void* K, const void* V, void* O,
                             int BH, int N, int D, float scale, int in_dtype, int out_dtype,
                             int algo, hipStream_t stream)
@@ -559,27 +560,26 @@ hipError_t forward_dispatch(const void* Q, const void* K, const void* V, void* O
     if (algo == 0) algo = auto_algo(BH, N, D, in_dtype);
     if (algo == 5) return il_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 8, stream);
     if (algo == 6) return il_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 4, stream);
-    if (algo == 23) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 0, stream);
-    if (algo == 24) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1, stream);
+    if (algo == 23) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, false, Rp16Family::kFull, stream);
+    if (algo == 24) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kFull, stream);
     if (algo == 29) {   // 32-row waves, keys split over two groups of four waves per 128-row workgroup (d = 64); the split needs
         if (D != 64) return hipErrorInvalidValue;   // whole tiles per group: other N run the 16-row waves (same workgroup size)
-        if (N % 128 != 0) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1 | 8, stream);
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1 | 4 | 16, stream);
+        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, N % 128 != 0 ? Rp16Family::kQuarter : Rp16Family::kKeySplit, stream);
     }
     if (algo == 28) {   // d = 128 with one wave per SIMD (four 64-row waves, the whole register file each)
         if (D != 128) return hipErrorInvalidValue;
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1 | 12, stream);
+        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kOneWave, stream);
     }
     if (algo == 26 || algo == 27) {   // the pipeline on half-width / quarter-width waves (32 / 16 rows at D = 64, 16 at D = 128)
         if (D != 64 && !(D == 128 && algo == 26)) return hipErrorInvalidValue;
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1 | (algo == 26 ? 4 : 8), stream);
+        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, algo == 26 ? Rp16Family::kHalf : Rp16Family::kQuarter, stream);
     }
 #ifdef FA_EXPERIMENTS
     if (algo == 13) return w64_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);    // round 1's defaults and the
     if (algo == 16) return w64x_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);   // 32x32x16 pipeline: A/B baselines
     if (algo == 21) return rp_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 0, stream);
     if (algo == 22) return rp_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1, stream);
-    if (algo == 25) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 3, stream);   // 24 with LDS-DMA staging
+    if (algo == 25) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kDma, stream);   // 24 with LDS-DMA staging
     if (algo >= 17 && algo <= 20) return sk_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, algo - 17, stream);   // A/B kernels AUTO never selects: only in libfa_mi355_exp.so (make experimental)
     if (algo == 7 || algo == 8) {   // occupancy variants of the plain tiled kernel, fp16 d=64 fp32-out
         if (D != 64 || in_dtype != 0 || out_dtype != 0) return hipErrorInvalidValue;

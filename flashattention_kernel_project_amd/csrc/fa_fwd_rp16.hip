@@ -1,5 +1,5 @@
 // fa_fwd_rp16.hip -- entry points of the rolling half-tile pipeline (fa_fwd_rp16_kernel.hpp); the kernel families are
-// instantiated in fa_fwd_rp16_{d64,d64n,d128,c}.hip.
+// instantiated in fa_fwd_rp16_{d64,d64n,d64ks,d128,d128w,c,cw}.hip.
 #include "fa_tile.hpp"
 
 namespace fa {
@@ -46,37 +46,31 @@ static bool rp16_shape_ok(int N, int D)
     return (unsigned long long)(N + 64 * 8 + 3 * kBlockN) * (unsigned)D * 4ull < (1ull << 32);   // per-head byte offsets are 32 bit
 }
 
-// fold: 1 = folded fast pass first, 0 = exact passes only; +2 = K/V staging by LDS-DMA (experimental build); bits 2-3: 1 = half-width
-// waves (32 rows at D = 64, 16 at D = 128), 2 = quarter-width (16 rows, D = 64), 3 = one wave per SIMD (64-row waves, D = 128); +16 with 1: keys split over two groups of four 32-row waves (N % 128 == 0)
+// fold: the folded fast pass first (else the exact passes only).  A family that does not exist at this D is an error.
 hipError_t rp16_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, int fold,
+                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, bool fold, Rp16Family family,
                          hipStream_t stream)
 {
     if (!rp16_shape_ok(N, D)) return hipErrorInvalidValue;
-    const bool dma = (fold & 2) != 0;
-    const int narrow = (fold >> 2) & 3;
-    bool f = (fold & 1) != 0;
-    if (!(scale == scale) || scale * kLog2e == 0.0f) f = false;   // NaN / zero scale: the exact passes define the result
+    const bool f = fold && (scale == scale) && scale * kLog2e != 0.0f;   // NaN / zero scale: the exact passes define the result
     if (D == 128) {
-        if (narrow == 3 && !dma) return rp16_d128x4w4(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
-        if (dma || narrow > 1) return hipErrorInvalidValue;
-        return narrow ? rp16_d128x1(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream)
-                      : rp16_d128x2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
+        switch (family) {
+            case Rp16Family::kFull: return rp16_d128x2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
+            case Rp16Family::kHalf: return rp16_d128x1(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
+            case Rp16Family::kOneWave: return rp16_d128x4w4(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
+            default: return hipErrorInvalidValue;
+        }
     }
-    if (narrow == 1 && (fold & 16) && !dma) return rp16_d64x2ks2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
-    if (narrow) {   // small grids: the same pipeline on narrower waves
-        if (dma || narrow > 2) return hipErrorInvalidValue;
-        return narrow == 1 ? rp16_d64x2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream)
-                           : rp16_d64x1(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
-    }
-    if (dma) {
+    switch (family) {
+        case Rp16Family::kFull: return rp16_d64x4(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
+        case Rp16Family::kHalf: return rp16_d64x2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);   // small grids: the same
+        case Rp16Family::kQuarter: return rp16_d64x1(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);   // pipeline on narrower waves
+        case Rp16Family::kKeySplit: return rp16_d64x2ks2(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
 #ifdef FA_EXPERIMENTS
-        return rp16_d64x4_dma(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
-#else
-        return hipErrorInvalidValue;   // the LDS-DMA variant lost the A/B (0.552 vs 0.508 ms): experimental build only
+        case Rp16Family::kDma: return rp16_d64x4_dma(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
 #endif
+        default: return hipErrorInvalidValue;   // (the LDS-DMA variant lost the A/B, 0.552 vs 0.508 ms: experimental build only)
     }
-    return rp16_d64x4(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, f, stream);
 }
 
 // Causal forward on the pipeline (folded fast pass first for both input types), D in {64, 128}.

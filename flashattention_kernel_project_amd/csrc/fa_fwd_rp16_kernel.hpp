@@ -22,6 +22,23 @@
 #include <type_traits>
 #include <utility>
 
+// The measuring instruments of this kernel: the only preprocessor switches it has.  None selects between product code paths;
+// all are set per build through tools/build_variant.sh and default to the product.
+//   FA_RP16_ABL     tools/ablate_rp16.sh, tools/sustain_libs.py, tools/ab_libs.py: timing ablations, results are garbage.
+//                   1 no LDS fragment reads, 2 no softmax vector work, 4 no matrix instructions, 8 no K/V staging, 16 no tile
+//                   barrier, 32 no O stores, 64 no Q loads, 128 no loads of an item's first two K/V tiles, 256 every fragment
+//                   read issued twice
+//   FA_RP16_GATES   built together with FA_RP16_ABL (=0: an ablated build must not refuse its garbage): which refusal gates of
+//                   the folded pass are armed (1 sum overflow, 2 sum too small, 4 reference, 8 Q range)
+//   FA_RP16_STAMPS  tools/item_phases.py: 100 MHz timestamps of an item's phases, written over O[first row of the item][0..7]
+//                   (fp32 out only)
+#ifndef FA_RP16_ABL
+#define FA_RP16_ABL 0
+#endif
+#ifndef FA_RP16_GATES
+#define FA_RP16_GATES 15
+#endif
+
 namespace fa {
 
 namespace rp16 {
@@ -67,71 +84,18 @@ template <> struct Mx<BF16> {
 };
 #undef FA_MFMA_V
 constexpr int kW = 8;
-#ifndef FA_RP16_AHEAD
-#define FA_RP16_AHEAD 2
-#endif
-constexpr int kAheadWide = FA_RP16_AHEAD;   // 64-row waves: fragments read ahead of their MFMAs (at most ring - 1), ring of 4 registers
+constexpr int kAheadWide = 2;          // 64-row waves: fragments read ahead of their MFMAs (at most ring - 1), ring of 4 registers
 constexpr float kHeadroom = 4.0f;      // exact optimistic pass: reference = the row's max over its first 32 keys + this
 constexpr float kHeadroomFold = 1.0f;  // folded pass: the reference already is the maximum over the wave's 64 rows
 constexpr float kFoldMax = 16.0f;  // folded pass: largest |reference| (log2 units) it accepts -- Q's fp16 rounding moves a logit by <= |logit| * 2^-11
 constexpr float kFoldAim = 6.0f;       // folded pass: log2 of the row sum the reference is placed for
 constexpr float kFoldShiftMin = 6.0f;  // ... and how far below the first scores' maximum it may go (weights stay below 2^16)
-#ifndef FA_RP16_ABL
-#define FA_RP16_ABL 0              // lab only (timing ablations, results are garbage): 1 no LDS fragment reads, 2 no softmax vector
-#endif                             // work, 4 no matrix instructions, 8 no K/V staging, 16 no tile barrier, 32 no O stores, 64 no Q loads,
-                                   // 128 no loads of an item's first two K/V tiles
-#ifndef FA_RP16_GATES
-#define FA_RP16_GATES 15           // lab only: which refusal gates of the folded pass are armed (1 sum overflow, 2 sum too small, 4 reference, 8 Q range)
-#endif
-#ifndef FA_RP16_SUMMFMA
-#define FA_RP16_SUMMFMA 1          // 1: the optimistic passes take the row sums from the matrix pipe (one more PV block against a
-#endif                             // fragment of ones: X matrix instructions per step instead of 32 v_add_f32 per lane)
-#ifndef FA_RP16_PREFETCH
-#define FA_RP16_PREFETCH 1         // 1: the next item's Q rows are requested under this item's epilogue, ahead of its stores
-#endif
-#ifndef FA_RP16_VALU_AT
-#define FA_RP16_VALU_AT 0          // lab: a vector pair-step goes behind the last (0) or the first (1) matrix instruction of its group
-#endif
-#ifndef FA_RP16_ONES_POS
-#define FA_RP16_ONES_POS 0         // lab: where in a step the X row-sum matrix instructions go: 0 one per kNF slots, 1 behind the first X
-#endif                             // slots, 2 behind the last X
-#ifndef FA_RP16_TOP_BARRIER
-#define FA_RP16_TOP_BARRIER 0      // lab: 1 = a barrier at the top of every item but the first (what the votes make redundant)
-#endif
-#ifndef FA_RP16_STAGGER
-#define FA_RP16_STAGGER 0          // lab: workgroups start in 8 phases, this many s_sleep units (~64 clocks each) apart, so that the
-#endif                             // item boundaries (stores, next Q) of the CUs do not all hit the memory system together
-#ifndef FA_RP16_PRIO
-#define FA_RP16_PRIO 0             // lab only: 1 = waves 0-3 (one of the two on each SIMD) run at raised priority
-#endif
-#ifndef FA_RP16_RUNSUM
-#define FA_RP16_RUNSUM 1           // 1: the optimistic passes keep their row-sum chains across steps (16 fewer v_add_f32 per tile)
-#endif
-#ifndef FA_RP16_VFIX
-#define FA_RP16_VFIX 2             // 1: the V image's 32-B key rows are XORed with the head-dim block (db & 3) inside their 256-B block, so that the
-#endif                             // eight lanes of a ds_write_b128 group (one key row, chunks 0..7) hit eight 16-B slots of the 128-B bank row
-#ifndef FA_RP16_VSPLIT
-#define FA_RP16_VSPLIT 1           // 1: a vector pair-step is spread over its matrix slots (one v_exp behind each of the first two, the v_cvt_pk
-#endif                             // behind the second / third) instead of all behind the last
-#ifndef FA_RP16_RAWBAR
-#define FA_RP16_RAWBAR 1           // 1: the tile barrier waits for this wave's staging writes only (counted lgkmcnt), not for the fragment reads behind them
-#endif
-#ifndef FA_RP16_PAIR
-#define FA_RP16_PAIR 1             // 1: narrow waves (X <= 2 at D = 64) run TWO tiles per barrier out of a ring of eight slots; 2: every D = 64 width (lab)
-#endif
-#ifndef FA_RP16_ASMQK
-#define FA_RP16_ASMQK 1
-#endif
-#ifndef FA_RP16_OLDS
-#define FA_RP16_OLDS 0             // lab: fp32 outputs at D = 64 go through a wave-private LDS region and leave as whole 256-B rows (four rows per
-#endif                             // store instruction) instead of sixteen 64-B pieces of sixteen rows
-#ifndef FA_RP16_STAGE_SLOT
-#define FA_RP16_STAGE_SLOT 8       // matrix slot (of 32; scaled for narrower steps) of the second step in front of which tile j+2 is written to LDS
-#endif
+constexpr int kStageSlot = 8;          // matrix slot (of 32; scaled for narrower steps) of the second step in front of which tile j+2 is written to LDS
 // Two tiles per loop iteration and barrier (ring of eight [K tile][V tile] slots, tiles landed three ahead instead of two): for
 // the narrow waves a tile is a few hundred issue cycles per wave, and the barrier of eight waves plus the landing of the next
 // tile cost as much again (stamps at B4 H8 N1024: 16 tiles took 13.8 us = 2000 cycles each).  D = 64 only (128 KB of LDS).
-constexpr bool pair_tiles(int D, int X, bool dma) { return FA_RP16_PAIR != 0 && D == 64 && !dma && (X <= 2 || FA_RP16_PAIR == 2); }
+// (At full width the same form lost: DESIGN.md 3.6 (8).)
+constexpr bool pair_tiles(int D, int X, bool dma) { return D == 64 && !dma && X <= 2; }
 }  // namespace rp16
 
 #ifdef FA_EXPERIMENTS
@@ -200,18 +164,18 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // full-width waves (64 rows at D = 64, 32 at D = 128): the running-max pass lives in the redo kernel (see kScan)
     constexpr bool kSplitTrack = !kScan && !kDma && 16 * X * (D / 64) >= 64;
     constexpr unsigned kMarker = 0x7FA5C0DEu;
-    constexpr bool kVSplit = FA_RP16_VSPLIT != 0 && (!kCausal || (kWv == 4 && kKeySplit == 1));   // (under the mask the pins cost the two-wave full-width kernels spills)
+    // a vector pair-step is spread over its matrix slots (one v_exp behind each of the first two, the v_cvt_pk behind the second /
+    // third) instead of all behind the last; under the mask the pins cost the two-wave full-width kernels spills
+    constexpr bool kVSplit = !kCausal || (kWv == 4 && kKeySplit == 1);
     static_assert(!(kCvtK && kDma), "the DMA path cannot convert K on the way");
     static_assert(!kDma || D == 64, "the DMA piece maps are written for 128-byte rows");
     constexpr int kRows = 16 * X * kW;
     constexpr int kKS = D / 32, kDB = D / 16;   // k-steps of QK^T, 16-row blocks of O^T
     constexpr int kNF = 2 * kKS + kDB;          // fragments per step (K and V^T alternate: 2 kKS == kDB)
     // fragment registers and read-ahead: a fragment feeds X matrix instructions, so the narrow waves (X < 4 at D = 64: small
-    // grids) need more of them in flight to cover the LDS latency
-#ifndef FA_RP16_D128_DEEP
-#define FA_RP16_D128_DEEP 0        // lab: 32-row waves at D = 128 with the narrow waves' ring of eight fragment registers, read four ahead
-#endif                             // (a fragment there feeds two matrix instructions only: 2 ahead = 64 cycles of cover)
-    constexpr bool kWide = 16 * X * (D / 64) >= 64 && !(FA_RP16_D128_DEEP && D == 128);
+    // grids) need more of them in flight to cover the LDS latency.  (32-row waves at D = 128 count as wide although a fragment
+    // there feeds two matrix instructions only: the ring of eight, read four ahead, measured -0.5 %, inside that A/B's noise -- DESIGN.md 3.6 (7)(a))
+    constexpr bool kWide = 16 * X * (D / 64) >= 64;
     constexpr int kRing = kWide ? 4 : 8;
     constexpr int kAhead = kWide ? kAheadWide : (X == 2 ? 4 : 6);
     constexpr int kSlots = kNF * X;             // matrix instructions per step (32 for the 64-row waves: X = 4 at D = 64, 2 at D = 128)
@@ -219,14 +183,12 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     constexpr int kLoads = (kBlockN * G::kChunks) / (64 * kW);   // 16-B chunks of K (and of V) per thread and tile
     // LDS instructions a wave issues in the second step behind the landing of tile j+2 (fragment reads: one ds_read_b128 per K
     // fragment, two ds_read_b64_tr_b16 per V^T fragment)
-    constexpr int kLandSlot = FA_RP16_STAGE_SLOT * kSlots / 32;
+    constexpr int kLandSlot = kStageSlot * kSlots / 32;
     // one wave per SIMD: no second wave issues while this one works through a bunch of loads or LDS writes, so tile j+2 is
     // requested one chunk per matrix slot (first step) and landed one chunk per slot (second step, from kLandSlot on)
-#ifndef FA_RP16_SPREAD
-#define FA_RP16_SPREAD 1
-#endif
+    // ("issue slots")
     constexpr bool kOneWave = kWv == 4 && kKeySplit == 1;   // one wave per SIMD
-    constexpr bool kSpread = FA_RP16_SPREAD != 0 && kOneWave && !kDma;
+    constexpr bool kSpread = kOneWave && !kDma;
     constexpr int kLandLast = kSpread ? kLandSlot + 2 * kLoads - 1 : kLandSlot;   // the slot of the last landing write
     // ... and the tile barrier is replaced by one flag word per wave behind the ring: a wave publishes "tile j+2 landed" (its
     // iteration count) right behind its last landing write and looks at all four flags only in front of its first read of that
@@ -234,12 +196,9 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // follow the look.  A lone wave per SIMD that waits at s_barrier for the slowest of four idles its matrix pipe; here the
     // waves may drift by most of a step.  (Ring reuse: a wave lands tile j+3 over tile j-1 only behind its look of iteration
     // j+1, i.e. when every wave has landed tile j+2 -- 16 slots into the second step of iteration j, past its last read of
-    // tile j-1 in the first.)
-#ifndef FA_RP16_FLAGBAR
-#define FA_RP16_FLAGBAR 1
-#endif
-    constexpr bool kFlagBar = (FA_RP16_FLAGBAR == 2 ? (!kDma && !pair_tiles(D, X, kDma) && kKeySplit == 1 && !kScan && FA_RP16_OLDS == 0) : (kSpread && FA_RP16_FLAGBAR != 0)) &&
-                              (FA_RP16_ABL & 24) == 0;
+    // tile j-1 in the first.)  The two-wave kernels keep s_barrier: it holds the two waves of a SIMD in the phase the slot
+    // placement assumes, and flags lost there ("No s_barrier").
+    constexpr bool kFlagBar = kSpread && (FA_RP16_ABL & 24) == 0;
     constexpr int kFlagCheck = (kNF - kAhead) * X + X - 2, kFlagRead = kFlagCheck >= 8 ? kFlagCheck - 8 : 0;   // the slot in front of the first read-ahead into the next step
     static_assert(!kFlagBar || (kFlagRead >= 0 && kFlagRead < kFlagCheck && kLandLast + 1 < kSlots), "flag slots");
     static_assert(kLandLast < kSlots && 2 * kLoads <= kSlots, "the landing fits the step");
@@ -256,7 +215,8 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // one wave per SIMD: QK^T spelled out with the scores in architectural registers (Mx::mfma_v*).  Every vector read of a score
     // lies at least X P.V matrix instructions behind the instruction that wrote it (the units alternate QK^T and P.V fragments and a
     // step ends with a P.V fragment); the prologue, whose reference maximum reads unit 0 at once, waits explicitly (settle).
-    constexpr bool kAsmQK = FA_RP16_ASMQK != 0 && kWv == 4 && kKeySplit == 1;   // (the key-split kernel has four waves per GROUP: two per SIMD, builtins)
+    // (With the builtin the scores land in the accumulator half and cost a v_accvgpr_read each: 5 % slower)
+    constexpr bool kAsmQK = kOneWave;   // (the key-split kernel has four waves per GROUP: two per SIMD, builtins)
     constexpr unsigned kRingSlots = kPair ? 8u : 4u, kRingMask = kRingSlots - 1u;
     constexpr int kLook = kPair ? 3 : 2;            // a tile is landed this many tiles ahead of the iteration that starts with it
     extern __shared__ __attribute__((aligned(16))) char smem_all[];   // one ring of slots per key-split group
@@ -278,25 +238,22 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
 #pragma unroll
     for (int p = 0; p < kLoads; ++p) {
         const unsigned idx = tid + p * 64u * kW;
-        unsigned srow = idx / G::kChunks, sch = idx % G::kChunks;
+        const unsigned srow = idx / G::kChunks, sch = idx % G::kChunks;
         st_goff[p] = srow * kRowB + sch * 16u;
         k_lds[p] = G::k_off(srow, sch);
-        if constexpr (FA_RP16_VFIX == 2) {
-            // V: the eight lanes of a ds_write_b128 group take 4 keys x 2 chunks of one head-dim block (128 contiguous bytes of
-            // the image) instead of one key's 8 chunks (8 slots 256 B apart: 4-way on the 128-B bank row of a write)
-            constexpr unsigned ndb = G::kChunks / 2, rpw = 64u / G::kChunks;   // head-dim blocks; key rows per wave-instruction
-            const unsigned w = idx >> 6, l = idx & 63u, t = l >> 3;
-            srow = w * rpw + 4u * (t / ndb) + ((l >> 1) & 3u);
-            sch = 2u * (t % ndb) + (l & 1u);
-        }
-        sv_goff[p] = srow * kRowB + sch * 16u;
-        v_lds[p] = kTile + ((srow >> 3) * (unsigned)kDB + (sch >> 1)) * 256u + (((srow & 7u) ^ (FA_RP16_VFIX == 1 ? ((sch >> 1) & 3u) : 0u)) << 5) + ((sch & 1u) << 4);
+        // V: the eight lanes of a ds_write_b128 group take 4 keys x 2 chunks of one head-dim block (128 contiguous bytes of the
+        // image) instead of one key's 8 chunks (8 slots 256 B apart: 4-way on the 128-B bank row of a write)
+        constexpr unsigned ndb = G::kChunks / 2, rpw = 64u / G::kChunks;   // head-dim blocks; key rows per wave-instruction
+        const unsigned w = idx >> 6, l = idx & 63u, t = l >> 3;
+        const unsigned vrow = w * rpw + 4u * (t / ndb) + ((l >> 1) & 3u), vch = 2u * (t % ndb) + (l & 1u);
+        sv_goff[p] = vrow * kRowB + vch * 16u;
+        v_lds[p] = kTile + ((vrow >> 3) * (unsigned)kDB + (vch >> 1)) * 256u + ((vrow & 7u) << 5) + ((vch & 1u) << 4);
     }
     // LDS-DMA: this wave's 1-KB piece of an image is bytes [1024 wave, +1024), lane l lands at +16 l; where that comes from
     const unsigned dk_row = 8u * wave + (lane >> 3), dk_slot = lane & 7u;
     const unsigned k_src = dk_row * kRowB + ((dk_slot ^ G::k_swz(dk_row)) << 4);
     const unsigned dv_l = 1024u * wave + 16u * lane, dv_blk = dv_l >> 8;
-    const unsigned dv_row = (dv_blk / (unsigned)kDB) * 8u + (((dv_l & 255u) >> 5) ^ (FA_RP16_VFIX == 1 ? ((dv_blk % (unsigned)kDB) & 3u) : 0u)), dv_ch = (dv_blk % (unsigned)kDB) * 2u + ((dv_l >> 4) & 1u);
+    const unsigned dv_row = (dv_blk / (unsigned)kDB) * 8u + ((dv_l & 255u) >> 5), dv_ch = (dv_blk % (unsigned)kDB) * 2u + ((dv_l >> 4) & 1u);
     const unsigned v_src = dv_row * kRowB + dv_ch * 16u;
     typedef __attribute__((address_space(3))) void lds_void;
     auto dma_tile = [&](__amdgpu_buffer_rsrc_t rks, __amdgpu_buffer_rsrc_t rvs, unsigned tile_off, unsigned slot_off) __attribute__((always_inline)) {
@@ -306,11 +263,12 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     unsigned k_rd[kKS];
 #pragma unroll
     for (int ks = 0; ks < kKS; ++ks) k_rd[ks] = c16 * kRowB + (((4u * ks + g) ^ G::k_swz(c16)) << 4);
-    // (FA_RP16_VFIX: one base per db & 3 -- the key row inside the 256-B block is XORed with it)
+    // (four equal elements, of which [0] is read.  As a scalar or a one-element array the same matrix instructions get another
+    // register allocation, i.e. a kernel nobody has timed: the array stays until somebody does)
     unsigned v_rd4[4];
 #pragma unroll
     for (unsigned dq = 0; dq < 4u; ++dq)
-        v_rd4[dq] = kTile + (g >> 1) * (unsigned)kDB * 256u + ((4u * (g & 1u) + ((c16 >> 2) ^ (FA_RP16_VFIX == 1 ? dq : 0u))) << 5) + (c16 & 3u) * 8u;
+        v_rd4[dq] = kTile + (g >> 1) * (unsigned)kDB * 256u + ((4u * (g & 1u) + (c16 >> 2)) << 5) + (c16 & 3u) * 8u;
 
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const u32x4 zero4u = {0u, 0u, 0u, 0u};
@@ -340,11 +298,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         return v + __shfl_xor(v, 32, 64);
     };
 
-    if constexpr (FA_RP16_STAGGER > 0) {
-        const unsigned phase = (blockIdx.x >> 3) & 7u;
-        for (unsigned i = 0; i < phase; ++i) __builtin_amdgcn_s_sleep(FA_RP16_STAGGER);
-    }
-    if constexpr (FA_RP16_PRIO == 1) { if (wave < 4u) __builtin_amdgcn_s_setprio(2); }   // lab: one wave of each SIMD's pair ahead
     const unsigned nwg = total_wg;
     // work item -> (head, query block): XCD-aware remap of the persistent grid's item index
     auto locate = [&](unsigned bid_, unsigned& bh_, unsigned& qb_) __attribute__((always_inline)) {
@@ -370,9 +323,9 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // Between two items of the persistent loop everything is a latency chain (stamps: Q 2.8-4.4 us, then K/V 2.2, reference
     // 2.2, gates 1.8, stores 1.6 of ~116 us per item at B8 H16 N4096).  kPrefetch: the NEXT item's Q rows are requested
     // (raw, into qf -- dead by then) as soon as the first pass' tile loop is over, i.e. ahead of this item's stores in the
-    // in-order vector memory queue, and every item requests its first three K/V tiles before it waits for its Q.
-    constexpr bool kPrefetch = FA_RP16_PREFETCH != 0 && !kDma;
-    constexpr bool kCarryKV = FA_RP16_PREFETCH == 2;   // lab: the K/V tiles 0..2 carried in registers as well (the allocator spills them)
+    // in-order vector memory queue, and every item requests its first three K/V tiles before it waits for its Q.  (The K/V
+    // tiles are not carried across the boundary as well: the allocator spills them)
+    constexpr bool kPrefetch = !kDma;
     u32x4 qf[X][kKS];   // B operand of QK^T: Q[row of block x][32 ks + 8 g .. +7]
     u32x4 kst[kLoads], vst[kLoads];
     u32x4 kst2[kLoads], vst2[kLoads];   // kPair: the second tile of an iteration
@@ -470,7 +423,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
             qb0 = __builtin_amdgcn_readfirstlane(qb0);
             const unsigned rb0 = qb0 * kRows + wave * (16u * X);
             q_issue(Qg + bh0 * head_elems, rb0);
-            if constexpr (kCarryKV) kv_issue(make_rsrc(Kg + bh0 * head_elems, head_bytes), make_rsrc(Vg + bh0 * head_elems, head_bytes));
             constexpr unsigned es0 = kOutF32 ? 4u : 2u;
             const __amdgpu_buffer_rsrc_t ro0 =
                 make_rsrc(reinterpret_cast<char*>(Og) + (size_t)bh0 * head_elems * es0, (unsigned)(head_elems * es0));
@@ -490,7 +442,7 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         __syncthreads();
     }
     for (unsigned bid = first_bid; bid < nwg; bid = kScan ? scan_next() : bid + gridDim.x) {
-#ifdef FA_RP16_STAMPS   // lab: 100 MHz timestamps of the item's phases, written over O[first row of the item][0..7] (fp32 out only)
+#ifdef FA_RP16_STAMPS   // (see the top of the file)
     unsigned long long ts[8] = {};
 #define FA_STAMP(i) ts[i] = wall_clock64()
 #else
@@ -501,7 +453,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // LDS read of the previous item (the epilogue's V fragments) lies before that item's vote (__syncthreads_or) -- or the
     // barrier behind the tracked pass, which has no vote after it.  A wave therefore requests its K/V tiles as soon as its
     // own stores are issued, not when the slowest wave's are.
-    if constexpr (FA_RP16_TOP_BARRIER) { if (bid != blockIdx.x) __syncthreads(); }
     unsigned bh, qb;
     locate(bid, bh, qb);
     const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kg + bh * head_elems + kv_first, kv_bytes);
@@ -559,12 +510,12 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     };
 
     f32x4 o[X][kDB];
-    float m_ref[X] = {}, l_part[X] = {};
-    float ls[X][2];   // optimistic passes: two running row-sum chains per block, folded into l_part once per item
+    float m_ref[X] = {};
     u32x4 frag[kRing];
     f32x4 minit;   // folded pass: every score chain starts at -(wave reference maximum)
     // row sums on the matrix pipe: lacc[x][i] = sum over keys of the ROUNDED weights of row (lane & 15) of block x, the
-    // same in every register and every lane group (all 16 "head-dim rows" of the ones fragment are equal)
+    // same in every register and every lane group (all 16 "head-dim rows" of the ones fragment are equal): one more PV block
+    // against a fragment of ones, X matrix instructions per step instead of 32 v_add_f32 per lane
     f32x4 lacc[X];
     u32x4 ones;   // written by an instruction the optimiser cannot hoist out of the item loop (and spill around the tile loop)
 #pragma unroll
@@ -578,7 +529,7 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         u32x4 vf;
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
-            const u32x2 half = lds_read_tr8(smem, so + v_rd4[FA_RP16_VFIX == 1 ? (db & 3) : 0] + (4u * h + 2u * jj) * (unsigned)kDB * 256u + db * 256u);
+            const u32x2 half = lds_read_tr8(smem, so + v_rd4[0] + (4u * h + 2u * jj) * (unsigned)kDB * 256u + db * 256u);
             vf[2 * jj] = half[0];
             vf[2 * jj + 1] = half[1];
         }
@@ -587,7 +538,7 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     // kBases (one wave per SIMD): a step's fragment addresses from per-step lane bases (ring slot + lane offset, one v_add
     // each at the top of the step) plus immediates, instead of one s_add + v_add in front of every fragment read -- with a
     // lone wave per SIMD every such instruction is a cycle the matrix pipe waits for
-    constexpr bool kBases = kSpread && FA_RP16_VFIX == 2 && (FA_RP16_ABL & 257) == 0;
+    constexpr bool kBases = kSpread && (FA_RP16_ABL & 257) == 0;
     auto read_frag_b = [&](auto fc, const unsigned (&kb)[kKS], unsigned vb, int h_q, int h_v) {
         constexpr int f = decltype(fc)::value;
         if constexpr ((f & 1) == 0) {
@@ -679,9 +630,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
                         for (int i = 0; i < 4; ++i) o[x][db][i] *= alpha;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) lacc[x][i] *= alpha;
-                    ls[x][0] *= alpha;
-                    ls[x][1] *= alpha;
-                    l_part[x] *= alpha;
 #pragma unroll
                     for (int w = 0; w < 4; ++w) pk_prev[x][w] = T::pack2(T::lo(pk_prev[x][w]) * alpha, T::hi(pk_prev[x][w]) * alpha);
                 }
@@ -689,10 +637,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         }
 
         constexpr int kPairs = 4 * X;   // vector pair-steps: pair j = (block j/4, key block (j/2)&1, registers 2(j&1), 2(j&1)+1)
-        if constexpr (!FA_RP16_RUNSUM) {
-#pragma unroll
-            for (int x = 0; x < X; ++x) ls[x][0] = ls[x][1] = 0.0f;
-        }
         auto fma_pair = [&](auto jc) {
             constexpr int j = decltype(jc)::value, x = j >> 2, kbl = (j >> 1) & 1, e = 2 * (j & 1);
             s_cur[x][kbl][e] = __builtin_fmaf(s_cur[x][kbl][e], c, -m_ref[x]);
@@ -718,13 +662,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
             unsigned w = T::pack2(s_cur[x][kbl][e], s_cur[x][kbl][e + 1]);
             if constexpr (kVSplit) asm volatile("" : "+v"(w));
             pk_cur[x][2 * kbl + (j & 1)] = w;
-            if constexpr (FA_RP16_SUMMFMA) {
-            } else if constexpr (T::kSumRounded) {
-                ls[x][j & 1] = T::sum2(w, ls[x][j & 1]);
-            } else {
-                ls[x][0] += s_cur[x][kbl][e];
-                ls[x][1] += s_cur[x][kbl][e + 1];
-            }
         };
         auto valu_step = [&](auto jc) {   // skewed: nothing waits on the instruction before it
             constexpr int j = decltype(jc)::value;
@@ -857,11 +794,8 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
                 }
             }
             issue_mfma(ic);
-            if constexpr (FA_RP16_SUMMFMA && (FA_RP16_ABL & 4) == 0) {   // the X row-sum instructions of the step
-                if constexpr (FA_RP16_ONES_POS == 0 && i % kNF == kNF - 1) lacc[i / kNF] = M::mfma(ones, pk_prev[i / kNF], lacc[i / kNF]);
-                if constexpr (FA_RP16_ONES_POS == 1 && i < X) lacc[i] = M::mfma(ones, pk_prev[i], lacc[i]);
-                if constexpr (FA_RP16_ONES_POS == 2 && i >= kSlots - X) lacc[i - (kSlots - X)] = M::mfma(ones, pk_prev[i - (kSlots - X)], lacc[i - (kSlots - X)]);
-            }
+            if constexpr ((FA_RP16_ABL & 4) == 0 && i % kNF == kNF - 1)   // the X row-sum instructions of the step, one per kNF slots
+                lacc[i / kNF] = M::mfma(ones, pk_prev[i / kNF], lacc[i / kNF]);
             if constexpr (i % X == X - 1) {   // the fragment just consumed X times is free: read kAhead ahead
                 constexpr int f = i / X + kAhead;
                 if constexpr (kBases) {
@@ -883,15 +817,11 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
                     if constexpr (j + 1 < kPairs) exp_one(std::integral_constant<int, j + 1>{}, std::integral_constant<int, sub>{});
                 }
                 if constexpr (sub == (kPer == 2 ? 1 : 2)) fin_pair(std::integral_constant<int, j>{});
-            } else {
-                if constexpr (i % kPer == (FA_RP16_VALU_AT ? 0 : kPer - 1)) valu_step(std::integral_constant<int, i / kPer>{});
+            } else if constexpr (i % kPer == kPer - 1) {   // the whole pair-step behind the last matrix instruction of its group
+                valu_step(std::integral_constant<int, i / kPer>{});
             }
         });
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!FA_RP16_RUNSUM) {
-#pragma unroll
-            for (int x = 0; x < X; ++x) l_part[x] += ls[x][0] + ls[x][1];
-        }
     };
 
     // a packed weight can only have overflowed if the fp32 row sum reached the 16-bit format's range; bf16 keeps a finite bound with
@@ -913,8 +843,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         for (int x = 0; x < X; ++x) {
 #pragma unroll
             for (int db = 0; db < kDB; ++db) o[x][db] = zero4;
-            l_part[x] = 0.0f;
-            ls[x][0] = ls[x][1] = 0.0f;
             lacc[x] = zero4;
             pkB[x] = zero4u;   // "P(-1)" = 0 against the zeroed V of the ring's last slot
         }
@@ -1026,16 +954,16 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         // req_c: request tile j+2 at the top (not in iteration 0 of the non-DMA path: the prologue already has it in flight)
         auto tile_barrier = [&]() __attribute__((always_inline)) {
             if constexpr ((FA_RP16_ABL & 16) != 0 || kFlagBar) {
-            } else if constexpr (FA_RP16_RAWBAR != 0 && !kDma && kLdsAfterLand <= 15) {
+            } else if constexpr (!kDma && kLdsAfterLand <= 15) {
                 // The barrier publishes this wave's ds_writes of the landed tile (first read at least one iteration later) and orders
                 // the ring's reuse; it does not need the fragment reads issued since (LDS operations of a wave complete in order: once
                 // at most kLdsAfterLand are outstanding, the writes are done).  __syncthreads() would wait for all of them
-                // (s_waitcnt lgkmcnt(0)): the latency of the last read, exposed once per tile.
+                // (s_waitcnt lgkmcnt(0)): the latency of the last read, exposed once per tile (DESIGN.md 3.6 (4)).
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(kLdsAfterLand) : "memory");
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
-            } else {
+            } else {   // (LDS-DMA: the barrier also has to wait for the tile's loads, vmcnt; beyond 15 the counter's field ends)
                 __syncthreads();
             }
         };
@@ -1090,7 +1018,7 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         // returns true when the pass was given up on a workgroup vote: fp16 weights of the exact optimistic pass overflowed (the
         // matrix-pipe row sums are complete in every lane, so the look costs a compare per block and a vote every kCheckEvery tiles)
         auto full_tiles = [&](int nfull) __attribute__((always_inline)) -> bool {
-            constexpr bool kLook4Overflow = kMode == 1 && T::id == 0 && FA_RP16_SUMMFMA && FA_RP16_ABL == 0;
+            constexpr bool kLook4Overflow = kMode == 1 && T::id == 0 && FA_RP16_ABL == 0;
             auto overflowed = [&]() -> bool {
                 bool over = false;
 #pragma unroll
@@ -1126,10 +1054,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
             if (full_tiles(partial ? ntiles - 1 : ntiles)) return true;
             if (partial) tile_iter(ntiles - 1, yes, dyn{}, yes);
         }
-        if constexpr (FA_RP16_RUNSUM && !FA_RP16_SUMMFMA) {
-#pragma unroll
-            for (int x = 0; x < X; ++x) l_part[x] = ls[x][0] + ls[x][1];
-        }
         if constexpr (kMode == (kFold ? 0 : 1)) FA_STAMP(4);
         // ---- epilogue: O^T += V(last tile, half 1)^T.P^T ----
         {
@@ -1140,24 +1064,20 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
 #pragma unroll
                 for (int x = 0; x < X; ++x) o[x][db] = M::mfma(vf, pkB[x], o[x][db]);
             }
-            if constexpr (FA_RP16_SUMMFMA) {
 #pragma unroll
-                for (int x = 0; x < X; ++x) {
-                    lacc[x] = M::mfma(ones, pkB[x], lacc[x]);
-                }
-            }
+            for (int x = 0; x < X; ++x) lacc[x] = M::mfma(ones, pkB[x], lacc[x]);
         }
         return false;
     };
 
     float l_row[X];
     bool bad = false, second_vote = false, direct = false;   // (second_vote, direct: workgroup-uniform)
-    // an optimistic pass' row sum: complete in every lane when it came from the matrix pipe
-    auto row_sum = [&](int x) -> float { return FA_RP16_SUMMFMA ? lacc[x][0] : across_sum(l_part[x]); };
+    // a pass' row sum: complete in every lane (it comes from the matrix pipe)
+    auto row_sum = [&](int x) -> float { return lacc[x][0]; };
     if constexpr (!kPrefetch) q_issue(Qg + bh * head_elems, q_row0 - c16);   // else: requested by the item before (next_in)
     else {
         if constexpr (kScan) { if (!q_pending) q_issue(Qg + bh * head_elems, q_row0 - c16); }   // (first block of a later list batch)
-        if constexpr (!kCarryKV) kv_issue(rk, rv);   // tiles 0..2 on their way before Q is waited for
+        kv_issue(rk, rv);   // tiles 0..2 on their way before Q is waited for
     }
     const std::integral_constant<bool, kPrefetch> pre_c{};
     // qf, pfk/pfv, kst/vst <- the next item's raw Q rows and K/V tiles 0..2 (called between the last pass and the stores)
@@ -1171,7 +1091,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
                 bh_n = __builtin_amdgcn_readfirstlane(bh_n);   // (uniform anyway: spares the descriptors a waterfall loop)
                 qb_n = __builtin_amdgcn_readfirstlane(qb_n);
                 q_issue(Qg + bh_n * head_elems, qb_n * kRows + wave * (16u * X));
-                if constexpr (kCarryKV) kv_issue(make_rsrc(Kg + bh_n * head_elems, head_bytes), make_rsrc(Vg + bh_n * head_elems, head_bytes));
             }
         }
     };
@@ -1312,9 +1231,6 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         for (int db = 0; db < kDB; ++db)
 #pragma unroll
             for (int i = 0; i < 4; ++i) o[x][db][i] *= inv;
-#ifdef FA_RP16_DIAG
-        if (g == 0) { o[x][0][0] = l_row[x]; o[x][0][1] = m_ref[x]; }
-#endif
     }
     FA_STAMP(5);
     if constexpr (kPrefetch) {
@@ -1325,26 +1241,10 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
     }
     next_in();
     // o[x][db][i] = O[q_row0 + 16x][16 db + 4 g + i]
-    constexpr bool kOLds = FA_RP16_OLDS != 0 && kOutF32 && D == 64 && !kPair && !kScan && kKeySplit == 1 && (FA_RP16_ABL & 32) == 0;
-    if constexpr (kOLds) {
-        // One 16-row block at a time through this wave's 4 KB of LDS behind the ring: written as the accumulators hold it
-        // (lane = row c16, 16-B chunk 4 db + g, chunk index XORed with row & 7: conflict-free both ways), read back with 16
-        // lanes per 256-B row and stored four whole rows per instruction.
-        char* const stg = smem_all + kRingSlots * kSlotBytes + wave * (16u * 256u);
-        const unsigned wr = c16 * 256u, wx = c16 & 7u;
-#pragma unroll
-        for (int x = 0; x < X; ++x) {
-#pragma unroll
-            for (int db = 0; db < kDB; ++db)
-                lds_write16(stg, wr + (((4u * db + g) ^ wx) << 4), __builtin_bit_cast(u32x4, o[x][db]));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned R = (lane >> 4) + 4u * j, cr = lane & 15u;
-                const u32x4 v = lds_read16(stg, R * 256u + ((cr ^ (R & 7u)) << 4));
-                buf_store16(ro, ((q_row0 - c16 + 16u * x + R) * D + cr * 4u) * 4u, v);
-            }
-        }
-    } else
+    // (sixteen 64-B pieces of sixteen rows per instruction: whole rows through LDS gained nothing)
+    // (A local constant on purpose: with no declaration at this point two independent scalar moves of the FA_EXPERIMENTS build
+    // swap places, and the device code is no longer instruction for instruction the one the records were measured on.)
+    constexpr bool kStoreF32 = (FA_RP16_ABL & 32) == 0;
 #pragma unroll
     for (int x = 0; x < X; ++x) {
         const unsigned row = q_row0 + 16u * x;
@@ -1352,7 +1252,7 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
         for (int db = 0; db < kDB; ++db) {
             const unsigned col = 16u * db + 4u * g;
             if constexpr (kOutF32) {
-                if constexpr ((FA_RP16_ABL & 32) != 0) asm volatile("" :: "v"(o[x][db]));
+                if constexpr (!kStoreF32) asm volatile("" :: "v"(o[x][db]));
                 else buf_store16(ro, (row * D + col) * 4u, __builtin_bit_cast(u32x4, o[x][db]));
             } else {
                 buf_store8(ro, (row * D + col) * 2u, u32x2{T::pack2(o[x][db][0], o[x][db][1]), T::pack2(o[x][db][2], o[x][db][3])});
@@ -1382,8 +1282,7 @@ static hipError_t launch_rp16(const void* Q, const void* K, const void* V, void*
     constexpr int kW = kWv;
     constexpr int lds_bytes = kKeySplit * ((pair_tiles(D, X, kDma) && kKeySplit == 1 && kWv == 8) ? 8 : 4) * 2 * kBlockN * D * 2;   // ring(s) of four (eight) [K tile][V tile] slots
     if (kKeySplit > 1 && N % (kBlockN * kKeySplit) != 0) return hipErrorInvalidValue;
-    constexpr int lds_extra = ((FA_RP16_OLDS != 0 && kOutF32 && D == 64 && !pair_tiles(D, X, kDma) && kKeySplit == 1) ? kWv * 16 * 256 : 0)   // the output staging region
-                              + 64;   // the waves' landing flags (kFlagBar)
+    constexpr int lds_extra = 64;   // the waves' landing flags (kFlagBar)
     constexpr int kRows = 16 * X * kW;
     const int nqb = (N + kRows - 1) / kRows;
     const long long nwg = (long long)BH * nqb;
@@ -1418,7 +1317,7 @@ static hipError_t launch_rp16(const void* Q, const void* K, const void* V, void*
 }
 
 // One (D, X, staging, mask) family of the pipeline: its (input type, output type, folded-first) instantiations.  The families
-// live in translation units of their own (fa_fwd_rp16_{d64,d64n,d128,c}.hip) so that they compile side by side.
+// live in translation units of their own (fa_fwd_rp16_{d64,d64n,d64ks,d128,d128w,c,cw}.hip) so that they compile side by side.
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 static hipError_t rp16_family(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
                               int in_dtype, int out_dtype, bool fold, hipStream_t stream)
