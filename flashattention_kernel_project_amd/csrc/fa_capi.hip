@@ -1,34 +1,7 @@
 // fa_capi.hip -- extern "C" launchers declared in include/fa_mi355.h.
 #include <hip/hip_runtime.h>
 #include "../../include/fa_mi355.h"
-
-namespace fa {
-hipError_t forward_dispatch(const void* Q, const void* K, const void* V, void* O,
-                            int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                            int algo, hipStream_t stream);
-hipError_t forward_causal_dispatch(const void* Q, const void* K, const void* V, void* O,
-                                   int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                                   int algo, hipStream_t stream);
-hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
-                          int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
-size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
-hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
-                                int dtype, hipStream_t stream);
-hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,
-                                int num_batches, int seq_len, float scale, bool k_transposed,
-                                hipStream_t stream);
-int auto_algo(int BH, int N, int D, int in_dtype);
-const char* algo_kernel_name(int algo, int D);
-#ifdef FA_EXPERIMENTS
-hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O,
-                            int BH, int N, float scale, unsigned long long* diag, int waves, hipStream_t stream);
-hipError_t sk_diag_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int variant,
-                            unsigned long long* diag, hipStream_t stream);
-hipError_t rp16_set_pass_ids(unsigned* dev_ptr);
-hipError_t lab_w64x_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
-                             int kstruct, int abl, unsigned long long* diag, hipStream_t stream);
-#endif
-}  // namespace fa
+#include "fa_dispatch.hpp"
 
 // The library is built with -fvisibility=hidden: only the entry points below leave it.
 #define FA_EXPORT __attribute__((visibility("default")))
@@ -64,7 +37,7 @@ FA_EXPORT int fa_debug_il_times(const void* Q, const void* K, const void* V, voi
 
 #endif  // FA_EXPERIMENTS
 
-// 1 when this build carries the experimental A/B kernels (explicit algo ids 7, 8, 13, 14, 16-22, 25), else 0.
+// 1 when this build carries the experimental A/B kernels (the rows of the algo table in fa_fwd_kernels.hip under FA_EXPERIMENTS), else 0.
 FA_EXPORT int fa_mi355_has_experiments(void)
 {
 #ifdef FA_EXPERIMENTS
@@ -77,8 +50,8 @@ FA_EXPORT int fa_mi355_has_experiments(void)
 FA_EXPORT int flashattn_forward_wmma(const void* Q, const void* K, const void* V, float* O,
                            int BH, int N, int D, float scale, void* stream)
 {
-    return (int)fa::forward_dispatch(Q, K, V, O, BH, N, D, scale, FA_DTYPE_F16, FA_OUT_F32, FA_ALGO_AUTO,
-                                     static_cast<hipStream_t>(stream));
+    return (int)fa::forward_dispatch({Q, K, V, O, BH, N, D, scale, FA_DTYPE_F16, FA_OUT_F32, static_cast<hipStream_t>(stream)},
+                                     FA_ALGO_AUTO);
 }
 
 FA_EXPORT int fa_forward_ex(const void* Q, const void* K, const void* V, void* O,
@@ -86,10 +59,9 @@ FA_EXPORT int fa_forward_ex(const void* Q, const void* K, const void* V, void* O
                   int in_dtype, int out_dtype, int algo, void* stream)
 {
     if (B <= 0 || H <= 0 || (long long)B * H > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
-    if (algo < FA_ALGO_AUTO || algo > 29) return (int)hipErrorInvalidValue;
     if (out_dtype != FA_OUT_F32 && out_dtype != FA_OUT_SAME) return (int)hipErrorInvalidValue;
-    return (int)fa::forward_dispatch(Q, K, V, O, B * H, N, d, scale, in_dtype, out_dtype, algo,
-                                     static_cast<hipStream_t>(stream));
+    // (an algo id the table in fa_fwd_kernels.hip has no row for is rejected there: no range is restated here)
+    return (int)fa::forward_dispatch({Q, K, V, O, B * H, N, d, scale, in_dtype, out_dtype, static_cast<hipStream_t>(stream)}, algo);
 }
 
 FA_EXPORT int fa_forward(const void* Q, const void* K, const void* V, void* O,
@@ -105,8 +77,7 @@ FA_EXPORT int fa_forward_causal(const void* Q, const void* K, const void* V, voi
 {
     if (B <= 0 || H <= 0 || (long long)B * H > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
     if (out_dtype != FA_OUT_F32 && out_dtype != FA_OUT_SAME) return (int)hipErrorInvalidValue;
-    return (int)fa::forward_causal_dispatch(Q, K, V, O, B * H, N, d, scale, in_dtype, out_dtype, algo,
-                                            static_cast<hipStream_t>(stream));
+    return (int)fa::forward_causal_dispatch({Q, K, V, O, B * H, N, d, scale, in_dtype, out_dtype, static_cast<hipStream_t>(stream)}, algo);
 }
 
 FA_EXPORT size_t fa_forward_splitkv_workspace_bytes(int B, int H, int Nq, int Nk, int d)

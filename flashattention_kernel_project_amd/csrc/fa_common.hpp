@@ -215,15 +215,4 @@ static inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, siz
 }
 #define FA_LAUNCH(...) ::fa::launch_k(__VA_ARGS__)
 
-// The kernel family a plain forward on the rolling pipeline runs on: what forward_dispatch() asks rp16_dispatch()
-// (fa_fwd_rp16.hip) for.
-enum class Rp16Family {
-    kFull,       // 64-row waves at D = 64 (512-row workgroups), 32-row waves at D = 128 (256-row workgroups)
-    kHalf,       // 32-row waves at D = 64, 16-row waves at D = 128
-    kQuarter,    // 16-row waves (D = 64)
-    kOneWave,    // one wave per SIMD: four 64-row waves per 256-row workgroup (D = 128)
-    kKeySplit,   // 32-row waves, keys split over two groups of four waves per 128-row workgroup (D = 64, N % 128 == 0)
-    kDma,        // kFull with K/V staging by LDS-DMA (D = 64, experimental build)
-};
-
 }  // namespace fa

@@ -14,6 +14,7 @@
 // One workgroup = 4 waves x 32 query rows; D in {64,128}; any N (ragged tails handled as in the
 // product kernels: rows/keys past N read as zero and are not stored).
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 namespace fa {
 

@@ -1,0 +1,98 @@
+// fa_dispatch.hpp -- the host side every translation unit shares: the argument struct of a forward, the element-type switch,
+// and the one declaration of each host function that crosses a translation unit.  Private to csrc/ (the public contract is
+// include/fa_mi355.h); no device code lives here.
+#pragma once
+#include "fa_common.hpp"
+
+#include <stddef.h>
+#include <type_traits>
+
+namespace fa {
+
+// One self-attention forward: Q, K, V, O [BH, N, D] row-major, in_dtype FA_DTYPE_*, out_dtype FA_OUT_*.  The split-KV, debug-stage,
+// streaming16 and lab entry points take other argument sets and keep their own lists.
+struct FwdArgs {
+    const void *Q, *K, *V;
+    void* O;
+    int BH, N, D;
+    float scale;
+    int in_dtype, out_dtype;
+    hipStream_t stream;
+};
+
+// The in_dtype x out_dtype switch: f(F16{} | BF16{}, std::true_type | std::false_type) -- the element traits and "output is
+// fp32" -- for the <T, kOutF32> instantiation the two ids name.  An out_dtype other than FA_OUT_F32 is the 16-bit output (the
+// C entry points admit the two values only).
+template <typename F>
+static inline hipError_t with_types(int in_dtype, int out_dtype, F&& f)
+{
+    if (in_dtype == 0) return out_dtype == 0 ? f(F16{}, std::true_type{}) : f(F16{}, std::false_type{});
+    if (in_dtype == 1) return out_dtype == 0 ? f(BF16{}, std::true_type{}) : f(BF16{}, std::false_type{});
+    return hipErrorInvalidValue;
+}
+
+// The kernel family a forward on the rolling pipeline runs on: what the algo table (fa_fwd_kernels.hip) asks rp16_dispatch() /
+// rp16_causal_dispatch() (fa_fwd_rp16.hip) for.
+enum class Rp16Family {
+    kFull,       // 64-row waves at D = 64 (512-row workgroups), 32-row waves at D = 128 (256-row workgroups)
+    kHalf,       // 32-row waves at D = 64, 16-row waves at D = 128
+    kQuarter,    // 16-row waves (D = 64)
+    kOneWave,    // one wave per SIMD: four 64-row waves per 256-row workgroup (D = 128)
+    kKeySplit,   // 32-row waves, keys split over two groups of four waves per 128-row workgroup (D = 64, N % 128 == 0)
+    kDma,        // kFull with K/V staging by LDS-DMA (D = 64, experimental build)
+};
+
+// ---- fa_fwd_kernels.hip: the algo table and the two dispatchers ----
+hipError_t forward_dispatch(const FwdArgs& a, int algo);
+hipError_t forward_causal_dispatch(const FwdArgs& a, int algo);
+int auto_algo(int BH, int N, int D, int in_dtype);
+const char* algo_kernel_name(int algo, int D);
+
+// ---- fa_fwd_il.hip ---- waves: 8 = one 256-row workgroup per CU, 4 = two 128-row workgroups per CU
+hipError_t il_dispatch(const FwdArgs& a, int waves);
+
+// ---- fa_fwd_rp16.hip ---- fold: the folded fast pass first (else the exact passes only)
+hipError_t rp16_dispatch(const FwdArgs& a, bool fold, Rp16Family family);
+hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull or kOneWave
+// One (D, X, staging, mask, waves, key split) family of the pipeline, defined in fa_fwd_rp16_kernel.hpp and explicitly instantiated
+// in fa_fwd_rp16_{d64,d64n,d64ks,d128,d128w,c,cw}.hip, one translation unit per group so that they compile side by side.
+template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
+hipError_t rp16_family(const FwdArgs& a, bool fold);
+
+// ---- fa_fwd_split.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
+                          int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
+size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
+hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
+                                int dtype, hipStream_t stream);
+hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,
+                                int num_batches, int seq_len, float scale, bool k_transposed,
+                                hipStream_t stream);
+
+#ifdef FA_EXPERIMENTS
+// ---- the A/B kernels of the experimental build: fa_fwd_{w64,w64x,w64p,rp,sk}.hip ----
+hipError_t w64_dispatch(const FwdArgs& a);
+hipError_t w64_causal_dispatch(const FwdArgs& a);
+hipError_t w64x_dispatch(const FwdArgs& a);
+hipError_t w64p_dispatch(const FwdArgs& a);
+hipError_t rp_dispatch(const FwdArgs& a, int fold);      // fold: 1 = folded fast pass where it exists (fp16, d = 64)
+hipError_t sk_dispatch(const FwdArgs& a, int variant);   // variant: 0 = shipped (fold for fp16, skew), 1 = no fold, 2 = no skew, 3 = neither
+// ---- ... and its measurement entry points ----
+hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O,
+                            int BH, int N, float scale, unsigned long long* diag, int waves, hipStream_t stream);
+hipError_t sk_diag_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int variant,
+                            unsigned long long* diag, hipStream_t stream);
+hipError_t lab_w64x_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
+                             int kstruct, int abl, unsigned long long* diag, hipStream_t stream);
+// the per-block pass-id recorder is a device variable of each pipeline translation unit: one setter per unit, and all of them
+hipError_t rp16_set_pass_ids(unsigned* dev_ptr);
+hipError_t rp16_set_pass_ids_d64(unsigned*);
+hipError_t rp16_set_pass_ids_d64n(unsigned*);
+hipError_t rp16_set_pass_ids_d64ks(unsigned*);
+hipError_t rp16_set_pass_ids_d128(unsigned*);
+hipError_t rp16_set_pass_ids_d128w(unsigned*);
+hipError_t rp16_set_pass_ids_c(unsigned*);
+hipError_t rp16_set_pass_ids_cw(unsigned*);
+#endif
+
+}  // namespace fa

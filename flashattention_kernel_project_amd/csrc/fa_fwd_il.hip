@@ -31,6 +31,7 @@
 // loader warp + cp.async ping-pong (flashattn_streaming_16x16_mw_v10.cu:156-195,
 // flashattn_forward_wmma_v5_cp_async.cu:221-256).
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -531,8 +532,7 @@ void fa_fwd_il_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
 }
 
 template <typename T, int D, bool kOutF32, int W>
-static hipError_t launch_il(const void* Q, const void* K, const void* V, void* O,
-                            int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_il(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     auto kern = fa_fwd_il_kernel<T, D, kOutF32, W>;
@@ -540,15 +540,15 @@ static hipError_t launch_il(const void* Q, const void* K, const void* V, void* O
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    const int nqb = (N + 32 * W - 1) / (32 * W);
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + 32 * W - 1) / (32 * W);
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     // persistent grid: one resident generation of workgroups (8 waves per CU at <= 256 VGPRs)
     const int grid_cap = device_cus() * (8 / W);
     const unsigned grid = (grid_cap > 0 && nwg > grid_cap) ? (unsigned)grid_cap : (unsigned)nwg;
-    FA_LAUNCH(kern, dim3(grid), dim3(64 * W), lds_bytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e,
+    FA_LAUNCH(kern, dim3(grid), dim3(64 * W), lds_bytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e,
                        static_cast<unsigned long long*>(nullptr), (unsigned)nwg);
     return launch_status();
 }
@@ -652,23 +652,12 @@ hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O
 #endif  // FA_EXPERIMENTS
 
 // waves: 8 = one 256-row workgroup per CU, 4 = two 128-row workgroups per CU
-hipError_t il_dispatch(const void* Q, const void* K, const void* V, void* O,
-                       int BH, int N, int D, float scale, int in_dtype, int out_dtype, int waves,
-                       hipStream_t stream)
+hipError_t il_dispatch(const FwdArgs& a, int waves)
 {
-    if (D != 64) return hipErrorInvalidValue;
-    if (waves == 8) {
-        if (in_dtype == 0)
-            return out_dtype == 0 ? launch_il<F16, 64, true, 8>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_il<F16, 64, false, 8>(Q, K, V, O, BH, N, scale, stream);
-        return out_dtype == 0 ? launch_il<BF16, 64, true, 8>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_il<BF16, 64, false, 8>(Q, K, V, O, BH, N, scale, stream);
-    }
-    if (in_dtype == 0)
-        return out_dtype == 0 ? launch_il<F16, 64, true, 4>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_il<F16, 64, false, 4>(Q, K, V, O, BH, N, scale, stream);
-    return out_dtype == 0 ? launch_il<BF16, 64, true, 4>(Q, K, V, O, BH, N, scale, stream)
-                          : launch_il<BF16, 64, false, 4>(Q, K, V, O, BH, N, scale, stream);
+    if (a.D != 64) return hipErrorInvalidValue;
+    if (waves == 8)
+        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_il<decltype(t), 64, decltype(f32)::value, 8>(a); });
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_il<decltype(t), 64, decltype(f32)::value, 4>(a); });
 }
 
 }  // namespace fa

@@ -28,6 +28,7 @@
 //   * buffer_load/buffer_store with a per-head resource descriptor give N-tail handling for free
 //     (rows >= N read 0 / are not stored); keys >= N are masked to -inf in the last tile only.
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 namespace fa {
 
@@ -394,95 +395,141 @@ void fa_fwd_generic_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __re
 namespace fa {
 
 template <typename T, int D, bool kOutF32, int W = kWaves, int kOcc = 2, bool kCausal = false>
-static hipError_t launch_tiled(const void* Q, const void* K, const void* V, void* O,
-                               int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_tiled(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     auto kern = fa_fwd_kernel<T, D, kOutF32, W, kOcc, kCausal>;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kern), G::kLdsBytes);
     if (attr != hipSuccess) return attr;
-    const int nqb = (N + 32 * W - 1) / (32 * W);
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + 32 * W - 1) / (32 * W);
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    FA_LAUNCH(kern, dim3((unsigned)nwg), dim3(64 * W), G::kLdsBytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e);
+    FA_LAUNCH(kern, dim3((unsigned)nwg), dim3(64 * W), G::kLdsBytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e);
     return launch_status();
 }
 
 template <typename T, bool kOutF32, bool kCausal = false>
-static hipError_t launch_generic(const void* Q, const void* K, const void* V, void* O,
-                                 int BH, int N, int D, float scale, hipStream_t stream)
+static hipError_t launch_generic(const FwdArgs& a)
 {
-    const int nqb = (N + 15) / 16;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + 15) / 16;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    FA_LAUNCH((fa_fwd_generic_kernel<T, kOutF32, kCausal>), dim3((unsigned)nwg), dim3(64), 0, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, D, nqb, scale * kLog2e);
+    FA_LAUNCH((fa_fwd_generic_kernel<T, kOutF32, kCausal>), dim3((unsigned)nwg), dim3(64), 0, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, a.D, nqb, a.scale * kLog2e);
     return launch_status();
 }
 
-template <typename T, bool kOutF32>
-static hipError_t dispatch_d(const void* Q, const void* K, const void* V, void* O,
-                             int BH, int N, int D, float scale, int algo, hipStream_t stream)
+// The tiled kernel on W waves per workgroup (32 query rows each), D in {64, 128}.
+template <int W, bool kCausal>
+static hipError_t tiled_forward(const FwdArgs& a)
 {
-    if (algo != 1) {   // 0 = auto, 2 = force tiled
-        if (D == 64)  return launch_tiled<T, 64, kOutF32>(Q, K, V, O, BH, N, scale, stream);
-        if (D == 128) return launch_tiled<T, 128, kOutF32>(Q, K, V, O, BH, N, scale, stream);
-        if (algo == 2) return hipErrorInvalidValue;
-    }
-    return launch_generic<T, kOutF32>(Q, K, V, O, BH, N, D, scale, stream);
-}
-
-template <typename T, bool kOutF32>
-static hipError_t dispatch_causal_d(const void* Q, const void* K, const void* V, void* O,
-                                    int BH, int N, int D, float scale, int algo, hipStream_t stream)
-{
-    // 128-row workgroups, two per CU: finer diagonal, prologues overlap the neighbour's main loop.  Measured
-    // B8 H16 N4096 d64: 0.375 ms against 0.442 (256-row) -> AUTO at d=64; N8192 d128: 2.40 vs 2.31 ms -> not at d=128.
-    if (algo == 6 || (algo == 0 && D == 64)) {
-        if (D == 64)  return launch_tiled<T, 64, kOutF32, 4, 2, true>(Q, K, V, O, BH, N, scale, stream);
-        if (D == 128) return launch_tiled<T, 128, kOutF32, 4, 2, true>(Q, K, V, O, BH, N, scale, stream);
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        if (a.D == 64)  return launch_tiled<T, 64, decltype(f32)::value, W, 2, kCausal>(a);
+        if (a.D == 128) return launch_tiled<T, 128, decltype(f32)::value, W, 2, kCausal>(a);
         return hipErrorInvalidValue;
-    }
-    if (algo != 1) {
-        if (D == 64)  return launch_tiled<T, 64, kOutF32, kWaves, 2, true>(Q, K, V, O, BH, N, scale, stream);
-        if (D == 128) return launch_tiled<T, 128, kOutF32, kWaves, 2, true>(Q, K, V, O, BH, N, scale, stream);
-        if (algo == 2) return hipErrorInvalidValue;
-    }
-    return launch_generic<T, kOutF32, true>(Q, K, V, O, BH, N, D, scale, stream);
+    });
 }
 
-hipError_t il_dispatch(const void* Q, const void* K, const void* V, void* O,
-                       int BH, int N, int D, float scale, int in_dtype, int out_dtype, int waves,
-                       hipStream_t stream);
+template <bool kCausal>
+static hipError_t generic_forward(const FwdArgs& a)
+{
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+        return launch_generic<decltype(t), decltype(f32)::value, kCausal>(a);
+    });
+}
 
-hipError_t w64p_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                         hipStream_t stream);
-hipError_t w64_dispatch(const void* Q, const void* K, const void* V, void* O,
-                        int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                        hipStream_t stream);
-hipError_t w64x_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                         hipStream_t stream);
-hipError_t rp16_causal_dispatch(const void* Q, const void* K, const void* V, void* O,
-                                int BH, int N, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
-hipError_t rp16_causal_dispatch_1w(const void* Q, const void* K, const void* V, void* O,
-                                int BH, int N, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
-hipError_t rp16_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, bool fold, Rp16Family family,
-                         hipStream_t stream);
-hipError_t rp_dispatch(const void* Q, const void* K, const void* V, void* O,
-                       int BH, int N, int D, float scale, int in_dtype, int out_dtype, int fold,
-                       hipStream_t stream);
-hipError_t sk_dispatch(const void* Q, const void* K, const void* V, void* O,
-                       int BH, int N, int D, float scale, int in_dtype, int out_dtype, int variant,
-                       hipStream_t stream);
-hipError_t w64_causal_dispatch(const void* Q, const void* K, const void* V, void* O,
-                               int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                               hipStream_t stream);
+#ifdef FA_EXPERIMENTS
+// occupancy variants of the plain tiled kernel on 128-row workgroups
+template <int kOcc>
+static hipError_t tiled_occupancy_forward(const FwdArgs& a)
+{
+    if (a.in_dtype != 0 || a.out_dtype != 0) return hipErrorInvalidValue;   // instantiated for fp16 in, fp32 out only
+    return launch_tiled<F16, 64, true, 4, kOcc>(a);
+}
+#endif
+
+// ---- the algo table: every explicit algo id there is, in which build, for which D, and whether it runs under the mask ----
+// The one source for forward_dispatch(), forward_causal_dispatch(), algo_kernel_name() and the range of ids fa_forward_ex()
+// takes; include/fa_mi355.h restates it for callers.  An id without a row (3, 4, 9-12, 15 were removed) is hipErrorInvalidValue.
+enum : unsigned {
+    kD64 = 1, kD128 = 2,
+    kDAny = 4,   // every D validate() lets through: D % 16 == 0, D <= kGenMaxD
+};
+struct AlgoEntry {
+    hipError_t (*launch)(const FwdArgs&);   // null: the id is not accepted here
+    unsigned dims;                          // kD* the launcher accepts
+};
+struct AlgoRow {
+    int id;
+    const char* name;     // its FA_ALGO_* constant in include/fa_mi355.h ("": the header names the id in prose only)
+    const char* kernel;   // the kernel template it launches
+    AlgoEntry plain, causal;
+};
+#define FA_ROW_GO(...) [](const FwdArgs& a) { return __VA_ARGS__; }
+static constexpr AlgoRow kAlgos[] = {
+    {1, "FA_ALGO_GENERIC", "fa::fa_fwd_generic_kernel", {generic_forward<false>, kDAny}, {generic_forward<true>, kDAny}},
+    {2, "FA_ALGO_TILED", "fa::fa_fwd_kernel", {tiled_forward<kWaves, false>, kD64 | kD128}, {tiled_forward<kWaves, true>, kD64 | kD128}},
+    {5, "FA_ALGO_INTERLEAVED", "fa::fa_fwd_il_kernel", {FA_ROW_GO(il_dispatch(a, 8)), kD64}, {}},
+    // under the mask id 6 is NOT the interleaved kernel: it is the tiled kernel on 128-row workgroups, two per CU, D in {64, 128}
+    {6, "FA_ALGO_INTERLEAVED_2WG", "fa::fa_fwd_il_kernel", {FA_ROW_GO(il_dispatch(a, 4)), kD64}, {tiled_forward<4, true>, kD64 | kD128}},
+#ifdef FA_EXPERIMENTS
+    // A/B kernels AUTO never selects: only in libfa_mi355_exp.so (make experimental)
+    {7, "", "fa::fa_fwd_kernel", {tiled_occupancy_forward<3>, kD64}, {}},   // fp16, fp32 out only (tiled_occupancy_forward)
+    {8, "", "fa::fa_fwd_kernel", {tiled_occupancy_forward<2>, kD64}, {}},
+    // round 1's defaults and (16) the 32x32x16 pipeline: A/B baselines.  13 under the mask: the 64-rows-per-wave kernel with the
+    // mask; measured 3-4 % SLOWER than the plain tiled kernel under the mask (B8 H16 N4096 d64: 0.462 vs 0.443 ms; N8192 d128:
+    // 2.41 vs 2.36 ms), so AUTO stays tiled.
+    {13, "FA_ALGO_W64", "fa::fa_fwd_w64_kernel", {w64_dispatch, kD64 | kD128}, {w64_causal_dispatch, kD64 | kD128}},
+    {14, "FA_ALGO_W64P", "fa::fa_fwd_w64p_kernel", {w64p_dispatch, kD64 | kD128}, {}},
+    {16, "FA_ALGO_W64X", "fa::fa_fwd_w64x_kernel", {w64x_dispatch, kD64 | kD128}, {}},
+    {17, "FA_ALGO_SK", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 0)), kD64}, {}},
+    {18, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 1)), kD64}, {}},
+    {19, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 2)), kD64}, {}},
+    {20, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 3)), kD64}, {}},
+    {21, "FA_ALGO_RP", "fa::fa_fwd_rp_kernel", {FA_ROW_GO(rp_dispatch(a, 0)), kD64 | kD128}, {}},
+    {22, "FA_ALGO_RP_FOLD", "fa::fa_fwd_rp_kernel", {FA_ROW_GO(rp_dispatch(a, 1)), kD64 | kD128}, {}},
+#endif
+    {23, "FA_ALGO_RP16", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, false, Rp16Family::kFull)), kD64 | kD128}, {}},
+    {24, "FA_ALGO_RP16_FOLD", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, true, Rp16Family::kFull)), kD64 | kD128},
+     {FA_ROW_GO(rp16_causal_dispatch(a, Rp16Family::kFull)), kD64 | kD128}},
+#ifdef FA_EXPERIMENTS
+    {25, "FA_ALGO_RP16_DMA", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, true, Rp16Family::kDma)), kD64}, {}},   // 24 with LDS-DMA staging
+#else
+    // kept as it was before the table: the product build rejects 25 and still names its kernel in fa_selected_kernel()
+    {25, "FA_ALGO_RP16_DMA", "fa::fa_fwd_rp16_kernel", {}, {}},
+#endif
+    // the pipeline on half-width / quarter-width waves (32 / 16 rows at D = 64, 16 at D = 128: no quarter width there)
+    {26, "FA_ALGO_RP16_FOLD_HALF", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, true, Rp16Family::kHalf)), kD64 | kD128}, {}},
+    {27, "FA_ALGO_RP16_FOLD_QUARTER", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, true, Rp16Family::kQuarter)), kD64}, {}},
+    // d = 128 with one wave per SIMD (four 64-row waves, the whole register file each)
+    {28, "FA_ALGO_RP16_FOLD_1W", "fa::fa_fwd_rp16_kernel", {FA_ROW_GO(rp16_dispatch(a, true, Rp16Family::kOneWave)), kD128},
+     {FA_ROW_GO(rp16_causal_dispatch(a, Rp16Family::kOneWave)), kD128}},
+    // 32-row waves, keys split over two groups of four waves per 128-row workgroup (d = 64); the split needs whole tiles per
+    // group: other N run the 16-row waves (same workgroup size)
+    {29, "FA_ALGO_RP16_FOLD_KS2", "fa::fa_fwd_rp16_kernel",
+     {FA_ROW_GO(rp16_dispatch(a, true, a.N % 128 != 0 ? Rp16Family::kQuarter : Rp16Family::kKeySplit)), kD64}, {}},
+};
+#undef FA_ROW_GO
+
+constexpr bool algo_ids_ascend()
+{
+    for (size_t i = 1; i < sizeof(kAlgos) / sizeof(kAlgos[0]); ++i)
+        if (kAlgos[i - 1].id >= kAlgos[i].id) return false;
+    return true;
+}
+static_assert(algo_ids_ascend(), "kAlgos holds one row per id, in ascending order");
+
+static const AlgoRow* find_algo(int algo)
+{
+    for (const AlgoRow& r : kAlgos)
+        if (r.id == algo) return &r;
+    return nullptr;
+}
+
 // AUTO: the explicit algo id a shape resolves to (one rule for the dispatcher and for fa_selected_kernel()).
 //   d = 64, N > 256 and at least one 512-row workgroup per CU: the rolling half-tile pipeline on 16x16x32 with the folded
 //     fast pass (fa_fwd_rp16.hip, 24), fp16 and bf16.  Round 2, one device, interleaved A/B, B8 H16 N4096, ms per launch:
@@ -528,115 +575,70 @@ int auto_algo(int BH, int N, int D, int in_dtype)
     return best;
 }
 
-// Name of the kernel template an explicit algo id launches (rocprofv3 kernel-trace names start with it).
-const char* algo_kernel_name(int algo, int D)
+// AUTO under the causal mask (not a reference entry point: SURVEY 8(f) rank 1).
+static int auto_algo_causal(int BH, int N, int D)
 {
-    switch (algo) {
-        case 1: return "fa::fa_fwd_generic_kernel";
-        case 2: return (D == 64 || D == 128) ? "fa::fa_fwd_kernel" : "fa::fa_fwd_generic_kernel";
-        case 5: case 6: return "fa::fa_fwd_il_kernel";
-#ifdef FA_EXPERIMENTS
-        case 13: return "fa::fa_fwd_w64_kernel";
-        case 16: return "fa::fa_fwd_w64x_kernel";
-        case 21: case 22: return "fa::fa_fwd_rp_kernel";
-#endif
-        case 23: case 24: case 25: case 26: case 27: case 28: case 29: return "fa::fa_fwd_rp16_kernel";
-        default: return "";
-    }
-}
-
-// algo: 0 auto, 1 generic single-fragment kernel, 2 tiled kernel (D in {64,128} only), 5 / 6 the interleaved kernel
-//       (fa_fwd_il.hip, D = 64), 23-29 the rolling pipeline (fa_fwd_rp16.hip); the other ids are A/B kernels of the
-//       experimental build or removed (include/fa_mi355.h has the list)
-hipError_t forward_dispatch(const void* Q, const void* K, const void* V, void* O,
-                            int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                            int algo, hipStream_t stream)
-{
-    if (!Q || !K || !V || !O) return hipErrorInvalidValue;
-    if (BH <= 0 || N <= 0 || D <= 0 || D % 16 != 0 || D > kGenMaxD) return hipErrorInvalidValue;
-    // per-head byte offsets are 32 bit, including the rows a partial last query block overhangs
-    if ((unsigned long long)(N + kBlockM) * D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (in_dtype != 0 && in_dtype != 1) return hipErrorInvalidValue;
-    if (algo == 0) algo = auto_algo(BH, N, D, in_dtype);
-    if (algo == 5) return il_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 8, stream);
-    if (algo == 6) return il_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 4, stream);
-    if (algo == 23) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, false, Rp16Family::kFull, stream);
-    if (algo == 24) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kFull, stream);
-    if (algo == 29) {   // 32-row waves, keys split over two groups of four waves per 128-row workgroup (d = 64); the split needs
-        if (D != 64) return hipErrorInvalidValue;   // whole tiles per group: other N run the 16-row waves (same workgroup size)
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, N % 128 != 0 ? Rp16Family::kQuarter : Rp16Family::kKeySplit, stream);
-    }
-    if (algo == 28) {   // d = 128 with one wave per SIMD (four 64-row waves, the whole register file each)
-        if (D != 128) return hipErrorInvalidValue;
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kOneWave, stream);
-    }
-    if (algo == 26 || algo == 27) {   // the pipeline on half-width / quarter-width waves (32 / 16 rows at D = 64, 16 at D = 128)
-        if (D != 64 && !(D == 128 && algo == 26)) return hipErrorInvalidValue;
-        return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, algo == 26 ? Rp16Family::kHalf : Rp16Family::kQuarter, stream);
-    }
-#ifdef FA_EXPERIMENTS
-    if (algo == 13) return w64_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);    // round 1's defaults and the
-    if (algo == 16) return w64x_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);   // 32x32x16 pipeline: A/B baselines
-    if (algo == 21) return rp_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 0, stream);
-    if (algo == 22) return rp_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, 1, stream);
-    if (algo == 25) return rp16_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, true, Rp16Family::kDma, stream);   // 24 with LDS-DMA staging
-    if (algo >= 17 && algo <= 20) return sk_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, algo - 17, stream);   // A/B kernels AUTO never selects: only in libfa_mi355_exp.so (make experimental)
-    if (algo == 7 || algo == 8) {   // occupancy variants of the plain tiled kernel, fp16 d=64 fp32-out
-        if (D != 64 || in_dtype != 0 || out_dtype != 0) return hipErrorInvalidValue;
-        return algo == 7 ? launch_tiled<F16, 64, true, 4, 3>(Q, K, V, O, BH, N, scale, stream)
-                         : launch_tiled<F16, 64, true, 4, 2>(Q, K, V, O, BH, N, scale, stream);
-    }
-    if (algo == 14) return w64p_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);
-#else
-    if (algo == 3 || algo == 4 || (algo >= 7 && algo <= 22) || algo == 25 || algo > 29) return hipErrorInvalidValue;
-#endif
-    if (algo == 3 || algo == 4 || (algo >= 9 && algo <= 12) || algo == 15) return hipErrorInvalidValue;   // ids of removed A/B kernels
-    if (in_dtype == 0)
-        return out_dtype == 0 ? dispatch_d<F16, true>(Q, K, V, O, BH, N, D, scale, algo, stream)
-                              : dispatch_d<F16, false>(Q, K, V, O, BH, N, D, scale, algo, stream);
-    if (in_dtype == 1)
-        return out_dtype == 0 ? dispatch_d<BF16, true>(Q, K, V, O, BH, N, D, scale, algo, stream)
-                              : dispatch_d<BF16, false>(Q, K, V, O, BH, N, D, scale, algo, stream);
-    return hipErrorInvalidValue;
-}
-
-// Causal forward (not a reference entry point).  algo: 0 auto, 1 generic, 2 tiled, 13 w64, 24 the pipeline, 28 the pipeline with one wave per SIMD (d = 128).
-hipError_t forward_causal_dispatch(const void* Q, const void* K, const void* V, void* O,
-                                   int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                                   int algo, hipStream_t stream)
-{
-    if (!Q || !K || !V || !O) return hipErrorInvalidValue;
-    if (BH <= 0 || N <= 0 || D <= 0 || D % 16 != 0 || D > kGenMaxD) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + kBlockM) * D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (algo != 0 && algo != 1 && algo != 2 && algo != 6 && algo != 13 && algo != 24 && algo != 28) return hipErrorInvalidValue;
-    if (in_dtype != 0 && in_dtype != 1) return hipErrorInvalidValue;
-    // algo 13: the 64-rows-per-wave kernel with the mask; measured 3-4 % SLOWER than the plain tiled kernel
-    // under the mask (B8 H16 N4096 d64: 0.462 vs 0.443 ms; N8192 d128: 2.41 vs 2.36 ms), so AUTO stays tiled.
-#ifdef FA_EXPERIMENTS
-    if (algo == 13)
-        return w64_causal_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);
-#else
-    if (algo == 13) return hipErrorInvalidValue;
-#endif
     // the pipeline under the mask (fa_fwd_rp16.hip): B8 H16 N4096 d64 fp16 0.309 ms against 0.369 for the tiled kernel (bf16 0.349 /
     // 0.364), N8192 d128 2.00 against 2.29 ms -- AUTO wherever the grid gives every CU a workgroup, else the tiled kernel
-    const bool algo_was_auto = algo == 0;
-    if (algo == 0 && (D == 64 || D == 128) && N > 256 &&
-        (long long)BH * ((N + (D == 64 ? 511 : 255)) / (D == 64 ? 512 : 256)) >= device_cus())
-        algo = 24;
-    // d = 128, long sequences on grids of four rounds or more: one wave per SIMD as in the plain forward (B8 H16 N8192 2.005 vs 2.063 ms,
-    // B1 H32 N16384 2.55 vs 2.68; N = 4096 loses 2 %; profiles/r03_d128_variants.txt)
-    if (algo_was_auto && algo == 24 && D == 128 && N >= 8192 && (long long)BH * ((N + 255) / 256) >= 4 * (long long)device_cus())
-        algo = 28;
-    if (algo == 28) return rp16_causal_dispatch_1w(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);   // (d = 128 only)
-    if (algo == 24) return rp16_causal_dispatch(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);
-    if (in_dtype == 0)
-        return out_dtype == 0 ? dispatch_causal_d<F16, true>(Q, K, V, O, BH, N, D, scale, algo, stream)
-                              : dispatch_causal_d<F16, false>(Q, K, V, O, BH, N, D, scale, algo, stream);
-    if (in_dtype == 1)
-        return out_dtype == 0 ? dispatch_causal_d<BF16, true>(Q, K, V, O, BH, N, D, scale, algo, stream)
-                              : dispatch_causal_d<BF16, false>(Q, K, V, O, BH, N, D, scale, algo, stream);
-    return hipErrorInvalidValue;
+    if ((D == 64 || D == 128) && N > 256 &&
+        (long long)BH * ((N + (D == 64 ? 511 : 255)) / (D == 64 ? 512 : 256)) >= device_cus()) {
+        // d = 128, long sequences on grids of four rounds or more: one wave per SIMD as in the plain forward (B8 H16 N8192 2.005 vs 2.063 ms,
+        // B1 H32 N16384 2.55 vs 2.68; N = 4096 loses 2 %; profiles/r03_d128_variants.txt)
+        if (D == 128 && N >= 8192 && (long long)BH * ((N + 255) / 256) >= 4 * (long long)device_cus())
+            return 28;
+        return 24;
+    }
+    // 128-row workgroups, two per CU (6 under the mask): finer diagonal, prologues overlap the neighbour's main loop.  Measured
+    // B8 H16 N4096 d64: 0.375 ms against 0.442 (256-row) -> AUTO at d=64; N8192 d128: 2.40 vs 2.31 ms -> not at d=128.
+    if (D == 64) return 6;
+    return D == 128 ? 2 : 1;
+}
+
+// Name of the kernel template an explicit algo id launches (rocprofv3 kernel-trace names start with it).  Kept as it was before
+// the table: the name does not look at whether the row accepts D (5 / 6 at D = 32, 28 at D = 64 are named and rejected), except
+// that the tiled kernel at a D it has no instantiation for names the generic one.
+const char* algo_kernel_name(int algo, int D)
+{
+    const AlgoRow* r = find_algo(algo);
+    if (!r) return "";
+    if (r->id == 2 && D != 64 && D != 128) return find_algo(1)->kernel;
+    return r->kernel;
+}
+
+// pointers non-null, BH / N / D ranges, element type: what every kernel behind the table relies on
+static bool validate(const FwdArgs& a)
+{
+    if (!a.Q || !a.K || !a.V || !a.O) return false;
+    if (a.BH <= 0 || a.N <= 0 || a.D <= 0 || a.D % 16 != 0 || a.D > kGenMaxD) return false;
+    // per-head byte offsets are 32 bit, including the rows a partial last query block overhangs
+    if ((unsigned long long)(a.N + kBlockM) * a.D * 4ull >= (1ull << 32)) return false;
+    return a.in_dtype == 0 || a.in_dtype == 1;
+}
+
+static hipError_t run_row(const FwdArgs& a, int algo, bool causal)
+{
+    const AlgoRow* r = find_algo(algo);
+    if (!r) return hipErrorInvalidValue;
+    const AlgoEntry& e = causal ? r->causal : r->plain;
+    const unsigned d = kDAny | (a.D == 64 ? kD64 : 0u) | (a.D == 128 ? kD128 : 0u);
+    if (!e.launch || !(e.dims & d)) return hipErrorInvalidValue;
+    return e.launch(a);
+}
+
+// algo: 0 = AUTO (auto_algo), else an id of kAlgos
+hipError_t forward_dispatch(const FwdArgs& a, int algo)
+{
+    if (!validate(a)) return hipErrorInvalidValue;
+    if (algo == 0) algo = auto_algo(a.BH, a.N, a.D, a.in_dtype);
+    return run_row(a, algo, false);
+}
+
+// Causal forward: the ids of kAlgos with a launcher under the mask.
+hipError_t forward_causal_dispatch(const FwdArgs& a, int algo)
+{
+    if (!validate(a)) return hipErrorInvalidValue;
+    if (algo == 0) algo = auto_algo_causal(a.BH, a.N, a.D);
+    return run_row(a, algo, true);
 }
 
 }  // namespace fa

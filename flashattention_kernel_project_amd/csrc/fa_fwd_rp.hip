@@ -25,6 +25,7 @@
 // Overflow safety, row sums, output, persistent XCD-aware grid: as fa_fwd_w64.hip (optimistic pass against a fixed
 // reference max + exact detection + tracked re-run).
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -569,48 +570,41 @@ void fa_fwd_rp_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
 }
 
 template <typename T, int D, int X, bool kOutF32, bool kFold = false>
-static hipError_t launch_rp(const void* Q, const void* K, const void* V, void* O,
-                              int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_rp(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     constexpr int kRows = 32 * X * rp::kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const int grid_cap = device_cus();
     const unsigned grid = nwg > grid_cap ? (unsigned)grid_cap : (unsigned)nwg;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_rp_kernel<T, D, X, kOutF32, kFold>), rp::kSlots * G::kBufBytes);
     if (attr != hipSuccess) return attr;
     FA_LAUNCH((fa_fwd_rp_kernel<T, D, X, kOutF32, kFold>), dim3(grid), dim3(64 * rp::kW),
-                       rp::kSlots * G::kBufBytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, (unsigned)nwg);
+                       rp::kSlots * G::kBufBytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg);
     return launch_status();
 }
 
 // fold: 1 = folded fast pass where it exists (fp16, d = 64), 0 = exact passes only
-hipError_t rp_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype, int fold,
-                         hipStream_t stream)
+hipError_t rp_dispatch(const FwdArgs& a, int fold)
 {
-    if (!(scale == scale) || scale * kLog2e == 0.0f) fold = 0;   // NaN / zero scale: the exact pass defines the result
-    if (D != 64 && D != 128) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + 64 * rp::kW + 3 * kBlockN) * (unsigned)D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (D == 64) {
-        if (in_dtype == 0 && fold)
-            return out_dtype == 0 ? launch_rp<F16, 64, 2, true, true>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_rp<F16, 64, 2, false, true>(Q, K, V, O, BH, N, scale, stream);
-        if (in_dtype == 0)
-            return out_dtype == 0 ? launch_rp<F16, 64, 2, true>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_rp<F16, 64, 2, false>(Q, K, V, O, BH, N, scale, stream);
-        return out_dtype == 0 ? launch_rp<BF16, 64, 2, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_rp<BF16, 64, 2, false>(Q, K, V, O, BH, N, scale, stream);
-    }
-    if (in_dtype == 0)
-        return out_dtype == 0 ? launch_rp<F16, 128, 1, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_rp<F16, 128, 1, false>(Q, K, V, O, BH, N, scale, stream);
-    return out_dtype == 0 ? launch_rp<BF16, 128, 1, true>(Q, K, V, O, BH, N, scale, stream)
-                          : launch_rp<BF16, 128, 1, false>(Q, K, V, O, BH, N, scale, stream);
+    if (!(a.scale == a.scale) || a.scale * kLog2e == 0.0f) fold = 0;   // NaN / zero scale: the exact pass defines the result
+    if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
+    if ((unsigned long long)(a.N + 64 * rp::kW + 3 * kBlockN) * (unsigned)a.D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        constexpr bool kOutF32 = decltype(f32)::value;
+        if (a.D == 64) {
+            if constexpr (std::is_same<T, F16>::value) {
+                if (fold) return launch_rp<T, 64, 2, kOutF32, true>(a);
+            }
+            return launch_rp<T, 64, 2, kOutF32>(a);
+        }
+        return launch_rp<T, 128, 1, kOutF32>(a);
+    });
 }
 
 }  // namespace fa

@@ -4,11 +4,7 @@
 
 namespace fa {
 
-hipError_t rp16_c_d128w4(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int in_dtype, int out_dtype,
-                         bool fold, hipStream_t stream)
-{
-    return rp16_family<128, 4, false, true, 4>(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, fold, stream);
-}
+template hipError_t rp16_family<128, 4, false, true, 4>(const FwdArgs&, bool);
 
 #ifdef FA_EXPERIMENTS
 hipError_t rp16_set_pass_ids_cw(unsigned* p) { return rp16_set_pass_ids_tu(p); }

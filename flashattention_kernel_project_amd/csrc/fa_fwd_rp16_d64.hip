@@ -3,18 +3,9 @@
 
 namespace fa {
 
-hipError_t rp16_d64x4(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int in_dtype, int out_dtype,
-                      bool fold, hipStream_t stream)
-{
-    return rp16_family<64, 4, false, false>(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, fold, stream);
-}
-
+template hipError_t rp16_family<64, 4, false, false>(const FwdArgs&, bool);
 #ifdef FA_EXPERIMENTS
-hipError_t rp16_d64x4_dma(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int in_dtype, int out_dtype,
-                          bool fold, hipStream_t stream)
-{
-    return rp16_family<64, 4, true, false>(Q, K, V, O, BH, N, scale, in_dtype, out_dtype, fold, stream);
-}
+template hipError_t rp16_family<64, 4, true, false>(const FwdArgs&, bool);   // K/V staged by LDS-DMA
 #endif
 
 #ifdef FA_EXPERIMENTS

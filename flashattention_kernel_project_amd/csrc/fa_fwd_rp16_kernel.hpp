@@ -18,6 +18,7 @@
 // feeding the wave's four query blocks) around the vector work of 32 scores per lane.
 #pragma once
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -1275,63 +1276,61 @@ void fa_fwd_rp16_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
 }
 
 template <typename T, int D, int X, bool kOutF32, bool kFold, bool kDma = false, bool kCausal = false, int kWv = 8, int kKeySplit = 1>
-static hipError_t launch_rp16(const void* Q, const void* K, const void* V, void* O,
-                              int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_rp16(const FwdArgs& a)
 {
     using namespace rp16;
     constexpr int kW = kWv;
     constexpr int lds_bytes = kKeySplit * ((pair_tiles(D, X, kDma) && kKeySplit == 1 && kWv == 8) ? 8 : 4) * 2 * kBlockN * D * 2;   // ring(s) of four (eight) [K tile][V tile] slots
-    if (kKeySplit > 1 && N % (kBlockN * kKeySplit) != 0) return hipErrorInvalidValue;
+    if (kKeySplit > 1 && a.N % (kBlockN * kKeySplit) != 0) return hipErrorInvalidValue;
     constexpr int lds_extra = 64;   // the waves' landing flags (kFlagBar)
     constexpr int kRows = 16 * X * kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const long long cap = device_cus();
     const unsigned grid = nwg > cap ? (unsigned)cap : (unsigned)nwg;
     auto kern = fa_fwd_rp16_kernel<T, D, X, kOutF32, kFold, kDma, kCausal, false, kWv, kKeySplit>;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds_bytes + lds_extra);
     if (attr != hipSuccess) return attr;
-    FA_LAUNCH(kern, dim3(grid), dim3(64 * kW * kKeySplit), lds_bytes + lds_extra, stream,
-              static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K), static_cast<const uint16_t*>(V), O, N, nqb,
-              scale * kLog2e, (unsigned)nwg);
+    FA_LAUNCH(kern, dim3(grid), dim3(64 * kW * kKeySplit), lds_bytes + lds_extra, a.stream,
+              static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K), static_cast<const uint16_t*>(a.V), a.O, a.N, nqb,
+              a.scale * kLog2e, (unsigned)nwg);
     if (launch_status() != hipSuccess) return launch_status();
     if constexpr (!kDma && 16 * X * (D / 64) >= 64) {
         // full-width waves: the redo kernel for the row blocks whose optimistic passes failed (see kScan): half-width waves,
         // running-max pass only; with nothing marked it ends after one look at the marker words
         constexpr int kW2 = 8, X2 = X * kW / (2 * kW2), kRows2 = 16 * X2 * kW2;
         constexpr int lds2 = (pair_tiles(D, X2, false) ? 8 : 4) * 2 * kBlockN * D * 2 + 4 * (1 + 64 * kW2);   // (half this kernel's row block, on eight waves)
-        const int nqb2 = (N + kRows2 - 1) / kRows2;
-        const long long nwg2 = (long long)BH * nqb2;
+        const int nqb2 = (a.N + kRows2 - 1) / kRows2;
+        const long long nwg2 = (long long)a.BH * nqb2;
         if (nwg2 > 0x7FFFFFFFll) return hipErrorInvalidValue;
         const unsigned grid2 = nwg2 > cap ? (unsigned)cap : (unsigned)nwg2;
         auto kern2 = fa_fwd_rp16_kernel<T, D, X2, kOutF32, false, false, kCausal, true>;
         const hipError_t attr2 = ensure_dyn_lds(reinterpret_cast<const void*>(kern2), lds2);
         if (attr2 != hipSuccess) return attr2;
         static_assert(2 * kRows2 == kRows, "the redo kernel's row block is half of this kernel's");
-        FA_LAUNCH(kern2, dim3(grid2), dim3(64 * kW2), lds2, stream,
-                  static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K), static_cast<const uint16_t*>(V), O, N, nqb2,
-                  scale * kLog2e, (unsigned)nwg2);
+        FA_LAUNCH(kern2, dim3(grid2), dim3(64 * kW2), lds2, a.stream,
+                  static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K), static_cast<const uint16_t*>(a.V), a.O, a.N, nqb2,
+                  a.scale * kLog2e, (unsigned)nwg2);
     }
     return launch_status();
 }
 
 // One (D, X, staging, mask) family of the pipeline: its (input type, output type, folded-first) instantiations.  The families
-// live in translation units of their own (fa_fwd_rp16_{d64,d64n,d64ks,d128,d128w,c,cw}.hip) so that they compile side by side.
-template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
-static hipError_t rp16_family(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
-                              int in_dtype, int out_dtype, bool fold, hipStream_t stream)
+// are explicitly instantiated in translation units of their own (fa_fwd_rp16_{d64,d64n,d64ks,d128,d128w,c,cw}.hip) so that they
+// compile side by side; fa_dispatch.hpp declares the template for fa_fwd_rp16.hip.
+template <int D, int X, bool kDma, bool kCausal, int kWv, int kKeySplit>
+hipError_t rp16_family(const FwdArgs& a, bool fold)
 {
-#define RP16_L(T, OUT, FOLD) launch_rp16<T, D, X, OUT, FOLD, kDma, kCausal, kWv, kKeySplit>(Q, K, V, O, BH, N, scale, stream)
-    if (in_dtype == 0) {
-        if (fold) return out_dtype == 0 ? RP16_L(F16, true, true) : RP16_L(F16, false, true);
-        return out_dtype == 0 ? RP16_L(F16, true, false) : RP16_L(F16, false, false);
-    }
-    if constexpr (!kDma) {   // (the LDS-DMA path cannot convert bf16 K on the way: exact passes only)
-        if (fold) return out_dtype == 0 ? RP16_L(BF16, true, true) : RP16_L(BF16, false, true);
-    }
-    return out_dtype == 0 ? RP16_L(BF16, true, false) : RP16_L(BF16, false, false);
-#undef RP16_L
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        constexpr bool kOutF32 = decltype(f32)::value;
+        // (the LDS-DMA path cannot convert bf16 K on the way: exact passes only)
+        if constexpr (!(kDma && std::is_same<T, BF16>::value)) {
+            if (fold) return launch_rp16<T, D, X, kOutF32, true, kDma, kCausal, kWv, kKeySplit>(a);
+        }
+        return launch_rp16<T, D, X, kOutF32, false, kDma, kCausal, kWv, kKeySplit>(a);
+    });
 }
 
 }  // namespace fa

@@ -33,6 +33,7 @@
 // Lane roles, LDS images, staging and the XCD-aware persistent grid are those of fa_fwd_w64.hip (K row-major,
 // 16-B chunks XOR-swizzled; V in [key/4][d/32] blocks for ds_read_b64_tr_b16).
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -412,22 +413,21 @@ void fa_fwd_sk_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restric
 }
 
 template <typename T, int D, int X, bool kOutF32, bool kFold, bool kSkew>
-static hipError_t launch_sk(const void* Q, const void* K, const void* V, void* O,
-                            int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_sk(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     constexpr int kRows = 32 * X * sk::kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const long long cap = device_cus();
     const unsigned grid = nwg > cap ? (unsigned)cap : (unsigned)nwg;
     auto kern = fa_fwd_sk_kernel<T, D, X, kOutF32, kFold, kSkew>;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 2 * G::kBufBytes);
     if (attr != hipSuccess) return attr;
-    FA_LAUNCH(kern, dim3(grid), dim3(64 * sk::kW), 2 * G::kBufBytes, stream,
-              static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-              static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, (unsigned)nwg,
+    FA_LAUNCH(kern, dim3(grid), dim3(64 * sk::kW), 2 * G::kBufBytes, a.stream,
+              static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+              static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg,
               static_cast<unsigned long long*>(nullptr));
     return launch_status();
 }
@@ -458,31 +458,31 @@ hipError_t sk_diag_dispatch(const void* Q, const void* K, const void* V, void* O
 }
 #endif
 
-// variant (experiments): 0 = shipped (fold for fp16, skew), 1 = no fold, 2 = no skew, 3 = neither
-hipError_t sk_dispatch(const void* Q, const void* K, const void* V, void* O,
-                       int BH, int N, int D, float scale, int in_dtype, int out_dtype, int variant,
-                       hipStream_t stream)
+// variant (experiments): 0 = shipped (fold for fp16, skew), 1 = no fold, 2 = no skew, 3 = neither.  Only fp16 with fp32 output has
+// all four; the other types run the nearest instantiation there is.
+hipError_t sk_dispatch(const FwdArgs& a, int variant)
 {
-    if (D != 64) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + 64 * sk::kW) * (unsigned)D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (!(scale == scale) || scale * kLog2e == 0.0f) variant |= 1;   // NaN / zero scale: the exact pass defines the result
-#define SK_GO(T, OUT, FOLD, SKEW) return launch_sk<T, 64, 2, OUT, FOLD, SKEW>(Q, K, V, O, BH, N, scale, stream)
-    if (in_dtype == 0) {
-        if (out_dtype == 0) {
-            if (variant == 0) SK_GO(F16, true, true, true);
-            if (variant == 1) SK_GO(F16, true, false, true);
-            if (variant == 2) SK_GO(F16, true, true, false);
-            SK_GO(F16, true, false, false);
+    if (a.D != 64) return hipErrorInvalidValue;
+    if ((unsigned long long)(a.N + 64 * sk::kW) * (unsigned)a.D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    if (!(a.scale == a.scale) || a.scale * kLog2e == 0.0f) variant |= 1;   // NaN / zero scale: the exact pass defines the result
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        constexpr bool kF16 = std::is_same<T, F16>::value, kOutF32 = decltype(f32)::value;
+        if constexpr (kF16 && kOutF32) {
+            if (variant == 0) return launch_sk<T, 64, 2, true, true, true>(a);
+            if (variant == 1) return launch_sk<T, 64, 2, true, false, true>(a);
+            if (variant == 2) return launch_sk<T, 64, 2, true, true, false>(a);
+            return launch_sk<T, 64, 2, true, false, false>(a);
+        } else if constexpr (kF16) {
+            if (variant & 1) return launch_sk<T, 64, 2, false, false, true>(a);
+            return launch_sk<T, 64, 2, false, true, true>(a);
+        } else if constexpr (kOutF32) {
+            if (variant & 2) return launch_sk<T, 64, 2, true, false, false>(a);
+            return launch_sk<T, 64, 2, true, false, true>(a);
+        } else {
+            return launch_sk<T, 64, 2, false, false, true>(a);
         }
-        if (variant & 1) SK_GO(F16, false, false, true);
-        SK_GO(F16, false, true, true);
-    }
-    if (out_dtype == 0) {
-        if (variant & 2) SK_GO(BF16, true, false, false);
-        SK_GO(BF16, true, false, true);
-    }
-    SK_GO(BF16, false, false, true);
-#undef SK_GO
+    });
 }
 
 }  // namespace fa

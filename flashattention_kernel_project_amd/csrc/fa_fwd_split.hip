@@ -18,6 +18,7 @@
 // 128-row workgroups (4 waves x 32 rows): query rows >= Nq read zeros and are not stored, so for a
 // handful of query rows most MFMA work is idle lanes -- irrelevant here, the path is HBM-bound.
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <cstdlib>
 
@@ -371,16 +372,13 @@ hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, 
     // per-head byte offsets are 32 bit (fp32 output / workspace rows of D+2 floats)
     if ((unsigned long long)(Nq + split::kRows) * (unsigned)(D + 2) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
     if ((unsigned long long)(Nk + kBlockN) * (unsigned)D * 2ull >= (1ull << 32)) return hipErrorInvalidValue;
-#define FA_SPLIT_GO(TT, DD, OF) return launch_split<TT, DD, OF>(Q, K, V, O, ws, ws_bytes, BH, Nq, Nk, scale, stream)
-    if (D == 64) {
-        if (in_dtype == 0) { if (out_dtype == 0) FA_SPLIT_GO(F16, 64, true); FA_SPLIT_GO(F16, 64, false); }
-        if (out_dtype == 0) FA_SPLIT_GO(BF16, 64, true);
-        FA_SPLIT_GO(BF16, 64, false);
-    }
-    if (in_dtype == 0) { if (out_dtype == 0) FA_SPLIT_GO(F16, 128, true); FA_SPLIT_GO(F16, 128, false); }
-    if (out_dtype == 0) FA_SPLIT_GO(BF16, 128, true);
-    FA_SPLIT_GO(BF16, 128, false);
-#undef FA_SPLIT_GO
+    if (D == 64)
+        return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
+            return launch_split<decltype(t), 64, decltype(f32)::value>(Q, K, V, O, ws, ws_bytes, BH, Nq, Nk, scale, stream);
+        });
+    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
+        return launch_split<decltype(t), 128, decltype(f32)::value>(Q, K, V, O, ws, ws_bytes, BH, Nq, Nk, scale, stream);
+    });
 }
 
 }  // namespace fa

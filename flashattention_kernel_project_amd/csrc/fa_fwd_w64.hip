@@ -14,6 +14,7 @@
 // accumulator registers, optimistic pass without per-tile row max + tracked re-run on overflow,
 // fp32 row sums by v_add, packed fma, persistent grid, XCD-aware item order.
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -385,13 +386,12 @@ void fa_fwd_w64_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restri
 }
 
 template <typename T, int D, int X, bool kOutF32, bool kCausal = false, int kW = w64::kW>
-static hipError_t launch_w64(const void* Q, const void* K, const void* V, void* O,
-                             int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_w64(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     constexpr int kRows = 32 * X * kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const int grid_cap = device_cus();
     const long long cap = (long long)grid_cap * (8 / kW);
@@ -399,20 +399,18 @@ static hipError_t launch_w64(const void* Q, const void* K, const void* V, void* 
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_w64_kernel<T, D, X, kOutF32, kCausal, kW>),
                                            2 * FA_W64_BARRIER_EVERY * G::kBufBytes);
     if (attr != hipSuccess) return attr;
-    FA_LAUNCH((fa_fwd_w64_kernel<T, D, X, kOutF32, kCausal, kW>), dim3(grid), dim3(64 * kW), 2 * FA_W64_BARRIER_EVERY * G::kBufBytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, (unsigned)nwg);
+    FA_LAUNCH((fa_fwd_w64_kernel<T, D, X, kOutF32, kCausal, kW>), dim3(grid), dim3(64 * kW), 2 * FA_W64_BARRIER_EVERY * G::kBufBytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg);
     return launch_status();
 }
 
 template <bool kCausal>
-static hipError_t w64_dispatch_impl(const void* Q, const void* K, const void* V, void* O,
-                                    int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                                    hipStream_t stream)
+static hipError_t w64_dispatch_impl(const FwdArgs& a)
 {
-    if (D != 64 && D != 128) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + 64 * w64::kW) * (unsigned)D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (D == 64) {
+    if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
+    if ((unsigned long long)(a.N + 64 * w64::kW) * (unsigned)a.D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    if (a.D == 64) {
         // under the mask: one 32-row block per wave (256-row workgroups): twice the items to balance, a
         // finer diagonal, and no spills (the two-block causal instantiation is 12 VGPRs over budget)
 #ifndef FA_W64_SMALL
@@ -420,31 +418,13 @@ static hipError_t w64_dispatch_impl(const void* Q, const void* K, const void* V,
 #endif
         constexpr int X = (kCausal || FA_W64_SMALL) ? 1 : 2;
         constexpr int W = (kCausal || FA_W64_SMALL) ? 4 : w64::kW;   // under the mask also 4 waves: 128-row workgroups, two per CU
-        if (in_dtype == 0)
-            return out_dtype == 0 ? launch_w64<F16, 64, X, true, kCausal, W>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_w64<F16, 64, X, false, kCausal, W>(Q, K, V, O, BH, N, scale, stream);
-        return out_dtype == 0 ? launch_w64<BF16, 64, X, true, kCausal, W>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64<BF16, 64, X, false, kCausal, W>(Q, K, V, O, BH, N, scale, stream);
+        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64<decltype(t), 64, X, decltype(f32)::value, kCausal, W>(a); });
     }
-    if (in_dtype == 0)
-        return out_dtype == 0 ? launch_w64<F16, 128, 1, true, kCausal>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64<F16, 128, 1, false, kCausal>(Q, K, V, O, BH, N, scale, stream);
-    return out_dtype == 0 ? launch_w64<BF16, 128, 1, true, kCausal>(Q, K, V, O, BH, N, scale, stream)
-                          : launch_w64<BF16, 128, 1, false, kCausal>(Q, K, V, O, BH, N, scale, stream);
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64<decltype(t), 128, 1, decltype(f32)::value, kCausal>(a); });
 }
 
-hipError_t w64_dispatch(const void* Q, const void* K, const void* V, void* O,
-                        int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                        hipStream_t stream)
-{
-    return w64_dispatch_impl<false>(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);
-}
+hipError_t w64_dispatch(const FwdArgs& a) { return w64_dispatch_impl<false>(a); }
 
-hipError_t w64_causal_dispatch(const void* Q, const void* K, const void* V, void* O,
-                               int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                               hipStream_t stream)
-{
-    return w64_dispatch_impl<true>(Q, K, V, O, BH, N, D, scale, in_dtype, out_dtype, stream);
-}
+hipError_t w64_causal_dispatch(const FwdArgs& a) { return w64_dispatch_impl<true>(a); }
 
 }  // namespace fa

@@ -23,6 +23,7 @@
 // Overflow safety, row sums, output: as fa_fwd_il.hip (optimistic pass against a fixed reference
 // max + exact detection + tracked re-run; fp32 v_add sums; persistent XCD-aware grid).
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -460,13 +461,12 @@ void fa_fwd_w64p_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
 }
 
 template <typename T, int D, int X, bool kOutF32>
-static hipError_t launch_w64p(const void* Q, const void* K, const void* V, void* O,
-                              int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_w64p(const FwdArgs& a)
 {
     using G = TileGeom<D>;
     constexpr int kRows = 32 * X * w64p::kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     static const int grid_cap = [] {
         int dev = 0, cus = 256;
@@ -476,31 +476,20 @@ static hipError_t launch_w64p(const void* Q, const void* K, const void* V, void*
     const unsigned grid = nwg > grid_cap ? (unsigned)grid_cap : (unsigned)nwg;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_w64p_kernel<T, D, X, kOutF32>), w64p::kSlots * G::kBufBytes);
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((fa_fwd_w64p_kernel<T, D, X, kOutF32>), dim3(grid), dim3(64 * w64p::kW),
-                       w64p::kSlots * G::kBufBytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, (unsigned)nwg);
-    return hipGetLastError();
+    FA_LAUNCH((fa_fwd_w64p_kernel<T, D, X, kOutF32>), dim3(grid), dim3(64 * w64p::kW),
+                       w64p::kSlots * G::kBufBytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg);
+    return launch_status();
 }
 
-hipError_t w64p_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                         hipStream_t stream)
+hipError_t w64p_dispatch(const FwdArgs& a)
 {
-    if (D != 64 && D != 128) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + 64 * w64p::kW + 3 * kBlockN) * (unsigned)D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (D == 64) {
-        if (in_dtype == 0)
-            return out_dtype == 0 ? launch_w64p<F16, 64, 2, true>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_w64p<F16, 64, 2, false>(Q, K, V, O, BH, N, scale, stream);
-        return out_dtype == 0 ? launch_w64p<BF16, 64, 2, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64p<BF16, 64, 2, false>(Q, K, V, O, BH, N, scale, stream);
-    }
-    if (in_dtype == 0)
-        return out_dtype == 0 ? launch_w64p<F16, 128, 1, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64p<F16, 128, 1, false>(Q, K, V, O, BH, N, scale, stream);
-    return out_dtype == 0 ? launch_w64p<BF16, 128, 1, true>(Q, K, V, O, BH, N, scale, stream)
-                          : launch_w64p<BF16, 128, 1, false>(Q, K, V, O, BH, N, scale, stream);
+    if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
+    if ((unsigned long long)(a.N + 64 * w64p::kW + 3 * kBlockN) * (unsigned)a.D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    if (a.D == 64)
+        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64p<decltype(t), 64, 2, decltype(f32)::value>(a); });
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64p<decltype(t), 128, 1, decltype(f32)::value>(a); });
 }
 
 }  // namespace fa

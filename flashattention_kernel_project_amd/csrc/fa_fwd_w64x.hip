@@ -17,6 +17,7 @@
 // [key/8][d/16] x [8 keys][16 cols].  Optimistic pass + tracked re-run, v_dot2c row sums, persistent grid
 // as fa_fwd_w64.hip.
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -352,22 +353,21 @@ void fa_fwd_w64x_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restr
 }
 
 template <typename T, int D, int X, bool kOutF32>
-static hipError_t launch_w64x(const void* Q, const void* K, const void* V, void* O,
-                              int BH, int N, float scale, hipStream_t stream)
+static hipError_t launch_w64x(const FwdArgs& a)
 {
     constexpr int lds_bytes = (FA_W64X_MIDBAR ? 6 : 4) * kBlockN * D * 2;   // two (three) [K tile][V tile] buffers
     constexpr int kRows = 16 * X * w64x::kW;
-    const int nqb = (N + kRows - 1) / kRows;
-    const long long nwg = (long long)BH * nqb;
+    const int nqb = (a.N + kRows - 1) / kRows;
+    const long long nwg = (long long)a.BH * nqb;
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const int grid_cap = device_cus();
     const long long cap = (long long)grid_cap * (8 / w64x::kW);
     const unsigned grid = nwg > cap ? (unsigned)cap : (unsigned)nwg;
     const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_w64x_kernel<T, D, X, kOutF32>), lds_bytes);
     if (attr != hipSuccess) return attr;
-    FA_LAUNCH((fa_fwd_w64x_kernel<T, D, X, kOutF32>), dim3(grid), dim3(64 * w64x::kW), lds_bytes, stream,
-                       static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                       static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, (unsigned)nwg);
+    FA_LAUNCH((fa_fwd_w64x_kernel<T, D, X, kOutF32>), dim3(grid), dim3(64 * w64x::kW), lds_bytes, a.stream,
+                       static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg);
     return launch_status();
 }
 
@@ -378,24 +378,13 @@ static hipError_t launch_w64x(const void* Q, const void* K, const void* V, void*
 #define FA_W64X_X128 2   // 16-row blocks per wave at d = 128
 #endif
 
-hipError_t w64x_dispatch(const void* Q, const void* K, const void* V, void* O,
-                         int BH, int N, int D, float scale, int in_dtype, int out_dtype,
-                         hipStream_t stream)
+hipError_t w64x_dispatch(const FwdArgs& a)
 {
-    if (D != 64 && D != 128) return hipErrorInvalidValue;
-    if ((unsigned long long)(N + 64 * w64x::kW) * (unsigned)D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    if (D == 64) {
-        if (in_dtype == 0)
-            return out_dtype == 0 ? launch_w64x<F16, 64, FA_W64X_X64, true>(Q, K, V, O, BH, N, scale, stream)
-                                  : launch_w64x<F16, 64, FA_W64X_X64, false>(Q, K, V, O, BH, N, scale, stream);
-        return out_dtype == 0 ? launch_w64x<BF16, 64, FA_W64X_X64, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64x<BF16, 64, FA_W64X_X64, false>(Q, K, V, O, BH, N, scale, stream);
-    }
-    if (in_dtype == 0)
-        return out_dtype == 0 ? launch_w64x<F16, 128, FA_W64X_X128, true>(Q, K, V, O, BH, N, scale, stream)
-                              : launch_w64x<F16, 128, FA_W64X_X128, false>(Q, K, V, O, BH, N, scale, stream);
-    return out_dtype == 0 ? launch_w64x<BF16, 128, FA_W64X_X128, true>(Q, K, V, O, BH, N, scale, stream)
-                          : launch_w64x<BF16, 128, FA_W64X_X128, false>(Q, K, V, O, BH, N, scale, stream);
+    if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
+    if ((unsigned long long)(a.N + 64 * w64x::kW) * (unsigned)a.D * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    if (a.D == 64)
+        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64x<decltype(t), 64, FA_W64X_X64, decltype(f32)::value>(a); });
+    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) { return launch_w64x<decltype(t), 128, FA_W64X_X128, decltype(f32)::value>(a); });
 }
 
 }  // namespace fa

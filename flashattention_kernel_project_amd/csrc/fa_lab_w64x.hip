@@ -13,6 +13,7 @@
 // The reference's analogue of this file: FlashAttention/flashattn_forward_memory_bound/
 // flashattn_stage_latency_breakdown.cu:181-207 (per-stage clock64 stamps) and flashattn_forward_cp_async_stall.cu:93-206.
 #include "fa_tile.hpp"
+#include "fa_dispatch.hpp"
 
 #include <type_traits>
 #include <utility>

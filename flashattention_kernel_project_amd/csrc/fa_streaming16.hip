@@ -15,6 +15,7 @@
 // These shapes are launch/latency bound (B=1024,L=128 is 134 MFLOP, 10 MB): no LDS staging, the
 // 512-B tiles come straight from L2 with the next tile's loads issued before the current math.
 #include "fa_common.hpp"
+#include "fa_dispatch.hpp"
 
 namespace fa {
 

@@ -146,7 +146,7 @@ int fa_selected_algo(int B, int H, int N, int d, int in_dtype);
 const char* fa_selected_kernel(int B, int H, int N, int d, int in_dtype, int algo);
 
 /* 1 when the library was built with the experimental A/B kernels (`make experimental`: explicit algo ids
- * 3, 4, 7-12, 14, 15 and the measurement entry points), 0 for the product build, where those ids return
+ * 7, 8, 13, 14, 16-22, 25 and the measurement entry points), 0 for the product build, where those ids return
  * hipErrorInvalidValue. */
 int fa_mi355_has_experiments(void);
 

@@ -60,6 +60,95 @@ def test_invalid_arguments_rejected_without_device(fa):
     assert L.flashattn_streaming_16x16_mw_kt(p, p, p, p, 4, 0, 0.25, None) == INVALID
 
 
+# The algo contract, stated apart from the library's table (csrc/fa_fwd_kernels.hip, kAlgos):
+#   id: (only in the experimental build, D accepted by fa_forward_ex, D accepted by fa_forward_causal)
+_ANY_D = (16, 32, 64, 128, 256)          # stands for every D % 16 == 0 up to 256
+_D_PROBED = _ANY_D
+_ALGO_CONTRACT = {
+    1: (False, _ANY_D, _ANY_D),
+    2: (False, (64, 128), (64, 128)),
+    5: (False, (64,), ()),
+    6: (False, (64,), (64, 128)),        # under the mask: the tiled kernel on 128-row workgroups
+    7: (True, (64,), ()),
+    8: (True, (64,), ()),
+    13: (True, (64, 128), (64, 128)),
+    14: (True, (64, 128), ()),
+    16: (True, (64, 128), ()),
+    17: (True, (64,), ()),
+    18: (True, (64,), ()),
+    19: (True, (64,), ()),
+    20: (True, (64,), ()),
+    21: (True, (64, 128), ()),
+    22: (True, (64, 128), ()),
+    23: (False, (64, 128), ()),
+    24: (False, (64, 128), (64, 128)),
+    25: (True, (64,), ()),
+    26: (False, (64, 128), ()),
+    27: (False, (64,), ()),
+    28: (False, (128,), (128,)),
+    29: (False, (64,), ()),
+}                                         # 3, 4, 9-12, 15 were removed; nothing above 29 exists
+
+
+def _header_algo_ids():
+    """{FA_ALGO_* name: (id, listed under the header's experimental-build block)}"""
+    text = open(os.path.join(ROOT, "include", "fa_mi355.h")).read()
+    cut = text.index("Only in the experimental build")
+    return {m.group(1): (int(m.group(2)), m.start() > cut) for m in re.finditer(r"#define\s+(FA_ALGO_\w+)\s+(\d+)", text)}
+
+
+def _algo_libraries(fa):
+    """The loaded product library and, when it is built, the experimental one."""
+    libs = [fa.lib()]
+    exp = os.path.join(os.path.dirname(fa.capi.LIB_PATH), "libfa_mi355_exp.so")
+    if os.path.exists(exp) and os.path.abspath(exp) != os.path.abspath(fa.capi.LIB_PATH):
+        L = ctypes.CDLL(exp)
+        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.fa_forward_ex.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]
+        L.fa_forward_causal.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]
+        L.fa_selected_kernel.argtypes = [i, i, i, i, i, i]
+        L.fa_selected_kernel.restype = ctypes.c_char_p
+        libs.append(L)
+    return libs
+
+
+def test_algo_contract_rejections_without_device(fa):
+    """Every (algo id, D, plain / causal) the contract forbids is rejected, every id a library accepts names its kernel, and
+    include/fa_mi355.h names the same ids.  Only calls that must be rejected are issued (safe where a GPU is visible)."""
+    INVALID = 1  # hipErrorInvalidValue
+    p = ctypes.c_void_p(16)
+    header = _header_algo_ids()
+    for L in _algo_libraries(fa):
+        have_exp = L.fa_mi355_has_experiments() == 1
+        for algo in list(range(-2, 0)) + list(range(1, 41)) + [99, 1 << 20]:
+            exp_only, d_plain, d_causal = _ALGO_CONTRACT.get(algo, (False, (), ()))
+            present = algo in _ALGO_CONTRACT and (have_exp or not exp_only)
+            for D in _D_PROBED:
+                for dt in (0, 1):
+                    if not (present and D in d_plain):
+                        assert L.fa_forward_ex(p, p, p, p, 1, 2, 256, D, 0.125, dt, 0, algo, None) == INVALID, (algo, D, dt)
+                    if not (present and D in d_causal):
+                        assert L.fa_forward_causal(p, p, p, p, 1, 2, 256, D, 0.125, dt, 0, algo, None) == INVALID, (algo, D, dt)
+            if present:
+                for D in d_plain:
+                    assert L.fa_selected_kernel(1, 2, 256, D, 0, algo), (algo, D)
+        # ids 7 / 8 exist for fp16 with fp32 output only
+        if have_exp:
+            for algo in (7, 8):
+                assert L.fa_forward_ex(p, p, p, p, 1, 2, 256, 64, 0.125, 1, 0, algo, None) == INVALID
+                assert L.fa_forward_ex(p, p, p, p, 1, 2, 256, 64, 0.125, 0, 1, algo, None) == INVALID
+        # the header and the contract name the same ids, each on its side of the experimental-build block
+        for name, (algo, in_exp_block) in header.items():
+            if name == "FA_ALGO_AUTO":
+                assert algo == 0
+                continue
+            assert algo in _ALGO_CONTRACT, name
+            assert _ALGO_CONTRACT[algo][0] == in_exp_block, name
+    product_ids = {a for a, c in _ALGO_CONTRACT.items() if not c[0]}
+    assert {a for a, e in header.values() if not e} == product_ids | {0}
+    assert fa.capi.ALGO_RP16_DMA == header["FA_ALGO_RP16_DMA"][0] == 25
+
+
 def test_ops_refuse_cpu_tensors(fa):
     torch = pytest.importorskip("torch")
     q = torch.zeros(1, 128, 64, dtype=torch.float16)
