@@ -32,6 +32,8 @@ SYMBOLS = (
     "fa_mi355_has_experiments",
     "fa_selected_algo",
     "fa_selected_kernel",
+    "fa_forward_kvcache_workspace_bytes",
+    "fa_forward_kvcache",
 )
 
 
@@ -98,6 +100,10 @@ def lib() -> C.CDLL:
         L.fa_selected_kernel.argtypes = [i, i, i, i, i, i]
         L.fa_selected_kernel.restype = C.c_char_p
         L.fa_forward_splitkv_workspace_bytes.restype = C.c_size_t
+        L.fa_forward_kvcache.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache.restype = C.c_int
+        L.fa_forward_kvcache_workspace_bytes.argtypes = [i, i, i, i, i, i]
+        L.fa_forward_kvcache_workspace_bytes.restype = C.c_size_t
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

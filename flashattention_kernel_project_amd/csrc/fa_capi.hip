@@ -95,6 +95,19 @@ FA_EXPORT int fa_forward_splitkv(const void* Q, const void* K, const void* V, vo
                                    static_cast<hipStream_t>(stream));
 }
 
+FA_EXPORT size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d)
+{
+    return fa::kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d);
+}
+
+FA_EXPORT int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse, const int* seqlens_k,
+                       int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal,
+                       int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvcache_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                      workspace, workspace_bytes, static_cast<hipStream_t>(stream)});
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

@@ -59,10 +59,27 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
+int split_count(int BH, int Nq, int Nk);   // number of key splits for a shape: from the shape alone (a fixed workgroup target), no device query
+// KV-cache decode (fa_forward_kvcache): Q, O [B, Hkv*G, Nq, D], K, V [B, Hkv, Ncap, D]; seqlens (device, B int32) and lse (device,
+// [B, Hkv*G, Nq] fp32) may be null; ws as for split_dispatch, sized by kvcache_workspace_bytes().
+struct KvCacheArgs {
+    const void *Q, *K, *V;
+    void* O;
+    float* lse;
+    const int* seqlens;
+    int B, Hkv, G, Nq, Ncap, D;
+    float scale;
+    int causal, in_dtype, out_dtype;
+    void* ws;
+    size_t ws_bytes;
+    hipStream_t stream;
+};
+hipError_t kvcache_dispatch(const KvCacheArgs& a);
+size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

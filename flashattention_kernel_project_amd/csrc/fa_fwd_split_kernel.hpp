@@ -1,0 +1,351 @@
+// fa_fwd_split_kernel.hpp -- device code of the split-KV stream, shared by fa_fwd_split.hip (fa_forward_splitkv) and
+// fa_fwd_kvcache.hip (fa_forward_kvcache).  One kernel template serves both: what the KV-cache entry adds is a template flag and
+// a trailing parameter pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt).
+// The two sets are instantiated in separate translation units so that neither perturbs the other's register allocation.
+// The design notes are at the head of fa_fwd_split.hip and in DESIGN.md 7.1.
+#pragma once
+#include "fa_tile.hpp"
+
+namespace fa {
+
+#ifndef FA_SPLIT_ROTATE
+#define FA_SPLIT_ROTATE 1
+#endif
+#ifndef FA_SPLIT_NT
+#define FA_SPLIT_NT 1   // K/V are read exactly once: non-temporal loads (5.97 -> 6.75 TB/s at B8 H16 Nq1 Nk32768 d128)
+#endif
+namespace split {
+constexpr int kW = 4;                 // waves per workgroup
+constexpr int kRows = 32 * kW;        // query rows per workgroup
+}  // namespace split
+constexpr float kLn2 = 0.6931471805599453f;
+
+// What the KV-cache instantiations (kCache) take as their trailing argument; the plain split kernels have no such argument.
+struct CacheArgs {
+    const int* seqlens;   // [B] key counts on the device, or nullptr: every sequence holds Nk keys
+    float* lse;           // [BH][Nq] natural-log sum of exponentials, or nullptr
+    int Hkv;              // K/V heads per batch entry: bh / Hkv indexes seqlens
+    int Nq1;              // query rows per query head (the Nq rows of a K/V head are G folded heads of Nq1 rows)
+    int causal;           // row i of its head sees the keys [0, L - Nq1 + 1 + i)
+};
+
+// kPartial: write (O^T unnormalised, m, l) to the workspace instead of the normalised output.
+// kCache: the key count L of the head's sequence is read on the device (Nk is then the capacity, the stride of a K/V head) and the
+// split's chunk follows from L; every row has its own key limit; a row or a split without a key is neutral (m = -inf, l = 0, O = 0).
+// With kCache false all of that compiles out and the kernel has the plain argument list (`cache` is empty).
+// Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
+// instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
+// allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
+// instruction (profiles/kvcache_decode.txt).  Do not simplify this without repeating that comparison.  The same holds for `Lse...`
+// of the merge kernel below.
+template <typename T, int D, bool kOutF32, bool kPartial, bool kCache = false, typename... Cache>
+__global__ __launch_bounds__(64 * split::kW, D == 64 ? 4 : 2)
+void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __restrict__ Kg,
+                         const uint16_t* __restrict__ Vg, void* __restrict__ Og, float* __restrict__ ws,
+                         int Nq, int Nk, int nqb, int S, int chunk, float scale_log2e, Cache... cache)
+{
+    static_assert(sizeof...(Cache) == (kCache ? 1 : 0), "the KV-cache instantiations take one CacheArgs, the plain ones nothing");
+    [[maybe_unused]] const CacheArgs ca = {cache...};
+    using namespace split;
+    using G = TileGeom<D>;
+    constexpr int W = kW;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    // block -> (head, query block, split): the splits of one (head, query block) are consecutive
+    const unsigned sp = blockIdx.x % (unsigned)S;
+    const unsigned rest = blockIdx.x / (unsigned)S;
+    const unsigned bh = rest / (unsigned)nqb, qb = rest % (unsigned)nqb;
+
+    const unsigned tid  = threadIdx.x;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned lane = tid & 63u;
+    const unsigned r = lane & 31u, h = lane >> 5;
+
+    unsigned nkeys = (unsigned)Nk;   // keys of this head
+    if constexpr (kCache) {
+        // the clamp keeps a bad length inside the cache; the tiles of THIS sequence are dealt out to the S splits
+        if (ca.seqlens) nkeys = (unsigned)min(max(ca.seqlens[bh / (unsigned)ca.Hkv], 0), Nk);
+        chunk = (int)(((nkeys + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
+    }
+    const unsigned key0 = sp * (unsigned)chunk;                       // multiple of kBlockN
+    const unsigned key1 = min(nkeys, key0 + (unsigned)chunk);         // exclusive
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc(Qg + (size_t)bh * Nq * D, (unsigned)((size_t)Nq * D * 2));
+    // K/V descriptors end at this split's last key: rows beyond it read 0 and are masked below
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kg + (size_t)bh * Nk * D, key1 * (unsigned)D * 2u);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(Vg + (size_t)bh * Nk * D, key1 * (unsigned)D * 2u);
+
+    constexpr int kLoadsW = (kBlockN * G::kChunks) / (64 * W);
+    const unsigned q_row = qb * (unsigned)kRows + wave * 32u + r;
+    const bool has_rows = qb * (unsigned)kRows + wave * 32u < (unsigned)Nq;   // wave-uniform
+
+    // first key a row does NOT see, and the smallest such limit of any row (tiles that end at or below it need no mask)
+    [[maybe_unused]] unsigned lim = key1, lim_lo = key1;
+    if constexpr (kCache) {
+        if (ca.causal) {
+            const int first = (int)nkeys - ca.Nq1 + 1;   // limit of row 0 of a head; may be <= 0
+            lim = min((unsigned)max(first + (int)(q_row % (unsigned)ca.Nq1), 0), key1);
+            lim_lo = min((unsigned)max(first, 0), key1);
+        }
+    }
+
+    // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf
+    const float c = kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
+    const unsigned q_flip = scale_log2e < 0.0f ? 0x80008000u : 0u;
+    u32x4 qf[G::kKSteps];
+#pragma unroll
+    for (int s = 0; s < G::kKSteps; ++s) {
+        u32x4 raw = buf_load16(rq, q_row * G::kRowBytes + (16u * s + 8u * h) * 2u);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) raw[w] ^= q_flip;
+        qf[s] = raw;
+    }
+
+    unsigned g_off[kLoadsW], k_lds[kLoadsW], v_lds[kLoadsW];
+#pragma unroll
+    for (int p = 0; p < kLoadsW; ++p) {
+        const unsigned idx = tid + p * 64u * W;
+        const unsigned row = idx / G::kChunks, ch = idx % G::kChunks;
+        g_off[p] = row * G::kRowBytes + ch * 16u;
+        k_lds[p] = G::k_off(row, ch);
+        v_lds[p] = G::kTileBytes + G::v_off(row, ch);
+    }
+    u32x4 kst[kLoadsW], vst[kLoadsW];
+    auto stage_load = [&](unsigned kv0) {
+#pragma unroll
+        for (int p = 0; p < kLoadsW; ++p) {
+#if FA_SPLIT_NT
+            kst[p] = buf_load16_nt(rk, kv0 * G::kRowBytes + g_off[p]);
+            vst[p] = buf_load16_nt(rv, kv0 * G::kRowBytes + g_off[p]);
+#else
+            kst[p] = buf_load16(rk, kv0 * G::kRowBytes + g_off[p]);
+            vst[p] = buf_load16(rv, kv0 * G::kRowBytes + g_off[p]);
+#endif
+        }
+    };
+    auto stage_write = [&](unsigned buf) {
+#pragma unroll
+        for (int p = 0; p < kLoadsW; ++p) {
+            lds_write16(smem, buf * G::kBufBytes + k_lds[p], kst[p]);
+            lds_write16(smem, buf * G::kBufBytes + v_lds[p], vst[p]);
+        }
+    };
+
+    const unsigned k_rd_row = r * G::kRowBytes;
+    const unsigned k_rd_swz = G::k_swz(r);
+    const unsigned i16 = lane & 15u, vq = i16 >> 2, vp = i16 & 3u, vg = (lane >> 4) & 1u;
+    unsigned v_rd[2];
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+        v_rd[par] = G::kTileBytes + h * G::kDBlocks * 256u + ((vq ^ par) << 6) + vg * 32u + vp * 8u;
+
+    f32x16 o[G::kDBlocks];
+    f32x16 zero16;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) zero16[i] = 0.0f;
+#pragma unroll
+    for (int db = 0; db < G::kDBlocks; ++db) o[db] = zero16;
+    float m_ref = kCache ? -INFINITY : 0.0f, l_part = 0.0f;
+
+    // >= 1 by construction of S; kCache: 0 for a split that lies past the sequence's last key, which touches no K/V
+    const int ntiles = (kCache && key0 >= nkeys) ? 0 : (int)((key1 - key0 + kBlockN - 1) / kBlockN);
+    // Tiles are visited in a rotated order that differs per (head, split): the chunks of one head start a
+    // power-of-two stride apart, and workgroups marching through them in lockstep would keep hitting the
+    // same few HBM channels.  The streaming softmax does not care about the order.
+    const unsigned rot = FA_SPLIT_ROTATE ? (sp * 5u + bh * 3u) % (unsigned)(kCache ? max(ntiles, 1) : ntiles) : 0u;
+    auto tile_of = [&](int t) { const unsigned ti = (unsigned)t + rot; return ti >= (unsigned)ntiles ? ti - (unsigned)ntiles : ti; };
+    if (!kCache || ntiles > 0) {   // workgroup-uniform
+        stage_load(key0 + tile_of(0) * kBlockN);
+        stage_write(0);
+        __syncthreads();
+    }
+
+    for (int t = 0; t < ntiles; ++t) {
+        const unsigned cur = t & 1u;
+        const char* kbuf = smem + cur * G::kBufBytes;
+        const unsigned kv0 = key0 + tile_of(t) * kBlockN;
+        if (t + 1 < ntiles) stage_load(key0 + tile_of(t + 1) * kBlockN);
+
+        // a wave whose 32 rows all lie past Nq (the usual case for a handful of query rows) only stages
+        if (has_rows) {
+        f32x16 s[2];
+#pragma unroll
+        for (int ks = 0; ks < G::kKSteps; ++ks)   // consecutive MFMAs alternate accumulators
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const u32x4 kf = lds_read16(kbuf, kb * 32u * G::kRowBytes + k_rd_row + (((2u * ks + h) ^ k_rd_swz) << 4));
+                s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
+            }
+        if (kv0 + kBlockN > (kCache ? lim_lo : key1)) {   // keys past the split's end (kCache: past the row's limit) -> -inf (p = 0)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const unsigned key = kv0 + (unsigned)(kb * 32 + (i & 3) + 8 * (i >> 2)) + 4u * h;
+                    if (key >= (kCache ? lim : key1)) s[kb][i] = -INFINITY;
+                }
+        }
+
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 32; e += 2) tmax = max3(tmax, s[e >> 4][e & 15], s[(e + 1) >> 4][(e + 1) & 15]);
+        tmax *= c;
+        // kCache: a tile can be fully masked for a row, in any position of the rotated order, so m_ref starts at -inf and stays
+        // there until the row meets a key.  The vote is written without a difference (-inf - -inf), and a row whose m_ref is
+        // -inf takes alpha = 0 instead of 2^(-inf + inf); a first live key always wins the vote (tmax > -inf).
+        if (kCache ? __any(tmax > m_ref + kThr) : (t == 0 || __any(tmax - m_ref > kThr))) {
+            const float mx = fmaxf(tmax, swap_halves(tmax));
+            const float m_new = (!kCache && t == 0) ? mx : fmaxf(mx, m_ref);
+            const float alpha = (kCache ? m_ref == -INFINITY : t == 0) ? 0.0f : fast_exp2(m_ref - m_new);
+            m_ref = m_new;
+#pragma unroll
+            for (int db = 0; db < G::kDBlocks; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
+            l_part *= alpha;
+        }
+
+        u32x4 pk[4];
+        float ls0 = 0.0f, ls1 = 0.0f;
+        const float neg_m = (kCache && m_ref == -INFINITY) ? 0.0f : -m_ref;   // every s of such a row is -inf: p = 2^(-inf + 0) = 0
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int kb = q4 >> 1, b8 = (q4 & 1) * 8;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const float p0 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w], c, neg_m));
+                const float p1 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w + 1], c, neg_m));
+                pk[q4][w] = T::pack2(p0, p1);
+                if (w & 1) ls1 = T::sum2(pk[q4][w], ls1);   // sums of the ROUNDED weights (fa_common.hpp)
+                else ls0 = T::sum2(pk[q4][w], ls0);
+            }
+        }
+        l_part += ls0 + ls1;
+
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+            for (int db = 0; db < G::kDBlocks; ++db) {
+                u32x4 vf;
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    const u32x2 half = lds_read_tr8(kbuf, v_rd[db & 1] + ((4u * ks + 2u * jj) * G::kDBlocks + db) * 256u);
+                    vf[2 * jj] = half[0];
+                    vf[2 * jj + 1] = half[1];
+                }
+                o[db] = T::mfma32(vf, pk[ks], o[db]);
+            }
+        }   // has_rows
+
+        if (t + 1 < ntiles) stage_write(cur ^ 1u);
+        __syncthreads();
+    }
+
+    const float l = l_part + swap_halves(l_part);
+    if constexpr (kPartial) {
+        // workspace row (bh, sp, q_row): D floats of O^T (unnormalised), then m, then l
+        const size_t rows = (size_t)Nq;
+        const unsigned rs = (unsigned)(D + 2) * 4u;
+        const __amdgpu_buffer_rsrc_t rw =
+            make_rsrc(ws + ((size_t)bh * S + sp) * rows * (D + 2), (unsigned)(rows * rs));
+#pragma unroll
+        for (int db = 0; db < G::kDBlocks; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const unsigned col = db * 32u + 8u * g + 4u * h;
+                // scalar copies first: __builtin_bit_cast applied to an ext-vector ELEMENT reads element 0
+                const float a = o[db][4 * g], b = o[db][4 * g + 1], cc = o[db][4 * g + 2], d = o[db][4 * g + 3];
+                // rows are (D+2)*4 bytes: 8-byte aligned, not 16 -> two 8-byte stores
+                buf_store8(rw, q_row * rs + col * 4u, u32x2{__float_as_uint(a), __float_as_uint(b)});
+                buf_store8(rw, q_row * rs + col * 4u + 8u, u32x2{__float_as_uint(cc), __float_as_uint(d)});
+            }
+        if (h == 0)
+            buf_store8(rw, q_row * rs + (unsigned)D * 4u, u32x2{__float_as_uint(m_ref), __float_as_uint(l)});
+    } else {
+        const float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        if constexpr (kCache) {
+            if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
+                buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), q_row * 4u,
+                           __float_as_uint(l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2));
+        }
+        constexpr unsigned es = kOutF32 ? 4u : 2u;
+        const __amdgpu_buffer_rsrc_t ro =
+            make_rsrc(reinterpret_cast<char*>(Og) + (size_t)bh * Nq * D * es, (unsigned)((size_t)Nq * D * es));
+#pragma unroll
+        for (int db = 0; db < G::kDBlocks; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const unsigned col = db * 32u + 8u * g + 4u * h;
+                const float a = o[db][4 * g] * inv, b = o[db][4 * g + 1] * inv;
+                const float cc = o[db][4 * g + 2] * inv, d = o[db][4 * g + 3] * inv;
+                if constexpr (kOutF32) {
+                    const f32x4 v = {a, b, cc, d};
+                    buf_store16(ro, (q_row * D + col) * 4u, __builtin_bit_cast(u32x4, v));
+                } else {
+                    buf_store8(ro, (q_row * D + col) * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
+                }
+            }
+    }
+}
+
+// One wave per (bh, row).  Lane = (slice, 4 output columns): the D/4 column groups times 64/(D/4) slices of
+// the split axis, so that the S partials of a row are read by parallel lanes with independent loads instead
+// of one lane walking them (a serial walk costs ~0.25 us per partial: 64 us at S = 128).
+// kCache: a partial with m = -inf is neutral (weight 0, not 2^(-inf + inf)), a row of neutral partials gives O = 0, and the
+// trailing float* argument (may be nullptr) receives ln(sum of exponentials) = (M + log2 L) ln 2.
+template <typename T, bool kOutF32, bool kCache = false, typename... Lse>
+__global__ __launch_bounds__(64)
+void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og, int BH, int Nq, int D, int S, Lse... lse_arg)
+{
+    static_assert(sizeof...(Lse) == (kCache ? 1 : 0), "the KV-cache instantiations take the lse pointer, the plain ones nothing");
+    [[maybe_unused]] float* const lse = {lse_arg...};
+    const int cols4 = D / 4;             // 16 or 32
+    const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
+    const unsigned lane = threadIdx.x;
+    const int c4 = (int)lane % cols4, sl = (int)lane / cols4;
+    const long long rowi = blockIdx.x;   // bh * Nq + row
+    const int row = (int)(rowi % Nq);
+    const int bh = (int)(rowi / Nq);
+    const size_t stride_s = (size_t)Nq * (D + 2);
+    const float* base = ws + (size_t)bh * S * stride_s + (size_t)row * (D + 2);
+    // global reference max: every lane takes splits lane, lane+64, ...
+    float M = -INFINITY;
+    for (int s = (int)lane; s < S; s += 64) M = fmaxf(M, base[(size_t)s * stride_s + D]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+    float L = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+    for (int s = sl; s < S; s += nsl) {
+        const float* p = base + (size_t)s * stride_s;
+        const float w = (kCache && p[D] == -INFINITY) ? 0.0f : fast_exp2(p[D] - M);
+        L += p[D + 1] * w;
+        // workspace rows are (D+2)*4 bytes: 8-byte aligned, so two 8-byte loads
+        const float2 v0 = *reinterpret_cast<const float2*>(p + 4 * c4), v1 = *reinterpret_cast<const float2*>(p + 4 * c4 + 2);
+        acc[0] += v0.x * w;
+        acc[1] += v0.y * w;
+        acc[2] += v1.x * w;
+        acc[3] += v1.y * w;
+    }
+    // sum the slices: lanes that differ only in `sl` are cols4, 2*cols4, ... apart
+    for (int o = cols4; o < 64; o <<= 1) {
+        L += __shfl_xor(L, o, 64);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
+    }
+    if (sl != 0) return;
+    const float inv = (kCache && L == 0.0f) ? 0.0f : 1.0f / L;
+    if constexpr (kCache) {
+        if (lse && lane == 0) lse[rowi] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
+    }
+    const size_t off = ((size_t)bh * Nq + row) * D + 4 * c4;
+    if constexpr (kOutF32) {
+        float* o = static_cast<float*>(Og) + off;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = acc[i] * inv;
+    } else {
+        unsigned* o = reinterpret_cast<unsigned*>(static_cast<uint16_t*>(Og) + off);
+        o[0] = T::pack2(acc[0] * inv, acc[1] * inv);
+        o[1] = T::pack2(acc[2] * inv, acc[3] * inv);
+    }
+}
+
+}  // namespace fa

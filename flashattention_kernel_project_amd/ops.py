@@ -128,8 +128,7 @@ def fa_forward_splitkv(q, k, v, scale: float | None = None, out_dtype=None, work
     if out_dtype not in (torch.float32, q.dtype):
         raise ValueError("out_dtype must be torch.float32 or the input dtype")
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    with torch.cuda.device(q.device):   # the split count follows the CU count of the device that will run it
-        need = splitkv_workspace_bytes(B, H, rows, Nk, d)
+    need = splitkv_workspace_bytes(B, H, rows, Nk, d)   # from the shape alone: the split count reads no device property
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
@@ -147,6 +146,60 @@ def fa_forward_splitkv(q, k, v, scale: float | None = None, out_dtype=None, work
 
 def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
     return int(capi.lib().fa_forward_splitkv_workspace_bytes(B, H, Nq, Nk, d))
+
+
+def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = False, scale: float | None = None,
+                       out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+    """Decode against a pre-allocated cache (fa_forward_kvcache): q [B,Hq,Nq,d], k_cache/v_cache [B,Hkv,Ncap,d]
+    fp16/bf16 device tensors, d in {64,128}, Hq a multiple of Hkv (the group's K/V is streamed once, as in
+    fa_forward_splitkv).
+    cache_seqlens: int32 contiguous device tensor [B], the keys each sequence holds (None: Ncap for all).  It is read on
+    the device only, so a call captured into a graph follows lengths that are later changed in place.
+    causal: row i sees the keys [0, L_b - Nq + 1 + i) -- the last query row sees the whole sequence.
+    A row that sees no key returns zeros (and lse = -inf).
+    return_lse: also return the fp32 [B,Hq,Nq] natural-log sum of exponentials, for merging results over key ranges.
+    workspace: optional uint8 device tensor of at least kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)."""
+    import torch
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
+            or q.shape[3] != k_cache.shape[3]:
+        raise ValueError("q must be [B,Hq,Nq,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
+    B, Hq, Nq, d = q.shape
+    Hkv, Ncap = k_cache.shape[1], k_cache.shape[2]
+    if Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
+    G = Hq // Hkv
+    dts = (torch.float16, torch.bfloat16)
+    if q.dtype not in dts or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("q, k_cache, v_cache must all be fp16 or all bf16")
+    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    len_ptr = None
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
+            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
+        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_cache, "k_cache", dts), _dev_ptr(v_cache, "v_cache", dts))
+    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+    need = kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)   # from the shape alone: the split count reads no device property
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    with torch.cuda.device(_one_device(q, k_cache, v_cache, cache_seqlens, workspace)):
+        code = capi.lib().fa_forward_kvcache(
+            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, B, Hkv, G, Nq, Ncap, d, float(scale),
+            1 if causal else 0, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
+            ws_ptr, ws_len, _stream_ptr(stream))
+    capi.check("fa_forward_kvcache", code)
+    return (out, lse) if return_lse else out
+
+
+def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int) -> int:
+    return int(capi.lib().fa_forward_kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d))
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

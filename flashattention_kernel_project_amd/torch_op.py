@@ -7,6 +7,7 @@ eager fallback.  Registered on first use:
     from flashattention_kernel_project_amd.torch_op import register
     register()
     o = torch.ops.fa_mi355.forward(q, k, v, scale, causal, out_fp32)
+    o = torch.ops.fa_mi355.decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward (idempotent)."""
+    """Define torch.ops.fa_mi355.forward and torch.ops.fa_mi355.decode (idempotent)."""
     global _registered
     if _registered:
         return
@@ -32,6 +33,19 @@ def register() -> None:
 
     @forward.register_fake
     def _(q, k, v, scale, causal, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
+                                    "bool out_fp32) -> Tensor")
+    def decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
+                                      None if cache_seqlens is None else cache_seqlens.contiguous(), causal=causal, scale=scale,
+                                      out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
+
+    @decode.register_fake
+    def _(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
         return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
 
     _registered = True

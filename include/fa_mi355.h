@@ -109,6 +109,32 @@ int fa_forward_splitkv(const void* Q, const void* K, const void* V, void* O,
                        int B, int H, int Nq, int Nk, int d, float scale,
                        int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Decode against a pre-allocated KV cache: fa_forward_splitkv with a key count PER SEQUENCE that is read on
+ * the device, an optional causal mask aligned to the end of the cache, and an optional log-sum-exp output.
+ *   Q, O            [B, Hkv*G, Nq, d]; query head hkv*G + g uses K/V head hkv (G = 1: plain multi-head)
+ *   Kcache, Vcache  [B, Hkv, Ncap, d] contiguous, fp16 or bf16; d in {64,128}
+ *   seqlens_k       device, B int32, or NULL (every sequence holds Ncap keys).  L_b = min(max(seqlens_k[b], 0), Ncap):
+ *                   a bad length is clamped and never becomes an out-of-range read.  Rows at and past L_b are not read.
+ *   causal = 0      row i of batch b attends to the keys [0, L_b)
+ *   causal = 1      row i attends to [0, c_i), c_i = max(0, L_b - Nq + 1 + i): the LAST query row sees the whole
+ *                   cache (i counts within the row's own head)
+ *   lse             device, [B, Hkv*G, Nq] fp32, or NULL: ln sum_j exp(scale * q.k_j) over the keys the row sees
+ * A row that sees no key (L_b = 0 or c_i = 0) gets O = 0 and lse = -inf, never NaN.  With lse, results over
+ * disjoint key ranges (another chunk, another device) merge exactly: O = sum_r O_r exp(lse_r - lse), lse = ln sum_r exp(lse_r).
+ * Nothing on the host reads seqlens_k: grid, split count and workspace size depend on (B, Hkv, G, Nq, Ncap, d) only,
+ * so a call captured into a HIP graph replays correctly after the lengths were changed in place.  The keys of a
+ * sequence are divided among its splits by L_b, not by Ncap: a cache filled to a fraction still uses every split.
+ * Workspace as for fa_forward_splitkv (size from fa_forward_kvcache_workspace_bytes(); 0: `workspace` may be NULL).
+ * Paged (block-table) caches, sliding windows and appending to the cache are not part of this entry.
+ * NOT a reference entry point. */
+size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d);
+int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, void* O,
+                       float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                       const int* seqlens_k,  /* device, B int32, may be NULL (= Ncap for all) */
+                       int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal,
+                       int in_dtype, int out_dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
  * the same LDS images, fragment loads and accumulator maps as the product kernels.  d in {64,128}.

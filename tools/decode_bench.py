@@ -3,6 +3,10 @@
 occupy (the path is HBM-bound: every K and V byte is read once).
 
     python tools/decode_bench.py --B 8 --H 16 --Nq 1 --Nk 32768 --d 128
+    python tools/decode_bench.py --kvcache --fill 0.25          # fa_forward_kvcache: a 32768-row cache holding 8192 keys per sequence
+
+--kvcache times fa_forward_kvcache against a cache of --Nk rows in which every sequence holds --fill x Nk keys (the lengths live
+in a device tensor); GB/s then counts the K and V bytes of the keys held, not of the capacity.  --causal adds the mask.
 """
 import argparse
 import os
@@ -21,29 +25,48 @@ def main():
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--kvcache", action="store_true", help="fa_forward_kvcache with per-sequence lengths instead of fa_forward_splitkv")
+    ap.add_argument("--fill", type=float, default=1.0, help="with --kvcache: every sequence holds FILL * Nk keys")
+    ap.add_argument("--causal", action="store_true", help="with --kvcache: the causal mask aligned to the end of the cache")
     args = ap.parse_args()
     import torch
     import flashattention_kernel_project_amd as fa
     g = torch.Generator(device="cuda").manual_seed(0)
     q = torch.randn(args.B, args.H, args.Nq, args.d, generator=g, device="cuda").half()
     k, v = (torch.randn(args.B, args.H, args.Nk, args.d, generator=g, device="cuda").half() for _ in range(2))
-    need = fa.splitkv_workspace_bytes(args.B, args.H, args.Nq, args.Nk, args.d)
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
+    if not args.kvcache and (args.fill != 1.0 or args.causal):
+        ap.error("--fill and --causal need --kvcache")
+    if args.kvcache:
+        held = min(max(int(round(args.fill * args.Nk)), 0), args.Nk)
+        lens = torch.full((args.B,), held, dtype=torch.int32, device="cuda")
+        need = fa.kvcache_workspace_bytes(args.B, args.H, 1, args.Nq, args.Nk, args.d)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
+
+        def call():
+            fa.fa_forward_kvcache(q, k, v, lens, causal=args.causal, workspace=ws)
+    else:
+        held = args.Nk
+        need = fa.splitkv_workspace_bytes(args.B, args.H, args.Nq, args.Nk, args.d)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
+
+        def call():
+            fa.fa_forward_splitkv(q, k, v, workspace=ws)
     for _ in range(3):
-        fa.fa_forward_splitkv(q, k, v, workspace=ws)
+        call()
     torch.cuda.synchronize()
     times = []
     for _ in range(args.rounds):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.iters):
-            fa.fa_forward_splitkv(q, k, v, workspace=ws)
+            call()
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1) / args.iters)
     med = statistics.median(times)
-    kv_bytes = 2.0 * args.B * args.H * args.Nk * args.d * 2
-    print(f"B{args.B} H{args.H} Nq{args.Nq} Nk{args.Nk} d{args.d}: workspace {need} B, median {med * 1e3:.1f} us, "
+    kv_bytes = 2.0 * args.B * args.H * held * args.d * 2
+    tag = f" kvcache fill {args.fill:g} ({held} keys){' causal' if args.causal else ''}" if args.kvcache else ""
+    print(f"B{args.B} H{args.H} Nq{args.Nq} Nk{args.Nk} d{args.d}{tag}: workspace {need} B, median {med * 1e3:.1f} us, "
           f"K+V {kv_bytes / 1e6:.1f} MB -> {kv_bytes / med / 1e6:.0f} GB/s ({kv_bytes / med / 1e6 / 8000 * 100:.1f} % of 8 TB/s)")
 
 
