@@ -10,23 +10,8 @@ extern "C" {
 
 #ifdef FA_EXPERIMENTS
 // ---- libfa_mi355_exp.so only (make experimental): measurement entry points, not in the public header ----
-// fa_fwd_w64x stream, instantiated per experiment (fa_lab_w64x.hip): kstruct 0 shipped order, 1 two half-iterations
-// per tile, 3 the same with waves 4-7 half an iteration behind; abl = timing-ablation bits; diag = per-phase stamps.
-FA_EXPORT int fa_lab_w64x(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
-                int kstruct, int abl, unsigned long long* diag, void* stream)
-{
-    return (int)fa::lab_w64x_dispatch(Q, K, V, O, BH, N, scale, kstruct, abl, diag, static_cast<hipStream_t>(stream));
-}
-
 // per-block pass ids of the fa_fwd_rp16 kernels (see g_rp16_pass_ids); nullptr switches the recording off again
 FA_EXPORT int fa_lab_rp16_pass_ids(unsigned* dev_ids) { return (int)fa::rp16_set_pass_ids(dev_ids); }
-
-// fa_fwd_sk (fp16 -> fp32, d = 64) with per-phase s_memtime stamps: diag[wg][wave][8]; variant 0 shipped, 1 no fold, 2 no skew, 3 neither
-FA_EXPORT int fa_lab_sk(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int variant,
-              unsigned long long* diag, void* stream)
-{
-    return (int)fa::sk_diag_dispatch(Q, K, V, O, BH, N, scale, variant, diag, static_cast<hipStream_t>(stream));
-}
 
 // compute / stage-wait / barrier time of the interleaved kernel.
 FA_EXPORT int fa_debug_il_times(const void* Q, const void* K, const void* V, void* O,

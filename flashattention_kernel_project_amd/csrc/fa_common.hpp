@@ -97,15 +97,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 __device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned voff) {
     return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
 }
-// per-lane offset + wave-uniform offset (SGPR): one address register serves many loads
-__device__ __forceinline__ u32x4 buf_load16_s(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-// explicit cache policy (gfx94x/gfx950 aux bits: 1 = sc0, 2 = nt, 16 = sc1)
-template <int kAux>
-__device__ __forceinline__ u32x4 buf_load16_cp(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, kAux);
-}
 // read-once streams (decode K/V): non-temporal hint (cache-policy bit 1 = nt on gfx94x/gfx950)
 __device__ __forceinline__ u32x4 buf_load16_nt(__amdgpu_buffer_rsrc_t r, unsigned voff) {
     return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 2);
@@ -118,12 +109,6 @@ __device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t r, unsigned v
 }
 __device__ __forceinline__ void buf_store8(__amdgpu_buffer_rsrc_t r, unsigned voff, u32x2 v) {
     __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 0);
-}
-__device__ __forceinline__ void buf_store16_nt(__amdgpu_buffer_rsrc_t r, unsigned voff, u32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, 0, 2);
-}
-__device__ __forceinline__ void buf_store8_nt(__amdgpu_buffer_rsrc_t r, unsigned voff, u32x2 v) {
-    __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 2);
 }
 __device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned v) {
     __builtin_amdgcn_raw_buffer_store_b32(v, r, voff, 0, 0);
@@ -174,7 +159,6 @@ __device__ __forceinline__ u32x2 lds_read_tr8(const char* smem, unsigned off) {
 }
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 

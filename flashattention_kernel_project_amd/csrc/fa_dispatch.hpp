@@ -87,20 +87,11 @@ hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, flo
                                 hipStream_t stream);
 
 #ifdef FA_EXPERIMENTS
-// ---- the A/B kernels of the experimental build: fa_fwd_{w64,w64x,w64p,rp,sk}.hip ----
-hipError_t w64_dispatch(const FwdArgs& a);
-hipError_t w64_causal_dispatch(const FwdArgs& a);
-hipError_t w64x_dispatch(const FwdArgs& a);
-hipError_t w64p_dispatch(const FwdArgs& a);
+// ---- the A/B kernel of the experimental build: fa_fwd_rp.hip ----
 hipError_t rp_dispatch(const FwdArgs& a, int fold);      // fold: 1 = folded fast pass where it exists (fp16, d = 64)
-hipError_t sk_dispatch(const FwdArgs& a, int variant);   // variant: 0 = shipped (fold for fp16, skew), 1 = no fold, 2 = no skew, 3 = neither
 // ---- ... and its measurement entry points ----
 hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O,
                             int BH, int N, float scale, unsigned long long* diag, int waves, hipStream_t stream);
-hipError_t sk_diag_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale, int variant,
-                            unsigned long long* diag, hipStream_t stream);
-hipError_t lab_w64x_dispatch(const void* Q, const void* K, const void* V, void* O, int BH, int N, float scale,
-                             int kstruct, int abl, unsigned long long* diag, hipStream_t stream);
 // the per-block pass-id recorder is a device variable of each pipeline translation unit: one setter per unit, and all of them
 hipError_t rp16_set_pass_ids(unsigned* dev_ptr);
 hipError_t rp16_set_pass_ids_d64(unsigned*);

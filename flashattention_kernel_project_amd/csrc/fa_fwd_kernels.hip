@@ -442,19 +442,10 @@ static hipError_t generic_forward(const FwdArgs& a)
     });
 }
 
-#ifdef FA_EXPERIMENTS
-// occupancy variants of the plain tiled kernel on 128-row workgroups
-template <int kOcc>
-static hipError_t tiled_occupancy_forward(const FwdArgs& a)
-{
-    if (a.in_dtype != 0 || a.out_dtype != 0) return hipErrorInvalidValue;   // instantiated for fp16 in, fp32 out only
-    return launch_tiled<F16, 64, true, 4, kOcc>(a);
-}
-#endif
-
 // ---- the algo table: every explicit algo id there is, in which build, for which D, and whether it runs under the mask ----
 // The one source for forward_dispatch(), forward_causal_dispatch(), algo_kernel_name() and the range of ids fa_forward_ex()
-// takes; include/fa_mi355.h restates it for callers.  An id without a row (3, 4, 9-12, 15 were removed) is hipErrorInvalidValue.
+// takes; include/fa_mi355.h restates it for callers.  An id without a row (3, 4, 7-20 were retired: DESIGN.md 3)
+// is hipErrorInvalidValue.
 enum : unsigned {
     kD64 = 1, kD128 = 2,
     kDAny = 4,   // every D validate() lets through: D % 16 == 0, D <= kGenMaxD
@@ -477,19 +468,7 @@ static constexpr AlgoRow kAlgos[] = {
     // under the mask id 6 is NOT the interleaved kernel: it is the tiled kernel on 128-row workgroups, two per CU, D in {64, 128}
     {6, "FA_ALGO_INTERLEAVED_2WG", "fa::fa_fwd_il_kernel", {FA_ROW_GO(il_dispatch(a, 4)), kD64}, {tiled_forward<4, true>, kD64 | kD128}},
 #ifdef FA_EXPERIMENTS
-    // A/B kernels AUTO never selects: only in libfa_mi355_exp.so (make experimental)
-    {7, "", "fa::fa_fwd_kernel", {tiled_occupancy_forward<3>, kD64}, {}},   // fp16, fp32 out only (tiled_occupancy_forward)
-    {8, "", "fa::fa_fwd_kernel", {tiled_occupancy_forward<2>, kD64}, {}},
-    // round 1's defaults and (16) the 32x32x16 pipeline: A/B baselines.  13 under the mask: the 64-rows-per-wave kernel with the
-    // mask; measured 3-4 % SLOWER than the plain tiled kernel under the mask (B8 H16 N4096 d64: 0.462 vs 0.443 ms; N8192 d128:
-    // 2.41 vs 2.36 ms), so AUTO stays tiled.
-    {13, "FA_ALGO_W64", "fa::fa_fwd_w64_kernel", {w64_dispatch, kD64 | kD128}, {w64_causal_dispatch, kD64 | kD128}},
-    {14, "FA_ALGO_W64P", "fa::fa_fwd_w64p_kernel", {w64p_dispatch, kD64 | kD128}, {}},
-    {16, "FA_ALGO_W64X", "fa::fa_fwd_w64x_kernel", {w64x_dispatch, kD64 | kD128}, {}},
-    {17, "FA_ALGO_SK", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 0)), kD64}, {}},
-    {18, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 1)), kD64}, {}},
-    {19, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 2)), kD64}, {}},
-    {20, "", "fa::fa_fwd_sk_kernel", {FA_ROW_GO(sk_dispatch(a, 3)), kD64}, {}},
+    // the A/B kernel AUTO never selects: only in libfa_mi355_exp.so (make experimental).  The 32x32x16 pipeline, rp16's predecessor
     {21, "FA_ALGO_RP", "fa::fa_fwd_rp_kernel", {FA_ROW_GO(rp_dispatch(a, 0)), kD64 | kD128}, {}},
     {22, "FA_ALGO_RP_FOLD", "fa::fa_fwd_rp_kernel", {FA_ROW_GO(rp_dispatch(a, 1)), kD64 | kD128}, {}},
 #endif
@@ -533,11 +512,11 @@ static const AlgoRow* find_algo(int algo)
 // AUTO: the explicit algo id a shape resolves to (one rule for the dispatcher and for fa_selected_kernel()).
 //   d = 64, N > 256 and at least one 512-row workgroup per CU: the rolling half-tile pipeline on 16x16x32 with the folded
 //     fast pass (fa_fwd_rp16.hip, 24), fp16 and bf16.  Round 2, one device, interleaved A/B, B8 H16 N4096, ms per launch:
-//     fp16 0.489 (24) / 0.524 (22, the same on 32x32x16) / 0.526 (23, exact) / 0.541 (fa_fwd_w64x);
-//     bf16 0.487 (24) / 0.502 (23) / 0.528 (21, fa_fwd_rp) / 0.533 (fa_fwd_w64);
+//     fp16 0.489 (24) / 0.524 (22, the same on 32x32x16) / 0.526 (23, exact) / 0.541 (round 1's default);
+//     bf16 0.487 (24) / 0.502 (23) / 0.528 (21, fa_fwd_rp) / 0.533 (round 1's default);
 //   d = 64, smaller grids or N <= 256: the interleaved kernel with 256-row workgroups, or 128-row ones (two per CU);
 //   d = 128: the same pipeline with two 16-row blocks per wave (256-row workgroups), B8 H16 N8192: fp16 3.74 ms against 3.94
-//     for fa_fwd_w64x, bf16 3.63 against 3.84 for fa_fwd_w64; from N = 4096 with one wave per SIMD (28);
+//     for round 1's default, bf16 3.63 against 3.84 (those kernels are retired); from N = 4096 with one wave per SIMD (28);
 //   anything else: the generic single-fragment kernel.
 // The CU count is read from the current device per call.
 int auto_algo(int BH, int N, int D, int in_dtype)

@@ -22,8 +22,24 @@
 // Reference analogue: the warp-specialised kernels' hand-off of MMA, softmax and load roles per tile
 // (flashattn_warp_spc/flashattn_streaming_16x16_mw_v10.cu:188-269, _v11.cu:189-258); with 64-lane waves and one
 // matrix pipe per SIMD the roles are slots of one instruction stream instead of warps.
-// Overflow safety, row sums, output, persistent XCD-aware grid: as fa_fwd_w64.hip (optimistic pass against a fixed
-// reference max + exact detection + tracked re-run).
+//
+// Overflow safety.  A workgroup first runs an OPTIMISTIC pass: p = 2^(c*S - m_ref) against a reference maximum that is
+// fixed after the first 32 keys (their row maximum plus 2^4 of headroom), so the steady state has no per-tile row
+// maximum and no rescale of O.  Detection is exact and costs one compare per row after the last tile: a packed p can
+// only have overflowed its 16-bit format if the fp32 row sum reached that format's range (fp16: 60000; bf16: 2^96,
+// which leaves room for sum(p*v) in fp32).  If any row of the workgroup trips, the whole workgroup (__syncthreads_or)
+// RE-RUNS its item in tracked mode: the same data flow in plain program order with the lazy running maximum per unit.
+// The folded fast pass (kFold) sits in front of this chain with its own, wider set of refusal gates.
+// Row sums are fp32.  The optimistic passes take them on the matrix pipe (FA_RP_SUMMFMA: the packed, that is ROUNDED,
+// weights against a selector operand); the tracked pass sums per half-wave (h = lane >> 5 holds half the keys of a
+// unit) by v_add_f32, or for bf16 by v_dot2c over the rounded weights (FA_RP_DOT2; fa_common.hpp says why), and
+// combines the halves once at the end.
+// Output: O^T accumulators times 1 / row sum, stored through a per-head buffer descriptor, so rows >= N are dropped by
+// the bounds check (as Q rows >= N and K/V tiles past the end read zeros).
+// Grid: persistent and XCD-aware.  min(items, CUs) workgroups are launched and workgroup b takes items b, b + grid, ...;
+// since hardware deals consecutive workgroup ids round-robin to the 8 XCDs, item ids are remapped (xcd = bid & 7 owns
+// one contiguous eighth of the items) so that the query blocks sharing a head's K/V run on one XCD, consecutively,
+// and meet in its L2.
 #include "fa_tile.hpp"
 #include "fa_dispatch.hpp"
 

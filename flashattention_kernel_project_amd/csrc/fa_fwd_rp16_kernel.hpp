@@ -1,15 +1,16 @@
 // fa_fwd_rp16_kernel.hpp -- the rolling half-tile pipeline of fa_fwd_rp.hip on v_mfma_f32_16x16x32 (d = 64).
 //
 // Why a second shape of the same stream: the d=64 forward runs at the package power cap, where wall time is joules per
-// launch divided by the cap (fa_fwd_rp needs 15 % fewer cycles than fa_fwd_w64x and lands at the same
-// 0.55 ms, the clock simply settles at 1.80 instead of 2.10 GHz).  Sustained at two waves per SIMD the slot model
+// launch divided by the cap (fa_fwd_rp needs 15 % fewer cycles than round 1's phase-ordered 16x16x32 stream and
+// lands at the same 0.55 ms, the clock simply settles at 1.80 instead of 2.10 GHz).  Sustained at two waves per SIMD the slot model
 // (tools/slot_energy.py, profiles/r02_slot_energy.txt) prices one slot -- two scores per lane -- at
 //     32x32x16 + folded vector work      21.7 nJ per SIMD     2 x 16x16x32 + folded      19.6 nJ   (-9 %)
 //     32x32x16 + exact vector work       25.7 nJ              2 x 16x16x32 + exact       23.4 nJ   (-9 %)
 // although the 16x16x32 form needs a quarter more cycles per slot (it holds the issue port 8 of every 16 cycles).
 // So: the same pipeline (QK^T one half tile ahead, PV one behind, the softmax of the half tile in between issued as
 // slices between the matrix instructions, branch-free steady state, folded fast pass with the wave reference maximum as
-// the accumulators' start value) with the lane roles and LDS images of fa_fwd_w64x.hip:
+// the accumulators' start value; overflow safety, row sums and the persistent XCD-aware grid as fa_fwd_rp.hip's header
+// describes them) with the lane roles and LDS images the 16x16x32 instruction asks for:
 //   lane = 16 g + c; the accumulator of S^T = K.Q^T for (16-row query block x, 16-key block kb) holds query 16x + c on
 //   the lane and keys 16kb + 4g + i in register i; the packed registers of key blocks 2s, 2s+1 are the B fragment of
 //   k-step s of O^T += V^T.P^T; K row-major with the 16-B chunk index XORed by (row >> 1) & 7, V in 256-B blocks

@@ -51,14 +51,10 @@ extern "C" {
                                      every LDS fragment feeding four matrix instructions; AUTO at D = 128 from N = 4096; also accepted by fa_forward_causal (D = 128; AUTO there from N = 8192 on grids of >= 4 rounds) */
 /* Only in the experimental build (`make experimental`, fa_mi355_has_experiments() == 1; hipErrorInvalidValue otherwise):
  * A/B kernels that AUTO never selects. */
-#define FA_ALGO_W64            13 /* round 1's default for bf16: 64 query rows per wave, phase-ordered stream on 32x32x16, packed fp32 */
-#define FA_ALGO_W64X           16 /* round 1's default for fp16: the W64 stream on v_mfma_f32_16x16x32 */
 #define FA_ALGO_RP             21 /* the rolling pipeline on 32x32x16 (two 32-row blocks per wave), exact passes */
 #define FA_ALGO_RP_FOLD        22 /* RP with the folded fast pass (fp16, D = 64) */
-#define FA_ALGO_W64P           14 /* W64 with a half-tile rolling pipeline, packed fp32 (round 1's form of RP), D in {64,128} */
 #define FA_ALGO_RP16_DMA       25 /* RP16_FOLD with K/V staged by LDS-DMA (buffer_load ... lds) instead of through registers */
-#define FA_ALGO_SK             17 /* skewed halves: waves 4-7 half an iteration behind waves 0-3, folded fast pass; 18 exact, 19/20 lock-step */
-/* 7, 8: occupancy variants of TILED (fp16, d=64).  3, 4, 9-12, 15 (round 1 / 2 A/B kernels two generations stale) were removed in round 3. */
+/* 3, 4 and 7-20 (round 1 / 2 A/B kernels two generations stale) were retired: hipErrorInvalidValue in both builds. */
 
 /* General-shape forward.  Replaces
  *   flashattn_forward_wmma_kernel(const half* Q, const half* K, const half* V, float* O,
@@ -88,7 +84,7 @@ int fa_forward_ex(const void* Q, const void* K, const void* V, void* O,
  * FA_ALGO_GENERIC, FA_ALGO_TILED (256-row workgroups), 6 (the tiled kernel with 128-row workgroups, two
  * per CU), FA_ALGO_RP16_FOLD (the pipeline under the mask; AUTO's choice whenever the grid gives every CU a
  * workgroup) or FA_ALGO_RP16_FOLD_1W (the same with one wave per SIMD, D = 128 only; AUTO's choice there from N = 8192 on
- * grids of >= 4 rounds); all but the first two need D in {64,128}.  (FA_ALGO_W64 under the mask: experimental build only.) */
+ * grids of >= 4 rounds); all but the first two need D in {64,128}. */
 int fa_forward_causal(const void* Q, const void* K, const void* V, void* O,
                       int B, int H, int N, int d, float scale,
                       int in_dtype, int out_dtype, int algo, void* stream);

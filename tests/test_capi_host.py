@@ -43,7 +43,7 @@ def test_invalid_arguments_rejected_without_device(fa):
     assert L.fa_forward_ex(p, p, p, p, 1, 1, 128, 32, 0.125, 0, 0, 2, None) == INVALID  # tiled needs D in {64,128}
     assert L.fa_forward_ex(p, p, p, p, 1, 1, 128, 64, 0.125, 0, 0, 99, None) == INVALID
     assert L.fa_forward(p, p, p, p, 1, 1, 1 << 24, 128, 0.125, 0, 0, None) == INVALID  # per-head offsets must fit 32 bit
-    assert L.fa_forward_causal(p, p, p, p, 1, 1, 128, 64, 0.125, 0, 0, 5, None) == INVALID   # only AUTO/GENERIC/TILED/2WG/W64
+    assert L.fa_forward_causal(p, p, p, p, 1, 1, 128, 64, 0.125, 0, 0, 5, None) == INVALID   # only AUTO/GENERIC/TILED/2WG/RP16_FOLD/_1W
     assert L.fa_forward_causal(p, p, p, p, 1, 1, 128, 32, 0.125, 0, 0, 2, None) == INVALID   # tiled needs D in {64,128}
     assert L.fa_forward_causal(null, p, p, p, 1, 1, 128, 64, 0.125, 0, 0, 0, None) == INVALID
     assert L.fa_forward_splitkv(p, p, p, p, 1, 1, 1, 4096, 32, 0.125, 0, 0, None, 0, None) == INVALID    # d in {64,128}
@@ -69,15 +69,6 @@ _ALGO_CONTRACT = {
     2: (False, (64, 128), (64, 128)),
     5: (False, (64,), ()),
     6: (False, (64,), (64, 128)),        # under the mask: the tiled kernel on 128-row workgroups
-    7: (True, (64,), ()),
-    8: (True, (64,), ()),
-    13: (True, (64, 128), (64, 128)),
-    14: (True, (64, 128), ()),
-    16: (True, (64, 128), ()),
-    17: (True, (64,), ()),
-    18: (True, (64,), ()),
-    19: (True, (64,), ()),
-    20: (True, (64,), ()),
     21: (True, (64, 128), ()),
     22: (True, (64, 128), ()),
     23: (False, (64, 128), ()),
@@ -87,7 +78,7 @@ _ALGO_CONTRACT = {
     27: (False, (64,), ()),
     28: (False, (128,), (128,)),
     29: (False, (64,), ()),
-}                                         # 3, 4, 9-12, 15 were removed; nothing above 29 exists
+}                                         # 3, 4 and 7-20 were retired; nothing above 29 exists
 
 
 def _header_algo_ids():
@@ -132,11 +123,6 @@ def test_algo_contract_rejections_without_device(fa):
             if present:
                 for D in d_plain:
                     assert L.fa_selected_kernel(1, 2, 256, D, 0, algo), (algo, D)
-        # ids 7 / 8 exist for fp16 with fp32 output only
-        if have_exp:
-            for algo in (7, 8):
-                assert L.fa_forward_ex(p, p, p, p, 1, 2, 256, 64, 0.125, 1, 0, algo, None) == INVALID
-                assert L.fa_forward_ex(p, p, p, p, 1, 2, 256, 64, 0.125, 0, 1, algo, None) == INVALID
         # the header and the contract name the same ids, each on its side of the experimental-build block
         for name, (algo, in_exp_block) in header.items():
             if name == "FA_ALGO_AUTO":

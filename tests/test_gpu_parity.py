@@ -50,7 +50,7 @@ def _run(fa, torch, qb, kb, vb, fmt, algo=0, out_same=False, scale=None):
     return o.float().cpu().numpy()
 
 
-_EXPERIMENTAL = (7, 8, 13, 14, 16, 17, 18, 19, 20, 21, 22, 25)   # A/B kernels: only in libfa_mi355_exp.so (FA_MI355_LIB=...)
+_EXPERIMENTAL = (21, 22, 25)   # A/B kernels: only in libfa_mi355_exp.so (FA_MI355_LIB=...)
 
 
 def _have_exp():
@@ -58,10 +58,14 @@ def _have_exp():
     return fa_.lib().fa_mi355_has_experiments() == 1
 
 
-def _algos_for(d):
-    algos = ((0, 1, 2, 5, 6, 13, 14, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 29) if d == 64
-             else ((0, 1, 2, 13, 14, 16, 21, 23, 24, 26, 28) if d == 128 else (0, 1)))
+def _present(algos):
+    """The ids of `algos` the loaded library carries."""
     return tuple(a for a in algos if a not in _EXPERIMENTAL or _have_exp())
+
+
+def _algos_for(d):
+    return _present((0, 1, 2, 5, 6, 21, 22, 23, 24, 25, 26, 27, 29) if d == 64
+                    else ((0, 1, 2, 21, 23, 24, 26, 28) if d == 128 else (0, 1)))
 
 
 def _check(oracle, got, want, fmt, what, out_same=False, max_abs=MAX_ABS, rel_l2=None):
@@ -306,11 +310,11 @@ def test_optimistic_pass_overflow_fallback(fa, oracle, torch_cuda, fmt):
     qb, kb, vb = (oracle.encode16(x, fmt) for x in (q, k, v))
     want = oracle.forward(q, k, v, accum=1, nthreads=8)
     # A one-hot row reproduces |V| times the rounding error of its single packed weight when the row sum
-    # is taken from the unrounded fp32 p: 2^-9 for bf16, |V| <= ~4.5.  The shipped kernels (AUTO, 5, 6,
-    # 13, 14) sum the ROUNDED bf16 weights instead and meet the plain bar; the A/B variants do not.
+    # is taken from the unrounded fp32 p: 2^-9 for bf16, |V| <= ~4.5.  The shipped kernels (AUTO, 5, 6)
+    # sum the ROUNDED bf16 weights instead and meet the plain bar; the A/B variants do not.
     def tol(algo):
         return MAX_ABS
-    for algo in (a for a in (0, 5, 6, 13, 14, 16, 17, 18, 21, 22, 23, 24, 25, 26, 27, 29) if a not in _EXPERIMENTAL or _have_exp()):
+    for algo in _present((0, 5, 6, 21, 22, 23, 24, 25, 26, 27, 29)):
         got = _run(fa, torch_cuda, qb, kb, vb, fmt, algo)
         _check(oracle, got, want, fmt, f"optimistic/fallback fmt={fmt} algo={algo}", max_abs=tol(algo))
     # ragged N with the overflow in the partial last tile
@@ -319,7 +323,7 @@ def test_optimistic_pass_overflow_fallback(fa, oracle, torch_cuda, fmt):
     k2[0, n2 - 1] = q2[0, 200] * 40.0
     q2, k2, v2 = (oracle.decode16(oracle.encode16(x, fmt), fmt) for x in (q2, k2, v2))
     want2 = oracle.forward(q2, k2, v2, accum=1, nthreads=8)
-    for algo in (a for a in (0, 5, 6, 13, 14, 16, 17, 18, 21, 22, 23, 24, 25, 26, 27, 29) if a not in _EXPERIMENTAL or _have_exp()):
+    for algo in _present((0, 5, 6, 21, 22, 23, 24, 25, 26, 27, 29)):
         got2 = _run(fa, torch_cuda, *(oracle.encode16(x, fmt) for x in (q2, k2, v2)), fmt, algo)
         _check(oracle, got2, want2, fmt, f"optimistic/fallback ragged fmt={fmt} algo={algo}", max_abs=tol(algo))
 
@@ -340,7 +344,7 @@ def test_causal_vs_oracle(fa, oracle, torch_cuda, fmt):
         for n in (1, 17, 64, 65, 255, 256, 257, 600):
             (q, k, v), (qb, kb, vb) = oracle.make_qkv(3, n, d, fmt=fmt, seed=900 + n + d)
             want = oracle.forward(q, k, v, causal=True, nthreads=8)
-            for algo in (tuple(a for a in (0, 1, 2, 6, 13, 24) + ((28,) if d == 128 else ()) if a not in _EXPERIMENTAL or _have_exp()) if d in (64, 128) else (0, 1)):
+            for algo in (_present((0, 1, 2, 6, 24) + ((28,) if d == 128 else ())) if d in (64, 128) else (0, 1)):
                 got = _run_causal(fa, torch_cuda, qb, kb, vb, fmt, algo=algo)
                 _check(oracle, got, want, fmt, f"causal d={d} n={n} algo={algo} fmt={fmt}")
             got = _run_causal(fa, torch_cuda, qb, kb, vb, fmt, out_same=True)
@@ -672,7 +676,7 @@ def test_bf16_overflow_window_below_inf(fa, oracle, torch_cuda):
     q, k, v = (oracle.decode16(oracle.encode16(x, fmt), fmt) for x in (q, k, v))
     qb, kb, vb = (oracle.encode16(x, fmt) for x in (q, k, v))
     want = oracle.forward(q, k, v, accum=1, nthreads=8)
-    for algo in (a for a in (0, 5, 6, 13, 16, 21, 23, 24, 26, 27, 14, 17) if a not in _EXPERIMENTAL or _have_exp()):
+    for algo in _present((0, 5, 6, 21, 23, 24, 26, 27)):
         got = _run(fa, torch_cuda, qb, kb, vb, fmt, algo)
         _check(oracle, got, want, fmt, f"bf16 window algo={algo}", max_abs=4 * MAX_ABS)   # |V| = 4 x the N(0,1) bar
 
@@ -733,7 +737,7 @@ def test_folded_pass_gates(fa, oracle, torch_cuda, fmt):
         q, k, v = (oracle.decode16(oracle.encode16(x, fmt), fmt) for x in (q, k, v))
         qb, kb, vb = (oracle.encode16(x, fmt) for x in (q, k, v))
         want = oracle.forward(q, k, v, accum=1, nthreads=8, **({} if scale is None else {"scale": scale}))
-        for algo in (a for a in (24, 26, 27, 29, 23, 22, 21, 0) if a not in _EXPERIMENTAL or _have_exp()):
+        for algo in _present((24, 26, 27, 29, 23, 22, 21, 0)):
             got = _run(fa, torch_cuda, qb, kb, vb, fmt, algo, scale=scale)
             # (case (i): O = 3 (w1 - w2) with w1 ~ w2 -- the row's output nearly cancels, so a relative measure over the tensor says
             # little; the max-abs bar is what holds there)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of kernel variants in ONE process (HIP events on the launch stream).
 
-    python tools/ab_bench.py --algos 2,3 --rounds 10 --iters 20 [--dtype f16] [--B 8 --H 16 --N 4096 --d 64]
+    python tools/ab_bench.py --algos 24,23 --rounds 10 --iters 20 [--dtype f16] [--B 8 --H 16 --N 4096 --d 64]
 
 Prints per variant: median / min ms and TFLOP/s, plus max-abs difference of each variant's output
 against the first variant's (a sanity check, not the parity test).
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algos", default="2,3")
+    ap.add_argument("--algos", default="24,23")
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--B", type=int, default=8)

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # On the GPU box: per-kernel cycle counters for a set of explicit algo ids (one rocprofv3 --pmc pass).
-#   bash tools/pmc_algos.sh <tag> <algos> [dtype]      e.g.  bash tools/pmc_algos.sh a1 16,14,17 f16
+#   bash tools/pmc_algos.sh <tag> <algos> [dtype]      e.g.  bash tools/pmc_algos.sh a1 24,23,26 f16
 set -euo pipefail
 tag="$1"; algos="$2"; dtype="${3:-f16}"
 R="${GRAFT_REPO_ROOT:-$(pwd)}"

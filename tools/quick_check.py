@@ -2,7 +2,7 @@
 """Quick GPU sanity sweep of explicit algo ids against fp32 torch ops (development aid; the parity tests are
 tests/test_gpu_parity.py against the CPU oracle).
 
-    python tools/quick_check.py --algos 17,18 [--exp]
+    python tools/quick_check.py --algos 24,23 [--exp]     (--exp: the experimental library, for 21, 22, 25)
 """
 import argparse
 import os
@@ -18,7 +18,7 @@ def ref(q, k, v, scale):
 
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--algos", default="17,18")
+ap.add_argument("--algos", default="24,23")
 ap.add_argument("--exp", action="store_true")
 args = ap.parse_args()
 if args.exp:
