@@ -14,6 +14,8 @@ from .ops import (  # noqa: F401
     splitkv_workspace_bytes,
     fa_forward_kvcache,
     kvcache_workspace_bytes,
+    fa_forward_kvcache_paged,
+    kvcache_paged_workspace_bytes,
     flashattn_forward_wmma,
     flashattn_streaming_16x16_mw,
     flashattn_streaming_16x16_mw_kt,
@@ -25,7 +27,7 @@ from .shard import shard_range  # noqa: F401
 __all__ = [
     "build", "lib", "version", "FaError",
     "fa_forward", "fa_forward_splitkv", "splitkv_workspace_bytes", "fa_forward_kvcache",
-    "kvcache_workspace_bytes", "flashattn_forward_wmma",
+    "kvcache_workspace_bytes", "fa_forward_kvcache_paged", "kvcache_paged_workspace_bytes", "flashattn_forward_wmma",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",
     "attention_flops", "attention_min_bytes", "shard_range",
 ]

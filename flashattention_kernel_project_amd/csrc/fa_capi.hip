@@ -93,6 +93,22 @@ FA_EXPORT int fa_forward_kvcache(const void* Q, const void* Kcache, const void* 
                                       workspace, workspace_bytes, static_cast<hipStream_t>(stream)});
 }
 
+FA_EXPORT size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d)
+{
+    return fa::kvpaged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d);
+}
+
+FA_EXPORT int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* seqlens_k,
+                             const int* block_table, int B, int Hkv, int G, int Nq, int num_pages, int page_size, int max_pages,
+                             int d, float scale, int causal, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
+                             void* stream)
+{
+    // Ncap (0 here) is set by the dispatcher once max_pages * page_size is known to fit
+    return (int)fa::kvpaged_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                       workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                      block_table, num_pages, page_size, max_pages});
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

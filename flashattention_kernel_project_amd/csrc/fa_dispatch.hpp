@@ -59,7 +59,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -80,6 +80,17 @@ struct KvCacheArgs {
 };
 hipError_t kvcache_dispatch(const KvCacheArgs& a);
 size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D);
+hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
+                           hipStream_t stream);   // the merge kernel of the KV-cache split, launched for the paged entry too
+// Paged KV-cache decode (fa_forward_kvcache_paged): the KvCacheArgs with K, V as page pools [num_pages, Hkv, page_size, D],
+// Ncap = max_pages * page_size, and the device block table [B, max_pages] int32.
+struct KvPagedArgs {
+    KvCacheArgs c;
+    const int* table;
+    int num_pages, page_size, max_pages;
+};
+hipError_t kvpaged_dispatch(const KvPagedArgs& a);
+size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

@@ -68,4 +68,17 @@ hipError_t kvcache_dispatch(const KvCacheArgs& a)
     });
 }
 
+// The merge behind a split, for the paged entry (fa_fwd_kvpaged.hip): the kernel is instantiated in this translation unit only.
+hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
+                           hipStream_t stream)
+{
+    const long long out_rows = (long long)BH * rows;   // one wave per output row
+    if (out_rows > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
+        FA_LAUNCH((fa_split_combine_kernel<decltype(t), decltype(f32)::value, true, float*>), dim3((unsigned)out_rows), dim3(64), 0,
+                  stream, static_cast<const float*>(ws), O, BH, rows, D, S, lse);
+        return launch_status();
+    });
+}
+
 }  // namespace fa

@@ -1,10 +1,14 @@
-// fa_fwd_split_kernel.hpp -- device code of the split-KV stream, shared by fa_fwd_split.hip (fa_forward_splitkv) and
-// fa_fwd_kvcache.hip (fa_forward_kvcache).  One kernel template serves both: what the KV-cache entry adds is a template flag and
-// a trailing parameter pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt).
-// The two sets are instantiated in separate translation units so that neither perturbs the other's register allocation.
+// fa_fwd_split_kernel.hpp -- device code of the split-KV stream, shared by fa_fwd_split.hip (fa_forward_splitkv),
+// fa_fwd_kvcache.hip (fa_forward_kvcache) and fa_fwd_kvpaged.hip (fa_forward_kvcache_paged).  One kernel template serves all
+// three: what the KV-cache entry adds is a template flag and a trailing parameter pack, so the plain instantiations keep their
+// argument list and their code (profiles/kvcache_decode.txt); the paged entry passes a PagedArgs in that pack, and everything it
+// adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt).
+// The three sets are instantiated in separate translation units so that none perturbs another's register allocation.
 // The design notes are at the head of fa_fwd_split.hip and in DESIGN.md 7.1.
 #pragma once
 #include "fa_tile.hpp"
+
+#include <type_traits>
 
 namespace fa {
 
@@ -29,10 +33,29 @@ struct CacheArgs {
     int causal;           // row i of its head sees the keys [0, L - Nq1 + 1 + i)
 };
 
+// What the paged instantiations take instead: the CacheArgs plus where a key's row lives.  K/V are pools [num_pages, Hkv, page, D];
+// key j of sequence b is row j % page of page table[b * max_pages + j / page].
+struct PagedArgs : CacheArgs {
+    const int* table;     // [B][max_pages] page numbers on the device
+    int max_pages;        // row pitch of the table; the capacity Nk is max_pages << lg_page
+    int num_pages;        // pages in the pool: a live entry outside [0, num_pages) reads as a page of zeros
+    int lg_page;          // log2 of the page size in keys (>= 4)
+};
+struct NoPages {};
+__device__ __forceinline__ NoPages paged_part() { return {}; }
+__device__ __forceinline__ NoPages paged_part(const CacheArgs&) { return {}; }
+__device__ __forceinline__ const PagedArgs& paged_part(const PagedArgs& p) { return p; }
+
 // kPartial: write (O^T unnormalised, m, l) to the workspace instead of the normalised output.
 // kCache: the key count L of the head's sequence is read on the device (Nk is then the capacity, the stride of a K/V head) and the
 // split's chunk follows from L; every row has its own key limit; a row or a split without a key is neutral (m = -inf, l = 0, O = 0).
 // With kCache false all of that compiles out and the kernel has the plain argument list (`cache` is empty).
+// kPaged (kCache with a PagedArgs in the pack): a tile's rows come from pages.  The 16-byte loads one wave issues for one p cover
+// 8 consecutive rows at D = 64 and 4 at D = 128, aligned to as many, so they lie inside ONE page of >= 16 keys: the page number is
+// wave-uniform and goes into a scalar buffer descriptor per (wave, p), which ends at the page's last row below key1 (rows past it
+// read 0 as the end of the contiguous descriptor does).  The page numbers of the tile after next are fetched while the current
+// tile computes, so no tile but a split's first waits for the table.  Splits, tile order, masks and arithmetic are the kCache
+// ones: on the same keys the result is bit-equal to the contiguous entry's.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -44,8 +67,10 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                          const uint16_t* __restrict__ Vg, void* __restrict__ Og, float* __restrict__ ws,
                          int Nq, int Nk, int nqb, int S, int chunk, float scale_log2e, Cache... cache)
 {
-    static_assert(sizeof...(Cache) == (kCache ? 1 : 0), "the KV-cache instantiations take one CacheArgs, the plain ones nothing");
+    static_assert(sizeof...(Cache) == (kCache ? 1 : 0), "the KV-cache instantiations take one CacheArgs or PagedArgs, the plain ones nothing");
     [[maybe_unused]] const CacheArgs ca = {cache...};
+    constexpr bool kPaged = (std::is_same_v<Cache, PagedArgs> || ...);
+    [[maybe_unused]] const auto pa = paged_part(cache...);
     using namespace split;
     using G = TileGeom<D>;
     constexpr int W = kW;
@@ -110,9 +135,39 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         v_lds[p] = G::kTileBytes + G::v_off(row, ch);
     }
     u32x4 kst[kLoadsW], vst[kLoadsW];
+    // kPaged: the page numbers of the tile that is staged next, one per (wave, p), in scalar registers.  fetch_pages() reads
+    // them for a tile; the entry index is clamped to the split's last live page, so no entry at or past ceil(L / page) is read
+    // (a (wave, p) whose rows all lie at or past key1 gets a descriptor of zero records whatever the number says).
+    [[maybe_unused]] int pg[kLoadsW];
+    [[maybe_unused]] auto fetch_pages = [&](unsigned kv0) {
+        if constexpr (kPaged) {
+            const int* tbl = pa.table + (size_t)(bh / (unsigned)ca.Hkv) * (unsigned)pa.max_pages;
+            const unsigned last = (key1 - 1u) >> pa.lg_page;   // only called with key1 > key0 >= 0
+#pragma unroll
+            for (int p = 0; p < kLoadsW; ++p) {
+                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;   // first row of the tile this wave loads with p
+                pg[p] = __builtin_amdgcn_readfirstlane(tbl[min((kv0 + wrow) >> pa.lg_page, last)]);
+            }
+        }
+    };
     auto stage_load = [&](unsigned kv0) {
 #pragma unroll
         for (int p = 0; p < kLoadsW; ++p) {
+            if constexpr (kPaged) {
+                const unsigned page = 1u << pa.lg_page;
+                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;
+                const unsigned first = (kv0 + wrow) & ~(page - 1u);             // first key of the page
+                const bool ok = (unsigned)pg[p] < (unsigned)pa.num_pages && first < key1;
+                // the page's rows below key1; a bad page number or a page past the split's end: no record, every load reads 0
+                const unsigned bytes = ok ? min(page, key1 - first) * (unsigned)G::kRowBytes : 0u;
+                // 64-bit: pools beyond 4 GiB are normal; only the offset inside one page-head block is 32 bit
+                const size_t blk = (((size_t)(ok ? pg[p] : 0) * (unsigned)ca.Hkv + bh % (unsigned)ca.Hkv) << pa.lg_page) * D;
+                const __amdgpu_buffer_rsrc_t pk = make_rsrc(Kg + blk, bytes), pv = make_rsrc(Vg + blk, bytes);
+                const unsigned off = (kv0 * G::kRowBytes + g_off[p]) & (page * G::kRowBytes - 1u);
+                kst[p] = buf_load16_nt(pk, off);
+                vst[p] = buf_load16_nt(pv, off);
+                continue;
+            }
 #if FA_SPLIT_NT
             kst[p] = buf_load16_nt(rk, kv0 * G::kRowBytes + g_off[p]);
             vst[p] = buf_load16_nt(rv, kv0 * G::kRowBytes + g_off[p]);
@@ -154,7 +209,9 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     const unsigned rot = FA_SPLIT_ROTATE ? (sp * 5u + bh * 3u) % (unsigned)(kCache ? max(ntiles, 1) : ntiles) : 0u;
     auto tile_of = [&](int t) { const unsigned ti = (unsigned)t + rot; return ti >= (unsigned)ntiles ? ti - (unsigned)ntiles : ti; };
     if (!kCache || ntiles > 0) {   // workgroup-uniform
+        if constexpr (kPaged) fetch_pages(key0 + tile_of(0) * kBlockN);
         stage_load(key0 + tile_of(0) * kBlockN);
+        if constexpr (kPaged) fetch_pages(key0 + tile_of(min(1, ntiles - 1)) * kBlockN);
         stage_write(0);
         __syncthreads();
     }
@@ -164,6 +221,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         const char* kbuf = smem + cur * G::kBufBytes;
         const unsigned kv0 = key0 + tile_of(t) * kBlockN;
         if (t + 1 < ntiles) stage_load(key0 + tile_of(t + 1) * kBlockN);
+        // the table read of the tile after next (a last tile re-reads its own entries) overlaps this tile's arithmetic
+        if constexpr (kPaged) fetch_pages(key0 + tile_of(min(t + 2, ntiles - 1)) * kBlockN);
 
         // a wave whose 32 rows all lie past Nq (the usual case for a handful of query rows) only stages
         if (has_rows) {

@@ -202,6 +202,63 @@ def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int
     return int(capi.lib().fa_forward_kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d))
 
 
+def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None, causal: bool = False, scale: float | None = None,
+                             out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+    """fa_forward_kvcache against a paged cache (fa_forward_kvcache_paged): q [B,Hq,Nq,d], k_pool/v_pool
+    [num_pages,Hkv,page_size,d] fp16/bf16 contiguous device tensors (a contiguous slice of a larger pool, pool[2:6], is a pool),
+    d in {64,128}, page_size a power of two >= 16, Hq a multiple of Hkv.
+    block_table: int32 contiguous device tensor [B, max_pages]; key j of sequence b is row j % page_size of page
+    block_table[b, j // page_size].  The capacity is max_pages * page_size.  Entries past a sequence's last live page are not read;
+    a live entry outside [0, num_pages) reads as a page of zeros.
+    cache_seqlens, causal, scale, out_dtype, return_lse: as in fa_forward_kvcache.  Table and lengths are read on the device only,
+    so a call captured into a graph follows both when they are later rewritten in place.
+    workspace: optional uint8 device tensor of at least kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)."""
+    import torch
+    if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
+        raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
+    B, Hq, Nq, d = q.shape
+    num_pages, Hkv, page_size = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    if Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
+    G = Hq // Hkv
+    dts = (torch.float16, torch.bfloat16)
+    if q.dtype not in dts or k_pool.dtype != q.dtype or v_pool.dtype != q.dtype:
+        raise ValueError("q, k_pool, v_pool must all be fp16 or all bf16")
+    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
+    max_pages = block_table.shape[1]
+    tbl_ptr = _dev_ptr(block_table, "block_table", (torch.int32,))
+    len_ptr = None
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
+            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
+        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_pool, "k_pool", dts), _dev_ptr(v_pool, "v_pool", dts))
+    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+    need = kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # from the shape alone
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, cache_seqlens, workspace)):
+        code = capi.lib().fa_forward_kvcache_paged(
+            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, B, Hkv, G, Nq, num_pages, page_size,
+            max_pages, d, float(scale), 1 if causal else 0, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
+            ws_ptr, ws_len, _stream_ptr(stream))
+    capi.check("fa_forward_kvcache_paged", code)
+    return (out, lse) if return_lse else out
+
+
+def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int) -> int:
+    return int(capi.lib().fa_forward_kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d))
+
+
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):
     import torch
     if Q.numel() != num_batches * 256 or K.numel() != num_batches * 16 * seq_len \

@@ -8,6 +8,7 @@ eager fallback.  Registered on first use:
     register()
     o = torch.ops.fa_mi355.forward(q, k, v, scale, causal, out_fp32)
     o = torch.ops.fa_mi355.decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache
+    o = torch.ops.fa_mi355.decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_paged
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward and torch.ops.fa_mi355.decode (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, .decode and .decode_paged (idempotent)."""
     global _registered
     if _registered:
         return
@@ -46,6 +47,19 @@ def register() -> None:
 
     @decode.register_fake
     def _(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode_paged", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
+                                    "bool causal, bool out_fp32) -> Tensor")
+    def decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                            None if cache_seqlens is None else cache_seqlens.contiguous(), causal=causal,
+                                            scale=scale, out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
+
+    @decode_paged.register_fake
+    def _(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
         return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
 
     _registered = True

@@ -121,7 +121,8 @@ int fa_forward_splitkv(const void* Q, const void* K, const void* V, void* O,
  * so a call captured into a HIP graph replays correctly after the lengths were changed in place.  The keys of a
  * sequence are divided among its splits by L_b, not by Ncap: a cache filled to a fraction still uses every split.
  * Workspace as for fa_forward_splitkv (size from fa_forward_kvcache_workspace_bytes(); 0: `workspace` may be NULL).
- * Paged (block-table) caches, sliding windows and appending to the cache are not part of this entry.
+ * Sliding windows and appending to the cache are not part of this entry; a paged (block-table) cache goes through
+ * fa_forward_kvcache_paged below.
  * NOT a reference entry point. */
 size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d);
 int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, void* O,
@@ -130,6 +131,38 @@ int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, vo
                        int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal,
                        int in_dtype, int out_dtype,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* fa_forward_kvcache against a PAGED cache: a pool of fixed-size pages and, per sequence, a table of page numbers that is read
+ * on the device.
+ *   Kpool, Vpool    [num_pages, Hkv, page_size, d] contiguous, fp16 or bf16; d in {64,128}: one head of one page is a contiguous
+ *                   block of page_size rows.  The token-major page layout [num_pages, page_size, Hkv, d] is NOT supported.
+ *   block_table     device, [B, max_pages] int32 contiguous: key j of sequence b is row j % page_size of page
+ *                   block_table[b][j / page_size]
+ *   page_size       a power of two, at least 16 (16, 32, 64, 128, 256, ...); the capacity is Ncap = max_pages * page_size
+ *   seqlens_k       as in fa_forward_kvcache: clamped to [0, Ncap]; NULL means every sequence holds Ncap keys
+ * Q, O, lse, G, causal, rows without a key (O = 0, lse = -inf, never NaN) and the workspace contract are those of
+ * fa_forward_kvcache, and so are the splits, the tile order and the arithmetic: on the same keys the two entries return the
+ * same bits.
+ * Nothing on the host reads seqlens_k or block_table.  Grid, split count and workspace depend on (B, Hkv, G, Nq, Ncap, d) only and
+ * are what fa_forward_kvcache computes for that Ncap: fa_forward_kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size,
+ * d) == fa_forward_kvcache_workspace_bytes(B, Hkv, G, Nq, max_pages * page_size, d).  A captured call follows a table and lengths
+ * that are later rewritten in place.
+ * What is read: table entries at or past ceil(L_b / page_size) are never read; rows of the last live page at or past L_b are
+ * never used and may hold anything; a live table entry outside [0, num_pages) is never dereferenced -- such a page reads as
+ * page_size rows of zeros (clamp, never fault, as for seqlens_k).  Page addresses are 64 bit: a pool may exceed 4 GiB.
+ * hipErrorInvalidValue, before the device is touched: a null Q, Kpool, Vpool, O or block_table; a page_size that is not a power of
+ * two or is below 16; num_pages <= 0 or max_pages <= 0; max_pages * page_size beyond int or beyond the 32-bit byte offsets
+ * fa_forward_kvcache allows for its Ncap; everything else fa_forward_kvcache rejects.
+ * Appending the new token's K/V, sliding windows and fp8 caches are not part of this entry.  NOT a reference entry point. */
+size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d);
+int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                             float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                             const int* seqlens_k,    /* device, B int32, may be NULL (= Ncap for all) */
+                             const int* block_table,  /* device, [B,max_pages] int32 */
+                             int B, int Hkv, int G, int Nq,
+                             int num_pages, int page_size, int max_pages, int d,
+                             float scale, int causal, int in_dtype, int out_dtype,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through

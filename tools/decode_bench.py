@@ -4,9 +4,12 @@ occupy (the path is HBM-bound: every K and V byte is read once).
 
     python tools/decode_bench.py --B 8 --H 16 --Nq 1 --Nk 32768 --d 128
     python tools/decode_bench.py --kvcache --fill 0.25          # fa_forward_kvcache: a 32768-row cache holding 8192 keys per sequence
+    python tools/decode_bench.py --paged 16 --fill 0.25         # fa_forward_kvcache_paged: the same cache in shuffled pages of 16 keys
 
 --kvcache times fa_forward_kvcache against a cache of --Nk rows in which every sequence holds --fill x Nk keys (the lengths live
 in a device tensor); GB/s then counts the K and V bytes of the keys held, not of the capacity.  --causal adds the mask.
+--paged PAGE_SIZE (implies --kvcache) scatters that cache into a pool [B * Nk / PAGE_SIZE, H, PAGE_SIZE, d] through a seeded random
+permutation of the pages and times fa_forward_kvcache_paged with the block table of that permutation.
 """
 import argparse
 import os
@@ -14,6 +17,22 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def scatter_pages(torch, k, v, page_size, seed=0):
+    """Caches [B, H, Nk, d] -> (K pool, V pool [B * Nk / page_size, H, page_size, d], block table [B, Nk / page_size] int32): logical
+    page p of sequence b becomes physical page perm[b * max_pages + p] of a seeded random permutation."""
+    B, H, Nk, d = k.shape
+    max_pages = Nk // page_size
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    perm = torch.randperm(B * max_pages, generator=g).to(k.device)
+    pools = []
+    for x in (k, v):
+        pages = x.view(B, H, max_pages, page_size, d).permute(0, 2, 1, 3, 4).reshape(B * max_pages, H, page_size, d)
+        pool = torch.empty_like(pages)
+        pool[perm] = pages
+        pools.append(pool)
+    return pools[0], pools[1], perm.view(B, max_pages).to(torch.int32).contiguous()
 
 
 def main():
@@ -28,7 +47,13 @@ def main():
     ap.add_argument("--kvcache", action="store_true", help="fa_forward_kvcache with per-sequence lengths instead of fa_forward_splitkv")
     ap.add_argument("--fill", type=float, default=1.0, help="with --kvcache: every sequence holds FILL * Nk keys")
     ap.add_argument("--causal", action="store_true", help="with --kvcache: the causal mask aligned to the end of the cache")
+    ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
+                    help="fa_forward_kvcache_paged on the cache scattered into shuffled pages of PAGE_SIZE keys (implies --kvcache)")
     args = ap.parse_args()
+    if args.paged:
+        args.kvcache = True
+        if args.paged < 16 or args.paged & (args.paged - 1) or args.Nk % args.paged:
+            ap.error("--paged needs a power of two >= 16 that divides --Nk")
     import torch
     import flashattention_kernel_project_amd as fa
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -42,8 +67,15 @@ def main():
         need = fa.kvcache_workspace_bytes(args.B, args.H, 1, args.Nq, args.Nk, args.d)
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
 
-        def call():
-            fa.fa_forward_kvcache(q, k, v, lens, causal=args.causal, workspace=ws)
+        if args.paged:
+            k, v, table = scatter_pages(torch, k, v, args.paged, seed=0)
+            need = fa.kvcache_paged_workspace_bytes(args.B, args.H, 1, args.Nq, args.Nk // args.paged, args.paged, args.d)
+
+            def call():
+                fa.fa_forward_kvcache_paged(q, k, v, table, lens, causal=args.causal, workspace=ws)
+        else:
+            def call():
+                fa.fa_forward_kvcache(q, k, v, lens, causal=args.causal, workspace=ws)
     else:
         held = args.Nk
         need = fa.splitkv_workspace_bytes(args.B, args.H, args.Nq, args.Nk, args.d)
@@ -66,6 +98,8 @@ def main():
     med = statistics.median(times)
     kv_bytes = 2.0 * args.B * args.H * held * args.d * 2
     tag = f" kvcache fill {args.fill:g} ({held} keys){' causal' if args.causal else ''}" if args.kvcache else ""
+    if args.paged:
+        tag += f" paged {args.paged}"
     print(f"B{args.B} H{args.H} Nq{args.Nq} Nk{args.Nk} d{args.d}{tag}: workspace {need} B, median {med * 1e3:.1f} us, "
           f"K+V {kv_bytes / 1e6:.1f} MB -> {kv_bytes / med / 1e6:.0f} GB/s ({kv_bytes / med / 1e6 / 8000 * 100:.1f} % of 8 TB/s)")
 
