@@ -31,6 +31,18 @@ static inline hipError_t with_types(int in_dtype, int out_dtype, F&& f)
     return hipErrorInvalidValue;
 }
 
+// scale * log2(e) as every kernel takes it.  The tiled, interleaved, pipeline and plain split-KV kernels mask a key by setting its
+// score to -inf and form fma(score, |c|, -m): with c == 0 that is 0 * -inf, a NaN, wherever a mask applies (ragged N or Nk, the
+// causal mask).  So a product of magnitude below FLT_MIN (scale 0, or a scale that underflows) goes to the device as +-FLT_MIN:
+// every finite score then moves the exponent by a negligible amount (uniform weights, as scale 0 asks) and -inf stays -inf.
+// A NaN scale passes through.  Host side only: the kernels are compiled as before.
+static inline float host_scale_log2e(float scale)
+{
+    const float c = scale * kLog2e;
+    if (!(__builtin_fabsf(c) < 1.17549435e-38f)) return c;
+    return __builtin_copysignf(1.17549435e-38f, c);
+}
+
 // The kernel family a forward on the rolling pipeline runs on: what the algo table (fa_fwd_kernels.hip) asks rp16_dispatch() /
 // rp16_causal_dispatch() (fa_fwd_rp16.hip) for.
 enum class Rp16Family {

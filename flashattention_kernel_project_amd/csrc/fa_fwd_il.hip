@@ -548,7 +548,7 @@ static hipError_t launch_il(const FwdArgs& a)
     const unsigned grid = (grid_cap > 0 && nwg > grid_cap) ? (unsigned)grid_cap : (unsigned)nwg;
     FA_LAUNCH(kern, dim3(grid), dim3(64 * W), lds_bytes, a.stream,
                        static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
-                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e,
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, host_scale_log2e(a.scale),
                        static_cast<unsigned long long*>(nullptr), (unsigned)nwg);
     return launch_status();
 }
@@ -566,7 +566,7 @@ hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             FA_LAUNCH(kern, dim3((unsigned)(BH * nqb)), dim3(256), lds, stream,
                                static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                               static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, diag, 0u);
+                               static_cast<const uint16_t*>(V), O, N, nqb, host_scale_log2e(scale), diag, 0u);
         };
         switch (waves - 200) {
             case 0: go(fa_fwd_il_kernel<F16, 64, true, 4, false, 0>); break;
@@ -590,7 +590,7 @@ hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O
         auto go = [&](auto kern) {
             FA_LAUNCH(kern, dim3((unsigned)(BH * nqb)), dim3(512), G::kLdsBytes, stream,
                                static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                               static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, diag, 0u);
+                               static_cast<const uint16_t*>(V), O, N, nqb, host_scale_log2e(scale), diag, 0u);
         };
         switch (waves - 100) {
             case 0: go(fa_fwd_il_kernel<F16, 64, true, 8, false, 0>); break;
@@ -619,7 +619,7 @@ hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O
         auto go = [&](auto kern) {
             FA_LAUNCH(kern, dim3((unsigned)(BH * nqb)), dim3(512), G::kLdsBytes, stream,
                                static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                               static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, diag, 0u);
+                               static_cast<const uint16_t*>(V), O, N, nqb, host_scale_log2e(scale), diag, 0u);
         };
         switch (waves - 10) {   // bit mask: 1 no LDS operand reads, 2 no MFMA, 4 no softmax VALU, 8 no staging, 16 no barrier
             case 1: go(fa_fwd_il_kernel<F16, 64, true, 8, true, 1>); break;
@@ -640,12 +640,12 @@ hipError_t il_diag_dispatch(const void* Q, const void* K, const void* V, void* O
         const int nqb = (N + 255) / 256;
         FA_LAUNCH((fa_fwd_il_kernel<F16, 64, true, 8, true>), dim3((unsigned)(BH * nqb)), dim3(512), G::kLdsBytes, stream,
                            static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                           static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, diag, 0u);
+                           static_cast<const uint16_t*>(V), O, N, nqb, host_scale_log2e(scale), diag, 0u);
     } else {
         const int nqb = (N + 127) / 128;
         FA_LAUNCH((fa_fwd_il_kernel<F16, 64, true, 4, true>), dim3((unsigned)(BH * nqb)), dim3(256), G::kLdsBytes, stream,
                            static_cast<const uint16_t*>(Q), static_cast<const uint16_t*>(K),
-                           static_cast<const uint16_t*>(V), O, N, nqb, scale * kLog2e, diag, 0u);
+                           static_cast<const uint16_t*>(V), O, N, nqb, host_scale_log2e(scale), diag, 0u);
     }
     return launch_status();
 }

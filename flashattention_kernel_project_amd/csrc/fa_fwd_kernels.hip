@@ -406,7 +406,7 @@ static hipError_t launch_tiled(const FwdArgs& a)
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     FA_LAUNCH(kern, dim3((unsigned)nwg), dim3(64 * W), G::kLdsBytes, a.stream,
                        static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
-                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e);
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, host_scale_log2e(a.scale));
     return launch_status();
 }
 
@@ -418,7 +418,7 @@ static hipError_t launch_generic(const FwdArgs& a)
     if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
     FA_LAUNCH((fa_fwd_generic_kernel<T, kOutF32, kCausal>), dim3((unsigned)nwg), dim3(64), 0, a.stream,
                        static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
-                       static_cast<const uint16_t*>(a.V), a.O, a.N, a.D, nqb, a.scale * kLog2e);
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, a.D, nqb, host_scale_log2e(a.scale));
     return launch_status();
 }
 

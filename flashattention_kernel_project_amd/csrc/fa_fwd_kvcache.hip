@@ -26,11 +26,11 @@ static hipError_t launch_kvcache(const KvCacheArgs& a, int BH, int rows)
     const CacheArgs ca = {a.seqlens, S == 1 ? a.lse : nullptr, a.Hkv, a.Nq, a.causal};
     if (S == 1) {
         FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, false, true, CacheArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                           a.stream, q, k, v, a.O, static_cast<float*>(nullptr), rows, a.Ncap, nqb, S, 0, a.scale * kLog2e, ca);
+                           a.stream, q, k, v, a.O, static_cast<float*>(nullptr), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), ca);
         return launch_status();
     }
     FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, true, true, CacheArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                       a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, a.scale * kLog2e, ca);
+                       a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), ca);
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
     const long long out_rows = (long long)BH * rows;   // one wave per output row

@@ -26,11 +26,11 @@ static hipError_t launch_kvpaged(const KvPagedArgs& p, int BH, int rows, int lg_
     const PagedArgs pa = {{a.seqlens, S == 1 ? a.lse : nullptr, a.Hkv, a.Nq, a.causal}, p.table, p.max_pages, p.num_pages, lg_page};
     if (S == 1) {
         FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, false, true, PagedArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                           a.stream, q, k, v, a.O, static_cast<float*>(nullptr), rows, a.Ncap, nqb, S, 0, a.scale * kLog2e, pa);
+                           a.stream, q, k, v, a.O, static_cast<float*>(nullptr), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), pa);
         return launch_status();
     }
     FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, true, true, PagedArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                       a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, a.scale * kLog2e, pa);
+                       a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), pa);
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
     return kvcache_combine(a.ws, a.O, a.lse, BH, rows, D, S, a.in_dtype, a.out_dtype, a.stream);

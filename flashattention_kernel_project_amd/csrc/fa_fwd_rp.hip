@@ -600,7 +600,7 @@ static hipError_t launch_rp(const FwdArgs& a)
     FA_LAUNCH((fa_fwd_rp_kernel<T, D, X, kOutF32, kFold>), dim3(grid), dim3(64 * rp::kW),
                        rp::kSlots * G::kBufBytes, a.stream,
                        static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K),
-                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, a.scale * kLog2e, (unsigned)nwg);
+                       static_cast<const uint16_t*>(a.V), a.O, a.N, nqb, host_scale_log2e(a.scale), (unsigned)nwg);
     return launch_status();
 }
 

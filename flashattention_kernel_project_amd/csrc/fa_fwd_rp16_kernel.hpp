@@ -1295,7 +1295,7 @@ static hipError_t launch_rp16(const FwdArgs& a)
     if (attr != hipSuccess) return attr;
     FA_LAUNCH(kern, dim3(grid), dim3(64 * kW * kKeySplit), lds_bytes + lds_extra, a.stream,
               static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K), static_cast<const uint16_t*>(a.V), a.O, a.N, nqb,
-              a.scale * kLog2e, (unsigned)nwg);
+              host_scale_log2e(a.scale), (unsigned)nwg);
     if (launch_status() != hipSuccess) return launch_status();
     if constexpr (!kDma && 16 * X * (D / 64) >= 64) {
         // full-width waves: the redo kernel for the row blocks whose optimistic passes failed (see kScan): half-width waves,
@@ -1312,7 +1312,7 @@ static hipError_t launch_rp16(const FwdArgs& a)
         static_assert(2 * kRows2 == kRows, "the redo kernel's row block is half of this kernel's");
         FA_LAUNCH(kern2, dim3(grid2), dim3(64 * kW2), lds2, a.stream,
                   static_cast<const uint16_t*>(a.Q), static_cast<const uint16_t*>(a.K), static_cast<const uint16_t*>(a.V), a.O, a.N, nqb2,
-                  a.scale * kLog2e, (unsigned)nwg2);
+                  host_scale_log2e(a.scale), (unsigned)nwg2);
     }
     return launch_status();
 }

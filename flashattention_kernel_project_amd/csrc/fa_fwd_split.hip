@@ -63,11 +63,11 @@ static hipError_t launch_split(const void* Q, const void* K, const void* V, void
     if (attr != hipSuccess) return attr;
     if (S == 1) {
         FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, false>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                           stream, q, k, v, O, static_cast<float*>(nullptr), Nq, Nk, nqb, S, chunk, scale * kLog2e);
+                           stream, q, k, v, O, static_cast<float*>(nullptr), Nq, Nk, nqb, S, chunk, host_scale_log2e(scale));
         return launch_status();
     }
     FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, true>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                       stream, q, k, v, O, static_cast<float*>(ws), Nq, Nk, nqb, S, chunk, scale * kLog2e);
+                       stream, q, k, v, O, static_cast<float*>(ws), Nq, Nk, nqb, S, chunk, host_scale_log2e(scale));
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
     const long long rows = (long long)BH * Nq;   // one wave per output row

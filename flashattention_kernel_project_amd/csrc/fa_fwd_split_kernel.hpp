@@ -113,7 +113,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         }
     }
 
-    // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf
+    // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf.  Redundant behind host_scale_log2e() (fa_dispatch.hpp), which
+    // hands every kernel +-FLT_MIN in place of 0: that host rule is what makes scale 0 safe, here and in the plain instantiations.
     const float c = kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
     const unsigned q_flip = scale_log2e < 0.0f ? 0x80008000u : 0u;
     u32x4 qf[G::kKSteps];

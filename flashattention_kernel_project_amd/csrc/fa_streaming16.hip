@@ -100,7 +100,7 @@ hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, flo
     if (!Q || !K || !V || !O || num_batches <= 0 || seq_len <= 0) return hipErrorInvalidValue;
     if ((long long)seq_len * 32 >= (1ll << 31)) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((num_batches + kS16WavesPerBlock - 1) / kS16WavesPerBlock);
-    const float c = scale * kLog2e;
+    const float c = host_scale_log2e(scale);
     if (k_transposed)
         FA_LAUNCH(fa_streaming16_kernel<true>, dim3(grid), dim3(64 * kS16WavesPerBlock), 0, stream,
                            (const uint16_t*)Q, (const uint16_t*)K, (const uint16_t*)V, O, num_batches, seq_len, c);

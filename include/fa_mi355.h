@@ -69,7 +69,11 @@ int flashattn_forward_wmma(const void* Q, const void* K, const void* V, float* O
                            int BH, int N, int D, float scale, void* stream);
 
 /* The same operation with the dtype / output / kernel choices BASELINE's configs need
- * (bf16 inputs, 16-bit outputs, B and H separate).  BH = B*H.  Same layouts as above. */
+ * (bf16 inputs, 16-bit outputs, B and H separate).  BH = B*H.  Same layouts as above.
+ * scale, here and in every entry point below: the logits are scale * q.k.  Any finite value is valid; a negative one negates
+ * the logits.  scale = 0 -- any scale with |scale * log2(e)| < FLT_MIN -- gives every key a row sees the same weight: O is the
+ * mean of their V rows (lse = ln of their number), never NaN, under every mask and at ragged sizes.  (The library hands the
+ * kernels +-FLT_MIN in its place, so that a masked score of -inf is never multiplied by 0.) */
 int fa_forward(const void* Q, const void* K, const void* V, void* O,
                int B, int H, int N, int d, float scale,
                int in_dtype, int out_dtype, void* stream);
