@@ -33,6 +33,8 @@ SYMBOLS = (
     "fa_selected_kernel",
     "fa_forward_kvcache_workspace_bytes",
     "fa_forward_kvcache",
+    "fa_forward_kvcache_fp8",
+    "fa_forward_kvcache_paged_fp8",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -107,6 +109,10 @@ def lib() -> C.CDLL:
         L.fa_forward_kvcache_workspace_bytes.restype = C.c_size_t
         L.fa_forward_kvcache_paged.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
         L.fa_forward_kvcache_paged.restype = C.c_int
+        L.fa_forward_kvcache_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache_fp8.restype = C.c_int
+        L.fa_forward_kvcache_paged_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache_paged_fp8.restype = C.c_int
         L.fa_forward_kvcache_paged_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_workspace_bytes.restype = C.c_size_t
         L.fa_mi355_version.argtypes = []

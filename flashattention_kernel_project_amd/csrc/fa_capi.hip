@@ -109,6 +109,24 @@ FA_EXPORT int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const v
                                       block_table, num_pages, page_size, max_pages});
 }
 
+FA_EXPORT int fa_forward_kvcache_fp8(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse, const int* seqlens_k,
+                           const float* k_scale, const float* v_scale, int B, int Hkv, int G, int Nq, int Ncap, int d, float scale,
+                           int causal, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvcache_fp8_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                          workspace, workspace_bytes, static_cast<hipStream_t>(stream)}, k_scale, v_scale);
+}
+
+FA_EXPORT int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* seqlens_k,
+                                 const int* block_table, const float* k_scale, const float* v_scale, int B, int Hkv, int G, int Nq,
+                                 int num_pages, int page_size, int max_pages, int d, float scale, int causal, int in_dtype,
+                                 int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvpaged_fp8_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                           workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                          block_table, num_pages, page_size, max_pages}, k_scale, v_scale);
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

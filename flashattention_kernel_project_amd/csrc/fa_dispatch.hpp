@@ -71,7 +71,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -91,6 +91,7 @@ struct KvCacheArgs {
     hipStream_t stream;
 };
 hipError_t kvcache_dispatch(const KvCacheArgs& a);
+hipError_t kvcache_check(const KvCacheArgs& a);   // the argument checks of kvcache_dispatch alone
 size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D);
 hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
                            hipStream_t stream);   // the merge kernel of the KV-cache split, launched for the paged entry too
@@ -102,6 +103,11 @@ struct KvPagedArgs {
     int num_pages, page_size, max_pages;
 };
 hipError_t kvpaged_dispatch(const KvPagedArgs& a);
+hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& with_capacity, int& lg_page);   // the argument checks of kvpaged_dispatch alone
+// fp8 (OCP e4m3fn) caches -- fa_fwd_kvfp8.hip: K, V point at one-byte elements that are widened to in_dtype on the way into LDS;
+// k_scale, v_scale: device, Hkv fp32 each, or null (1.0).  Everything else as in the two entries above, workspace included.
+hipError_t kvcache_fp8_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale);
+hipError_t kvpaged_fp8_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale);
 size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);

@@ -47,7 +47,9 @@ size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D)
     return split_workspace_bytes(B * Hkv, G * Nq, Ncap, D);
 }
 
-hipError_t kvcache_dispatch(const KvCacheArgs& a)
+// What every KV-cache entry rejects before the device is touched (the fp8 entries of fa_fwd_kvfp8.hip too: their one-byte
+// elements keep the 16-bit bound on the byte offsets).
+hipError_t kvcache_check(const KvCacheArgs& a)
 {
     if (!a.Q || !a.K || !a.V || !a.O) return hipErrorInvalidValue;
     if (a.B <= 0 || a.Hkv <= 0 || a.G <= 0 || a.Nq <= 0 || a.Ncap <= 0 || (a.D != 64 && a.D != 128)) return hipErrorInvalidValue;
@@ -55,10 +57,18 @@ hipError_t kvcache_dispatch(const KvCacheArgs& a)
     if (a.in_dtype != 0 && a.in_dtype != 1) return hipErrorInvalidValue;
     if (a.out_dtype != 0 && a.out_dtype != 1) return hipErrorInvalidValue;
     if ((long long)a.B * a.Hkv > 0x7FFFFFFFll || (long long)a.G * a.Nq > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    const int BH = a.B * a.Hkv, rows = a.G * a.Nq;
+    const int rows = a.G * a.Nq;
     // per-head byte offsets are 32 bit: the checks of split_dispatch, on the folded rows and the capacity
     if (((unsigned long long)rows + split::kRows) * (unsigned)(a.D + 2) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
     if (((unsigned long long)a.Ncap + kBlockN) * (unsigned)a.D * 2ull >= (1ull << 32)) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+hipError_t kvcache_dispatch(const KvCacheArgs& a)
+{
+    const hipError_t bad = kvcache_check(a);
+    if (bad != hipSuccess) return bad;
+    const int BH = a.B * a.Hkv, rows = a.G * a.Nq;
     if (a.D == 64)
         return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
             return launch_kvcache<decltype(t), 64, decltype(f32)::value>(a, BH, rows);

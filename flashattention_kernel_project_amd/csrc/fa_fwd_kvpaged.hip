@@ -51,25 +51,28 @@ size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int
     return kvcache_workspace_bytes(B, Hkv, G, Nq, max_pages * page_size, D);
 }
 
-hipError_t kvpaged_dispatch(const KvPagedArgs& p)
+// What the paged entries (fa_fwd_kvfp8.hip's too) reject before the device is touched.  On success q is p with the capacity
+// filled in and lg_page the log2 of the page size.
+hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& q, int& lg_page)
 {
-    const int lg_page = page_log2(p.page_size);
+    lg_page = page_log2(p.page_size);
     if (!p.table || lg_page < 0 || p.num_pages <= 0 || p.max_pages <= 0) return hipErrorInvalidValue;
     if ((long long)p.max_pages * p.page_size > 0x7FFFFFFFll) return hipErrorInvalidValue;   // the capacity is an int
-    KvPagedArgs q = p;
-    KvCacheArgs& a = q.c;
-    a.Ncap = p.max_pages * p.page_size;
-    // from here on the checks of kvcache_dispatch, on that capacity
-    if (!a.Q || !a.K || !a.V || !a.O) return hipErrorInvalidValue;
-    if (a.B <= 0 || a.Hkv <= 0 || a.G <= 0 || a.Nq <= 0 || (a.D != 64 && a.D != 128)) return hipErrorInvalidValue;
-    if (a.causal != 0 && a.causal != 1) return hipErrorInvalidValue;
-    if (a.in_dtype != 0 && a.in_dtype != 1) return hipErrorInvalidValue;
-    if (a.out_dtype != 0 && a.out_dtype != 1) return hipErrorInvalidValue;
-    if ((long long)a.B * a.Hkv > 0x7FFFFFFFll || (long long)a.G * a.Nq > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    q = p;
+    q.c.Ncap = p.max_pages * p.page_size;
+    // from here on the checks of kvcache_dispatch, on that capacity.  Its bound on the byte offsets covers what is 32 bit in the
+    // kernel here: a tile's byte offset before it is reduced to the page (hence the page-head block too)
+    return kvcache_check(q.c);
+}
+
+hipError_t kvpaged_dispatch(const KvPagedArgs& p)
+{
+    KvPagedArgs q;
+    int lg_page;
+    const hipError_t bad = kvpaged_check(p, q, lg_page);
+    if (bad != hipSuccess) return bad;
+    const KvCacheArgs& a = q.c;
     const int BH = a.B * a.Hkv, rows = a.G * a.Nq;
-    if (((unsigned long long)rows + split::kRows) * (unsigned)(a.D + 2) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
-    // 32 bit in the kernel: a tile's byte offset before it is reduced to the page (hence the page-head block too)
-    if (((unsigned long long)a.Ncap + kBlockN) * (unsigned)a.D * 2ull >= (1ull << 32)) return hipErrorInvalidValue;
     if (a.D == 64)
         return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
             return launch_kvpaged<decltype(t), 64, decltype(f32)::value>(q, BH, rows, lg_page);

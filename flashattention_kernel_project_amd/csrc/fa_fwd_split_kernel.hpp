@@ -1,9 +1,11 @@
 // fa_fwd_split_kernel.hpp -- device code of the split-KV stream, shared by fa_fwd_split.hip (fa_forward_splitkv),
-// fa_fwd_kvcache.hip (fa_forward_kvcache) and fa_fwd_kvpaged.hip (fa_forward_kvcache_paged).  One kernel template serves all
-// three: what the KV-cache entry adds is a template flag and a trailing parameter pack, so the plain instantiations keep their
-// argument list and their code (profiles/kvcache_decode.txt); the paged entry passes a PagedArgs in that pack, and everything it
-// adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt).
-// The three sets are instantiated in separate translation units so that none perturbs another's register allocation.
+// fa_fwd_kvcache.hip (fa_forward_kvcache), fa_fwd_kvpaged.hip (fa_forward_kvcache_paged) and fa_fwd_kvfp8.hip (the two _fp8
+// entries).  One kernel template serves all of them: what the KV-cache entry adds is a template flag and a trailing parameter
+// pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt); the paged entry passes
+// a PagedArgs in that pack, and everything it adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt); the fp8
+// entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
+// selects (profiles/kvcache_fp8.txt).
+// The sets are instantiated in separate translation units so that none perturbs another's register allocation.
 // The design notes are at the head of fa_fwd_split.hip and in DESIGN.md 7.1.
 #pragma once
 #include "fa_tile.hpp"
@@ -46,6 +48,40 @@ __device__ __forceinline__ NoPages paged_part() { return {}; }
 __device__ __forceinline__ NoPages paged_part(const CacheArgs&) { return {}; }
 __device__ __forceinline__ const PagedArgs& paged_part(const PagedArgs& p) { return p; }
 
+// What the fp8 instantiations take: the CacheArgs or the PagedArgs plus the dequantisation scales.  K/V elements are then ONE byte
+// (OCP e4m3fn) and are widened to T while a tile is written to LDS; the kernel's K/V pointers address bytes.
+template <typename Base> struct Fp8Args : Base {
+    const float* k_scale;   // [Hkv] on the device, or nullptr (1.0): the logits are scale * k_scale[hkv] * q.k8
+    const float* v_scale;   // [Hkv] on the device, or nullptr (1.0): the output is v_scale[hkv] * softmax.v8
+};
+template <typename A> struct IsFp8Args : std::false_type {};
+template <typename Base> struct IsFp8Args<Fp8Args<Base>> : std::true_type {};
+struct NoScales {};
+__device__ __forceinline__ NoScales fp8_part() { return {}; }
+__device__ __forceinline__ NoScales fp8_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const Fp8Args<Base>& fp8_part(const Fp8Args<Base>& f) { return f; }
+
+// Two e4m3fn bytes of w (kHi: bytes 2 and 3) as one packed pair of T.  Every e4m3fn value is a normal number of fp16 and of bf16,
+// so the conversion is exact, and the NaN codes 0x7F / 0xFF stay NaN.  One v_cvt_scalef32_pk_{f16,bf16}_fp8 with a scale of 1.
+// FA_FP8_VIA_F32 takes the way through fp32 (v_cvt_pk_f32_fp8, then the pack of the type), which is exact for the same reason.
+#ifndef FA_FP8_VIA_F32
+#define FA_FP8_VIA_F32 0
+#endif
+template <typename T, bool kHi> __device__ __forceinline__ unsigned fp8x2_widen(unsigned w) {
+#if FA_FP8_VIA_F32
+    const f32x2 f = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, kHi);
+    return T::pack2(f[0], f[1]);
+#else
+    if constexpr (T::id == 0) return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, kHi));
+    else return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, kHi));
+#endif
+}
+// 16 e4m3fn bytes (one load) -> the two 16-byte LDS chunks of 8 elements of T they become
+template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u32x4& lo, u32x4& hi) {
+    lo = u32x4{fp8x2_widen<T, false>(raw[0]), fp8x2_widen<T, true>(raw[0]), fp8x2_widen<T, false>(raw[1]), fp8x2_widen<T, true>(raw[1])};
+    hi = u32x4{fp8x2_widen<T, false>(raw[2]), fp8x2_widen<T, true>(raw[2]), fp8x2_widen<T, false>(raw[3]), fp8x2_widen<T, true>(raw[3])};
+}
+
 // kPartial: write (O^T unnormalised, m, l) to the workspace instead of the normalised output.
 // kCache: the key count L of the head's sequence is read on the device (Nk is then the capacity, the stride of a K/V head) and the
 // split's chunk follows from L; every row has its own key limit; a row or a split without a key is neutral (m = -inf, l = 0, O = 0).
@@ -56,6 +92,14 @@ __device__ __forceinline__ const PagedArgs& paged_part(const PagedArgs& p) { ret
 // read 0 as the end of the contiguous descriptor does).  The page numbers of the tile after next are fetched while the current
 // tile computes, so no tile but a split's first waits for the table.  Splits, tile order, masks and arithmetic are the kCache
 // ones: on the same keys the result is bit-equal to the contiguous entry's.
+// kFp8 (kCache with an Fp8Args in the pack): a K/V row is D bytes.  One 16-byte load carries 16 elements, the two adjacent LDS
+// chunks 2c and 2c + 1 of a row, so a thread issues half the loads per tile (1 at D = 64, 2 at D = 128, each for K and for V),
+// keeps the raw bytes across the tile's arithmetic and widens them in stage_write(): the LDS image, and everything that reads it,
+// is the 16-bit kernels'.  One wave's loads for one p cover 16 rows at D = 64 and 8 at D = 128, aligned to as many -- still inside
+// one page of >= 16 keys, so the paged scheme carries over with byte counts per one-byte element.  k_scale joins scale_log2e
+// (the FLT_MIN clamp comes AFTER the product: +-FLT_MIN * 0.5 must not meet a masked -inf as 0); v_scale joins 1 / l in the
+// one-pass kernel and the accumulators before the workspace store in the partial one, so the merge kernel is the 16-bit one.
+// With scales of 1 the result is bit-equal to the 16-bit kernels' on the widened cache.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -68,11 +112,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                          int Nq, int Nk, int nqb, int S, int chunk, float scale_log2e, Cache... cache)
 {
     static_assert(sizeof...(Cache) == (kCache ? 1 : 0), "the KV-cache instantiations take one CacheArgs or PagedArgs, the plain ones nothing");
-    [[maybe_unused]] const CacheArgs ca = {cache...};
-    constexpr bool kPaged = (std::is_same_v<Cache, PagedArgs> || ...);
-    [[maybe_unused]] const auto pa = paged_part(cache...);
-    using namespace split;
     using G = TileGeom<D>;
+    [[maybe_unused]] const CacheArgs ca = {cache...};
+    constexpr bool kPaged = (std::is_base_of_v<PagedArgs, Cache> || ...);
+    [[maybe_unused]] const auto pa = paged_part(cache...);
+    constexpr bool kFp8 = (IsFp8Args<Cache>::value || ...);
+    [[maybe_unused]] const auto fa8 = fp8_part(cache...);
+    constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
+    constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
+    using namespace split;
     constexpr int W = kW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -96,10 +144,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     const unsigned key1 = min(nkeys, key0 + (unsigned)chunk);         // exclusive
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(Qg + (size_t)bh * Nq * D, (unsigned)((size_t)Nq * D * 2));
     // K/V descriptors end at this split's last key: rows beyond it read 0 and are masked below
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kg + (size_t)bh * Nk * D, key1 * (unsigned)D * 2u);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(Vg + (size_t)bh * Nk * D, key1 * (unsigned)D * 2u);
+    // element offset -> address: the fp8 instantiations get byte pointers in Kg / Vg
+    [[maybe_unused]] auto kv_at = [](const uint16_t* base, size_t elems) -> const void* {
+        if constexpr (kFp8) return reinterpret_cast<const uint8_t*>(base) + elems;
+        else return base + elems;
+    };
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(kv_at(Kg, (size_t)bh * Nk * D), key1 * kKvRowBytes);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(kv_at(Vg, (size_t)bh * Nk * D), key1 * kKvRowBytes);
 
-    constexpr int kLoadsW = (kBlockN * G::kChunks) / (64 * W);
+    constexpr int kLoadsW = (kBlockN * kLdChunks) / (64 * W);
     const unsigned q_row = qb * (unsigned)kRows + wave * 32u + r;
     const bool has_rows = qb * (unsigned)kRows + wave * 32u < (unsigned)Nq;   // wave-uniform
 
@@ -115,7 +168,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 
     // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf.  Redundant behind host_scale_log2e() (fa_dispatch.hpp), which
     // hands every kernel +-FLT_MIN in place of 0: that host rule is what makes scale 0 safe, here and in the plain instantiations.
-    const float c = kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
+    // kFp8: the head's k_scale is part of the factor, and the clamp applies to the product; v_scale is used at the end
+    [[maybe_unused]] float k_scale = 1.0f, v_scale = 1.0f;
+    if constexpr (kFp8) {
+        const unsigned hkv = bh % (unsigned)ca.Hkv;
+        if (fa8.k_scale) k_scale = fa8.k_scale[hkv];
+        if (fa8.v_scale) v_scale = fa8.v_scale[hkv];
+    }
+    const float c = kFp8 ? fmaxf(fabsf(scale_log2e * k_scale), 1.17549435e-38f)
+                         : kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
     const unsigned q_flip = scale_log2e < 0.0f ? 0x80008000u : 0u;
     u32x4 qf[G::kKSteps];
 #pragma unroll
@@ -130,10 +191,12 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 #pragma unroll
     for (int p = 0; p < kLoadsW; ++p) {
         const unsigned idx = tid + p * 64u * W;
-        const unsigned row = idx / G::kChunks, ch = idx % G::kChunks;
-        g_off[p] = row * G::kRowBytes + ch * 16u;
-        k_lds[p] = G::k_off(row, ch);
-        v_lds[p] = G::kTileBytes + G::v_off(row, ch);
+        const unsigned row = idx / kLdChunks, ch = idx % kLdChunks;
+        g_off[p] = row * kKvRowBytes + ch * 16u;
+        // kFp8: the load holds the LDS chunks 2 ch and 2 ch + 1; the second one's offset is the first's with bit 4 flipped, in
+        // the K image (the swizzle XORs the chunk index) and in the V image (chunk & 3 is even)
+        k_lds[p] = G::k_off(row, kFp8 ? 2u * ch : ch);
+        v_lds[p] = G::kTileBytes + G::v_off(row, kFp8 ? 2u * ch : ch);
     }
     u32x4 kst[kLoadsW], vst[kLoadsW];
     // kPaged: the page numbers of the tile that is staged next, one per (wave, p), in scalar registers.  fetch_pages() reads
@@ -146,7 +209,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             const unsigned last = (key1 - 1u) >> pa.lg_page;   // only called with key1 > key0 >= 0
 #pragma unroll
             for (int p = 0; p < kLoadsW; ++p) {
-                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;   // first row of the tile this wave loads with p
+                const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;   // first row of the tile this wave loads with p
                 pg[p] = __builtin_amdgcn_readfirstlane(tbl[min((kv0 + wrow) >> pa.lg_page, last)]);
             }
         }
@@ -156,31 +219,41 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         for (int p = 0; p < kLoadsW; ++p) {
             if constexpr (kPaged) {
                 const unsigned page = 1u << pa.lg_page;
-                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;
+                const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;
                 const unsigned first = (kv0 + wrow) & ~(page - 1u);             // first key of the page
                 const bool ok = (unsigned)pg[p] < (unsigned)pa.num_pages && first < key1;
                 // the page's rows below key1; a bad page number or a page past the split's end: no record, every load reads 0
-                const unsigned bytes = ok ? min(page, key1 - first) * (unsigned)G::kRowBytes : 0u;
+                const unsigned bytes = ok ? min(page, key1 - first) * kKvRowBytes : 0u;
                 // 64-bit: pools beyond 4 GiB are normal; only the offset inside one page-head block is 32 bit
                 const size_t blk = (((size_t)(ok ? pg[p] : 0) * (unsigned)ca.Hkv + bh % (unsigned)ca.Hkv) << pa.lg_page) * D;
-                const __amdgpu_buffer_rsrc_t pk = make_rsrc(Kg + blk, bytes), pv = make_rsrc(Vg + blk, bytes);
-                const unsigned off = (kv0 * G::kRowBytes + g_off[p]) & (page * G::kRowBytes - 1u);
+                const __amdgpu_buffer_rsrc_t pk = make_rsrc(kv_at(Kg, blk), bytes), pv = make_rsrc(kv_at(Vg, blk), bytes);
+                const unsigned off = (kv0 * kKvRowBytes + g_off[p]) & (page * kKvRowBytes - 1u);
                 kst[p] = buf_load16_nt(pk, off);
                 vst[p] = buf_load16_nt(pv, off);
                 continue;
             }
 #if FA_SPLIT_NT
-            kst[p] = buf_load16_nt(rk, kv0 * G::kRowBytes + g_off[p]);
-            vst[p] = buf_load16_nt(rv, kv0 * G::kRowBytes + g_off[p]);
+            kst[p] = buf_load16_nt(rk, kv0 * kKvRowBytes + g_off[p]);
+            vst[p] = buf_load16_nt(rv, kv0 * kKvRowBytes + g_off[p]);
 #else
-            kst[p] = buf_load16(rk, kv0 * G::kRowBytes + g_off[p]);
-            vst[p] = buf_load16(rv, kv0 * G::kRowBytes + g_off[p]);
+            kst[p] = buf_load16(rk, kv0 * kKvRowBytes + g_off[p]);
+            vst[p] = buf_load16(rv, kv0 * kKvRowBytes + g_off[p]);
 #endif
         }
     };
     auto stage_write = [&](unsigned buf) {
 #pragma unroll
         for (int p = 0; p < kLoadsW; ++p) {
+            if constexpr (kFp8) {
+                u32x4 lo, hi;
+                fp8x16_widen<T>(kst[p], lo, hi);
+                lds_write16(smem, buf * G::kBufBytes + k_lds[p], lo);
+                lds_write16(smem, buf * G::kBufBytes + (k_lds[p] ^ 16u), hi);
+                fp8x16_widen<T>(vst[p], lo, hi);
+                lds_write16(smem, buf * G::kBufBytes + v_lds[p], lo);
+                lds_write16(smem, buf * G::kBufBytes + (v_lds[p] ^ 16u), hi);
+                continue;
+            }
             lds_write16(smem, buf * G::kBufBytes + k_lds[p], kst[p]);
             lds_write16(smem, buf * G::kBufBytes + v_lds[p], vst[p]);
         }
@@ -305,6 +378,12 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         // workspace row (bh, sp, q_row): D floats of O^T (unnormalised), then m, then l
         const size_t rows = (size_t)Nq;
         const unsigned rs = (unsigned)(D + 2) * 4u;
+        if constexpr (kFp8) {   // v_scale goes into the partial, so the merge kernel needs no scale
+#pragma unroll
+            for (int db = 0; db < G::kDBlocks; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[db][i] *= v_scale;
+        }
         const __amdgpu_buffer_rsrc_t rw =
             make_rsrc(ws + ((size_t)bh * S + sp) * rows * (D + 2), (unsigned)(rows * rs));
 #pragma unroll
@@ -321,7 +400,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if (h == 0)
             buf_store8(rw, q_row * rs + (unsigned)D * 4u, u32x2{__float_as_uint(m_ref), __float_as_uint(l)});
     } else {
-        const float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        if constexpr (kFp8) inv *= v_scale;
         if constexpr (kCache) {
             if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
                 buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), q_row * 4u,

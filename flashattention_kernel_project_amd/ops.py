@@ -259,6 +259,138 @@ def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: 
     return int(capi.lib().fa_forward_kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d))
 
 
+_FP8_CACHE = "an fp8 cache must be torch.float8_e4m3fn (OCP e4m3fn, the gfx950 format); float8_e4m3fnuz, float8_e5m2 and " \
+             "16-bit caches are not accepted here"
+
+
+def _fp8_decode_args(q, k8, v8, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, what):
+    """What the two fp8 decode front ends share once the shapes are known: dtype checks, scales, lengths, outputs.
+    k8/v8: [*, Hkv, rows, d] float8_e4m3fn.  -> (pointers in ABI order up to v_scale without the table, out, lse, in_dt, out_dt)"""
+    import torch
+    B, Hq, Nq, d = q.shape
+    Hkv = k8.shape[1]
+    if k8.dtype != torch.float8_e4m3fn or v8.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{what}: {_FP8_CACHE} (got {k8.dtype}, {v8.dtype})")
+    dts = (torch.float16, torch.bfloat16)
+    if q.dtype not in dts:
+        raise ValueError("q must be fp16 or bf16")
+    if Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    scale_ptrs = []
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            scale_ptrs.append(None)
+            continue
+        if not isinstance(s, torch.Tensor) or s.dim() != 1 or s.shape[0] != Hkv or s.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 device tensor of shape [Hkv] = [{Hkv}]")
+        scale_ptrs.append(_dev_ptr(s, name, (torch.float32,)))
+    len_ptr = None
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
+            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
+        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k8, "k cache", (torch.float8_e4m3fn,)), _dev_ptr(v8, "v cache", (torch.float8_e4m3fn,)))
+    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    out_dt = capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME
+    return ptrs, len_ptr, scale_ptrs, out, lse, in_dt, out_dt
+
+
+def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, causal: bool = False,
+                           scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+    """fa_forward_kvcache against an fp8 cache (fa_forward_kvcache_fp8): q [B,Hq,Nq,d] fp16/bf16, k_cache/v_cache [B,Hkv,Ncap,d]
+    torch.float8_e4m3fn (OCP e4m3fn; fnuz and e5m2 are refused) device tensors, d in {64,128}.  K and V are widened to q's type
+    on the way into the kernel, exactly.
+    k_scale, v_scale: float32 contiguous device tensors [Hkv], or None (1.0): the logits are scale * k_scale[h] * q.k8, the output
+    is v_scale[h] * softmax.v8, lse is that of the scaled logits.  Scales must be finite and > 0; they are read on the device only,
+    like cache_seqlens, so a captured call follows all three when they are rewritten in place.  quantize_kv_fp8() makes a cache
+    and its scales from a 16-bit or fp32 tensor.
+    Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes) -- is
+    fa_forward_kvcache's."""
+    import torch
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
+            or q.shape[3] != k_cache.shape[3]:
+        raise ValueError("q must be [B,Hq,Nq,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
+    B, Hq, Nq, d = q.shape
+    Hkv, Ncap = k_cache.shape[1], k_cache.shape[2]
+    ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
+        q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_cache, v_cache")
+    G = Hq // Hkv
+    need = kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)   # the 16-bit entry's, from the shape alone
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    with torch.cuda.device(_one_device(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, workspace)):
+        code = capi.lib().fa_forward_kvcache_fp8(
+            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq, Ncap, d,
+            float(scale), 1 if causal else 0, in_dt, out_dt, ws_ptr, ws_len, _stream_ptr(stream))
+    capi.check("fa_forward_kvcache_fp8", code)
+    return (out, lse) if return_lse else out
+
+
+def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
+                                 causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
+                                 workspace=None, stream=None):
+    """fa_forward_kvcache_paged against fp8 pools (fa_forward_kvcache_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
+    torch.float8_e4m3fn, block_table as in fa_forward_kvcache_paged, k_scale / v_scale and everything else as in
+    fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes."""
+    import torch
+    if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
+        raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
+    B, Hq, Nq, d = q.shape
+    num_pages, Hkv, page_size = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    if k_pool.dtype != torch.float8_e4m3fn or v_pool.dtype != torch.float8_e4m3fn:   # judged first, as in the contiguous front end
+        raise ValueError(f"k_pool, v_pool: {_FP8_CACHE} (got {k_pool.dtype}, {v_pool.dtype})")
+    if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
+    max_pages = block_table.shape[1]
+    tbl_ptr = _dev_ptr(block_table, "block_table", (torch.int32,))
+    ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
+        q, k_pool, v_pool, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_pool, v_pool")
+    G = Hq // Hkv
+    need = kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # the 16-bit entry's, from the shape alone
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, workspace)):
+        code = capi.lib().fa_forward_kvcache_paged_fp8(
+            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq,
+            num_pages, page_size, max_pages, d, float(scale), 1 if causal else 0, in_dt, out_dt, ws_ptr, ws_len,
+            _stream_ptr(stream))
+    capi.check("fa_forward_kvcache_paged_fp8", code)
+    return (out, lse) if return_lse else out
+
+
+FP8_E4M3_MAX = 448.0   # largest finite e4m3fn value
+
+
+def quantize_kv_fp8(x, scale=None):
+    """x [*, Hkv, N, d] (head axis at dim 1: a cache [B,Hkv,Ncap,d] or a pool [num_pages,Hkv,page_size,d]), any float type, CPU or
+    GPU -> (x8 torch.float8_e4m3fn of x's shape, scale float32 [Hkv]) with x ~= x8 * scale[h].
+    scale[h] = amax over head h / 448 (1.0 for a head of zeros), so each head's largest magnitude lands on +-448; or the given
+    `scale` (float32 [Hkv], finite and > 0: scales calibrated elsewhere), returned as it is.  The quotient is clamped to +-448
+    before the conversion: torch's conversion to float8_e4m3fn does not saturate (a value that rounds past 448 becomes NaN)."""
+    import torch
+    if x.dim() != 4:
+        raise ValueError("x must be [*, Hkv, N, d]")
+    xf = x.float()
+    if scale is None:
+        amax = xf.abs().amax(dim=(0, 2, 3))
+        scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    elif scale.shape != (x.shape[1],) or scale.dtype != torch.float32 or scale.device != x.device:
+        raise ValueError("scale must be a float32 tensor of shape [Hkv] on x's device")
+    x8 = (xf / scale.view(1, -1, 1, 1)).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return x8, scale.contiguous()
+
+
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):
     import torch
     if Q.numel() != num_batches * 256 or K.numel() != num_batches * 16 * seq_len \

@@ -9,6 +9,8 @@ eager fallback.  Registered on first use:
     o = torch.ops.fa_mi355.forward(q, k, v, scale, causal, out_fp32)
     o = torch.ops.fa_mi355.decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache
     o = torch.ops.fa_mi355.decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_paged
+    o = torch.ops.fa_mi355.decode_fp8(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_fp8
+    o = torch.ops.fa_mi355.decode_paged_fp8(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode and .decode_paged (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8 and .decode_paged_fp8 (idempotent)."""
     global _registered
     if _registered:
         return
@@ -60,6 +62,35 @@ def register() -> None:
 
     @decode_paged.register_fake
     def _(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    def opt(t):
+        return None if t is None else t.contiguous()
+
+    @torch.library.custom_op("fa_mi355::decode_fp8", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
+    def decode_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
+                                          opt(cache_seqlens), causal=causal, scale=scale,
+                                          out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
+
+    @decode_fp8.register_fake
+    def _(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode_paged_fp8", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
+    def decode_paged_fp8(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
+                                                out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
+
+    @decode_paged_fp8.register_fake
+    def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
         return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
 
     _registered = True

@@ -126,7 +126,7 @@ int fa_forward_splitkv(const void* Q, const void* K, const void* V, void* O,
  * sequence are divided among its splits by L_b, not by Ncap: a cache filled to a fraction still uses every split.
  * Workspace as for fa_forward_splitkv (size from fa_forward_kvcache_workspace_bytes(); 0: `workspace` may be NULL).
  * Sliding windows and appending to the cache are not part of this entry; a paged (block-table) cache goes through
- * fa_forward_kvcache_paged below.
+ * fa_forward_kvcache_paged below, an fp8 cache through fa_forward_kvcache_fp8.
  * NOT a reference entry point. */
 size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d);
 int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, void* O,
@@ -157,7 +157,8 @@ int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, vo
  * hipErrorInvalidValue, before the device is touched: a null Q, Kpool, Vpool, O or block_table; a page_size that is not a power of
  * two or is below 16; num_pages <= 0 or max_pages <= 0; max_pages * page_size beyond int or beyond the 32-bit byte offsets
  * fa_forward_kvcache allows for its Ncap; everything else fa_forward_kvcache rejects.
- * Appending the new token's K/V, sliding windows and fp8 caches are not part of this entry.  NOT a reference entry point. */
+ * Appending the new token's K/V and sliding windows are not part of this entry; fp8 pools go through fa_forward_kvcache_paged_fp8
+ * below.  NOT a reference entry point. */
 size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d);
 int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool, void* O,
                              float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
@@ -167,6 +168,47 @@ int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool
                              int num_pages, int page_size, int max_pages, int d,
                              float scale, int causal, int in_dtype, int out_dtype,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* fa_forward_kvcache and fa_forward_kvcache_paged against an fp8 cache with one dequantisation scale per K/V head.
+ *   Kcache, Vcache  [B, Hkv, Ncap, d], resp. Kpool, Vpool [num_pages, Hkv, page_size, d]: ONE byte per element, OCP e4m3fn (the gfx950
+ *                   format: bias 7, 3 mantissa bits, no infinities, 0x7F / 0xFF NaN) -- not MI300X's e4m3fnuz, not e5m2.
+ *   Q, O            as in the 16-bit entries; in_dtype is Q's type, and the type K and V are widened to on the way into the kernel.
+ *                   Every e4m3fn value is exactly representable in fp16 and in bf16, so widening adds no error.
+ *   k_scale, v_scale  device, Hkv fp32 each, or NULL (1.0 for every head).  The logits are scale * k_scale[hkv] * q.k8, the output is
+ *                   v_scale[hkv] * softmax.v8, and lse is that of the scaled logits.  A scale must be finite and > 0.  Scales only
+ *                   enter arithmetic: a bad one gives a meaningless result, never an out-of-range access.
+ * Codes 0x7F and 0xFF behave as a NaN in a 16-bit cache does; rows at or past L_b and pages that are not live are never read and may
+ * hold them.
+ * Everything else is the 16-bit entries' contract: d in {64,128}; the length clamp; rows without a key (O = 0, lse = -inf); causal;
+ * page_size a power of two >= 16, bad live table entries read as zeros, 64-bit page addresses; the same hipErrorInvalidValue cases
+ * before the device is touched (the bound on Ncap is the 16-bit entries', although a row is half as long).  The workspace is exactly
+ * what the 16-bit entry takes for the same shape: size it with fa_forward_kvcache_workspace_bytes() /
+ * fa_forward_kvcache_paged_workspace_bytes().
+ * Nothing on the host reads seqlens_k, block_table, k_scale or v_scale: a captured call follows all of them when they are rewritten in
+ * place.  scale = 0 keeps its meaning (uniform weights, never NaN) for every k_scale: |scale * log2(e) * k_scale| is clamped to FLT_MIN
+ * on the device, after the product.
+ * Splits, tile order and arithmetic are the 16-bit entries': with all scales 1, O and lse equal fa_forward_kvcache[_paged] on the
+ * widened cache bit for bit; a power-of-two k_scale equals that entry called with scale * k_scale, a power-of-two v_scale multiplies
+ * its fp32 result exactly.
+ * fp8 Q, e5m2, per-token or per-block scales and appending are not part of these entries.  NOT reference entry points. */
+int fa_forward_kvcache_fp8(const void* Q, const void* Kcache, const void* Vcache, void* O,
+                           float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                           const int* seqlens_k,  /* device, B int32, may be NULL (= Ncap for all) */
+                           const float* k_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                           const float* v_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                           int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal,
+                           int in_dtype, int out_dtype,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                                 float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                                 const int* seqlens_k,    /* device, B int32, may be NULL (= Ncap for all) */
+                                 const int* block_table,  /* device, [B,max_pages] int32 */
+                                 const float* k_scale,    /* device, Hkv fp32, may be NULL (= 1.0) */
+                                 const float* v_scale,    /* device, Hkv fp32, may be NULL (= 1.0) */
+                                 int B, int Hkv, int G, int Nq,
+                                 int num_pages, int page_size, int max_pages, int d,
+                                 float scale, int causal, int in_dtype, int out_dtype,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through

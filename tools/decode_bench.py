@@ -5,11 +5,15 @@ occupy (the path is HBM-bound: every K and V byte is read once).
     python tools/decode_bench.py --B 8 --H 16 --Nq 1 --Nk 32768 --d 128
     python tools/decode_bench.py --kvcache --fill 0.25          # fa_forward_kvcache: a 32768-row cache holding 8192 keys per sequence
     python tools/decode_bench.py --paged 16 --fill 0.25         # fa_forward_kvcache_paged: the same cache in shuffled pages of 16 keys
+    python tools/decode_bench.py --kvcache --fp8 [--paged 16]   # the fp8 entry against the 16-bit entry on the same shape
 
 --kvcache times fa_forward_kvcache against a cache of --Nk rows in which every sequence holds --fill x Nk keys (the lengths live
 in a device tensor); GB/s then counts the K and V bytes of the keys held, not of the capacity.  --causal adds the mask.
 --paged PAGE_SIZE (implies --kvcache) scatters that cache into a pool [B * Nk / PAGE_SIZE, H, PAGE_SIZE, d] through a seeded random
 permutation of the pages and times fa_forward_kvcache_paged with the block table of that permutation.
+--fp8 (with --kvcache or --paged) quantises the cache with quantize_kv_fp8 and times fa_forward_kvcache[_paged]_fp8 AND the 16-bit
+entry on the same shape in the same process, interleaved round by round; each line counts the bytes its cache actually holds, and
+the last line gives the ratio of the medians next to the round-to-round spread of the 16-bit timings.
 """
 import argparse
 import os
@@ -28,10 +32,11 @@ def scatter_pages(torch, k, v, page_size, seed=0):
     perm = torch.randperm(B * max_pages, generator=g).to(k.device)
     pools = []
     for x in (k, v):
-        pages = x.view(B, H, max_pages, page_size, d).permute(0, 2, 1, 3, 4).reshape(B * max_pages, H, page_size, d)
+        raw = x.view(torch.uint8) if x.element_size() == 1 else x   # an fp8 cache is moved as bytes
+        pages = raw.view(B, H, max_pages, page_size, d).permute(0, 2, 1, 3, 4).reshape(B * max_pages, H, page_size, d)
         pool = torch.empty_like(pages)
         pool[perm] = pages
-        pools.append(pool)
+        pools.append(pool.view(x.dtype))
     return pools[0], pools[1], perm.view(B, max_pages).to(torch.int32).contiguous()
 
 
@@ -49,6 +54,8 @@ def main():
     ap.add_argument("--causal", action="store_true", help="with --kvcache: the causal mask aligned to the end of the cache")
     ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
                     help="fa_forward_kvcache_paged on the cache scattered into shuffled pages of PAGE_SIZE keys (implies --kvcache)")
+    ap.add_argument("--fp8", action="store_true",
+                    help="with --kvcache / --paged: also time the fp8 entry on the quantised cache, interleaved with the 16-bit one")
     args = ap.parse_args()
     if args.paged:
         args.kvcache = True
@@ -59,23 +66,34 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     q = torch.randn(args.B, args.H, args.Nq, args.d, generator=g, device="cuda").half()
     k, v = (torch.randn(args.B, args.H, args.Nk, args.d, generator=g, device="cuda").half() for _ in range(2))
-    if not args.kvcache and (args.fill != 1.0 or args.causal):
-        ap.error("--fill and --causal need --kvcache")
+    if not args.kvcache and (args.fill != 1.0 or args.causal or args.fp8):
+        ap.error("--fill, --causal and --fp8 need --kvcache")
+    calls = {}   # name -> (call, bytes per K/V element)
     if args.kvcache:
         held = min(max(int(round(args.fill * args.Nk)), 0), args.Nk)
         lens = torch.full((args.B,), held, dtype=torch.int32, device="cuda")
         need = fa.kvcache_workspace_bytes(args.B, args.H, 1, args.Nq, args.Nk, args.d)
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
 
+        if args.fp8:
+            (k8, ks), (v8, vs) = fa.quantize_kv_fp8(k), fa.quantize_kv_fp8(v)
+            if args.paged:
+                k8, v8, _ = scatter_pages(torch, k8, v8, args.paged, seed=0)   # the same permutation as the 16-bit pools below
         if args.paged:
             k, v, table = scatter_pages(torch, k, v, args.paged, seed=0)
             need = fa.kvcache_paged_workspace_bytes(args.B, args.H, 1, args.Nq, args.Nk // args.paged, args.paged, args.d)
 
             def call():
                 fa.fa_forward_kvcache_paged(q, k, v, table, lens, causal=args.causal, workspace=ws)
+
+            def call8():
+                fa.fa_forward_kvcache_paged_fp8(q, k8, v8, table, ks, vs, lens, causal=args.causal, workspace=ws)
         else:
             def call():
                 fa.fa_forward_kvcache(q, k, v, lens, causal=args.causal, workspace=ws)
+
+            def call8():
+                fa.fa_forward_kvcache_fp8(q, k8, v8, ks, vs, lens, causal=args.causal, workspace=ws)
     else:
         held = args.Nk
         need = fa.splitkv_workspace_bytes(args.B, args.H, args.Nq, args.Nk, args.d)
@@ -83,26 +101,39 @@ def main():
 
         def call():
             fa.fa_forward_splitkv(q, k, v, workspace=ws)
-    for _ in range(3):
-        call()
+    calls["16-bit"] = (call, 2)
+    if args.fp8:
+        calls["fp8"] = (call8, 1)
+    for fn, _ in calls.values():
+        for _ in range(3):
+            fn()
     torch.cuda.synchronize()
-    times = []
-    for _ in range(args.rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1) / args.iters)
-    med = statistics.median(times)
-    kv_bytes = 2.0 * args.B * args.H * held * args.d * 2
+    times = {name: [] for name in calls}
+    for _ in range(args.rounds):   # the entries alternate inside every round: drift hits both alike
+        for name, (fn, _) in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / args.iters)
     tag = f" kvcache fill {args.fill:g} ({held} keys){' causal' if args.causal else ''}" if args.kvcache else ""
     if args.paged:
         tag += f" paged {args.paged}"
-    print(f"B{args.B} H{args.H} Nq{args.Nq} Nk{args.Nk} d{args.d}{tag}: workspace {need} B, median {med * 1e3:.1f} us, "
-          f"K+V {kv_bytes / 1e6:.1f} MB -> {kv_bytes / med / 1e6:.0f} GB/s ({kv_bytes / med / 1e6 / 8000 * 100:.1f} % of 8 TB/s)")
-
+    med = {}
+    for name, (_, elem) in calls.items():
+        med[name] = statistics.median(times[name])
+        kv_bytes = 2.0 * args.B * args.H * held * args.d * elem
+        which = f" [{name}]" if args.fp8 else ""
+        print(f"B{args.B} H{args.H} Nq{args.Nq} Nk{args.Nk} d{args.d}{tag}{which}: workspace {need} B, median {med[name] * 1e3:.1f} us "
+              f"(rounds {min(times[name]) * 1e3:.1f}-{max(times[name]) * 1e3:.1f}), "
+              f"K+V {kv_bytes / 1e6:.1f} MB -> {kv_bytes / med[name] / 1e6:.0f} GB/s ({kv_bytes / med[name] / 1e6 / 8000 * 100:.1f} % of 8 TB/s)")
+    if args.fp8:
+        spread = max(times["16-bit"]) - min(times["16-bit"])
+        gain = med["16-bit"] - med["fp8"]
+        print(f"fp8 / 16-bit = {med['fp8'] / med['16-bit']:.3f} (ideal 0.5); fp8 is {gain * 1e3:.1f} us faster, the 16-bit rounds spread "
+              f"over {spread * 1e3:.1f} us: {'faster beyond the spread' if gain > spread else 'NOT faster beyond the spread'}")
 
 if __name__ == "__main__":
     main()
