@@ -36,14 +36,14 @@ hipError_t rp16_dispatch(const FwdArgs& a, bool fold, Rp16Family family)
     const bool f = fold && rp16_fold_ok(a.scale);
     if (a.D == 128) {
         switch (family) {
-            case Rp16Family::kFull: return rp16_family<128, 2, false, false>(a, f);   // 32-row waves, 256-row workgroups (+ redo kernel on 16-row waves)
+            case Rp16Family::kFull: return rp16_family<128, 2, false, false>(a, f);   // 32-row waves, 256-row workgroups (+ the running-max body on 16-row waves, same launch)
             case Rp16Family::kHalf: return rp16_family<128, 1, false, false>(a, f);
             case Rp16Family::kOneWave: return rp16_family<128, 4, false, false, 4>(a, f);   // four 64-row waves, 512 registers per wave
             default: return hipErrorInvalidValue;
         }
     }
     switch (family) {
-        case Rp16Family::kFull: return rp16_family<64, 4, false, false>(a, f);      // 64-row waves, 512-row workgroups (+ the half-width redo kernel)
+        case Rp16Family::kFull: return rp16_family<64, 4, false, false>(a, f);      // 64-row waves, 512-row workgroups (+ the half-width running-max body, same launch)
         case Rp16Family::kHalf: return rp16_family<64, 2, false, false>(a, f);      // small grids: the same
         case Rp16Family::kQuarter: return rp16_family<64, 1, false, false>(a, f);   // pipeline on narrower waves
         case Rp16Family::kKeySplit: return rp16_family<64, 2, false, false, 4, 2>(a, f);   // two groups of FOUR 32-row waves (N % 128 == 0)

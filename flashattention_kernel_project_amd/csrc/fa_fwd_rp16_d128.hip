@@ -1,4 +1,4 @@
-// fa_fwd_rp16_d128.hip -- the pipeline at d = 128 on 32-row waves (256-row workgroups, with the redo kernel on 16-row waves) and on 16-row waves (fa_fwd_rp16_kernel.hpp).
+// fa_fwd_rp16_d128.hip -- the pipeline at d = 128 on 32-row waves (256-row workgroups, with the running-max body on 16-row waves inside the same kernels) and on 16-row waves (fa_fwd_rp16_kernel.hpp).
 #include "fa_fwd_rp16_kernel.hpp"
 
 namespace fa {

@@ -1,4 +1,4 @@
-// fa_fwd_rp16_d64.hip -- the pipeline at d = 64 on 64-row waves (512-row workgroups) and its half-width redo kernel (fa_fwd_rp16_kernel.hpp).
+// fa_fwd_rp16_d64.hip -- the pipeline at d = 64 on 64-row waves (512-row workgroups), its half-width running-max body inside the same kernels (fa_fwd_rp16_kernel.hpp).
 #include "fa_fwd_rp16_kernel.hpp"
 
 namespace fa {
