@@ -19,6 +19,10 @@ from .ops import (  # noqa: F401
     fa_forward_kvcache_fp8,
     fa_forward_kvcache_paged_fp8,
     quantize_kv_fp8,
+    fa_kvcache_append,
+    fa_kvcache_append_paged,
+    fa_kvcache_append_fp8,
+    fa_kvcache_append_paged_fp8,
     flashattn_forward_wmma,
     flashattn_streaming_16x16_mw,
     flashattn_streaming_16x16_mw_kt,
@@ -32,6 +36,7 @@ __all__ = [
     "fa_forward", "fa_forward_splitkv", "splitkv_workspace_bytes", "fa_forward_kvcache",
     "kvcache_workspace_bytes", "fa_forward_kvcache_paged", "kvcache_paged_workspace_bytes", "flashattn_forward_wmma",
     "fa_forward_kvcache_fp8", "fa_forward_kvcache_paged_fp8", "quantize_kv_fp8",
+    "fa_kvcache_append", "fa_kvcache_append_paged", "fa_kvcache_append_fp8", "fa_kvcache_append_paged_fp8",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",
     "attention_flops", "attention_min_bytes", "shard_range",
 ]

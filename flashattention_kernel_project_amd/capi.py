@@ -35,6 +35,10 @@ SYMBOLS = (
     "fa_forward_kvcache",
     "fa_forward_kvcache_fp8",
     "fa_forward_kvcache_paged_fp8",
+    "fa_kvcache_append",
+    "fa_kvcache_append_paged",
+    "fa_kvcache_append_fp8",
+    "fa_kvcache_append_paged_fp8",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -115,6 +119,14 @@ def lib() -> C.CDLL:
         L.fa_forward_kvcache_paged_fp8.restype = C.c_int
         L.fa_forward_kvcache_paged_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_workspace_bytes.restype = C.c_size_t
+        L.fa_kvcache_append.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.fa_kvcache_append.restype = C.c_int
+        L.fa_kvcache_append_paged.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
+        L.fa_kvcache_append_paged.restype = C.c_int
+        L.fa_kvcache_append_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.fa_kvcache_append_fp8.restype = C.c_int
+        L.fa_kvcache_append_paged_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
+        L.fa_kvcache_append_paged_fp8.restype = C.c_int
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

@@ -127,6 +127,38 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, con
                                           block_table, num_pages, page_size, max_pages}, k_scale, v_scale);
 }
 
+FA_EXPORT int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
+                      int B, int Hkv, int Nnew, int Ncap, int d, int dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kcache, Vcache, seqlens_k, seqlens_out, nullptr, nullptr, nullptr, B, Hkv, Nnew,
+                                             Ncap, d, dtype, 0, 0, 0, false, false, static_cast<hipStream_t>(stream)});
+}
+
+FA_EXPORT int fa_kvcache_append_paged(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* seqlens_k,
+                            int* seqlens_out, const int* block_table, int B, int Hkv, int Nnew, int num_pages, int page_size,
+                            int max_pages, int d, int dtype, void* stream)
+{
+    // Ncap (0 here) follows from max_pages * page_size once that is known to fit
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kpool, Vpool, seqlens_k, seqlens_out, block_table, nullptr, nullptr, B, Hkv, Nnew,
+                                             0, d, dtype, num_pages, page_size, max_pages, true, false, static_cast<hipStream_t>(stream)});
+}
+
+FA_EXPORT int fa_kvcache_append_fp8(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
+                          const float* k_scale, const float* v_scale, int B, int Hkv, int Nnew, int Ncap, int d, int in_dtype,
+                          void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kcache, Vcache, seqlens_k, seqlens_out, nullptr, k_scale, v_scale, B, Hkv, Nnew,
+                                             Ncap, d, in_dtype, 0, 0, 0, false, true, static_cast<hipStream_t>(stream)});
+}
+
+FA_EXPORT int fa_kvcache_append_paged_fp8(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* seqlens_k,
+                                int* seqlens_out, const int* block_table, const float* k_scale, const float* v_scale, int B, int Hkv,
+                                int Nnew, int num_pages, int page_size, int max_pages, int d, int in_dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kpool, Vpool, seqlens_k, seqlens_out, block_table, k_scale, v_scale, B, Hkv, Nnew,
+                                             0, d, in_dtype, num_pages, page_size, max_pages, true, true, static_cast<hipStream_t>(stream)});
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

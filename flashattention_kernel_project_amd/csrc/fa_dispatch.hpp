@@ -71,7 +71,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_kvcache_append.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -109,6 +109,23 @@ hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& with_capacity, int& 
 hipError_t kvcache_fp8_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale);
 hipError_t kvpaged_fp8_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale);
 size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
+// KV-cache append (fa_kvcache_append and its paged / fp8 forms) -- fa_kvcache_append.hip: Knew, Vnew [B, Hkv, Nnew, D] of `dtype` go
+// behind each sequence's length into K, V (a cache [B, Hkv, Ncap, D], or with `paged` a pool [num_pages, Hkv, page_size, D] through
+// `table`; with `fp8` one e4m3fn byte per element, quantised by k_scale / v_scale).  seqlens (null: all empty), seqlens_out (null:
+// not written), table and the scales are device pointers.
+struct KvAppendArgs {
+    const void *Knew, *Vnew;
+    void *K, *V;
+    const int* seqlens;
+    int* seqlens_out;
+    const int* table;
+    const float *k_scale, *v_scale;
+    int B, Hkv, Nnew, Ncap, D, dtype;
+    int num_pages, page_size, max_pages;
+    bool paged, fp8;
+    hipStream_t stream;
+};
+hipError_t kvcache_append_dispatch(const KvAppendArgs& a);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

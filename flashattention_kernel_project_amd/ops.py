@@ -391,6 +391,136 @@ def quantize_kv_fp8(x, scale=None):
     return x8, scale.contiguous()
 
 
+def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, what):
+    """What the four append front ends share once the cache is known to be 4-D: shapes and dtypes of the new rows against the cache
+    ([*, Hkv, rows, d]), the two length tensors.  -> (B, Hkv, Nnew, d, dtype id, source pointers, cache pointers, len_ptr, out_ptr)"""
+    import torch
+    if k_new.dim() != 4 or v_new.shape != k_new.shape or k_new.shape[1] != k_dst.shape[1] or k_new.shape[3] != k_dst.shape[3]:
+        raise ValueError(f"k_new, v_new must be [B,Hkv,Nnew,d] with the Hkv and d of {what}")
+    B, Hkv, Nnew, d = k_new.shape
+    dts = (torch.float16, torch.bfloat16)
+    if k_new.dtype not in dts or v_new.dtype != k_new.dtype:
+        raise ValueError("k_new, v_new must both be fp16 or both bf16")
+    if fp8:
+        if k_dst.dtype != torch.float8_e4m3fn or v_dst.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{what}: {_FP8_CACHE} (got {k_dst.dtype}, {v_dst.dtype})")
+        cache_dts = (torch.float8_e4m3fn,)
+    else:
+        if k_dst.dtype != k_new.dtype or v_dst.dtype != k_new.dtype:
+            raise ValueError(f"{what} must have the dtype of k_new ({k_new.dtype}; got {k_dst.dtype}, {v_dst.dtype}); an fp8 cache "
+                             "goes through fa_kvcache_append_fp8 / fa_kvcache_append_paged_fp8")
+        cache_dts = dts
+    len_ptrs = []
+    for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
+        if t is None:
+            len_ptrs.append(None)
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"{name} must be an int32 device tensor of shape [B]")
+        len_ptrs.append(_dev_ptr(t, name, (torch.int32,)))
+    src = (_dev_ptr(k_new, "k_new", dts), _dev_ptr(v_new, "v_new", dts))
+    dst = (_dev_ptr(k_dst, "k cache", cache_dts), _dev_ptr(v_dst, "v cache", cache_dts))
+    return B, Hkv, Nnew, d, capi.F16 if k_new.dtype == torch.float16 else capi.BF16, src, dst, len_ptrs[0], len_ptrs[1]
+
+
+def _scale_ptrs(k_scale, v_scale, Hkv):
+    import torch
+    out = []
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            out.append(None)
+            continue
+        if not isinstance(s, torch.Tensor) or s.dim() != 1 or s.shape[0] != Hkv or s.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 device tensor of shape [Hkv] = [{Hkv}]")
+        out.append(_dev_ptr(s, name, (torch.float32,)))
+    return out
+
+
+def _table_ptr(block_table, B):
+    import torch
+    if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
+    return _dev_ptr(block_table, "block_table", (torch.int32,))
+
+
+def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlens_out=None, stream=None) -> None:
+    """Write k_new/v_new [B,Hkv,Nnew,d] behind each sequence's length into k_cache/v_cache [B,Hkv,Ncap,d] (fa_kvcache_append): fp16 or
+    bf16 device tensors of ONE dtype, d in {64,128}.  Token t of sequence b goes to row L_b + t, L_b = cache_seqlens[b] clamped to
+    [0, Ncap]; a token at or past Ncap is dropped; nothing else in the cache changes.  The caches are mutated, None is returned.
+    cache_seqlens: int32 contiguous device tensor [B], or None: every sequence is EMPTY (a prefill into a fresh cache) -- not "full",
+    which is what None means to fa_forward_kvcache.
+    seqlens_out: int32 contiguous device tensor [B] that receives min(L_b + Nnew, Ncap), or None (the caller updates the lengths).  It
+    may be cache_seqlens itself (in place) or a tensor that does not overlap it.
+    Lengths are read on the device only: append(seqlens_out=lens) followed by fa_forward_kvcache(lens), captured once into a graph,
+    serves every step of a growing cache."""
+    import torch
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
+        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, False,
+                                                                   "k_cache, v_cache")
+    with torch.cuda.device(_one_device(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)):
+        code = capi.lib().fa_kvcache_append(*src, *dst, len_ptr, out_ptr, B, Hkv, Nnew, k_cache.shape[2], d, dt, _stream_ptr(stream))
+    capi.check("fa_kvcache_append", code)
+
+
+def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens=None, seqlens_out=None, stream=None) -> None:
+    """fa_kvcache_append into a paged cache (fa_kvcache_append_paged): k_pool/v_pool [num_pages,Hkv,page_size,d] of k_new's dtype,
+    block_table int32 [B, max_pages] as in fa_forward_kvcache_paged; position p is row p % page_size of page
+    block_table[b, p // page_size], the capacity is max_pages * page_size.  A table entry outside [0, num_pages) drops the tokens of
+    that page; entries of pages that receive no token are not read.  The pages a sequence appends into must be its own: a page shared
+    between sequences may only be written by the caller's copy-on-write (not checked)."""
+    import torch
+    if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
+        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
+    tbl_ptr = _table_ptr(block_table, k_new.shape[0])
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, False,
+                                                                   "k_pool, v_pool")
+    with torch.cuda.device(_one_device(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)):
+        code = capi.lib().fa_kvcache_append_paged(*src, *dst, len_ptr, out_ptr, tbl_ptr, B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2],
+                                                  block_table.shape[1], d, dt, _stream_ptr(stream))
+    capi.check("fa_kvcache_append_paged", code)
+
+
+def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, seqlens_out=None,
+                          stream=None) -> None:
+    """fa_kvcache_append into an fp8 cache (fa_kvcache_append_fp8): k_new/v_new fp16 or bf16, k_cache/v_cache [B,Hkv,Ncap,d]
+    torch.float8_e4m3fn (fnuz and e5m2 are refused).  The stored code is quantize_kv_fp8(x, scale) bit for bit: x / scale[h] in fp32,
+    clamped to +-448, rounded to nearest even; +-inf becomes +-448, NaN a NaN code.
+    k_scale, v_scale: float32 contiguous device tensors [Hkv], finite and > 0, or None (1.0); read on the device only."""
+    import torch
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
+        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
+    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
+        raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_cache.dtype}, {v_cache.dtype})")
+    ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, True,
+                                                                   "k_cache, v_cache")
+    with torch.cuda.device(_one_device(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out)):
+        code = capi.lib().fa_kvcache_append_fp8(*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr, B, Hkv, Nnew, k_cache.shape[2], d, dt,
+                                                _stream_ptr(stream))
+    capi.check("fa_kvcache_append_fp8", code)
+
+
+def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
+                                seqlens_out=None, stream=None) -> None:
+    """fa_kvcache_append_paged into fp8 pools (fa_kvcache_append_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
+    torch.float8_e4m3fn, block_table as in fa_kvcache_append_paged, scales and codes as in fa_kvcache_append_fp8."""
+    import torch
+    if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
+        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
+    if k_pool.dtype != torch.float8_e4m3fn or v_pool.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
+        raise ValueError(f"k_pool, v_pool: {_FP8_CACHE} (got {k_pool.dtype}, {v_pool.dtype})")
+    tbl_ptr = _table_ptr(block_table, k_new.shape[0])
+    ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, True,
+                                                                   "k_pool, v_pool")
+    with torch.cuda.device(_one_device(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out)):
+        code = capi.lib().fa_kvcache_append_paged_fp8(*src, *dst, len_ptr, out_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, Nnew,
+                                                      k_pool.shape[0], k_pool.shape[2], block_table.shape[1], d, dt,
+                                                      _stream_ptr(stream))
+    capi.check("fa_kvcache_append_paged_fp8", code)
+
+
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):
     import torch
     if Q.numel() != num_batches * 256 or K.numel() != num_batches * 16 * seq_len \

@@ -11,6 +11,10 @@ eager fallback.  Registered on first use:
     o = torch.ops.fa_mi355.decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_paged
     o = torch.ops.fa_mi355.decode_fp8(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_fp8
     o = torch.ops.fa_mi355.decode_paged_fp8(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)
+    torch.ops.fa_mi355.append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)   # ops.fa_kvcache_append; returns nothing
+    torch.ops.fa_mi355.append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)
+    torch.ops.fa_mi355.append_fp8(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out)
+    torch.ops.fa_mi355.append_paged_fp8(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out)
 """
 from __future__ import annotations
 
@@ -20,7 +24,8 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8 and .decode_paged_fp8 (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8 and the four .append ops
+    (idempotent)."""
     global _registered
     if _registered:
         return
@@ -92,6 +97,55 @@ def register() -> None:
     @decode_paged_fp8.register_fake
     def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
         return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by
+    # .contiguous() would take the writes, so a cache that is not contiguous is refused by the front end.
+    @torch.library.custom_op("fa_mi355::append", mutates_args=("k_cache", "v_cache", "seqlens_out"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cache_seqlens, "
+                                    "Tensor(c!)? seqlens_out) -> ()")
+    def append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
+        stream = torch.cuda.current_stream(k_new.device)
+        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out, stream=stream)
+
+    @append.register_fake
+    def _(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
+        return None
+
+    @torch.library.custom_op("fa_mi355::append_paged", mutates_args=("k_pool", "v_pool", "seqlens_out"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    "Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
+    def append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
+        stream = torch.cuda.current_stream(k_new.device)
+        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                    opt(cache_seqlens), seqlens_out, stream=stream)
+
+    @append_paged.register_fake
+    def _(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
+        return None
+
+    @torch.library.custom_op("fa_mi355::append_fp8", mutates_args=("k_cache", "v_cache", "seqlens_out"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
+                                    "Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
+    def append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
+        stream = torch.cuda.current_stream(k_new.device)
+        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
+                                  opt(cache_seqlens), seqlens_out, stream=stream)
+
+    @append_fp8.register_fake
+    def _(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
+        return None
+
+    @torch.library.custom_op("fa_mi355::append_paged_fp8", mutates_args=("k_pool", "v_pool", "seqlens_out"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    "Tensor? k_scale, Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
+    def append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
+        stream = torch.cuda.current_stream(k_new.device)
+        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream)
+
+    @append_paged_fp8.register_fake
+    def _(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
+        return None
 
     _registered = True
 

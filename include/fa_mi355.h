@@ -125,8 +125,8 @@ int fa_forward_splitkv(const void* Q, const void* K, const void* V, void* O,
  * so a call captured into a HIP graph replays correctly after the lengths were changed in place.  The keys of a
  * sequence are divided among its splits by L_b, not by Ncap: a cache filled to a fraction still uses every split.
  * Workspace as for fa_forward_splitkv (size from fa_forward_kvcache_workspace_bytes(); 0: `workspace` may be NULL).
- * Sliding windows and appending to the cache are not part of this entry; a paged (block-table) cache goes through
- * fa_forward_kvcache_paged below, an fp8 cache through fa_forward_kvcache_fp8.
+ * Sliding windows are not part of this entry; a paged (block-table) cache goes through fa_forward_kvcache_paged below, an fp8 cache
+ * through fa_forward_kvcache_fp8; fa_kvcache_append and its forms write the new token's K/V into any of them.
  * NOT a reference entry point. */
 size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d);
 int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, void* O,
@@ -157,8 +157,8 @@ int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, vo
  * hipErrorInvalidValue, before the device is touched: a null Q, Kpool, Vpool, O or block_table; a page_size that is not a power of
  * two or is below 16; num_pages <= 0 or max_pages <= 0; max_pages * page_size beyond int or beyond the 32-bit byte offsets
  * fa_forward_kvcache allows for its Ncap; everything else fa_forward_kvcache rejects.
- * Appending the new token's K/V and sliding windows are not part of this entry; fp8 pools go through fa_forward_kvcache_paged_fp8
- * below.  NOT a reference entry point. */
+ * Sliding windows are not part of this entry; fp8 pools go through fa_forward_kvcache_paged_fp8 below, the new token's K/V is written
+ * by fa_kvcache_append_paged.  NOT a reference entry point. */
 size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d);
 int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool, void* O,
                              float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
@@ -190,7 +190,8 @@ int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool
  * Splits, tile order and arithmetic are the 16-bit entries': with all scales 1, O and lse equal fa_forward_kvcache[_paged] on the
  * widened cache bit for bit; a power-of-two k_scale equals that entry called with scale * k_scale, a power-of-two v_scale multiplies
  * its fp32 result exactly.
- * fp8 Q, e5m2, per-token or per-block scales and appending are not part of these entries.  NOT reference entry points. */
+ * fp8 Q, e5m2 and per-token or per-block scales are not part of these entries; fa_kvcache_append_fp8 / _paged_fp8 write such a cache.
+ * NOT reference entry points. */
 int fa_forward_kvcache_fp8(const void* Q, const void* Kcache, const void* Vcache, void* O,
                            float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
                            const int* seqlens_k,  /* device, B int32, may be NULL (= Ncap for all) */
@@ -209,6 +210,59 @@ int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* V
                                  int num_pages, int page_size, int max_pages, int d,
                                  float scale, int causal, int in_dtype, int out_dtype,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* KV-cache append: the write half of a decode step.  Nnew new K and V rows per sequence are written behind the sequence's current
+ * length, by one kernel for K and V, into any cache the decode entries above read.
+ *   Knew, Vnew      [B, Hkv, Nnew, d] contiguous, fp16 or bf16 (`dtype` / `in_dtype`); d in {64,128}
+ *   Kcache, Vcache  [B, Hkv, Ncap, d], resp. Kpool, Vpool [num_pages, Hkv, page_size, d] with block_table [B, max_pages] int32 on the
+ *                   device and page_size a power of two >= 16 (Ncap = max_pages * page_size): the layouts of the decode entries.
+ *                   Elements are 16 bit of the same `dtype` (the copy keeps every bit, NaN payloads included); on the _fp8 entries one
+ *                   byte, OCP e4m3fn.
+ *   seqlens_k       device, B int32, or NULL.  L_b = min(max(seqlens_k[b], 0), Ncap), the decode entries' clamp.  NULL means every
+ *                   sequence is EMPTY (L_b = 0: a prefill into a fresh cache) -- NOT "full", which is what NULL means to the decode
+ *                   entries.
+ *   seqlens_out     device, B int32, or NULL: receives min(L_b + Nnew, Ncap).  NULL: no length is written and the caller updates the
+ *                   lengths.  It may be exactly seqlens_k (an update in place) or a buffer that does not overlap seqlens_k; a partial
+ *                   overlap is hipErrorInvalidValue.  It is written by a second, tiny kernel (ceil(B / 256) workgroups) behind the
+ *                   copy on the same stream, launched only when seqlens_out is non-null: no copy thread can see a new length.
+ * Placement: token t of sequence b goes to key position p = L_b + t.  A token with p >= Ncap is dropped: it is not written and no
+ * address is formed from p.  On the paged entries position p is row p % page_size of page block_table[b][p / page_size]; a table
+ * entry outside [0, num_pages) drops the tokens that would land in that page (the write-side counterpart of "reads as zeros"), and
+ * table entries are read only for pages that receive a kept token.  Page addresses are 64 bit: a pool may exceed 4 GiB.  Every byte of
+ * the cache or pool that is not the destination of a kept token is left as it was.
+ * The pages a sequence appends into must be owned by that sequence alone: pages shared between sequences (a common prefix) may only
+ * be written by the caller's own copy-on-write.  This is not checked.
+ * fp8 entries: the stored code is e4m3fn_RNE(clamp(x / scale[hkv], -448, +448)) with x widened exactly to fp32 and a correctly rounded
+ * fp32 division (never a reciprocal) -- ops.quantize_kv_fp8(x, scale) bit for bit, for every finite x.  k_scale, v_scale: device, Hkv
+ * fp32 each, or NULL (1.0), read on the device only.  +-inf becomes +-448 (codes 0x7E / 0xFE), a NaN becomes a NaN code (0x7F or
+ * 0xFF).  A scale must be finite and > 0; a bad one gives meaningless bytes, never an out-of-range access.
+ * Nothing on the host reads seqlens_k, block_table or the scales; the grid depends on (B, Hkv, Nnew, d) only and there is no workspace,
+ * so append -> decode with seqlens_out == seqlens_k, captured once into a HIP graph, serves every step of a growing cache.
+ * hipErrorInvalidValue, before the device is touched: a null Knew, Vnew, cache or pool, or block_table; B, Hkv, Nnew or Ncap <= 0; d
+ * not in {64,128}; a dtype not in {0,1}; an Ncap beyond the decode entries' bound; the paged entries' conditions on page_size,
+ * num_pages, max_pages and their product; a source of 2^31 or more 16-byte chunks per tensor (B * Hkv * Nnew * d / 8: the kernel's
+ * index type and the grid); the partial overlap of seqlens_out and seqlens_k.
+ * Rotary embedding, token-major pages, per-token or per-block scales, e5m2, fp8 sources and sliding windows are not part of these
+ * entries.  NOT reference entry points. */
+int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache,
+                      const int* seqlens_k,  /* device, B int32, may be NULL (= 0 for all: every sequence empty) */
+                      int* seqlens_out,      /* device, B int32, may be NULL or == seqlens_k */
+                      int B, int Hkv, int Nnew, int Ncap, int d, int dtype, void* stream);
+int fa_kvcache_append_paged(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                            const int* seqlens_k, int* seqlens_out,
+                            const int* block_table,  /* device, [B,max_pages] int32 */
+                            int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages,
+                            int d, int dtype, void* stream);
+int fa_kvcache_append_fp8(const void* Knew, const void* Vnew, void* Kcache, void* Vcache,
+                          const int* seqlens_k, int* seqlens_out,
+                          const float* k_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                          const float* v_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                          int B, int Hkv, int Nnew, int Ncap, int d, int in_dtype, void* stream);
+int fa_kvcache_append_paged_fp8(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                                const int* seqlens_k, int* seqlens_out, const int* block_table,
+                                const float* k_scale, const float* v_scale,
+                                int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages,
+                                int d, int in_dtype, void* stream);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
