@@ -16,6 +16,8 @@ from .ops import (  # noqa: F401
     kvcache_workspace_bytes,
     fa_forward_kvcache_paged,
     kvcache_paged_workspace_bytes,
+    kvcache_window_workspace_bytes,
+    kvcache_paged_window_workspace_bytes,
     fa_forward_kvcache_fp8,
     fa_forward_kvcache_paged_fp8,
     quantize_kv_fp8,
@@ -35,6 +37,7 @@ __all__ = [
     "build", "lib", "version", "FaError",
     "fa_forward", "fa_forward_splitkv", "splitkv_workspace_bytes", "fa_forward_kvcache",
     "kvcache_workspace_bytes", "fa_forward_kvcache_paged", "kvcache_paged_workspace_bytes", "flashattn_forward_wmma",
+    "kvcache_window_workspace_bytes", "kvcache_paged_window_workspace_bytes",
     "fa_forward_kvcache_fp8", "fa_forward_kvcache_paged_fp8", "quantize_kv_fp8",
     "fa_kvcache_append", "fa_kvcache_append_paged", "fa_kvcache_append_fp8", "fa_kvcache_append_paged_fp8",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",

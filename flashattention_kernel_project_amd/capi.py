@@ -39,6 +39,12 @@ SYMBOLS = (
     "fa_kvcache_append_paged",
     "fa_kvcache_append_fp8",
     "fa_kvcache_append_paged_fp8",
+    "fa_forward_kvcache_window_workspace_bytes",
+    "fa_forward_kvcache_paged_window_workspace_bytes",
+    "fa_forward_kvcache_window",
+    "fa_forward_kvcache_paged_window",
+    "fa_forward_kvcache_fp8_window",
+    "fa_forward_kvcache_paged_fp8_window",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -119,6 +125,19 @@ def lib() -> C.CDLL:
         L.fa_forward_kvcache_paged_fp8.restype = C.c_int
         L.fa_forward_kvcache_paged_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_workspace_bytes.restype = C.c_size_t
+        # the windowed forms: the base entry's list with `int window` after `causal`, the sizing functions' with it at the end
+        L.fa_forward_kvcache_window.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache_paged_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache_fp8_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
+        L.fa_forward_kvcache_paged_fp8_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, i, vp,
+                                                          C.c_size_t, vp]
+        for s in ("fa_forward_kvcache_window", "fa_forward_kvcache_paged_window", "fa_forward_kvcache_fp8_window",
+                  "fa_forward_kvcache_paged_fp8_window"):
+            getattr(L, s).restype = C.c_int
+        L.fa_forward_kvcache_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+        L.fa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
+        L.fa_forward_kvcache_paged_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
+        L.fa_forward_kvcache_paged_window_workspace_bytes.restype = C.c_size_t
         L.fa_kvcache_append.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.fa_kvcache_append.restype = C.c_int
         L.fa_kvcache_append_paged.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]

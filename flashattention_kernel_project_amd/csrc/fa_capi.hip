@@ -127,6 +127,56 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, con
                                           block_table, num_pages, page_size, max_pages}, k_scale, v_scale);
 }
 
+FA_EXPORT size_t fa_forward_kvcache_window_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d, int window)
+{
+    return fa::kvwindow_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window);
+}
+
+FA_EXPORT size_t fa_forward_kvcache_paged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d,
+                                                                 int window)
+{
+    return fa::kvpaged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window);
+}
+
+FA_EXPORT int fa_forward_kvcache_window(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse, const int* seqlens_k,
+                              int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal, int window,
+                              int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvcache_window_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype,
+                                             out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)}, window);
+}
+
+FA_EXPORT int fa_forward_kvcache_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
+                                    const int* seqlens_k, const int* block_table, int B, int Hkv, int G, int Nq, int num_pages,
+                                    int page_size, int max_pages, int d, float scale, int causal, int window, int in_dtype,
+                                    int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvpaged_window_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                              workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                             block_table, num_pages, page_size, max_pages}, window);
+}
+
+FA_EXPORT int fa_forward_kvcache_fp8_window(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse,
+                                  const int* seqlens_k, const float* k_scale, const float* v_scale, int B, int Hkv, int G, int Nq,
+                                  int Ncap, int d, float scale, int causal, int window, int in_dtype, int out_dtype, void* workspace,
+                                  size_t workspace_bytes, void* stream)
+{
+    return (int)fa::kvcache_fp8_window_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype,
+                                                 out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                                k_scale, v_scale, window);
+}
+
+FA_EXPORT int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
+                                        const int* seqlens_k, const int* block_table, const float* k_scale, const float* v_scale,
+                                        int B, int Hkv, int G, int Nq, int num_pages, int page_size, int max_pages, int d, float scale,
+                                        int causal, int window, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
+                                        void* stream)
+{
+    return (int)fa::kvpaged_fp8_window_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype,
+                                                  out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                                 block_table, num_pages, page_size, max_pages}, k_scale, v_scale, window);
+}
+
 FA_EXPORT int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
                       int B, int Hkv, int Nnew, int Ncap, int d, int dtype, void* stream)
 {

@@ -71,7 +71,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_kvcache_append.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_kvcache_append.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -109,6 +109,16 @@ hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& with_capacity, int& 
 hipError_t kvcache_fp8_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale);
 hipError_t kvpaged_fp8_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale);
 size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
+// Sliding-window decode -- fa_fwd_kvwindow.hip (16-bit caches), fa_fwd_kvwindow_fp8.hip (fp8 caches): the four entries above with
+// a host integer `window` >= 1 (row i sees the last `window` keys up to its own position; 0: the entry above itself; < 0:
+// rejected).  The split count, and with it grid and workspace, follows from window_span_cap() in place of the capacity.
+int window_span_cap(int Nq, int Ncap, int window);   // the longest key range a sequence can stream, in keys (window >= 1)
+hipError_t kvcache_window_dispatch(const KvCacheArgs& a, int window);
+hipError_t kvpaged_window_dispatch(const KvPagedArgs& a, int window);
+hipError_t kvcache_fp8_window_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale, int window);
+hipError_t kvpaged_fp8_window_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale, int window);
+size_t kvwindow_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D, int window);
+size_t kvpaged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D, int window);
 // KV-cache append (fa_kvcache_append and its paged / fp8 forms) -- fa_kvcache_append.hip: Knew, Vnew [B, Hkv, Nnew, D] of `dtype` go
 // behind each sequence's length into K, V (a cache [B, Hkv, Ncap, D], or with `paged` a pool [num_pages, Hkv, page_size, D] through
 // `table`; with `fp8` one e4m3fn byte per element, quantised by k_scale / v_scale).  seqlens (null: all empty), seqlens_out (null:

@@ -4,7 +4,8 @@
 // pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt); the paged entry passes
 // a PagedArgs in that pack, and everything it adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt); the fp8
 // entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
-// selects (profiles/kvcache_fp8.txt).
+// selects (profiles/kvcache_fp8.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
+// behind `if constexpr (kWindow)` (profiles/kvcache_window.txt).
 // The sets are instantiated in separate translation units so that none perturbs another's register allocation.
 // The design notes are at the head of fa_fwd_split.hip and in DESIGN.md 7.1.
 #pragma once
@@ -61,6 +62,20 @@ __device__ __forceinline__ NoScales fp8_part() { return {}; }
 __device__ __forceinline__ NoScales fp8_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const Fp8Args<Base>& fp8_part(const Fp8Args<Base>& f) { return f; }
 
+// What the sliding-window instantiations take: any of the packs above plus the window.  Row i of a head sees the keys
+// [max(0, L - Nq1 + 1 + i - window), c_i) with c_i the limit of the wrapped pack (L, or the causal one).  The wrapper derives from
+// what it wraps, so the kPaged test and paged_part() / fp8_part() see through it; IsFp8Args needs the line below.
+template <typename Base> struct WindowArgs : Base {
+    int window;           // >= 1 (0, "no window", never reaches the kernel: the host calls the wrapped entry)
+};
+template <typename A> struct IsWindowArgs : std::false_type {};
+template <typename Base> struct IsWindowArgs<WindowArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<WindowArgs<Base>> : IsFp8Args<Base> {};
+struct NoWindow {};
+__device__ __forceinline__ NoWindow window_part() { return {}; }
+__device__ __forceinline__ NoWindow window_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const WindowArgs<Base>& window_part(const WindowArgs<Base>& w) { return w; }
+
 // Two e4m3fn bytes of w (kHi: bytes 2 and 3) as one packed pair of T.  Every e4m3fn value is a normal number of fp16 and of bf16,
 // so the conversion is exact, and the NaN codes 0x7F / 0xFF stay NaN.  One v_cvt_scalef32_pk_{f16,bf16}_fp8 with a scale of 1.
 // FA_FP8_VIA_F32 takes the way through fp32 (v_cvt_pk_f32_fp8, then the pack of the type), which is exact for the same reason.
@@ -100,6 +115,13 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // (the FLT_MIN clamp comes AFTER the product: +-FLT_MIN * 0.5 must not meet a masked -inf as 0); v_scale joins 1 / l in the
 // one-pass kernel and the accumulators before the workspace store in the partial one, so the merge kernel is the 16-bit one.
 // With scales of 1 the result is bit-equal to the 16-bit kernels' on the widened cache.
+// kWindow (kCache with a WindowArgs around the pack): every row also has a LOWER key limit lo.  No row of the sequence sees a key
+// below start_b (row 0's lower limit), so the splits deal out the tiles from start_t = start_b rounded down to a tile -- tiles stay
+// at absolute multiples of kBlockN, which the paged scheme needs -- and nothing below start_t is touched.  The rows of the first
+// tile below start_b are loaded (a page wholly below start_b is not: it gets a descriptor of zero records, and its table entry is
+// not read) but reach LDS as zeros: masking the score is not enough for V, because a weight of 0 times a NaN is a NaN in the PV
+// MFMA.  Scores of keys below a row's lo become -inf in the tiles that start below the last row's lower limit; a tile that is
+// fully masked for a row is what m_ref = -inf already handles.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -118,6 +140,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto pa = paged_part(cache...);
     constexpr bool kFp8 = (IsFp8Args<Cache>::value || ...);
     [[maybe_unused]] const auto fa8 = fp8_part(cache...);
+    constexpr bool kWindow = (IsWindowArgs<Cache>::value || ...);
+    [[maybe_unused]] const auto wa = window_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -138,9 +162,16 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     if constexpr (kCache) {
         // the clamp keeps a bad length inside the cache; the tiles of THIS sequence are dealt out to the S splits
         if (ca.seqlens) nkeys = (unsigned)min(max(ca.seqlens[bh / (unsigned)ca.Hkv], 0), Nk);
-        chunk = (int)(((nkeys + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
+        if constexpr (!kWindow) chunk = (int)(((nkeys + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
     }
-    const unsigned key0 = sp * (unsigned)chunk;                       // multiple of kBlockN
+    // kWindow: the first key any row of the sequence sees, the tile it lies in, and the tiles from there dealt out to the splits
+    [[maybe_unused]] unsigned start_b = 0, start_t = 0;
+    if constexpr (kWindow) {
+        start_b = (unsigned)max((int)nkeys - ca.Nq1 + 1 - wa.window, 0);
+        start_t = start_b & ~(unsigned)(kBlockN - 1);
+        chunk = (int)(((nkeys - start_t + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
+    }
+    const unsigned key0 = (kWindow ? start_t : 0u) + sp * (unsigned)chunk;   // multiple of kBlockN
     const unsigned key1 = min(nkeys, key0 + (unsigned)chunk);         // exclusive
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(Qg + (size_t)bh * Nq * D, (unsigned)((size_t)Nq * D * 2));
     // K/V descriptors end at this split's last key: rows beyond it read 0 and are masked below
@@ -164,6 +195,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             lim = min((unsigned)max(first + (int)(q_row % (unsigned)ca.Nq1), 0), key1);
             lim_lo = min((unsigned)max(first, 0), key1);
         }
+    }
+    // kWindow: the row's causal limit before any clamp -- both of its limits follow from it in the few tiles that mask, so the row
+    // keeps ONE register for them, as the kCache kernels do (at D = 64 a second one spills) -- and the largest lower limit of any
+    // row: tiles that start at or past it need no lower mask
+    [[maybe_unused]] int row_end = 0;
+    [[maybe_unused]] unsigned lo_hi = 0;
+    if constexpr (kWindow) {
+        row_end = (int)nkeys - ca.Nq1 + 1 + (int)(q_row % (unsigned)ca.Nq1);
+        lo_hi = (unsigned)max((int)nkeys - wa.window, 0);
     }
 
     // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf.  Redundant behind host_scale_log2e() (fa_dispatch.hpp), which
@@ -210,7 +250,10 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 #pragma unroll
             for (int p = 0; p < kLoadsW; ++p) {
                 const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;   // first row of the tile this wave loads with p
-                pg[p] = __builtin_amdgcn_readfirstlane(tbl[min((kv0 + wrow) >> pa.lg_page, last)]);
+                unsigned e = min((kv0 + wrow) >> pa.lg_page, last);
+                // kWindow: nor is an entry below start_b's page read (last is at or past it: key1 > start_b)
+                if constexpr (kWindow) e = max(e, start_b >> pa.lg_page);
+                pg[p] = __builtin_amdgcn_readfirstlane(tbl[e]);
             }
         }
     };
@@ -221,7 +264,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 const unsigned page = 1u << pa.lg_page;
                 const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;
                 const unsigned first = (kv0 + wrow) & ~(page - 1u);             // first key of the page
-                const bool ok = (unsigned)pg[p] < (unsigned)pa.num_pages && first < key1;
+                bool ok = (unsigned)pg[p] < (unsigned)pa.num_pages && first < key1;
+                if constexpr (kWindow) ok = ok && first + page > start_b;   // a page wholly below the window: pg[p] is another page's
                 // the page's rows below key1; a bad page number or a page past the split's end: no record, every load reads 0
                 const unsigned bytes = ok ? min(page, key1 - first) * kKvRowBytes : 0u;
                 // 64-bit: pools beyond 4 GiB are normal; only the offset inside one page-head block is 32 bit
@@ -241,7 +285,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 #endif
         }
     };
-    auto stage_write = [&](unsigned buf) {
+    // kv0: the tile stage_load() was last called for
+    auto stage_write = [&](unsigned buf, [[maybe_unused]] unsigned kv0) {
+        if constexpr (kWindow) {
+            if (kv0 < start_b) {   // workgroup-uniform, one tile per sequence: rows below the window go to LDS as zeros
+#pragma unroll
+                for (int p = 0; p < kLoadsW; ++p)
+                    if (kv0 + (tid + p * 64u * W) / kLdChunks < start_b) kst[p] = vst[p] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
 #pragma unroll
         for (int p = 0; p < kLoadsW; ++p) {
             if constexpr (kFp8) {
@@ -286,7 +338,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if constexpr (kPaged) fetch_pages(key0 + tile_of(0) * kBlockN);
         stage_load(key0 + tile_of(0) * kBlockN);
         if constexpr (kPaged) fetch_pages(key0 + tile_of(min(1, ntiles - 1)) * kBlockN);
-        stage_write(0);
+        stage_write(0, key0 + tile_of(0) * kBlockN);
         __syncthreads();
     }
 
@@ -308,7 +360,21 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 const u32x4 kf = lds_read16(kbuf, kb * 32u * G::kRowBytes + k_rd_row + (((2u * ks + h) ^ k_rd_swz) << 4));
                 s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
             }
-        if (kv0 + kBlockN > (kCache ? lim_lo : key1)) {   // keys past the split's end (kCache: past the row's limit) -> -inf (p = 0)
+        if constexpr (kWindow) {
+            // keys outside [lo, hi) -> -inf: hi is `lim` above, lo the row's lower limit; one unsigned compare per score
+            if (kv0 + kBlockN > lim_lo || kv0 < lo_hi) {
+                const unsigned lo = (unsigned)max(row_end - wa.window, 0);
+                const unsigned hi = ca.causal ? min((unsigned)max(row_end, 0), key1) : key1;
+                const unsigned seen = hi > lo ? hi - lo : 0u;   // a split that ends below lo: nothing
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const unsigned key = kv0 + (unsigned)(kb * 32 + (i & 3) + 8 * (i >> 2)) + 4u * h;
+                        if (key - lo >= seen) s[kb][i] = -INFINITY;
+                    }
+            }
+        } else if (kv0 + kBlockN > (kCache ? lim_lo : key1)) {   // keys past the split's end (kCache: past the row's limit) -> -inf (p = 0)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -369,7 +435,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             }
         }   // has_rows
 
-        if (t + 1 < ntiles) stage_write(cur ^ 1u);
+        if (t + 1 < ntiles) stage_write(cur ^ 1u, key0 + tile_of(t + 1) * kBlockN);
         __syncthreads();
     }
 

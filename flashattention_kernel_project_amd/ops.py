@@ -149,7 +149,7 @@ def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
 
 
 def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = False, scale: float | None = None,
-                       out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+                       out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0):
     """Decode against a pre-allocated cache (fa_forward_kvcache): q [B,Hq,Nq,d], k_cache/v_cache [B,Hkv,Ncap,d]
     fp16/bf16 device tensors, d in {64,128}, Hq a multiple of Hkv (the group's K/V is streamed once, as in
     fa_forward_splitkv).
@@ -158,7 +158,10 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     causal: row i sees the keys [0, L_b - Nq + 1 + i) -- the last query row sees the whole sequence.
     A row that sees no key returns zeros (and lse = -inf).
     return_lse: also return the fp32 [B,Hq,Nq] natural-log sum of exponentials, for merging results over key ranges.
-    workspace: optional uint8 device tensor of at least kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)."""
+    workspace: optional uint8 device tensor of at least kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d).
+    window: 0 (no window), or W >= 1: row i sees only the keys [max(0, L_b - Nq + 1 + i - W), its upper limit) -- with causal its own
+    position and the W - 1 before it (fa_forward_kvcache_window).  Keys below row 0's lower limit are never used.  The window is a host
+    integer (baked into a captured call); the workspace is then sized by kvcache_window_workspace_bytes."""
     import torch
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
             or q.shape[3] != k_cache.shape[3]:
@@ -183,12 +186,22 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_cache, "k_cache", dts), _dev_ptr(v_cache, "v_cache", dts))
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
-    need = kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)   # from the shape alone: the split count reads no device property
+    window = _window(window)
+    # from the shape (and the window) alone: the split count reads no device property
+    need = kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window) if window else kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if window:
+        with torch.cuda.device(_one_device(q, k_cache, v_cache, cache_seqlens, workspace)):
+            code = capi.lib().fa_forward_kvcache_window(
+                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, B, Hkv, G, Nq, Ncap, d, float(scale),
+                1 if causal else 0, window, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
+                ws_ptr, ws_len, _stream_ptr(stream))
+        capi.check("fa_forward_kvcache_window", code)
+        return (out, lse) if return_lse else out
     with torch.cuda.device(_one_device(q, k_cache, v_cache, cache_seqlens, workspace)):
         code = capi.lib().fa_forward_kvcache(
             *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, B, Hkv, G, Nq, Ncap, d, float(scale),
@@ -202,8 +215,19 @@ def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int
     return int(capi.lib().fa_forward_kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d))
 
 
+def kvcache_window_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int, window: int) -> int:
+    """Workspace of the windowed contiguous entries (16 bit and fp8): the split count follows the window, not the capacity."""
+    return int(capi.lib().fa_forward_kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window))
+
+
+def _window(window) -> int:
+    if isinstance(window, bool) or not isinstance(window, int) or window < 0:
+        raise ValueError("window must be an int >= 0 (0: no window)")
+    return window
+
+
 def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None, causal: bool = False, scale: float | None = None,
-                             out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+                             out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0):
     """fa_forward_kvcache against a paged cache (fa_forward_kvcache_paged): q [B,Hq,Nq,d], k_pool/v_pool
     [num_pages,Hkv,page_size,d] fp16/bf16 contiguous device tensors (a contiguous slice of a larger pool, pool[2:6], is a pool),
     d in {64,128}, page_size a power of two >= 16, Hq a multiple of Hkv.
@@ -212,7 +236,11 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
     a live entry outside [0, num_pages) reads as a page of zeros.
     cache_seqlens, causal, scale, out_dtype, return_lse: as in fa_forward_kvcache.  Table and lengths are read on the device only,
     so a call captured into a graph follows both when they are later rewritten in place.
-    workspace: optional uint8 device tensor of at least kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)."""
+    workspace: optional uint8 device tensor of at least kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d).
+    window: 0 (no window), or W >= 1: row i sees only the keys [max(0, L_b - Nq + 1 + i - W), its upper limit) -- with causal its own
+    position and the W - 1 before it (fa_forward_kvcache_paged_window).  Keys below row 0's lower limit are never used.  The window is a host
+    integer (baked into a captured call); the workspace is then sized by kvcache_paged_window_workspace_bytes.
+    Under a window a page wholly below row 0's lower limit is not dereferenced and its table entry is not read."""
     import torch
     if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
         raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
@@ -240,12 +268,22 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
     ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_pool, "k_pool", dts), _dev_ptr(v_pool, "v_pool", dts))
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
-    need = kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # from the shape alone
+    window = _window(window)
+    need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window) if window \
+        else kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # from the shape (and the window) alone
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if window:
+        with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, cache_seqlens, workspace)):
+            code = capi.lib().fa_forward_kvcache_paged_window(
+                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, B, Hkv, G, Nq, num_pages, page_size,
+                max_pages, d, float(scale), 1 if causal else 0, window, in_dt,
+                capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, ws_ptr, ws_len, _stream_ptr(stream))
+        capi.check("fa_forward_kvcache_paged_window", code)
+        return (out, lse) if return_lse else out
     with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, cache_seqlens, workspace)):
         code = capi.lib().fa_forward_kvcache_paged(
             *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, B, Hkv, G, Nq, num_pages, page_size,
@@ -257,6 +295,11 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
 
 def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int) -> int:
     return int(capi.lib().fa_forward_kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d))
+
+
+def kvcache_paged_window_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int, window: int) -> int:
+    """Workspace of the windowed paged entries (16 bit and fp8): kvcache_window_workspace_bytes for Ncap = max_pages * page_size."""
+    return int(capi.lib().fa_forward_kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window))
 
 
 _FP8_CACHE = "an fp8 cache must be torch.float8_e4m3fn (OCP e4m3fn, the gfx950 format); float8_e4m3fnuz, float8_e5m2 and " \
@@ -301,7 +344,8 @@ def _fp8_decode_args(q, k8, v8, k_scale, v_scale, cache_seqlens, out_dtype, retu
 
 
 def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, causal: bool = False,
-                           scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None):
+                           scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None,
+                           window: int = 0):
     """fa_forward_kvcache against an fp8 cache (fa_forward_kvcache_fp8): q [B,Hq,Nq,d] fp16/bf16, k_cache/v_cache [B,Hkv,Ncap,d]
     torch.float8_e4m3fn (OCP e4m3fn; fnuz and e5m2 are refused) device tensors, d in {64,128}.  K and V are widened to q's type
     on the way into the kernel, exactly.
@@ -309,8 +353,8 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     is v_scale[h] * softmax.v8, lse is that of the scaled logits.  Scales must be finite and > 0; they are read on the device only,
     like cache_seqlens, so a captured call follows all three when they are rewritten in place.  quantize_kv_fp8() makes a cache
     and its scales from a 16-bit or fp32 tensor.
-    Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes) -- is
-    fa_forward_kvcache's."""
+    Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (then
+    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes) -- is fa_forward_kvcache's."""
     import torch
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
             or q.shape[3] != k_cache.shape[3]:
@@ -320,12 +364,21 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
         q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_cache, v_cache")
     G = Hq // Hkv
-    need = kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)   # the 16-bit entry's, from the shape alone
+    window = _window(window)
+    # the 16-bit entry's, from the shape (and the window) alone
+    need = kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window) if window else kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if window:
+        with torch.cuda.device(_one_device(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, workspace)):
+            code = capi.lib().fa_forward_kvcache_fp8_window(
+                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq, Ncap, d,
+                float(scale), 1 if causal else 0, window, in_dt, out_dt, ws_ptr, ws_len, _stream_ptr(stream))
+        capi.check("fa_forward_kvcache_fp8_window", code)
+        return (out, lse) if return_lse else out
     with torch.cuda.device(_one_device(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, workspace)):
         code = capi.lib().fa_forward_kvcache_fp8(
             *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq, Ncap, d,
@@ -336,10 +389,11 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
 
 def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
                                  causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
-                                 workspace=None, stream=None):
+                                 workspace=None, stream=None, window: int = 0):
     """fa_forward_kvcache_paged against fp8 pools (fa_forward_kvcache_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
     torch.float8_e4m3fn, block_table as in fa_forward_kvcache_paged, k_scale / v_scale and everything else as in
-    fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes."""
+    fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes; with a window (fa_forward_kvcache_paged_fp8_window)
+    kvcache_paged_window_workspace_bytes."""
     import torch
     if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
         raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
@@ -354,12 +408,22 @@ def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v
     ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
         q, k_pool, v_pool, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_pool, v_pool")
     G = Hq // Hkv
-    need = kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # the 16-bit entry's, from the shape alone
+    window = _window(window)
+    need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window) if window \
+        else kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # the 16-bit entry's, from the shape alone
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if window:
+        with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, workspace)):
+            code = capi.lib().fa_forward_kvcache_paged_fp8_window(
+                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq,
+                num_pages, page_size, max_pages, d, float(scale), 1 if causal else 0, window, in_dt, out_dt, ws_ptr, ws_len,
+                _stream_ptr(stream))
+        capi.check("fa_forward_kvcache_paged_fp8_window", code)
+        return (out, lse) if return_lse else out
     with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, workspace)):
         code = capi.lib().fa_forward_kvcache_paged_fp8(
             *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq,

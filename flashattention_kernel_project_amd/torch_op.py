@@ -11,6 +11,12 @@ eager fallback.  Registered on first use:
     o = torch.ops.fa_mi355.decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_paged
     o = torch.ops.fa_mi355.decode_fp8(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_fp8
     o = torch.ops.fa_mi355.decode_paged_fp8(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)
+    # the same four with a sliding window: `window` (an int >= 0, 0 = none) follows `causal`, as in the C entries
+    o = torch.ops.fa_mi355.decode_window(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_window(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32)
+    o = torch.ops.fa_mi355.decode_fp8_window(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_fp8_window(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal,
+                                                   window, out_fp32)
     torch.ops.fa_mi355.append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)   # ops.fa_kvcache_append; returns nothing
     torch.ops.fa_mi355.append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)
     torch.ops.fa_mi355.append_fp8(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out)
@@ -24,8 +30,8 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8 and the four .append ops
-    (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window forms and
+    the four .append ops (idempotent)."""
     global _registered
     if _registered:
         return
@@ -96,6 +102,58 @@ def register() -> None:
 
     @decode_paged_fp8.register_fake
     def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    # The sliding-window forms: the schema of the op above each with `int window` after `causal`; the existing ops keep theirs.
+    @torch.library.custom_op("fa_mi355::decode_window", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
+                                    "int window, bool out_fp32) -> Tensor")
+    def decode_window(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
+                                      scale=scale, out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
+
+    @decode_window.register_fake
+    def _(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode_paged_window", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
+                                    "bool causal, int window, bool out_fp32) -> Tensor")
+    def decode_paged_window(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                            opt(cache_seqlens), causal=causal, scale=scale,
+                                            out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
+
+    @decode_paged_window.register_fake
+    def _(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode_fp8_window", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
+    def decode_fp8_window(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
+                                          opt(cache_seqlens), causal=causal, scale=scale,
+                                          out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
+
+    @decode_fp8_window.register_fake
+    def _(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
+        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+
+    @torch.library.custom_op("fa_mi355::decode_paged_fp8_window", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
+    def decode_paged_fp8_window(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
+        stream = torch.cuda.current_stream(q.device)
+        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
+                                                out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
+
+    @decode_paged_fp8_window.register_fake
+    def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
         return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
 
     # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by

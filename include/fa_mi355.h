@@ -125,7 +125,7 @@ int fa_forward_splitkv(const void* Q, const void* K, const void* V, void* O,
  * so a call captured into a HIP graph replays correctly after the lengths were changed in place.  The keys of a
  * sequence are divided among its splits by L_b, not by Ncap: a cache filled to a fraction still uses every split.
  * Workspace as for fa_forward_splitkv (size from fa_forward_kvcache_workspace_bytes(); 0: `workspace` may be NULL).
- * Sliding windows are not part of this entry; a paged (block-table) cache goes through fa_forward_kvcache_paged below, an fp8 cache
+ * Sliding windows are not part of this entry (they are fa_forward_kvcache_window's, below); a paged (block-table) cache goes through fa_forward_kvcache_paged below, an fp8 cache
  * through fa_forward_kvcache_fp8; fa_kvcache_append and its forms write the new token's K/V into any of them.
  * NOT a reference entry point. */
 size_t fa_forward_kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d);
@@ -157,7 +157,7 @@ int fa_forward_kvcache(const void* Q, const void* Kcache, const void* Vcache, vo
  * hipErrorInvalidValue, before the device is touched: a null Q, Kpool, Vpool, O or block_table; a page_size that is not a power of
  * two or is below 16; num_pages <= 0 or max_pages <= 0; max_pages * page_size beyond int or beyond the 32-bit byte offsets
  * fa_forward_kvcache allows for its Ncap; everything else fa_forward_kvcache rejects.
- * Sliding windows are not part of this entry; fp8 pools go through fa_forward_kvcache_paged_fp8 below, the new token's K/V is written
+ * Sliding windows are not part of this entry (they are fa_forward_kvcache_paged_window's, below); fp8 pools go through fa_forward_kvcache_paged_fp8 below, the new token's K/V is written
  * by fa_kvcache_append_paged.  NOT a reference entry point. */
 size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d);
 int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool, void* O,
@@ -190,7 +190,8 @@ int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const void* Vpool
  * Splits, tile order and arithmetic are the 16-bit entries': with all scales 1, O and lse equal fa_forward_kvcache[_paged] on the
  * widened cache bit for bit; a power-of-two k_scale equals that entry called with scale * k_scale, a power-of-two v_scale multiplies
  * its fp32 result exactly.
- * fp8 Q, e5m2 and per-token or per-block scales are not part of these entries; fa_kvcache_append_fp8 / _paged_fp8 write such a cache.
+ * fp8 Q, e5m2 and per-token or per-block scales are not part of these entries; fa_kvcache_append_fp8 / _paged_fp8 write such a cache;
+ * sliding windows are fa_forward_kvcache_fp8_window's and fa_forward_kvcache_paged_fp8_window's, below.
  * NOT reference entry points. */
 int fa_forward_kvcache_fp8(const void* Q, const void* Kcache, const void* Vcache, void* O,
                            float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
@@ -210,6 +211,72 @@ int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* V
                                  int num_pages, int page_size, int max_pages, int d,
                                  float scale, int causal, int in_dtype, int out_dtype,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Sliding-window attention on the four KV-cache decode entries above.  Each _window entry takes the argument list of its base entry
+ * with ONE more host integer, `window` = W, directly after `causal`.  Write L_b for the clamped length, Nq for the rows per query head
+ * and c_i for row i's upper limit as the base entry defines it (L_b without causal, max(0, L_b - Nq + 1 + i) with it).
+ *   W >= 1   row i attends to the keys [lo_i, c_i), lo_i = max(0, L_b - Nq + 1 + i - W).  The lower limit is the same with and without
+ *            causal.  With causal a row sees its own position and the W - 1 before it (flash-attn's window_size = (W - 1, 0)); without
+ *            causal it sees those and every later key (window_size = (W - 1, -1)).  With Nq = 1 the row sees the last W keys.
+ *   W == 0   no window: the entry calls its base entry and returns its bits.
+ *   W < 0    hipErrorInvalidValue, before the device is touched -- as is everything the base entry rejects.
+ * A row with c_i = 0 still gets O = 0 and lse = -inf, never NaN; lo_i < c_i whenever c_i >= 1.  lse is taken over the keys the row
+ * sees, so the merge rule over disjoint key ranges (fa_forward_kvcache) still holds.
+ * What is read.  start_b = max(0, L_b - Nq + 1 - W) is row 0's lower limit: no row of the sequence sees a key below it.  Cache and
+ * page rows below start_b are never used and may hold anything, NaN bit patterns included (they reach the arithmetic as zeros, not
+ * as masked scores: a weight of 0 times a NaN would be a NaN).  On the paged entries a page that lies wholly below start_b is never
+ * dereferenced and its block_table entry is never read, so it may hold garbage: the pages behind the window can be freed and reused.
+ * Unchanged from the base entries: the clamp of seqlens_k, rows at and past L_b, bad live table entries reading as zeros, 64-bit page
+ * addresses, the meaning of scale = 0, the fp8 scales, the folding of the G query heads of a group, and "nothing on the host reads
+ * seqlens_k, block_table, k_scale or v_scale".  `window` is a host argument and is baked into a captured call; the lengths are still
+ * followed on the device.
+ * Splits and workspace.  The split count follows from the longest range one sequence can stream, not from the capacity:
+ *   span_cap = min(Ncap, roundup64(W + Nq - 1) + 64)      (Ncap when W + Nq - 1 >= Ncap)
+ * takes the place of Ncap in the base entry's rule, so grid and workspace still depend on host integers only:
+ * fa_forward_kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, W) resp. fa_forward_kvcache_paged_window_workspace_bytes(B, Hkv,
+ * G, Nq, max_pages, page_size, d, W) size the workspace of the 16-bit and of the fp8 entries (0: `workspace` may be NULL; also 0 for
+ * W < 0).  With W = 0 and with W + Nq - 1 >= Ncap they return the base function's value; otherwise the value may be SMALLER OR
+ * LARGER than the base function's (the split count is not monotone in the key count): size a windowed call with these functions.
+ * Per sequence the tiles from start_b rounded down to a multiple of 64 up to L_b are dealt out to the splits; nothing below that tile
+ * is touched.  With W >= Ncap the result equals the base entry's bit for bit; with Nq = 1 and (L_b - W) % 64 == 0 it equals
+ * fa_forward_kvcache on a cache of capacity W + 64 that holds the last W keys.  The paged entries return the bits of the contiguous
+ * ones on the same keys, the fp8 entries with all scales 1 those of the 16-bit ones on the widened cache.
+ * Not part of these entries: attention sinks, soft-capping of the logits, a ring-buffer (rolling) cache layout, a window on the
+ * prefill entries (fa_forward*), a window per sequence or per head.  NOT reference entry points. */
+size_t fa_forward_kvcache_window_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d, int window);
+size_t fa_forward_kvcache_paged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d, int window);
+int fa_forward_kvcache_window(const void* Q, const void* Kcache, const void* Vcache, void* O,
+                              float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                              const int* seqlens_k,  /* device, B int32, may be NULL (= Ncap for all) */
+                              int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal, int window,
+                              int in_dtype, int out_dtype,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int fa_forward_kvcache_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                                    float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                                    const int* seqlens_k,    /* device, B int32, may be NULL (= Ncap for all) */
+                                    const int* block_table,  /* device, [B,max_pages] int32 */
+                                    int B, int Hkv, int G, int Nq,
+                                    int num_pages, int page_size, int max_pages, int d,
+                                    float scale, int causal, int window, int in_dtype, int out_dtype,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int fa_forward_kvcache_fp8_window(const void* Q, const void* Kcache, const void* Vcache, void* O,
+                                  float* lse,            /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                                  const int* seqlens_k,  /* device, B int32, may be NULL (= Ncap for all) */
+                                  const float* k_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                                  const float* v_scale,  /* device, Hkv fp32, may be NULL (= 1.0) */
+                                  int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal, int window,
+                                  int in_dtype, int out_dtype,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                                        float* lse,              /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+                                        const int* seqlens_k,    /* device, B int32, may be NULL (= Ncap for all) */
+                                        const int* block_table,  /* device, [B,max_pages] int32 */
+                                        const float* k_scale,    /* device, Hkv fp32, may be NULL (= 1.0) */
+                                        const float* v_scale,    /* device, Hkv fp32, may be NULL (= 1.0) */
+                                        int B, int Hkv, int G, int Nq,
+                                        int num_pages, int page_size, int max_pages, int d,
+                                        float scale, int causal, int window, int in_dtype, int out_dtype,
+                                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* KV-cache append: the write half of a decode step.  Nnew new K and V rows per sequence are written behind the sequence's current
  * length, by one kernel for K and V, into any cache the decode entries above read.

@@ -6,6 +6,7 @@ occupy (the path is HBM-bound: every K and V byte is read once).
     python tools/decode_bench.py --kvcache --fill 0.25          # fa_forward_kvcache: a 32768-row cache holding 8192 keys per sequence
     python tools/decode_bench.py --paged 16 --fill 0.25         # fa_forward_kvcache_paged: the same cache in shuffled pages of 16 keys
     python tools/decode_bench.py --kvcache --fp8 [--paged 16]   # the fp8 entry against the 16-bit entry on the same shape
+    python tools/decode_bench.py --kvcache --window 4096 [--paged 64] [--fp8]   # a sliding window against two yardsticks
 
 --kvcache times fa_forward_kvcache against a cache of --Nk rows in which every sequence holds --fill x Nk keys (the lengths live
 in a device tensor); GB/s then counts the K and V bytes of the keys held, not of the capacity.  --causal adds the mask.
@@ -14,6 +15,11 @@ permutation of the pages and times fa_forward_kvcache_paged with the block table
 --fp8 (with --kvcache or --paged) quantises the cache with quantize_kv_fp8 and times fa_forward_kvcache[_paged]_fp8 AND the 16-bit
 entry on the same shape in the same process, interleaved round by round; each line counts the bytes its cache actually holds, and
 the last line gives the ratio of the medians next to the round-to-round spread of the 16-bit timings.
+--window W (with --kvcache, --paged or --fp8; --Nq 1) times three calls of ONE entry form (the fp8 one with --fp8, else the 16-bit one;
+paged with --paged), interleaved round by round in one process: "window", the windowed entry on the cache; "full", the unwindowed
+entry on the same cache; and "short", the unwindowed entry on a cache of capacity W + 64 filled to W keys -- by the split rule the
+same keys per sequence, the same split count and the same bytes as "window" when the fill leaves (L - W) a multiple of 64.  The last
+lines give window / short next to the spread of the "short" rounds, and window / full.
 """
 import argparse
 import os
@@ -40,6 +46,72 @@ def scatter_pages(torch, k, v, page_size, seed=0):
     return pools[0], pools[1], perm.view(B, max_pages).to(torch.int32).contiguous()
 
 
+def bench_window(args, torch, fa, q, k, v):
+    """--window: "window", "full" and "short" of one entry form, alternating inside every round"""
+    B, H, Nk, d, W, ps = args.B, args.H, args.Nk, args.d, args.window, args.paged
+    held = min(max(int(round(args.fill * Nk)), 0), Nk)
+    seen = min(W, held)
+    ncap_s = W + 64
+    lens, lens_s = (torch.full((B,), n, dtype=torch.int32, device="cuda") for n in (held, seen))
+    # the short cache holds the keys the window sees, at its front
+    ks_, vs_ = (torch.zeros(B, H, ncap_s, d, dtype=x.dtype, device="cuda") for x in (k, v))
+    ks_[:, :, :seen], vs_[:, :, :seen] = k[:, :, held - seen:held], v[:, :, held - seen:held]
+    scales = ()
+    if args.fp8:
+        (k, sk), (v, sv) = fa.quantize_kv_fp8(k), fa.quantize_kv_fp8(v)
+        (ks_, _), (vs_, _) = fa.quantize_kv_fp8(ks_, scale=sk), fa.quantize_kv_fp8(vs_, scale=sv)
+        scales = (sk, sv)
+    if ps:
+        k, v, table = scatter_pages(torch, k, v, ps, seed=0)
+        ks_, vs_, table_s = scatter_pages(torch, ks_, vs_, ps, seed=1)
+        entry = fa.fa_forward_kvcache_paged_fp8 if args.fp8 else fa.fa_forward_kvcache_paged
+        need = {"window": fa.kvcache_paged_window_workspace_bytes(B, H, 1, 1, Nk // ps, ps, d, W),
+                "full": fa.kvcache_paged_workspace_bytes(B, H, 1, 1, Nk // ps, ps, d),
+                "short": fa.kvcache_paged_workspace_bytes(B, H, 1, 1, ncap_s // ps, ps, d)}
+        big, small = (k, v, table), (ks_, vs_, table_s)
+    else:
+        entry = fa.fa_forward_kvcache_fp8 if args.fp8 else fa.fa_forward_kvcache
+        need = {"window": fa.kvcache_window_workspace_bytes(B, H, 1, 1, Nk, d, W), "full": fa.kvcache_workspace_bytes(B, H, 1, 1, Nk, d),
+                "short": fa.kvcache_workspace_bytes(B, H, 1, 1, ncap_s, d)}
+        big, small = (k, v), (ks_, vs_)
+    ws = torch.empty(max(max(need.values()), 1), dtype=torch.uint8, device="cuda")
+    calls = {"window": lambda: entry(q, *big, *scales, lens, causal=args.causal, workspace=ws, window=W),
+             "full": lambda: entry(q, *big, *scales, lens, causal=args.causal, workspace=ws),
+             "short": lambda: entry(q, *small, *scales, lens_s, causal=args.causal, workspace=ws)}
+    got = {name: fn().float() for name, fn in calls.items()}
+    torch.cuda.synchronize()
+    same = torch.equal(got["window"], got["short"]) if (held - seen) % 64 == 0 else None
+    for fn in calls.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in calls}
+    for _ in range(args.rounds):
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / args.iters)
+    elem = 1 if args.fp8 else 2
+    form = ("fp8" if args.fp8 else "16-bit") + (f" paged {ps}" if ps else "") + (" causal" if args.causal else "")
+    med = {}
+    for name in calls:
+        med[name] = statistics.median(times[name])
+        keys = held if name == "full" else seen
+        kv_bytes = 2.0 * B * H * keys * d * elem
+        print(f"B{B} H{H} Nq1 Nk{Nk} d{d} {form} window {W}, {held} keys held [{name}]: workspace {need[name]} B, median "
+              f"{med[name] * 1e3:.1f} us (rounds {min(times[name]) * 1e3:.1f}-{max(times[name]) * 1e3:.1f}), K+V {kv_bytes / 1e6:.1f} MB -> "
+              f"{kv_bytes / med[name] / 1e6:.0f} GB/s")
+    spread = (max(times["short"]) - min(times["short"])) / med["short"]
+    ratio = med["window"] / med["short"]
+    print(f"window / short = {ratio:.3f}; the short rounds spread over {spread * 100:.1f} %: bound 1 + spread + 5 % = {1 + spread + 0.05:.3f} "
+          f"-> {'within' if ratio <= 1 + spread + 0.05 else 'MISSED'}" + ("" if same is None else f"; results bit-equal: {same}"))
+    print(f"window / full = {med['window'] / med['full']:.3f} (keys seen / keys held = {seen / max(held, 1):.3f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -56,6 +128,8 @@ def main():
                     help="fa_forward_kvcache_paged on the cache scattered into shuffled pages of PAGE_SIZE keys (implies --kvcache)")
     ap.add_argument("--fp8", action="store_true",
                     help="with --kvcache / --paged: also time the fp8 entry on the quantised cache, interleaved with the 16-bit one")
+    ap.add_argument("--window", type=int, default=0, metavar="W",
+                    help="with --kvcache / --paged / --fp8: time the windowed entry against the unwindowed one and a cache of W + 64 rows")
     args = ap.parse_args()
     if args.paged:
         args.kvcache = True
@@ -68,6 +142,10 @@ def main():
     k, v = (torch.randn(args.B, args.H, args.Nk, args.d, generator=g, device="cuda").half() for _ in range(2))
     if not args.kvcache and (args.fill != 1.0 or args.causal or args.fp8):
         ap.error("--fill, --causal and --fp8 need --kvcache")
+    if args.window and (not args.kvcache or args.window < 1 or args.Nq != 1 or (args.window + 64) % max(args.paged, 1)):
+        ap.error("--window needs --kvcache or --paged, W >= 1, --Nq 1 and, with --paged, a page size that divides W + 64")
+    if args.window:
+        return bench_window(args, torch, fa, q, k, v)
     calls = {}   # name -> (call, bytes per K/V element)
     if args.kvcache:
         held = min(max(int(round(args.fill * args.Nk)), 0), args.Nk)
