@@ -113,27 +113,20 @@ def lib() -> C.CDLL:
         L.fa_selected_kernel.argtypes = [i, i, i, i, i, i]
         L.fa_selected_kernel.restype = C.c_char_p
         L.fa_forward_splitkv_workspace_bytes.restype = C.c_size_t
-        L.fa_forward_kvcache.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache.restype = C.c_int
+        # the eight decode entries, from one rule: Q, K, V, O, lse, seqlens [, table] [, k_scale, v_scale], B, Hkv, G, Nq, Ncap (paged:
+        # num_pages, page_size, max_pages), d, scale, causal [, window], in_dtype, out_dtype, workspace, workspace_bytes, stream
+        for paged in (False, True):
+            for fp8 in (False, True):
+                for window in (False, True):
+                    fn = getattr(L, "fa_forward_kvcache" + "_paged" * paged + "_fp8" * fp8 + "_window" * window)
+                    fn.argtypes = ([vp] * (6 + paged + 2 * fp8) + [i] * (7 if paged else 5) + [i, f, i] + [i] * window
+                                   + [i, i, vp, C.c_size_t, vp])
+                    fn.restype = C.c_int
         L.fa_forward_kvcache_workspace_bytes.argtypes = [i, i, i, i, i, i]
         L.fa_forward_kvcache_workspace_bytes.restype = C.c_size_t
-        L.fa_forward_kvcache_paged.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_paged.restype = C.c_int
-        L.fa_forward_kvcache_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_fp8.restype = C.c_int
-        L.fa_forward_kvcache_paged_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_paged_fp8.restype = C.c_int
         L.fa_forward_kvcache_paged_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_workspace_bytes.restype = C.c_size_t
-        # the windowed forms: the base entry's list with `int window` after `causal`, the sizing functions' with it at the end
-        L.fa_forward_kvcache_window.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_paged_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_fp8_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, i, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_kvcache_paged_fp8_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, i, i, i, vp,
-                                                          C.c_size_t, vp]
-        for s in ("fa_forward_kvcache_window", "fa_forward_kvcache_paged_window", "fa_forward_kvcache_fp8_window",
-                  "fa_forward_kvcache_paged_fp8_window"):
-            getattr(L, s).restype = C.c_int
+        # the windowed sizing functions: the base one's list with `int window` at the end
         L.fa_forward_kvcache_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
         L.fa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
         L.fa_forward_kvcache_paged_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]

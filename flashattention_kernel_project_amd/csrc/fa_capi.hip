@@ -89,8 +89,8 @@ FA_EXPORT int fa_forward_kvcache(const void* Q, const void* Kcache, const void* 
                        int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal,
                        int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvcache_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
-                                      workspace, workspace_bytes, static_cast<hipStream_t>(stream)});
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)}}});
 }
 
 FA_EXPORT size_t fa_forward_kvcache_paged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d)
@@ -104,17 +104,19 @@ FA_EXPORT int fa_forward_kvcache_paged(const void* Q, const void* Kpool, const v
                              void* stream)
 {
     // Ncap (0 here) is set by the dispatcher once max_pages * page_size is known to fit
-    return (int)fa::kvpaged_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
-                                       workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
-                                      block_table, num_pages, page_size, max_pages});
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                             .table = block_table, .num_pages = num_pages, .page_size = page_size, .max_pages = max_pages},
+                                       .paged = true});
 }
 
 FA_EXPORT int fa_forward_kvcache_fp8(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse, const int* seqlens_k,
                            const float* k_scale, const float* v_scale, int B, int Hkv, int G, int Nq, int Ncap, int d, float scale,
                            int causal, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvcache_fp8_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
-                                          workspace, workspace_bytes, static_cast<hipStream_t>(stream)}, k_scale, v_scale);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)}},
+                                       .k_scale = k_scale, .v_scale = v_scale, .fp8 = true});
 }
 
 FA_EXPORT int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* seqlens_k,
@@ -122,9 +124,10 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, con
                                  int num_pages, int page_size, int max_pages, int d, float scale, int causal, int in_dtype,
                                  int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvpaged_fp8_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
-                                           workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
-                                          block_table, num_pages, page_size, max_pages}, k_scale, v_scale);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                             .table = block_table, .num_pages = num_pages, .page_size = page_size, .max_pages = max_pages},
+                                       .k_scale = k_scale, .v_scale = v_scale, .paged = true, .fp8 = true});
 }
 
 FA_EXPORT size_t fa_forward_kvcache_window_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d, int window)
@@ -142,8 +145,9 @@ FA_EXPORT int fa_forward_kvcache_window(const void* Q, const void* Kcache, const
                               int B, int Hkv, int G, int Nq, int Ncap, int d, float scale, int causal, int window,
                               int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvcache_window_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype,
-                                             out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)}, window);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)}},
+                                       .window = window});
 }
 
 FA_EXPORT int fa_forward_kvcache_paged_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
@@ -151,9 +155,10 @@ FA_EXPORT int fa_forward_kvcache_paged_window(const void* Q, const void* Kpool, 
                                     int page_size, int max_pages, int d, float scale, int causal, int window, int in_dtype,
                                     int out_dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvpaged_window_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
-                                              workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
-                                             block_table, num_pages, page_size, max_pages}, window);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                             .table = block_table, .num_pages = num_pages, .page_size = page_size, .max_pages = max_pages},
+                                       .window = window, .paged = true});
 }
 
 FA_EXPORT int fa_forward_kvcache_fp8_window(const void* Q, const void* Kcache, const void* Vcache, void* O, float* lse,
@@ -161,9 +166,9 @@ FA_EXPORT int fa_forward_kvcache_fp8_window(const void* Q, const void* Kcache, c
                                   int Ncap, int d, float scale, int causal, int window, int in_dtype, int out_dtype, void* workspace,
                                   size_t workspace_bytes, void* stream)
 {
-    return (int)fa::kvcache_fp8_window_dispatch({Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype,
-                                                 out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
-                                                k_scale, v_scale, window);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kcache, Vcache, O, lse, seqlens_k, B, Hkv, G, Nq, Ncap, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)}},
+                                       .k_scale = k_scale, .v_scale = v_scale, .window = window, .fp8 = true});
 }
 
 FA_EXPORT int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
@@ -172,9 +177,10 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpo
                                         int causal, int window, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes,
                                         void* stream)
 {
-    return (int)fa::kvpaged_fp8_window_dispatch({{Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype,
-                                                  out_dtype, workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
-                                                 block_table, num_pages, page_size, max_pages}, k_scale, v_scale, window);
+    return (int)fa::kvdecode_dispatch({.p = {.c = {Q, Kpool, Vpool, O, lse, seqlens_k, B, Hkv, G, Nq, 0, d, scale, causal, in_dtype, out_dtype,
+                                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream)},
+                                             .table = block_table, .num_pages = num_pages, .page_size = page_size, .max_pages = max_pages},
+                                       .k_scale = k_scale, .v_scale = v_scale, .window = window, .paged = true, .fp8 = true});
 }
 
 FA_EXPORT int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,

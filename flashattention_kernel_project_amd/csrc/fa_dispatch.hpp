@@ -1,6 +1,7 @@
-// fa_dispatch.hpp -- the host side every translation unit shares: the argument struct of a forward, the element-type switch,
-// and the one declaration of each host function that crosses a translation unit.  Private to csrc/ (the public contract is
-// include/fa_mi355.h); no device code lives here.
+// fa_dispatch.hpp -- the host side every translation unit shares: the argument structs (one per family: a forward, a KV-cache
+// decode, an append), the element-type switch, and the one declaration of each host function that crosses a translation unit.
+// Private to csrc/ (the public contract is include/fa_mi355.h); no device code and none of the kernels' argument packs live here
+// (the decode launcher that needs both is fa_fwd_kvdecode.hpp).
 #pragma once
 #include "fa_common.hpp"
 
@@ -90,11 +91,6 @@ struct KvCacheArgs {
     size_t ws_bytes;
     hipStream_t stream;
 };
-hipError_t kvcache_dispatch(const KvCacheArgs& a);
-hipError_t kvcache_check(const KvCacheArgs& a);   // the argument checks of kvcache_dispatch alone
-size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D);
-hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
-                           hipStream_t stream);   // the merge kernel of the KV-cache split, launched for the paged entry too
 // Paged KV-cache decode (fa_forward_kvcache_paged): the KvCacheArgs with K, V as page pools [num_pages, Hkv, page_size, D],
 // Ncap = max_pages * page_size, and the device block table [B, max_pages] int32.
 struct KvPagedArgs {
@@ -102,21 +98,36 @@ struct KvPagedArgs {
     const int* table;
     int num_pages, page_size, max_pages;
 };
-hipError_t kvpaged_dispatch(const KvPagedArgs& a);
-hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& with_capacity, int& lg_page);   // the argument checks of kvpaged_dispatch alone
-// fp8 (OCP e4m3fn) caches -- fa_fwd_kvfp8.hip: K, V point at one-byte elements that are widened to in_dtype on the way into LDS;
-// k_scale, v_scale: device, Hkv fp32 each, or null (1.0).  Everything else as in the two entries above, workspace included.
-hipError_t kvcache_fp8_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale);
-hipError_t kvpaged_fp8_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale);
-size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
-// Sliding-window decode -- fa_fwd_kvwindow.hip (16-bit caches), fa_fwd_kvwindow_fp8.hip (fp8 caches): the four entries above with
-// a host integer `window` >= 1 (row i sees the last `window` keys up to its own position; 0: the entry above itself; < 0:
-// rejected).  The split count, and with it grid and workspace, follows from window_span_cap() in place of the capacity.
+// All eight decode entries (fa_forward_kvcache and its _paged / _fp8 / _window forms): p.c alone for a contiguous cache, all of p
+// with `paged` (Ncap is then filled in by the dispatcher).  With `fp8` K, V point at one-byte e4m3fn elements that are widened to
+// in_dtype on the way into LDS, and k_scale, v_scale are device pointers to Hkv fp32 each, or null (1.0).  window >= 1: row i
+// sees the last `window` keys up to its own position, and the split count, with it grid and workspace, follows from
+// window_span_cap() in place of the capacity; 0: no window; < 0: rejected.
+struct KvDecodeArgs {
+    KvPagedArgs p;
+    const float *k_scale, *v_scale;
+    int window;
+    bool paged, fp8;
+};
+hipError_t kvdecode_dispatch(const KvDecodeArgs& a);
+// What kvdecode_dispatch hands checked arguments to: one function per translation unit that owns decode kernels -- fa_fwd_kvcache,
+// _kvpaged, _kvfp8 (contiguous and paged), _kvwindow and _kvwindow_fp8 (window >= 1; contiguous and paged).  lg_page: log2 of the
+// page size (paged only).
+hipError_t kvcache_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvpaged_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvfp8_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvwindow_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvwindow_fp8_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
+                           hipStream_t stream);   // the merge kernel behind a split, for all of them
+// The argument checks alone: the append runs them too, so it accepts exactly the caches the decode accepts.  kvpaged_check fills
+// in the capacity and returns page_log2(page_size): log2 of a page size the kernels take, else -1.
+hipError_t kvcache_check(const KvCacheArgs& a);
+hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& with_capacity, int& lg_page);
+int page_log2(int page_size);
 int window_span_cap(int Nq, int Ncap, int window);   // the longest key range a sequence can stream, in keys (window >= 1)
-hipError_t kvcache_window_dispatch(const KvCacheArgs& a, int window);
-hipError_t kvpaged_window_dispatch(const KvPagedArgs& a, int window);
-hipError_t kvcache_fp8_window_dispatch(const KvCacheArgs& a, const float* k_scale, const float* v_scale, int window);
-hipError_t kvpaged_fp8_window_dispatch(const KvPagedArgs& a, const float* k_scale, const float* v_scale, int window);
+size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D);
+size_t kvpaged_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D);
 size_t kvwindow_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D, int window);
 size_t kvpaged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int D, int window);
 // KV-cache append (fa_kvcache_append and its paged / fp8 forms) -- fa_kvcache_append.hip: Knew, Vnew [B, Hkv, Nnew, D] of `dtype` go

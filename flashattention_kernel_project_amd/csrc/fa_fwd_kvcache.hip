@@ -1,44 +1,11 @@
 // fa_fwd_kvcache.hip -- decode against a pre-allocated KV cache (fa_forward_kvcache): the split-KV stream of fa_fwd_split.hip with
 // the key count of each sequence read on the device, a causal mask aligned to the end of the cache and a log-sum-exp output.
-// DESIGN.md section 7 has the reasoning; the kernels are the kCache = true instantiations of fa_fwd_split_kernel.hpp.
-#include "fa_fwd_split_kernel.hpp"
-#include "fa_dispatch.hpp"
+// DESIGN.md section 7 has the reasoning; the kernels are the CacheArgs instantiations of fa_fwd_split_kernel.hpp, launched through
+// the host path of fa_fwd_kvdecode.hpp like those of the four units beside this one.  Also here, once for all eight decode entries:
+// the argument checks, the entry kvdecode_dispatch and the merge kernel.
+#include "fa_fwd_kvdecode.hpp"
 
 namespace fa {
-
-// ---- KV-cache decode: BH = B * Hkv K/V heads of Ncap rows, rows = G * Nq folded query rows per K/V head ----
-// Grid, split count and workspace follow from the capacity alone: nothing here reads seqlens, so a captured launch stays valid
-// when the lengths change in place.
-template <typename T, int D, bool kOutF32>
-static hipError_t launch_kvcache(const KvCacheArgs& a, int BH, int rows)
-{
-    using G = TileGeom<D>;
-    const int S = split_count(BH, rows, a.Ncap);
-    const int nqb = (rows + split::kRows - 1) / split::kRows;
-    const long long nwg = (long long)BH * nqb * S;
-    if (nwg > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    if (S > 1 && (!a.ws || a.ws_bytes < split_workspace_bytes(BH, rows, a.Ncap, D))) return hipErrorInvalidValue;
-    const uint16_t *q = static_cast<const uint16_t*>(a.Q), *k = static_cast<const uint16_t*>(a.K), *v = static_cast<const uint16_t*>(a.V);
-    hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_split_kernel<T, D, kOutF32, false, true, CacheArgs>), G::kLdsBytes);
-    if (attr == hipSuccess) attr = ensure_dyn_lds(reinterpret_cast<const void*>(&fa_fwd_split_kernel<T, D, kOutF32, true, true, CacheArgs>), G::kLdsBytes);
-    if (attr != hipSuccess) return attr;
-    // the one-pass kernel stores the log-sum-exp itself; behind a split the merge does
-    const CacheArgs ca = {a.seqlens, S == 1 ? a.lse : nullptr, a.Hkv, a.Nq, a.causal};
-    if (S == 1) {
-        FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, false, true, CacheArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                           a.stream, q, k, v, a.O, static_cast<float*>(nullptr), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), ca);
-        return launch_status();
-    }
-    FA_LAUNCH((fa_fwd_split_kernel<T, D, kOutF32, true, true, CacheArgs>), dim3((unsigned)nwg), dim3(64 * split::kW), G::kLdsBytes,
-                       a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), ca);
-    hipError_t e = launch_status();
-    if (e != hipSuccess) return e;
-    const long long out_rows = (long long)BH * rows;   // one wave per output row
-    if (out_rows > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    FA_LAUNCH((fa_split_combine_kernel<T, kOutF32, true, float*>), dim3((unsigned)out_rows), dim3(64), 0, a.stream,
-                       static_cast<const float*>(a.ws), a.O, BH, rows, D, S, a.lse);
-    return launch_status();
-}
 
 size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D)
 {
@@ -47,8 +14,8 @@ size_t kvcache_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int D)
     return split_workspace_bytes(B * Hkv, G * Nq, Ncap, D);
 }
 
-// What every KV-cache entry rejects before the device is touched (the fp8 entries of fa_fwd_kvfp8.hip too: their one-byte
-// elements keep the 16-bit bound on the byte offsets).
+// What every KV-cache entry rejects before the device is touched (the fp8 entries too: their one-byte elements keep the 16-bit
+// bound on the byte offsets).
 hipError_t kvcache_check(const KvCacheArgs& a)
 {
     if (!a.Q || !a.K || !a.V || !a.O) return hipErrorInvalidValue;
@@ -64,21 +31,31 @@ hipError_t kvcache_check(const KvCacheArgs& a)
     return hipSuccess;
 }
 
-hipError_t kvcache_dispatch(const KvCacheArgs& a)
+// The translation unit that owns the kernels of the pack the flags name.  Window 0 is the un-windowed entry itself: it launches
+// the un-windowed kernels.
+static hipError_t kvdecode_handover(const KvDecodeArgs& d, int lg_page)
 {
-    const hipError_t bad = kvcache_check(a);
-    if (bad != hipSuccess) return bad;
-    const int BH = a.B * a.Hkv, rows = a.G * a.Nq;
-    if (a.D == 64)
-        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
-            return launch_kvcache<decltype(t), 64, decltype(f32)::value>(a, BH, rows);
-        });
-    return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
-        return launch_kvcache<decltype(t), 128, decltype(f32)::value>(a, BH, rows);
-    });
+    if (d.window == 0) return d.fp8 ? kvfp8_decode(d, lg_page) : d.paged ? kvpaged_decode(d, lg_page) : kvcache_decode(d, lg_page);
+    return d.fp8 ? kvwindow_fp8_decode(d, lg_page) : kvwindow_decode(d, lg_page);
 }
 
-// The merge behind a split, for the paged entry (fa_fwd_kvpaged.hip): the kernel is instantiated in this translation unit only.
+// The one entry behind the eight fa_forward_kvcache* functions: the checks, once, then the hand-over.
+hipError_t kvdecode_dispatch(const KvDecodeArgs& d)
+{
+    if (d.window < 0) return hipErrorInvalidValue;
+    if (!d.paged) {
+        const hipError_t bad = kvcache_check(d.p.c);
+        return bad != hipSuccess ? bad : kvdecode_handover(d, 0);
+    }
+    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8};   // q.p: d.p with the capacity, from the check
+    int lg_page;
+    const hipError_t bad = kvpaged_check(d.p, q.p, lg_page);
+    return bad != hipSuccess ? bad : kvdecode_handover(q, lg_page);
+}
+
+hipError_t kvcache_decode(const KvDecodeArgs& d, int lg_page) { return dispatch_kvdecode<CacheArgs>(d, lg_page); }
+
+// The merge behind a split, for every decode entry: the kernel is instantiated in this translation unit only.
 hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
                            hipStream_t stream)
 {

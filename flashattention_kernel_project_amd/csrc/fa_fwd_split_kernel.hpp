@@ -6,8 +6,8 @@
 // entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
 // selects (profiles/kvcache_fp8.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
 // behind `if constexpr (kWindow)` (profiles/kvcache_window.txt).
-// The sets are instantiated in separate translation units so that none perturbs another's register allocation.
-// The design notes are at the head of fa_fwd_split.hip and in DESIGN.md 7.1.
+// The sets are instantiated in separate translation units so that none perturbs another's register allocation; the host path of the
+// KV-cache sets (pack builder, launcher, type switch) is fa_fwd_kvdecode.hpp.  Design notes: head of fa_fwd_split.hip, DESIGN.md 7.1.
 #pragma once
 #include "fa_tile.hpp"
 

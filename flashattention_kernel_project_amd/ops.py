@@ -148,6 +148,71 @@ def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
     return int(capi.lib().fa_forward_splitkv_workspace_bytes(B, H, Nq, Nk, d))
 
 
+def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream, window, paged=False,
+            block_table=None, scales=None):
+    """The four decode front ends: k, v (named k_name, v_name in messages) are a cache [B,Hkv,Ncap,d] or, with `paged`, a pool
+    [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one.  The C entry
+    is fa_forward_kvcache + _paged + _fp8 + _window, and each suffix inserts its arguments: the table after the lengths, the two
+    scales after that, the geometry of the pool in the place of Ncap, the window after causal."""
+    import torch
+    fp8 = scales is not None
+    if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[3] != k.shape[3] or (not paged and q.shape[0] != k.shape[0]):
+        raise ValueError(f"q must be [B,Hq,Nq,d] and {k_name}, {v_name} " + ("[num_pages,Hkv,page_size,d]" if paged else "[B,Hkv,Ncap,d]"))
+    B, Hq, Nq, d = q.shape
+    Hkv = k.shape[1]
+    dts = (torch.float16, torch.bfloat16)
+    if fp8:   # the cache format is judged first, then (paged) the table: before q and before anything that needs a device
+        if k.dtype != torch.float8_e4m3fn or v.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{k_name}, {v_name}: {_FP8_CACHE} (got {k.dtype}, {v.dtype})")
+        args = (_table_ptr(block_table, B),) if paged else ()
+        if q.dtype not in dts:
+            raise ValueError("q must be fp16 or bf16")
+    if Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
+    G = Hq // Hkv
+    if not fp8 and (q.dtype not in dts or k.dtype != q.dtype or v.dtype != q.dtype):
+        raise ValueError(f"q, {k_name}, {v_name} must all be fp16 or all bf16")
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    if fp8:
+        args += tuple(_scale_ptrs(scales[0], scales[1], Hkv))
+        cache_dts = (torch.float8_e4m3fn,)
+    else:
+        args = (_table_ptr(block_table, B),) if paged else ()
+        cache_dts = dts
+    len_ptr = None
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
+            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
+        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k, "k cache" if fp8 else k_name, cache_dts),
+            _dev_ptr(v, "v cache" if fp8 else v_name, cache_dts))
+    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+    window = _window(window)
+    # in the place of Ncap a pool has (num_pages, page_size, max_pages)
+    cap = (k.shape[0], k.shape[2], block_table.shape[1]) if paged else (k.shape[2],)
+    if workspace is None:
+        # from the shape and the window alone (the split count reads no device property); the 16-bit entry's for an fp8 cache
+        need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, cap[2], cap[1], d, window) if paged \
+            else kvcache_window_workspace_bytes(B, Hkv, G, Nq, cap[0], d, window)
+        if need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    fn_name = "fa_forward_kvcache" + ("_paged" if paged else "") + ("_fp8" if fp8 else "") + ("_window" if window else "")
+    args = ptrs + (out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr) + args + (B, Hkv, G, Nq) + cap \
+        + (d, float(scale), 1 if causal else 0) + ((window,) if window else ()) \
+        + (capi.F16 if q.dtype == torch.float16 else capi.BF16, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
+           ws_ptr, ws_len, _stream_ptr(stream))
+    with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace)):
+        code = getattr(capi.lib(), fn_name)(*args)
+    capi.check(fn_name, code)
+    return (out, lse) if return_lse else out
+
+
 def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = False, scale: float | None = None,
                        out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0):
     """Decode against a pre-allocated cache (fa_forward_kvcache): q [B,Hq,Nq,d], k_cache/v_cache [B,Hkv,Ncap,d]
@@ -162,53 +227,8 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     window: 0 (no window), or W >= 1: row i sees only the keys [max(0, L_b - Nq + 1 + i - W), its upper limit) -- with causal its own
     position and the W - 1 before it (fa_forward_kvcache_window).  Keys below row 0's lower limit are never used.  The window is a host
     integer (baked into a captured call); the workspace is then sized by kvcache_window_workspace_bytes."""
-    import torch
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
-            or q.shape[3] != k_cache.shape[3]:
-        raise ValueError("q must be [B,Hq,Nq,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
-    B, Hq, Nq, d = q.shape
-    Hkv, Ncap = k_cache.shape[1], k_cache.shape[2]
-    if Hq % Hkv != 0:
-        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
-    G = Hq // Hkv
-    dts = (torch.float16, torch.bfloat16)
-    if q.dtype not in dts or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise ValueError("q, k_cache, v_cache must all be fp16 or all bf16")
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
-    out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
-    len_ptr = None
-    if cache_seqlens is not None:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
-            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
-        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
-    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_cache, "k_cache", dts), _dev_ptr(v_cache, "v_cache", dts))
-    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
-    window = _window(window)
-    # from the shape (and the window) alone: the split count reads no device property
-    need = kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window) if window else kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
-    if window:
-        with torch.cuda.device(_one_device(q, k_cache, v_cache, cache_seqlens, workspace)):
-            code = capi.lib().fa_forward_kvcache_window(
-                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, B, Hkv, G, Nq, Ncap, d, float(scale),
-                1 if causal else 0, window, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
-                ws_ptr, ws_len, _stream_ptr(stream))
-        capi.check("fa_forward_kvcache_window", code)
-        return (out, lse) if return_lse else out
-    with torch.cuda.device(_one_device(q, k_cache, v_cache, cache_seqlens, workspace)):
-        code = capi.lib().fa_forward_kvcache(
-            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, B, Hkv, G, Nq, Ncap, d, float(scale),
-            1 if causal else 0, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
-            ws_ptr, ws_len, _stream_ptr(stream))
-    capi.check("fa_forward_kvcache", code)
-    return (out, lse) if return_lse else out
+    return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
+                   window)
 
 
 def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int) -> int:
@@ -241,56 +261,8 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
     position and the W - 1 before it (fa_forward_kvcache_paged_window).  Keys below row 0's lower limit are never used.  The window is a host
     integer (baked into a captured call); the workspace is then sized by kvcache_paged_window_workspace_bytes.
     Under a window a page wholly below row 0's lower limit is not dereferenced and its table entry is not read."""
-    import torch
-    if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
-        raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
-    B, Hq, Nq, d = q.shape
-    num_pages, Hkv, page_size = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
-    if Hq % Hkv != 0:
-        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
-    G = Hq // Hkv
-    dts = (torch.float16, torch.bfloat16)
-    if q.dtype not in dts or k_pool.dtype != q.dtype or v_pool.dtype != q.dtype:
-        raise ValueError("q, k_pool, v_pool must all be fp16 or all bf16")
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
-    out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
-    if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B:
-        raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
-    max_pages = block_table.shape[1]
-    tbl_ptr = _dev_ptr(block_table, "block_table", (torch.int32,))
-    len_ptr = None
-    if cache_seqlens is not None:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
-            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
-        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
-    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k_pool, "k_pool", dts), _dev_ptr(v_pool, "v_pool", dts))
-    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
-    window = _window(window)
-    need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window) if window \
-        else kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # from the shape (and the window) alone
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
-    if window:
-        with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, cache_seqlens, workspace)):
-            code = capi.lib().fa_forward_kvcache_paged_window(
-                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, B, Hkv, G, Nq, num_pages, page_size,
-                max_pages, d, float(scale), 1 if causal else 0, window, in_dt,
-                capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, ws_ptr, ws_len, _stream_ptr(stream))
-        capi.check("fa_forward_kvcache_paged_window", code)
-        return (out, lse) if return_lse else out
-    with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, cache_seqlens, workspace)):
-        code = capi.lib().fa_forward_kvcache_paged(
-            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, B, Hkv, G, Nq, num_pages, page_size,
-            max_pages, d, float(scale), 1 if causal else 0, in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
-            ws_ptr, ws_len, _stream_ptr(stream))
-    capi.check("fa_forward_kvcache_paged", code)
-    return (out, lse) if return_lse else out
+    return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
+                   window, paged=True, block_table=block_table)
 
 
 def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int) -> int:
@@ -306,43 +278,6 @@ _FP8_CACHE = "an fp8 cache must be torch.float8_e4m3fn (OCP e4m3fn, the gfx950 f
              "16-bit caches are not accepted here"
 
 
-def _fp8_decode_args(q, k8, v8, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, what):
-    """What the two fp8 decode front ends share once the shapes are known: dtype checks, scales, lengths, outputs.
-    k8/v8: [*, Hkv, rows, d] float8_e4m3fn.  -> (pointers in ABI order up to v_scale without the table, out, lse, in_dt, out_dt)"""
-    import torch
-    B, Hq, Nq, d = q.shape
-    Hkv = k8.shape[1]
-    if k8.dtype != torch.float8_e4m3fn or v8.dtype != torch.float8_e4m3fn:
-        raise ValueError(f"{what}: {_FP8_CACHE} (got {k8.dtype}, {v8.dtype})")
-    dts = (torch.float16, torch.bfloat16)
-    if q.dtype not in dts:
-        raise ValueError("q must be fp16 or bf16")
-    if Hq % Hkv != 0:
-        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
-    out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
-    scale_ptrs = []
-    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-        if s is None:
-            scale_ptrs.append(None)
-            continue
-        if not isinstance(s, torch.Tensor) or s.dim() != 1 or s.shape[0] != Hkv or s.dtype != torch.float32:
-            raise ValueError(f"{name} must be a float32 device tensor of shape [Hkv] = [{Hkv}]")
-        scale_ptrs.append(_dev_ptr(s, name, (torch.float32,)))
-    len_ptr = None
-    if cache_seqlens is not None:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
-            raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
-        len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
-    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k8, "k cache", (torch.float8_e4m3fn,)), _dev_ptr(v8, "v cache", (torch.float8_e4m3fn,)))
-    out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
-    out_dt = capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME
-    return ptrs, len_ptr, scale_ptrs, out, lse, in_dt, out_dt
-
-
 def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, causal: bool = False,
                            scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None,
                            window: int = 0):
@@ -355,36 +290,8 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     and its scales from a 16-bit or fp32 tensor.
     Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (then
     fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes) -- is fa_forward_kvcache's."""
-    import torch
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0] \
-            or q.shape[3] != k_cache.shape[3]:
-        raise ValueError("q must be [B,Hq,Nq,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
-    B, Hq, Nq, d = q.shape
-    Hkv, Ncap = k_cache.shape[1], k_cache.shape[2]
-    ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
-        q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_cache, v_cache")
-    G = Hq // Hkv
-    window = _window(window)
-    # the 16-bit entry's, from the shape (and the window) alone
-    need = kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window) if window else kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
-    if window:
-        with torch.cuda.device(_one_device(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, workspace)):
-            code = capi.lib().fa_forward_kvcache_fp8_window(
-                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq, Ncap, d,
-                float(scale), 1 if causal else 0, window, in_dt, out_dt, ws_ptr, ws_len, _stream_ptr(stream))
-        capi.check("fa_forward_kvcache_fp8_window", code)
-        return (out, lse) if return_lse else out
-    with torch.cuda.device(_one_device(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, workspace)):
-        code = capi.lib().fa_forward_kvcache_fp8(
-            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq, Ncap, d,
-            float(scale), 1 if causal else 0, in_dt, out_dt, ws_ptr, ws_len, _stream_ptr(stream))
-    capi.check("fa_forward_kvcache_fp8", code)
-    return (out, lse) if return_lse else out
+    return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
+                   window, scales=(k_scale, v_scale))
 
 
 def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
@@ -394,43 +301,8 @@ def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v
     torch.float8_e4m3fn, block_table as in fa_forward_kvcache_paged, k_scale / v_scale and everything else as in
     fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes; with a window (fa_forward_kvcache_paged_fp8_window)
     kvcache_paged_window_workspace_bytes."""
-    import torch
-    if q.dim() != 4 or k_pool.dim() != 4 or v_pool.shape != k_pool.shape or q.shape[3] != k_pool.shape[3]:
-        raise ValueError("q must be [B,Hq,Nq,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
-    B, Hq, Nq, d = q.shape
-    num_pages, Hkv, page_size = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
-    if k_pool.dtype != torch.float8_e4m3fn or v_pool.dtype != torch.float8_e4m3fn:   # judged first, as in the contiguous front end
-        raise ValueError(f"k_pool, v_pool: {_FP8_CACHE} (got {k_pool.dtype}, {v_pool.dtype})")
-    if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B:
-        raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
-    max_pages = block_table.shape[1]
-    tbl_ptr = _dev_ptr(block_table, "block_table", (torch.int32,))
-    ptrs, len_ptr, (ks_ptr, vs_ptr), out, lse, in_dt, out_dt = _fp8_decode_args(
-        q, k_pool, v_pool, k_scale, v_scale, cache_seqlens, out_dtype, return_lse, "k_pool, v_pool")
-    G = Hq // Hkv
-    window = _window(window)
-    need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window) if window \
-        else kvcache_paged_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d)   # the 16-bit entry's, from the shape alone
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
-    if window:
-        with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, workspace)):
-            code = capi.lib().fa_forward_kvcache_paged_fp8_window(
-                *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq,
-                num_pages, page_size, max_pages, d, float(scale), 1 if causal else 0, window, in_dt, out_dt, ws_ptr, ws_len,
-                _stream_ptr(stream))
-        capi.check("fa_forward_kvcache_paged_fp8_window", code)
-        return (out, lse) if return_lse else out
-    with torch.cuda.device(_one_device(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, workspace)):
-        code = capi.lib().fa_forward_kvcache_paged_fp8(
-            *ptrs, out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, G, Nq,
-            num_pages, page_size, max_pages, d, float(scale), 1 if causal else 0, in_dt, out_dt, ws_ptr, ws_len,
-            _stream_ptr(stream))
-    capi.check("fa_forward_kvcache_paged_fp8", code)
-    return (out, lse) if return_lse else out
+    return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
+                   window, paged=True, block_table=block_table, scales=(k_scale, v_scale))
 
 
 FP8_E4M3_MAX = 448.0   # largest finite e4m3fn value

@@ -38,123 +38,94 @@ def register() -> None:
     import torch
     from . import ops
 
+    def opt(t):
+        return None if t is None else t.contiguous()
+
+    def out_dtype(q, out_fp32):
+        return torch.float32 if out_fp32 else q.dtype
+
+    def stream(t):
+        return torch.cuda.current_stream(t.device)
+
+    def decode_fake(q, *args):   # every decode op: an output of q's shape; out_fp32 is each schema's last argument
+        return q.new_empty(q.shape, dtype=out_dtype(q, args[-1]))
+
     @torch.library.custom_op("fa_mi355::forward", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k, Tensor v, float scale, bool causal, bool out_fp32) -> Tensor")
     def forward(q, k, v, scale, causal, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
-        return ops.fa_forward(q.contiguous(), k.contiguous(), v.contiguous(), scale=scale,
-                              out_dtype=torch.float32 if out_fp32 else q.dtype, causal=causal, stream=stream)
+        return ops.fa_forward(q.contiguous(), k.contiguous(), v.contiguous(), scale=scale, out_dtype=out_dtype(q, out_fp32),
+                              causal=causal, stream=stream(q))
 
     @forward.register_fake
     def _(q, k, v, scale, causal, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+        return q.new_empty(q.shape, dtype=out_dtype(q, out_fp32))
 
     @torch.library.custom_op("fa_mi355::decode", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
                                     "bool out_fp32) -> Tensor")
     def decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
-        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
-                                      None if cache_seqlens is None else cache_seqlens.contiguous(), causal=causal, scale=scale,
-                                      out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
-
-    @decode.register_fake
-    def _(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
+                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q))
 
     @torch.library.custom_op("fa_mi355::decode_paged", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
                                     "bool causal, bool out_fp32) -> Tensor")
     def decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            None if cache_seqlens is None else cache_seqlens.contiguous(), causal=causal,
-                                            scale=scale, out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
-
-    @decode_paged.register_fake
-    def _(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
-
-    def opt(t):
-        return None if t is None else t.contiguous()
+                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                            stream=stream(q))
 
     @torch.library.custom_op("fa_mi355::decode_fp8", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
                                     "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
     def decode_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          opt(cache_seqlens), causal=causal, scale=scale,
-                                          out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
-
-    @decode_fp8.register_fake
-    def _(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                          stream=stream(q))
 
     @torch.library.custom_op("fa_mi355::decode_paged_fp8", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
                                     "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
     def decode_paged_fp8(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
                                                 opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
-                                                out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream)
-
-    @decode_paged_fp8.register_fake
-    def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q))
 
     # The sliding-window forms: the schema of the op above each with `int window` after `causal`; the existing ops keep theirs.
     @torch.library.custom_op("fa_mi355::decode_window", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
                                     "int window, bool out_fp32) -> Tensor")
     def decode_window(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
-                                      scale=scale, out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
-
-    @decode_window.register_fake
-    def _(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window)
 
     @torch.library.custom_op("fa_mi355::decode_paged_window", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
                                     "bool causal, int window, bool out_fp32) -> Tensor")
     def decode_paged_window(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            opt(cache_seqlens), causal=causal, scale=scale,
-                                            out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
-
-    @decode_paged_window.register_fake
-    def _(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                            stream=stream(q), window=window)
 
     @torch.library.custom_op("fa_mi355::decode_fp8_window", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
                                     "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
     def decode_fp8_window(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          opt(cache_seqlens), causal=causal, scale=scale,
-                                          out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
-
-    @decode_fp8_window.register_fake
-    def _(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                          stream=stream(q), window=window)
 
     @torch.library.custom_op("fa_mi355::decode_paged_fp8_window", mutates_args=(), device_types="cuda",
                              schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
                                     "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
     def decode_paged_fp8_window(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        stream = torch.cuda.current_stream(q.device)
         return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
                                                 opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
-                                                out_dtype=torch.float32 if out_fp32 else q.dtype, stream=stream, window=window)
+                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window)
 
-    @decode_paged_fp8_window.register_fake
-    def _(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        return q.new_empty(q.shape, dtype=torch.float32 if out_fp32 else q.dtype)
+    for op in (decode, decode_paged, decode_fp8, decode_paged_fp8, decode_window, decode_paged_window, decode_fp8_window,
+               decode_paged_fp8_window):
+        op.register_fake(decode_fake)
 
     # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by
     # .contiguous() would take the writes, so a cache that is not contiguous is refused by the front end.
@@ -162,8 +133,8 @@ def register() -> None:
                              schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cache_seqlens, "
                                     "Tensor(c!)? seqlens_out) -> ()")
     def append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
-        stream = torch.cuda.current_stream(k_new.device)
-        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out, stream=stream)
+        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out,
+                              stream=stream(k_new))
 
     @append.register_fake
     def _(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
@@ -173,9 +144,8 @@ def register() -> None:
                              schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
                                     "Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
     def append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
-        stream = torch.cuda.current_stream(k_new.device)
         ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                    opt(cache_seqlens), seqlens_out, stream=stream)
+                                    opt(cache_seqlens), seqlens_out, stream=stream(k_new))
 
     @append_paged.register_fake
     def _(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
@@ -185,9 +155,8 @@ def register() -> None:
                              schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
                                     "Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
     def append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
-        stream = torch.cuda.current_stream(k_new.device)
         ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
-                                  opt(cache_seqlens), seqlens_out, stream=stream)
+                                  opt(cache_seqlens), seqlens_out, stream=stream(k_new))
 
     @append_fp8.register_fake
     def _(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
@@ -197,9 +166,8 @@ def register() -> None:
                              schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
                                     "Tensor? k_scale, Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
     def append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
-        stream = torch.cuda.current_stream(k_new.device)
         ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream)
+                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream(k_new))
 
     @append_paged_fp8.register_fake
     def _(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
