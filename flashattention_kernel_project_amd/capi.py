@@ -39,6 +39,10 @@ SYMBOLS = (
     "fa_kvcache_append_paged",
     "fa_kvcache_append_fp8",
     "fa_kvcache_append_paged_fp8",
+    "fa_kvcache_append_rope",
+    "fa_kvcache_append_paged_rope",
+    "fa_kvcache_append_fp8_rope",
+    "fa_kvcache_append_paged_fp8_rope",
     "fa_forward_kvcache_window_workspace_bytes",
     "fa_forward_kvcache_paged_window_workspace_bytes",
     "fa_forward_kvcache_window",
@@ -131,14 +135,15 @@ def lib() -> C.CDLL:
         L.fa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
         L.fa_forward_kvcache_paged_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_window_workspace_bytes.restype = C.c_size_t
-        L.fa_kvcache_append.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
-        L.fa_kvcache_append.restype = C.c_int
-        L.fa_kvcache_append_paged.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
-        L.fa_kvcache_append_paged.restype = C.c_int
-        L.fa_kvcache_append_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
-        L.fa_kvcache_append_fp8.restype = C.c_int
-        L.fa_kvcache_append_paged_fp8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp]
-        L.fa_kvcache_append_paged_fp8.restype = C.c_int
+        # the eight append entries, from one rule: Knew, Vnew, K, V, seqlens_k, seqlens_out [, table] [, k_scale, v_scale]
+        # [, Q, Qout, rope_cos, rope_sin], B, Hkv, Nnew, Ncap (paged: num_pages, page_size, max_pages), d
+        # [, G, rot_dim, max_pos, interleaved], dtype, stream
+        for paged in (False, True):
+            for fp8 in (False, True):
+                for rope in (False, True):
+                    fn = getattr(L, "fa_kvcache_append" + "_paged" * paged + "_fp8" * fp8 + "_rope" * rope)
+                    fn.argtypes = [vp] * (6 + paged + 2 * fp8 + 4 * rope) + [i] * (6 if paged else 4) + [i] + [i] * (4 * rope) + [i, vp]
+                    fn.restype = C.c_int
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

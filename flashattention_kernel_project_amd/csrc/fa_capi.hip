@@ -215,6 +215,48 @@ FA_EXPORT int fa_kvcache_append_paged_fp8(const void* Knew, const void* Vnew, vo
                                              0, d, in_dtype, num_pages, page_size, max_pages, true, true, static_cast<hipStream_t>(stream)});
 }
 
+// The _rope forms: the base entry's list with (Q, Qout, rope_cos, rope_sin) before B and (G, rot_dim, max_pos, interleaved) after d;
+// the rope fields are the tail of KvAppendArgs.
+FA_EXPORT int fa_kvcache_append_rope(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
+                           const void* Q, void* Qout, const float* rope_cos, const float* rope_sin, int B, int Hkv, int Nnew, int Ncap,
+                           int d, int G, int rot_dim, int max_pos, int interleaved, int dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kcache, Vcache, seqlens_k, seqlens_out, nullptr, nullptr, nullptr, B, Hkv, Nnew,
+                                             Ncap, d, dtype, 0, 0, 0, false, false, static_cast<hipStream_t>(stream), Q, Qout, rope_cos,
+                                             rope_sin, G, rot_dim, max_pos, interleaved, true});
+}
+
+FA_EXPORT int fa_kvcache_append_paged_rope(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* seqlens_k,
+                                 int* seqlens_out, const int* block_table, const void* Q, void* Qout, const float* rope_cos,
+                                 const float* rope_sin, int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages, int d,
+                                 int G, int rot_dim, int max_pos, int interleaved, int dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kpool, Vpool, seqlens_k, seqlens_out, block_table, nullptr, nullptr, B, Hkv, Nnew,
+                                             0, d, dtype, num_pages, page_size, max_pages, true, false, static_cast<hipStream_t>(stream),
+                                             Q, Qout, rope_cos, rope_sin, G, rot_dim, max_pos, interleaved, true});
+}
+
+FA_EXPORT int fa_kvcache_append_fp8_rope(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k,
+                               int* seqlens_out, const float* k_scale, const float* v_scale, const void* Q, void* Qout,
+                               const float* rope_cos, const float* rope_sin, int B, int Hkv, int Nnew, int Ncap, int d, int G,
+                               int rot_dim, int max_pos, int interleaved, int in_dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kcache, Vcache, seqlens_k, seqlens_out, nullptr, k_scale, v_scale, B, Hkv, Nnew,
+                                             Ncap, d, in_dtype, 0, 0, 0, false, true, static_cast<hipStream_t>(stream), Q, Qout, rope_cos,
+                                             rope_sin, G, rot_dim, max_pos, interleaved, true});
+}
+
+FA_EXPORT int fa_kvcache_append_paged_fp8_rope(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* seqlens_k,
+                                     int* seqlens_out, const int* block_table, const float* k_scale, const float* v_scale,
+                                     const void* Q, void* Qout, const float* rope_cos, const float* rope_sin, int B, int Hkv, int Nnew,
+                                     int num_pages, int page_size, int max_pages, int d, int G, int rot_dim, int max_pos,
+                                     int interleaved, int in_dtype, void* stream)
+{
+    return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kpool, Vpool, seqlens_k, seqlens_out, block_table, k_scale, v_scale, B, Hkv, Nnew,
+                                             0, d, in_dtype, num_pages, page_size, max_pages, true, true, static_cast<hipStream_t>(stream),
+                                             Q, Qout, rope_cos, rope_sin, G, rot_dim, max_pos, interleaved, true});
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

@@ -72,7 +72,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_kvcache_append.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -145,8 +145,20 @@ struct KvAppendArgs {
     int num_pages, page_size, max_pages;
     bool paged, fp8;
     hipStream_t stream;
+    // the _rope entries (fa_kvcache_append_rope.hip), at the end so that the plain entries' initialisers leave them zero: K is rotated
+    // at its position on the way into the cache, and Q [B, Hkv*G, Nnew, D] of `dtype` into Qout (the same buffer, a disjoint one, or
+    // both null: K only).  rope_cos, rope_sin: device fp32 [max_pos, rot_dim / 2].
+    const void* Q;
+    void* Qout;
+    const float *rope_cos, *rope_sin;
+    int G, rot_dim, max_pos, interleaved;
+    bool rope;
 };
 hipError_t kvcache_append_dispatch(const KvAppendArgs& a);
+// what kvcache_append_dispatch hands a checked `rope` call to; Ncap: the checked capacity, lg_page: log2 of the page size (paged only)
+hipError_t kvcache_append_rope(const KvAppendArgs& a, int Ncap, int lg_page);
+// the lengths kernel behind either append kernel (fa_kvcache_append.hip); nothing is launched without a seqlens_out
+hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

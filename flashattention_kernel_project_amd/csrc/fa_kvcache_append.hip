@@ -1,56 +1,11 @@
 // fa_kvcache_append.hip -- the write half of a decode step (fa_kvcache_append, _paged, _fp8, _paged_fp8): Nnew new K and V rows per
 // sequence are copied behind the sequence's current length, into a contiguous cache or through a block table into a page pool, as
 // they are or quantised to e4m3fn with the head's scale.  Lengths, table and scales are read on the device, so a captured
-// append -> decode pair follows a growing cache.  DESIGN.md section 7.5 has the reasoning.  The kernels live in this translation
-// unit alone: no other unit's code moves.
-#include "fa_dispatch.hpp"
-
-// Non-temporal hint on the source loads (read once): 1 = on the 16-bit copy only, where it measured 7-13 % faster at Nnew = 4096;
-// 2 = on the fp8 kernels too (measured: no gain); 0 = nowhere.  Never on the stores: at Nnew = 1 the decode that follows reads them.
-#ifndef FA_APPEND_NT_LOAD
-#define FA_APPEND_NT_LOAD 1
-#endif
+// append -> decode pair follows a growing cache.  DESIGN.md section 7.5 has the reasoning.  The device helpers are shared with the
+// _rope entries' unit through fa_kvcache_append.hpp.
+#include "fa_kvcache_append.hpp"
 
 namespace fa {
-
-namespace {
-
-struct AppendDev {
-    const int* seqlens;     // [B] on the device, or nullptr: every sequence is EMPTY (a prefill into a fresh cache)
-    const int* table;       // [B][max_pages] page numbers on the device (paged only)
-    const float* k_scale;   // [Hkv] on the device, or nullptr (1.0) (fp8 only)
-    const float* v_scale;
-    unsigned chunks;        // 16-byte source chunks per tensor: B * Hkv * Nnew * D / 8
-    int Hkv, Nnew, Ncap;
-    int max_pages, num_pages, lg_page;
-};
-
-constexpr int kAppendThreads = 256;
-constexpr float kE4m3Max = 448.0f;
-
-// A quotient x / s made ready for the conversion: a NaN is taken out (its code is set by nan_code below) and the rest is clamped to
-// +-448, so what reaches the conversion is finite and in range and neither the clamp's nor the conversion's treatment of NaN and
-// overflow matters.
-__device__ __forceinline__ float quant_operand(float q)
-{
-    q = (q != q) ? 0.0f : q;
-    q = q > kE4m3Max ? kE4m3Max : q;
-    return q < -kE4m3Max ? -kE4m3Max : q;
-}
-// 0x7F in byte `i` where the quotient is a NaN (OR-ed over the converted code: 0x7F or 0xFF, both NaN in e4m3fn)
-__device__ __forceinline__ unsigned nan_code(float q, int i) { return (q != q) ? (0x7Fu << (8 * i)) : 0u; }
-// four elements of T (two packed words) -> four e4m3fn codes of x / s, round to nearest even (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950)
-template <typename T> __device__ __forceinline__ unsigned quant4(unsigned w0, unsigned w1, float s)
-{
-    // exact widening, then IEEE division (v_div_scale / v_div_fmas / v_div_fixup; fp32 denormals kept), never a reciprocal
-    const float q0 = T::lo(w0) / s, q1 = T::hi(w0) / s, q2 = T::lo(w1) / s, q3 = T::hi(w1) / s;
-    int w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(quant_operand(q0), quant_operand(q1), w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(quant_operand(q2), quant_operand(q3), w, true);
-    return (unsigned)w | nan_code(q0, 0) | nan_code(q1, 1) | nan_code(q2, 2) | nan_code(q3, 3);
-}
-
-}  // namespace
 
 // One thread moves one 16-byte chunk (8 elements) of a source row; blockIdx.y: 0 = K, 1 = V.  The source tensors are contiguous
 // [B, Hkv, Nnew, D], so thread g of a tensor reads bytes [16 g, 16 g + 16): the loads of a wave are 1 KiB in a row.  Length, page
@@ -114,17 +69,23 @@ fa_kvcache_append_lens_kernel(const int* in, int* out, int B, int Nnew, int Ncap
     out[i] = n < Ncap ? (int)n : Ncap;
 }
 
+// the launch of the kernel above, for both append units; Ncap: the checked capacity
+hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap)
+{
+    if (!a.seqlens_out) return hipSuccess;
+    FA_LAUNCH(fa_kvcache_append_lens_kernel, dim3(((unsigned)a.B + kAppendThreads - 1) / kAppendThreads), dim3(kAppendThreads), 0,
+              a.stream, a.seqlens, a.seqlens_out, a.B, a.Nnew, Ncap);
+    return launch_status();
+}
+
 template <typename T, int D, bool kPaged, bool kFp8>
 static hipError_t launch_append(const KvAppendArgs& a, const AppendDev& dev)
 {
     const unsigned blocks = (dev.chunks + kAppendThreads - 1) / kAppendThreads;   // from (B, Hkv, Nnew, D) alone
     FA_LAUNCH((fa_kvcache_append_kernel<T, D, kPaged, kFp8>), dim3(blocks, 2), dim3(kAppendThreads), 0, a.stream,
               static_cast<const uint16_t*>(a.Knew), static_cast<const uint16_t*>(a.Vnew), a.K, a.V, dev);
-    hipError_t e = launch_status();
-    if (e != hipSuccess || !a.seqlens_out) return e;
-    FA_LAUNCH(fa_kvcache_append_lens_kernel, dim3(((unsigned)a.B + kAppendThreads - 1) / kAppendThreads), dim3(kAppendThreads), 0,
-              a.stream, a.seqlens, a.seqlens_out, a.B, a.Nnew, dev.Ncap);
-    return launch_status();
+    const hipError_t e = launch_status();
+    return e != hipSuccess ? e : kvcache_append_lens(a, dev.Ncap);
 }
 
 template <bool kPaged, bool kFp8>
@@ -157,6 +118,7 @@ hipError_t kvcache_append_dispatch(const KvAppendArgs& a)
         const uintptr_t bytes = (uintptr_t)a.B * sizeof(int);
         if (in < out + bytes && out < in + bytes) return hipErrorInvalidValue;
     }
+    if (a.rope) return kvcache_append_rope(a, Ncap, lg_page);   // its own checks, then its own kernels (fa_kvcache_append_rope.hip)
     const AppendDev dev = {a.seqlens, a.table, a.k_scale, a.v_scale, (unsigned)chunks, a.Hkv, a.Nnew, Ncap, a.max_pages, a.num_pages, lg_page};
     if (a.paged) return a.fp8 ? append_types<true, true>(a, dev) : append_types<true, false>(a, dev);
     return a.fp8 ? append_types<false, true>(a, dev) : append_types<false, false>(a, dev);

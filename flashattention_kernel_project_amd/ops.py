@@ -327,9 +327,10 @@ def quantize_kv_fp8(x, scale=None):
     return x8, scale.contiguous()
 
 
-def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, what):
+def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, what, rope=(None, None, None, None, False)):
     """What the four append front ends share once the cache is known to be 4-D: shapes and dtypes of the new rows against the cache
-    ([*, Hkv, rows, d]), the two length tensors.  -> (B, Hkv, Nnew, d, dtype id, source pointers, cache pointers, len_ptr, out_ptr)"""
+    ([*, Hkv, rows, d]), the rotary arguments (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), the two length tensors.
+    -> (B, Hkv, Nnew, d, dtype id, source pointers, cache pointers, len_ptr, out_ptr, rotary groups or None)"""
     import torch
     if k_new.dim() != 4 or v_new.shape != k_new.shape or k_new.shape[1] != k_dst.shape[1] or k_new.shape[3] != k_dst.shape[3]:
         raise ValueError(f"k_new, v_new must be [B,Hkv,Nnew,d] with the Hkv and d of {what}")
@@ -346,6 +347,7 @@ def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, wh
             raise ValueError(f"{what} must have the dtype of k_new ({k_new.dtype}; got {k_dst.dtype}, {v_dst.dtype}); an fp8 cache "
                              "goes through fa_kvcache_append_fp8 / fa_kvcache_append_paged_fp8")
         cache_dts = dts
+    rot = _rope_shapes(k_new, *rope)
     len_ptrs = []
     for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
         if t is None:
@@ -356,7 +358,58 @@ def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, wh
         len_ptrs.append(_dev_ptr(t, name, (torch.int32,)))
     src = (_dev_ptr(k_new, "k_new", dts), _dev_ptr(v_new, "v_new", dts))
     dst = (_dev_ptr(k_dst, "k cache", cache_dts), _dev_ptr(v_dst, "v cache", cache_dts))
-    return B, Hkv, Nnew, d, capi.F16 if k_new.dtype == torch.float16 else capi.BF16, src, dst, len_ptrs[0], len_ptrs[1]
+    if rot is not None:
+        q, q_out, cos, sin, ints = rot
+        ptrs = (None, None) if q is None else (_dev_ptr(q, "q", dts), _dev_ptr(q_out, "q_out", dts))
+        rot = (ptrs + (_dev_ptr(cos, "rotary_cos", (torch.float32,)), _dev_ptr(sin, "rotary_sin", (torch.float32,))), ints,
+               (q, q_out, cos, sin))
+    return B, Hkv, Nnew, d, capi.F16 if k_new.dtype == torch.float16 else capi.BF16, src, dst, len_ptrs[0], len_ptrs[1], rot
+
+
+def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
+    """The rotary keywords of the append front ends against k_new [B,Hkv,Nnew,d], by shape and dtype alone (nothing here needs a
+    device).  -> None without rotary_cos, else (q, q_out or q, cos, sin, (G, rot_dim, max_pos, interleaved))"""
+    import torch
+    if cos is None:
+        if q is not None or q_out is not None or sin is not None:
+            raise ValueError("q, q_out and rotary_sin are arguments of the rotary append: they need rotary_cos")
+        return None
+    B, Hkv, Nnew, d = k_new.shape
+    for name, t in (("rotary_cos", cos), ("rotary_sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 device tensor of shape [max_pos, rot_dim/2]")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if sin.shape != cos.shape:
+        raise ValueError(f"rotary_cos and rotary_sin must have one shape (got {tuple(cos.shape)}, {tuple(sin.shape)})")
+    max_pos, rot_dim = cos.shape[0], 2 * cos.shape[1]
+    if max_pos < 1 or rot_dim % 16 != 0 or not 16 <= rot_dim <= d:
+        raise ValueError(f"rotary_cos must be [max_pos >= 1, rot_dim/2] with rot_dim a multiple of 16 in [16, d = {d}] (got "
+                         f"{tuple(cos.shape)})")
+    G = 1
+    if q is None:
+        if q_out is not None:
+            raise ValueError("q_out needs q")
+    else:
+        if not isinstance(q, torch.Tensor) or q.dim() != 4 or q.shape[0] != B or q.shape[2] != Nnew or q.shape[3] != d \
+                or q.shape[1] % Hkv != 0 or q.shape[1] == 0 or q.dtype != k_new.dtype:
+            raise ValueError(f"q must be [B,Hq,Nnew,d] = [{B},Hq,{Nnew},{d}] with Hq a multiple of Hkv = {Hkv}, of k_new's dtype")
+        G = q.shape[1] // Hkv
+        if q_out is None:
+            q_out = q   # in place
+        elif not isinstance(q_out, torch.Tensor) or q_out.shape != q.shape or q_out.dtype != q.dtype:
+            raise ValueError("q_out must have q's shape and dtype")
+    return q, q_out, cos, sin, (G, rot_dim, max_pos, 1 if interleaved else 0)
+
+
+def _append_call(base, tensors, head, geometry, d, dt, rot, stream):
+    """The C call of an append front end: `base` + "_rope" with the rotary groups inserted, pointers before B and integers after d."""
+    import torch
+    name = base + ("_rope" if rot else "")
+    ptrs, ints, more = rot if rot else ((), (), ())
+    with torch.cuda.device(_one_device(*tensors, *more)):
+        code = getattr(capi.lib(), name)(*head, *ptrs, *geometry, d, *ints, dt, _stream_ptr(stream))
+    capi.check(name, code)
 
 
 def _scale_ptrs(k_scale, v_scale, Hkv):
@@ -379,7 +432,8 @@ def _table_ptr(block_table, B):
     return _dev_ptr(block_table, "block_table", (torch.int32,))
 
 
-def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlens_out=None, stream=None) -> None:
+def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlens_out=None, stream=None, *, q=None, q_out=None,
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
     """Write k_new/v_new [B,Hkv,Nnew,d] behind each sequence's length into k_cache/v_cache [B,Hkv,Ncap,d] (fa_kvcache_append): fp16 or
     bf16 device tensors of ONE dtype, d in {64,128}.  Token t of sequence b goes to row L_b + t, L_b = cache_seqlens[b] clamped to
     [0, Ncap]; a token at or past Ncap is dropped; nothing else in the cache changes.  The caches are mutated, None is returned.
@@ -388,73 +442,82 @@ def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlen
     seqlens_out: int32 contiguous device tensor [B] that receives min(L_b + Nnew, Ncap), or None (the caller updates the lengths).  It
     may be cache_seqlens itself (in place) or a tensor that does not overlap it.
     Lengths are read on the device only: append(seqlens_out=lens) followed by fa_forward_kvcache(lens), captured once into a graph,
-    serves every step of a growing cache."""
-    import torch
+    serves every step of a growing cache.
+    rotary_cos, rotary_sin: float32 contiguous device tensors [max_pos, rot_dim/2] (rot_dim a multiple of 16 in [16, d]), or None.  With
+    them the call is fa_kvcache_append_rope: K is rotated at its position p = L_b + t (table row min(p, max_pos - 1)) on its way into
+    the cache, elements [rot_dim, d) pass through, V is written as without them.  rotary_interleaved: False pairs (x[i], x[i+rot_dim/2])
+    (NeoX / HF), True pairs (x[2i], x[2i+1]) (GPT-J).  The arithmetic is stepwise fp32 without fused multiply-add (include/fa_mi355.h).
+    q: [B,Hq,Nnew,d] of k_new's dtype, Hq a multiple of Hkv, or None: rotated by the same positions in the same launch, into q_out
+    (same shape and dtype, not overlapping q) or, with q_out=None, in place.  Without rotary_cos, q and q_out must be None."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, False,
-                                                                   "k_cache, v_cache")
-    with torch.cuda.device(_one_device(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)):
-        code = capi.lib().fa_kvcache_append(*src, *dst, len_ptr, out_ptr, B, Hkv, Nnew, k_cache.shape[2], d, dt, _stream_ptr(stream))
-    capi.check("fa_kvcache_append", code)
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
+        k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, False, "k_cache, v_cache",
+        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+    _append_call("fa_kvcache_append", (k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out), (*src, *dst, len_ptr, out_ptr),
+                 (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream)
 
 
-def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens=None, seqlens_out=None, stream=None) -> None:
+def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens=None, seqlens_out=None, stream=None, *, q=None,
+                            q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
     """fa_kvcache_append into a paged cache (fa_kvcache_append_paged): k_pool/v_pool [num_pages,Hkv,page_size,d] of k_new's dtype,
     block_table int32 [B, max_pages] as in fa_forward_kvcache_paged; position p is row p % page_size of page
     block_table[b, p // page_size], the capacity is max_pages * page_size.  A table entry outside [0, num_pages) drops the tokens of
     that page; entries of pages that receive no token are not read.  The pages a sequence appends into must be its own: a page shared
-    between sequences may only be written by the caller's copy-on-write (not checked)."""
-    import torch
+    between sequences may only be written by the caller's copy-on-write (not checked).
+    q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_paged_rope); the q row of a
+    dropped token is still rotated."""
     if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
     tbl_ptr = _table_ptr(block_table, k_new.shape[0])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, False,
-                                                                   "k_pool, v_pool")
-    with torch.cuda.device(_one_device(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)):
-        code = capi.lib().fa_kvcache_append_paged(*src, *dst, len_ptr, out_ptr, tbl_ptr, B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2],
-                                                  block_table.shape[1], d, dt, _stream_ptr(stream))
-    capi.check("fa_kvcache_append_paged", code)
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
+        k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, False, "k_pool, v_pool",
+        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+    _append_call("fa_kvcache_append_paged", (k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out),
+                 (*src, *dst, len_ptr, out_ptr, tbl_ptr), (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt,
+                 rot, stream)
 
 
 def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, seqlens_out=None,
-                          stream=None) -> None:
+                          stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
     """fa_kvcache_append into an fp8 cache (fa_kvcache_append_fp8): k_new/v_new fp16 or bf16, k_cache/v_cache [B,Hkv,Ncap,d]
     torch.float8_e4m3fn (fnuz and e5m2 are refused).  The stored code is quantize_kv_fp8(x, scale) bit for bit: x / scale[h] in fp32,
     clamped to +-448, rounded to nearest even; +-inf becomes +-448, NaN a NaN code.
-    k_scale, v_scale: float32 contiguous device tensors [Hkv], finite and > 0, or None (1.0); read on the device only."""
-    import torch
+    k_scale, v_scale: float32 contiguous device tensors [Hkv], finite and > 0, or None (1.0); read on the device only.
+    q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_fp8_rope).  The fp32 rotated K is
+    quantised directly, without a 16-bit rounding in between; q stays 16 bit."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
+    import torch
     if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
         raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_cache.dtype}, {v_cache.dtype})")
     ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, True,
-                                                                   "k_cache, v_cache")
-    with torch.cuda.device(_one_device(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out)):
-        code = capi.lib().fa_kvcache_append_fp8(*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr, B, Hkv, Nnew, k_cache.shape[2], d, dt,
-                                                _stream_ptr(stream))
-    capi.check("fa_kvcache_append_fp8", code)
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
+        k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, True, "k_cache, v_cache",
+        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+    _append_call("fa_kvcache_append_fp8", (k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out),
+                 (*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr), (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream)
 
 
 def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
-                                seqlens_out=None, stream=None) -> None:
+                                seqlens_out=None, stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None,
+                                rotary_interleaved=False) -> None:
     """fa_kvcache_append_paged into fp8 pools (fa_kvcache_append_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
-    torch.float8_e4m3fn, block_table as in fa_kvcache_append_paged, scales and codes as in fa_kvcache_append_fp8."""
-    import torch
+    torch.float8_e4m3fn, block_table as in fa_kvcache_append_paged, scales and codes as in fa_kvcache_append_fp8; the rotary keywords
+    as there (fa_kvcache_append_paged_fp8_rope)."""
     if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
+    import torch
     if k_pool.dtype != torch.float8_e4m3fn or v_pool.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
         raise ValueError(f"k_pool, v_pool: {_FP8_CACHE} (got {k_pool.dtype}, {v_pool.dtype})")
     tbl_ptr = _table_ptr(block_table, k_new.shape[0])
     ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr = _append_args(k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, True,
-                                                                   "k_pool, v_pool")
-    with torch.cuda.device(_one_device(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out)):
-        code = capi.lib().fa_kvcache_append_paged_fp8(*src, *dst, len_ptr, out_ptr, tbl_ptr, ks_ptr, vs_ptr, B, Hkv, Nnew,
-                                                      k_pool.shape[0], k_pool.shape[2], block_table.shape[1], d, dt,
-                                                      _stream_ptr(stream))
-    capi.check("fa_kvcache_append_paged_fp8", code)
+    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
+        k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, True, "k_pool, v_pool",
+        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+    _append_call("fa_kvcache_append_paged_fp8", (k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out),
+                 (*src, *dst, len_ptr, out_ptr, tbl_ptr, ks_ptr, vs_ptr),
+                 (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt, rot, stream)
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

@@ -21,6 +21,14 @@ eager fallback.  Registered on first use:
     torch.ops.fa_mi355.append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)
     torch.ops.fa_mi355.append_fp8(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out)
     torch.ops.fa_mi355.append_paged_fp8(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out)
+    # the same four with rotary embedding: (q, rotary_cos, rotary_sin, interleaved) follow the base op's list; q (or None) is rotated in place
+    torch.ops.fa_mi355.append_rope(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_paged_rope(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
+                                         interleaved)
+    torch.ops.fa_mi355.append_fp8_rope(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos,
+                                       rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_paged_fp8_rope(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
+                                             q, rotary_cos, rotary_sin, interleaved)
 """
 from __future__ import annotations
 
@@ -30,8 +38,8 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window forms and
-    the four .append ops (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window forms, the
+    four .append ops and their four _rope forms (idempotent)."""
     global _registered
     if _registered:
         return
@@ -172,6 +180,51 @@ def register() -> None:
     @append_paged_fp8.register_fake
     def _(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
         return None
+
+    # The rotary forms: the schema of the op above each plus (q, rotary_cos, rotary_sin, interleaved).  q is rotated in place, so it is
+    # passed as it is, like the caches, and is among the mutated arguments.
+    ROPE = "Tensor(d!)? q, Tensor rotary_cos, Tensor rotary_sin, bool interleaved) -> ()"
+
+    def rope_kw(q, rotary_cos, rotary_sin, interleaved):
+        return dict(q=q, rotary_cos=rotary_cos.contiguous(), rotary_sin=rotary_sin.contiguous(), rotary_interleaved=interleaved)
+
+    @torch.library.custom_op("fa_mi355::append_rope", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cache_seqlens, "
+                                    "Tensor(c!)? seqlens_out, " + ROPE)
+    def append_rope(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin, interleaved):
+        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out,
+                              stream=stream(k_new), **rope_kw(q, rotary_cos, rotary_sin, interleaved))
+
+    @torch.library.custom_op("fa_mi355::append_paged_rope", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
+    def append_paged_rope(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
+                          interleaved):
+        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                    opt(cache_seqlens), seqlens_out, stream=stream(k_new),
+                                    **rope_kw(q, rotary_cos, rotary_sin, interleaved))
+
+    @torch.library.custom_op("fa_mi355::append_fp8_rope", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
+                                    "Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
+    def append_fp8_rope(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
+                        interleaved):
+        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
+                                  opt(cache_seqlens), seqlens_out, stream=stream(k_new),
+                                  **rope_kw(q, rotary_cos, rotary_sin, interleaved))
+
+    @torch.library.custom_op("fa_mi355::append_paged_fp8_rope", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"),
+                             device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    "Tensor? k_scale, Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
+    def append_paged_fp8_rope(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos,
+                              rotary_sin, interleaved):
+        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream(k_new),
+                                        **rope_kw(q, rotary_cos, rotary_sin, interleaved))
+
+    for op in (append_rope, append_paged_rope, append_fp8_rope, append_paged_fp8_rope):
+        op.register_fake(lambda *args: None)
 
     _registered = True
 

@@ -309,8 +309,9 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  * not in {64,128}; a dtype not in {0,1}; an Ncap beyond the decode entries' bound; the paged entries' conditions on page_size,
  * num_pages, max_pages and their product; a source of 2^31 or more 16-byte chunks per tensor (B * Hkv * Nnew * d / 8: the kernel's
  * index type and the grid); the partial overlap of seqlens_out and seqlens_k.
- * Rotary embedding, token-major pages, per-token or per-block scales, e5m2, fp8 sources and sliding windows are not part of these
- * entries.  NOT reference entry points. */
+ * Token-major pages, per-token or per-block scales, e5m2, fp8 sources and sliding windows are not part of these entries; nor, on the
+ * _rope forms below, are explicit position ids or a per-sequence position offset, 16-bit tables, rotary on the prefill entries
+ * (fa_forward*) and a rot_dim that is not a multiple of 16.  NOT reference entry points. */
 int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache,
                       const int* seqlens_k,  /* device, B int32, may be NULL (= 0 for all: every sequence empty) */
                       int* seqlens_out,      /* device, B int32, may be NULL or == seqlens_k */
@@ -330,6 +331,61 @@ int fa_kvcache_append_paged_fp8(const void* Knew, const void* Vnew, void* Kpool,
                                 const float* k_scale, const float* v_scale,
                                 int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages,
                                 int d, int in_dtype, void* stream);
+
+/* KV-cache append with rotary position embedding: fa_kvcache_append* with the new token's K rotated at its key position on its way
+ * into the cache and the step's Q rows rotated by the same positions, in the same launch.  Each entry is its base entry's list with
+ * (Q, Qout, rope_cos, rope_sin) inserted before B and (G, rot_dim, max_pos, interleaved) after d.  V, seqlens_out, placement, the
+ * refusals and "nothing on the host reads device data" are the base entry's, unchanged; the grid depends on (B, Hkv, G, Nnew, d) and
+ * on whether there is a Q only, and there is no workspace, so append_rope -> decode is captured once like append -> decode.
+ *   rope_cos, rope_sin  device fp32 [max_pos, rot_dim/2], contiguous, the caller's: NTK, YaRN or Llama-3 scaling and any magnitude
+ *                   factor are whatever the caller put into the table.  Read on the device only.
+ *   rot_dim         a multiple of 16 with 16 <= rot_dim <= d.  Elements [rot_dim, d) of a row pass through untouched: on 16-bit caches
+ *                   and on Q every bit is kept, as the copy keeps it; on fp8 caches they are quantised as the plain fp8 entry does.
+ *   interleaved     0, the half-split (NeoX / HF) convention: pair i is (x[i], x[i + rot_dim/2]); 1, the GPT-J convention: pair i is
+ *                   (x[2i], x[2i+1]).  In both, pair i uses c = rope_cos[r][i], s = rope_sin[r][i].
+ *   position        token t of sequence b has p = L_b + t (L_b clamped as above, NULL lengths: 0): the position the append places it
+ *                   at and the position the decode's causal mask gives query row t after the append.  The table row is
+ *                   r = min(p, max_pos - 1): clamp, never fault.  A dropped token (p >= Ncap, or a bad table entry on the paged
+ *                   forms) is still not written; its Q row is still rotated, with row r.
+ *   Q, Qout         [B, Hkv*G, Nnew, d] contiguous, of the sources' 16-bit dtype (on the fp8 entries too).  Row (b, hq, t) is rotated
+ *                   at p = L_b + t and written to the same place of Qout.  Qout == Q rotates in place; Q == NULL && Qout == NULL
+ *                   rotates K only; the two buffers must be identical or disjoint, the rule of seqlens_out.
+ * Arithmetic, pinned so that the bytes are a contract: the sources are widened exactly to fp32; y1 = fp32(x1*c) - fp32(x2*s) and
+ * y2 = fp32(x2*c) + fp32(x1*s), each product and each sum rounded to fp32 on its own -- NO fused multiply-add.  For Q and 16-bit
+ * caches one rounding to nearest even into the 16-bit type follows.  For fp8 caches the fp32 y goes into the recipe above,
+ * e4m3fn_RNE(clamp(y / scale[hkv], -448, +448)), with no 16-bit rounding in between (one rounding fewer than rotating first and
+ * appending afterwards).  This is what element-wise fp32 operators of torch and numpy compute, so a CPU reference reproduces every
+ * byte.  A NaN result is a NaN; its payload is not promised.
+ * hipErrorInvalidValue, before the device is touched, besides the base entry's: a NULL rope_cos or rope_sin; a rot_dim outside the rule;
+ * max_pos <= 0; G <= 0; interleaved not in {0,1}; B * Hkv * G beyond int; 2^31 or more 16-byte chunks in Q; exactly one of Q, Qout
+ * NULL; a partial overlap of Q and Qout.  NOT reference entry points. */
+int fa_kvcache_append_rope(const void* Knew, const void* Vnew, void* Kcache, void* Vcache,
+                           const int* seqlens_k, int* seqlens_out,
+                           const void* Q, void* Qout,   /* device, [B,Hkv*G,Nnew,d]; both NULL, identical or disjoint */
+                           const float* rope_cos, const float* rope_sin,   /* device, [max_pos,rot_dim/2] fp32 */
+                           int B, int Hkv, int Nnew, int Ncap, int d,
+                           int G, int rot_dim, int max_pos, int interleaved,
+                           int dtype, void* stream);
+int fa_kvcache_append_paged_rope(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                                 const int* seqlens_k, int* seqlens_out, const int* block_table,
+                                 const void* Q, void* Qout, const float* rope_cos, const float* rope_sin,
+                                 int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages, int d,
+                                 int G, int rot_dim, int max_pos, int interleaved,
+                                 int dtype, void* stream);
+int fa_kvcache_append_fp8_rope(const void* Knew, const void* Vnew, void* Kcache, void* Vcache,
+                               const int* seqlens_k, int* seqlens_out,
+                               const float* k_scale, const float* v_scale,
+                               const void* Q, void* Qout, const float* rope_cos, const float* rope_sin,
+                               int B, int Hkv, int Nnew, int Ncap, int d,
+                               int G, int rot_dim, int max_pos, int interleaved,
+                               int in_dtype, void* stream);
+int fa_kvcache_append_paged_fp8_rope(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                                     const int* seqlens_k, int* seqlens_out, const int* block_table,
+                                     const float* k_scale, const float* v_scale,
+                                     const void* Q, void* Qout, const float* rope_cos, const float* rope_sin,
+                                     int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages, int d,
+                                     int G, int rot_dim, int max_pos, int interleaved,
+                                     int in_dtype, void* stream);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through

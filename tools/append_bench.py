@@ -3,6 +3,7 @@
 
     python tools/append_bench.py                       # B8 Hkv16 d128, Ncap 32768 at length 8192, Nnew 1 and 4096, the four layouts
     python tools/append_bench.py --alt-lib PATH        # a second build of the library as a third contender (e.g. -DFA_APPEND_NT_LOAD=0 or 2)
+    python tools/append_bench.py --rope --G 1 4        # the rotary append (rotary_cos=, q=) against torch rotation ops + the plain entry
 
 Method of tools/decode_bench.py --fp8: the contenders of one (layout, Nnew) run in one process, interleaved round by round, 5 rounds of
 50 launches each between two device events; a line gives the median of the rounds and their range.  The torch baselines:
@@ -13,6 +14,13 @@ The baselines know the length on the host; the library entry reads it on the dev
 compared byte for byte.  For Nnew >= 1024 a line also gives GB/s over the bytes read plus the bytes written.
 The verdict of a pair: the entry is "not slower" when its median is at most the baseline's median plus the baseline's round-to-round
 spread (max - min of its rounds).
+--rope adds Q [B, Hkv*G, Nnew, d] and fp32 tables (rot_dim = d, half-split) and times three contenders per (layout, G, Nnew):
+  rope         fa_kvcache_append*(..., q=, rotary_cos=, rotary_sin=): K and Q rotated inside the append's launch
+  torch+entry  what a caller does without it: positions from the device-side lengths, a gather of the table rows, the rotation of q and
+               k_new with element-wise fp32 torch ops and a rounding to 16 bit, then the plain fa_kvcache_append* entry
+  plain        the plain entry alone on the same shape (no rotation): context for what the extra bytes cost
+Their results are compared first: equal bytes for a 16-bit cache and for Q; for an fp8 cache the composition rounds K to 16 bit before
+the quantisation, so some codes differ and their number is printed.  The verdict is the one above, with torch+entry as the baseline.
 """
 import argparse
 import ctypes
@@ -36,7 +44,12 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--alt-lib", default=None, help="another build of libfa_mi355.so, timed as a third contender")
+    ap.add_argument("--rope", action="store_true", help="time the rotary append against torch rotation ops + the plain entry")
+    ap.add_argument("--G", type=int, nargs="+", default=[1, 4], help="query heads per K/V head (--rope)")
+    ap.add_argument("--max-pos", type=int, default=None, help="rows of the cos / sin tables (--rope; default Ncap)")
     args = ap.parse_args()
+    if args.rope:
+        return rope_main(args)
 
     import torch
     import flashattention_kernel_project_amd as fa
@@ -140,6 +153,117 @@ def main():
             print(f"{layout:10s} Nnew {Nnew:5d}: entry / torch = {med['entry'] / med['torch']:.3f}; torch's rounds spread over "
                   f"{spread * 1e3:.1f} us: {'not slower' if ok else 'SLOWER beyond the spread'}")
             del kn, vn
+        del caches
+        torch.cuda.empty_cache()
+
+
+def timed_rounds(calls, rounds, iters):
+    """{name: fn} -> {name: [ms per launch of each round]}; the contenders alternate inside every round: drift hits all alike"""
+    import torch
+    times = {name: [] for name in calls}
+    for _ in range(rounds):
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / iters)
+    return times
+
+
+def rope_main(args):
+    import torch
+    import flashattention_kernel_project_amd as fa
+
+    assert torch.cuda.is_available(), "a measurement needs the GPU"
+    B, H, d, Ncap, L, ps = args.B, args.H, args.d, args.Ncap, args.L, args.page
+    dev, half = "cuda", args.d // 2
+    max_pos = args.max_pos or Ncap
+    layouts = [l for l in args.layouts if l in ("contiguous", "paged_fp8")] if args.layouts == ["contiguous", "paged", "fp8", "paged_fp8"] \
+        else args.layouts
+    print(f"{fa.version()}; rope: B{B} Hkv{H} d{d} rot_dim {d} half-split, Ncap{Ncap} length {L}, pages of {ps}, table of {max_pos} rows; "
+          f"median of {args.rounds} rounds of {args.iters} launches")
+    g = torch.Generator(device="cpu").manual_seed(0)
+    max_pages = Ncap // ps
+    table = torch.randperm(B * max_pages, generator=g).to(dev).view(B, max_pages).to(torch.int32).contiguous()
+    lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+    k_scale = torch.rand(H, device=dev) * 0.02 + 0.005
+    v_scale = torch.rand(H, device=dev) * 0.02 + 0.005
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * (10000.0 ** (-torch.arange(0, d, 2, dtype=torch.float64) / d))[None]
+    cos, sin = ang.cos().float().to(dev).contiguous(), ang.sin().float().to(dev).contiguous()
+
+    for layout in layouts:
+        paged, fp8 = "paged" in layout, "fp8" in layout
+        cdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+        shape = (B * max_pages, H, ps, d) if paged else (B, H, Ncap, d)
+        fn = getattr(fa, "fa_kvcache_append" + ("_paged" if paged else "") + ("_fp8" if fp8 else ""))
+        extra = ((table,) if paged else ()) + ((k_scale, v_scale) if fp8 else ())
+        caches = {name: [torch.zeros(shape, dtype=torch.uint8 if fp8 else cdt, device=dev).view(cdt) for _ in range(2)]
+                  for name in ("rope", "torch+entry", "plain")}
+        for G in args.G:
+            for Nnew in args.Nnew:
+                kn = torch.randn(B, H, Nnew, d, device=dev).to(torch.bfloat16)
+                vn = torch.randn(B, H, Nnew, d, device=dev).to(torch.bfloat16)
+                q0 = torch.randn(B, H * G, Nnew, d, device=dev).to(torch.bfloat16)
+                qs = {name: q0.clone() for name in ("rope", "torch+entry")}
+                q_out = torch.empty_like(q0)
+                steps = torch.arange(Nnew, device=dev)
+
+                def rotate(x, c, s):
+                    xf = x.float()
+                    x1, x2 = xf[..., :half], xf[..., half:]
+                    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
+
+                def fused():
+                    fn(kn, vn, *caches["rope"], *extra, cache_seqlens=lens, q=qs["rope"], q_out=q_out, rotary_cos=cos, rotary_sin=sin)
+
+                def composition():
+                    pos = (lens.long()[:, None] + steps[None]).clamp(max=max_pos - 1)   # from the device-side lengths
+                    c, s = cos[pos][:, None], sin[pos][:, None]                         # [B, 1, Nnew, half]
+                    composition.q = rotate(qs["torch+entry"], c, s)
+                    fn(rotate(kn, c, s), vn, *caches["torch+entry"], *extra, cache_seqlens=lens)
+
+                def plain():
+                    fn(kn, vn, *caches["plain"], *extra, cache_seqlens=lens)
+
+                calls = {"rope": fused, "torch+entry": composition, "plain": plain}
+                for pair in caches.values():   # rows of an earlier (G, Nnew) would count in the comparison below
+                    for c in pair:
+                        c.view(torch.uint8).zero_()
+                for f in calls.values():
+                    for _ in range(3):
+                        f()
+                torch.cuda.synchronize()
+                tag = f"{layout:10s} G{G} Nnew {Nnew:5d}"
+                if not torch.equal(q_out.view(torch.int16), composition.q.view(torch.int16)):
+                    print(f"{tag}: Q DIFFERS from torch's rotation")
+                raw = {name: [c.view(torch.uint8) for c in caches[name]] for name in calls}
+                diff = int((raw["rope"][0] != raw["torch+entry"][0]).sum())
+                if not torch.equal(raw["rope"][1], raw["torch+entry"][1]) or (diff and not fp8):
+                    print(f"{tag}: the caches DIFFER from the composition's")
+                assert int(torch.count_nonzero(raw["rope"][0])) > 0
+                if diff:
+                    print(f"{tag}: {diff} of {B * H * Nnew * d} K codes differ from the composition's (its 16-bit rounding before the "
+                          "quantisation)")
+                times = timed_rounds(calls, args.rounds, args.iters)
+                med = {name: statistics.median(t) for name, t in times.items()}
+                kv = 2.0 * B * H * Nnew * d * (2 + (1 if fp8 else 2))            # K and V: 16-bit rows read, rows written
+                moved = {"rope": kv + 4.0 * B * H * G * Nnew * d, "plain": kv}   # Q: read and written, 16 bit
+                for name in calls:
+                    rate = f", {moved[name] / med[name] / 1e6:.0f} GB/s over {moved[name] / 1e6:.0f} MB read + written" \
+                        if Nnew >= 1024 and name in moved else ""
+                    print(f"{tag} [{name:11s}]: median {med[name] * 1e3:8.1f} us "
+                          f"(rounds {min(times[name]) * 1e3:.1f}-{max(times[name]) * 1e3:.1f}){rate}")
+                spread = max(times["torch+entry"]) - min(times["torch+entry"])
+                ok = med["rope"] <= med["torch+entry"] + spread
+                print(f"{tag}: rope / torch+entry = {med['rope'] / med['torch+entry']:.3f}, rope / plain = "
+                      f"{med['rope'] / med['plain']:.3f}; torch+entry's rounds spread over {spread * 1e3:.1f} us: "
+                      f"{'not slower' if ok else 'SLOWER beyond the spread'}")
+                del kn, vn, q0, qs, q_out
+                composition.q = None
+                torch.cuda.empty_cache()
         del caches
         torch.cuda.empty_cache()
 
