@@ -49,9 +49,29 @@ SYMBOLS = (
     "fa_forward_kvcache_paged_window",
     "fa_forward_kvcache_fp8_window",
     "fa_forward_kvcache_paged_fp8_window",
+    "fa_kvcache_decode_workspace_bytes",
+    "fa_kvcache_decode",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
+
+
+KV_16BIT, KV_FP8_E4M3 = 0, 1
+
+
+class KvDecodeDesc(C.Structure):
+    """fa_kvdecode_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p),
+                ("seqlens_k", C.c_void_p), ("block_table", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+                ("sinks", C.c_void_p), ("kv_dtype", C.c_int), ("B", C.c_int), ("Hkv", C.c_int), ("G", C.c_int), ("Nq", C.c_int),
+                ("d", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int), ("max_pages", C.c_int),
+                ("scale", C.c_float), ("causal", C.c_int), ("window", C.c_int), ("softcap", C.c_float), ("in_dtype", C.c_int),
+                ("out_dtype", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvDecodeDesc)
 
 
 class FaError(RuntimeError):
@@ -135,6 +155,11 @@ def lib() -> C.CDLL:
         L.fa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
         L.fa_forward_kvcache_paged_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
         L.fa_forward_kvcache_paged_window_workspace_bytes.restype = C.c_size_t
+        # the descriptor form of the eight, with sinks and softcap
+        L.fa_kvcache_decode.argtypes = [C.POINTER(KvDecodeDesc)]
+        L.fa_kvcache_decode.restype = C.c_int
+        L.fa_kvcache_decode_workspace_bytes.argtypes = [C.POINTER(KvDecodeDesc)]
+        L.fa_kvcache_decode_workspace_bytes.restype = C.c_size_t
         # the eight append entries, from one rule: Knew, Vnew, K, V, seqlens_k, seqlens_out [, table] [, k_scale, v_scale]
         # [, Q, Qout, rope_cos, rope_sin], B, Hkv, Nnew, Ncap (paged: num_pages, page_size, max_pages), d
         # [, G, rot_dim, max_pos, interleaved], dtype, stream

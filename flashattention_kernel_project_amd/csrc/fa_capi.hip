@@ -183,6 +183,37 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpo
                                        .k_scale = k_scale, .v_scale = v_scale, .window = window, .paged = true, .fp8 = true});
 }
 
+// The descriptor form of the eight entries above, plus sinks and softcap.  What the descriptor alone can get wrong is judged here;
+// everything else by kvdecode_dispatch, as for the flat entries.
+static bool kvdecode_desc_ok(const fa_kvdecode_desc* desc)
+{
+    if (!desc || desc->size != sizeof(fa_kvdecode_desc)) return false;
+    if (desc->kv_dtype != FA_KV_16BIT && desc->kv_dtype != FA_KV_FP8_E4M3) return false;
+    return desc->kv_dtype == FA_KV_FP8_E4M3 || (!desc->k_scale && !desc->v_scale);   // a 16-bit cache has no scales
+}
+
+FA_EXPORT size_t fa_kvcache_decode_workspace_bytes(const fa_kvdecode_desc* desc)
+{
+    if (!kvdecode_desc_ok(desc)) return 0;
+    if (desc->block_table)
+        return fa::kvpaged_window_workspace_bytes(desc->B, desc->Hkv, desc->G, desc->Nq, desc->max_pages, desc->page_size, desc->d, desc->window);
+    return fa::kvwindow_workspace_bytes(desc->B, desc->Hkv, desc->G, desc->Nq, desc->Ncap, desc->d, desc->window);
+}
+
+FA_EXPORT int fa_kvcache_decode(const fa_kvdecode_desc* desc)
+{
+    if (!kvdecode_desc_ok(desc)) return (int)hipErrorInvalidValue;
+    const bool paged = desc->block_table != nullptr;
+    return (int)fa::kvdecode_dispatch({.p = {.c = {desc->Q, desc->K, desc->V, desc->O, desc->lse, desc->seqlens_k, desc->B, desc->Hkv, desc->G,
+                                                   desc->Nq, paged ? 0 : desc->Ncap, desc->d, desc->scale, desc->causal, desc->in_dtype,
+                                                   desc->out_dtype, desc->workspace, desc->workspace_bytes,
+                                                   static_cast<hipStream_t>(desc->stream)},
+                                             .table = desc->block_table, .num_pages = paged ? desc->num_pages : 0,
+                                             .page_size = paged ? desc->page_size : 0, .max_pages = paged ? desc->max_pages : 0},
+                                       .k_scale = desc->k_scale, .v_scale = desc->v_scale, .window = desc->window, .paged = paged,
+                                       .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap});
+}
+
 FA_EXPORT int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
                       int B, int Hkv, int Nnew, int Ncap, int d, int dtype, void* stream)
 {

@@ -72,7 +72,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -103,23 +103,33 @@ struct KvPagedArgs {
 // in_dtype on the way into LDS, and k_scale, v_scale are device pointers to Hkv fp32 each, or null (1.0).  window >= 1: row i
 // sees the last `window` keys up to its own position, and the split count, with it grid and workspace, follows from
 // window_span_cap() in place of the capacity; 0: no window; < 0: rejected.
+// fa_kvcache_decode alone sets the last two, at the end so that the eight flat entries' initialisers leave them zero: sinks, a device
+// pointer to Hkv * G fp32 logits (null: none), and softcap (0: off; negative, NaN or inf: rejected).  A call with either runs the
+// LogitArgs kernels of fa_fwd_kvlogits*.hip, which exist around the windowed packs only: window 0 runs there as window = Ncap.
 struct KvDecodeArgs {
     KvPagedArgs p;
     const float *k_scale, *v_scale;
     int window;
     bool paged, fp8;
+    const float* sinks;
+    float softcap;
 };
 hipError_t kvdecode_dispatch(const KvDecodeArgs& a);
 // What kvdecode_dispatch hands checked arguments to: one function per translation unit that owns decode kernels -- fa_fwd_kvcache,
-// _kvpaged, _kvfp8 (contiguous and paged), _kvwindow and _kvwindow_fp8 (window >= 1; contiguous and paged).  lg_page: log2 of the
-// page size (paged only).
+// _kvpaged, _kvfp8 (contiguous and paged), _kvwindow and _kvwindow_fp8 (window >= 1; contiguous and paged), _kvlogits and
+// _kvlogits_fp8 (sinks or softcap set, window >= 1; contiguous and paged).  lg_page: log2 of the page size (paged only).
 hipError_t kvcache_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvpaged_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvfp8_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvwindow_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvwindow_fp8_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvlogits_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvlogits_fp8_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
                            hipStream_t stream);   // the merge kernel behind a split, for all of them
+// ... and the merge that also joins the heads' sinks (not null), once per row -- fa_fwd_kvlogits.hip; Nq: rows per query head
+hipError_t kvlogits_combine(const void* ws, void* O, float* lse, const float* sinks, int BH, int rows, int Hkv, int Nq, int D, int S,
+                            int in_dtype, int out_dtype, hipStream_t stream);
 // The argument checks alone: the append runs them too, so it accepts exactly the caches the decode accepts.  kvpaged_check fills
 // in the capacity and returns page_log2(page_size): log2 of a page size the kernels take, else -1.
 hipError_t kvcache_check(const KvCacheArgs& a);

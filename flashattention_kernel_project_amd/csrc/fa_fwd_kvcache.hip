@@ -1,7 +1,7 @@
 // fa_fwd_kvcache.hip -- decode against a pre-allocated KV cache (fa_forward_kvcache): the split-KV stream of fa_fwd_split.hip with
 // the key count of each sequence read on the device, a causal mask aligned to the end of the cache and a log-sum-exp output.
 // DESIGN.md section 7 has the reasoning; the kernels are the CacheArgs instantiations of fa_fwd_split_kernel.hpp, launched through
-// the host path of fa_fwd_kvdecode.hpp like those of the four units beside this one.  Also here, once for all eight decode entries:
+// the host path of fa_fwd_kvdecode.hpp like those of the six units beside this one.  Also here, once for all decode entries:
 // the argument checks, the entry kvdecode_dispatch and the merge kernel.
 #include "fa_fwd_kvdecode.hpp"
 
@@ -32,9 +32,15 @@ hipError_t kvcache_check(const KvCacheArgs& a)
 }
 
 // The translation unit that owns the kernels of the pack the flags name.  Window 0 is the un-windowed entry itself: it launches
-// the un-windowed kernels.
+// the un-windowed kernels.  With sinks or a soft-cap the LogitArgs kernels run, which wrap the windowed packs only: window 0 goes
+// there as window = Ncap, which include/fa_mi355.h guarantees to be the un-windowed result bit for bit, on the same split count.
 static hipError_t kvdecode_handover(const KvDecodeArgs& d, int lg_page)
 {
+    if (d.sinks || d.softcap != 0.0f) {
+        KvDecodeArgs w = d;
+        if (w.window == 0) w.window = w.p.c.Ncap;
+        return w.fp8 ? kvlogits_fp8_decode(w, lg_page) : kvlogits_decode(w, lg_page);
+    }
     if (d.window == 0) return d.fp8 ? kvfp8_decode(d, lg_page) : d.paged ? kvpaged_decode(d, lg_page) : kvcache_decode(d, lg_page);
     return d.fp8 ? kvwindow_fp8_decode(d, lg_page) : kvwindow_decode(d, lg_page);
 }
@@ -43,11 +49,12 @@ static hipError_t kvdecode_handover(const KvDecodeArgs& d, int lg_page)
 hipError_t kvdecode_dispatch(const KvDecodeArgs& d)
 {
     if (d.window < 0) return hipErrorInvalidValue;
+    if (!(d.softcap >= 0.0f) || __builtin_isinf(d.softcap)) return hipErrorInvalidValue;   // negative, NaN or inf
     if (!d.paged) {
         const hipError_t bad = kvcache_check(d.p.c);
         return bad != hipSuccess ? bad : kvdecode_handover(d, 0);
     }
-    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8};   // q.p: d.p with the capacity, from the check
+    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8, d.sinks, d.softcap};   // q.p: d.p with the capacity, from the check
     int lg_page;
     const hipError_t bad = kvpaged_check(d.p, q.p, lg_page);
     return bad != hipSuccess ? bad : kvdecode_handover(q, lg_page);

@@ -5,7 +5,8 @@
 // a PagedArgs in that pack, and everything it adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt); the fp8
 // entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
 // selects (profiles/kvcache_fp8.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
-// behind `if constexpr (kWindow)` (profiles/kvcache_window.txt).
+// behind `if constexpr (kWindow)` (profiles/kvcache_window.txt); the soft-cap / sink entry wraps the four windowed packs in a
+// LogitArgs, and what it adds sits behind `if constexpr (kLogits)` (profiles/kvcache_logits.txt).
 // The sets are instantiated in separate translation units so that none perturbs another's register allocation; the host path of the
 // KV-cache sets (pack builder, launcher, type switch) is fa_fwd_kvdecode.hpp.  Design notes: head of fa_fwd_split.hip, DESIGN.md 7.1.
 #pragma once
@@ -76,6 +77,43 @@ __device__ __forceinline__ NoWindow window_part() { return {}; }
 __device__ __forceinline__ NoWindow window_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const WindowArgs<Base>& window_part(const WindowArgs<Base>& w) { return w; }
 
+// What the soft-cap / attention-sink instantiations take (fa_kvcache_decode): a WindowArgs pack plus the two options on the logits.
+// The cap comes in log2 units, as the scores do once they are multiplied by the folded factor c; the sinks are one natural-log
+// logit per QUERY head and never enter the tile loop (they join in the one-pass epilogue and in the merge, SinkLse below).
+template <typename Base> struct LogitArgs : Base {
+    const float* sinks;   // [Hkv * G] on the device, or nullptr: none
+    float cap2;           // softcap * log2(e); 0: no cap (the tile loop then runs the wrapped pack's arithmetic)
+    float cap_rk;         // 2 / softcap: 2^(x * cap_rk) = e^(2 x / cap2) for a score x in log2 units
+};
+template <typename A> struct IsLogitArgs : std::false_type {};
+template <typename Base> struct IsLogitArgs<LogitArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<LogitArgs<Base>> : IsFp8Args<Base> {};
+template <typename Base> struct IsWindowArgs<LogitArgs<Base>> : IsWindowArgs<Base> {};
+struct NoLogits {};
+__device__ __forceinline__ NoLogits logit_part() { return {}; }
+__device__ __forceinline__ NoLogits logit_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const LogitArgs<Base>& logit_part(const LogitArgs<Base>& l) { return l; }
+
+// A wave-uniform float into a scalar register.  gfx950 has no scalar float arithmetic, so a value computed from kernel arguments
+// lives in a VGPR unless it is read back; the d = 64 kernels sit at their 128 VGPRs and spill for every such value they keep.
+__device__ __forceinline__ float to_sgpr(float x)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+
+// One sink joins a row's running (m, l), both in log2 units: the new reference is max(m, a2), `l` comes back as the sum under it
+// and the return value is the factor the row's accumulators take.  m = -inf (no key) and a2 = -inf (no sink for the head) take the
+// weight 0, not 2^(-inf + inf); with a2 = -inf the factor is 2^0 = 1 and (m, l) keep their bits.
+__device__ __forceinline__ float sink_join(float a2, float& m, float& l)
+{
+    const float m_new = fmaxf(m, a2);
+    const float w_keys = m == -INFINITY ? 0.0f : fast_exp2(m - m_new);
+    const float w_sink = a2 == -INFINITY ? 0.0f : fast_exp2(a2 - m_new);
+    l = l * w_keys + w_sink;
+    m = m_new;
+    return w_keys;
+}
+
 // Two e4m3fn bytes of w (kHi: bytes 2 and 3) as one packed pair of T.  Every e4m3fn value is a normal number of fp16 and of bf16,
 // so the conversion is exact, and the NaN codes 0x7F / 0xFF stay NaN.  One v_cvt_scalef32_pk_{f16,bf16}_fp8 with a scale of 1.
 // FA_FP8_VIA_F32 takes the way through fp32 (v_cvt_pk_f32_fp8, then the pack of the type), which is exact for the same reason.
@@ -122,6 +160,13 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // not read) but reach LDS as zeros: masking the score is not enough for V, because a weight of 0 times a NaN is a NaN in the PV
 // MFMA.  Scores of keys below a row's lo become -inf in the tiles that start below the last row's lower limit; a tile that is
 // fully masked for a row is what m_ref = -inf already handles.
+// kLogits (kWindow with a LogitArgs around the pack): two options on the logits.  Soft-cap: before the masks every score x = s c (log2
+// units) becomes cap2 tanh(x / cap2), with tanh(y) = 1 - 2 / (1 + e^(2y)) on v_exp_f32 and v_rcp_f32, which saturates at both ends
+// without a branch; the scores are then final, so the factor the vote and the weights multiply them by is 1 (`cs`).  The masks come
+// AFTER the cap: tanh(-inf) = -1 would turn a masked key into the finite logit -cap2.  cap2 == 0 skips all of it by a wave-uniform
+// branch, and the tile loop is the windowed kernel's.  Sinks: one extra key per row with the head's logit and a zero V row, joined to
+// (m, l) by sink_join() in the one-pass epilogue here and in the merge kernel -- NEVER by a partial kernel: a row's sink counts once,
+// however many splits its keys were dealt to.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -142,6 +187,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto fa8 = fp8_part(cache...);
     constexpr bool kWindow = (IsWindowArgs<Cache>::value || ...);
     [[maybe_unused]] const auto wa = window_part(cache...);
+    constexpr bool kLogits = (IsLogitArgs<Cache>::value || ...);
+    [[maybe_unused]] const auto la = logit_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -218,6 +265,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     const float c = kFp8 ? fmaxf(fabsf(scale_log2e * k_scale), 1.17549435e-38f)
                          : kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
     const unsigned q_flip = scale_log2e < 0.0f ? 0x80008000u : 0u;
+    // what a score is multiplied by on its way into the vote and the exponent: c, or 1 once the soft-cap has made the scores final
+    // kLogits: that factor and the cap's two constants in scalar registers (to_sgpr), so that the kernel keeps no more VGPRs through
+    // the tile loop than the windowed one: c itself is then dead after this point
+    [[maybe_unused]] float cs = c, cap_k1 = 0.0f, cap_n2 = 0.0f;
+    if constexpr (kLogits) {
+        cs = to_sgpr(la.cap2 > 0.0f ? 1.0f : c);
+        cap_k1 = to_sgpr(c * la.cap_rk);
+        cap_n2 = to_sgpr(-2.0f * la.cap2);
+    }
     u32x4 qf[G::kKSteps];
 #pragma unroll
     for (int s = 0; s < G::kKSteps; ++s) {
@@ -360,6 +416,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 const u32x4 kf = lds_read16(kbuf, kb * 32u * G::kRowBytes + k_rd_row + (((2u * ks + h) ^ k_rd_swz) << 4));
                 s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
             }
+        if constexpr (kLogits) {
+            if (la.cap2 > 0.0f) {   // wave-uniform; before the masks, so a masked key stays at -inf
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i)
+                        s[kb][i] = __builtin_fmaf(cap_n2, __builtin_amdgcn_rcpf(1.0f + fast_exp2(s[kb][i] * cap_k1)), la.cap2);
+            }
+        }
         if constexpr (kWindow) {
             // keys outside [lo, hi) -> -inf: hi is `lim` above, lo the row's lower limit; one unsigned compare per score
             if (kv0 + kBlockN > lim_lo || kv0 < lo_hi) {
@@ -387,7 +452,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         float tmax = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 32; e += 2) tmax = max3(tmax, s[e >> 4][e & 15], s[(e + 1) >> 4][(e + 1) & 15]);
-        tmax *= c;
+        tmax *= kLogits ? cs : c;
         // kCache: a tile can be fully masked for a row, in any position of the rotated order, so m_ref starts at -inf and stays
         // there until the row meets a key.  The vote is written without a difference (-inf - -inf), and a row whose m_ref is
         // -inf takes alpha = 0 instead of 2^(-inf + inf); a first live key always wins the vote (tmax > -inf).
@@ -411,8 +476,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             const int kb = q4 >> 1, b8 = (q4 & 1) * 8;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                const float p0 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w], c, neg_m));
-                const float p1 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w + 1], c, neg_m));
+                const float p0 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w], kLogits ? cs : c, neg_m));
+                const float p1 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w + 1], kLogits ? cs : c, neg_m));
                 pk[q4][w] = T::pack2(p0, p1);
                 if (w & 1) ls1 = T::sum2(pk[q4][w], ls1);   // sums of the ROUNDED weights (fa_common.hpp)
                 else ls0 = T::sum2(pk[q4][w], ls0);
@@ -439,7 +504,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         __syncthreads();
     }
 
-    const float l = l_part + swap_halves(l_part);
+    float l = l_part + swap_halves(l_part);
     if constexpr (kPartial) {
         // workspace row (bh, sp, q_row): D floats of O^T (unnormalised), then m, then l
         const size_t rows = (size_t)Nq;
@@ -466,7 +531,21 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if (h == 0)
             buf_store8(rw, q_row * rs + (unsigned)D * 4u, u32x2{__float_as_uint(m_ref), __float_as_uint(l)});
     } else {
+        // kLogits: the sink joins here, once per row; rows past Nq read the sink of the head's last row and store nothing
+        [[maybe_unused]] float w_keys = 1.0f;
+        if constexpr (kLogits) {
+            if (la.sinks) {
+                // the two divisors go through an empty asm so that these divisions share nothing with `bh % ca.Hkv` and `q_row %
+                // ca.Nq1` of the prologue: shared, two reciprocals stay in VGPRs across the tile loop, which the d = 64 kernels
+                // spill (profiles/kvcache_logits.txt); recomputed here they cost a few instructions once per workgroup
+                unsigned nq1 = (unsigned)ca.Nq1, nhkv = (unsigned)ca.Hkv;
+                asm volatile("" : "+s"(nq1), "+s"(nhkv));
+                const unsigned hq = (bh % nhkv) * ((unsigned)Nq / nq1) + min(q_row, (unsigned)Nq - 1u) / nq1;
+                w_keys = sink_join(la.sinks[hq] * kLog2e, m_ref, l);
+            }
+        }
         float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        if constexpr (kLogits) inv *= w_keys;
         if constexpr (kFp8) inv *= v_scale;
         if constexpr (kCache) {
             if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
@@ -498,12 +577,27 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 // of one lane walking them (a serial walk costs ~0.25 us per partial: 64 us at S = 128).
 // kCache: a partial with m = -inf is neutral (weight 0, not 2^(-inf + inf)), a row of neutral partials gives O = 0, and the
 // trailing float* argument (may be nullptr) receives ln(sum of exponentials) = (M + log2 L) ln 2.
+// SinkLse in the place of the float*: the row's head has an attention sink, which joins (M, L) here, once per row.
+struct SinkLse {
+    float* lse;           // as the float* of the kCache instantiations
+    const float* sinks;   // [Hkv * G] on the device, not null
+    int Hkv, Nq1;         // K/V heads per batch entry and rows per query head: row `row` of K/V head bh belongs to query head
+};                        // (bh % Hkv) * (Nq / Nq1) + row / Nq1
+__device__ __forceinline__ float* lse_part() { return nullptr; }
+__device__ __forceinline__ float* lse_part(float* p) { return p; }
+__device__ __forceinline__ float* lse_part(const SinkLse& s) { return s.lse; }
+struct NoSink {};
+__device__ __forceinline__ NoSink sink_part() { return {}; }
+__device__ __forceinline__ NoSink sink_part(float*) { return {}; }
+__device__ __forceinline__ const SinkLse& sink_part(const SinkLse& s) { return s; }
 template <typename T, bool kOutF32, bool kCache = false, typename... Lse>
 __global__ __launch_bounds__(64)
 void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og, int BH, int Nq, int D, int S, Lse... lse_arg)
 {
     static_assert(sizeof...(Lse) == (kCache ? 1 : 0), "the KV-cache instantiations take the lse pointer, the plain ones nothing");
-    [[maybe_unused]] float* const lse = {lse_arg...};
+    [[maybe_unused]] float* const lse = lse_part(lse_arg...);
+    constexpr bool kSink = (std::is_same_v<Lse, SinkLse> || ...);
+    [[maybe_unused]] const auto sk = sink_part(lse_arg...);
     const int cols4 = D / 4;             // 16 or 32
     const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
     const unsigned lane = threadIdx.x;
@@ -518,6 +612,12 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     for (int s = (int)lane; s < S; s += 64) M = fmaxf(M, base[(size_t)s * stride_s + D]);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+    // kSink: the sink takes part in the reference maximum (a sink far above the keys' logits must not overflow the sum)
+    [[maybe_unused]] float a2 = -INFINITY;
+    if constexpr (kSink) {
+        a2 = sk.sinks[(bh % sk.Hkv) * (Nq / sk.Nq1) + row / sk.Nq1] * kLog2e;
+        M = fmaxf(M, a2);
+    }
     float L = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 4
     for (int s = sl; s < S; s += nsl) {
@@ -538,6 +638,7 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
         for (int i = 0; i < 4; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
     }
     if (sl != 0) return;
+    if constexpr (kSink) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
     const float inv = (kCache && L == 0.0f) ? 0.0f : 1.0f / L;
     if constexpr (kCache) {
         if (lse && lane == 0) lse[rowi] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;

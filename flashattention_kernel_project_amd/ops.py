@@ -149,11 +149,12 @@ def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
 
 
 def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream, window, paged=False,
-            block_table=None, scales=None):
+            block_table=None, scales=None, sinks=None, softcap=0.0):
     """The four decode front ends: k, v (named k_name, v_name in messages) are a cache [B,Hkv,Ncap,d] or, with `paged`, a pool
     [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one.  The C entry
     is fa_forward_kvcache + _paged + _fp8 + _window, and each suffix inserts its arguments: the table after the lengths, the two
-    scales after that, the geometry of the pool in the place of Ncap, the window after causal."""
+    scales after that, the geometry of the pool in the place of Ncap, the window after causal.  With `sinks` (a tensor) or a
+    `softcap` other than 0 the call goes through the descriptor entry fa_kvcache_decode instead, which alone has the two."""
     import torch
     fp8 = scales is not None
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[3] != k.shape[3] or (not paged and q.shape[0] != k.shape[0]):
@@ -191,6 +192,8 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
     window = _window(window)
+    softcap = _softcap(softcap)
+    sink_ptr = _sinks_ptr(sinks, Hq, q.device)
     # in the place of Ncap a pool has (num_pages, page_size, max_pages)
     cap = (k.shape[0], k.shape[2], block_table.shape[1]) if paged else (k.shape[2],)
     if workspace is None:
@@ -202,6 +205,21 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if sinks is not None or softcap != 0.0:
+        # args: [table] [k_scale, v_scale]; the descriptor names every field, so no suffix rule is needed
+        desc = capi.KvDecodeDesc(
+            Q=ptrs[0], K=ptrs[1], V=ptrs[2], O=out.data_ptr(), lse=lse.data_ptr() if return_lse else None, seqlens_k=len_ptr,
+            block_table=args[0] if paged else None, k_scale=args[-2] if fp8 else None, v_scale=args[-1] if fp8 else None,
+            sinks=sink_ptr, kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, G=G, Nq=Nq, d=d,
+            Ncap=0 if paged else cap[0], num_pages=cap[0] if paged else 0, page_size=cap[1] if paged else 0,
+            max_pages=cap[2] if paged else 0, scale=float(scale), causal=1 if causal else 0, window=window, softcap=softcap,
+            in_dtype=capi.F16 if q.dtype == torch.float16 else capi.BF16,
+            out_dtype=capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, workspace=ws_ptr, workspace_bytes=ws_len,
+            stream=_stream_ptr(stream))
+        with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace, sinks)):
+            code = capi.lib().fa_kvcache_decode(desc)
+        capi.check("fa_kvcache_decode", code)
+        return (out, lse) if return_lse else out
     fn_name = "fa_forward_kvcache" + ("_paged" if paged else "") + ("_fp8" if fp8 else "") + ("_window" if window else "")
     args = ptrs + (out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr) + args + (B, Hkv, G, Nq) + cap \
         + (d, float(scale), 1 if causal else 0) + ((window,) if window else ()) \
@@ -214,7 +232,8 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
 
 
 def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = False, scale: float | None = None,
-                       out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0):
+                       out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0, sinks=None,
+                       softcap: float = 0.0):
     """Decode against a pre-allocated cache (fa_forward_kvcache): q [B,Hq,Nq,d], k_cache/v_cache [B,Hkv,Ncap,d]
     fp16/bf16 device tensors, d in {64,128}, Hq a multiple of Hkv (the group's K/V is streamed once, as in
     fa_forward_splitkv).
@@ -226,9 +245,15 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     workspace: optional uint8 device tensor of at least kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d).
     window: 0 (no window), or W >= 1: row i sees only the keys [max(0, L_b - Nq + 1 + i - W), its upper limit) -- with causal its own
     position and the W - 1 before it (fa_forward_kvcache_window).  Keys below row 0's lower limit are never used.  The window is a host
-    integer (baked into a captured call); the workspace is then sized by kvcache_window_workspace_bytes."""
+    integer (baked into a captured call); the workspace is then sized by kvcache_window_workspace_bytes.
+    softcap: 0 (off), or a finite float > 0: every logit s becomes softcap * tanh(s / softcap) before the masks and the softmax
+    (flash-attn's softcap; baked into a captured call).
+    sinks: None, or a float32 contiguous device tensor of Hq values: head h gets one extra key with the natural-log logit sinks[h]
+    (not scaled, not capped) and a zero V row, which every row sees under any mask or window -- lse includes it; -inf: no sink for
+    that head.  Read on the device only.  When merging over key ranges, pass sinks to exactly one range.
+    With either the call is fa_kvcache_decode; workspace sizes are unchanged."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window)
+                   window, sinks=sinks, softcap=softcap)
 
 
 def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int) -> int:
@@ -240,6 +265,28 @@ def kvcache_window_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int,
     return int(capi.lib().fa_forward_kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window))
 
 
+def _softcap(softcap) -> float:
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)) or not (0.0 <= softcap < math.inf):
+        raise ValueError("softcap must be a finite float >= 0 (0: no soft-cap)")
+    return float(softcap)
+
+
+def _sinks_ptr(sinks, Hq: int, device):
+    """None, or the device pointer of a checked sink vector: one fp32 natural-log logit per query head."""
+    if sinks is None:
+        return None
+    import torch
+    if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+        raise ValueError("sinks must be a float32 device tensor")
+    if sinks.numel() != Hq:
+        raise ValueError(f"sinks must hold one value per query head ({Hq}), got {sinks.numel()}")
+    if not sinks.is_contiguous():
+        raise ValueError("sinks must be contiguous")
+    if sinks.device != device:
+        raise ValueError(f"sinks is on {sinks.device}, q on {device}")
+    return _dev_ptr(sinks, "sinks", (torch.float32,))
+
+
 def _window(window) -> int:
     if isinstance(window, bool) or not isinstance(window, int) or window < 0:
         raise ValueError("window must be an int >= 0 (0: no window)")
@@ -247,7 +294,8 @@ def _window(window) -> int:
 
 
 def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None, causal: bool = False, scale: float | None = None,
-                             out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0):
+                             out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0, sinks=None,
+                             softcap: float = 0.0):
     """fa_forward_kvcache against a paged cache (fa_forward_kvcache_paged): q [B,Hq,Nq,d], k_pool/v_pool
     [num_pages,Hkv,page_size,d] fp16/bf16 contiguous device tensors (a contiguous slice of a larger pool, pool[2:6], is a pool),
     d in {64,128}, page_size a power of two >= 16, Hq a multiple of Hkv.
@@ -260,9 +308,10 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
     window: 0 (no window), or W >= 1: row i sees only the keys [max(0, L_b - Nq + 1 + i - W), its upper limit) -- with causal its own
     position and the W - 1 before it (fa_forward_kvcache_paged_window).  Keys below row 0's lower limit are never used.  The window is a host
     integer (baked into a captured call); the workspace is then sized by kvcache_paged_window_workspace_bytes.
-    Under a window a page wholly below row 0's lower limit is not dereferenced and its table entry is not read."""
+    Under a window a page wholly below row 0's lower limit is not dereferenced and its table entry is not read.
+    sinks, softcap: as in fa_forward_kvcache."""
     return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, paged=True, block_table=block_table)
+                   window, paged=True, block_table=block_table, sinks=sinks, softcap=softcap)
 
 
 def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int) -> int:
@@ -280,7 +329,7 @@ _FP8_CACHE = "an fp8 cache must be torch.float8_e4m3fn (OCP e4m3fn, the gfx950 f
 
 def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, causal: bool = False,
                            scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None,
-                           window: int = 0):
+                           window: int = 0, sinks=None, softcap: float = 0.0):
     """fa_forward_kvcache against an fp8 cache (fa_forward_kvcache_fp8): q [B,Hq,Nq,d] fp16/bf16, k_cache/v_cache [B,Hkv,Ncap,d]
     torch.float8_e4m3fn (OCP e4m3fn; fnuz and e5m2 are refused) device tensors, d in {64,128}.  K and V are widened to q's type
     on the way into the kernel, exactly.
@@ -289,20 +338,21 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     like cache_seqlens, so a captured call follows all three when they are rewritten in place.  quantize_kv_fp8() makes a cache
     and its scales from a 16-bit or fp32 tensor.
     Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (then
-    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes) -- is fa_forward_kvcache's."""
+    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes), sinks and softcap (the sinks take neither scale) -- is
+    fa_forward_kvcache's."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, scales=(k_scale, v_scale))
+                   window, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap)
 
 
 def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
                                  causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
-                                 workspace=None, stream=None, window: int = 0):
+                                 workspace=None, stream=None, window: int = 0, sinks=None, softcap: float = 0.0):
     """fa_forward_kvcache_paged against fp8 pools (fa_forward_kvcache_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
     torch.float8_e4m3fn, block_table as in fa_forward_kvcache_paged, k_scale / v_scale and everything else as in
     fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes; with a window (fa_forward_kvcache_paged_fp8_window)
-    kvcache_paged_window_workspace_bytes."""
+    kvcache_paged_window_workspace_bytes.  sinks, softcap: as in fa_forward_kvcache."""
     return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, paged=True, block_table=block_table, scales=(k_scale, v_scale))
+                   window, paged=True, block_table=block_table, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap)
 
 
 FP8_E4M3_MAX = 448.0   # largest finite e4m3fn value

@@ -17,6 +17,13 @@ eager fallback.  Registered on first use:
     o = torch.ops.fa_mi355.decode_fp8_window(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32)
     o = torch.ops.fa_mi355.decode_paged_fp8_window(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal,
                                                    window, out_fp32)
+    # ... and with attention sinks and soft-capped logits: (window, sinks, softcap) follow `causal`; sinks is a float32 [Hq] tensor or None
+    o = torch.ops.fa_mi355.decode_ex(q, k_cache, v_cache, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_ex(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32)
+    o = torch.ops.fa_mi355.decode_fp8_ex(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap,
+                                         out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_fp8_ex(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window,
+                                               sinks, softcap, out_fp32)
     torch.ops.fa_mi355.append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)   # ops.fa_kvcache_append; returns nothing
     torch.ops.fa_mi355.append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)
     torch.ops.fa_mi355.append_fp8(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out)
@@ -38,7 +45,7 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window forms, the
+    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window and four _ex forms, the
     four .append ops and their four _rope forms (idempotent)."""
     global _registered
     if _registered:
@@ -131,8 +138,46 @@ def register() -> None:
                                                 opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
                                                 out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window)
 
+    # The forms with attention sinks and a soft-cap: the schema of the windowed op above each with `Tensor? sinks, float softcap`
+    # after `window`.
+    @torch.library.custom_op("fa_mi355::decode_ex", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
+                                    "int window, Tensor? sinks, float softcap, bool out_fp32) -> Tensor")
+    def decode_ex(q, k_cache, v_cache, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
+        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
+                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window,
+                                      sinks=opt(sinks), softcap=softcap)
+
+    @torch.library.custom_op("fa_mi355::decode_paged_ex", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
+                                    "bool causal, int window, Tensor? sinks, float softcap, bool out_fp32) -> Tensor")
+    def decode_paged_ex(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
+        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                            stream=stream(q), window=window, sinks=opt(sinks), softcap=softcap)
+
+    @torch.library.custom_op("fa_mi355::decode_fp8_ex", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, int window, Tensor? sinks, float softcap, "
+                                    "bool out_fp32) -> Tensor")
+    def decode_fp8_ex(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
+        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
+                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+                                          stream=stream(q), window=window, sinks=opt(sinks), softcap=softcap)
+
+    @torch.library.custom_op("fa_mi355::decode_paged_fp8_ex", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, int window, Tensor? sinks, float softcap, "
+                                    "bool out_fp32) -> Tensor")
+    def decode_paged_fp8_ex(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap,
+                            out_fp32):
+        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
+                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window,
+                                                sinks=opt(sinks), softcap=softcap)
+
     for op in (decode, decode_paged, decode_fp8, decode_paged_fp8, decode_window, decode_paged_window, decode_fp8_window,
-               decode_paged_fp8_window):
+               decode_paged_fp8_window, decode_ex, decode_paged_ex, decode_fp8_ex, decode_paged_fp8_ex):
         op.register_fake(decode_fake)
 
     # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by

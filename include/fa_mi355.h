@@ -241,8 +241,8 @@ int fa_forward_kvcache_paged_fp8(const void* Q, const void* Kpool, const void* V
  * is touched.  With W >= Ncap the result equals the base entry's bit for bit; with Nq = 1 and (L_b - W) % 64 == 0 it equals
  * fa_forward_kvcache on a cache of capacity W + 64 that holds the last W keys.  The paged entries return the bits of the contiguous
  * ones on the same keys, the fp8 entries with all scales 1 those of the 16-bit ones on the widened cache.
- * Not part of these entries: attention sinks, soft-capping of the logits, a ring-buffer (rolling) cache layout, a window on the
- * prefill entries (fa_forward*), a window per sequence or per head.  NOT reference entry points. */
+ * Not part of these entries: a ring-buffer (rolling) cache layout, a window on the prefill entries (fa_forward*), a window per
+ * sequence or per head.  Attention sinks and soft-capping of the logits are fa_kvcache_decode's, below.  NOT reference entry points. */
 size_t fa_forward_kvcache_window_workspace_bytes(int B, int Hkv, int G, int Nq, int Ncap, int d, int window);
 size_t fa_forward_kvcache_paged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pages, int page_size, int d, int window);
 int fa_forward_kvcache_window(const void* Q, const void* Kcache, const void* Vcache, void* O,
@@ -277,6 +277,69 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
                                         int num_pages, int page_size, int max_pages, int d,
                                         float scale, int causal, int window, int in_dtype, int out_dtype,
                                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* KV-cache decode by descriptor: the one-call form of the eight decode entries above, with two options on the logits that the
+ * model families with local-attention layers use next to the window -- soft-capped logits (Gemma-2 style) and one learned attention
+ * sink per query head (gpt-oss style).  Which of the eight forms a call is follows from the descriptor: block_table (NULL: a
+ * contiguous cache of Ncap rows; else pools with num_pages, page_size, max_pages, and Ncap is ignored), kv_dtype (FA_KV_16BIT:
+ * K, V elements of in_dtype, k_scale and v_scale must be NULL; FA_KV_FP8_E4M3: one e4m3fn byte per element) and window (0: none).
+ * Every field means what the argument of that name means in the flat entries.  `size` must equal sizeof(fa_kvdecode_desc).
+ * With sinks == NULL and softcap == 0 the call IS the flat entry the descriptor names: same checks, same kernels, same bits.
+ * Terms, for row i of query head hq = hkv*G + g: s_j = scale * q.k_j is the logit of key j (scale * k_scale[hkv] * q.k8_j on an
+ * fp8 cache), and [lo_i, c_i) are the keys the row sees under the length clamp, the causal flag and the window, as above.
+ * softcap   a host float, baked into a captured call like `window`.  0: off.  > 0 and finite: the logit becomes
+ *           t_j = softcap * tanh(s_j / softcap) (flash-attn's softcap).  Negative, NaN or inf: hipErrorInvalidValue.  The masks apply
+ *           AFTER the cap: a key outside [lo_i, c_i) has weight exactly 0 (tanh(-inf) = -1 never makes a masked key a finite logit).
+ *           scale = 0 keeps its meaning (uniform weights over the visible keys, never NaN), a negative scale negates the logits
+ *           (tanh is odd), a NaN key behaves as in the base entries.  tanh is computed as 1 - 2 / (1 + e^(2y)) on the hardware
+ *           exponential and reciprocal: an absolute error of the order of softcap * 1e-7 on a logit.
+ * sinks     a device pointer to Hkv*G fp32 values, or NULL for none.  Head hq has the sink logit a = sinks[hq], in natural-log units
+ *           and final: not multiplied by scale or k_scale, not soft-capped.  It is one extra key that every row of the head sees,
+ *           with logit a and a zero V row, which no mask or window removes:
+ *             O_i = sum_j exp(t_j) v_j / (exp(a) + sum_j exp(t_j)),   lse_i = ln(exp(a) + sum_j exp(t_j)).
+ *           A row that sees no key gets O = 0 exactly and lse = a.  a = -inf is "no sink for this head": the head returns what it
+ *           returns with sinks == NULL (a row without a key then has lse = -inf; never NaN).  lse is finite and correct for any
+ *           finite a, however far above or below the keys' logits: the sink takes part in the reference maximum.  a = +inf or NaN
+ *           gives a meaningless result, never an out-of-range access.  The sink counts ONCE per row, whatever the split count.
+ *           The vector is read on the device only: a captured call follows a vector that is rewritten in place.  v_scale does not
+ *           touch the sink (its V row is zero).
+ * Merging over key ranges: the sink is part of lse, so a caller who merges results over disjoint key ranges by the rule of
+ * fa_forward_kvcache (O = sum_r O_r exp(lse_r - lse), lse = ln sum_r exp(lse_r)) passes `sinks` to exactly ONE of the ranges.
+ * Unchanged from the base entries: the length clamp; what is and is not read (rows past L_b, rows and pages below the window, bad
+ * table entries reading as zeros); 64-bit page addresses; the fp8 scales; the folding of the G heads of a group (row r of a K/V head
+ * belongs to query head hkv*G + r / Nq); "nothing on the host reads device data"; the split count and the workspace size, which
+ * depend on (B, Hkv, G, Nq, capacity or span_cap, d) exactly as before -- fa_kvcache_decode_workspace_bytes returns what the flat
+ * sizing function of the descriptor's form returns (0 for a descriptor that is NULL, of the wrong size or of an unknown kv_dtype).
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor, a wrong `size`, an unknown kv_dtype, scales on
+ * a 16-bit cache, a bad softcap, and everything the flat entry of the descriptor's form rejects.
+ * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the prefill entries (fa_forward*), a tanh other than
+ * the one above.  NOT a reference entry point. */
+#define FA_KV_16BIT    0   /* K, V elements are of in_dtype */
+#define FA_KV_FP8_E4M3 1   /* K, V elements are OCP e4m3fn bytes */
+typedef struct fa_kvdecode_desc {
+    size_t size;               /* sizeof(fa_kvdecode_desc) */
+    const void *Q, *K, *V;     /* K, V: the cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d] */
+    void* O;
+    float* lse;                /* device, [B,Hkv*G,Nq] fp32, may be NULL */
+    const int* seqlens_k;      /* device, B int32, may be NULL (= Ncap for all) */
+    const int* block_table;    /* device, [B,max_pages] int32; NULL: a contiguous cache */
+    const float* k_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const float* v_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const float* sinks;        /* device, Hkv*G fp32 natural-log logits, may be NULL (none) */
+    int kv_dtype;              /* FA_KV_16BIT or FA_KV_FP8_E4M3 */
+    int B, Hkv, G, Nq, d;
+    int Ncap;                  /* contiguous only */
+    int num_pages, page_size, max_pages;   /* paged only */
+    float scale;
+    int causal, window;
+    float softcap;             /* 0: off */
+    int in_dtype, out_dtype;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} fa_kvdecode_desc;
+size_t fa_kvcache_decode_workspace_bytes(const fa_kvdecode_desc* desc);
+int fa_kvcache_decode(const fa_kvdecode_desc* desc);
 
 /* KV-cache append: the write half of a decode step.  Nnew new K and V rows per sequence are written behind the sequence's current
  * length, by one kernel for K and V, into any cache the decode entries above read.
