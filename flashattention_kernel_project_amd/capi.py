@@ -51,6 +51,7 @@ SYMBOLS = (
     "fa_forward_kvcache_paged_fp8_window",
     "fa_kvcache_decode_workspace_bytes",
     "fa_kvcache_decode",
+    "fa_kvcache_append_ex",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -66,12 +67,28 @@ class KvDecodeDesc(C.Structure):
                 ("sinks", C.c_void_p), ("kv_dtype", C.c_int), ("B", C.c_int), ("Hkv", C.c_int), ("G", C.c_int), ("Nq", C.c_int),
                 ("d", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int), ("max_pages", C.c_int),
                 ("scale", C.c_float), ("causal", C.c_int), ("window", C.c_int), ("softcap", C.c_float), ("in_dtype", C.c_int),
-                ("out_dtype", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+                ("out_dtype", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p),
+                ("seqlens_q", C.c_void_p)]
 
     def __init__(self, **fields):
         super().__init__(**fields)
         if "size" not in fields:
             self.size = C.sizeof(KvDecodeDesc)
+
+
+class KvAppendDesc(C.Structure):
+    """fa_kvappend_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Knew", C.c_void_p), ("Vnew", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p),
+                ("seqlens_k", C.c_void_p), ("seqlens_out", C.c_void_p), ("seqlens_new", C.c_void_p), ("block_table", C.c_void_p),
+                ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("Q", C.c_void_p), ("Qout", C.c_void_p), ("rope_cos", C.c_void_p),
+                ("rope_sin", C.c_void_p), ("kv_dtype", C.c_int), ("B", C.c_int), ("Hkv", C.c_int), ("Nnew", C.c_int), ("d", C.c_int),
+                ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int), ("max_pages", C.c_int), ("G", C.c_int),
+                ("rot_dim", C.c_int), ("max_pos", C.c_int), ("interleaved", C.c_int), ("dtype", C.c_int), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvAppendDesc)
 
 
 class FaError(RuntimeError):
@@ -169,6 +186,9 @@ def lib() -> C.CDLL:
                     fn = getattr(L, "fa_kvcache_append" + "_paged" * paged + "_fp8" * fp8 + "_rope" * rope)
                     fn.argtypes = [vp] * (6 + paged + 2 * fp8 + 4 * rope) + [i] * (6 if paged else 4) + [i] + [i] * (4 * rope) + [i, vp]
                     fn.restype = C.c_int
+        # the descriptor form of the eight, with seqlens_new
+        L.fa_kvcache_append_ex.argtypes = [C.POINTER(KvAppendDesc)]
+        L.fa_kvcache_append_ex.restype = C.c_int
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

@@ -185,9 +185,10 @@ FA_EXPORT int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpo
 
 // The descriptor form of the eight entries above, plus sinks and softcap.  What the descriptor alone can get wrong is judged here;
 // everything else by kvdecode_dispatch, as for the flat entries.
+// A descriptor of the size the structure had before seqlens_q was appended is a valid one without the field.
 static bool kvdecode_desc_ok(const fa_kvdecode_desc* desc)
 {
-    if (!desc || desc->size != sizeof(fa_kvdecode_desc)) return false;
+    if (!desc || (desc->size != sizeof(fa_kvdecode_desc) && desc->size != offsetof(fa_kvdecode_desc, seqlens_q))) return false;
     if (desc->kv_dtype != FA_KV_16BIT && desc->kv_dtype != FA_KV_FP8_E4M3) return false;
     return desc->kv_dtype == FA_KV_FP8_E4M3 || (!desc->k_scale && !desc->v_scale);   // a 16-bit cache has no scales
 }
@@ -211,7 +212,8 @@ FA_EXPORT int fa_kvcache_decode(const fa_kvdecode_desc* desc)
                                              .table = desc->block_table, .num_pages = paged ? desc->num_pages : 0,
                                              .page_size = paged ? desc->page_size : 0, .max_pages = paged ? desc->max_pages : 0},
                                        .k_scale = desc->k_scale, .v_scale = desc->v_scale, .window = desc->window, .paged = paged,
-                                       .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap});
+                                       .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap,
+                                       .seqlens_q = desc->size == sizeof(fa_kvdecode_desc) ? desc->seqlens_q : nullptr});
 }
 
 FA_EXPORT int fa_kvcache_append(const void* Knew, const void* Vnew, void* Kcache, void* Vcache, const int* seqlens_k, int* seqlens_out,
@@ -286,6 +288,23 @@ FA_EXPORT int fa_kvcache_append_paged_fp8_rope(const void* Knew, const void* Vne
     return (int)fa::kvcache_append_dispatch({Knew, Vnew, Kpool, Vpool, seqlens_k, seqlens_out, block_table, k_scale, v_scale, B, Hkv, Nnew,
                                              0, d, in_dtype, num_pages, page_size, max_pages, true, true, static_cast<hipStream_t>(stream),
                                              Q, Qout, rope_cos, rope_sin, G, rot_dim, max_pos, interleaved, true});
+}
+
+// The descriptor form of the eight append entries above, plus seqlens_new.  What the descriptor alone can get wrong is judged here;
+// everything else by kvcache_append_dispatch, as for the flat entries.
+FA_EXPORT int fa_kvcache_append_ex(const fa_kvappend_desc* desc)
+{
+    if (!desc || desc->size != sizeof(fa_kvappend_desc)) return (int)hipErrorInvalidValue;
+    if (desc->kv_dtype != FA_KV_16BIT && desc->kv_dtype != FA_KV_FP8_E4M3) return (int)hipErrorInvalidValue;
+    const bool fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, paged = desc->block_table != nullptr, rope = desc->rope_cos != nullptr;
+    if (!fp8 && (desc->k_scale || desc->v_scale)) return (int)hipErrorInvalidValue;   // a 16-bit cache has no scales
+    if (!rope && (desc->Q || desc->Qout || desc->rope_sin)) return (int)hipErrorInvalidValue;   // arguments of the rotary forms
+    return (int)fa::kvcache_append_dispatch({desc->Knew, desc->Vnew, desc->K, desc->V, desc->seqlens_k, desc->seqlens_out, desc->block_table,
+                                             desc->k_scale, desc->v_scale, desc->B, desc->Hkv, desc->Nnew, paged ? 0 : desc->Ncap, desc->d,
+                                             desc->dtype, paged ? desc->num_pages : 0, paged ? desc->page_size : 0,
+                                             paged ? desc->max_pages : 0, paged, fp8, static_cast<hipStream_t>(desc->stream), desc->Q,
+                                             desc->Qout, desc->rope_cos, desc->rope_sin, rope ? desc->G : 0, rope ? desc->rot_dim : 0,
+                                             rope ? desc->max_pos : 0, rope ? desc->interleaved : 0, rope, desc->seqlens_new});
 }
 
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,

@@ -72,7 +72,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_fwd_kvragged*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -106,6 +106,8 @@ struct KvPagedArgs {
 // fa_kvcache_decode alone sets the last two, at the end so that the eight flat entries' initialisers leave them zero: sinks, a device
 // pointer to Hkv * G fp32 logits (null: none), and softcap (0: off; negative, NaN or inf: rejected).  A call with either runs the
 // LogitArgs kernels of fa_fwd_kvlogits*.hip, which exist around the windowed packs only: window 0 runs there as window = Ncap.
+// seqlens_q, also the descriptor's alone: a device pointer to B int32 query counts (null: every sequence has Nq rows).  A call with it
+// runs the RaggedArgs kernels of fa_fwd_kvragged*.hip, which wrap the LogitArgs packs, so window 0 runs there as window = Ncap too.
 struct KvDecodeArgs {
     KvPagedArgs p;
     const float *k_scale, *v_scale;
@@ -113,11 +115,13 @@ struct KvDecodeArgs {
     bool paged, fp8;
     const float* sinks;
     float softcap;
+    const int* seqlens_q;
 };
 hipError_t kvdecode_dispatch(const KvDecodeArgs& a);
 // What kvdecode_dispatch hands checked arguments to: one function per translation unit that owns decode kernels -- fa_fwd_kvcache,
 // _kvpaged, _kvfp8 (contiguous and paged), _kvwindow and _kvwindow_fp8 (window >= 1; contiguous and paged), _kvlogits and
-// _kvlogits_fp8 (sinks or softcap set, window >= 1; contiguous and paged).  lg_page: log2 of the page size (paged only).
+// _kvlogits_fp8 (sinks or softcap set, window >= 1; contiguous and paged), _kvragged and _kvragged_fp8 (seqlens_q set, window >= 1;
+// contiguous and paged).  lg_page: log2 of the page size (paged only).
 hipError_t kvcache_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvpaged_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvfp8_decode(const KvDecodeArgs& a, int lg_page);
@@ -125,11 +129,17 @@ hipError_t kvwindow_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvwindow_fp8_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvlogits_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvlogits_fp8_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvragged_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvragged_fp8_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
                            hipStream_t stream);   // the merge kernel behind a split, for all of them
 // ... and the merge that also joins the heads' sinks (not null), once per row -- fa_fwd_kvlogits.hip; Nq: rows per query head
 hipError_t kvlogits_combine(const void* ws, void* O, float* lse, const float* sinks, int BH, int rows, int Hkv, int Nq, int D, int S,
                             int in_dtype, int out_dtype, hipStream_t stream);
+// ... and the merge behind the per-sequence query counts (seqlens_q not null; sinks may be null) -- fa_fwd_kvragged.hip; Nq: the padded
+// rows per query head
+hipError_t kvragged_combine(const void* ws, void* O, float* lse, const float* sinks, const int* seqlens_q, int BH, int rows, int Hkv,
+                            int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
 // The argument checks alone: the append runs them too, so it accepts exactly the caches the decode accepts.  kvpaged_check fills
 // in the capacity and returns page_log2(page_size): log2 of a page size the kernels take, else -1.
 hipError_t kvcache_check(const KvCacheArgs& a);
@@ -163,10 +173,17 @@ struct KvAppendArgs {
     const float *rope_cos, *rope_sin;
     int G, rot_dim, max_pos, interleaved;
     bool rope;
+    // fa_kvcache_append_ex alone (fa_kvcache_append_ragged.hip): a device pointer to B int32 token counts, m_b = min(max(., 0), Nnew);
+    // null: every sequence appends Nnew tokens, and the call is the flat entry's
+    const int* seqlens_new;
 };
 hipError_t kvcache_append_dispatch(const KvAppendArgs& a);
 // what kvcache_append_dispatch hands a checked `rope` call to; Ncap: the checked capacity, lg_page: log2 of the page size (paged only)
 hipError_t kvcache_append_rope(const KvAppendArgs& a, int Ncap, int lg_page);
+// the rotary arguments' checks alone (fa_kvcache_append_rope.hip); qchunks: the 16-byte chunks of Q (counted whether or not there is a Q)
+hipError_t kvcache_append_rope_check(const KvAppendArgs& a, unsigned long long& qchunks);
+// what kvcache_append_dispatch hands a checked call with seqlens_new to, rotary or not (fa_kvcache_append_ragged.hip)
+hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
 // the lengths kernel behind either append kernel (fa_kvcache_append.hip); nothing is launched without a seqlens_out
 hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,

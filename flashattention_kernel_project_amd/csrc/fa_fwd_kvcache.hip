@@ -1,7 +1,7 @@
 // fa_fwd_kvcache.hip -- decode against a pre-allocated KV cache (fa_forward_kvcache): the split-KV stream of fa_fwd_split.hip with
 // the key count of each sequence read on the device, a causal mask aligned to the end of the cache and a log-sum-exp output.
 // DESIGN.md section 7 has the reasoning; the kernels are the CacheArgs instantiations of fa_fwd_split_kernel.hpp, launched through
-// the host path of fa_fwd_kvdecode.hpp like those of the six units beside this one.  Also here, once for all decode entries:
+// the host path of fa_fwd_kvdecode.hpp like those of the eight units beside this one.  Also here, once for all decode entries:
 // the argument checks, the entry kvdecode_dispatch and the merge kernel.
 #include "fa_fwd_kvdecode.hpp"
 
@@ -34,11 +34,13 @@ hipError_t kvcache_check(const KvCacheArgs& a)
 // The translation unit that owns the kernels of the pack the flags name.  Window 0 is the un-windowed entry itself: it launches
 // the un-windowed kernels.  With sinks or a soft-cap the LogitArgs kernels run, which wrap the windowed packs only: window 0 goes
 // there as window = Ncap, which include/fa_mi355.h guarantees to be the un-windowed result bit for bit, on the same split count.
+// With seqlens_q the RaggedArgs kernels run, which wrap the LogitArgs packs, under the same rule for window 0.
 static hipError_t kvdecode_handover(const KvDecodeArgs& d, int lg_page)
 {
-    if (d.sinks || d.softcap != 0.0f) {
+    if (d.sinks || d.softcap != 0.0f || d.seqlens_q) {
         KvDecodeArgs w = d;
         if (w.window == 0) w.window = w.p.c.Ncap;
+        if (w.seqlens_q) return w.fp8 ? kvragged_fp8_decode(w, lg_page) : kvragged_decode(w, lg_page);
         return w.fp8 ? kvlogits_fp8_decode(w, lg_page) : kvlogits_decode(w, lg_page);
     }
     if (d.window == 0) return d.fp8 ? kvfp8_decode(d, lg_page) : d.paged ? kvpaged_decode(d, lg_page) : kvcache_decode(d, lg_page);
@@ -54,7 +56,7 @@ hipError_t kvdecode_dispatch(const KvDecodeArgs& d)
         const hipError_t bad = kvcache_check(d.p.c);
         return bad != hipSuccess ? bad : kvdecode_handover(d, 0);
     }
-    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8, d.sinks, d.softcap};   // q.p: d.p with the capacity, from the check
+    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8, d.sinks, d.softcap, d.seqlens_q};   // q.p: d.p with the capacity, from the check
     int lg_page;
     const hipError_t bad = kvpaged_check(d.p, q.p, lg_page);
     return bad != hipSuccess ? bad : kvdecode_handover(q, lg_page);

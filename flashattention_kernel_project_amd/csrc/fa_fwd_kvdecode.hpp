@@ -1,7 +1,7 @@
 // fa_fwd_kvdecode.hpp -- the host path the eight KV-cache decode entries share: the pack builder, the launcher and the type switch,
-// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>) the kernel takes.  Private to the seven
-// translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow, _kvwindow_fp8, _kvlogits,
-// _kvlogits_fp8): it instantiates
+// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>) the kernel takes.  Private
+// to the nine translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow, _kvwindow_fp8,
+// _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8): it instantiates
 // kernels, so a unit names only its own packs and no other unit's code moves.
 #pragma once
 #include "fa_fwd_split_kernel.hpp"
@@ -33,6 +33,7 @@ static Pack kvdecode_pack(const KvDecodeArgs& d, int lg_page)
         pack.cap2 = d.softcap * kLog2e;
         pack.cap_rk = d.softcap > 0.0f ? 2.0f / d.softcap : 0.0f;
     }
+    if constexpr (IsRaggedArgs<Pack>::value) pack.seqlens_q = d.seqlens_q;
     return pack;
 }
 
@@ -68,8 +69,11 @@ static hipError_t launch_kvdecode(const KvCacheArgs& a, Pack pack, int span)
                        a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), pack);
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
+    // per-sequence query counts: the merge maps padded rows to the packed workspace rows, writes the dead rows and joins the sinks
+    if constexpr (IsRaggedArgs<Pack>::value)
+        return kvragged_combine(a.ws, a.O, a.lse, pack.sinks, pack.seqlens_q, BH, rows, a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // the partial kernels leave the sinks alone: the merge joins them, once per row
-    if constexpr (IsLogitArgs<Pack>::value)
+    else if constexpr (IsLogitArgs<Pack>::value)
         if (pack.sinks) return kvlogits_combine(a.ws, a.O, a.lse, pack.sinks, BH, rows, a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     return kvcache_combine(a.ws, a.O, a.lse, BH, rows, D, S, a.in_dtype, a.out_dtype, a.stream);
 }

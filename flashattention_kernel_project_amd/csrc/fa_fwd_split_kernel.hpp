@@ -6,7 +6,8 @@
 // entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
 // selects (profiles/kvcache_fp8.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
 // behind `if constexpr (kWindow)` (profiles/kvcache_window.txt); the soft-cap / sink entry wraps the four windowed packs in a
-// LogitArgs, and what it adds sits behind `if constexpr (kLogits)` (profiles/kvcache_logits.txt).
+// LogitArgs, and what it adds sits behind `if constexpr (kLogits)` (profiles/kvcache_logits.txt); the per-sequence query count wraps
+// the four LogitArgs packs in a RaggedArgs, and what it adds sits behind `if constexpr (kRagged)` (profiles/kvcache_ragged.txt).
 // The sets are instantiated in separate translation units so that none perturbs another's register allocation; the host path of the
 // KV-cache sets (pack builder, launcher, type switch) is fa_fwd_kvdecode.hpp.  Design notes: head of fa_fwd_split.hip, DESIGN.md 7.1.
 #pragma once
@@ -94,6 +95,22 @@ __device__ __forceinline__ NoLogits logit_part() { return {}; }
 __device__ __forceinline__ NoLogits logit_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const LogitArgs<Base>& logit_part(const LogitArgs<Base>& l) { return l; }
 
+// What the per-sequence query count instantiations take (fa_kvcache_decode with seqlens_q): a LogitArgs pack plus the counts.  The
+// CacheArgs' Nq1 is then the PADDED row count per query head; sequence b has n_b = min(max(seqlens_q[b], 0), Nq1) live rows per
+// head, and n_b takes the place of Nq1 in every limit.
+template <typename Base> struct RaggedArgs : Base {
+    const int* seqlens_q;   // [B] on the device, not null (without it the host runs the wrapped pack's kernels)
+};
+template <typename A> struct IsRaggedArgs : std::false_type {};
+template <typename Base> struct IsRaggedArgs<RaggedArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<RaggedArgs<Base>> : IsFp8Args<Base> {};
+template <typename Base> struct IsWindowArgs<RaggedArgs<Base>> : IsWindowArgs<Base> {};
+template <typename Base> struct IsLogitArgs<RaggedArgs<Base>> : IsLogitArgs<Base> {};
+struct NoRagged {};
+__device__ __forceinline__ NoRagged ragged_part() { return {}; }
+__device__ __forceinline__ NoRagged ragged_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const RaggedArgs<Base>& ragged_part(const RaggedArgs<Base>& g) { return g; }
+
 // A wave-uniform float into a scalar register.  gfx950 has no scalar float arithmetic, so a value computed from kernel arguments
 // lives in a VGPR unless it is read back; the d = 64 kernels sit at their 128 VGPRs and spill for every such value they keep.
 __device__ __forceinline__ float to_sgpr(float x)
@@ -167,6 +184,19 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // branch, and the tile loop is the windowed kernel's.  Sinks: one extra key per row with the head's logit and a zero V row, joined to
 // (m, l) by sink_join() in the one-pass epilogue here and in the merge kernel -- NEVER by a partial kernel: a row's sink counts once,
 // however many splits its keys were dealt to.
+// kRagged (kLogits with a RaggedArgs around the pack): sequence b has n_b <= Nq1 live rows per query head, read on the device, and
+// n_b replaces Nq1 in start_b, in the causal limit and in the lower limit.  The G * n_b live rows of a K/V head are PACKED into the
+// leading row blocks: packed row r' is row r' % n_b of head r' / n_b, and Q is loaded from (O and lse stored to) that row's padded
+// address.  A lane past the live rows gets a row past the descriptors (its Q reads as zeros -- the caller's Q row is never loaded --
+// and it stores nothing) and the limits of the last live row, so that it votes for a new reference maximum only in a tile in which
+// that live row votes too: a dead row cannot move a live row's bits.  (With n_b = Nq1 no row is dead, and a lane past Nq keeps the
+// limits the wrapped kernel gives it, so that the bits are the wrapped kernel's in every shape.)  The dead rows' zeros and -inf are written by the workgroup
+// whose block holds their PADDED index (one-pass kernels; behind a split the merge writes them), and a workgroup whose block holds
+// no live row returns before any table entry or K/V row is read -- with n_b = 0 that is every workgroup of the sequence.  The
+// partial kernels store workspace rows by packed index.  Nothing of this lives in a VGPR across the tile loop: the row's limit
+// takes the register the wrapped kernel keeps for it, and the one-pass epilogue derives the padded row again.
+// The wrapped kernels' own expressions are left textually alone, with the ragged ones beside them: naming "rows per head" once for
+// both changed the schedule of the windowed units (profiles/kvcache_ragged.txt).
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -189,6 +219,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto wa = window_part(cache...);
     constexpr bool kLogits = (IsLogitArgs<Cache>::value || ...);
     [[maybe_unused]] const auto la = logit_part(cache...);
+    constexpr bool kRagged = (IsRaggedArgs<Cache>::value || ...);
+    [[maybe_unused]] const auto ra = ragged_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -211,10 +243,32 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if (ca.seqlens) nkeys = (unsigned)min(max(ca.seqlens[bh / (unsigned)ca.Hkv], 0), Nk);
         if constexpr (!kWindow) chunk = (int)(((nkeys + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
     }
+    // kRagged: the sequence's live rows per query head and per K/V head (wave-uniform).  The one-pass kernels write the dead rows
+    // of this block's padded share -- two threads per row, half a row each -- and a block without a live packed row ends here.
+    [[maybe_unused]] unsigned n_q = 0, live = 0;
+    if constexpr (kRagged) {
+        n_q = (unsigned)min(max(ra.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
+        live = ((unsigned)Nq / (unsigned)ca.Nq1) * n_q;
+        if constexpr (!kPartial) {
+            const unsigned pr = qb * (unsigned)kRows + (tid >> 1);
+            if (pr < (unsigned)Nq && pr % (unsigned)ca.Nq1 >= n_q) {
+                constexpr unsigned es = kOutF32 ? 4u : 2u, kHalf = (unsigned)D * es / 2u;
+                const __amdgpu_buffer_rsrc_t rz =
+                    make_rsrc(reinterpret_cast<char*>(Og) + (size_t)bh * Nq * D * es, (unsigned)((size_t)Nq * D * es));
+#pragma unroll
+                for (unsigned o = 0; o < kHalf; o += 16u)
+                    buf_store16(rz, pr * (unsigned)D * es + (tid & 1u) * kHalf + o, u32x4{0u, 0u, 0u, 0u});
+                if (ca.lse && !(tid & 1u))
+                    buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), pr * 4u, __float_as_uint(-INFINITY));
+            }
+        }
+        if (qb * (unsigned)kRows >= live) return;   // workgroup-uniform; n_q >= 1 from here on
+    }
     // kWindow: the first key any row of the sequence sees, the tile it lies in, and the tiles from there dealt out to the splits
     [[maybe_unused]] unsigned start_b = 0, start_t = 0;
     if constexpr (kWindow) {
-        start_b = (unsigned)max((int)nkeys - ca.Nq1 + 1 - wa.window, 0);
+        if constexpr (kRagged) start_b = (unsigned)max((int)nkeys - (int)n_q + 1 - wa.window, 0);
+        else start_b = (unsigned)max((int)nkeys - ca.Nq1 + 1 - wa.window, 0);
         start_t = start_b & ~(unsigned)(kBlockN - 1);
         chunk = (int)(((nkeys - start_t + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
     }
@@ -231,16 +285,34 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(kv_at(Vg, (size_t)bh * Nk * D), key1 * kKvRowBytes);
 
     constexpr int kLoadsW = (kBlockN * kLdChunks) / (64 * W);
-    const unsigned q_row = qb * (unsigned)kRows + wave * 32u + r;
-    const bool has_rows = qb * (unsigned)kRows + wave * 32u < (unsigned)Nq;   // wave-uniform
+    const unsigned q_row = qb * (unsigned)kRows + wave * 32u + r;   // kRagged: the PACKED row
+    const bool has_rows = qb * (unsigned)kRows + wave * 32u < (kRagged ? live : (unsigned)Nq);   // wave-uniform
+    // kRagged: the lane's packed row -> its padded row, where Q, O and lse live (a lane past the live rows: a row past every
+    // descriptor), and its index within its head, which for such a lane is the last live row's -- except with n_b = Nq1, where no
+    // row is dead and a lane past Nq keeps the index q_row % Nq1 the wrapped kernel gives it: its votes then fall in the same tiles,
+    // which is what makes full counts return the wrapped kernel's bits in every shape.  Else io_row is q_row.
+    [[maybe_unused]] unsigned rag_row1 = 0, rag_io = 0;
+    if constexpr (kRagged) {
+        const unsigned last = n_q == (unsigned)ca.Nq1 ? ~0u : live - 1u;   // wave-uniform
+        const unsigned pc = min(q_row, last), hd = pc / n_q;
+        rag_row1 = pc - hd * n_q;
+        rag_io = q_row < live ? hd * (unsigned)ca.Nq1 + rag_row1 : (unsigned)Nq;
+    }
+    const unsigned io_row = kRagged ? rag_io : q_row;
 
     // first key a row does NOT see, and the smallest such limit of any row (tiles that end at or below it need no mask)
     [[maybe_unused]] unsigned lim = key1, lim_lo = key1;
     if constexpr (kCache) {
         if (ca.causal) {
-            const int first = (int)nkeys - ca.Nq1 + 1;   // limit of row 0 of a head; may be <= 0
-            lim = min((unsigned)max(first + (int)(q_row % (unsigned)ca.Nq1), 0), key1);
-            lim_lo = min((unsigned)max(first, 0), key1);
+            if constexpr (kRagged) {
+                const int first = (int)nkeys - (int)n_q + 1;
+                lim = min((unsigned)max(first + (int)rag_row1, 0), key1);
+                lim_lo = min((unsigned)max(first, 0), key1);
+            } else {
+                const int first = (int)nkeys - ca.Nq1 + 1;   // limit of row 0 of a head; may be <= 0
+                lim = min((unsigned)max(first + (int)(q_row % (unsigned)ca.Nq1), 0), key1);
+                lim_lo = min((unsigned)max(first, 0), key1);
+            }
         }
     }
     // kWindow: the row's causal limit before any clamp -- both of its limits follow from it in the few tiles that mask, so the row
@@ -249,7 +321,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] int row_end = 0;
     [[maybe_unused]] unsigned lo_hi = 0;
     if constexpr (kWindow) {
-        row_end = (int)nkeys - ca.Nq1 + 1 + (int)(q_row % (unsigned)ca.Nq1);
+        if constexpr (kRagged) row_end = (int)nkeys - (int)n_q + 1 + (int)rag_row1;
+        else row_end = (int)nkeys - ca.Nq1 + 1 + (int)(q_row % (unsigned)ca.Nq1);
         lo_hi = (unsigned)max((int)nkeys - wa.window, 0);
     }
 
@@ -277,7 +350,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     u32x4 qf[G::kKSteps];
 #pragma unroll
     for (int s = 0; s < G::kKSteps; ++s) {
-        u32x4 raw = buf_load16(rq, q_row * G::kRowBytes + (16u * s + 8u * h) * 2u);
+        u32x4 raw = buf_load16(rq, io_row * G::kRowBytes + (16u * s + 8u * h) * 2u);
 #pragma unroll
         for (int w = 0; w < 4; ++w) raw[w] ^= q_flip;
         qf[s] = raw;
@@ -517,6 +590,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         }
         const __amdgpu_buffer_rsrc_t rw =
             make_rsrc(ws + ((size_t)bh * S + sp) * rows * (D + 2), (unsigned)(rows * rs));
+        // kRagged: q_row is the PACKED row; the merge maps padded rows to it
 #pragma unroll
         for (int db = 0; db < G::kDBlocks; ++db)
 #pragma unroll
@@ -531,6 +605,17 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if (h == 0)
             buf_store8(rw, q_row * rs + (unsigned)D * 4u, u32x2{__float_as_uint(m_ref), __float_as_uint(l)});
     } else {
+        // kRagged: the padded row once more, from the packed one and the two counts taken through an empty asm: kept from the
+        // prologue it stays in a VGPR across the tile loop, and so does q_row once the prologue has divided it (the wrapped kernels
+        // re-derive q_row from the thread id), which the d = 64 paged kernels spill; the counts themselves are scalar
+        [[maybe_unused]] unsigned o_row = io_row;
+        if constexpr (kRagged) {
+            unsigned nq = n_q, lv = live, t = tid;
+            asm volatile("" : "+s"(nq), "+s"(lv), "+v"(t));
+            const unsigned pk = qb * (unsigned)kRows + (t >> 6) * 32u + (t & 31u);   // q_row, from the thread id again
+            const unsigned pc = min(pk, lv - 1u), hd = pc / nq;
+            o_row = pk < lv ? hd * (unsigned)ca.Nq1 + (pc - hd * nq) : (unsigned)Nq;
+        }
         // kLogits: the sink joins here, once per row; rows past Nq read the sink of the head's last row and store nothing
         [[maybe_unused]] float w_keys = 1.0f;
         if constexpr (kLogits) {
@@ -540,7 +625,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 // spill (profiles/kvcache_logits.txt); recomputed here they cost a few instructions once per workgroup
                 unsigned nq1 = (unsigned)ca.Nq1, nhkv = (unsigned)ca.Hkv;
                 asm volatile("" : "+s"(nq1), "+s"(nhkv));
-                const unsigned hq = (bh % nhkv) * ((unsigned)Nq / nq1) + min(q_row, (unsigned)Nq - 1u) / nq1;
+                const unsigned hq = (bh % nhkv) * ((unsigned)Nq / nq1) + min(o_row, (unsigned)Nq - 1u) / nq1;
                 w_keys = sink_join(la.sinks[hq] * kLog2e, m_ref, l);
             }
         }
@@ -549,7 +634,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if constexpr (kFp8) inv *= v_scale;
         if constexpr (kCache) {
             if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
-                buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), q_row * 4u,
+                buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), o_row * 4u,
                            __float_as_uint(l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2));
         }
         constexpr unsigned es = kOutF32 ? 4u : 2u;
@@ -564,9 +649,9 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 const float cc = o[db][4 * g + 2] * inv, d = o[db][4 * g + 3] * inv;
                 if constexpr (kOutF32) {
                     const f32x4 v = {a, b, cc, d};
-                    buf_store16(ro, (q_row * D + col) * 4u, __builtin_bit_cast(u32x4, v));
+                    buf_store16(ro, (o_row * D + col) * 4u, __builtin_bit_cast(u32x4, v));
                 } else {
-                    buf_store8(ro, (q_row * D + col) * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
+                    buf_store8(ro, (o_row * D + col) * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
                 }
             }
     }
@@ -590,6 +675,23 @@ struct NoSink {};
 __device__ __forceinline__ NoSink sink_part() { return {}; }
 __device__ __forceinline__ NoSink sink_part(float*) { return {}; }
 __device__ __forceinline__ const SinkLse& sink_part(const SinkLse& s) { return s; }
+// RaggedLse in the place of the float*: the merge behind the RaggedArgs partial kernels.  Output row `row` (padded) of K/V head bh is
+// row i = row % Nq1 of its query head; with n_b = min(max(seqlens_q[bh / Hkv], 0), Nq1) it is dead for i >= n_b -- the wave writes
+// zeros and -inf and reads no partial -- and else its partials are workspace row (row / Nq1) * n_b + i.  Sinks (may be null here)
+// join the live rows as under SinkLse.
+struct RaggedLse {
+    float* lse;
+    const float* sinks;       // [Hkv * G] on the device, or nullptr
+    const int* seqlens_q;     // [B] on the device, not null
+    int Hkv, Nq1;
+};
+__device__ __forceinline__ float* lse_part(const RaggedLse& s) { return s.lse; }
+__device__ __forceinline__ NoSink sink_part(const RaggedLse&) { return {}; }
+struct NoRaggedLse {};
+__device__ __forceinline__ NoRaggedLse ragged_lse_part() { return {}; }
+__device__ __forceinline__ NoRaggedLse ragged_lse_part(float*) { return {}; }
+__device__ __forceinline__ NoRaggedLse ragged_lse_part(const SinkLse&) { return {}; }
+__device__ __forceinline__ const RaggedLse& ragged_lse_part(const RaggedLse& s) { return s; }
 template <typename T, bool kOutF32, bool kCache = false, typename... Lse>
 __global__ __launch_bounds__(64)
 void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og, int BH, int Nq, int D, int S, Lse... lse_arg)
@@ -598,6 +700,8 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     [[maybe_unused]] float* const lse = lse_part(lse_arg...);
     constexpr bool kSink = (std::is_same_v<Lse, SinkLse> || ...);
     [[maybe_unused]] const auto sk = sink_part(lse_arg...);
+    constexpr bool kRaggedM = (std::is_same_v<Lse, RaggedLse> || ...);
+    [[maybe_unused]] const auto rg = ragged_lse_part(lse_arg...);
     const int cols4 = D / 4;             // 16 or 32
     const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
     const unsigned lane = threadIdx.x;
@@ -606,7 +710,26 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     const int row = (int)(rowi % Nq);
     const int bh = (int)(rowi / Nq);
     const size_t stride_s = (size_t)Nq * (D + 2);
-    const float* base = ws + (size_t)bh * S * stride_s + (size_t)row * (D + 2);
+    int ws_row = row;                    // the row's partials in the workspace
+    if constexpr (kRaggedM) {
+        const int n_q = min(max(rg.seqlens_q[bh / rg.Hkv], 0), rg.Nq1), hd = row / rg.Nq1, i = row - hd * rg.Nq1;
+        if (i >= n_q) {   // wave-uniform: a dead row
+            if (sl != 0) return;
+            if (lse && lane == 0) lse[rowi] = -INFINITY;
+            const size_t off = ((size_t)bh * Nq + row) * D + 4 * c4;
+            if constexpr (kOutF32) {
+                float* o = static_cast<float*>(Og) + off;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = 0.0f;
+            } else {
+                unsigned* o = reinterpret_cast<unsigned*>(static_cast<uint16_t*>(Og) + off);
+                o[0] = o[1] = 0u;
+            }
+            return;
+        }
+        ws_row = hd * n_q + i;
+    }
+    const float* base = ws + (size_t)bh * S * stride_s + (size_t)ws_row * (D + 2);
     // global reference max: every lane takes splits lane, lane+64, ...
     float M = -INFINITY;
     for (int s = (int)lane; s < S; s += 64) M = fmaxf(M, base[(size_t)s * stride_s + D]);
@@ -616,6 +739,10 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     [[maybe_unused]] float a2 = -INFINITY;
     if constexpr (kSink) {
         a2 = sk.sinks[(bh % sk.Hkv) * (Nq / sk.Nq1) + row / sk.Nq1] * kLog2e;
+        M = fmaxf(M, a2);
+    }
+    if constexpr (kRaggedM) {
+        if (rg.sinks) a2 = rg.sinks[(bh % rg.Hkv) * (Nq / rg.Nq1) + row / rg.Nq1] * kLog2e;
         M = fmaxf(M, a2);
     }
     float L = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -638,7 +765,7 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
         for (int i = 0; i < 4; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
     }
     if (sl != 0) return;
-    if constexpr (kSink) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
+    if constexpr (kSink || kRaggedM) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
     const float inv = (kCache && L == 0.0f) ? 0.0f : 1.0f / L;
     if constexpr (kCache) {
         if (lse && lane == 0) lse[rowi] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;

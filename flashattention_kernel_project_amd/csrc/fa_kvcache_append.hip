@@ -118,6 +118,8 @@ hipError_t kvcache_append_dispatch(const KvAppendArgs& a)
         const uintptr_t bytes = (uintptr_t)a.B * sizeof(int);
         if (in < out + bytes && out < in + bytes) return hipErrorInvalidValue;
     }
+    // a token count per sequence: its own checks and kernels, rotary or not (fa_kvcache_append_ragged.hip)
+    if (a.seqlens_new) return kvcache_append_ragged(a, Ncap, lg_page);
     if (a.rope) return kvcache_append_rope(a, Ncap, lg_page);   // its own checks, then its own kernels (fa_kvcache_append_rope.hip)
     const AppendDev dev = {a.seqlens, a.table, a.k_scale, a.v_scale, (unsigned)chunks, a.Hkv, a.Nnew, Ncap, a.max_pages, a.num_pages, lg_page};
     if (a.paged) return a.fp8 ? append_types<true, true>(a, dev) : append_types<true, false>(a, dev);

@@ -149,12 +149,13 @@ def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
 
 
 def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream, window, paged=False,
-            block_table=None, scales=None, sinks=None, softcap=0.0):
+            block_table=None, scales=None, sinks=None, softcap=0.0, seqlens_q=None):
     """The four decode front ends: k, v (named k_name, v_name in messages) are a cache [B,Hkv,Ncap,d] or, with `paged`, a pool
     [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one.  The C entry
     is fa_forward_kvcache + _paged + _fp8 + _window, and each suffix inserts its arguments: the table after the lengths, the two
     scales after that, the geometry of the pool in the place of Ncap, the window after causal.  With `sinks` (a tensor) or a
-    `softcap` other than 0 the call goes through the descriptor entry fa_kvcache_decode instead, which alone has the two."""
+    `softcap` other than 0 or `seqlens_q` (a tensor) the call goes through the descriptor entry fa_kvcache_decode instead, which alone has
+    the three."""
     import torch
     fp8 = scales is not None
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[3] != k.shape[3] or (not paged and q.shape[0] != k.shape[0]):
@@ -194,6 +195,7 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     window = _window(window)
     softcap = _softcap(softcap)
     sink_ptr = _sinks_ptr(sinks, Hq, q.device)
+    nq_ptr = _counts_ptr(seqlens_q, "seqlens_q", B, q.device)
     # in the place of Ncap a pool has (num_pages, page_size, max_pages)
     cap = (k.shape[0], k.shape[2], block_table.shape[1]) if paged else (k.shape[2],)
     if workspace is None:
@@ -205,7 +207,7 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
     if scale is None:
         scale = 1.0 / math.sqrt(d)
-    if sinks is not None or softcap != 0.0:
+    if sinks is not None or softcap != 0.0 or seqlens_q is not None:
         # args: [table] [k_scale, v_scale]; the descriptor names every field, so no suffix rule is needed
         desc = capi.KvDecodeDesc(
             Q=ptrs[0], K=ptrs[1], V=ptrs[2], O=out.data_ptr(), lse=lse.data_ptr() if return_lse else None, seqlens_k=len_ptr,
@@ -215,8 +217,8 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
             max_pages=cap[2] if paged else 0, scale=float(scale), causal=1 if causal else 0, window=window, softcap=softcap,
             in_dtype=capi.F16 if q.dtype == torch.float16 else capi.BF16,
             out_dtype=capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, workspace=ws_ptr, workspace_bytes=ws_len,
-            stream=_stream_ptr(stream))
-        with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace, sinks)):
+            stream=_stream_ptr(stream), seqlens_q=nq_ptr)
+        with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace, sinks, seqlens_q)):
             code = capi.lib().fa_kvcache_decode(desc)
         capi.check("fa_kvcache_decode", code)
         return (out, lse) if return_lse else out
@@ -233,7 +235,7 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
 
 def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = False, scale: float | None = None,
                        out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0, sinks=None,
-                       softcap: float = 0.0):
+                       softcap: float = 0.0, seqlens_q=None):
     """Decode against a pre-allocated cache (fa_forward_kvcache): q [B,Hq,Nq,d], k_cache/v_cache [B,Hkv,Ncap,d]
     fp16/bf16 device tensors, d in {64,128}, Hq a multiple of Hkv (the group's K/V is streamed once, as in
     fa_forward_splitkv).
@@ -251,9 +253,13 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     sinks: None, or a float32 contiguous device tensor of Hq values: head h gets one extra key with the natural-log logit sinks[h]
     (not scaled, not capped) and a zero V row, which every row sees under any mask or window -- lse includes it; -inf: no sink for
     that head.  Read on the device only.  When merging over key ranges, pass sinks to exactly one range.
-    With either the call is fa_kvcache_decode; workspace sizes are unchanged."""
+    seqlens_q: None, or an int32 contiguous device tensor [B]: Nq is then the PADDED row count and sequence b has
+    n_b = min(max(seqlens_q[b], 0), Nq) live rows per head, rows i < n_b, with n_b in the place of Nq in the causal and window limits.
+    Dead rows return O = 0 and lse = -inf exactly and their q rows are never used; n_b = 0 is an idle slot that reads nothing of the
+    sequence.  Read on the device only: a captured call follows counts rewritten in place; grid, splits and workspace follow the padded Nq.
+    With any of the three the call is fa_kvcache_decode; workspace sizes are unchanged."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, sinks=sinks, softcap=softcap)
+                   window, sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
 
 def kvcache_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, Ncap: int, d: int) -> int:
@@ -287,6 +293,22 @@ def _sinks_ptr(sinks, Hq: int, device):
     return _dev_ptr(sinks, "sinks", (torch.float32,))
 
 
+def _counts_ptr(counts, name: str, B: int, device):
+    """None, or the device pointer of a checked per-sequence count vector (seqlens_q, seqlens_new): one int32 per sequence."""
+    if counts is None:
+        return None
+    import torch
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+        raise ValueError(f"{name} must be an int32 device tensor")
+    if counts.numel() != B or counts.dim() != 1:
+        raise ValueError(f"{name} must hold one value per sequence (shape [{B}]), got {tuple(counts.shape)}")
+    if not counts.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if counts.device != device:
+        raise ValueError(f"{name} is on {counts.device}, the call's tensors on {device}")
+    return _dev_ptr(counts, name, (torch.int32,))
+
+
 def _window(window) -> int:
     if isinstance(window, bool) or not isinstance(window, int) or window < 0:
         raise ValueError("window must be an int >= 0 (0: no window)")
@@ -295,7 +317,7 @@ def _window(window) -> int:
 
 def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None, causal: bool = False, scale: float | None = None,
                              out_dtype=None, return_lse: bool = False, workspace=None, stream=None, window: int = 0, sinks=None,
-                             softcap: float = 0.0):
+                             softcap: float = 0.0, seqlens_q=None):
     """fa_forward_kvcache against a paged cache (fa_forward_kvcache_paged): q [B,Hq,Nq,d], k_pool/v_pool
     [num_pages,Hkv,page_size,d] fp16/bf16 contiguous device tensors (a contiguous slice of a larger pool, pool[2:6], is a pool),
     d in {64,128}, page_size a power of two >= 16, Hq a multiple of Hkv.
@@ -309,9 +331,9 @@ def fa_forward_kvcache_paged(q, k_pool, v_pool, block_table, cache_seqlens=None,
     position and the W - 1 before it (fa_forward_kvcache_paged_window).  Keys below row 0's lower limit are never used.  The window is a host
     integer (baked into a captured call); the workspace is then sized by kvcache_paged_window_workspace_bytes.
     Under a window a page wholly below row 0's lower limit is not dereferenced and its table entry is not read.
-    sinks, softcap: as in fa_forward_kvcache."""
+    sinks, softcap, seqlens_q: as in fa_forward_kvcache."""
     return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, paged=True, block_table=block_table, sinks=sinks, softcap=softcap)
+                   window, paged=True, block_table=block_table, sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
 
 def kvcache_paged_workspace_bytes(B: int, Hkv: int, G: int, Nq: int, max_pages: int, page_size: int, d: int) -> int:
@@ -329,7 +351,7 @@ _FP8_CACHE = "an fp8 cache must be torch.float8_e4m3fn (OCP e4m3fn, the gfx950 f
 
 def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, causal: bool = False,
                            scale: float | None = None, out_dtype=None, return_lse: bool = False, workspace=None, stream=None,
-                           window: int = 0, sinks=None, softcap: float = 0.0):
+                           window: int = 0, sinks=None, softcap: float = 0.0, seqlens_q=None):
     """fa_forward_kvcache against an fp8 cache (fa_forward_kvcache_fp8): q [B,Hq,Nq,d] fp16/bf16, k_cache/v_cache [B,Hkv,Ncap,d]
     torch.float8_e4m3fn (OCP e4m3fn; fnuz and e5m2 are refused) device tensors, d in {64,128}.  K and V are widened to q's type
     on the way into the kernel, exactly.
@@ -338,21 +360,21 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     like cache_seqlens, so a captured call follows all three when they are rewritten in place.  quantize_kv_fp8() makes a cache
     and its scales from a 16-bit or fp32 tensor.
     Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (then
-    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes), sinks and softcap (the sinks take neither scale) -- is
+    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes), sinks and softcap (the sinks take neither scale), seqlens_q -- is
     fa_forward_kvcache's."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap)
+                   window, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
 
 def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
                                  causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
-                                 workspace=None, stream=None, window: int = 0, sinks=None, softcap: float = 0.0):
+                                 workspace=None, stream=None, window: int = 0, sinks=None, softcap: float = 0.0, seqlens_q=None):
     """fa_forward_kvcache_paged against fp8 pools (fa_forward_kvcache_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
     torch.float8_e4m3fn, block_table as in fa_forward_kvcache_paged, k_scale / v_scale and everything else as in
     fa_forward_kvcache_fp8.  Workspace: kvcache_paged_workspace_bytes; with a window (fa_forward_kvcache_paged_fp8_window)
-    kvcache_paged_window_workspace_bytes.  sinks, softcap: as in fa_forward_kvcache."""
+    kvcache_paged_window_workspace_bytes.  sinks, softcap, seqlens_q: as in fa_forward_kvcache."""
     return _decode(q, k_pool, v_pool, "k_pool", "v_pool", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
-                   window, paged=True, block_table=block_table, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap)
+                   window, paged=True, block_table=block_table, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
 
 FP8_E4M3_MAX = 448.0   # largest finite e4m3fn value
@@ -452,11 +474,31 @@ def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
     return q, q_out, cos, sin, (G, rot_dim, max_pos, 1 if interleaved else 0)
 
 
-def _append_call(base, tensors, head, geometry, d, dt, rot, stream):
-    """The C call of an append front end: `base` + "_rope" with the rotary groups inserted, pointers before B and integers after d."""
+def _append_call(base, tensors, head, geometry, d, dt, rot, stream, seqlens_new=None):
+    """The C call of an append front end: `base` + "_rope" with the rotary groups inserted, pointers before B and integers after d.
+    With seqlens_new (a tensor) the call is fa_kvcache_append_ex, whose descriptor names every field."""
     import torch
     name = base + ("_rope" if rot else "")
     ptrs, ints, more = rot if rot else ((), (), ())
+    if seqlens_new is not None:
+        paged, fp8 = "_paged" in base, "_fp8" in base
+        B, Hkv, Nnew = geometry[:3]
+        cnt_ptr = _counts_ptr(seqlens_new, "seqlens_new", B, tensors[0].device)
+        rest = list(head[6:])          # [table] [k_scale, v_scale]
+        table = rest.pop(0) if paged else None
+        ks, vs = rest if fp8 else (None, None)
+        G, rot_dim, max_pos, il = ints if rot else (0, 0, 0, 0)
+        q_ptr, qout_ptr, cos_ptr, sin_ptr = ptrs if rot else (None, None, None, None)
+        desc = capi.KvAppendDesc(
+            Knew=head[0], Vnew=head[1], K=head[2], V=head[3], seqlens_k=head[4], seqlens_out=head[5], seqlens_new=cnt_ptr,
+            block_table=table, k_scale=ks, v_scale=vs, Q=q_ptr, Qout=qout_ptr, rope_cos=cos_ptr, rope_sin=sin_ptr,
+            kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, Nnew=Nnew, d=d, Ncap=0 if paged else geometry[3],
+            num_pages=geometry[3] if paged else 0, page_size=geometry[4] if paged else 0, max_pages=geometry[5] if paged else 0,
+            G=G, rot_dim=rot_dim, max_pos=max_pos, interleaved=il, dtype=dt, stream=_stream_ptr(stream))
+        with torch.cuda.device(_one_device(*tensors, *more, seqlens_new)):
+            code = capi.lib().fa_kvcache_append_ex(desc)
+        capi.check("fa_kvcache_append_ex", code)
+        return
     with torch.cuda.device(_one_device(*tensors, *more)):
         code = getattr(capi.lib(), name)(*head, *ptrs, *geometry, d, *ints, dt, _stream_ptr(stream))
     capi.check(name, code)
@@ -483,7 +525,7 @@ def _table_ptr(block_table, B):
 
 
 def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlens_out=None, stream=None, *, q=None, q_out=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlens_new=None) -> None:
     """Write k_new/v_new [B,Hkv,Nnew,d] behind each sequence's length into k_cache/v_cache [B,Hkv,Ncap,d] (fa_kvcache_append): fp16 or
     bf16 device tensors of ONE dtype, d in {64,128}.  Token t of sequence b goes to row L_b + t, L_b = cache_seqlens[b] clamped to
     [0, Ncap]; a token at or past Ncap is dropped; nothing else in the cache changes.  The caches are mutated, None is returned.
@@ -498,25 +540,29 @@ def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlen
     the cache, elements [rot_dim, d) pass through, V is written as without them.  rotary_interleaved: False pairs (x[i], x[i+rot_dim/2])
     (NeoX / HF), True pairs (x[2i], x[2i+1]) (GPT-J).  The arithmetic is stepwise fp32 without fused multiply-add (include/fa_mi355.h).
     q: [B,Hq,Nnew,d] of k_new's dtype, Hq a multiple of Hkv, or None: rotated by the same positions in the same launch, into q_out
-    (same shape and dtype, not overlapping q) or, with q_out=None, in place.  Without rotary_cos, q and q_out must be None."""
+    (same shape and dtype, not overlapping q) or, with q_out=None, in place.  Without rotary_cos, q and q_out must be None.
+    seqlens_new: None, or an int32 contiguous device tensor [B] that does not overlap seqlens_out: Nnew is then the PADDED token count,
+    sequence b appends its first m_b = min(max(seqlens_new[b], 0), Nnew) tokens and grows by m_b; a token t >= m_b is not written (no
+    table entry is read for it) and its q row reaches q_out unchanged.  Read on the device only.  The call is fa_kvcache_append_ex;
+    fa_forward_kvcache(seqlens_q=the same tensor) is its read half."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
     B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
         k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, False, "k_cache, v_cache",
         (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
     _append_call("fa_kvcache_append", (k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out), (*src, *dst, len_ptr, out_ptr),
-                 (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream)
+                 (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream, seqlens_new)
 
 
 def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens=None, seqlens_out=None, stream=None, *, q=None,
-                            q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
+                            q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlens_new=None) -> None:
     """fa_kvcache_append into a paged cache (fa_kvcache_append_paged): k_pool/v_pool [num_pages,Hkv,page_size,d] of k_new's dtype,
     block_table int32 [B, max_pages] as in fa_forward_kvcache_paged; position p is row p % page_size of page
     block_table[b, p // page_size], the capacity is max_pages * page_size.  A table entry outside [0, num_pages) drops the tokens of
     that page; entries of pages that receive no token are not read.  The pages a sequence appends into must be its own: a page shared
     between sequences may only be written by the caller's copy-on-write (not checked).
     q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_paged_rope); the q row of a
-    dropped token is still rotated."""
+    dropped token is still rotated.  seqlens_new: as in fa_kvcache_append."""
     if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
     tbl_ptr = _table_ptr(block_table, k_new.shape[0])
@@ -525,17 +571,17 @@ def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seq
         (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
     _append_call("fa_kvcache_append_paged", (k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out),
                  (*src, *dst, len_ptr, out_ptr, tbl_ptr), (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt,
-                 rot, stream)
+                 rot, stream, seqlens_new)
 
 
 def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, seqlens_out=None,
-                          stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
+                          stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlens_new=None) -> None:
     """fa_kvcache_append into an fp8 cache (fa_kvcache_append_fp8): k_new/v_new fp16 or bf16, k_cache/v_cache [B,Hkv,Ncap,d]
     torch.float8_e4m3fn (fnuz and e5m2 are refused).  The stored code is quantize_kv_fp8(x, scale) bit for bit: x / scale[h] in fp32,
     clamped to +-448, rounded to nearest even; +-inf becomes +-448, NaN a NaN code.
     k_scale, v_scale: float32 contiguous device tensors [Hkv], finite and > 0, or None (1.0); read on the device only.
     q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_fp8_rope).  The fp32 rotated K is
-    quantised directly, without a 16-bit rounding in between; q stays 16 bit."""
+    quantised directly, without a 16-bit rounding in between; q stays 16 bit.  seqlens_new: as in fa_kvcache_append."""
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
     import torch
@@ -546,15 +592,15 @@ def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=
         k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, True, "k_cache, v_cache",
         (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
     _append_call("fa_kvcache_append_fp8", (k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out),
-                 (*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr), (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream)
+                 (*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr), (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream, seqlens_new)
 
 
 def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
                                 seqlens_out=None, stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None,
-                                rotary_interleaved=False) -> None:
+                                rotary_interleaved=False, seqlens_new=None) -> None:
     """fa_kvcache_append_paged into fp8 pools (fa_kvcache_append_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
     torch.float8_e4m3fn, block_table as in fa_kvcache_append_paged, scales and codes as in fa_kvcache_append_fp8; the rotary keywords
-    as there (fa_kvcache_append_paged_fp8_rope)."""
+    as there (fa_kvcache_append_paged_fp8_rope); seqlens_new as in fa_kvcache_append."""
     if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
         raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
     import torch
@@ -567,7 +613,7 @@ def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_sca
         (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
     _append_call("fa_kvcache_append_paged_fp8", (k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out),
                  (*src, *dst, len_ptr, out_ptr, tbl_ptr, ks_ptr, vs_ptr),
-                 (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt, rot, stream)
+                 (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt, rot, stream, seqlens_new)
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

@@ -36,6 +36,23 @@ eager fallback.  Registered on first use:
                                        rotary_sin, interleaved)
     torch.ops.fa_mi355.append_paged_fp8_rope(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
                                              q, rotary_cos, rotary_sin, interleaved)
+    # a count per sequence (ops' seqlens_q / seqlens_new): the _ex schema with `Tensor? seqlens_q` after cache_seqlens, and the _rope schema
+    # with q, rotary_cos, rotary_sin optional and `Tensor? seqlens_new` after seqlens_out
+    o = torch.ops.fa_mi355.decode_ragged(q, k_cache, v_cache, cache_seqlens, seqlens_q, scale, causal, window, sinks, softcap, out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_ragged(q, k_pool, v_pool, block_table, cache_seqlens, seqlens_q, scale, causal, window, sinks,
+                                               softcap, out_fp32)
+    o = torch.ops.fa_mi355.decode_fp8_ragged(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_q, scale, causal, window,
+                                             sinks, softcap, out_fp32)
+    o = torch.ops.fa_mi355.decode_paged_fp8_ragged(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_q, scale,
+                                                   causal, window, sinks, softcap, out_fp32)
+    torch.ops.fa_mi355.append_ragged(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin,
+                                     interleaved)
+    torch.ops.fa_mi355.append_paged_ragged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, seqlens_new, q,
+                                           rotary_cos, rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_fp8_ragged(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out, seqlens_new, q,
+                                         rotary_cos, rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_paged_fp8_ragged(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
+                                               seqlens_new, q, rotary_cos, rotary_sin, interleaved)
 """
 from __future__ import annotations
 
@@ -46,7 +63,7 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window and four _ex forms, the
-    four .append ops and their four _rope forms (idempotent)."""
+    four .append ops and their four _rope forms, and the four decode and four append _ragged forms (idempotent)."""
     global _registered
     if _registered:
         return
@@ -176,8 +193,41 @@ def register() -> None:
                                                 out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window,
                                                 sinks=opt(sinks), softcap=softcap)
 
+    # The forms with a query count per sequence: the schema of the _ex op above each with `Tensor? seqlens_q` after `cache_seqlens`.
+    RAGGED = "Tensor? cache_seqlens, Tensor? seqlens_q, float scale, bool causal, int window, Tensor? sinks, float softcap, " \
+             "bool out_fp32) -> Tensor"
+
+    def ragged_kw(q, cache_seqlens, seqlens_q, scale, causal, window, sinks, softcap, out_fp32):
+        return dict(cache_seqlens=opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q),
+                    window=window, sinks=opt(sinks), softcap=softcap, seqlens_q=opt(seqlens_q))
+
+    @torch.library.custom_op("fa_mi355::decode_ragged", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, " + RAGGED)
+    def decode_ragged(q, k_cache, v_cache, *rest):
+        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), **ragged_kw(q, *rest))
+
+    @torch.library.custom_op("fa_mi355::decode_paged_ragged", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, " + RAGGED)
+    def decode_paged_ragged(q, k_pool, v_pool, block_table, *rest):
+        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                            **ragged_kw(q, *rest))
+
+    @torch.library.custom_op("fa_mi355::decode_fp8_ragged", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, " + RAGGED)
+    def decode_fp8_ragged(q, k_cache, v_cache, k_scale, v_scale, *rest):
+        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
+                                          **ragged_kw(q, *rest))
+
+    @torch.library.custom_op("fa_mi355::decode_paged_fp8_ragged", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
+                                    + RAGGED)
+    def decode_paged_fp8_ragged(q, k_pool, v_pool, block_table, k_scale, v_scale, *rest):
+        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
+                                                opt(k_scale), opt(v_scale), **ragged_kw(q, *rest))
+
     for op in (decode, decode_paged, decode_fp8, decode_paged_fp8, decode_window, decode_paged_window, decode_fp8_window,
-               decode_paged_fp8_window, decode_ex, decode_paged_ex, decode_fp8_ex, decode_paged_fp8_ex):
+               decode_paged_fp8_window, decode_ex, decode_paged_ex, decode_fp8_ex, decode_paged_fp8_ex, decode_ragged,
+               decode_paged_ragged, decode_fp8_ragged, decode_paged_fp8_ragged):
         op.register_fake(decode_fake)
 
     # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by
@@ -268,7 +318,44 @@ def register() -> None:
                                         opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream(k_new),
                                         **rope_kw(q, rotary_cos, rotary_sin, interleaved))
 
-    for op in (append_rope, append_paged_rope, append_fp8_rope, append_paged_fp8_rope):
+    # The forms with a token count per sequence: the schema of the _rope op above each with `Tensor? seqlens_new` after `seqlens_out` and
+    # the rotary arguments optional (all three None: no rotation).
+    RAGGED_APPEND = "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, Tensor? seqlens_new, Tensor(d!)? q, Tensor? rotary_cos, " \
+                    "Tensor? rotary_sin, bool interleaved) -> ()"
+
+    def ragged_append_kw(k_new, cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin, interleaved):
+        return dict(cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, stream=stream(k_new), q=q, rotary_cos=opt(rotary_cos),
+                    rotary_sin=opt(rotary_sin), rotary_interleaved=interleaved, seqlens_new=opt(seqlens_new))
+
+    @torch.library.custom_op("fa_mi355::append_ragged", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, " + RAGGED_APPEND)
+    def append_ragged(k_new, v_new, k_cache, v_cache, *rest):
+        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, **ragged_append_kw(k_new, *rest))
+
+    @torch.library.custom_op("fa_mi355::append_paged_ragged", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    + RAGGED_APPEND)
+    def append_paged_ragged(k_new, v_new, k_pool, v_pool, block_table, *rest):
+        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                    **ragged_append_kw(k_new, *rest))
+
+    @torch.library.custom_op("fa_mi355::append_fp8_ragged", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
+                                    "Tensor? v_scale, " + RAGGED_APPEND)
+    def append_fp8_ragged(k_new, v_new, k_cache, v_cache, k_scale, v_scale, *rest):
+        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
+                                  **ragged_append_kw(k_new, *rest))
+
+    @torch.library.custom_op("fa_mi355::append_paged_fp8_ragged", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"),
+                             device_types="cuda",
+                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                                    "Tensor? k_scale, Tensor? v_scale, " + RAGGED_APPEND)
+    def append_paged_fp8_ragged(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, *rest):
+        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
+                                        opt(k_scale), opt(v_scale), **ragged_append_kw(k_new, *rest))
+
+    for op in (append_rope, append_paged_rope, append_fp8_rope, append_paged_fp8_rope, append_ragged, append_paged_ragged,
+               append_fp8_ragged, append_paged_fp8_ragged):
         op.register_fake(lambda *args: None)
 
     _registered = True

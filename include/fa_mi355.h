@@ -284,7 +284,7 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  * contiguous cache of Ncap rows; else pools with num_pages, page_size, max_pages, and Ncap is ignored), kv_dtype (FA_KV_16BIT:
  * K, V elements of in_dtype, k_scale and v_scale must be NULL; FA_KV_FP8_E4M3: one e4m3fn byte per element) and window (0: none).
  * Every field means what the argument of that name means in the flat entries.  `size` must equal sizeof(fa_kvdecode_desc).
- * With sinks == NULL and softcap == 0 the call IS the flat entry the descriptor names: same checks, same kernels, same bits.
+ * With sinks == NULL, softcap == 0 and seqlens_q == NULL the call IS the flat entry the descriptor names: same checks, same kernels, same bits.
  * Terms, for row i of query head hq = hkv*G + g: s_j = scale * q.k_j is the logit of key j (scale * k_scale[hkv] * q.k8_j on an
  * fp8 cache), and [lo_i, c_i) are the keys the row sees under the length clamp, the causal flag and the window, as above.
  * softcap   a host float, baked into a captured call like `window`.  0: off.  > 0 and finite: the logit becomes
@@ -312,8 +312,25 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  * sizing function of the descriptor's form returns (0 for a descriptor that is NULL, of the wrong size or of an unknown kv_dtype).
  * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor, a wrong `size`, an unknown kv_dtype, scales on
  * a 16-bit cache, a bad softcap, and everything the flat entry of the descriptor's form rejects.
+ * seqlens_q   a device pointer to B int32, or NULL.  NULL: every sequence has Nq rows per head, and the call is exactly the one
+ *           described above -- same checks, same kernels, same bits.  Else Nq is the PADDED row count and sequence b has
+ *           n_b = min(max(seqlens_q[b], 0), Nq) LIVE rows per query head, rows i < n_b (a clamp, never a fault); Q, O [B,Hkv*G,Nq,d] and
+ *           lse [B,Hkv*G,Nq] keep their padded layouts.  n_b takes the place of Nq in every limit:
+ *             c_i = max(0, L_b - n_b + 1 + i) with causal (L_b without), lo_i = max(0, L_b - n_b + 1 + i - W), start_b = max(0, L_b - n_b + 1 - W),
+ *           and what is and is not read below the window follows that start_b.  A live row that sees no key behaves as above (O = 0,
+ *           lse = -inf, or the sink logit with sinks).  DEAD rows, i >= n_b, get O = 0 and lse = -inf exactly, with or without sinks;
+ *           their Q rows are never used, may hold NaN bit patterns, and cannot move a live row's bits.  n_b = 0 is an idle slot: every
+ *           row is dead, and none of the sequence's K/V rows, pages or table entries are read.  After fa_kvcache_append_ex with
+ *           seqlens_new pointing at the same vector, row i of sequence b has the causal position L_b(before the append) + i -- its
+ *           rotary position there.  Nothing on the host reads seqlens_q: grid, split count and workspace follow the host shape
+ *           (the padded Nq; span_cap stays valid because n_b <= Nq), and fa_kvcache_decode_workspace_bytes ignores the field.  The
+ *           split count therefore follows the padded G * Nq: a batch padded to a long prefill chunk gives its one-token sequences few
+ *           splits.  With every n_b >= Nq the bits are those of the call without seqlens_q.
+ *           A descriptor whose `size` is offsetof(fa_kvdecode_desc, seqlens_q) -- the structure before this field existed -- is
+ *           accepted and means seqlens_q == NULL; every other wrong size is refused.
  * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the prefill entries (fa_forward*), a tanh other than
- * the one above.  NOT a reference entry point. */
+ * the one above; token-packed (cu_seqlens) layouts, a split count or a window per sequence, explicit position ids, per-sequence
+ * query counts on the prefill entries or on the flat decode entries.  NOT a reference entry point. */
 #define FA_KV_16BIT    0   /* K, V elements are of in_dtype */
 #define FA_KV_FP8_E4M3 1   /* K, V elements are OCP e4m3fn bytes */
 typedef struct fa_kvdecode_desc {
@@ -337,6 +354,7 @@ typedef struct fa_kvdecode_desc {
     void* workspace;
     size_t workspace_bytes;
     void* stream;
+    const int* seqlens_q;      /* device, B int32 live rows per query head, may be NULL (= Nq for all) */
 } fa_kvdecode_desc;
 size_t fa_kvcache_decode_workspace_bytes(const fa_kvdecode_desc* desc);
 int fa_kvcache_decode(const fa_kvdecode_desc* desc);
@@ -449,6 +467,49 @@ int fa_kvcache_append_paged_fp8_rope(const void* Knew, const void* Vnew, void* K
                                      int B, int Hkv, int Nnew, int num_pages, int page_size, int max_pages, int d,
                                      int G, int rot_dim, int max_pos, int interleaved,
                                      int in_dtype, void* stream);
+
+/* KV-cache append by descriptor: the one-call form of the eight append entries above, with a token count per sequence.  Which of
+ * the eight forms a call is follows from the descriptor: block_table (NULL: a contiguous cache of Ncap rows; else pools with
+ * num_pages, page_size, max_pages, and Ncap is ignored), kv_dtype (FA_KV_16BIT: cache elements of `dtype`, k_scale and v_scale must be
+ * NULL; FA_KV_FP8_E4M3: one e4m3fn byte per element) and rope_cos (NULL: no rotation, and Q, Qout and rope_sin must be NULL too; else
+ * the _rope form with Q, Qout, rope_sin, G, rot_dim, max_pos, interleaved).  Every field means what the argument of that name means in
+ * the flat entries; `dtype` is their dtype / in_dtype.  `size` must equal sizeof(fa_kvappend_desc).
+ * With seqlens_new == NULL the call IS the flat entry the descriptor names: same checks, same kernels, same bytes.
+ * seqlens_new  a device pointer to B int32, or NULL.  Nnew is then the PADDED token count (Knew, Vnew [B,Hkv,Nnew,d], Q [B,Hkv*G,Nnew,d]),
+ *           and sequence b appends m_b = min(max(seqlens_new[b], 0), Nnew) tokens (a clamp, never a fault).  Token t < m_b goes to
+ *           p = L_b + t exactly as in the flat entry: the drops at p >= Ncap and at a bad table entry, the fp8 recipe and the pinned rotary
+ *           arithmetic are unchanged.  Token t >= m_b is not written: no address is formed for it and no table entry is read for it, so
+ *           a table slot only padding would reach may name a page the sequence does not own; its Q row reaches Qout with every bit
+ *           kept.  seqlens_out[b] = min(L_b + m_b, Ncap), in place or disjoint as in the flat entries.  seqlens_new must not overlap
+ *           seqlens_out (hipErrorInvalidValue).  Nothing on the host reads seqlens_new; the grid is the flat entry's for the padded Nnew.
+ *           fa_kvcache_decode with seqlens_q pointing at the same vector then gives row i the causal position L_b + i.
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor, a wrong `size`, an unknown kv_dtype, scales on a
+ * 16-bit cache, Q, Qout or rope_sin without rope_cos, the overlap above, and everything the flat entry of the descriptor's form rejects.
+ * Not part of this entry: token-packed (cu_seqlens) sources, explicit position ids, and what the flat entries exclude.  NOT a
+ * reference entry point. */
+typedef struct fa_kvappend_desc {
+    size_t size;               /* sizeof(fa_kvappend_desc) */
+    const void *Knew, *Vnew;   /* device, [B,Hkv,Nnew,d] of `dtype` */
+    void *K, *V;               /* the cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d] */
+    const int* seqlens_k;      /* device, B int32, may be NULL (= 0 for all: every sequence empty) */
+    int* seqlens_out;          /* device, B int32, may be NULL or == seqlens_k */
+    const int* seqlens_new;    /* device, B int32 tokens per sequence, may be NULL (= Nnew for all) */
+    const int* block_table;    /* device, [B,max_pages] int32; NULL: a contiguous cache */
+    const float* k_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const float* v_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const void* Q;             /* rotary only: device, [B,Hkv*G,Nnew,d]; Q and Qout both NULL, identical or disjoint */
+    void* Qout;
+    const float* rope_cos;     /* device, [max_pos,rot_dim/2] fp32; NULL: no rotation */
+    const float* rope_sin;
+    int kv_dtype;              /* FA_KV_16BIT or FA_KV_FP8_E4M3 */
+    int B, Hkv, Nnew, d;
+    int Ncap;                  /* contiguous only */
+    int num_pages, page_size, max_pages;   /* paged only */
+    int G, rot_dim, max_pos, interleaved;  /* rotary only */
+    int dtype;
+    void* stream;
+} fa_kvappend_desc;
+int fa_kvcache_append_ex(const fa_kvappend_desc* desc);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
