@@ -52,6 +52,7 @@ SYMBOLS = (
     "fa_kvcache_decode_workspace_bytes",
     "fa_kvcache_decode",
     "fa_kvcache_append_ex",
+    "fa_merge_states",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -89,6 +90,31 @@ class KvAppendDesc(C.Structure):
         super().__init__(**fields)
         if "size" not in fields:
             self.size = C.sizeof(KvAppendDesc)
+
+
+MERGE_MAX_PARTS = 16
+STATE_F16, STATE_BF16, STATE_F32 = 0, 1, 2
+
+
+class StatePart(C.Structure):
+    """fa_state_part of include/fa_mi355.h: one (O, lse) pair and its two row strides."""
+    _fields_ = [("O", C.c_void_p), ("lse", C.c_void_p), ("stride_b", C.c_longlong), ("stride_h", C.c_longlong)]
+
+
+class MergeDesc(C.Structure):
+    """fa_merge_desc of include/fa_mi355.h, field for field; `size` is filled in.  `parts` takes a sequence of up to MERGE_MAX_PARTS
+    StatePart (or (O, lse, stride_b, stride_h) tuples); the rest stay zero."""
+    _fields_ = [("size", C.c_size_t), ("parts", StatePart * MERGE_MAX_PARTS), ("R", C.c_int), ("B", C.c_int), ("H", C.c_int),
+                ("rows", C.c_int), ("d", C.c_int), ("part_dtype", C.c_int), ("O", C.c_void_p), ("lse", C.c_void_p),
+                ("out_dtype", C.c_int), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        parts = fields.pop("parts", ())
+        super().__init__(**fields)
+        for i, p in enumerate(parts):
+            self.parts[i] = p if isinstance(p, StatePart) else StatePart(*p)
+        if "size" not in fields:
+            self.size = C.sizeof(MergeDesc)
 
 
 class FaError(RuntimeError):
@@ -189,6 +215,9 @@ def lib() -> C.CDLL:
         # the descriptor form of the eight, with seqlens_new
         L.fa_kvcache_append_ex.argtypes = [C.POINTER(KvAppendDesc)]
         L.fa_kvcache_append_ex.restype = C.c_int
+        # the merge of attention states over key ranges
+        L.fa_merge_states.argtypes = [C.POINTER(MergeDesc)]
+        L.fa_merge_states.restype = C.c_int
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

@@ -8,6 +8,8 @@
 #include <stddef.h>
 #include <type_traits>
 
+struct fa_merge_desc;   // include/fa_mi355.h
+
 namespace fa {
 
 // One self-attention forward: Q, K, V, O [BH, N, D] row-major, in_dtype FA_DTYPE_*, out_dtype FA_OUT_*.  The split-KV, debug-stage,
@@ -186,6 +188,8 @@ hipError_t kvcache_append_rope_check(const KvAppendArgs& a, unsigned long long& 
 hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
 // the lengths kernel behind either append kernel (fa_kvcache_append.hip); nothing is launched without a seqlens_out
 hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
+// fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
+hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

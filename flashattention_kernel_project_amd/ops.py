@@ -377,6 +377,135 @@ def fa_forward_kvcache_paged_fp8(q, k_pool, v_pool, block_table, k_scale=None, v
                    window, paged=True, block_table=block_table, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
 
+def _state_dtype(dtype):
+    import torch
+    ids = {torch.float16: capi.STATE_F16, torch.bfloat16: capi.STATE_BF16, torch.float32: capi.STATE_F32}
+    if dtype not in ids:
+        raise ValueError(f"an attention state is float32, float16 or bfloat16 (got {dtype})")
+    return ids[dtype]
+
+
+def _merge_call(parts, B, H, rows, d, part_dtype, out, lse, tensors, stream):
+    """fa_merge_states: parts is a list of (O pointer, lse pointer, stride_b, stride_h), strides in rows; out [B,H,rows,d]
+    contiguous, lse [B,H,rows] fp32 or None."""
+    import torch
+    desc = capi.MergeDesc(parts=parts, R=len(parts), B=B, H=H, rows=rows, d=d, part_dtype=_state_dtype(part_dtype), O=out.data_ptr(),
+                          lse=None if lse is None else lse.data_ptr(), out_dtype=_state_dtype(out.dtype), stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(*tensors)):
+        code = capi.lib().fa_merge_states(desc)
+    capi.check("fa_merge_states", code)
+
+
+def fa_merge_states(outs, lses, out_dtype=None, return_lse: bool = True, stream=None):
+    """Merge R attention states over disjoint key ranges (fa_merge_states): outs a list of R tensors [B,Hq,Nq,d], all float32 or all
+    float16 or all bfloat16, lses a list of R float32 tensors [B,Hq,Nq] -- what R decode calls with return_lse=True return, each
+    over its own keys.  1 <= R <= 16, d in {64,128}, contiguous device tensors on one device.
+    -> (O [B,Hq,Nq,d] of out_dtype, lse [B,Hq,Nq] float32), or O alone with return_lse=False:
+    lse = ln sum_r exp(lse_r), O = sum_r O_r exp(lse_r - lse), evaluated in fp32 against the largest lse_r and rounded once.
+    out_dtype: torch.float32 (None), torch.float16 or torch.bfloat16.
+    A part with lse_r = -inf (a range without a visible key) is neutral and its O row is never used; if every part is -inf the row is
+    O = 0, lse = -inf.  With one part, or one finite part, the result is that part's bits (rounded once if the dtypes differ).
+    Sinks are part of the lse of the range they were passed to: pass `sinks` to exactly one of the decode calls.
+    One kernel, no workspace, nothing read on the host: a captured call follows parts that are rewritten in place."""
+    import torch
+    outs, lses = list(outs), list(lses)
+    if not 1 <= len(outs) <= capi.MERGE_MAX_PARTS or len(lses) != len(outs):
+        raise ValueError(f"outs and lses must be lists of the same length R, 1 <= R <= {capi.MERGE_MAX_PARTS}")
+    first = outs[0]
+    if not isinstance(first, torch.Tensor) or first.dim() != 4:
+        raise ValueError("every out must be a tensor [B,Hq,Nq,d]")
+    B, Hq, Nq, d = first.shape
+    states = (torch.float32, torch.float16, torch.bfloat16)
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in states:
+        raise ValueError("out_dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    parts = []
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        if not isinstance(o, torch.Tensor) or o.shape != first.shape or o.dtype != first.dtype:
+            raise ValueError(f"outs[{i}] must have the shape and dtype of outs[0] ({tuple(first.shape)}, {first.dtype})")
+        if not isinstance(l, torch.Tensor) or l.shape != first.shape[:3]:
+            raise ValueError(f"lses[{i}] must be a float32 tensor [B,Hq,Nq] = {tuple(first.shape[:3])}")
+        parts.append((_dev_ptr(o, f"outs[{i}]", states), _dev_ptr(l, f"lses[{i}]", (torch.float32,)), Hq * Nq, Nq))
+    dev = _one_device(*outs, *lses)
+    out = torch.empty(first.shape, dtype=out_dtype, device=dev)
+    lse = torch.empty(first.shape[:3], dtype=torch.float32, device=dev) if return_lse else None
+    _merge_call(parts, B, Hq, Nq, d, first.dtype, out, lse, outs + lses, stream)
+    return (out, lse) if return_lse else out
+
+
+def fa_forward_kvcache_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len=None, cache_seqlens=None, block_table=None,
+                                     k_scale=None, v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None,
+                                     return_lse: bool = False, sinks=None, softcap: float = 0.0, stream=None):
+    """Decode for B sequences that share one prefix: sequence b holds the keys of the prefix [0, P) followed by its own [0, L_b).
+    q [B,Hq,Nq,d] fp16/bf16; k_prefix, v_prefix [1,Hkv,Pcap,d], one copy for the whole batch; the suffix is k_cache, v_cache
+    [B,Hkv,Ncap,d] or, with block_table [B,max_pages], pools [num_pages,Hkv,page_size,d].  Suffix and prefix have ONE element type:
+    q's 16-bit type, or torch.float8_e4m3fn with k_scale, v_scale ([Hkv] float32 or None) that apply to both.
+    prefix_len: int32 device tensor [1], P = its value clamped to [0, Pcap], or None (P = Pcap).  cache_seqlens: as in
+    fa_forward_kvcache.  Both are read on the device only.
+    causal: the mask is aligned to the end of the suffix, as in fa_forward_kvcache -- row i sees the suffix keys
+    [0, L_b - Nq + 1 + i) -- and every row sees the whole prefix.  sinks, softcap, scale, out_dtype, return_lse: as there; the sinks
+    count once.
+    The batch is folded into the rows of ONE stream over the prefix, as the G heads of a group are folded everywhere in the decode
+    family, so the prefix K/V is read once and not B times.  Three launches and one small copy: q permuted to [1,Hkv*(B*G),Nq,d] (the
+    copy) and fa_forward_kvcache on the prefix with B = 1 and G' = B*G; the suffix's own decode entry; fa_merge_states over the two
+    (fp32) results, the prefix part read in place through its [Hkv,B,G*Nq] strides.  Workspaces are allocated here, sized by
+    kvcache_workspace_bytes(1, Hkv, B*G, Nq, Pcap, d) and the suffix form's function.  The whole call can be captured into one graph
+    (after a warm-up call), and the replay follows prefix_len, cache_seqlens, block_table, the scales and the sinks.
+    With P = 0 the result is the plain entry's, bit for bit; a sequence with L_b = 0 gets the prefix part's rows.
+    A short prefix does not pay for the copy and the two extra launches (DESIGN.md 7.11 has the measured crossover): below it,
+    keep the prefix in every sequence's own cache and call fa_forward_kvcache.
+    `window` and `seqlens_q` are NOT keywords of this function: a window would cross the boundary between prefix and suffix, and a
+    dead row's q would reach the prefix decode.  Not supported either: a prefix of another element type than the suffix, a paged
+    prefix, more than one prefix level (fa_merge_states takes 16 parts; compose them yourself).
+    stream: a torch.cuda.Stream, or None for the current one (the permute copy and the allocations are torch's)."""
+    import contextlib
+    import torch
+    paged = block_table is not None
+    dts = (torch.float16, torch.bfloat16)
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3]:
+        raise ValueError("q must be [B,Hq,Nq,d] and k_cache, v_cache " + ("[num_pages,Hkv,page_size,d]" if paged else "[B,Hkv,Ncap,d]"))
+    B, Hq, Nq, d = q.shape
+    Hkv = k_cache.shape[1]
+    if k_prefix.dim() != 4 or v_prefix.shape != k_prefix.shape or k_prefix.shape[0] != 1 or k_prefix.shape[1] != Hkv \
+            or k_prefix.shape[3] != d or k_prefix.shape[2] < 1:
+        raise ValueError(f"k_prefix, v_prefix must be [1,Hkv,Pcap,d] = [1,{Hkv},Pcap,{d}]: one prefix for the whole batch")
+    if k_prefix.dtype != k_cache.dtype or v_prefix.dtype != v_cache.dtype:
+        raise ValueError(f"the prefix must have the suffix's element type ({k_cache.dtype}; got {k_prefix.dtype}, {v_prefix.dtype})")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("k_scale, v_scale belong to an fp8 cache (torch.float8_e4m3fn)")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a multiple of the number of K/V heads")
+    G = Hq // Hkv
+    if prefix_len is not None and (not isinstance(prefix_len, torch.Tensor) or prefix_len.dim() != 1 or prefix_len.shape[0] != 1):
+        raise ValueError("prefix_len must be an int32 device tensor of shape [1]")
+    _dev_ptr(q, "q", dts)
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    if isinstance(stream, torch.cuda.Stream):
+        on_stream = torch.cuda.stream(stream)
+    elif stream is None:
+        on_stream = contextlib.nullcontext()
+    else:
+        raise ValueError("stream must be a torch.cuda.Stream or None: the permute copy is torch's")
+    scales = (k_scale, v_scale) if fp8 else None
+    with on_stream:
+        # row (hkv, b*G*Nq + g*Nq + i) of the folded stream is row (b, hkv*G + g, i) of q
+        qp = q.view(B, Hkv, G, Nq, d).permute(1, 0, 2, 3, 4).reshape(1, Hkv * B * G, Nq, d).contiguous()
+        o_p, lse_p = _decode(qp, k_prefix, v_prefix, "k_prefix", "v_prefix", prefix_len, False, scale, torch.float32, True, None, stream,
+                             0, scales=scales, softcap=softcap)
+        o_s, lse_s = _decode(q, k_cache, v_cache, "k_pool" if paged else "k_cache", "v_pool" if paged else "v_cache", cache_seqlens,
+                             causal, scale, torch.float32, True, None, stream, 0, paged=paged, block_table=block_table, scales=scales,
+                             sinks=sinks, softcap=softcap)
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+        lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+        rows = G * Nq
+        parts = [(o_p.data_ptr(), lse_p.data_ptr(), rows, B * rows), (o_s.data_ptr(), lse_s.data_ptr(), Hkv * rows, rows)]
+        _merge_call(parts, B, Hkv, rows, d, torch.float32, out, lse, (o_p, o_s), stream)
+    return (out, lse) if return_lse else out
+
+
 FP8_E4M3_MAX = 448.0   # largest finite e4m3fn value
 
 

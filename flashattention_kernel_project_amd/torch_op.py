@@ -53,6 +53,11 @@ eager fallback.  Registered on first use:
                                          rotary_cos, rotary_sin, interleaved)
     torch.ops.fa_mi355.append_paged_fp8_ragged(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
                                                seqlens_new, q, rotary_cos, rotary_sin, interleaved)
+    # the merge of R attention states, stacked [R,B,Hq,Nq,d] and [R,B,Hq,Nq] (ops.fa_merge_states), and shared-prefix decode on a
+    # contiguous 16-bit suffix (ops.fa_forward_kvcache_shared_prefix)
+    o, lse = torch.ops.fa_mi355.merge_states(outs, lses, out_f32)
+    o = torch.ops.fa_mi355.decode_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len, cache_seqlens, scale, causal, sinks,
+                                                softcap, out_fp32)
 """
 from __future__ import annotations
 
@@ -63,7 +68,8 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window and four _ex forms, the
-    four .append ops and their four _rope forms, and the four decode and four append _ragged forms (idempotent)."""
+    four .append ops and their four _rope forms, the four decode and four append _ragged forms, .merge_states and
+    .decode_shared_prefix (idempotent)."""
     global _registered
     if _registered:
         return
@@ -357,6 +363,31 @@ def register() -> None:
     for op in (append_rope, append_paged_rope, append_fp8_rope, append_paged_fp8_rope, append_ragged, append_paged_ragged,
                append_fp8_ragged, append_paged_fp8_ragged):
         op.register_fake(lambda *args: None)
+
+    # The merge of attention states over key ranges (ops.fa_merge_states) on stacked parts, and shared-prefix decode on a contiguous
+    # 16-bit suffix (ops.fa_forward_kvcache_shared_prefix; the paged and fp8 forms are the front end's).
+    @torch.library.custom_op("fa_mi355::merge_states", mutates_args=(), device_types="cuda",
+                             schema="(Tensor outs, Tensor lses, bool out_f32) -> (Tensor, Tensor)")
+    def merge_states(outs, lses, out_f32):
+        outs, lses = outs.contiguous(), lses.contiguous()
+        return ops.fa_merge_states(list(outs.unbind(0)), list(lses.unbind(0)), out_dtype=out_dtype(outs, out_f32), stream=stream(outs))
+
+    @merge_states.register_fake
+    def _(outs, lses, out_f32):
+        return outs.new_empty(outs.shape[1:], dtype=out_dtype(outs, out_f32)), lses.new_empty(lses.shape[1:], dtype=torch.float32)
+
+    @torch.library.custom_op("fa_mi355::decode_shared_prefix", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k_prefix, Tensor v_prefix, Tensor k_cache, Tensor v_cache, Tensor? prefix_len, "
+                                    "Tensor? cache_seqlens, float scale, bool causal, Tensor? sinks, float softcap, bool out_fp32) "
+                                    "-> Tensor")
+    def decode_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len, cache_seqlens, scale, causal, sinks, softcap,
+                             out_fp32):
+        return ops.fa_forward_kvcache_shared_prefix(
+            q.contiguous(), k_prefix.contiguous(), v_prefix.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
+            prefix_len=opt(prefix_len), cache_seqlens=opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
+            sinks=opt(sinks), softcap=softcap, stream=stream(q))
+
+    decode_shared_prefix.register_fake(decode_fake)
 
     _registered = True
 

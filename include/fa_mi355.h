@@ -511,6 +511,65 @@ typedef struct fa_kvappend_desc {
 } fa_kvappend_desc;
 int fa_kvcache_append_ex(const fa_kvappend_desc* desc);
 
+/* Merge of attention states over disjoint key ranges: the rule the decode entries above promise (fa_forward_kvcache),
+ *   lse = ln sum_r exp(lse_r),   O = sum_r O_r exp(lse_r - lse),
+ * applied by ONE kernel to R parts, each an (O_r, lse_r) pair as a decode entry returns it with lse.  A part is addressed by rows:
+ * row (b, h, r) of part p is x = b * stride_b + h * stride_h + r with r in [0, rows), its O row is the d elements at O + x * d and
+ * its lse is lse[x].  The two strides let one launch read a part laid out [B, H, rows] (what a decode entry returns: stride_b =
+ * H * rows, stride_h = rows) next to a part laid out [H, B, rows] (what a decode returns whose BATCH was folded into the rows of one
+ * stream over a shared prefix: stride_h = B * rows, stride_b = rows), or a padded one, without a permute copy.  Bytes between the
+ * rows a part names are never read.  H counts K/V heads and rows = G * Nq, so a part is exactly a decode entry's O and lse.
+ * The parts travel in the kernel's argument block (FA_MERGE_MAX_PARTS * sizeof(fa_state_part) = 512 bytes): `parts` is HOST data that
+ * is copied at the call, there is no device allocation, no host-to-device copy and no workspace, the launch is a single kernel that a
+ * HIP graph captures, and nothing on the host reads device data.  The grid follows (B, H, rows) only.
+ * Arithmetic, in fp32, each part's O widened exactly: M = max_r lse_r (natural-log units), w_r = exp(lse_r - M) on the hardware
+ * exponential, L = sum_r w_r, O = (sum_r w_r O_r) / L with a correctly rounded division, lse = M + ln L; O is rounded ONCE, to
+ * out_dtype.  The part with the largest lse has weight exactly 1.  Hence:
+ *   R = 1            O and lse are the part's bits when part_dtype == out_dtype, else O is the one rounding of the part's bits to
+ *                    out_dtype (the sign of a zero included)
+ *   one finite part  among parts with lse_r = -inf: it comes through in the same way, exactly
+ *   lse_r = -inf     the part is neutral: its O row is selected away, never multiplied -- it may hold NaN bit patterns (the O row of
+ *                    a row without a key is 0 in the decode entries, but nothing here relies on that) and cannot move the result
+ *   all -inf         O = +0 and lse = -inf exactly, never NaN
+ *   lse_r = +inf or NaN   a meaningless row, never an out-of-range access: no address depends on an lse
+ * Sinks are not an argument: a sink is part of the lse of the range it was passed to, and the caller passes `sinks` to exactly ONE
+ * of the ranges (fa_kvcache_decode).  The output must not alias a part; this is not checked.
+ * hipErrorInvalidValue, before the device is touched: a NULL descriptor or a wrong `size`; R outside [1, FA_MERGE_MAX_PARTS]; a null
+ * O, or a null O or lse in any of the first R parts; B, H or rows <= 0; d not in {64,128}; a part_dtype or out_dtype that is no
+ * FA_STATE_*; a negative stride in any of the first R parts; B * H * rows of 2^26 or more (one wave per row: the grid); an O, or a
+ * part's O, that is not aligned to four of its elements (16 bytes for fp32, 8 for the 16-bit types).
+ * Shared-prefix decode is a composition of entries above and this one (ops.fa_forward_kvcache_shared_prefix does it): B sequences
+ * that share the keys [0, P) of one prefix cache [1, Hkv, Pcap, d] and own a suffix each.  (1) Q [B, Hkv*G, Nq, d] is permuted to
+ * [1, Hkv*(B*G), Nq, d] and fa_forward_kvcache runs on the prefix with B = 1, G' = B*G, seqlens_k = the prefix length, causal = 0,
+ * no sinks, fp32 O and lse: the batch is folded into the rows of one stream, so the prefix is read once, not B times.  (2) The
+ * decode entry of the suffix's form runs as usual (its causal flag, its sinks), fp32 O and lse.  (3) fa_merge_states with H = Hkv,
+ * rows = G*Nq: the prefix part has stride_h = B*G*Nq, stride_b = G*Nq, the suffix part stride_b = Hkv*G*Nq, stride_h = G*Nq.  A
+ * causal mask is aligned to the end of the suffix, so every row sees the whole prefix.  A window or seqlens_q cannot be composed
+ * this way (a window would cross the boundary; a dead row's q would reach the prefix decode).
+ * Not part of this entry: parts of different element types in one call, more than FA_MERGE_MAX_PARTS parts (merge twice: the
+ * rule is associative), a weight per part other than its lse, any collective.  NOT a reference entry point. */
+#define FA_MERGE_MAX_PARTS 16
+#define FA_STATE_F16  0   /* as in_dtype elsewhere */
+#define FA_STATE_BF16 1
+#define FA_STATE_F32  2
+typedef struct fa_state_part {
+    const void*  O;          /* device; row x of the part is d elements at O + x*d */
+    const float* lse;        /* device; natural log, one per row, same row index x */
+    long long stride_b, stride_h;   /* in ROWS: row (b, h, r) is x = b*stride_b + h*stride_h + r, r in [0, rows) */
+} fa_state_part;
+typedef struct fa_merge_desc {
+    size_t size;             /* sizeof(fa_merge_desc) */
+    fa_state_part parts[FA_MERGE_MAX_PARTS];   /* HOST data, copied into the kernel's arguments at the call */
+    int R;                   /* 1 .. FA_MERGE_MAX_PARTS */
+    int B, H, rows, d;       /* H = K/V heads, rows = G*Nq rows per K/V head; d in {64,128} */
+    int part_dtype;          /* one FA_STATE_* for every part's O */
+    void* O;                 /* [B, H, rows, d] contiguous, of out_dtype */
+    float* lse;              /* [B, H, rows] fp32, may be NULL */
+    int out_dtype;           /* FA_STATE_* */
+    void* stream;
+} fa_merge_desc;
+int fa_merge_states(const fa_merge_desc* desc);
+
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
  * the same LDS images, fragment loads and accumulator maps as the product kernels.  d in {64,128}.
