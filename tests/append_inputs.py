@@ -8,21 +8,16 @@ token.  Everything else in the cache or pool stays as it was.
 """
 import numpy as np
 
+import common_inputs as cm
 import fp8_inputs as f8
-
-GARBAGE = (-1, 1 << 30)   # what a table holds for pages no kept token reaches
 
 # the common shape of the GPU tier: empty, mid-page, nearly full, full, clamped up, clamped down
 SHAPE = dict(B=6, Hkv=2, Ncap=128)
 LENS = (0, 17, 123, 128, -3, 1000)
 
 
-def clamp(L, ncap):
-    return min(max(int(L), 0), ncap)
-
-
 def start_lens(lens, B, ncap):
-    return [0] * B if lens is None else [clamp(L, ncap) for L in lens]
+    return [0] * B if lens is None else [cm.clamp(L, ncap) for L in lens]
 
 
 def lens_after(lens, B, nnew, ncap):
@@ -73,7 +68,7 @@ def make_table(lens, B, ncap, nnew, ps, seed, spare=3):
     for b in range(B):
         for pi in range(max_pages):
             if pi * ps >= after[b]:
-                table[b, pi] = GARBAGE[pi % 2]
+                table[b, pi] = cm.GARBAGE[pi % 2]
             else:
                 table[b, pi] = perm[nxt]
                 nxt += 1

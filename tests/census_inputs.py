@@ -28,13 +28,11 @@ import functools
 
 import numpy as np
 
+import common_inputs as cm
 import decode_inputs as di
 import fallback_inputs as fi
-import window_inputs as wi
 
 F16, BF16 = 0, 1
-TILE = di.TILE
-P_EPS = di.P_EPS
 P_BITS = {F16: 11, BF16: 8}       # significant bits of a weight packed to the input format
 MARGIN = 0.25                     # decision margin between neighbouring integers (not a measured tolerance)
 CODINGS = ("residue", "tile")
@@ -51,7 +49,7 @@ def columns(n, d, coding):
     """the column key j marks: [n] int"""
     j = np.arange(n)
     assert coding in CODINGS
-    return j % d if coding == "residue" else (j // TILE) % d
+    return j % d if coding == "residue" else (j // cm.TILE) % d
 
 
 def v_coded(m, n, d, coding):
@@ -81,7 +79,7 @@ def expected_sums(m, lo, c, n, d, coding):
 def expected_sums_torch(torch, m, lo, c, n, d, coding, device):
     """expected_sums in torch float64 on `device` (the full-size shapes): m [bh], lo and c [rows] int64 tensors or lists"""
     j = torch.arange(n, device=device)
-    col = j % d if coding == "residue" else (j // TILE) % d
+    col = j % d if coding == "residue" else (j // cm.TILE) % d
     unit = torch.zeros((n + 1, d), dtype=torch.float64, device=device)
     unit[j + 1, col] = 1.0
     P = torch.cumsum(unit, 0)
@@ -92,7 +90,7 @@ def expected_sums_torch(torch, m, lo, c, n, d, coding, device):
 
 def v_coded_torch(torch, m, n, d, coding, dtype, device):
     j = torch.arange(n, device=device)
-    col = j % d if coding == "residue" else (j // TILE) % d
+    col = j % d if coding == "residue" else (j // cm.TILE) % d
     v = torch.zeros((len(m), n, d), dtype=dtype, device=device)
     v[:, j, col] = torch.as_tensor(m, dtype=torch.float32, device=device).to(dtype)[:, None]
     return v
@@ -110,15 +108,12 @@ def prefill_limits(n, causal):
 
 
 def decode_limits(lens, B, Hkv, G, Nq, Ncap, causal, W=0):
-    """the cache entries: per query head [B * Hkv * G, Nq] lower and upper limits (di.limits, wi.lows; a bad length is clamped)"""
+    """the cache entries: per query head [B * Hkv * G, Nq] lower and upper limits (cm.row_limits; a bad length is clamped)"""
     lo = np.zeros((B * Hkv * G, Nq), np.int64)
     c = np.zeros((B * Hkv * G, Nq), np.int64)
     for b in range(B):
-        L = di.clamp(lens[b], Ncap)
         hs = slice(b * Hkv * G, (b + 1) * Hkv * G)
-        c[hs] = di.limits(L, Nq, causal)
-        lo[hs] = wi.lows(L, Nq, W)
-    lo = np.minimum(lo, c)
+        lo[hs], c[hs], _ = cm.row_limits(cm.clamp(lens[b], Ncap), Nq, Nq, causal, W)
     return lo, c
 
 
@@ -167,12 +162,12 @@ def z_exact(fmt, s_max):
 
 def r_exact(fmt, count_max):
     """family R: a sum of unrounded weights against packed ones in P.V"""
-    return 4 * P_EPS[fmt] * count_max <= 0.125
+    return 4 * cm.P_EPS[fmt] * count_max <= 0.125
 
 
 def out16_exact(fmt, count_max):
     """16-bit output: O itself is rounded to the format"""
-    return 2 * P_EPS[fmt] * count_max <= 0.125
+    return 2 * cm.P_EPS[fmt] * count_max <= 0.125
 
 
 # ---- family Z ---------------------------------------------------------------------------------------------------------------------------
@@ -280,7 +275,7 @@ def assert_regimes(case, d, fmt, causal, wave_rows):
     s = scores(case)
     n = s.shape[1]
     # the scores lie where they were built, up to the rounding of Q and K to the format: 2 P_EPS on every product of the row
-    slack = 2 * P_EPS[fmt] * np.einsum("hid,hd->hi", np.abs(case["q"]).astype(np.float64), np.abs(case["k"][:, 0]).astype(np.float64)) \
+    slack = 2 * cm.P_EPS[fmt] * np.einsum("hid,hd->hi", np.abs(case["q"]).astype(np.float64), np.abs(case["k"][:, 0]).astype(np.float64)) \
         * (LOG2E / np.sqrt(d))
     assert (np.abs(s - case["targets"]) <= slack + 1e-6).all(), np.abs(s - case["targets"]).max()
     folded_q = np.abs(case["q"]).max() * LOG2E / np.sqrt(d)

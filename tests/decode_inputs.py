@@ -5,44 +5,17 @@ fixture (tests/conftest.py); nothing here touches a GPU.
 
 Method of tests/test_gpu_kvcache.py and tests/test_gpu_kvcache_paged.py: inputs from oracle.make_qkv, expected O from
 oracle.forward_cross on the keys a row sees (zeros for a row that sees none), expected log-sum-exps from float64 numpy on the same
-16-bit-rounded inputs.  What is new here is the `scale` argument and the clamp of a bad length: the reference of a length outside
-[0, Ncap] is the one of min(max(L, 0), Ncap).
+16-bit-rounded inputs.  The bounds, the row limits, the references, the poison and the page scatter are tests/common_inputs.py's;
+here are the cases, and the host's and the kernel's split arithmetic restated.
 """
 import functools
 
 import numpy as np
 
+import common_inputs as cm
 import fallback_inputs as fi
 
-# The project's bounds.  Copies: tests/test_gpu_parity.py (the origin), tests/test_gpu_kvcache.py, tests/test_gpu_kvcache_paged.py and
-# tests/test_gpu_fallback_paths.py define the same values; a change to the bounds has to be made in all of them.
-MAX_ABS = 1e-2                          # the project's north-star tolerance (tests/test_gpu_parity.py)
-REL_L2 = {0: 2e-3, 1: 1.2e-2}           # fp16 / bf16 inputs
-P_EPS = {0: 2.0 ** -11, 1: 2.0 ** -8}   # largest relative rounding error of one weight in the format P is packed to
-NAN16 = 0x7FFF                          # a NaN in fp16 and in bf16
-GARBAGE = (-1, 1 << 30)                 # what a table holds past a sequence's last live page
-INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
-TILE = 64                               # kBlockN
-ROWS = 128                              # split::kRows, query rows per workgroup
-FMT_NAME = {0: "fp16", 1: "bf16"}
-
-
-def peaked_tol(fmt, vmax, kernels=1):
-    """tests/test_gpu_parity.py::_peaked_tol: the north-star bar plus what the 16-bit format of P imposes on a peaked row."""
-    return MAX_ABS + kernels * float(vmax) * P_EPS[fmt]
-
-
 # ---- the arithmetic of the host and of the kernel, restated ---------------------------------------------------------------------
-def clamp(L, ncap):
-    """the kernel's min(max(L, 0), Ncap)"""
-    return min(max(int(L), 0), ncap)
-
-
-def limits(L, nq, causal):
-    """c_i: the number of keys row i of a head sees (the mask is aligned to the end of the sequence)."""
-    return [max(0, L - nq + 1 + i) if causal else L for i in range(nq)]
-
-
 def splits_of(ws_bytes, bh, rows, d):
     """the split count S a workspace size stands for: S * BH * rows rows of d + 2 floats (0 bytes: one pass)"""
     row = bh * rows * (d + 2) * 4
@@ -52,7 +25,7 @@ def splits_of(ws_bytes, bh, rows, d):
 
 def chunk_of(L, S):
     """keys per split of a sequence of L keys: its tiles dealt out to S splits"""
-    return -(-(-(-L // TILE)) // S) * TILE
+    return -(-(-(-L // cm.TILE)) // S) * cm.TILE
 
 
 def live_splits(L, S):
@@ -76,99 +49,6 @@ def inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed):
     for a in (q, k, v, qb, kb, vb):
         a.setflags(write=False)
     return (q, k, v), (qb, kb, vb)
-
-
-def scatter(kb, vb, lens, B, Hkv, ps, seed, spare=3):
-    """K and V encodings [B*Hkv, Ncap, d] -> (K pool, V pool [num_pages, Hkv, ps, d] uint16, table [B, max_pages] int32).
-    Pages are dealt out by a seeded permutation of a pool with `spare` pages more than B * max_pages.  Every page no table names
-    and every row at or past a (clamped) length holds NaN; every table entry past the last live page holds garbage.  A sequence
-    whose raw length exceeds the capacity is full: all its entries are live and all its rows valid."""
-    Ncap, d = kb.shape[1], kb.shape[2]
-    max_pages = Ncap // ps
-    assert max_pages * ps == Ncap
-    num_pages = B * max_pages + spare
-    perm = np.random.default_rng(seed).permutation(num_pages)
-    pools = [np.full((num_pages, Hkv, ps, d), NAN16, np.uint16) for _ in range(2)]
-    table = np.empty((B, max_pages), np.int32)
-    nxt = 0
-    for b in range(B):
-        L = clamp(lens[b], Ncap)
-        for pi in range(max_pages):
-            if pi >= live_pages(L, ps):
-                table[b, pi] = GARBAGE[pi % 2]
-                continue
-            page = int(perm[nxt])
-            nxt += 1
-            table[b, pi] = page
-            n = min(ps, L - pi * ps)   # rows of the page below the length; the rest stay NaN
-            for pool, src in zip(pools, (kb, vb)):
-                pool[page, :, :n] = src[b * Hkv:(b + 1) * Hkv, pi * ps:pi * ps + n]
-    return pools[0], pools[1], table
-
-
-def poisoned(bits, lens, B, Hkv):
-    """[B*Hkv, Ncap, d] encodings -> cache [B, Hkv, Ncap, d] with NaN in every row at and past the sequence's (clamped) length"""
-    bits = bits.reshape(B, Hkv, bits.shape[1], bits.shape[2]).copy()
-    for b in range(B):
-        bits[b, :, clamp(lens[b], bits.shape[2]):] = NAN16
-    return bits
-
-
-def expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal, scale=None):
-    """q [B*Hkv*G, Nq, d], k/v [B*Hkv, Ncap, d] fp32 (16-bit-rounded) -> (O [B*Hq, Nq, d] fp32, lse [B*Hq, Nq] float64).
-    O from oracle.forward_cross (float64 accumulators) on the keys a row sees, lse from float64 numpy; a row without a key is
-    zeros and -inf.  A length outside [0, Ncap] counts as the clamped one."""
-    Hq, d, Ncap = Hkv * G, q.shape[2], k.shape[1]
-    out = np.zeros(q.shape, np.float32)
-    lse = np.full(q.shape[:2], -np.inf, np.float64)
-    sc = 1.0 / np.sqrt(d) if scale is None else float(scale)
-    for b in range(B):
-        qs = slice(b * Hq, (b + 1) * Hq)
-        kb, vb = (np.repeat(x[b * Hkv:(b + 1) * Hkv], G, axis=0) for x in (k, v))   # K/V head of every query head
-        lim = limits(clamp(lens[b], Ncap), Nq, causal)
-        for c in sorted(set(lim)):
-            if c == 0:
-                continue
-            rows = [i for i in range(Nq) if lim[i] == c]
-            qr = np.ascontiguousarray(q[qs][:, rows])
-            out[qs, rows] = oracle.forward_cross(qr, np.ascontiguousarray(kb[:, :c]), np.ascontiguousarray(vb[:, :c]), scale=sc,
-                                                 accum=1, nthreads=8)
-            s = np.einsum("hid,hjd->hij", qr.astype(np.float64), kb[:, :c].astype(np.float64)) * sc
-            m = s.max(-1)
-            lse[qs, rows] = m + np.log(np.exp(s - m[..., None]).sum(-1))
-    return out, lse
-
-
-def expected_f64(q, k, v, lens, B, Hkv, G, Nq, causal, scale=None):
-    """expected() without the oracle: softmax(q k^T scale) v in float64 numpy.  The CPU tier holds the oracle's O against it."""
-    Hq, d, Ncap = Hkv * G, q.shape[2], k.shape[1]
-    out = np.zeros(q.shape, np.float64)
-    sc = 1.0 / np.sqrt(d) if scale is None else float(scale)
-    for b in range(B):
-        L = clamp(lens[b], Ncap)
-        lim = limits(L, Nq, causal)
-        for h in range(Hq):
-            kk, vv = (x[b * Hkv + h // G, :L].astype(np.float64) for x in (k, v))
-            s = (q[b * Hq + h].astype(np.float64) @ kk.T) * sc
-            for i, c in enumerate(lim):
-                if c:
-                    p = np.exp(s[i, :c] - s[i, :c].max())
-                    out[b * Hq + h, i] = (p / p.sum()) @ vv[:c]
-    return out
-
-
-def uniform_expected(v, lens, B, Hkv, G, Nq, causal):
-    """what scale 0 must give: every visible key weighs the same -- O is the mean of the visible V rows, lse = ln(their number)"""
-    Hq, Ncap = Hkv * G, v.shape[1]
-    out = np.zeros((B * Hq, Nq, v.shape[2]), np.float64)
-    lse = np.full((B * Hq, Nq), -np.inf, np.float64)
-    for b in range(B):
-        for i, c in enumerate(limits(clamp(lens[b], Ncap), Nq, causal)):
-            if c:
-                for h in range(Hq):
-                    out[b * Hq + h, i] = v[b * Hkv + h // G, :c].astype(np.float64).mean(0)
-                lse[b * Hq:(b + 1) * Hq, i] = np.log(c)
-    return out, lse
 
 
 # ---- A. more than 64 splits -----------------------------------------------------------------------------------------------------
@@ -235,7 +115,7 @@ C_SHAPE = dict(B=48, Hkv=1, G=2, Nq=3, Ncap=1024)
 C_SPLITS = 4
 C_PAGES = (16, 256)
 C_FIXED = ((0, 1, 2, 15, 16, 17) + tuple(64 * k + e for k in range(1, 6) for e in (-1, 0, 1))
-           + (511, 512, 513, 767, 768, 769, 1023, 1024) + (-1, INT_MIN, 1025, INT_MAX))
+           + (511, 512, 513, 767, 768, 769, 1023, 1024) + (-1, cm.INT_MIN, 1025, cm.INT_MAX))
 
 
 def c_lens():
@@ -249,10 +129,10 @@ def length_categories(lens, ncap, S, pages):
     edge = {0: "at", 1: "above"}
     for raw in lens:
         if raw < 0:
-            cats.add("clamped up" + (" from INT_MIN" if raw == INT_MIN else ""))
+            cats.add("clamped up" + (" from INT_MIN" if raw == cm.INT_MIN else ""))
             continue
         if raw > ncap:
-            cats.add("clamped down" + (" from INT_MAX" if raw == INT_MAX else ""))
+            cats.add("clamped down" + (" from INT_MAX" if raw == cm.INT_MAX else ""))
             continue
         L = raw
         if L == 0:
@@ -260,7 +140,7 @@ def length_categories(lens, ncap, S, pages):
             continue
         if live_splits(L, S) < S:
             cats.add("empty split")
-        for name, unit in [("tile", TILE), ("chunk", chunk_of(L, S))] + [(f"page{ps}", ps) for ps in pages]:
+        for name, unit in [("tile", cm.TILE), ("chunk", chunk_of(L, S))] + [(f"page{ps}", ps) for ps in pages]:
             if L % unit in edge and (L > unit or L % unit == 0):
                 cats.add(f"{edge[L % unit]} {name} edge")
             if L % unit == unit - 1:

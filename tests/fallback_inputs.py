@@ -14,6 +14,8 @@ import functools
 
 import numpy as np
 
+import common_inputs as cm
+
 LOG2E = 1.4426950408889634
 LN2 = float(np.log(2.0))
 F16, BF16 = 0, 1
@@ -256,11 +258,6 @@ def kvcache_case(oracle, d, fmt):
     return dict(q=q, k=k, v=v, bits=bits, spikes=spikes, shifted=((4, -KV_SHIFT), (5, KV_SHIFT)))
 
 
-def kv_limits(L, Nq, causal):
-    """c_i: the number of keys row i of a head sees (the mask is aligned to the end of the sequence)."""
-    return [max(0, L - Nq + 1 + i) if causal else L for i in range(Nq)]
-
-
 # ---- the forcing conditions: asserted by tests/test_fallback_inputs.py and again by every GPU test that uses the input -------
 def fails(lift, fmt):
     """a lift that the exact optimistic pass cannot survive: fp16 from 21 (20 + a margin), bf16 past 2^128 or inside the
@@ -386,13 +383,13 @@ def assert_kvcache_case(case, causal):
     G, Nq = KV_SHAPE["G"], KV_SHAPE["Nq"]
     for (h, row, seq, key, lift) in case["spikes"]:
         L = KV_LENS[seq]
-        c = kv_limits(L, Nq, causal)[row]
+        c = cm.row_limits(L, Nq, Nq, causal)[1][row]
         assert key < c, "the spiked key is visible to its row"
         s = scores_log2(q[h:h + 1], k[seq:seq + 1, :c], 0)[row]
         assert s.argmax() == key and abs(s[key] - np.delete(s, key).max() - lift) < 1.0, (h, row, s[key] - np.delete(s, key).max())
     # sequence 0 under the mask: keys 64 and 65 are seen by the last rows only
-    assert [c > 64 for c in kv_limits(KV_LENS[0], Nq, True)] == [False, False, False, True, True]
-    assert [c > 65 for c in kv_limits(KV_LENS[0], Nq, True)] == [False, False, False, False, True]
+    assert [c > 64 for c in cm.row_limits(KV_LENS[0], Nq, Nq, True)[1]] == [False, False, False, True, True]
+    assert [c > 65 for c in cm.row_limits(KV_LENS[0], Nq, Nq, True)[1]] == [False, False, False, False, True]
     # the full sequence's spike lies behind the cut of the two-range merge, in a late part of the keys
     assert case["spikes"][2][3] >= max(KV_CUT, KV_LENS[1] * 3 // 4)
     for (h, shift) in case["shifted"]:

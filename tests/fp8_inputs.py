@@ -1,6 +1,7 @@
 """Inputs for the fp8 KV-cache decode tests (tests/test_gpu_kvcache_fp8.py, tests/test_kvcache_fp8_host.py): the OCP e4m3fn format
 restated from its definition, independent of torch and of the library, and builders for caches whose bytes run through every
-finite code.  Pure numpy; tests/test_fp8_inputs.py checks it against torch's CPU conversion without a GPU.
+finite code (their poison and page scatter are tests/common_inputs.py's, with the NaN code 0x7F).  Pure numpy;
+tests/test_fp8_inputs.py checks it against torch's CPU conversion without a GPU.
 
 OCP e4m3fn: 1 sign bit, 4 exponent bits (bias 7), 3 mantissa bits.  Exponent field 0: subnormals, m / 8 * 2^-6.  No infinities: the
 exponent field 15 holds ordinary numbers up to 1.75 * 2^8 = 448, except mantissa 7 (codes 0x7F and 0xFF), which is NaN.
@@ -72,42 +73,3 @@ def all_codes_cache(B, Hkv, Ncap, d, lens, seed):
             elif L:
                 out[b, h, :L] = np.random.default_rng(seed + 131 * b + h).choice(FINITE_CODES, (L, d), replace=False)
     return out
-
-
-GARBAGE = (-1, 1 << 30)   # what a block table holds past a sequence's last live page
-
-
-def poisoned(codes, lens):
-    """cache [B, Hkv, Ncap, d] of codes -> a copy with the NaN code 0x7F in every row at and past the sequence's length"""
-    out = np.array(codes, np.uint8)
-    for b in range(out.shape[0]):
-        out[b, :, min(max(int(lens[b]), 0), out.shape[2]):] = NAN_CODES[0]
-    return out
-
-
-def scatter(k8, v8, lens, ps, seed, spare=3):
-    """K and V caches [B, Hkv, Ncap, d] of codes -> (K pool, V pool [num_pages, Hkv, ps, d] uint8, table [B, max_pages] int32).
-    The method of tests/decode_inputs.py::scatter for one-byte elements: pages dealt out by a seeded permutation of a pool with
-    `spare` pages more than B * max_pages; every page no table names and every row at or past a length holds 0x7F (NaN); every
-    table entry past the last live page holds garbage."""
-    B, Hkv, Ncap, d = k8.shape
-    max_pages = Ncap // ps
-    assert max_pages * ps == Ncap
-    num_pages = B * max_pages + spare
-    perm = np.random.default_rng(seed).permutation(num_pages)
-    pools = [np.full((num_pages, Hkv, ps, d), NAN_CODES[0], np.uint8) for _ in range(2)]
-    table = np.empty((B, max_pages), np.int32)
-    nxt = 0
-    for b in range(B):
-        L = min(max(int(lens[b]), 0), Ncap)
-        for pi in range(max_pages):
-            if pi >= (L + ps - 1) // ps:
-                table[b, pi] = GARBAGE[pi % 2]
-                continue
-            page = int(perm[nxt])
-            nxt += 1
-            table[b, pi] = page
-            n = min(ps, L - pi * ps)   # rows of the page below the length; the rest stay NaN
-            for pool, src in zip(pools, (k8, v8)):
-                pool[page, :, :n] = src[b, :, pi * ps:pi * ps + n]
-    return pools[0], pools[1], table

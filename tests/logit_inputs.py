@@ -1,7 +1,8 @@
 """Seeded inputs for tests/test_gpu_kvcache_logits.py -- attention sinks and soft-capped logits on KV-cache decode (fa_kvcache_decode
-behind the `sinks` and `softcap` keywords of the four decode front ends) -- with the two rules restated in float64 numpy, and the
+behind the `sinks` and `softcap` keywords of the four decode front ends) -- with the options of every launch, and the
 helpers that show each launch could not pass on a kernel that ignores the feature (tests/test_logit_inputs.py asserts them without a
-GPU).  Pure numpy plus the `oracle` fixture (tests/conftest.py); nothing here touches a GPU.
+GPU).  Pure numpy plus the `oracle` fixture (tests/conftest.py); nothing here touches a GPU.  The reference is
+tests/common_inputs.py::expected_f64 with its `softcap` and `sinks` arguments.
 
 Shapes, inputs and poison are tests/window_inputs.py's (its three families are already the smallest that reach one pass, a split with
 empty splits and a start inside a tile, and five rows on folded heads under both masks).  What is new here:
@@ -15,7 +16,7 @@ import functools
 import numpy as np
 
 import census_inputs as ci
-import decode_inputs as di
+import common_inputs as cm
 import window_inputs as wi
 
 SOFTCAP = 1.0                       # the parity value: at the default scale it moves lse by 0.26 .. 0.56 and O by 0.05 .. 0.34
@@ -36,37 +37,6 @@ def options(variant, Hq):
     return (sinks_for(Hq) if variant in ("sinks", "both") else None), (SOFTCAP if variant in ("softcap", "both") else 0.0)
 
 
-def capped(s, softcap):
-    return softcap * np.tanh(s / softcap) if softcap else s
-
-
-# ---- the reference ------------------------------------------------------------------------------------------------------------------
-def expected_f64(q, k, v, lens, B, Hkv, G, Nq, causal, W, scale=None, softcap=0.0, sinks=None):
-    """wi.expected_f64 extended by the two rules: q [B*Hkv*G, Nq, d], k/v [B*Hkv, Ncap, d] fp32 (16-bit-rounded), sinks [Hkv*G] or
-    None -> (O [B*Hq, Nq, d], lse [B*Hq, Nq]) float64.  The sink takes part in the reference maximum."""
-    Hq, d, Ncap = Hkv * G, q.shape[2], k.shape[1]
-    out = np.zeros(q.shape, np.float64)
-    lse = np.full(q.shape[:2], -np.inf, np.float64)
-    sc = 1.0 / np.sqrt(d) if scale is None else float(scale)
-    for b in range(B):
-        L = di.clamp(lens[b], Ncap)
-        lim, lo = wi.limits(L, Nq, causal), wi.lows(L, Nq, W)
-        for h in range(Hq):
-            a = -np.inf if sinks is None else float(sinks[h])
-            kk, vv = (x[b * Hkv + h // G].astype(np.float64) for x in (k, v))
-            for i in range(Nq):
-                t = capped((kk[lo[i]:lim[i]] @ q[b * Hq + h, i].astype(np.float64)) * sc, softcap) if lim[i] else np.zeros(0)
-                m = max(t.max() if t.size else -np.inf, a)
-                if m == -np.inf:
-                    continue
-                p = np.exp(t - m)
-                den = p.sum() + np.exp(a - m)
-                if t.size:
-                    out[b * Hq + h, i] = (p / den) @ vv[lo[i]:lim[i]]
-                lse[b * Hq + h, i] = m + np.log(den)
-    return out, lse
-
-
 def case_windows(name):
     return (0, WINDOWED[name])
 
@@ -80,11 +50,11 @@ def want_S(name, W):
 
 @functools.lru_cache(maxsize=None)
 def reference(oracle, name, d, fmt, W, causal, variant, scale=None):
-    """expected_f64 of a case of wi.CASES under a variant ("none": the feature off), computed once and read-only"""
+    """cm.expected_f64 of a case of wi.CASES under a variant ("none": the feature off), computed once and read-only"""
     c = wi.CASES[name]
     (q, k, v), _ = wi.inputs(oracle, c["B"], c["Hkv"], c["G"], c["Nq"], c["Ncap"], d, fmt, c["seed"])
     sinks, softcap = options(variant, c["Hkv"] * c["G"])
-    out, lse = expected_f64(q, k, v, c["lens"], c["B"], c["Hkv"], c["G"], c["Nq"], causal, W, scale=scale, softcap=softcap, sinks=sinks)
+    out, lse = cm.expected_f64(q, k, v, c["lens"], c["B"], c["Hkv"], c["G"], c["Nq"], causal, W, scale=scale, softcap=softcap, sinks=sinks)
     out.setflags(write=False), lse.setflags(write=False)
     return out, lse
 

@@ -10,7 +10,7 @@ A part is addressed by rows: row (b, h, r) is x = b * stride_b + h * stride_h + 
 
 The composed call: sequence b holds the prefix keys [0, P) and then its own [0, L_b); row i of the sequence sees the WHOLE prefix and
 the suffix keys [0, c_i), c_i = L_b without the causal mask and max(0, L_b - Nq + 1 + i) with it.  The reference is
-logit_inputs.expected_f64 (W = 0) on the concatenated keys, lengths P + c_i.  It is taken row by row, with the row's own length and no
+common_inputs.expected_f64 (W = 0) on the concatenated keys, lengths P + c_i.  It is taken row by row, with the row's own length and no
 mask: for L_b >= Nq that is exactly expected_f64 with causal on lengths P + L_b, and for L_b < Nq (rows that see no suffix key at
 all) it keeps the whole prefix visible, as the entry defines it, where a mask aligned to the end of P + L_b keys would cut into the
 prefix.
@@ -20,6 +20,7 @@ import functools
 import numpy as np
 
 import census_inputs as ci
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import logit_inputs as li
@@ -158,7 +159,7 @@ K_MULT, V_MULT = (1.0, 6.0), (6.0, 1.0)   # fp8: per-head scales 6x apart, in op
 
 def suffix_limits(lens, Nq, Ncap, causal):
     """[B][Nq]: c_i, the suffix keys row i of sequence b sees"""
-    return [di.limits(di.clamp(L, Ncap), Nq, causal) for L in lens]
+    return [cm.row_limits(cm.clamp(L, Ncap), Nq, Nq, causal)[1].tolist() for L in lens]
 
 
 @functools.lru_cache(maxsize=None)
@@ -203,7 +204,7 @@ def concatenated(x, c):
 
 @functools.lru_cache(maxsize=None)
 def reference(oracle, shape_name, Nq, d, fmt, causal, variant, fp8=False):
-    """(O [B*Hq, Nq, d], lse [B*Hq, Nq]) float64: logit_inputs.expected_f64, W = 0, on the concatenated keys, row by row with the
+    """(O [B*Hq, Nq, d], lse [B*Hq, Nq]) float64: common_inputs.expected_f64, W = 0, on the concatenated keys, row by row with the
     lengths P + c_i (see the module docstring)"""
     c = SHAPE if shape_name == "base" else LONG
     B, Hkv, G, P, Ncap = (c[k] for k in ("B", "Hkv", "G", "P", "Ncap"))
@@ -214,7 +215,7 @@ def reference(oracle, shape_name, Nq, d, fmt, causal, variant, fp8=False):
     out = np.zeros(x["q"].shape, np.float64)
     lse = np.zeros(x["q"].shape[:2], np.float64)
     for i in range(Nq):
-        o1, l1 = li.expected_f64(np.ascontiguousarray(x["q"][:, i:i + 1]), k, v, [P + lim[b][i] for b in range(B)], B, Hkv, G, 1, False,
+        o1, l1 = cm.expected_f64(np.ascontiguousarray(x["q"][:, i:i + 1]), k, v, [P + lim[b][i] for b in range(B)], B, Hkv, G, 1, False,
                                  0, softcap=softcap, sinks=sinks)
         out[:, i], lse[:, i] = o1[:, 0], l1[:, 0]
     out.setflags(write=False), lse.setflags(write=False)
@@ -237,8 +238,8 @@ def parts_f64(oracle, shape_name, Nq, d, fmt, causal, variant, fp8=False):
     x = inputs(oracle, shape_name, Nq, d, fmt, fp8)
     sinks, softcap = li.options(variant, Hkv * G)
     rows = G * Nq
-    o_p, l_p = li.expected_f64(folded_q(x["q"], B, Hkv, G), x["kp"], x["vp"], [P], 1, Hkv, B * G, Nq, False, 0, softcap=softcap)
-    o_s, l_s = li.expected_f64(x["q"], x["ks"], x["vs"], c["lens"], B, Hkv, G, Nq, causal, 0, softcap=softcap, sinks=sinks)
+    o_p, l_p = cm.expected_f64(folded_q(x["q"], B, Hkv, G), x["kp"], x["vp"], [P], 1, Hkv, B * G, Nq, False, 0, softcap=softcap)
+    o_s, l_s = cm.expected_f64(x["q"], x["ks"], x["vs"], c["lens"], B, Hkv, G, Nq, causal, 0, softcap=softcap, sinks=sinks)
     return ((o_p.reshape(-1, d), l_p.reshape(-1), rows, B * rows), (o_s.reshape(-1, d), l_s.reshape(-1), Hkv * rows, rows))
 
 
@@ -246,16 +247,16 @@ CASES = [(Nq, causal, variant) for Nq in NQS for causal in (False, True) for var
 
 
 def misses(oracle, got, got_lse, want, want_lse, fmt, vmax):
-    """True when (got, got_lse) fails a bound the GPU parity test applies: di.peaked_tol(fmt, vmax, kernels=2) on max |O - want|,
-    di.REL_L2 on the relative L2 error, 2 * di.P_EPS absolute on lse over the rows that see a key (or a sink), -inf elsewhere"""
+    """True when (got, got_lse) fails a bound the GPU parity test applies: cm.peaked_tol(fmt, vmax, kernels=2) on max |O - want|,
+    cm.REL_L2 on the relative L2 error, 2 * cm.P_EPS absolute on lse over the rows that see a key (or a sink), -inf elsewhere"""
     got, want = np.asarray(got, np.float64).reshape(want.shape), np.asarray(want, np.float64)
     got_lse = np.asarray(got_lse, np.float64).reshape(want_lse.shape)
     live = np.isfinite(want_lse)
     if not np.isfinite(got).all() or np.isnan(got_lse).any() or (np.isfinite(got_lse) != live).any():
         return True
     rl = float(np.sqrt(((got - want) ** 2).sum() / (want ** 2).sum()))
-    return bool(np.abs(got - want).max() > di.peaked_tol(fmt, vmax, kernels=2) or rl > di.REL_L2[fmt]
-                or np.abs(got_lse[live] - want_lse[live]).max() > 2 * di.P_EPS[fmt])
+    return bool(np.abs(got - want).max() > cm.peaked_tol(fmt, vmax, kernels=2) or rl > cm.REL_L2[fmt]
+                or np.abs(got_lse[live] - want_lse[live]).max() > 2 * cm.P_EPS[fmt])
 
 
 WRONG = ("drops the prefix", "drops the suffix", "prefix twice", "lse as log2", "strides ignored")

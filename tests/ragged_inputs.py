@@ -1,6 +1,7 @@
 """Inputs and references for the per-sequence counts of the KV-cache step (tests/test_gpu_kvcache_ragged.py, tests/test_ragged_inputs.py):
-`seqlens_q` of fa_kvcache_decode and `seqlens_new` of fa_kvcache_append_ex, restated in float64 / integer numpy.  Pure numpy plus the
-`oracle` fixture (tests/conftest.py); nothing here touches a GPU.
+`seqlens_q` of fa_kvcache_decode and `seqlens_new` of fa_kvcache_append_ex.  Pure numpy plus the `oracle` fixture
+(tests/conftest.py); nothing here touches a GPU.  The clamp of a count, a sequence's row limits and the decode reference with its
+`nq` argument are tests/common_inputs.py's; here are the families, their boosted inputs, and the append restated in integer numpy.
 
 The contract, from include/fa_mi355.h.  Decode: Nq is the padded row count, n_b = min(max(seqlens_q[b], 0), Nq); row i < n_b of every
 head of sequence b is live and sees the keys [lo_i, c_i) with c_i = max(0, L_b - n_b + 1 + i) under the causal mask (L_b without) and
@@ -19,6 +20,7 @@ import functools
 
 import numpy as np
 
+import common_inputs as cm
 import decode_inputs as di
 import logit_inputs as li
 import window_inputs as wi
@@ -55,16 +57,6 @@ def shape(f):
     return tuple(f[x] for x in ("B", "Hkv", "G", "Nq", "Ncap"))
 
 
-def count(raw, padded):
-    """n_b resp. m_b: the clamp of one count"""
-    return min(max(int(raw), 0), padded)
-
-
-def counts(raw, B, padded):
-    """None (no vector: every sequence has the padded count) or a vector -> the clamped counts"""
-    return [padded] * B if raw is None else [count(x, padded) for x in raw]
-
-
 def want_S(f, W):
     """the split count of a launch: from the PADDED shape (window 0: the capacity, else the window's span)"""
     B, Hkv, G, Nq, Ncap = shape(f)
@@ -72,49 +64,14 @@ def want_S(f, W):
 
 
 # ---- the limits -----------------------------------------------------------------------------------------------------------------------
-def row_limits(L, n, Nq, causal, W):
-    """one sequence -> (lo [Nq], c [Nq], live [Nq]); dead rows have lo = c = 0"""
-    lo, c = np.zeros(Nq, np.int64), np.zeros(Nq, np.int64)
-    for i in range(n):
-        c[i] = max(0, L - n + 1 + i) if causal else L
-        lo[i] = min(max(0, L - n + 1 + i - W) if W else 0, c[i])
-    return lo, c, np.arange(Nq) < n
-
-
 def limits(lens, nq, B, Hkv, G, Nq, Ncap, causal, W):
     """-> lo, c int64 and live bool, each [B * Hkv * G, Nq] (ci.decode_limits with the sequence's own count)"""
     Hq = Hkv * G
     out = [np.zeros((B * Hq, Nq), t) for t in (np.int64, np.int64, bool)]
-    for b, n in enumerate(counts(nq, B, Nq)):
-        for a, x in zip(out, row_limits(di.clamp(lens[b], Ncap), n, Nq, causal, W)):
+    for b, n in enumerate(cm.counts(nq, B, Nq)):
+        for a, x in zip(out, cm.row_limits(cm.clamp(lens[b], Ncap), n, Nq, causal, W)):
             a[b * Hq:(b + 1) * Hq] = x
     return out
-
-
-# ---- the decode reference -------------------------------------------------------------------------------------------------------------
-def expected_f64(q, k, v, lens, nq, B, Hkv, G, Nq, causal, W, scale=None, softcap=0.0, sinks=None):
-    """li.expected_f64 with a count per sequence: q [B*Hkv*G, Nq, d], k/v [B*Hkv, Ncap, d] fp32 (16-bit-rounded), nq [B] or None
-    -> (O [B*Hq, Nq, d], lse [B*Hq, Nq]) float64.  Dead rows: zeros and -inf, sinks or not."""
-    Hq, d, Ncap = Hkv * G, q.shape[2], k.shape[1]
-    out = np.zeros(q.shape, np.float64)
-    lse = np.full(q.shape[:2], -np.inf, np.float64)
-    sc = 1.0 / np.sqrt(d) if scale is None else float(scale)
-    lo, c, live = limits(lens, nq, B, Hkv, G, Nq, Ncap, causal, W)
-    for r in range(B * Hq):
-        b, h = divmod(r, Hq)
-        a = -np.inf if sinks is None else float(sinks[h])
-        kk, vv = (x[b * Hkv + h // G].astype(np.float64) for x in (k, v))
-        for i in np.flatnonzero(live[r]):
-            t = li.capped((kk[lo[r, i]:c[r, i]] @ q[r, i].astype(np.float64)) * sc, softcap)
-            m = max(t.max() if t.size else -np.inf, a)
-            if m == -np.inf:
-                continue
-            p = np.exp(t - m)
-            den = p.sum() + np.exp(a - m)
-            if t.size:
-                out[r, i] = (p / den) @ vv[lo[r, i]:c[r, i]]
-            lse[r, i] = m + np.log(den)
-    return out, lse
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------
@@ -126,7 +83,7 @@ def inputs(oracle, name, d, fmt):
     (q, k, v), _ = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, f["seed"])
     q, k = q.copy(), k.copy()
     for b in range(B if f.get("boost", True) else 0):
-        L = di.clamp(f["lens"][b], Ncap)
+        L = cm.clamp(f["lens"][b], Ncap)
         q[b * Hkv * G:(b + 1) * Hkv * G, :, 0] = BOOST
         k[b * Hkv:(b + 1) * Hkv, max(0, L - Nq):L, 0] = np.sqrt(d)
     bits = tuple(oracle.encode16(x, fmt) for x in (q, k, v))
@@ -138,12 +95,12 @@ def inputs(oracle, name, d, fmt):
 
 @functools.lru_cache(maxsize=None)
 def reference(oracle, name, d, fmt, W, causal, ragged=True, variant="none"):
-    """expected_f64 of a family, computed once and read-only; ragged=False: what a kernel that ignores seqlens_q would return"""
+    """cm.expected_f64 of a family, computed once and read-only; ragged=False: what a kernel that ignores seqlens_q would return"""
     f = FAMILIES[name]
     B, Hkv, G, Nq, Ncap = shape(f)
     (q, k, v), _ = inputs(oracle, name, d, fmt)
     sinks, softcap = li.options(variant, Hkv * G)
-    out, lse = expected_f64(q, k, v, f["lens"], f["nq"] if ragged else None, B, Hkv, G, Nq, causal, W, softcap=softcap, sinks=sinks)
+    out, lse = cm.expected_f64(q, k, v, f["lens"], B, Hkv, G, Nq, causal, W, softcap=softcap, sinks=sinks, nq=f["nq"] if ragged else None)
     out.setflags(write=False), lse.setflags(write=False)
     return out, lse
 
@@ -158,7 +115,7 @@ def live_rows(name):
 def poison_dead_q(qb, name):
     """q encodings [B*Hq, Nq, d] -> a copy with a NaN bit pattern in every element of every dead row"""
     out = np.array(qb)
-    out[~live_rows(name)] = di.NAN16
+    out[~live_rows(name)] = cm.NAN16
     return out
 
 
@@ -181,8 +138,8 @@ def census_check(ci, O, lse, S, cnt, m, sink, live, what):
 # ---- the append -----------------------------------------------------------------------------------------------------------------------
 def lens_after(lens, new, B, nnew, ncap):
     """what seqlens_out receives: min(L_b + m_b, Ncap) (lens None: every sequence empty)"""
-    start = [0] * B if lens is None else [di.clamp(L, ncap) for L in lens]
-    return np.array([min(L + m, ncap) for L, m in zip(start, counts(new, B, nnew))], np.int32)
+    start = [0] * B if lens is None else [cm.clamp(L, ncap) for L in lens]
+    return np.array([min(L + m, ncap) for L, m in zip(start, cm.counts(new, B, nnew))], np.int32)
 
 
 def place(cache, rows, lens, new, table=None):
@@ -191,8 +148,8 @@ def place(cache, rows, lens, new, table=None):
     out = np.array(cache)
     B, nnew = rows.shape[0], rows.shape[2]
     ncap = cache.shape[2] if table is None else table.shape[1] * cache.shape[2]
-    start = [0] * B if lens is None else [di.clamp(L, ncap) for L in lens]
-    for b, m in enumerate(counts(new, B, nnew)):
+    start = [0] * B if lens is None else [cm.clamp(L, ncap) for L in lens]
+    for b, m in enumerate(cm.counts(new, B, nnew)):
         for t in range(m):
             p = start[b] + t
             if p >= ncap:
@@ -210,6 +167,6 @@ def place(cache, rows, lens, new, table=None):
 def keep_dead_q(q_rot, q_src, new):
     """Qout [B, Hq, Nnew, d]: the rotated rows of the first m_b tokens, the source bits of the rest"""
     out = np.array(q_rot)
-    for b, m in enumerate(counts(new, q_src.shape[0], q_src.shape[2])):
+    for b, m in enumerate(cm.counts(new, q_src.shape[0], q_src.shape[2])):
         out[b, :, m:] = q_src[b, :, m:]
     return out

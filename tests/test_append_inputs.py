@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import append_inputs as ai
+import common_inputs as cm
 import fp8_inputs as f8
 
 SCALES = (1.0, 0.5, 4.0, 0.37, 1.9)
@@ -82,7 +83,7 @@ def test_paged_helpers():
     assert list(after) == [37, 54, 128, 128, 37, 128]
     live = [int(table[b, pi]) for b in range(B) for pi in range(8) if pi * ps < after[b]]
     assert len(set(live)) == len(live) and all(0 <= p < num_pages for p in live)
-    assert all(int(table[b, pi]) in ai.GARBAGE for b in range(B) for pi in range(8) if pi * ps >= after[b])
+    assert all(int(table[b, pi]) in cm.GARBAGE for b in range(B) for pi in range(8) if pi * ps >= after[b])
     written = ai.written_pages(ai.LENS, B, ncap, nnew, ps)
     assert {pi for (b, pi) in written if b == 1} == {1, 2, 3}            # 17 .. 53 crosses two page boundaries
     assert {pi for (b, pi) in written if b == 2} == {7} and not {1 for (b, _) in written if b in (3, 5)}
@@ -96,7 +97,7 @@ def test_paged_helpers():
     for (b, pi) in written:
         page = table[b, pi]
         changed[page] = True
-        L = ai.clamp(ai.LENS[b], ncap)
+        L = cm.clamp(ai.LENS[b], ncap)
         for r in range(ps):
             p = pi * ps + r
             want = flat[b, :, p] if L <= p < L + nnew else pool[page, :, r]

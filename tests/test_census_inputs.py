@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 import census_inputs as ci
+import common_inputs as cm
 import decode_inputs as di
 import window_inputs as wi
 
 MODEL_ROWS = 128
-TILE = ci.TILE
 
 
 # ---- the float64 model ------------------------------------------------------------------------------------------------------------------
@@ -28,9 +28,9 @@ def _block(q, k, v, lo, c, h, r0, r1, sc, mult_fn=None, src=None):
         mult_fn(mult)
     kk, vv = k[h].astype(np.float64), v[h].astype(np.float64)
     for t, (hs, ts) in (src or {}).items():
-        assert (t + 1) * TILE <= nk and (ts + 1) * TILE <= nk
-        kk[t * TILE:(t + 1) * TILE] = k[hs, ts * TILE:(ts + 1) * TILE]
-        vv[t * TILE:(t + 1) * TILE] = v[hs, ts * TILE:(ts + 1) * TILE]
+        assert (t + 1) * cm.TILE <= nk and (ts + 1) * cm.TILE <= nk
+        kk[t * cm.TILE:(t + 1) * cm.TILE] = k[hs, ts * cm.TILE:(ts + 1) * cm.TILE]
+        vv[t * cm.TILE:(t + 1) * cm.TILE] = v[hs, ts * cm.TILE:(ts + 1) * cm.TILE]
     s = np.where(mult > 0, (q[h, r0:r1].astype(np.float64) @ kk.T) * sc, -np.inf)
     mx = s.max(1, keepdims=True)
     mx[~np.isfinite(mx)] = 0.0
@@ -75,7 +75,7 @@ def mutants(lo, c, h, row, tile, windowed, rows=MODEL_ROWS):
     i = row % rows
     out = [dict(name="drop the last visible key of one row", h=h, row=row, mult_fn=_edit(i, c[h, row] - 1, 0.0)),
            dict(name="count one key twice", h=h, row=row, mult_fn=_edit(i, (lo[h, row] + c[h, row]) // 2, 2.0)),
-           dict(name="skip one tile for one row block", h=h, row=row, mult_fn=_edit(slice(None), slice(tile * TILE, (tile + 1) * TILE), 0.0)),
+           dict(name="skip one tile for one row block", h=h, row=row, mult_fn=_edit(slice(None), slice(tile * cm.TILE, (tile + 1) * cm.TILE), 0.0)),
            dict(name="read tile t in place of t+1", h=h, row=row, src={tile + 1: (h, tile)}),
            dict(name="take one tile from head h+1", h=h, row=row, src={tile: (h + 1, tile)})]
     if windowed:
@@ -87,8 +87,8 @@ SINGLE_ROW = ("drop the last visible key of one row", "count one key twice", "dr
 
 
 def window_limits(n, W):
-    """self-attention limits with a lower edge: row i sees [max(0, i + 1 - W), i + 1) (wi.lows for L = Nq = n)"""
-    return np.array(wi.lows(n, n, W), np.int64), np.array(di.limits(n, n, True), np.int64)
+    """self-attention limits with a lower edge: row i sees [max(0, i + 1 - W), i + 1) (cm.row_limits for L = Nq = n)"""
+    return cm.row_limits(n, n, n, True, W)[:2]
 
 
 # ---- closed form ------------------------------------------------------------------------------------------------------------------------
@@ -145,8 +145,9 @@ def test_closed_form_cache_lengths(oracle, family, coding, causal, W):
     assert np.abs(got[live] - (S / np.maximum(cnt, 1)[..., None])[live]).max() <= 1e-12
     assert (got[~live] == 0.0).all() and (S[~live] == 0.0).all()
     assert ci.census_check(got, S, cnt, m_q) <= 1e-9
-    if W:   # the lower edge is wi.lows, the upper di.limits
-        assert lo[-1].tolist() == [min(a, b) for a, b in zip(wi.lows(200, Nq, W), di.limits(200, Nq, causal))]
+    if W:   # by hand at 200 keys: under the mask row i sees the W keys below 196 + i; without it, every key from there up to 200
+        assert lo[-1].tolist() == [196 + i - W for i in range(Nq)]
+        assert c[-1].tolist() == ([196, 197, 198, 199, 200] if causal else [200] * 5)
 
 
 def test_torch_variants_match_numpy():
@@ -234,7 +235,7 @@ def _criterion(diff, want_sq, fmt):
     """the project's criterion (oracle.max_abs and oracle.rel_l2 restated): diff = got - want where they differ, want_sq = the sum of
     want^2 over the WHOLE tensor -> (max_abs, rel_l2, accepted)"""
     ma, rl = float(np.abs(diff).max()), float(np.sqrt((diff ** 2).sum() / (want_sq + 1e-12)))
-    return ma, rl, ma <= di.MAX_ABS and rl <= di.REL_L2[fmt]
+    return ma, rl, ma <= cm.MAX_ABS and rl <= cm.REL_L2[fmt]
 
 
 @pytest.mark.parametrize("fmt", [0, 1], ids=["fp16", "bf16"])
@@ -256,7 +257,7 @@ def test_random_data_bounds_accept_single_row_mutants(oracle, fmt, logits):
         got = mutated(base, q, k, v, lo, c, mu)
         assert oracle.max_abs(got.astype(np.float32), base.astype(np.float32)) > 0.0
         ma, rl, ok = _criterion(got - base, (base ** 2).sum(), fmt)
-        print(f"{mu['name']} at N={n}, {logits} weights: max_abs={ma:.3e} rel_l2={rl:.3e} (bounds {di.MAX_ABS:.1e} {di.REL_L2[fmt]:.1e})")
+        print(f"{mu['name']} at N={n}, {logits} weights: max_abs={ma:.3e} rel_l2={rl:.3e} (bounds {cm.MAX_ABS:.1e} {cm.REL_L2[fmt]:.1e})")
         assert abs(rl - oracle.rel_l2(got.astype(np.float32), base.astype(np.float32))) <= 1e-6   # (_criterion is the oracle's measure)
         assert ok, f"{mu['name']}: max_abs={ma:.3e} rel_l2={rl:.3e}"
         seen.append(mu["name"])
@@ -298,7 +299,7 @@ def test_random_data_bounds_accept_single_block_tile_mutants(oracle, fmt):
             got = _block(sub_q, sub_k, sub_v, lo, c, 0, r0, r0 + rows, 0.125, mu.get("mult_fn"), mu.get("src"))
             ma, rl, ok = _criterion(got - base, want_sq, fmt)
             print(f"{mu['name']} at N={n}, {rows}-row block of {bh} heads: max_abs={ma:.3e} rel_l2={rl:.3e} "
-                  f"(bounds {di.MAX_ABS:.1e} {di.REL_L2[fmt]:.1e}) {'accepted' if ok else 'REJECTED'}")
+                  f"(bounds {cm.MAX_ABS:.1e} {cm.REL_L2[fmt]:.1e}) {'accepted' if ok else 'REJECTED'}")
             assert ma > 0.0
             accepted[rows, mu["name"]] = ok
     names = {name for (_, name) in accepted}
@@ -363,7 +364,7 @@ def test_cases_reach_what_they_are_named_for():
         assert 1 in ns and 65 in ns and any(n > 512 and n % 64 for n in ns)
     assert {63, 64, 65} <= set(ci.Z_PREFILL_N[64])
     # split-KV: one pass with a ragged tile, many splits, more rows than one workgroup's 128
-    assert [nq > di.ROWS for (nq, _) in ci.SPLITKV] == [False, False, True] and all(nk % 64 for (_, nk) in ci.SPLITKV)
+    assert [nq > cm.ROWS for (nq, _) in ci.SPLITKV] == [False, False, True] and all(nk % 64 for (_, nk) in ci.SPLITKV)
     # the decode lengths: an empty sequence, rows without a key under the mask, tile edges, the full capacity
     assert 0 in di.D_LENS and 1 in di.D_LENS and di.D_SHAPE["Ncap"] in di.D_LENS and 2 < di.D_SHAPE["Nq"]
     # neighbouring heads carry different values

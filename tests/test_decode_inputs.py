@@ -5,9 +5,10 @@ These are conditions on seeded inputs and on host arithmetic, not measurements o
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 
 
 def _kv_splits(fa, shape, d):
@@ -18,11 +19,11 @@ def _kv_splits(fa, shape, d):
 def _self_consistent(oracle, q, k, v, lens, shape, causal, scale=None):
     """the oracle's O is finite, agrees with the float64 softmax, and is zero with lse = -inf exactly on the rows without a key"""
     B, Hkv, G, Nq = (shape[x] for x in ("B", "Hkv", "G", "Nq"))
-    out, lse = di.expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal, scale)
+    out, lse = cm.expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal, scale=scale)
     assert np.isfinite(out).all() and not np.isnan(lse).any()
-    ref = di.expected_f64(q, k, v, lens, B, Hkv, G, Nq, causal, scale)
+    ref = cm.expected_f64(q, k, v, lens, B, Hkv, G, Nq, causal, scale=scale)[0]
     assert np.abs(out - ref).max() <= 1e-5 * max(1.0, np.abs(v).max())
-    dead = np.array([[c == 0 for c in di.limits(di.clamp(lens[b], k.shape[1]), Nq, causal)] for b in range(B)])
+    dead = np.array([[c == 0 for c in cm.row_limits(cm.clamp(lens[b], k.shape[1]), Nq, Nq, causal)[1]] for b in range(B)])
     dead = np.repeat(dead, Hkv * G, axis=0)
     assert np.array_equal(np.isneginf(lse), dead) and (out[dead] == 0.0).all()
     return out, lse
@@ -83,16 +84,16 @@ def test_case_b_rows():
     split 4 and live in splits 0-3; at 7 keys rows 0-12 see nothing."""
     G, Nq = di.B_SHAPE["G"], di.B_SHAPE["Nq"]
     rows = G * Nq
-    assert rows == 160 and di.ROWS < rows <= 2 * di.ROWS
+    assert rows == 160 and cm.ROWS < rows <= 2 * cm.ROWS
     edges = [h * Nq for h in range(1, G)]
-    assert any(e % 32 for e in edges) and any(e < di.ROWS < e + Nq for e in [0] + edges)   # inside a wave; across the blocks
+    assert any(e % 32 for e in edges) and any(e < cm.ROWS < e + Nq for e in [0] + edges)   # inside a wave; across the blocks
     S, L = di.B_SPLITS, di.B_LENS[0]
     assert di.chunk_of(L, S) == 256 and di.live_splits(L, S) == 5
     key0 = 4 * 256
-    lim = di.limits(L, Nq, True)
+    lim = cm.row_limits(L, Nq, Nq, True)[1]
     assert [c > key0 for c in lim] == [False] * 14 + [True] * 6 and min(lim) > 3 * 256 + 64
-    assert [c == 0 for c in di.limits(di.B_LENS[1], Nq, True)] == [True] * 13 + [False] * 7
-    assert di.B_LENS[1] < Nq and all(c == L for c in di.limits(L, Nq, False))
+    assert [c == 0 for c in cm.row_limits(di.B_LENS[1], Nq, Nq, True)[1]] == [True] * 13 + [False] * 7
+    assert di.B_LENS[1] < Nq and all(c == L for c in cm.row_limits(L, Nq, Nq, False)[1])
 
 
 @pytest.mark.parametrize("fmt,d", FMT_D)
@@ -113,7 +114,7 @@ def test_case_c_lengths():
         assert {64 * k - 1, 64 * k, 64 * k + 1} <= set(lens)
     cats = di.length_categories(lens, s["Ncap"], di.C_SPLITS, di.C_PAGES)
     assert cats >= di.c_categories_wanted(di.C_PAGES), di.c_categories_wanted(di.C_PAGES) - cats
-    assert [di.clamp(x, s["Ncap"]) for x in (-1, di.INT_MIN, 1025, di.INT_MAX)] == [0, 0, 1024, 1024]
+    assert [cm.clamp(x, s["Ncap"]) for x in (-1, cm.INT_MIN, 1025, cm.INT_MAX)] == [0, 0, 1024, 1024]
     assert np.array(lens, dtype=np.int64).astype(np.int32).tolist() == list(lens)   # every one is an int32
 
 
@@ -125,21 +126,22 @@ def test_case_c_reference(oracle, fmt, d):
     for causal in (False, True):
         _self_consistent(oracle, q, k, v, lens, s, causal)
     # the hygiene helpers: NaN at and past the clamped length and nowhere else; garbage exactly in the dead table entries
-    cache = di.poisoned(kb, lens, s["B"], s["Hkv"])
+    kc, vc = (x.reshape(s["B"], s["Hkv"], s["Ncap"], d) for x in (kb, vb))
+    cache = cm.poisoned(kc, lens)
     for ps in di.C_PAGES:
-        kp, vp, table = di.scatter(kb, vb, lens, s["B"], s["Hkv"], ps, seed=ps)
+        kp, vp, table = cm.scatter(kc, vc, lens, ps, seed=ps)
         named = set()
         for b, raw in enumerate(lens):
-            L = di.clamp(raw, s["Ncap"])
-            assert (cache[b, :, L:] == di.NAN16).all() and np.array_equal(cache[b, 0, :L], kb[b, :L])
+            L = cm.clamp(raw, s["Ncap"])
+            assert (cache[b, :, L:] == cm.NAN16).all() and np.array_equal(cache[b, 0, :L], kb[b, :L])
             n = di.live_pages(L, ps)
-            assert all(x in di.GARBAGE for x in table[b, n:]) and all(0 <= x < kp.shape[0] for x in table[b, :n])
+            assert all(x in cm.GARBAGE for x in table[b, n:]) and all(0 <= x < kp.shape[0] for x in table[b, :n])
             named |= set(int(x) for x in table[b, :n])
             for pi in range(n):
                 r = min(ps, L - pi * ps)
-                assert np.array_equal(kp[table[b, pi], 0, :r], kb[b, pi * ps:pi * ps + r]) and (vp[table[b, pi], 0, r:] == di.NAN16).all()
+                assert np.array_equal(kp[table[b, pi], 0, :r], kb[b, pi * ps:pi * ps + r]) and (vp[table[b, pi], 0, r:] == cm.NAN16).all()
         unnamed = sorted(set(range(kp.shape[0])) - named)
-        assert unnamed and (kp[unnamed] == di.NAN16).all() and (vp[unnamed] == di.NAN16).all()
+        assert unnamed and (kp[unnamed] == cm.NAN16).all() and (vp[unnamed] == cm.NAN16).all()
 
 
 @pytest.mark.parametrize("fmt,d", FMT_D)
@@ -152,7 +154,7 @@ def test_case_d_reference(oracle, fmt, d):
         for scale in di.D_SCALES:
             out, lse = _self_consistent(oracle, q, k, v, di.D_LENS, s, causal, scale)
             if scale == 0.0:
-                uo, ul = di.uniform_expected(v, di.D_LENS, s["B"], s["Hkv"], s["G"], s["Nq"], causal)
+                uo, ul = cm.uniform_expected(v, di.D_LENS, s["B"], s["Hkv"], s["G"], s["Nq"], causal)
                 live = np.isfinite(ul)
                 assert np.abs(out - uo).max() < 1e-6 and np.array_equal(live, np.isfinite(lse)) and np.abs(lse[live] - ul[live]).max() < 1e-12
     f = di.D_FORWARD

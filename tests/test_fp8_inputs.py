@@ -3,6 +3,7 @@ decode kernels rest on: every finite e4m3fn value survives a round trip through 
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import fp8_inputs as f8
 
 
@@ -65,15 +66,15 @@ def test_all_codes_builders():
 def test_scatter_and_poison():
     B, Hkv, Ncap, d, ps, lens = 3, 2, 64, 16, 16, (0, 17, 64)
     k8, v8 = f8.all_codes((B, Hkv, Ncap, d), 1), f8.all_codes((B, Hkv, Ncap, d), 2)
-    pk = f8.poisoned(k8, lens)
+    pk = cm.poisoned(k8, lens, nan=f8.NAN_CODES[0])
     for b, L in enumerate(lens):
         assert (pk[b, :, L:] == 0x7F).all() and np.array_equal(pk[b, :, :L], k8[b, :, :L])
-    kp, vp, table = f8.scatter(k8, v8, lens, ps, seed=4)
+    kp, vp, table = cm.scatter(k8, v8, lens, ps, seed=4, nan=f8.NAN_CODES[0])
     assert kp.shape == vp.shape == (B * 4 + 3, Hkv, ps, d) and kp.dtype == np.uint8 and table.shape == (B, 4)
     live = []
     for b, L in enumerate(lens):
         n_live = (L + ps - 1) // ps
-        assert all(int(t) in f8.GARBAGE for t in table[b, n_live:])
+        assert all(int(t) in cm.GARBAGE for t in table[b, n_live:])
         for pi in range(n_live):
             n = min(ps, L - pi * ps)
             page = table[b, pi]

@@ -17,14 +17,15 @@ import numpy as np
 import pytest
 
 import census_inputs as ci
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import window_inputs as wi
 
 pytestmark = pytest.mark.gpu
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
-FMTS = [pytest.param(fmt, id=di.FMT_NAME[fmt]) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMTS = [pytest.param(fmt, id=cm.FMT_NAME[fmt]) for fmt in (0, 1)]
 _EXPERIMENTAL = (21, 22, 25)   # A/B kernels: only in the experimental library (tests/test_gpu_parity.py)
 
 
@@ -37,14 +38,6 @@ def torch_cuda():
 
 def _tdtype(torch, fmt):
     return torch.float16 if fmt == 0 else torch.bfloat16
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.array(bits, order="C").view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.array(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -85,7 +78,7 @@ def test_prefill_zero_k(fa, oracle, torch_cuda, fmt, d, coding):
     worst = 0.0
     for n in ci.Z_PREFILL_N[d]:
         case = ci.z_prefill(oracle, ci.Z_BH, n, d, fmt, coding)
-        dq, dk, dv = (_dev16(torch, x, fmt) for x in case["bits"])
+        dq, dk, dv = (cm.dev16(torch, x, fmt) for x in case["bits"])
         for causal in (False, True):
             lo, c = ci.prefill_limits(n, causal)
             S = ci.expected_sums_torch(torch, case["m"], lo, c, n, d, coding, "cuda")
@@ -93,7 +86,7 @@ def test_prefill_zero_k(fa, oracle, torch_cuda, fmt, d, coding):
                 o = fa.fa_forward(dq, dk, dv, algo=algo, causal=causal)
                 torch.cuda.synchronize()
                 worst = max(worst, ci.census_check(o, S, torch.as_tensor(c - lo), case["m"],
-                                                   what=f"fa_forward Z n={n} d={d} {di.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"))
+                                                   what=f"fa_forward Z n={n} d={d} {cm.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"))
     _note("fa_forward", "Z", worst)
 
 
@@ -105,7 +98,7 @@ def test_prefill_zero_k_16bit_output(fa, oracle, torch_cuda, fmt):
     worst = 0.0
     for coding in ci.out16_codings(fmt):
         case = ci.z_prefill(oracle, bh, n, d, fmt, coding)
-        dq, dk, dv = (_dev16(torch, x, fmt) for x in case["bits"])
+        dq, dk, dv = (cm.dev16(torch, x, fmt) for x in case["bits"])
         for causal in (False, True):
             lo, c = ci.prefill_limits(n, causal)
             S = ci.expected_sums_torch(torch, case["m"], lo, c, n, d, coding, "cuda")
@@ -115,7 +108,7 @@ def test_prefill_zero_k_16bit_output(fa, oracle, torch_cuda, fmt):
                 torch.cuda.synchronize()
                 assert o.dtype == _tdtype(torch, fmt)
                 worst = max(worst, ci.census_check(o, S, torch.as_tensor(c - lo), case["m"],
-                                                   what=f"fa_forward Z out16 {di.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"))
+                                                   what=f"fa_forward Z out16 {cm.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"))
     _note("fa_forward out16", "Z", worst)
 
 
@@ -149,7 +142,7 @@ def test_causal_grid_all_rows(fa, torch_cuda, fmt, bh, n, d, coding):
     torch = torch_cuda
     q, k, v, m = _grid_inputs(torch, bh, n, d, fmt, coding, 9000 + bh)
     _note("fa_forward causal grid", "Z", _grid_check(fa, torch, q, k, v, m, n, d, coding, True, ci.GRID_ALGOS,
-                                                     f"causal grid bh={bh} n={n} d={d} {di.FMT_NAME[fmt]} {coding}"))
+                                                     f"causal grid bh={bh} n={n} d={d} {cm.FMT_NAME[fmt]} {coding}"))
 
 
 @pytest.mark.parametrize("coding", ci.CODINGS)
@@ -162,7 +155,7 @@ def test_bench_shape_all_rows(fa, torch_cuda, fmt, coding):
     q, k, v, m = _grid_inputs(torch, bh, n, d, fmt, coding, 9100)
     q, k, v = (x.view(g["B"], g["H"], n, d) for x in (q, k, v))
     _note("fa_forward bench shape", "Z", _grid_check(fa, torch, q, k, v, m, n, d, coding, False, ci.GRID_ALGOS,
-                                                     f"bench shape {di.FMT_NAME[fmt]} {coding}"))
+                                                     f"bench shape {cm.FMT_NAME[fmt]} {coding}"))
 
 
 @pytest.mark.parametrize("coding", ci.CODINGS)
@@ -174,7 +167,7 @@ def test_one_wave_grid_all_rows(fa, torch_cuda, fmt, coding):
     bh = max(torch.cuda.get_device_properties(0).multi_processor_count // 8, 2)
     q, k, v, m = _grid_inputs(torch, bh, g["n"], g["d"], fmt, coding, 9200)
     _note("fa_forward one-wave grid", "Z", _grid_check(fa, torch, q, k, v, m, g["n"], g["d"], coding, False, (g["algo"],),
-                                                       f"one-wave grid bh={bh} {di.FMT_NAME[fmt]} {coding}"))
+                                                       f"one-wave grid bh={bh} {cm.FMT_NAME[fmt]} {coding}"))
 
 
 # ---- the fallback chain, family R -------------------------------------------------------------------------------------------------------
@@ -237,10 +230,10 @@ def test_fallback_chain_row_constant_k(fa, oracle, torch_cuda, fmt, d, causal):
             for wave in (ci.WAVE_ROWS[d], ci.WAVE_ROWS[d] // 2, 16):
                 ci.assert_regimes(case, d, fmt, causal, wave)
             assert ci.r_exact(fmt, ci.max_count(lo, c, n, d, coding))
-            dq, dk, dv = (_dev16(torch, x, fmt) for x in case["bits"])
+            dq, dk, dv = (cm.dev16(torch, x, fmt) for x in case["bits"])
             S = ci.expected_sums_torch(torch, case["m"], lo, c, n, d, coding, "cuda")
             for algo in algos:
-                what = f"fa_forward R n={n} d={d} {di.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"
+                what = f"fa_forward R n={n} d={d} {cm.FMT_NAME[fmt]} {coding} algo={algo} causal={causal}"
                 o = fa.fa_forward(dq, dk, dv, algo=algo, causal=causal)
                 torch.cuda.synchronize()
                 worst = max(worst, ci.census_check(o, S, torch.as_tensor(c - lo), case["m"], what=what))
@@ -285,12 +278,12 @@ def test_splitkv_zero_k(fa, oracle, torch_cuda, fmt, d, coding):
         S = ci.expected_sums(m, np.zeros(nq, np.int64), np.full(nq, nk, np.int64), nk, d, coding)
         assert ci.z_exact(fmt, S.max())
         need = fa.splitkv_workspace_bytes(1, 2, nq, nk, d)
-        dq = _dev16(torch, qb[None], fmt)
-        dv = _dev16(torch, oracle.encode16(v, fmt)[None], fmt)
+        dq = cm.dev16(torch, qb[None], fmt)
+        dv = cm.dev16(torch, oracle.encode16(v, fmt)[None], fmt)
         o = fa.fa_forward_splitkv(dq, torch.zeros_like(dv), dv, workspace=_nan_workspace(torch, need))
         torch.cuda.synchronize()
         worst = max(worst, ci.census_check(o.cpu().numpy().reshape(S.shape), S, np.full(nq, nk), m,
-                                           what=f"splitkv Z nq={nq} nk={nk} d={d} {di.FMT_NAME[fmt]} {coding}"))
+                                           what=f"splitkv Z nq={nq} nk={nk} d={d} {cm.FMT_NAME[fmt]} {coding}"))
     _note("fa_forward_splitkv", "Z", worst)
 
 
@@ -299,14 +292,14 @@ K_SCALE, V_SCALES = 3.0, (None, 0.5)   # fp8: any k_scale leaves a zero score ze
 
 def _cache_run(fa, torch, dq, kc, vc, lens, W, causal, fmt, ps=0, seed=0, v_scale=None):
     """kc, vc [B, Hkv, Ncap, d] poisoned for (lens, W): uint16 encodings (16-bit entries) or uint8 codes (fp8 entries, with
-    k_scale = K_SCALE and the given v_scale).  ps = 0: the contiguous entry, else the paged one on wi.scatter's pool (W = 0 is
-    di.scatter's contract: no start, no dead pages).  W = 0 goes to the base entries, W > 0 to the windowed ones.  -> O, lse"""
+    k_scale = K_SCALE and the given v_scale).  ps = 0: the contiguous entry, else the paged one on cm.scatter's pool (W = 0: no
+    start, no dead pages).  W = 0 goes to the base entries, W > 0 to the windowed ones.  -> O, lse"""
     B, Hq, Nq, d = dq.shape
     Hkv, Ncap = kc.shape[1], kc.shape[2]
     G = Hq // Hkv
     fp8 = kc.dtype == np.uint8
     need = fa.kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, W) if W else fa.kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
-    dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     kw = dict(cache_seqlens=_ints(torch, lens), causal=causal, return_lse=True, workspace=_nan_workspace(torch, need), window=W)
     if fp8:
         kw.update(k_scale=torch.full((Hkv,), K_SCALE, dtype=torch.float32, device="cuda"),
@@ -314,7 +307,7 @@ def _cache_run(fa, torch, dq, kc, vc, lens, W, causal, fmt, ps=0, seed=0, v_scal
     if ps == 0:
         o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(kc), dev(vc), **kw)
     else:
-        kp, vp, table = wi.scatter(kc, vc, lens, Nq, W, ps, seed, nan=wi.NAN8 if fp8 else di.NAN16)
+        kp, vp, table = cm.scatter(kc, vc, lens, ps, seed, Nq, W, nan=wi.NAN8 if fp8 else cm.NAN16)
         o, lse = (fa.fa_forward_kvcache_paged_fp8 if fp8 else fa.fa_forward_kvcache_paged)(
             dq, dev(kp), dev(vp), torch.from_numpy(table).cuda(), **kw)
     torch.cuda.synchronize()
@@ -330,7 +323,7 @@ def _cache_check(o, lse, S, cnt, m_q, fmt, what, v_scale=1.0):
     assert not np.isnan(got).any(), what + ": NaN in lse"
     assert (got[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
     le = float(np.abs(got[live] - np.log(cnt[live])).max()) if live.any() else 0.0
-    assert le <= 2 * di.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
     return dev
 
 
@@ -344,9 +337,9 @@ def _cache_entries(fa, oracle, torch, shape, lens, d, fmt, coding, W, causal, pa
     S, m_q = ci.decode_sums(case["m"], lo, c, G, Ncap, d, coding)
     cnt = c - lo
     assert ci.z_exact(fmt, S.max())
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
     out = {}
-    kc, vc = wi.poisoned(kb, lens, Nq, W), wi.poisoned(vb, lens, Nq, W)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), lens, Nq, W) for x in (kb, vb))
     o, lse = _cache_run(fa, torch, dq, kc, vc, lens, W, causal, fmt)
     out["kvcache"] = _cache_check(o, lse, S, cnt, m_q, fmt, what + " contiguous")
     for ps in pages:
@@ -355,7 +348,7 @@ def _cache_entries(fa, oracle, torch, shape, lens, d, fmt, coding, W, causal, pa
     out["kvcache_paged"] = out["kvcache"]
     k8, v8 = (f8.encode(x).reshape(B, Hkv, Ncap, d) for x in (case["k"], case["v"]))
     assert np.array_equal(f8.decode(v8).reshape(case["v"].shape), case["v"]) and not k8.any()   # the codes hold the values exactly
-    k8, v8 = wi.poisoned(k8, lens, Nq, W, nan=wi.NAN8), wi.poisoned(v8, lens, Nq, W, nan=wi.NAN8)
+    k8, v8 = cm.poisoned(k8, lens, Nq, W, nan=wi.NAN8), cm.poisoned(v8, lens, Nq, W, nan=wi.NAN8)
     for vs in V_SCALES:
         o8, lse8 = _cache_run(fa, torch, dq, k8, v8, lens, W, causal, fmt, v_scale=vs)
         dev = _cache_check(o8, lse8, S, cnt, m_q, fmt, what + f" fp8 v_scale={vs}", v_scale=1.0 if vs is None else vs)
@@ -375,7 +368,7 @@ def test_cache_entries_zero_k(fa, oracle, torch_cuda, fmt, d, causal, coding):
     K/V head) through fa_forward_kvcache, _paged (pages of 16 and 256), _fp8 and _paged_fp8"""
     shape = tuple(di.D_SHAPE[x] for x in ("B", "Hkv", "G", "Nq", "Ncap"))
     devs = _cache_entries(fa, oracle, torch_cuda, shape, di.D_LENS, d, fmt, coding, 0, causal, (di.D_PAGE, 256),
-                          f"cache Z d={d} {di.FMT_NAME[fmt]} {coding} causal={causal}")
+                          f"cache Z d={d} {cm.FMT_NAME[fmt]} {coding} causal={causal}")
     for entry, dev in devs.items():
         _note("fa_forward_" + entry, "Z", dev)
 
@@ -393,6 +386,6 @@ def test_window_entries_zero_k(fa, oracle, torch_cuda, fmt, d, name, W, causal):
     shape = tuple(case[x] for x in ("B", "Hkv", "G", "Nq", "Ncap"))
     for coding in ci.CODINGS:
         devs = _cache_entries(fa, oracle, torch_cuda, shape, case["lens"], d, fmt, coding, W, causal, wi.PAGES,
-                              f"window Z {name} W={W} d={d} {di.FMT_NAME[fmt]} {coding} causal={causal}")
+                              f"window Z {name} W={W} d={d} {cm.FMT_NAME[fmt]} {coding} causal={causal}")
         for entry, dev in devs.items():
             _note("fa_forward_" + entry + "_window", "Z", dev)

@@ -15,7 +15,7 @@ key must be exactly 0 with lse = -inf.
 
 Tolerances are the project's, fixed before any run: max-abs 1e-2, relative L2 2e-3 (fp16) / 1.2e-2 (bf16), x 1.5 with 16-bit
 output, lse within 2 * P_EPS.  Where the input makes peaked rows (the spikes of case A, scale 0.3) the max-abs bound is
-_peaked_tol of tests/test_gpu_parity.py.  Wherever the paged and the contiguous entry run on the same keys, O and lse are also
+peaked_tol of tests/common_inputs.py.  Wherever the paged and the contiguous entry run on the same keys, O and lse are also
 compared bit for bit.  Every case prints its figures next to the bounds (pytest -s).
 
 That the cases bite was measured on scratch builds of the library (one edit each, never committed; all give wrong numbers inside
@@ -34,11 +34,12 @@ the allocations), 102 cases per run on an MI355X:
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 
 pytestmark = pytest.mark.gpu
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 GIB = 1 << 30
 
 
@@ -75,7 +76,7 @@ def _contig(fa, torch, bits, lens, shape, fmt, causal=False, out_same=False, sca
     qb, kb, vb = bits
     d = qb.shape[2]
     dq = _to_dev(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    dk, dv = (_to_dev(torch, di.poisoned(x, lens, B, Hkv), fmt) for x in (kb, vb))
+    dk, dv = (_to_dev(torch, cm.poisoned(x.reshape(B, Hkv, Ncap, d), lens), fmt) for x in (kb, vb))
     need = fa.kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
     assert splits is None or di.splits_of(need, B * Hkv, G * Nq, d) == splits
     o, lse = fa.fa_forward_kvcache(dq, dk, dv, _lens_dev(torch, lens), causal=causal, scale=scale,
@@ -91,7 +92,7 @@ def _paged(fa, torch, bits, lens, shape, fmt, ps, seed, causal=False, out_same=F
     B, Hkv, G, Nq, Ncap = shape
     qb, kb, vb = bits
     d = qb.shape[2]
-    kp, vp, table = di.scatter(kb, vb, lens, B, Hkv, ps, seed)
+    kp, vp, table = cm.scatter(kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d), lens, ps, seed)
     dq = _to_dev(torch, qb, fmt).view(B, Hkv * G, Nq, d)
     need = fa.kvcache_paged_workspace_bytes(B, Hkv, G, Nq, Ncap // ps, ps, d)
     assert need == fa.kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
@@ -108,12 +109,12 @@ def _host(t, shape):
     return t.float().cpu().numpy().reshape(shape)
 
 
-def _check(oracle, res, want, want_lse, fmt, what, out_same=False, max_abs=di.MAX_ABS):
+def _check(oracle, res, want, want_lse, fmt, what, out_same=False, max_abs=cm.MAX_ABS):
     """the checks of tests/test_gpu_kvcache.py::_check; res = (O, lse) device tensors, or O alone (want_lse None)"""
     o, lse = res if isinstance(res, tuple) else (res, None)
     got = _host(o, want.shape)
     ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
-    tol_rl = di.REL_L2[fmt] * (1.5 if out_same else 1.0)
+    tol_rl = cm.REL_L2[fmt] * (1.5 if out_same else 1.0)
     assert np.isfinite(got).all(), what + ": O is not finite"
     if lse is None:
         print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} (bounds {max_abs:.2e} {tol_rl:.1e})")
@@ -122,13 +123,13 @@ def _check(oracle, res, want, want_lse, fmt, what, out_same=False, max_abs=di.MA
     got_lse = _host(lse, want_lse.shape)
     live = np.isfinite(want_lse)
     le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {max_abs:.2e} {tol_rl:.1e} {2 * di.P_EPS[fmt]:.2e})")
+    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {max_abs:.2e} {tol_rl:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert not np.isnan(got_lse).any(), what + ": NaN in lse"
     assert ma <= max_abs and rl <= tol_rl, f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
     assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
     assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
     assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * di.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
 
 
 def _same_bits(torch, a, b, what):
@@ -141,10 +142,10 @@ _REF = {}
 
 
 def _reference(oracle, key, q, k, v, lens, shape, causal, scale=None):
-    """di.expected, computed once per case and shared (read-only)"""
+    """cm.expected, computed once per case and shared (read-only)"""
     if key not in _REF:
         B, Hkv, G, Nq, _ = shape
-        out, lse = di.expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal, scale)
+        out, lse = cm.expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal, scale=scale)
         out.setflags(write=False), lse.setflags(write=False)
         _REF[key] = (out, lse)
     return _REF[key]
@@ -162,9 +163,9 @@ def test_many_splits_kvcache(fa, oracle, torch_cuda, fmt, d, spiked):
     case = di.case_a(oracle, d, fmt, "kvcache", spiked)
     di.assert_case_a(case, di.A_SPLITS)
     want, want_lse = _reference(oracle, ("A", d, fmt, spiked), case["q"], case["k"], case["v"], case["lens"], shape, False)
-    tol = di.peaked_tol(fmt, np.abs(case["v"]).max()) if spiked else di.MAX_ABS
+    tol = cm.peaked_tol(fmt, np.abs(case["v"]).max()) if spiked else cm.MAX_ABS
     for out_same in (False, True):
-        what = f"A kvcache d={d} {di.FMT_NAME[fmt]} spiked={spiked} out_same={out_same}"
+        what = f"A kvcache d={d} {cm.FMT_NAME[fmt]} spiked={spiked} out_same={out_same}"
         base = _contig(fa, torch, case["bits"], case["lens"], shape, fmt, out_same=out_same, splits=di.A_SPLITS)
         _check(oracle, base, want, want_lse, fmt, what, out_same, tol)
         got = _paged(fa, torch, case["bits"], case["lens"], shape, fmt, di.A_PAGE, seed=d + fmt, out_same=out_same)
@@ -185,12 +186,12 @@ def test_many_splits_splitkv(fa, oracle, torch_cuda, fmt, d, spiked):
     want = oracle.forward_cross(case["q"], case["k"], case["v"], accum=1, nthreads=8)
     assert np.isfinite(want).all()
     dq, dk, dv = (_to_dev(torch, x[None], fmt) for x in case["bits"])   # B = 1, H = bh
-    tol = di.peaked_tol(fmt, np.abs(case["v"]).max()) if spiked else di.MAX_ABS
+    tol = cm.peaked_tol(fmt, np.abs(case["v"]).max()) if spiked else cm.MAX_ABS
     for out_same in (False, True):
         o = fa.fa_forward_splitkv(dq, dk, dv, out_dtype=_tdtype(torch, fmt) if out_same else torch.float32,
                                   workspace=_nan_workspace(torch, need))
         torch.cuda.synchronize()
-        _check(oracle, o, want, None, fmt, f"A splitkv d={d} {di.FMT_NAME[fmt]} spiked={spiked} out_same={out_same}", out_same, tol)
+        _check(oracle, o, want, None, fmt, f"A splitkv d={d} {cm.FMT_NAME[fmt]} spiked={spiked} out_same={out_same}", out_same, tol)
 
 
 # ---- B. the causal mask on folded heads -----------------------------------------------------------------------------------------
@@ -207,7 +208,7 @@ def test_folded_causal_mask(fa, oracle, torch_cuda, fmt, d, ps):
     want, want_lse = _reference(oracle, ("B", d, fmt), q, k, v, di.B_LENS, shape, True)
     dead = np.isinf(want_lse).reshape(B, Hkv * G, Nq)
     assert not dead[0].any() and (dead[1] == (np.arange(Nq) < 13)[None, :]).all()
-    what = f"B folded causal d={d} {di.FMT_NAME[fmt]} page={ps}"
+    what = f"B folded causal d={d} {cm.FMT_NAME[fmt]} page={ps}"
     base = _contig(fa, torch, bits, di.B_LENS, shape, fmt, causal=True, splits=di.B_SPLITS)
     _check(oracle, base, want, want_lse, fmt, what)
     got = _paged(fa, torch, bits, di.B_LENS, shape, fmt, ps, seed=ps + d + fmt, causal=True)
@@ -231,7 +232,7 @@ def test_length_sweep(fa, oracle, torch_cuda, fmt, d, causal):
     assert di.length_categories(lens, Ncap, di.C_SPLITS, di.C_PAGES) >= di.c_categories_wanted(di.C_PAGES)
     (q, k, v), bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 3400)
     want, want_lse = _reference(oracle, ("C", d, fmt, causal), q, k, v, lens, shape, causal)
-    what = f"C length sweep d={d} {di.FMT_NAME[fmt]} causal={causal}"
+    what = f"C length sweep d={d} {cm.FMT_NAME[fmt]} causal={causal}"
     base = _contig(fa, torch, bits, lens, shape, fmt, causal=causal, splits=di.C_SPLITS)
     _check(oracle, base, want, want_lse, fmt, what)
     for ps in di.C_PAGES:
@@ -253,10 +254,10 @@ def test_scale_kvcache(fa, oracle, torch_cuda, fmt, d, causal, scale):
     (q, k, v), bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 3500)
     want, want_lse = _reference(oracle, ("D", d, fmt, causal, scale), q, k, v, di.D_LENS, shape, causal, scale)
     if scale == 0.0:
-        uo, ul = di.uniform_expected(v, di.D_LENS, B, Hkv, G, Nq, causal)
+        uo, ul = cm.uniform_expected(v, di.D_LENS, B, Hkv, G, Nq, causal)
         assert np.abs(want - uo).max() < 1e-6 and np.array_equal(np.isfinite(ul), np.isfinite(want_lse))
-    tol = di.peaked_tol(fmt, np.abs(v).max()) if scale == 0.3 else di.MAX_ABS
-    what = f"D scale={scale} d={d} {di.FMT_NAME[fmt]} causal={causal}"
+    tol = cm.peaked_tol(fmt, np.abs(v).max()) if scale == 0.3 else cm.MAX_ABS
+    what = f"D scale={scale} d={d} {cm.FMT_NAME[fmt]} causal={causal}"
     base = _contig(fa, torch, bits, di.D_LENS, shape, fmt, causal=causal, scale=scale, splits=4)
     _check(oracle, base, want, want_lse, fmt, what, max_abs=tol)
     got = _paged(fa, torch, bits, di.D_LENS, shape, fmt, di.D_PAGE, seed=d + fmt, causal=causal, scale=scale)
@@ -280,7 +281,7 @@ def test_scale_splitkv(fa, oracle, torch_cuda, fmt, d, scale):
         assert (need > 0) == (nk > 1000)
         o = fa.fa_forward_splitkv(*(_to_dev(torch, x[None], fmt) for x in (qb, kb, vb)), scale=scale, workspace=_nan_workspace(torch, need))
         torch.cuda.synchronize()
-        _check(oracle, o, want, None, fmt, f"D splitkv scale={scale} d={d} {di.FMT_NAME[fmt]} nq={nq} nk={nk}")
+        _check(oracle, o, want, None, fmt, f"D splitkv scale={scale} d={d} {cm.FMT_NAME[fmt]} nq={nq} nk={nk}")
 
 
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
@@ -293,7 +294,7 @@ def test_scale_zero_forward(fa, oracle, torch_cuda, fmt, algo, causal):
     want = oracle.forward(q, k, v, scale=0.0, accum=1, nthreads=4, causal=causal)
     o = fa.fa_forward(*(_to_dev(torch, x, fmt) for x in bits), scale=0.0, algo=algo, causal=causal)
     torch.cuda.synchronize()
-    _check(oracle, o, want, None, fmt, f"D fa_forward scale=0 {di.FMT_NAME[fmt]} algo={algo} causal={causal}")
+    _check(oracle, o, want, None, fmt, f"D fa_forward scale=0 {cm.FMT_NAME[fmt]} algo={algo} causal={causal}")
 
 
 # the kernels behind fa_forward that the N = 100 case above does not reach: (d, n, algo, causal); n is ragged and spans two row blocks
@@ -315,7 +316,7 @@ def test_scale_zero_forward_pipeline(fa, oracle, torch_cuda, fmt, d, n, algo, ca
     assert np.abs(want - mean).max() < 1e-6
     o = fa.fa_forward(*(_to_dev(torch, x, fmt) for x in bits), scale=0.0, algo=algo, causal=causal)
     torch.cuda.synchronize()
-    _check(oracle, o, want, None, fmt, f"D fa_forward scale=0 d={d} n={n} {di.FMT_NAME[fmt]} algo={algo} causal={causal}")
+    _check(oracle, o, want, None, fmt, f"D fa_forward scale=0 d={d} n={n} {cm.FMT_NAME[fmt]} algo={algo} causal={causal}")
 
 
 # ---- E. addresses past 2^32 elements --------------------------------------------------------------------------------------------
@@ -349,7 +350,7 @@ def test_heads_past_4g_elements_contiguous(fa, oracle, torch_cuda):
     for t, src in ((dk, kb), (dv, vb)):
         for b in di.wrap_aliases(live, Ncap * d, B):
             t[b].fill_(float("nan"))
-        rows = _to_dev(torch, di.poisoned(src, lens_live, len(live), 1), fmt)
+        rows = _to_dev(torch, cm.poisoned(src[:, None], lens_live), fmt)
         for i, b in enumerate(live):
             t[b].copy_(rows[i])
     dq = torch.randn((B, 1, 1, d), generator=torch.Generator(device="cuda").manual_seed(5), device="cuda").half()
@@ -378,12 +379,12 @@ def test_pages_past_4g_elements_paged(fa, oracle, torch_cuda):
     (qb, kb, vb), want, want_lse = _live_reference(oracle, d, fmt, di.E_PAGED_LENS, 3900, Ncap)
     kp, vp = (torch.empty((num_pages, 1, ps, d), dtype=torch.float16, device="cuda") for _ in range(2))
     assert kp.numel() > 2 ** 32
-    table = np.array([[di.GARBAGE[i % 2] for i in range(max_pages)] for _ in range(B)], np.int32)
+    table = np.array([[cm.GARBAGE[i % 2] for i in range(max_pages)] for _ in range(B)], np.int32)
     named = [x for row in di.E_PAGED_TABLE for x in row]
     for pool, src in ((kp, kb), (vp, vb)):
         for page in di.wrap_aliases(named, ps * d, num_pages):
             pool[page].fill_(float("nan"))
-        rows = _to_dev(torch, di.poisoned(src, di.E_PAGED_LENS, B, 1), fmt)   # [B, 1, Ncap, d], NaN past the lengths
+        rows = _to_dev(torch, cm.poisoned(src[:, None], di.E_PAGED_LENS), fmt)   # [B, 1, Ncap, d], NaN past the lengths
         for b, entries in enumerate(di.E_PAGED_TABLE):
             for pi, page in enumerate(entries):
                 table[b, pi] = page

@@ -10,8 +10,8 @@ named for, and every test here repeats that assertion before it trusts a result)
 accumulators on the 16-bit-rounded inputs (oracle.forward / forward_cross, accum=1), float64 numpy for the log-sum-exp.
 
 Tolerances are the project's, fixed before any run (tests/test_gpu_parity.py, tests/test_gpu_kvcache.py):
-  fp16   max-abs MAX_ABS = 1e-2, rel-L2 REL_L2[fp16]
-  bf16   part A (peaked rows: near-one-hot rows, the first rows under the mask, logits spread x 6): max-abs _peaked_tol(bf16, vmax),
+  fp16   max-abs MAX_ABS (1e-2), rel-L2 REL_L2[fp16]
+  bf16   part A (peaked rows: near-one-hot rows, the first rows under the mask, logits spread x 6): max-abs cm.peaked_tol(bf16, vmax),
          rel-L2 3e-2 as test_redo_kernel_takes_the_blocks_the_fast_passes_refuse; the plain-forward inputs of
          test_optimistic_pass_overflow_fallback and part B keep MAX_ABS and REL_L2[bf16] as there
   16-bit output: the same max-abs bound and rel-L2 x 1.5, as test_golden_general and test_causal_vs_oracle
@@ -26,29 +26,19 @@ import os
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import fallback_inputs as fi
 
 pytestmark = pytest.mark.gpu
 
-MAX_ABS = 1e-2                          # the project's north-star tolerance (tests/test_gpu_parity.py)
-REL_L2 = {0: 2e-3, 1: 1.2e-2}           # fp16 / bf16 inputs
-P_EPS = {0: 2.0 ** -11, 1: 2.0 ** -8}   # largest relative rounding error of one value in the 16-bit format
-NAN16 = 0x7FFF                          # a NaN in fp16 and in bf16
 MARKER = 0x7FA5C0DE                     # kMarker of fa_fwd_rp16_kernel.hpp
-FMT_NAME = {0: "fp16", 1: "bf16"}
-FMT_D = [pytest.param(fmt, d, id=f"{FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
-
-
-def _peaked_tol(fmt, vmax, kernels=1):
-    """tests/test_gpu_parity.py::_peaked_tol: the north-star bar plus what the 16-bit format of P imposes on a row whose weight
-    sits on two or three comparable keys."""
-    return MAX_ABS + kernels * float(vmax) * P_EPS[fmt]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 
 
 def _bounds(fmt, vmax, out_same, peaked):
     """(max-abs, rel-L2) of the module docstring."""
-    ma = MAX_ABS if (fmt == 0 or not peaked) else _peaked_tol(fmt, vmax)
-    rl = REL_L2[fmt] if (fmt == 0 or not peaked) else 3e-2
+    ma = cm.MAX_ABS if (fmt == 0 or not peaked) else cm.peaked_tol(fmt, vmax)
+    rl = cm.REL_L2[fmt] if (fmt == 0 or not peaked) else 3e-2
     return ma, rl * (1.5 if out_same else 1.0)
 
 
@@ -108,7 +98,7 @@ def _causal_algos(d):
     return (0, 24, 6, 2, 1) if d == 64 else (0, 24, 28, 2, 1)
 
 
-CHAIN = [pytest.param(fmt, d, n, id=f"{FMT_NAME[fmt]}-d{d}-n{n}") for d in (64, 128) for n in fi.CHAIN_N[d] for fmt in (0, 1)]
+CHAIN = [pytest.param(fmt, d, n, id=f"{cm.FMT_NAME[fmt]}-d{d}-n{n}") for d in (64, 128) for n in fi.CHAIN_N[d] for fmt in (0, 1)]
 
 
 # ---- A. the fallback chain under the mask ------------------------------------------------------------------------------------
@@ -129,7 +119,7 @@ def test_causal_chain_vs_oracle(fa, oracle, torch_cuda, fmt, d, n):
     for out_same in (False, True):
         for algo in _causal_algos(d):
             got = _forward(fa, torch, dev, fmt, algo, out_same, True).float().cpu().numpy()
-            what = f"causal chain d={d} n={n} {FMT_NAME[fmt]} algo={algo} out={'same' if out_same else 'fp32'}"
+            what = f"causal chain d={d} n={n} {cm.FMT_NAME[fmt]} algo={algo} out={'same' if out_same else 'fp32'}"
             _check(oracle, got, want, fmt, what, vmax, out_same)
             _check(oracle, got[2, :fk], want[2, :fk], fmt, what + " rows before the huge key", vmax, out_same)
             if out_same:
@@ -195,7 +185,7 @@ def test_causal_chain_pass_identity(fa, oracle, torch_cuda, fmt, d, n):
     for algo in ((24,) if d == 64 else (24, 28)):
         for out_same in (False, True):
             ids, o_exp = _pass_ids(torch, dev, algo, case["rows"], True, out_same)
-            print(f"pass ids d={d} n={n} {FMT_NAME[fmt]} algo={algo} out_same={out_same}: {ids.tolist()}")
+            print(f"pass ids d={d} n={n} {cm.FMT_NAME[fmt]} algo={algo} out_same={out_same}: {ids.tolist()}")
             assert ids.shape == case["fail"].shape
             assert (ids[case["fail"]] == 3).all() and (ids[~case["fail"]] <= 1).all(), (algo, ids.tolist())
             o = _forward(fa, torch, dev, fmt, algo, out_same, True)
@@ -228,8 +218,8 @@ def test_causal_large_grid_marked_blocks(fa, oracle, torch_cuda, fmt):
             torch.cuda.synchronize()
             err = float((o - want).abs().max())
             # (bf16 under the mask: the first rows have two or three keys -- peaked by construction)
-            tol = MAX_ABS if fmt == 0 else _peaked_tol(fmt, vmax)
-            print(f"large grid bh={bh} n={n} d={d} {FMT_NAME[fmt]} algo={algo}: max_abs={err:.3e} (bound {tol:.2e})")
+            tol = cm.MAX_ABS if fmt == 0 else cm.peaked_tol(fmt, vmax)
+            print(f"large grid bh={bh} n={n} d={d} {cm.FMT_NAME[fmt]} algo={algo}: max_abs={err:.3e} (bound {tol:.2e})")
             assert bool(torch.isfinite(o).all()) and err <= tol, (bh, n, d, algo, err)
             for b in sample:
                 _check(oracle, o[b:b + 1].cpu().numpy(), want_cpu[b], fmt, f"large grid d={d} algo={algo} head {b}", vmax)
@@ -238,7 +228,7 @@ def test_causal_large_grid_marked_blocks(fa, oracle, torch_cuda, fmt):
         torch.cuda.empty_cache()
 
 
-PLAIN = [pytest.param(fmt, d, n, id=f"{FMT_NAME[fmt]}-d{d}-n{n}") for (d, n) in ((64, 640), (64, 333), (128, 300), (128, 400)) for fmt in (0, 1)]
+PLAIN = [pytest.param(fmt, d, n, id=f"{cm.FMT_NAME[fmt]}-d{d}-n{n}") for (d, n) in ((64, 640), (64, 333), (128, 300), (128, 400)) for fmt in (0, 1)]
 
 
 @pytest.mark.parametrize("fmt,d,n", PLAIN)
@@ -254,19 +244,19 @@ def test_plain_fallback_16bit_output(fa, oracle, torch_cuda, fmt, d, n):
     for algo in (0, 23, 24, 26) + ((28,) if d == 128 else ()):
         for out_same in (True, False):
             got = _forward(fa, torch, dev, fmt, algo, out_same, False).float().cpu().numpy()
-            _check(oracle, got, want, fmt, f"plain fallback d={d} n={n} {FMT_NAME[fmt]} algo={algo} out={'same' if out_same else 'fp32'}",
+            _check(oracle, got, want, fmt, f"plain fallback d={d} n={n} {cm.FMT_NAME[fmt]} algo={algo} out={'same' if out_same else 'fp32'}",
                    vmax, out_same, peaked=False)
     if case["spikes"]:
         # the full-width kernel did leave the blocks of the rows that must fail to the redo kernel, with 16-bit output (the other
         # blocks see the spiked keys as well, without a mask: they are not asserted on); x 6 is beyond fp16's overflow point only
         ids, _ = _pass_ids(torch, dev, 24, case["rows"], False, True)
-        print(f"pass ids plain d={d} n={n} {FMT_NAME[fmt]}: {ids.tolist()}")
+        print(f"pass ids plain d={d} n={n} {cm.FMT_NAME[fmt]}: {ids.tolist()}")
         must = sorted({(b, row // case["rows"]) for (b, row, _, lift) in case["spikes"] if fi.fails(lift, fmt)})
         assert must and all(ids[b, blk] == 3 for (b, blk) in must), (must, ids.tolist())
         assert fmt == 1 or (ids[2] == 3).all()
 
 
-HYGIENE = [pytest.param(fmt, d, causal, out_same, id=f"{FMT_NAME[fmt]}-d{d}-{'causal' if causal else 'plain'}-{'out16' if out_same else 'out32'}")
+HYGIENE = [pytest.param(fmt, d, causal, out_same, id=f"{cm.FMT_NAME[fmt]}-d{d}-{'causal' if causal else 'plain'}-{'out16' if out_same else 'out32'}")
            for d in (64, 128) for causal in (False, True) for out_same in (False, True) for fmt in (0, 1)]
 
 
@@ -292,7 +282,7 @@ def test_marker_hygiene(fa, oracle, torch_cuda, fmt, d, causal, out_same):
     sub = tuple(x[1:3].contiguous() for x in dev)
     vmax = np.abs(case["v"]).max()
     for algo in ((24,) if d == 64 else (24, 28)):
-        what = f"marker hygiene d={d} n={n} {FMT_NAME[fmt]} algo={algo} causal={causal} out_same={out_same}"
+        what = f"marker hygiene d={d} n={n} {cm.FMT_NAME[fmt]} algo={algo} causal={causal} out_same={out_same}"
         ids, _ = _pass_ids(torch, dev, algo, case["rows"], causal, out_same)
         # marked blocks in the launch; under the mask the benign head's unmarked ones beside them (without a mask every row
         # sees every spiked key, so no block is promised to a fast pass)
@@ -347,7 +337,7 @@ def test_splitkv_hostile_rows(fa, oracle, torch_cuda, fmt, d):
             o = fa.fa_forward_splitkv(dq, dk, dv, out_dtype=_tdtype(torch, fmt) if out_same else torch.float32,
                                       workspace=_nan_workspace(torch, need))
             torch.cuda.synchronize()
-            _check(oracle, o[0].float().cpu().numpy(), want, fmt, f"splitkv hostile d={d} nk={nk} {FMT_NAME[fmt]} out_same={out_same}",
+            _check(oracle, o[0].float().cpu().numpy(), want, fmt, f"splitkv hostile d={d} nk={nk} {cm.FMT_NAME[fmt]} out_same={out_same}",
                    vmax, out_same, peaked=False)
 
 
@@ -362,7 +352,7 @@ def _kv_expected(oracle, case, lens, causal):
     for b in range(B):
         qs = slice(b * G, (b + 1) * G)
         kb, vb = (np.repeat(x[b:b + 1], G, axis=0) for x in (k, v))
-        lim = fi.kv_limits(int(lens[b]), Nq, causal)
+        lim = cm.row_limits(int(lens[b]), Nq, Nq, causal)[1]
         for c in sorted(set(lim)):
             if c == 0:
                 continue
@@ -384,7 +374,7 @@ def _kv_run(fa, torch, case, lens, fmt, causal=False, out_same=False, key0=0):
     def cache(bits):
         bits = bits.reshape(B, Hkv, Ncap, d).copy()
         for b in range(B):
-            bits[b, :, max(int(lens[b]), 0):] = NAN16
+            bits[b, :, max(int(lens[b]), 0):] = cm.NAN16
         return _to_dev(torch, bits, fmt)
 
     dq = _to_dev(torch, qb, fmt).view(B, Hkv * G, Nq, d)
@@ -402,13 +392,13 @@ def _kv_check(oracle, got, got_lse, want, want_lse, fmt, what, vmax, out_same=Fa
     """tests/test_gpu_kvcache.py::_check"""
     live = np.isfinite(want_lse)
     le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: lse_abs={le:.3e} (bound {2 * P_EPS[fmt]:.2e})")
+    print(f"{what}: lse_abs={le:.3e} (bound {2 * cm.P_EPS[fmt]:.2e})")
     assert not np.isnan(got_lse).any(), what + ": NaN in lse"
     _check(oracle, got, want, fmt, what, vmax, out_same, peaked=False)
     assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
     assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
     assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -428,7 +418,7 @@ def test_kvcache_hostile_logits(fa, oracle, torch_cuda, fmt, d, causal):
     vmax = np.abs(case["v"]).max()
     for out_same in (False, True):
         got, lse = _kv_run(fa, torch_cuda, case, fi.KV_LENS, fmt, causal=causal, out_same=out_same)
-        _kv_check(oracle, got, lse, want, want_lse, fmt, f"kvcache hostile d={d} {FMT_NAME[fmt]} causal={causal} out_same={out_same}",
+        _kv_check(oracle, got, lse, want, want_lse, fmt, f"kvcache hostile d={d} {cm.FMT_NAME[fmt]} causal={causal} out_same={out_same}",
                   vmax, out_same)
 
 
@@ -451,7 +441,7 @@ def test_lse_merges_spiked_ranges(fa, oracle, torch_cuda, fmt, d):
     lse = np.logaddexp(l1, l2)
     merged = o1 * np.exp(l1 - lse)[..., None] + o2 * np.exp(l2 - lse)[..., None]
     ma, le = oracle.max_abs(merged.astype(np.float32), want), float(np.abs(lse - want_lse).max())
-    print(f"merged over two key ranges, hostile, d={d} {FMT_NAME[fmt]}: max_abs={ma:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {2 * P_EPS[fmt]:.2e})")
+    print(f"merged over two key ranges, hostile, d={d} {cm.FMT_NAME[fmt]}: max_abs={ma:.3e} lse_abs={le:.3e} (bounds {cm.MAX_ABS:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert np.isfinite(merged).all()
-    assert ma <= MAX_ABS
-    assert le <= 2 * P_EPS[fmt]
+    assert ma <= cm.MAX_ABS
+    assert le <= 2 * cm.P_EPS[fmt]

@@ -15,13 +15,10 @@ import functools
 import numpy as np
 import pytest
 
+import common_inputs as cm
+import decode_inputs as di
+
 pytestmark = pytest.mark.gpu
-
-MAX_ABS = 1e-2                          # the project's north-star tolerance (tests/test_gpu_parity.py)
-REL_L2 = {0: 2e-3, 1: 1.2e-2}           # fp16 / bf16 inputs
-P_EPS = {0: 2.0 ** -11, 1: 2.0 ** -8}   # largest relative rounding error of one weight in the format P is packed to
-NAN16 = 0x7FFF                          # a NaN in fp16 and in bf16
-
 
 @pytest.fixture(scope="module")
 def torch_cuda():
@@ -42,17 +39,12 @@ def _cache_to_dev(torch, bits, lens, B, Hkv, fmt):
     """[B*Hkv, Ncap, d] encodings -> device cache [B, Hkv, Ncap, d] with NaN in every row at and past the sequence's length."""
     bits = bits.reshape(B, Hkv, bits.shape[1], bits.shape[2]).copy()
     for b in range(B):
-        bits[b, :, max(int(lens[b]), 0):] = NAN16
+        bits[b, :, max(int(lens[b]), 0):] = cm.NAN16
     return _to_dev(torch, bits, fmt)
 
 
 def _nan_workspace(torch, need):
     return torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device="cuda")   # fp32 0xFFFFFFFF is a NaN
-
-
-def _limits(L, Nq, causal):
-    """c_i: the number of keys row i of a head sees."""
-    return [max(0, L - Nq + 1 + i) if causal else L for i in range(Nq)]
 
 
 def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
@@ -64,7 +56,7 @@ def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
     for b in range(B):
         qs = slice(b * Hq, (b + 1) * Hq)
         kb, vb = (np.repeat(x[b * Hkv:(b + 1) * Hkv], G, axis=0) for x in (k, v))   # K/V head of every query head
-        lim = _limits(int(lens[b]), Nq, causal)
+        lim = [int(c) for c in cm.row_limits(int(lens[b]), Nq, Nq, causal)[1]]
         for c in sorted(set(lim)):
             if c == 0:
                 continue
@@ -77,18 +69,8 @@ def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
 
 
 @functools.lru_cache(maxsize=None)
-def _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed):
-    """Seeded inputs, drawn once per shape and shared (read-only) by the tests that use them."""
-    (q, _, _), (qb, _, _) = oracle.make_qkv(B * Hkv * G, Nq, d, fmt=fmt, seed=seed)
-    (_, k, v), (_, kb, vb) = oracle.make_qkv(B * Hkv, Ncap, d, fmt=fmt, seed=seed + 1)
-    for a in (q, k, v, qb, kb, vb):
-        a.setflags(write=False)
-    return (q, k, v), (qb, kb, vb)
-
-
-@functools.lru_cache(maxsize=None)
 def _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed, lens, causal):
-    (q, k, v), _ = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed)
+    (q, k, v), _ = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed)
     out, lse = _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal)
     out.setflags(write=False), lse.setflags(write=False)
     return out, lse
@@ -109,21 +91,6 @@ def _run(fa, torch, bits, lens, B, Hkv, G, Nq, fmt, causal=False, out_same=False
     return o.float().cpu().numpy().reshape(B * Hkv * G, Nq, d), lse.cpu().numpy().reshape(B * Hkv * G, Nq), need
 
 
-def _check(oracle, got, got_lse, want, want_lse, fmt, what):
-    ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
-    live = np.isfinite(want_lse)
-    le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
-    assert np.isfinite(got).all(), what + ": O is not finite"
-    assert not np.isnan(got_lse).any(), what + ": NaN in lse"
-    assert ma <= MAX_ABS and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
-    # rows without a key: exact zeros and -inf; every other row: a finite lse within the bound
-    assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
-    assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
-    assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
-
-
 FMT_D = [pytest.param(fmt, d, id=f"{'fp16' if fmt == 0 else 'bf16'}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 
 
@@ -131,12 +98,12 @@ FMT_D = [pytest.param(fmt, d, id=f"{'fp16' if fmt == 0 else 'bf16'}-d{d}") for d
 def test_single_pass(fa, oracle, torch_cuda, fmt, d):
     """S = 1 (no workspace): lengths 1, one full tile, and the ragged capacity; both output types.  One key returns its V row."""
     B, Hkv, G, Nq, Ncap, lens = 3, 2, 1, 1, 200, (1, 64, 200)
-    (q, k, v), bits = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 101)
+    (q, k, v), bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 101)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 101, lens, False)
     for out_same in (False, True):
         got, lse, need = _run(fa, torch_cuda, bits, lens, B, Hkv, G, Nq, fmt, out_same=out_same)
         assert need == 0
-        _check(oracle, got, lse, want, want_lse, fmt, f"single pass d={d} fmt={fmt} out_same={out_same}")
+        cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"single pass d={d} fmt={fmt} out_same={out_same}")
         assert np.array_equal(got[:Hkv, 0], v[:Hkv, 0]), "a sequence of one key must return v[0]"
 
 
@@ -144,11 +111,11 @@ def test_single_pass(fa, oracle, torch_cuda, fmt, d):
 def test_split_with_empty_splits_gqa(fa, oracle, torch_cuda, fmt, d):
     """A full cache beside one filled to 77 keys (two tiles: every later split is empty), four query heads per K/V head."""
     B, Hkv, G, Nq, Ncap, lens = 2, 2, 4, 1, 8229, (8229, 77)
-    _, bits = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201)
+    _, bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201, lens, False)
     got, lse, need = _run(fa, torch_cuda, bits, lens, B, Hkv, G, Nq, fmt)
     assert need > 0
-    _check(oracle, got, lse, want, want_lse, fmt, f"split + empty splits d={d} fmt={fmt}")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"split + empty splits d={d} fmt={fmt}")
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -157,23 +124,23 @@ def test_mask_and_degenerate_rows(fa, oracle, torch_cuda, fmt, d, causal):
     """Lengths 0, 2, 66 and the capacity with five query rows in two folded heads.  Under the mask: length 66 puts keys 64-65 in a
     tile only rows 3 and 4 see, length 2 leaves rows 0-2 without a key, length 0 leaves every row without one."""
     B, Hkv, G, Nq, Ncap, lens = 4, 1, 2, 5, 4096, (0, 2, 66, 4096)
-    _, bits = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 301)
+    _, bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 301)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 301, lens, causal)
     dead = np.isinf(want_lse).reshape(B, Hkv * G, Nq)
     assert dead[0].all() and (dead[1].all(0).tolist() == [causal] * 3 + [False] * 2) and not dead[2:].any()
     got, lse, need = _run(fa, torch_cuda, bits, lens, B, Hkv, G, Nq, fmt, causal=causal)
     assert need > 0
-    _check(oracle, got, lse, want, want_lse, fmt, f"mask + degenerate rows d={d} fmt={fmt} causal={causal}")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"mask + degenerate rows d={d} fmt={fmt} causal={causal}")
 
 
 def test_mask_across_query_blocks(fa, oracle, torch_cuda):
     """Nq = Ncap = 130 without lengths is causal self-attention over two query blocks: the oracle's causal forward and fa_forward."""
     B, Hkv, G, Nq, Ncap, d, fmt = 1, 2, 1, 130, 130, 64, 0
-    (q, k, v), bits = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 401)
+    (q, k, v), bits = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 401)
     want = oracle.forward(q, k, v, nthreads=8, causal=True)
     _, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 401, (Ncap,), True)
     got, lse, _ = _run(fa, torch_cuda, bits, (Ncap,), B, Hkv, G, Nq, fmt, causal=True, pass_lens=False)
-    _check(oracle, got, lse, want, want_lse, fmt, "mask across query blocks")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, "mask across query blocks")
     dq, dk, dv = (_to_dev(torch_cuda, x, fmt) for x in bits)
     plain = fa.fa_forward(dq, dk, dv, causal=True)
     torch_cuda.cuda.synchronize()
@@ -209,7 +176,7 @@ def test_lse_merges_key_ranges(fa, oracle, torch_cuda, fmt, d):
     merged in numpy through their log-sum-exps, give the result over the whole range.  The 77-key sequence has nothing in the
     second range: lse = -inf there, weight 0 in the merge."""
     B, Hkv, G, Nq, Ncap, lens, a = 2, 2, 4, 1, 8229, (8229, 77), 4000
-    _, (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201)
+    _, (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 201, lens, False)
     o1, l1, _ = _run(fa, torch_cuda, (qb, kb[:, :a], vb[:, :a]), tuple(min(n, a) for n in lens), B, Hkv, G, Nq, fmt)
     o2, l2, _ = _run(fa, torch_cuda, (qb, kb[:, a:], vb[:, a:]), tuple(max(n - a, 0) for n in lens), B, Hkv, G, Nq, fmt)
@@ -221,8 +188,8 @@ def test_lse_merges_key_ranges(fa, oracle, torch_cuda, fmt, d):
     ma, le = oracle.max_abs(merged.astype(np.float32), want), float(np.abs(lse - want_lse).max())
     print(f"merged over two key ranges d={d} fmt={fmt}: max_abs={ma:.3e} lse_abs={le:.3e}")
     assert np.isfinite(merged).all()
-    assert ma <= MAX_ABS
-    assert le <= 2 * P_EPS[fmt]
+    assert ma <= cm.MAX_ABS
+    assert le <= 2 * cm.P_EPS[fmt]
 
 
 def test_graph_replay_follows_lengths(fa, torch_cuda):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import append_inputs as ai
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 
@@ -20,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 B, HKV, NCAP = ai.SHAPE["B"], ai.SHAPE["Hkv"], ai.SHAPE["Ncap"]
 LENS = ai.LENS
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 LAYOUTS = [pytest.param(0, id="contiguous"), pytest.param(16, id="p16"), pytest.param(64, id="p64")]
 K_SCALES, V_SCALES = (1.0, 0.37), (1.9, 0.5)   # per head, all different: a wrong head index shows
 
@@ -34,14 +35,6 @@ def torch_cuda():
 
 def _tdtype(torch, fmt):
     return torch.float16 if fmt == 0 else torch.bfloat16
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.ascontiguousarray(bits, dtype=np.uint16).view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -82,7 +75,7 @@ class _Case:
                 table_edit(self.table, num_pages)
             shape = (num_pages, HKV, ps, d)
         self.k0, self.v0 = ai.random_bytes(shape, size, seed + 1), ai.random_bytes(shape, size, seed + 2)
-        to_dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+        to_dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
         self.dk, self.dv = to_dev(self.k0), to_dev(self.v0)
         self.dtable = None if ps == 0 else torch.from_numpy(self.table).cuda()
 
@@ -120,7 +113,7 @@ def test_append_is_an_exact_copy(fa, torch_cuda, fmt, d, ps, nnew):
     if ps == 0:
         assert np.array_equal(want_k[[3, 5]], case.k0[[3, 5]])   # the full sequences: nothing fits
     assert not np.array_equal(want_k, case.k0) and not np.array_equal(want_k, want_v)
-    case.append(fa, _dev16(torch, k_new, fmt), _dev16(torch, v_new, fmt), _ints(torch, LENS))
+    case.append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), _ints(torch, LENS))
     case.check(want_k, want_v, f"Nnew={nnew} ps={ps}")
 
 
@@ -131,7 +124,7 @@ def test_append_null_lengths_is_a_prefill(fa, torch_cuda, ps):
     fmt, d, nnew = 1, 128, 21
     case = _Case(torch, d, fmt, ps, nnew, seed=31 + ps, lens=None)
     k_new, v_new = ai.random_bytes((B, HKV, nnew, d), 2, 1), ai.random_bytes((B, HKV, nnew, d), 2, 2)
-    case.append(fa, _dev16(torch, k_new, fmt), _dev16(torch, v_new, fmt), None)
+    case.append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), None)
     case.check(*case.expected(k_new, v_new), f"prefill ps={ps}")
 
 
@@ -158,7 +151,7 @@ def test_bad_live_table_entries_drop_their_tokens(fa, torch_cuda, fmt, d, ps, ba
     for page in lost:   # the pages the tokens would have reached are as they were
         assert np.array_equal(want_k[page], case.k0[page]) and np.array_equal(want_v[page], case.v0[page])
     assert not np.array_equal(want_k, case.k0)
-    case.append(fa, _dev16(torch, k_new, fmt), _dev16(torch, v_new, fmt), _ints(torch, LENS))
+    case.append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), _ints(torch, LENS))
     case.check(want_k, want_v, f"bad entry {bad} ps={ps}")
 
 
@@ -180,7 +173,7 @@ def test_fp8_append_is_quantize_kv_fp8(fa, torch_cuda, fmt, d, ps, with_scales):
             assert set(codes[h].ravel().tolist()) == set(f8.FINITE_CODES.tolist())
     case = _Case(torch, d, fmt, ps, nnew, seed=500 + d + ps, fp8=True)
     want_k, want_v = case.expected(k8, v8)
-    case.append(fa, _dev16(torch, k_new, fmt), _dev16(torch, v_new, fmt), _ints(torch, LENS), k_scale=_scales(torch, ks),
+    case.append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), _ints(torch, LENS), k_scale=_scales(torch, ks),
                 v_scale=_scales(torch, vs))
     got_k = case.dk.view(torch.uint8).cpu().numpy()
     print(f"fp8 K bytes differing: {int((got_k != want_k).sum())} of {want_k.size}")
@@ -197,7 +190,7 @@ def test_fp8_append_of_inf_and_nan(fa, torch_cuda, fmt):
     neg_nan = torch.tensor([-1], dtype=torch.int16).view(dt)   # 0xFFFF: a NaN with the sign bit set
     new = row.repeat(1, 1, nnew, 1).contiguous()
     new[0, 0, 1, 3] = neg_nan[0]
-    cache = _dev8(torch, ai.random_bytes((1, 1, 16, d), 1, 5))
+    cache = cm.dev8(torch, ai.random_bytes((1, 1, 16, d), 1, 5))
     before = cache.view(torch.uint8).clone()
     vcache = cache.clone()
     for scale in (None, torch.tensor([0.37], dtype=torch.float32, device="cuda")):
@@ -228,7 +221,7 @@ def test_seqlens_out(fa, torch_cuda, ps, fp8):
     fmt, d, nnew = 0, 64, 5
     k_new, v_new = ai.random_bytes((B, HKV, nnew, d), 2, 3), ai.random_bytes((B, HKV, nnew, d), 2, 4)
     k_new, v_new = k_new & 0x3FFF, v_new & 0x3FFF   # finite, so that the fp8 form has a CPU reference
-    dk_new, dv_new = _dev16(torch, k_new, fmt), _dev16(torch, v_new, fmt)
+    dk_new, dv_new = cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt)
     want_lens = _ints(torch, ai.lens_after(LENS, B, nnew, NCAP))
     assert want_lens.tolist() == [5, 22, 128, 128, 5, 128]
     src_k, src_v = (_quantized_cpu(fa, torch, k_new, fmt, None), _quantized_cpu(fa, torch, v_new, fmt, None)) if fp8 else (k_new, v_new)
@@ -286,7 +279,7 @@ def test_captured_append_then_decode_follows_a_growing_cache(fa, oracle, torch_c
         dtable = torch.from_numpy(table).cuda()
     else:
         host_k, host_v = k0, v0
-    to_dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    to_dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     dscale = dict(k_scale=_scales(torch, ks), v_scale=_scales(torch, vs)) if fp8 else {}
     ws = torch.empty(max(fa.kvcache_workspace_bytes(B, HKV, G, 1, NCAP, d), 1), dtype=torch.uint8, device="cuda")
 
@@ -311,7 +304,7 @@ def test_captured_append_then_decode_follows_a_growing_cache(fa, oracle, torch_c
         place = (lambda c, n: ai.expected_paged(c, n, lens_h, table)) if ps else (lambda c, n: ai.expected_contiguous(c, n, lens_h))
         host_k, host_v = place(host_k, stored(kn, ks)), place(host_v, stored(vn, vs))
         lens_h = list(ai.lens_after(lens_h, B, 1, NCAP))
-        o, lse = decode(_dev16(torch, qn, fmt), to_dev(host_k), to_dev(host_v), _ints(torch, lens_h))
+        o, lse = decode(cm.dev16(torch, qn, fmt), to_dev(host_k), to_dev(host_v), _ints(torch, lens_h))
         torch.cuda.synchronize()
         assert torch.isfinite(o).all()
         want.append((o.clone(), lse.clone(), list(lens_h)))
@@ -321,7 +314,7 @@ def test_captured_append_then_decode_follows_a_growing_cache(fa, oracle, torch_c
     dk, dv = to_dev(pool_k if ps else k0), to_dev(pool_v if ps else v0)
     dlens = _ints(torch, LENS)
     kn, vn, qn = new_rows(0)
-    dkn, dvn, dq = _dev16(torch, kn, fmt), _dev16(torch, vn, fmt), _dev16(torch, qn, fmt)
+    dkn, dvn, dq = cm.dev16(torch, kn, fmt), cm.dev16(torch, vn, fmt), cm.dev16(torch, qn, fmt)
     scratch_k, scratch_v, scratch_lens = dk.clone(), dv.clone(), dlens.clone()
     append(dkn, dvn, scratch_k, scratch_v, scratch_lens)
     decode(dq, scratch_k, scratch_v, scratch_lens)
@@ -333,7 +326,7 @@ def test_captured_append_then_decode_follows_a_growing_cache(fa, oracle, torch_c
     assert dlens.tolist() == list(LENS)   # a capture runs nothing
     for step in range(steps):
         kn, vn, qn = new_rows(step)
-        dkn.copy_(_dev16(torch, kn, fmt)), dvn.copy_(_dev16(torch, vn, fmt)), dq.copy_(_dev16(torch, qn, fmt))
+        dkn.copy_(cm.dev16(torch, kn, fmt)), dvn.copy_(cm.dev16(torch, vn, fmt)), dq.copy_(cm.dev16(torch, qn, fmt))
         ws.fill_(0xFF), o.fill_(float("nan")), lse.fill_(float("nan"))
         graph.replay()
         torch.cuda.synchronize()
@@ -353,7 +346,7 @@ def test_page_addresses_are_64_bit(fa, torch_cuda):
     assert num_pages * ps * d * 2 > 1 << 32 and (target * ps * d * 2) % (1 << 32) == alias * ps * d * 2
     pools = [torch.zeros(num_pages, 1, ps, d, dtype=torch.float16, device="cuda") for _ in range(2)]
     table = torch.tensor([[3, target, -1, 1 << 30]], dtype=torch.int32, device="cuda")
-    new = [_dev16(torch, ai.random_bytes((1, 1, 1, d), 2, s) | 1, 0) for s in (1, 2)]   # | 1: no element is zero
+    new = [cm.dev16(torch, ai.random_bytes((1, 1, 1, d), 2, s) | 1, 0) for s in (1, 2)]   # | 1: no element is zero
     fa.fa_kvcache_append_paged(new[0], new[1], pools[0], pools[1], table, cache_seqlens=_ints(torch, [ps + row]))
     torch.cuda.synchronize()
     for pool, src in zip(pools, new):

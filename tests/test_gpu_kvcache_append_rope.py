@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import append_inputs as ai
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import rope_inputs as ri
@@ -83,10 +84,10 @@ def _run16(fa, torch, fmt, d, ps, nnew, G, rot_dim, interleaved, max_pos, seed, 
     want_q = ri.rotated_rows16(q, fmt, lens, NCAP, cos, sin, interleaved)
     assert not np.array_equal(want_k[..., :rot_dim], k_new[..., :rot_dim]) and np.array_equal(want_k[..., rot_dim:], k_new[..., rot_dim:])
     want_kc, want_vc = case.expected(want_k, v_new, lens)
-    dq = ta._dev16(torch, q, fmt)
-    dq_out = {"in place": None, "separate": ta._dev16(torch, ai.random_bytes(q.shape, 2, seed + 6), fmt), "absent": None}[q_mode]
+    dq = cm.dev16(torch, q, fmt)
+    dq_out = {"in place": None, "separate": cm.dev16(torch, ai.random_bytes(q.shape, 2, seed + 6), fmt), "absent": None}[q_mode]
     dlens = None if lens is None else ta._ints(torch, lens)
-    case.rope_append(fa, ta._dev16(torch, k_new, fmt), ta._dev16(torch, v_new, fmt), dlens, cos, sin, interleaved,
+    case.rope_append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), dlens, cos, sin, interleaved,
                      q=None if q_mode == "absent" else dq, q_out=dq_out)
     what = f"d={d} ps={ps} Nnew={nnew} G={G} rot={rot_dim} il={interleaved} q {q_mode}"
     case.check(want_kc, want_vc, what)
@@ -140,7 +141,7 @@ def test_q_overlap_is_refused(fa, torch_cuda):
     torch = torch_cuda
     case = _Case(torch, 64, 0, 0, 1, seed=5)
     cos, sin = ri.identity_table(8, 8)
-    new = ta._dev16(torch, ai.random_bytes((B, HKV, 1, 64), 2, 1), 0)
+    new = cm.dev16(torch, ai.random_bytes((B, HKV, 1, 64), 2, 1), 0)
     buf = torch.zeros(B * HKV * 64 + 64, dtype=torch.float16, device="cuda")
     before = case.dk.view(torch.int16).clone()
     with pytest.raises(fa.FaError) as err:
@@ -191,8 +192,8 @@ def test_contraction_witnesses_get_the_pinned_bytes(fa, torch_cuda, fmt, interle
         sl = slice(0, nnew // 2) if form == 0 else slice(nnew // 2, nnew)
         assert (ai.round16_bits(contracted, fmt)[sl] != want[0, 0][:, i1][sl]).all()
     k0 = ai.random_bytes((1, 1, 32, d), 2, 3)
-    dk, dv = ta._dev16(torch, k0, fmt), ta._dev16(torch, k0, fmt)
-    dnew, dq = ta._dev16(torch, rows, fmt), ta._dev16(torch, rows, fmt)
+    dk, dv = cm.dev16(torch, k0, fmt), cm.dev16(torch, k0, fmt)
+    dnew, dq = cm.dev16(torch, rows, fmt), cm.dev16(torch, rows, fmt)
     fa.fa_kvcache_append(dnew, dnew, dk, dv, q=dq, rotary_cos=_f32(torch, cos), rotary_sin=_f32(torch, sin),
                          rotary_interleaved=interleaved)
     torch.cuda.synchronize()
@@ -237,8 +238,8 @@ def test_fp8_rope_append_is_the_recipe_on_the_fp32_value(fa, torch_cuda, fmt, d,
     print(f"codes the unfused path (a 16-bit rounding first) would store differently: {int((ri.fp8_codes(y16, ks) != k8).sum())}")
     case = _Case(torch, d, fmt, ps, nnew, seed=500 + d + ps, fp8=True)
     want_k, want_v = case.expected(k8, v8)
-    dq = ta._dev16(torch, q, fmt)
-    case.rope_append(fa, ta._dev16(torch, k_new, fmt), ta._dev16(torch, v_new, fmt), ta._ints(torch, LENS), cos, sin, interleaved, q=dq,
+    dq = cm.dev16(torch, q, fmt)
+    case.rope_append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), ta._ints(torch, LENS), cos, sin, interleaved, q=dq,
                      k_scale=ta._scales(torch, ks), v_scale=ta._scales(torch, vs))
     got_k = case.dk.view(torch.uint8).cpu().numpy()
     print(f"fp8 K bytes differing: {int((got_k != want_k).sum())} of {want_k.size}")
@@ -264,7 +265,7 @@ def test_fp8_every_code_and_tie_through_the_rope_kernels(fa, torch_cuda, fmt, ps
         assert set(k8[0][h].ravel().tolist()) == set(f8.FINITE_CODES.tolist())
     case = _Case(torch, d, fmt, ps, nnew, seed=600 + ps, fp8=True)
     want_k, want_v = case.expected(k8, v8)
-    case.rope_append(fa, ta._dev16(torch, k_new, fmt), ta._dev16(torch, v_new, fmt), ta._ints(torch, LENS), cos, sin, interleaved,
+    case.rope_append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), ta._ints(torch, LENS), cos, sin, interleaved,
                      k_scale=ta._scales(torch, K_SCALES), v_scale=ta._scales(torch, V_SCALES))
     case.check(want_k, want_v, f"fp8 identity ps={ps}")
 
@@ -288,9 +289,9 @@ def test_rope_seqlens_out(fa, torch_cuda, ps, fp8):
     want_lens = ta._ints(torch, ai.lens_after(LENS, B, nnew, NCAP))
     for mode in ("separate", "in place", "none"):
         case = _Case(torch, d, fmt, ps, nnew, seed=77 + ps, fp8=fp8)
-        dlens, dq = ta._ints(torch, LENS), ta._dev16(torch, q, fmt)
+        dlens, dq = ta._ints(torch, LENS), cm.dev16(torch, q, fmt)
         out = {"separate": torch.full((B,), -7, dtype=torch.int32, device="cuda"), "in place": dlens, "none": None}[mode]
-        case.rope_append(fa, ta._dev16(torch, k_new, fmt), ta._dev16(torch, v_new, fmt), dlens, cos, sin, False, q=dq, out=out)
+        case.rope_append(fa, cm.dev16(torch, k_new, fmt), cm.dev16(torch, v_new, fmt), dlens, cos, sin, False, q=dq, out=out)
         case.check(*case.expected(src_k, src_v), mode)
         assert ta._bytes_equal(torch, dq, want_q), mode
         if mode == "none":
@@ -335,7 +336,7 @@ def test_captured_rope_append_then_decode_follows_a_growing_cache(fa, oracle, to
         dtable = torch.from_numpy(table).cuda()
     else:
         host_k, host_v = k0, v0
-    to_dev = (lambda a: ta._dev8(torch, a)) if fp8 else (lambda a: ta._dev16(torch, a, fmt))
+    to_dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     dscale = dict(k_scale=ta._scales(torch, ks), v_scale=ta._scales(torch, vs)) if fp8 else {}
     dcos, dsin = _f32(torch, cos), _f32(torch, sin)
     ws = torch.empty(max(fa.kvcache_workspace_bytes(B, HKV, G, 1, NCAP, d), 1), dtype=torch.uint8, device="cuda")
@@ -362,7 +363,7 @@ def test_captured_rope_append_then_decode_follows_a_growing_cache(fa, oracle, to
         host_k, host_v = place(host_k, stored_k(kn, lens_h)), place(host_v, stored_v(vn))
         q_rot = ri.rotated_rows16(qn, fmt, lens_h, NCAP, cos, sin, False)
         lens_h = list(ai.lens_after(lens_h, B, 1, NCAP))
-        o = decode(ta._dev16(torch, q_rot, fmt), to_dev(host_k), to_dev(host_v), ta._ints(torch, lens_h))
+        o = decode(cm.dev16(torch, q_rot, fmt), to_dev(host_k), to_dev(host_v), ta._ints(torch, lens_h))
         torch.cuda.synchronize()
         assert torch.isfinite(o).all()
         want.append((o.clone(), q_rot, list(lens_h)))
@@ -371,7 +372,7 @@ def test_captured_rope_append_then_decode_follows_a_growing_cache(fa, oracle, to
     dk, dv = to_dev(pool_k if ps else k0), to_dev(pool_v if ps else v0)
     dlens = ta._ints(torch, LENS)
     kn, vn, qn = new_rows(0)
-    dkn, dvn, dq = ta._dev16(torch, kn, fmt), ta._dev16(torch, vn, fmt), ta._dev16(torch, qn, fmt)
+    dkn, dvn, dq = cm.dev16(torch, kn, fmt), cm.dev16(torch, vn, fmt), cm.dev16(torch, qn, fmt)
     scratch_k, scratch_v, scratch_lens, scratch_q = dk.clone(), dv.clone(), dlens.clone(), dq.clone()
     append(dkn, dvn, scratch_q, scratch_k, scratch_v, scratch_lens)
     decode(scratch_q, scratch_k, scratch_v, scratch_lens)
@@ -383,7 +384,7 @@ def test_captured_rope_append_then_decode_follows_a_growing_cache(fa, oracle, to
     assert dlens.tolist() == list(LENS)   # a capture runs nothing
     for step in range(steps):
         kn, vn, qn = new_rows(step)
-        dkn.copy_(ta._dev16(torch, kn, fmt)), dvn.copy_(ta._dev16(torch, vn, fmt)), dq.copy_(ta._dev16(torch, qn, fmt))
+        dkn.copy_(cm.dev16(torch, kn, fmt)), dvn.copy_(cm.dev16(torch, vn, fmt)), dq.copy_(cm.dev16(torch, qn, fmt))
         ws.fill_(0xFF), o.fill_(float("nan"))
         graph.replay()
         torch.cuda.synchronize()

@@ -20,13 +20,13 @@ import functools
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 
 pytestmark = pytest.mark.gpu
 
-MAX_ABS, REL_L2, P_EPS = di.MAX_ABS, di.REL_L2, di.P_EPS   # the project's bounds (tests/test_gpu_parity.py is their origin)
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 LAYOUTS = [pytest.param(0, id="contiguous"), pytest.param(16, id="p16"), pytest.param(64, id="p64")]
 
 
@@ -43,10 +43,6 @@ def _tdtype(torch, fmt):
 
 def _q_dev(torch, qb, fmt, B, Hq):
     return torch.from_numpy(np.array(qb).view(np.int16)).cuda().view(_tdtype(torch, fmt)).view(B, Hq, qb.shape[1], qb.shape[2])
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _widened(torch, codes, fmt):
@@ -72,31 +68,31 @@ def _run(fa, torch, dq, k8, v8, lens, ps, seed, k_scale=None, v_scale=None, caus
     kw = dict(k_scale=_scales(torch, k_scale), v_scale=_scales(torch, v_scale), cache_seqlens=dl, causal=causal, scale=scale,
               out_dtype=out_dtype, return_lse=True, workspace=_nan_workspace(torch, need))
     if ps == 0:
-        o, lse = fa.fa_forward_kvcache_fp8(dq, _dev8(torch, k8), _dev8(torch, v8), **kw)
+        o, lse = fa.fa_forward_kvcache_fp8(dq, cm.dev8(torch, k8), cm.dev8(torch, v8), **kw)
     else:
         assert fa.kvcache_paged_workspace_bytes(B, Hkv, Hq // Hkv, Nq, Ncap // ps, ps, d) == need
-        kp, vp, table = f8.scatter(k8, v8, lens, ps, seed)
-        o, lse = fa.fa_forward_kvcache_paged_fp8(dq, _dev8(torch, kp), _dev8(torch, vp), torch.from_numpy(table).cuda(), **kw)
+        kp, vp, table = cm.scatter(k8, v8, lens, ps, seed, nan=f8.NAN_CODES[0])
+        o, lse = fa.fa_forward_kvcache_paged_fp8(dq, cm.dev8(torch, kp), cm.dev8(torch, vp), torch.from_numpy(table).cuda(), **kw)
     torch.cuda.synchronize()
     assert o.shape == dq.shape and lse.shape == dq.shape[:3] and lse.dtype == torch.float32
     return o, lse, need
 
 
-def _check(oracle, o, lse, want, want_lse, fmt, what, max_abs=MAX_ABS):
+def _check(oracle, o, lse, want, want_lse, fmt, what, max_abs=cm.MAX_ABS):
     got = o.float().cpu().numpy().reshape(want.shape)
     got_lse = lse.cpu().numpy().reshape(want_lse.shape)
     ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
     live = np.isfinite(want_lse)
     le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {max_abs:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
+    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {max_abs:.1e} {cm.REL_L2[fmt]:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert np.isfinite(got).all(), what + ": O is not finite"
     assert not np.isnan(got_lse).any(), what + ": NaN in lse"
-    assert ma <= max_abs and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
+    assert ma <= max_abs and rl <= cm.REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
     # rows without a key: exact zeros and -inf; every other row: a finite lse within the bound
     assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
     assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
     assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
 
 
 # ---- bit equality on all finite codes ----------------------------------------------------------------------------------------------
@@ -205,7 +201,7 @@ def _quantised_inputs(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed):
 @functools.lru_cache(maxsize=None)
 def _reference(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed, lens, causal):
     q, _, _, _, kd, vd, _, _ = _quantised_inputs(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed)
-    out, lse = di.expected(oracle, q, kd, vd, lens, B, Hkv, G, Nq, causal)
+    out, lse = cm.expected(oracle, q, kd, vd, lens, B, Hkv, G, Nq, causal)
     out.setflags(write=False), lse.setflags(write=False)
     return out, lse
 
@@ -220,7 +216,7 @@ def test_oracle_parity(fa, oracle, torch_cuda, fmt, d, ps, Ncap):
     _, qb, k8, v8, _, _, ks, vs = _quantised_inputs(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, 2201)
     want, want_lse = _reference(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, 2201, lens, False)
     dq = _q_dev(torch_cuda, qb, fmt, B, Hkv * G)
-    pk, pv = f8.poisoned(k8, lens), f8.poisoned(v8, lens)
+    pk, pv = (cm.poisoned(x, lens, nan=f8.NAN_CODES[0]) for x in (k8, v8))
     for out_same in (False, True):
         o, lse, need = _run(fa, torch_cuda, dq, pk, pv, lens, ps, seed=ps + d, k_scale=ks, v_scale=vs,
                             out_dtype=_tdtype(torch_cuda, fmt) if out_same else None)
@@ -237,7 +233,7 @@ def test_single_pass(fa, oracle, torch_cuda, fmt, d, ps):
     _, qb, k8, v8, _, vd, ks, vs = _quantised_inputs(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, 2301)
     want, want_lse = _reference(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, 2301, lens, False)
     dq = _q_dev(torch_cuda, qb, fmt, B, Hkv * G)
-    pk, pv = f8.poisoned(k8, lens), f8.poisoned(v8, lens)
+    pk, pv = (cm.poisoned(x, lens, nan=f8.NAN_CODES[0]) for x in (k8, v8))
     for out_same in (False, True):
         o, lse, need = _run(fa, torch_cuda, dq, pk, pv, lens, ps, seed=ps + d + 1, k_scale=ks, v_scale=vs,
                             out_dtype=_tdtype(torch_cuda, fmt) if out_same else None)
@@ -260,7 +256,7 @@ def test_mask_and_degenerate_rows(fa, oracle, torch_cuda, fmt, d, causal, ps):
     dead = np.isinf(want_lse).reshape(B, Hkv * G, Nq)
     assert dead[0].all() and (dead[1].all(0).tolist() == [causal] * 3 + [False] * 2) and not dead[2:].any()
     dq = _q_dev(torch_cuda, qb, fmt, B, Hkv * G)
-    o, lse, need = _run(fa, torch_cuda, dq, f8.poisoned(k8, lens), f8.poisoned(v8, lens), lens, ps, seed=ps + d + 2, k_scale=ks,
+    o, lse, need = _run(fa, torch_cuda, dq, *(cm.poisoned(x, lens, nan=f8.NAN_CODES[0]) for x in (k8, v8)), lens, ps, seed=ps + d + 2, k_scale=ks,
                         v_scale=vs, causal=causal)
     assert need > 0
     _check(oracle, o, lse, want, want_lse, fmt, f"fp8 mask + degenerate rows d={d} fmt={fmt} layout={ps} causal={causal}")
@@ -276,10 +272,10 @@ def test_scale_zero_with_half_k_scale(fa, oracle, torch_cuda, fmt, d, causal, ps
     key.  The weights are all exactly 1, so the usual bounds hold with room to spare."""
     B, Hkv, G, Nq, Ncap, lens = 4, 2, 2, 5, 1024, (0, 2, 66, 1021)
     _, qb, k8, v8, _, vd, _, vs = _quantised_inputs(fa, oracle, B, Hkv, G, Nq, Ncap, d, fmt, 2501)
-    want, want_lse = di.uniform_expected(vd, lens, B, Hkv, G, Nq, causal)
+    want, want_lse = cm.uniform_expected(vd, lens, B, Hkv, G, Nq, causal)
     dq = _q_dev(torch_cuda, qb, fmt, B, Hkv * G)
     for scale in (0.0, -0.0):
-        o, lse, need = _run(fa, torch_cuda, dq, f8.poisoned(k8, lens), f8.poisoned(v8, lens), lens, ps, seed=ps + d + 3,
+        o, lse, need = _run(fa, torch_cuda, dq, *(cm.poisoned(x, lens, nan=f8.NAN_CODES[0]) for x in (k8, v8)), lens, ps, seed=ps + d + 3,
                             k_scale=(0.5, 0.5), v_scale=vs, causal=causal, scale=scale)
         assert need > 0
         _check(oracle, o, lse, want.astype(np.float32), want_lse, fmt, f"fp8 scale {scale} d={d} fmt={fmt} layout={ps} causal={causal}")
@@ -311,7 +307,7 @@ def test_graph_replay_follows_table_lengths_and_scales(fa, torch_cuda):
         for b, L in enumerate(lengths):
             for pi in range(max_pages):
                 if pi >= di.live_pages(L, ps):
-                    tb[b, pi] = f8.GARBAGE[pi % 2]
+                    tb[b, pi] = cm.GARBAGE[pi % 2]
                     continue
                 page, n = int(perm[nxt]), min(ps, L - pi * ps)
                 nxt += 1

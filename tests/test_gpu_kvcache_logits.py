@@ -15,6 +15,7 @@ import functools
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import logit_inputs as li
@@ -22,8 +23,7 @@ import window_inputs as wi
 
 pytestmark = pytest.mark.gpu
 
-MAX_ABS, REL_L2, P_EPS = di.MAX_ABS, di.REL_L2, di.P_EPS
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 LAUNCHES = [pytest.param(*x, id=f"{x[0]}-W{x[1]}-{'causal' if x[2] else 'full'}-{x[3]}") for x in li.LAUNCHES]
 FP8_LAUNCHES = [p for p in LAUNCHES if p.values[0] in ("one_pass", "split") and p.values[3] in ("sinks", "both")]
 
@@ -37,14 +37,6 @@ def torch_cuda():
 
 def _tdtype(torch, fmt):
     return torch.float16 if fmt == 0 else torch.bfloat16
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.array(bits).view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.array(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -74,7 +66,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
     need = fa.kvcache_window_workspace_bytes(B, Hkv, Hq // Hkv, Nq, Ncap, d, W)
     if want_S is not None:
         assert di.splits_of(need, B * Hkv, (Hq // Hkv) * Nq, d) == want_S
-    dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     kw = dict(cache_seqlens=_ints(torch, lens), causal=causal, scale=scale, return_lse=True, workspace=_nan_workspace(torch, need),
               window=W, sinks=_floats(torch, sinks), softcap=softcap)
     if fp8:
@@ -83,7 +75,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
         o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(kc), dev(vc), **kw)
     else:
         assert fa.kvcache_paged_window_workspace_bytes(B, Hkv, Hq // Hkv, Nq, Ncap // ps, ps, d, W) == need
-        kp, vp, table = wi.scatter(kc, vc, lens, Nq, W, ps, seed, nan=wi.NAN8 if fp8 else di.NAN16)
+        kp, vp, table = cm.scatter(kc, vc, lens, ps, seed, Nq, W, nan=wi.NAN8 if fp8 else cm.NAN16)
         o, lse = (fa.fa_forward_kvcache_paged_fp8 if fp8 else fa.fa_forward_kvcache_paged)(
             dq, dev(kp), dev(vp), torch.from_numpy(table).cuda(), **kw)
     torch.cuda.synchronize()
@@ -93,7 +85,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
 
 def _nokey(lens, B, Hq, Nq, Ncap, causal):
     """[B*Hq, Nq] bool: rows that see no key"""
-    return np.array([[c == 0 for c in di.limits(di.clamp(lens[b], Ncap), Nq, causal)] for b in range(B) for _ in range(Hq)])
+    return np.array([cm.row_limits(cm.clamp(lens[b], Ncap), Nq, Nq, causal)[1] == 0 for b in range(B) for _ in range(Hq)])
 
 
 def _check(oracle, o, lse, want, want_lse, fmt, what, nokey=None, sinks=None):
@@ -105,14 +97,14 @@ def _check(oracle, o, lse, want, want_lse, fmt, what, nokey=None, sinks=None):
     ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
     live = np.isfinite(want_lse)
     le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
+    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {cm.MAX_ABS:.1e} {cm.REL_L2[fmt]:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert np.isfinite(got).all(), what + ": O is not finite"
     assert not np.isnan(got_lse).any(), what + ": NaN in lse"
-    assert ma <= MAX_ABS and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
+    assert ma <= cm.MAX_ABS and rl <= cm.REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
     assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
     assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key or a sink has lse != -inf"
     assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
     if nokey is not None:
         assert (got[nokey] == 0.0).all(), what + ": a row without a key is not exactly zero"
         if sinks is not None:
@@ -125,8 +117,8 @@ def _case(oracle, torch, name, d, fmt, W):
     c = wi.CASES[name]
     B, Hkv, G, Nq, Ncap = _shape(c)
     _, (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, c["seed"])
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    return c, dq, wi.poisoned(kb, c["lens"], Nq, W), wi.poisoned(vb, c["lens"], Nq, W)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    return c, dq, *(cm.poisoned(x.reshape(B, Hkv, Ncap, d), c["lens"], Nq, W) for x in (kb, vb))
 
 
 # ---- 1. parity of the contiguous entry; the paged entry returns its bits ----------------------------------------------------------
@@ -190,14 +182,14 @@ def test_fp8(fa, oracle, torch_cuda, fmt, d, name, W, causal, variant):
     sinks, softcap = li.options(variant, Hkv * G)
     q, qb, k8, v8, kd, vd, ks, vs = _quantised(fa, oracle, name, d, fmt)
     assert max(abs(np.log(s)) for s in ks) > 1.0   # k_scale != 1 by far
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    pk, pv = wi.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), wi.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    pk, pv = cm.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), cm.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
     wide = [torch.from_numpy(x).view(torch.float8_e4m3fn).to(_tdtype(torch, fmt)).view(torch.int16).numpy().view(np.uint16) for x in (pk, pv)]
     sc = 2.0 ** -7 / np.sqrt(d)
     S = li.want_S(name, W)
     base, base_lse = _run(fa, torch, dq, wide[0], wide[1], c["lens"], W, causal, scale=sc, fmt=fmt, want_S=S, sinks=sinks, softcap=softcap)
     assert torch.isfinite(base).all() and not torch.isnan(base_lse).any()
-    want, want_lse = li.expected_f64(q, kd, vd, c["lens"], B, Hkv, G, Nq, causal, W, softcap=softcap, sinks=sinks)
+    want, want_lse = cm.expected_f64(q, kd, vd, c["lens"], B, Hkv, G, Nq, causal, W, softcap=softcap, sinks=sinks)
     for ps in (0, 16):
         o, lse = _run(fa, torch, dq, pk, pv, c["lens"], W, causal, ps=ps, seed=ps + d, scale=sc, want_S=S, sinks=sinks, softcap=softcap)
         assert torch.equal(o, base) and torch.equal(lse, base_lse), f"fp8 layout {ps}: not the 16-bit entry's bits"
@@ -244,15 +236,15 @@ def test_descriptor_without_options_is_each_of_the_eight_entries(fa, oracle, tor
         kw = dict(cache_seqlens=dl, causal=True, return_lse=True, window=W)
         k8, v8 = (torch.from_numpy(np.array(x).view(np.int16)).view(_tdtype(torch, fmt)).float().clamp(-400, 400).nan_to_num(0.0)
                   .to(torch.float8_e4m3fn).view(torch.uint8).numpy() for x in (kc, vc))
-        k8, v8 = wi.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), wi.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
+        k8, v8 = cm.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), cm.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
         sc = (_floats(torch, [0.5, 2.0]), _floats(torch, [3.0, 0.25]))
         for paged in (False, True):
             for fp8 in (False, True):
                 kk, vv = (k8, v8) if fp8 else (kc, vc)
-                dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+                dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
                 table = None
                 if paged:
-                    kk, vv, table = wi.scatter(kk, vv, c["lens"], Nq, W, 16, 77, nan=wi.NAN8 if fp8 else di.NAN16)
+                    kk, vv, table = cm.scatter(kk, vv, c["lens"], 16, 77, Nq, W, nan=wi.NAN8 if fp8 else cm.NAN16)
                     table = torch.from_numpy(table).cuda()
                 dk, dv = dev(kk), dev(vv)
                 fn = getattr(fa, "fa_forward_kvcache" + "_paged" * paged + "_fp8" * fp8)
@@ -298,12 +290,12 @@ def test_sink_census(fa, oracle, torch_cuda, fmt, d, name, W, causal):
     B, Hkv, G, Nq, Ncap = _shape(c)
     z = li.census_case(oracle, name, d, fmt, W, causal)
     qb, kb, vb = z["bits"]
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    kc, vc = wi.poisoned(kb, c["lens"], Nq, W), wi.poisoned(vb, c["lens"], Nq, W)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), c["lens"], Nq, W) for x in (kb, vb))
     to8 = lambda bits: oracle.decode16(np.array(bits), fmt)   # K = 0 and V in {0, m_h <= 8}: exact in e4m3fn
     k8, v8 = (torch.from_numpy(to8(x).reshape(B, Hkv, Ncap, d)).to(torch.float8_e4m3fn).view(torch.uint8).numpy() for x in (kb, vb))
     assert np.array_equal(f8.decode(v8).reshape(-1), to8(vb).reshape(-1))
-    k8, v8 = wi.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), wi.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
+    k8, v8 = cm.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), cm.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
     sinks = li.census_sinks(Hkv * G)
     for ps in (0, 16):
         for fp8 in (False, True):
@@ -327,7 +319,7 @@ def test_sinks_far_from_the_logits(fa, oracle, torch_cuda, fmt, d, name, W):
     nokey = _nokey(c["lens"], B, Hkv * G, Nq, Ncap, causal)
     for a in (200.0, -200.0):
         sinks = np.full(Hkv * G, a, np.float32)
-        want, want_lse = li.expected_f64(q, k, v, c["lens"], B, Hkv, G, Nq, causal, W, sinks=sinks)
+        want, want_lse = cm.expected_f64(q, k, v, c["lens"], B, Hkv, G, Nq, causal, W, sinks=sinks)
         o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, causal, fmt=fmt, want_S=li.want_S(name, W), sinks=sinks)
         assert torch.isfinite(lse).all()
         _check(oracle, o, lse, want, want_lse, fmt, f"sink {a} {name} d={d} fmt={fmt}", nokey=nokey, sinks=sinks)
@@ -358,15 +350,15 @@ def test_softcap_under_the_masks(fa, oracle, torch_cuda, fmt, d, W):
     for ps in (0, 16):
         o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, True, ps=ps, seed=5, fmt=fmt, softcap=li.SOFTCAP)
         _check(oracle, o, lse, want, want_lse, fmt, f"softcap under the mask W={W} layout={ps} d={d} fmt={fmt}", nokey=nokey)
-    uni, uni_lse = wi.uniform_expected(v, c["lens"], B, Hkv, G, Nq, True, W)
+    uni, uni_lse = cm.uniform_expected(v, c["lens"], B, Hkv, G, Nq, True, W)
     for scale in (0.0, -0.0):
         o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, True, scale=scale, fmt=fmt, softcap=li.SOFTCAP)
         _check(oracle, o, lse, uni, uni_lse, fmt, f"scale {scale} under the cap W={W} d={d} fmt={fmt}", nokey=nokey)
     neg = -1.0 / np.sqrt(d)
-    want, want_lse = li.expected_f64(q, -k, v, c["lens"], B, Hkv, G, Nq, True, W, softcap=li.SOFTCAP)
+    want, want_lse = cm.expected_f64(q, -k, v, c["lens"], B, Hkv, G, Nq, True, W, softcap=li.SOFTCAP)
     o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, True, scale=neg, fmt=fmt, softcap=li.SOFTCAP)
     _check(oracle, o, lse, want, want_lse, fmt, f"negative scale under the cap W={W} d={d} fmt={fmt}", nokey=nokey)
-    assert np.abs(want - li.reference(oracle, name, d, fmt, W, True, "softcap")[0]).max() >= 3 * MAX_ABS   # the sign matters
+    assert np.abs(want - li.reference(oracle, name, d, fmt, W, True, "softcap")[0]).max() >= 3 * cm.MAX_ABS   # the sign matters
 
 
 # ---- 7. graph -------------------------------------------------------------------------------------------------------------------------
@@ -381,7 +373,7 @@ def test_captured_append_rope_then_decode_with_sinks_and_softcap(fa, oracle, tor
     (q, k, v), (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, steps, Ncap, d, fmt, g["seed"])
     kb4, vb4, qb4 = kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d), qb.reshape(B, Hq, steps, d)
     lens = list(g["start"])
-    dk, dv = _dev16(torch, di.poisoned(kb, lens, B, Hkv), fmt), _dev16(torch, di.poisoned(vb, lens, B, Hkv), fmt)
+    dk, dv = (cm.dev16(torch, cm.poisoned(x, lens), fmt) for x in (kb4, vb4))
     dl = _ints(torch, lens)
     # a rotation by angle 0 (cos 1, sin 0): the fused append is on the captured path, and K and Q reach the cache as they were drawn
     cos = torch.ones(Ncap, d // 2, dtype=torch.float32, device="cuda")
@@ -391,7 +383,7 @@ def test_captured_append_rope_then_decode_with_sinks_and_softcap(fa, oracle, tor
 
     def new_rows(t):
         rows = [np.stack([src[b, :, lens[b] + t:lens[b] + t + 1] for b in range(B)]) for src in (kb4, vb4)]
-        return _dev16(torch, rows[0], fmt), _dev16(torch, rows[1], fmt), _dev16(torch, qb4[:, :, t:t + 1], fmt)
+        return cm.dev16(torch, rows[0], fmt), cm.dev16(torch, rows[1], fmt), cm.dev16(torch, qb4[:, :, t:t + 1], fmt)
 
     need = fa.kvcache_window_workspace_bytes(B, Hkv, G, 1, Ncap, d, W)
     ws = _nan_workspace(torch, need)
@@ -421,10 +413,10 @@ def test_captured_append_rope_then_decode_with_sinks_and_softcap(fa, oracle, tor
         now = [L + t + 1 for L in lens]
         assert dl.tolist() == now
         qt = np.ascontiguousarray(q.reshape(B * Hq, steps, d)[:, t:t + 1])
-        want, want_lse = li.expected_f64(qt, k, v, now, B, Hkv, G, 1, True, W, softcap=li.SOFTCAP, sinks=sinks)
+        want, want_lse = cm.expected_f64(qt, k, v, now, B, Hkv, G, 1, True, W, softcap=li.SOFTCAP, sinks=sinks)
         _check(oracle, o, lse, want, want_lse, fmt, f"graph step {t} lengths {now}")
         if t == steps - 1:
-            old, old_lse = li.expected_f64(qt, k, v, now, B, Hkv, G, 1, True, W, softcap=li.SOFTCAP, sinks=li.sinks_for(Hq))
+            old, old_lse = cm.expected_f64(qt, k, v, now, B, Hkv, G, 1, True, W, softcap=li.SOFTCAP, sinks=li.sinks_for(Hq))
             assert np.abs(old_lse - want_lse).min() >= li.LSE_MOVES   # the rewritten vector shows on every row
 
 
@@ -440,8 +432,8 @@ def test_ex_ops_are_the_front_ends(fa, oracle, torch_cuda):
     B, Hkv, G, Nq, Ncap = _shape(c)
     dl, ds = _ints(torch, c["lens"]), _floats(torch, li.sinks_for(Hkv * G))
     sc = 1.0 / np.sqrt(d)
-    kp, vp, table = wi.scatter(kc, vc, c["lens"], Nq, W, 16, 3)
-    dk, dv, dkp, dvp, dt = _dev16(torch, kc, fmt), _dev16(torch, vc, fmt), _dev16(torch, kp, fmt), _dev16(torch, vp, fmt), torch.from_numpy(table).cuda()
+    kp, vp, table = cm.scatter(kc, vc, c["lens"], 16, 3, Nq, W)
+    dk, dv, dkp, dvp, dt = cm.dev16(torch, kc, fmt), cm.dev16(torch, vc, fmt), cm.dev16(torch, kp, fmt), cm.dev16(torch, vp, fmt), torch.from_numpy(table).cuda()
     z8 = lambda x: torch.where(torch.isnan(x), torch.zeros_like(x), x).clamp(-400, 400).to(torch.float8_e4m3fn)
     dk8, dv8, dkp8, dvp8 = z8(dk.float()), z8(dv.float()), z8(dkp.float()), z8(dvp.float())
     s8 = _floats(torch, [0.5, 2.0])

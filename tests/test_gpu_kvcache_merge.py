@@ -4,7 +4,7 @@ Inputs, the float64 rule, the float64 reference of the composed call and the der
 tier, tests/test_merge_inputs.py, shows that no parity launch here passes on a merge that drops a part, doubles one, takes lse for
 log2 units or ignores the strides).  The merge is held against the float64 rule on the SAME parts within the derived bound; the
 composed call against the float64 reference on the concatenated keys within the project's bounds for two kernels in a row
-(di.peaked_tol(kernels=2), di.REL_L2, 2 * di.P_EPS on lse); the exact cases, the ties and the graph replay are bit comparisons.
+(cm.peaked_tol(kernels=2), cm.REL_L2, 2 * cm.P_EPS on lse); the exact cases, the ties and the graph replay are bit comparisons.
 
 Poison: rows a part's strides do not name hold NaN; every cache row at or past a length (prefix and suffix) holds NaN bit patterns;
 every pool page no table names holds NaN and every dead table entry garbage; the blocks the front end's own allocations reuse
@@ -16,14 +16,14 @@ import numpy as np
 import pytest
 
 import census_inputs as ci
-import decode_inputs as di
+import common_inputs as cm
 import fp8_inputs as f8
 import logit_inputs as li
 import merge_inputs as mi
 
 pytestmark = pytest.mark.gpu
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 CASES = [pytest.param(*c, id=f"Nq{c[0]}-{'causal' if c[1] else 'full'}-{c[2]}") for c in mi.CASES]
 
 
@@ -36,14 +36,6 @@ def torch_cuda():
 
 def _tdtype(torch, name):
     return {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32, 0: torch.float16, 1: torch.bfloat16}[name]
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.array(bits).view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.array(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -65,8 +57,8 @@ def _dev_state(torch, oracle, o, dtype):
         return torch.from_numpy(np.array(o, np.float32)).cuda()
     fmt = 0 if dtype == "f16" else 1
     bits = oracle.encode16(np.nan_to_num(o), fmt)
-    bits[np.isnan(o)] = di.NAN16
-    return _dev16(torch, bits, fmt)
+    bits[np.isnan(o)] = cm.NAN16
+    return cm.dev16(torch, bits, fmt)
 
 
 def _poison_allocator(torch, sizes):
@@ -179,13 +171,10 @@ def _device_inputs(torch, oracle, shape_name, Nq, d, fmt, fp8, lens=None, P=None
     P = c["P"] if P is None else P
     x = mi.inputs(oracle, shape_name, Nq, d, fmt, fp8)
     kpb, vpb, ksb, vsb = x["bits"]
-    dq = _dev16(torch, x["qb"], fmt).view(B, Hkv * G, Nq, d)
-    if fp8:
-        pre = [_dev8(torch, f8.poisoned(a.reshape(1, Hkv, c["Pcap"], d), [P])) for a in (kpb, vpb)]
-        suf = [f8.poisoned(a.reshape(B, Hkv, c["Ncap"], d), lens) for a in (ksb, vsb)]
-    else:
-        pre = [_dev16(torch, di.poisoned(a, [P], 1, Hkv), fmt) for a in (kpb, vpb)]
-        suf = [di.poisoned(a, lens, B, Hkv) for a in (ksb, vsb)]
+    dq = cm.dev16(torch, x["qb"], fmt).view(B, Hkv * G, Nq, d)
+    dev, nan = ((lambda a: cm.dev8(torch, a)), f8.NAN_CODES[0]) if fp8 else ((lambda a: cm.dev16(torch, a, fmt)), cm.NAN16)
+    pre = [dev(cm.poisoned(a.reshape(1, Hkv, c["Pcap"], d), [P], nan=nan)) for a in (kpb, vpb)]
+    suf = [cm.poisoned(a.reshape(B, Hkv, c["Ncap"], d), lens, nan=nan) for a in (ksb, vsb)]
     return dict(x=x, c=c, dq=dq, pre=pre, suf=suf, lens=lens, P=P, k_scale=_floats(torch, x["k_scale"]), v_scale=_floats(torch, x["v_scale"]))
 
 
@@ -195,16 +184,14 @@ def _composed(fa, torch, t, fmt, fp8, causal, variant, paged, seed=0, out_dtype=
     B, Hkv, G = c["B"], c["Hkv"], c["G"]
     Nq, d = t["dq"].shape[2:]
     sinks, softcap = li.options(variant, Hkv * G)
-    dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     kw = dict(prefix_len=_ints(torch, [t["P"]]) if dP is None else dP, cache_seqlens=_ints(torch, t["lens"]) if dlens is None else dlens,
               causal=causal, return_lse=True, softcap=softcap, out_dtype=out_dtype,
               sinks=(_floats(torch, sinks) if dsinks is None else dsinks) if sinks is not None else None)
     if fp8:
         kw.update(k_scale=t["k_scale"], v_scale=t["v_scale"])
     if paged:
-        kp, vp, table = (f8.scatter(t["suf"][0], t["suf"][1], t["lens"], c["page"], seed) if fp8
-                         else di.scatter(t["suf"][0].reshape(B * Hkv, c["Ncap"], d), t["suf"][1].reshape(B * Hkv, c["Ncap"], d), t["lens"],
-                                         B, Hkv, c["page"], seed))
+        kp, vp, table = cm.scatter(t["suf"][0], t["suf"][1], t["lens"], c["page"], seed, nan=f8.NAN_CODES[0] if fp8 else cm.NAN16)
         kw.update(block_table=torch.from_numpy(table).cuda())
         ks, vs = dev(kp), dev(vp)
     else:
@@ -219,7 +206,7 @@ def _composed(fa, torch, t, fmt, fp8, causal, variant, paged, seed=0, out_dtype=
 
 
 def _check(oracle, o, lse, want, want_lse, fmt, vmax, what):
-    """the project's bounds for two kernels in a row: di.peaked_tol(fmt, vmax, kernels=2) and di.REL_L2 for O, 2 * di.P_EPS absolute
+    """the project's bounds for two kernels in a row: cm.peaked_tol(fmt, vmax, kernels=2) and cm.REL_L2 for O, 2 * cm.P_EPS absolute
     for lse; every figure is printed before it is judged"""
     want = np.asarray(want, np.float32)
     got = o.float().cpu().numpy().reshape(want.shape)
@@ -227,12 +214,12 @@ def _check(oracle, o, lse, want, want_lse, fmt, vmax, what):
     assert np.isfinite(want_lse).all()
     ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
     le = float(np.abs(got_lse - want_lse).max())
-    tol = di.peaked_tol(fmt, vmax, kernels=2)
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {tol:.2e} {di.REL_L2[fmt]:.1e} {2 * di.P_EPS[fmt]:.2e})")
+    tol = cm.peaked_tol(fmt, vmax, kernels=2)
+    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {tol:.2e} {cm.REL_L2[fmt]:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert np.isfinite(got).all(), what + ": O is not finite"
     assert np.isfinite(got_lse).all(), what + ": lse is not finite"
-    assert ma <= tol and rl <= di.REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
-    assert le <= 2 * di.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert ma <= tol and rl <= cm.REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
+    assert le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
 
 
 @pytest.mark.parametrize("Nq,causal,variant", CASES)
@@ -288,7 +275,7 @@ def test_ties(fa, oracle, torch_cuda, fmt, d):
     B, Hkv, G = c["B"], c["Hkv"], c["G"]
     lens = (5, 1, 150)
     t = _device_inputs(torch, oracle, "base", Nq, d, fmt, False, lens=lens, P=0)
-    ks, vs = _dev16(torch, t["suf"][0], fmt), _dev16(torch, t["suf"][1], fmt)
+    ks, vs = cm.dev16(torch, t["suf"][0], fmt), cm.dev16(torch, t["suf"][1], fmt)
     sinks = _floats(torch, li.sinks_for(Hkv * G))
     for out_dtype in (torch.float32, _tdtype(torch, fmt)):
         plain, plain_lse = fa.fa_forward_kvcache(t["dq"], ks, vs, _ints(torch, lens), causal=causal, return_lse=True, out_dtype=out_dtype,
@@ -321,9 +308,9 @@ def test_census(fa, oracle, torch_cuda, fmt, d, causal):
     Nq = 3
     z = mi.census_case(oracle, Nq, d, fmt, causal)
     assert (z["cnt"] == P).any()
-    dq = _dev16(torch, z["qb"], fmt).view(B, Hkv * G, Nq, d)
-    pre = [_dev16(torch, di.poisoned(a, [P], 1, Hkv), fmt) for a in z["prefix"]]
-    suf = [di.poisoned(a, c["lens"], B, Hkv) for a in z["suffix"]]
+    dq = cm.dev16(torch, z["qb"], fmt).view(B, Hkv * G, Nq, d)
+    pre = [cm.dev16(torch, cm.poisoned(a.reshape(1, Hkv, Pcap, d), [P]), fmt) for a in z["prefix"]]
+    suf = [cm.poisoned(a.reshape(B, Hkv, Ncap, d), c["lens"]) for a in z["suffix"]]
     t = dict(c=c, dq=dq, pre=pre, suf=suf, lens=c["lens"], P=P)
     for paged in (False, True):
         o, lse = _composed(fa, torch, t, fmt, False, causal, "none", paged, seed=3)
@@ -342,7 +329,7 @@ def test_captured_call_follows_lengths_and_sinks(fa, oracle, torch_cuda):
     c = mi.SHAPE
     B, Hkv, G = c["B"], c["Hkv"], c["G"]
     t = _device_inputs(torch, oracle, "base", Nq, d, fmt, False, lens=(c["Ncap"],) * B, P=c["Pcap"])   # nothing poisoned: any length is live
-    ks, vs = _dev16(torch, t["suf"][0], fmt), _dev16(torch, t["suf"][1], fmt)
+    ks, vs = cm.dev16(torch, t["suf"][0], fmt), cm.dev16(torch, t["suf"][1], fmt)
     dP, dlens, dsinks = _ints(torch, [c["P"]]), _ints(torch, c["lens"]), _floats(torch, li.sinks_for(Hkv * G))
 
     def call():
@@ -377,7 +364,7 @@ def test_ops_are_the_front_ends(fa, oracle, torch_cuda):
     c = mi.SHAPE
     B, Hkv, G = c["B"], c["Hkv"], c["G"]
     t = _device_inputs(torch, oracle, "base", Nq, d, fmt, False)
-    ks, vs = _dev16(torch, t["suf"][0], fmt), _dev16(torch, t["suf"][1], fmt)
+    ks, vs = cm.dev16(torch, t["suf"][0], fmt), cm.dev16(torch, t["suf"][1], fmt)
     dP, dlens, dsinks = _ints(torch, [c["P"]]), _ints(torch, c["lens"]), _floats(torch, li.sinks_for(Hkv * G))
     sc = 1.0 / np.sqrt(d)
     for f32 in (True, False):

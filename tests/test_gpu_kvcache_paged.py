@@ -16,14 +16,10 @@ import functools
 import numpy as np
 import pytest
 
+import common_inputs as cm
+import decode_inputs as di
+
 pytestmark = pytest.mark.gpu
-
-MAX_ABS = 1e-2                          # the project's north-star tolerance (tests/test_gpu_parity.py)
-REL_L2 = {0: 2e-3, 1: 1.2e-2}           # fp16 / bf16 inputs
-P_EPS = {0: 2.0 ** -11, 1: 2.0 ** -8}   # largest relative rounding error of one weight in the format P is packed to
-NAN16 = 0x7FFF                          # a NaN in fp16 and in bf16
-GARBAGE = (-1, 1 << 30)                 # what the table holds past a sequence's last live page
-
 
 @pytest.fixture(scope="module")
 def torch_cuda():
@@ -44,7 +40,7 @@ def _cache_to_dev(torch, bits, lens, B, Hkv, fmt):
     """[B*Hkv, Ncap, d] encodings -> device cache [B, Hkv, Ncap, d] with NaN in every row at and past the sequence's length."""
     bits = bits.reshape(B, Hkv, bits.shape[1], bits.shape[2]).copy()
     for b in range(B):
-        bits[b, :, max(int(lens[b]), 0):] = NAN16
+        bits[b, :, max(int(lens[b]), 0):] = cm.NAN16
     return _to_dev(torch, bits, fmt)
 
 
@@ -65,14 +61,14 @@ def _scatter(kb, vb, lens, B, Hkv, ps, seed, spare=3, shared=0):
     assert max_pages * ps == Ncap
     num_pages = B * max_pages + spare
     perm = np.random.default_rng(seed).permutation(num_pages)
-    pools = [np.full((num_pages, Hkv, ps, d), NAN16, np.uint16) for _ in range(2)]
+    pools = [np.full((num_pages, Hkv, ps, d), cm.NAN16, np.uint16) for _ in range(2)]
     table = np.empty((B, max_pages), np.int32)
     nxt = 0
     for b in range(B):
         L = min(max(int(lens[b]), 0), Ncap)
         for pi in range(max_pages):
             if pi >= _live_pages(L, ps):
-                table[b, pi] = GARBAGE[pi % 2]
+                table[b, pi] = cm.GARBAGE[pi % 2]
                 continue
             if b > 0 and pi < shared:
                 assert pi < _live_pages(lens[0], ps) and (pi + 1) * ps <= min(L, int(lens[0])), "a shared page is full in both"
@@ -87,11 +83,6 @@ def _scatter(kb, vb, lens, B, Hkv, ps, seed, spare=3, shared=0):
     return pools[0], pools[1], table
 
 
-def _limits(L, Nq, causal):
-    """c_i: the number of keys row i of a head sees."""
-    return [max(0, L - Nq + 1 + i) if causal else L for i in range(Nq)]
-
-
 def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
     """q [B*Hkv*G, Nq, d], k/v [B*Hkv, Ncap, d] fp32 (16-bit-rounded) -> (O [B*Hq, Nq, d] fp32, lse [B*Hq, Nq] float64)."""
     Hq, d = Hkv * G, q.shape[2]
@@ -101,7 +92,7 @@ def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
     for b in range(B):
         qs = slice(b * Hq, (b + 1) * Hq)
         kb, vb = (np.repeat(x[b * Hkv:(b + 1) * Hkv], G, axis=0) for x in (k, v))   # K/V head of every query head
-        lim = _limits(int(lens[b]), Nq, causal)
+        lim = [int(c) for c in cm.row_limits(int(lens[b]), Nq, Nq, causal)[1]]
         for c in sorted(set(lim)):
             if c == 0:
                 continue
@@ -115,18 +106,8 @@ def _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal):
 
 
 @functools.lru_cache(maxsize=None)
-def _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed):
-    """Seeded inputs, drawn once per shape and shared (read-only) by the tests that use them."""
-    (q, _, _), (qb, _, _) = oracle.make_qkv(B * Hkv * G, Nq, d, fmt=fmt, seed=seed)
-    (_, k, v), (_, kb, vb) = oracle.make_qkv(B * Hkv, Ncap, d, fmt=fmt, seed=seed + 1)
-    for a in (q, k, v, qb, kb, vb):
-        a.setflags(write=False)
-    return (q, k, v), (qb, kb, vb)
-
-
-@functools.lru_cache(maxsize=None)
 def _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed, lens, causal):
-    (q, k, v), _ = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed)
+    (q, k, v), _ = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, seed)
     out, lse = _expected(oracle, q, k, v, lens, B, Hkv, G, Nq, causal)
     out.setflags(write=False), lse.setflags(write=False)
     return out, lse
@@ -149,21 +130,6 @@ def _run(fa, torch, qb, pools, table, lens, B, Hkv, G, Nq, fmt, causal=False, ou
     return o.float().cpu().numpy().reshape(B * Hkv * G, Nq, d), lse.cpu().numpy().reshape(B * Hkv * G, Nq), need
 
 
-def _check(oracle, got, got_lse, want, want_lse, fmt, what):
-    ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
-    live = np.isfinite(want_lse)
-    le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
-    assert np.isfinite(got).all(), what + ": O is not finite"
-    assert not np.isnan(got_lse).any(), what + ": NaN in lse"
-    assert ma <= MAX_ABS and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
-    # rows without a key: exact zeros and -inf; every other row: a finite lse within the bound
-    assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
-    assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
-    assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
-
-
 FMT_D = [pytest.param(fmt, d, id=f"{'fp16' if fmt == 0 else 'bf16'}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 
 
@@ -174,14 +140,14 @@ def test_oracle_parity(fa, oracle, torch_cuda, fmt, d, ps, max_pages):
     pages into every tile; with pages of 256 the 773-key sequence has its split boundaries (192 keys apart) inside pages."""
     B, Hkv, G, Nq, Ncap = 3, 2, 2, 1, ps * max_pages
     lens = (1, 3 * ps + 5, Ncap)
-    _, (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1101)
+    _, (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1101)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1101, lens, False)
     kp, vp, table = _scatter(kb, vb, lens, B, Hkv, ps, seed=ps + d)
     pools = tuple(_to_dev(torch_cuda, p, fmt) for p in (kp, vp))
     for out_same in (False, True):
         got, lse, need = _run(fa, torch_cuda, qb, pools, table, lens, B, Hkv, G, Nq, fmt, out_same=out_same)
         assert need > 0
-        _check(oracle, got, lse, want, want_lse, fmt, f"paged parity d={d} fmt={fmt} page={ps} out_same={out_same}")
+        cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"paged parity d={d} fmt={fmt} page={ps} out_same={out_same}")
 
 
 @pytest.mark.parametrize("ps", [16, 64])
@@ -189,13 +155,13 @@ def test_oracle_parity(fa, oracle, torch_cuda, fmt, d, ps, max_pages):
 def test_single_pass(fa, oracle, torch_cuda, fmt, d, ps):
     """S = 1 (no workspace, the kernel writes O and the log-sum-exp itself).  A sequence of one key returns its V row."""
     B, Hkv, G, Nq, Ncap, lens = 3, 2, 1, 1, 192, (1, 64, 190)
-    (q, k, v), (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1201)
+    (q, k, v), (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1201)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1201, lens, False)
     kp, vp, table = _scatter(kb, vb, lens, B, Hkv, ps, seed=ps + d + 1)
     for out_same in (False, True):
         got, lse, need = _run(fa, torch_cuda, qb, (kp, vp), table, lens, B, Hkv, G, Nq, fmt, out_same=out_same)
         assert need == 0
-        _check(oracle, got, lse, want, want_lse, fmt, f"paged single pass d={d} fmt={fmt} page={ps} out_same={out_same}")
+        cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"paged single pass d={d} fmt={fmt} page={ps} out_same={out_same}")
         assert np.array_equal(got[:Hkv, 0], v[:Hkv, 0]), "a sequence of one key must return v[0]"
 
 
@@ -207,14 +173,14 @@ def test_mask_and_degenerate_rows(fa, oracle, torch_cuda, fmt, d, causal, ps):
     tile only rows 3 and 4 see, length 2 leaves rows 0-2 without a key, length 0 leaves every row (and the whole table row: all
     garbage) without one."""
     B, Hkv, G, Nq, Ncap, lens = 4, 1, 2, 5, 1024, (0, 2, 66, 1024)
-    _, (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1301)
+    _, (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1301)
     want, want_lse = _reference(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1301, lens, causal)
     dead = np.isinf(want_lse).reshape(B, Hkv * G, Nq)
     assert dead[0].all() and (dead[1].all(0).tolist() == [causal] * 3 + [False] * 2) and not dead[2:].any()
     kp, vp, table = _scatter(kb, vb, lens, B, Hkv, ps, seed=ps + d + 2)
     got, lse, need = _run(fa, torch_cuda, qb, (kp, vp), table, lens, B, Hkv, G, Nq, fmt, causal=causal)
     assert need > 0
-    _check(oracle, got, lse, want, want_lse, fmt, f"paged mask + degenerate rows d={d} fmt={fmt} page={ps} causal={causal}")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"paged mask + degenerate rows d={d} fmt={fmt} page={ps} causal={causal}")
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -226,7 +192,7 @@ def test_bit_equal_to_contiguous_entry(fa, oracle, torch_cuda, fmt, d, ps, causa
     torch = torch_cuda
     B, Hkv, G, Nq = 3, 2, 2, 3
     for Ncap, lens, split in ((1280, (1, 773, 1280), True), (256, (5, 200, 256), False)):
-        _, (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1401)
+        _, (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1401)
         dq = _to_dev(torch, qb, fmt).view(B, Hkv * G, Nq, d)
         dk, dv = (_cache_to_dev(torch, x, lens, B, Hkv, fmt) for x in (kb, vb))
         dl = torch.tensor(lens, dtype=torch.int32, device="cuda")
@@ -249,7 +215,7 @@ def test_shared_prefix(fa, oracle, torch_cuda, fmt, d, ps, shared):
     """Two sequences whose tables name the SAME physical pages for their first `shared` pages and differ afterwards."""
     B, Hkv, G, Nq, Ncap = 2, 2, 2, 1, 1088
     lens = (shared * ps + 7, Ncap - 9)
-    (q, k, v), (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1501)
+    (q, k, v), (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1501)
     k, v, kb, vb = (x.copy() for x in (k, v, kb, vb))
     for x in (k, v, kb, vb):
         x[Hkv:, :shared * ps] = x[:Hkv, :shared * ps]   # sequence 1 starts with sequence 0's prefix
@@ -258,7 +224,7 @@ def test_shared_prefix(fa, oracle, torch_cuda, fmt, d, ps, shared):
     assert (table[0, :shared] == table[1, :shared]).all() and table[0, shared] != table[1, shared]
     got, lse, need = _run(fa, torch_cuda, qb, (kp, vp), table, lens, B, Hkv, G, Nq, fmt)
     assert need > 0
-    _check(oracle, got, lse, want, want_lse, fmt, f"paged shared prefix d={d} fmt={fmt} page={ps}")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"paged shared prefix d={d} fmt={fmt} page={ps}")
 
 
 @pytest.mark.parametrize("fmt,d,ps", [pytest.param(0, 64, 16, id="fp16-d64-p16"), pytest.param(0, 64, 64, id="fp16-d64-p64"),
@@ -272,9 +238,9 @@ def test_bad_live_entries_read_zeros(fa, oracle, torch_cuda, fmt, d, ps):
     Ncap = max_pages * ps
     L = Ncap - 3
     slots = [0, -1, 1, 4, 2, -2, 5, 3]   # page number of each table slot; the last page (a good one) is live up to row ps - 3
-    (q, k, v), (qb, kb, vb) = _inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1601)
+    (q, k, v), (qb, kb, vb) = di.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, 1601)
     k, v = k.copy(), v.copy()
-    alloc = [np.full((8, Hkv, ps, d), NAN16, np.uint16) for _ in range(2)]
+    alloc = [np.full((8, Hkv, ps, d), cm.NAN16, np.uint16) for _ in range(2)]
     for pi, page in enumerate(slots):
         n = min(ps, L - pi * ps)
         if 0 <= page < 4:
@@ -288,7 +254,7 @@ def test_bad_live_entries_read_zeros(fa, oracle, torch_cuda, fmt, d, ps):
     assert all(p.is_contiguous() and p.shape[0] == 4 and p.storage_offset() > 0 for p in views)
     got, lse, need = _run(fa, torch, qb, views, np.array([slots], np.int32), (L,), B, Hkv, G, Nq, fmt)
     assert (need > 0) == (ps == 64)
-    _check(oracle, got, lse, want, want_lse, fmt, f"paged bad live entries d={d} fmt={fmt} page={ps}")
+    cm.check_decode(oracle, got, lse, want, want_lse, fmt, f"paged bad live entries d={d} fmt={fmt} page={ps}")
 
 
 def test_graph_replay_follows_table_and_lengths(fa, torch_cuda):
@@ -314,7 +280,7 @@ def test_graph_replay_follows_table_and_lengths(fa, torch_cuda):
         for b, L in enumerate(lengths):
             for pi in range(max_pages):
                 if pi >= _live_pages(L, ps):
-                    tb[b, pi] = GARBAGE[pi % 2]
+                    tb[b, pi] = cm.GARBAGE[pi % 2]
                     continue
                 page, n = int(perm[nxt]), min(ps, L - pi * ps)
                 nxt += 1

@@ -13,6 +13,7 @@ import pytest
 
 import append_inputs as ai
 import census_inputs as ci
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import logit_inputs as li
@@ -21,8 +22,7 @@ import rope_inputs as rp
 
 pytestmark = pytest.mark.gpu
 
-MAX_ABS, REL_L2, P_EPS = di.MAX_ABS, di.REL_L2, di.P_EPS
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 NAMES = list(ri.FAMILIES)
 MASKS = [pytest.param(c, W, id=f"{'causal' if c else 'full'}-W{W}") for c in (True, False) for W in ri.WINDOWS]
 
@@ -32,18 +32,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return torch
-
-
-def _tdtype(torch, fmt):
-    return torch.float16 if fmt == 0 else torch.bfloat16
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.array(bits).view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.array(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -68,22 +56,21 @@ def _run(fa, torch, f, d, fmt, qb, kb, vb, nq, W, causal, ps=0, seed=0, sinks=No
     need = fa.kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, W)
     if check_S:
         assert di.splits_of(need, B * Hkv, G * Nq, d) == ri.want_S(f, W)
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     kw = dict(cache_seqlens=_ints(torch, lens), causal=causal, return_lse=True, workspace=_nan_workspace(torch, need), window=W,
               sinks=_floats(torch, sinks), softcap=softcap)
     if nq is not None:
         kw["seqlens_q"] = _ints(torch, nq)
     if fp8:
         kw.update(k_scale=_floats(torch, k_scale), v_scale=_floats(torch, v_scale))
+    nan = f8.NAN_CODES[0] if fp8 else cm.NAN16
+    kc, vc = (x.reshape(B, Hkv, Ncap, d) for x in (kb, vb))
     if ps == 0:
-        pois = (lambda x: f8.poisoned(x.reshape(B, Hkv, Ncap, d), lens)) if fp8 else (lambda x: di.poisoned(x, lens, B, Hkv))
-        o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(pois(kb)), dev(pois(vb)), **kw)
+        o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(cm.poisoned(kc, lens, nan=nan)),
+                                                                               dev(cm.poisoned(vc, lens, nan=nan)), **kw)
     else:
-        if fp8:
-            kp, vp, table = f8.scatter(kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d), lens, ps, seed)
-        else:
-            kp, vp, table = di.scatter(kb, vb, lens, B, Hkv, ps, seed)
+        kp, vp, table = cm.scatter(kc, vc, lens, ps, seed, nan=nan)
         o, lse = (fa.fa_forward_kvcache_paged_fp8 if fp8 else fa.fa_forward_kvcache_paged)(dq, dev(kp), dev(vp), torch.from_numpy(table).cuda(),
                                                                                        **kw)
     torch.cuda.synchronize()
@@ -99,15 +86,15 @@ def _check(oracle, o, lse, want, want_lse, live_rows, fmt, what):
     ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
     fin = np.isfinite(want_lse)
     le = float(np.abs(got_lse[fin] - want_lse[fin]).max()) if fin.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
+    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {cm.MAX_ABS:.1e} {cm.REL_L2[fmt]:.1e} {2 * cm.P_EPS[fmt]:.2e})")
     assert np.isfinite(got).all(), what + ": O is not finite"
     assert not np.isnan(got_lse).any(), what + ": NaN in lse"
     assert (got[~live_rows] == 0.0).all() and (got_lse[~live_rows] == -np.inf).all(), what + ": a dead row is not exactly 0 / -inf"
     assert (got[~fin] == 0.0).all() and (got_lse[~fin] == -np.inf).all(), what + ": a row without a key is not exactly 0 / -inf"
     nokey = live_rows & (np.abs(want).max(-1) == 0)
     assert (got[nokey] == 0.0).all(), what + ": a live row without a key is not exactly zero"
-    assert ma <= MAX_ABS and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
-    assert np.isfinite(got_lse[fin]).all() and le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    assert ma <= cm.MAX_ABS and rl <= cm.REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
+    assert np.isfinite(got_lse[fin]).all() and le <= 2 * cm.P_EPS[fmt], f"{what}: lse off by {le:.3e}"
 
 
 def _pages(f):
@@ -178,7 +165,7 @@ def test_fp8_ties_and_per_head_scales(fa, oracle, torch_cuda, fmt, d):
         ks, vs = np.array([0.5 + 0.25 * h for h in range(Hkv)], np.float32), np.array([2.0 - 0.5 * h for h in range(Hkv)], np.float32)
         kd = f8.decode(k8) * np.tile(ks, B)[:, None, None]
         vd = f8.decode(v8) * np.tile(vs, B)[:, None, None]
-        want, want_lse = ri.expected_f64(q, kd, vd, f["lens"], f["nq"], B, Hkv, G, Nq, causal, W)
+        want, want_lse = cm.expected_f64(q, kd, vd, f["lens"], B, Hkv, G, Nq, causal, W, nq=f["nq"])
         o, lse = _run(fa, torch, f, d, fmt, qb, k8, v8, f["nq"], W, causal, fp8=True, k_scale=ks, v_scale=vs)
         _check(oracle, o, lse, want, want_lse, ri.live_rows(name), fmt, f"{name} fp8 per-head scales")
 
@@ -249,10 +236,10 @@ def _append_table(a):
                 first.setdefault(b, int(perm[nxt]))
                 nxt += 1
             else:
-                table[b, pi] = ai.GARBAGE[pi % 2]
+                table[b, pi] = cm.GARBAGE[pi % 2]
     foreign = []
     for b in range(B):
-        L = di.clamp(a["lens"][b], Ncap)
+        L = cm.clamp(a["lens"][b], Ncap)
         padded_end = min(L + a["Nnew"], Ncap)
         for pi in range(-(-int(after[b]) // ps), -(-padded_end // ps)):          # slots only tokens t >= m_b would reach
             other = next(x for x in first if x != b)
@@ -304,11 +291,11 @@ def test_append_bytes(fa, oracle, torch_cuda, fmt, d, paged, fp8, rope):
     def launch(new_counts, flat=False, table=table, disjoint=False, by_desc=False):
         """-> K, V, lengths, Qout, Q after one append.  flat: no seqlens_new (the flat entry); by_desc: the same through
         fa_kvcache_append_ex with seqlens_new = NULL; disjoint: Q goes to a NaN-filled q_out of its own instead of in place"""
-        dev = (lambda x: _dev8(torch, x)) if fp8 else (lambda x: _dev16(torch, x, fmt))
+        dev = (lambda x: cm.dev8(torch, x)) if fp8 else (lambda x: cm.dev16(torch, x, fmt))
         dk, dv, dl = dev(kc0), dev(vc0), _ints(torch, lens)
-        dkn, dvn = _dev16(torch, knb, fmt), _dev16(torch, vnb, fmt)
-        dq = _dev16(torch, qsrc, fmt) if rope else None
-        dqo = _dev16(torch, np.full(qsrc.shape, di.NAN16, np.uint16), fmt) if rope and disjoint else dq
+        dkn, dvn = cm.dev16(torch, knb, fmt), cm.dev16(torch, vnb, fmt)
+        dq = cm.dev16(torch, qsrc, fmt) if rope else None
+        dqo = cm.dev16(torch, np.full(qsrc.shape, cm.NAN16, np.uint16), fmt) if rope and disjoint else dq
         dt = torch.from_numpy(table).cuda() if paged else None
         dks, dvs, dcos, dsin = _floats(torch, ks), _floats(torch, vs), _floats(torch, cos), _floats(torch, sin)
         if by_desc:
@@ -357,7 +344,7 @@ def test_append_bytes(fa, oracle, torch_cuda, fmt, d, paged, fp8, rope):
     if paged:
         own = table.copy()
         for b, pi in foreign:
-            own[b, pi] = ai.GARBAGE[0]
+            own[b, pi] = cm.GARBAGE[0]
         for b, pi in foreign:
             page = int(table[b, pi])
             assert np.array_equal(gk[page], ri.place(kc0, krows, lens, new, own)[page])
@@ -390,14 +377,14 @@ def test_captured_ragged_step(fa, oracle, torch_cuda):
     max_pages = Ncap // ps
     table = np.random.default_rng(8600).permutation(B * max_pages + 3)[:B * max_pages].astype(np.int32).reshape(B, max_pages)
     num_pages = B * max_pages + 3
-    nan_pool = np.full((num_pages, Hkv, ps, d), di.NAN16, np.uint16)
+    nan_pool = np.full((num_pages, Hkv, ps, d), cm.NAN16, np.uint16)
     for b in range(B):                                  # the keys the sequences start with: rows 0 .. L_b - 1 of the drawn cache
         kcpu[b * Hkv:(b + 1) * Hkv, :lens[b]] = k[b * Hkv:(b + 1) * Hkv, :lens[b]]
         vcpu[b * Hkv:(b + 1) * Hkv, :lens[b]] = v[b * Hkv:(b + 1) * Hkv, :lens[b]]
     kb4, vb4 = kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d)
     kp = ri.place(nan_pool, kb4, None, lens, table)     # a ragged "append into an empty cache" places the start
     vp = ri.place(nan_pool, vb4, None, lens, table)
-    dkp, dvp, dt, dl = _dev16(torch, kp, fmt), _dev16(torch, vp, fmt), torch.from_numpy(table).cuda(), _ints(torch, lens)
+    dkp, dvp, dt, dl = cm.dev16(torch, kp, fmt), cm.dev16(torch, vp, fmt), torch.from_numpy(table).cuda(), _ints(torch, lens)
     # angle 0: the fused rotation is on the captured path, and K and Q arrive as they were drawn
     cos = torch.ones(Ncap, d // 2, dtype=torch.float32, device="cuda")
     sin = torch.zeros(Ncap, d // 2, dtype=torch.float32, device="cuda")
@@ -421,7 +408,7 @@ def test_captured_ragged_step(fa, oracle, torch_cuda):
     used = [0] * B               # tokens of the drawn rows each sequence has consumed
     for s, cnt in enumerate(steps):
         newk, newv = np.zeros((B, Hkv, N, d), np.uint16), np.zeros((B, Hkv, N, d), np.uint16)
-        newq = np.full((B, Hq, N, d), di.NAN16, np.uint16)                       # dead Q rows: NaN
+        newq = np.full((B, Hq, N, d), cm.NAN16, np.uint16)                       # dead Q rows: NaN
         qf = np.zeros((B * Hq, N, d), np.float32)
         for b in range(B):
             for t in range(cnt[b]):
@@ -431,13 +418,13 @@ def test_captured_ragged_step(fa, oracle, torch_cuda):
                 newq[b, :, t] = qb.reshape(B, Hq, 3 * N, d)[b, :, used[b] + t]
                 qf[b * Hq:(b + 1) * Hq, t] = q.reshape(B, Hq, 3 * N, d)[b, :, used[b] + t]
             used[b] += cnt[b]
-        dn.copy_(_ints(torch, cnt)), dkn.copy_(_dev16(torch, newk, fmt)), dvn.copy_(_dev16(torch, newv, fmt)), dq.copy_(_dev16(torch, newq, fmt))
+        dn.copy_(_ints(torch, cnt)), dkn.copy_(cm.dev16(torch, newk, fmt)), dvn.copy_(cm.dev16(torch, newv, fmt)), dq.copy_(cm.dev16(torch, newq, fmt))
         ws.fill_(0xFF), o.fill_(float("nan")), lse.fill_(float("nan"))
         graph.replay()
         torch.cuda.synchronize()
         lens = [L + c for L, c in zip(lens, cnt)]
         assert dl.tolist() == lens, s
-        want, want_lse = ri.expected_f64(qf, kcpu, vcpu, lens, cnt, B, Hkv, G, N, True, 0)
+        want, want_lse = cm.expected_f64(qf, kcpu, vcpu, lens, B, Hkv, G, N, True, nq=cnt)
         live = ri.limits(lens, cnt, B, Hkv, G, N, Ncap, True, 0)[2]
         _check(oracle, o, lse, want, want_lse, live, fmt, f"captured step {s}: counts {cnt}, lengths {lens}")
     assert dl.tolist() == [15, 37, 3]
@@ -454,12 +441,12 @@ def test_ragged_ops_are_the_front_ends(fa, oracle, torch_cuda):
     f = ri.FAMILIES[name]
     B, Hkv, G, Nq, Ncap = ri.shape(f)
     (q, k, v), (qb, kb, vb) = ri.inputs(oracle, name, d, fmt)
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
     dl, dn, ds = _ints(torch, f["lens"]), _ints(torch, f["nq"]), _floats(torch, li.sinks_for(Hkv * G))
     sc = 1.0 / np.sqrt(d)
-    kp, vp, table = di.scatter(kb, vb, f["lens"], B, Hkv, 16, 3)
-    dk, dv = _dev16(torch, di.poisoned(kb, f["lens"], B, Hkv), fmt), _dev16(torch, di.poisoned(vb, f["lens"], B, Hkv), fmt)
-    dkp, dvp, dt = _dev16(torch, kp, fmt), _dev16(torch, vp, fmt), torch.from_numpy(table).cuda()
+    kp, vp, table = cm.scatter(kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d), f["lens"], 16, 3)
+    dk, dv = (cm.dev16(torch, cm.poisoned(x.reshape(B, Hkv, Ncap, d), f["lens"]), fmt) for x in (kb, vb))
+    dkp, dvp, dt = cm.dev16(torch, kp, fmt), cm.dev16(torch, vp, fmt), torch.from_numpy(table).cuda()
     z8 = lambda x: torch.where(torch.isnan(x), torch.zeros_like(x), x).clamp(-400, 400).to(torch.float8_e4m3fn)
     dk8, dv8, dkp8, dvp8 = z8(dk.float()), z8(dv.float()), z8(dkp.float()), z8(dvp.float())
     s8 = _floats(torch, [0.5, 2.0])

@@ -16,14 +16,14 @@ import functools
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 import fp8_inputs as f8
 import window_inputs as wi
 
 pytestmark = pytest.mark.gpu
 
-MAX_ABS, REL_L2, P_EPS = di.MAX_ABS, di.REL_L2, di.P_EPS   # the project's bounds (tests/test_gpu_parity.py is their origin)
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 LAUNCHES = [pytest.param(name, W, causal, id=f"{name}-W{W}-{'causal' if causal else 'full'}")
             for name, c in wi.CASES.items() for W in c["windows"] for causal in c["causal"]]
 FP8_LAUNCHES = [p for p in LAUNCHES if p.values[0] in ("one_pass", "split")]
@@ -38,14 +38,6 @@ def torch_cuda():
 
 def _tdtype(torch, fmt):
     return torch.float16 if fmt == 0 else torch.bfloat16
-
-
-def _dev16(torch, bits, fmt):
-    return torch.from_numpy(np.array(bits).view(np.int16)).cuda().view(_tdtype(torch, fmt))
-
-
-def _dev8(torch, codes):
-    return torch.from_numpy(np.array(codes, dtype=np.uint8)).cuda().view(torch.float8_e4m3fn)
 
 
 def _ints(torch, values):
@@ -74,7 +66,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
     need = fa.kvcache_window_workspace_bytes(B, Hkv, Hq // Hkv, Nq, Ncap, d, W)
     if want_S is not None:
         assert di.splits_of(need, B * Hkv, (Hq // Hkv) * Nq, d) == want_S
-    dev = (lambda a: _dev8(torch, a)) if fp8 else (lambda a: _dev16(torch, a, fmt))
+    dev = (lambda a: cm.dev8(torch, a)) if fp8 else (lambda a: cm.dev16(torch, a, fmt))
     kw = dict(cache_seqlens=_ints(torch, lens), causal=causal, scale=scale, return_lse=True, workspace=_nan_workspace(torch, need),
               window=W)
     if fp8:
@@ -83,7 +75,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
         o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(kc), dev(vc), **kw)
     else:
         assert fa.kvcache_paged_window_workspace_bytes(B, Hkv, Hq // Hkv, Nq, Ncap // ps, ps, d, W) == need
-        kp, vp, table = wi.scatter(kc, vc, lens, Nq, W, ps, seed, nan=wi.NAN8 if fp8 else di.NAN16)
+        kp, vp, table = cm.scatter(kc, vc, lens, ps, seed, Nq, W, nan=wi.NAN8 if fp8 else cm.NAN16)
         o, lse = (fa.fa_forward_kvcache_paged_fp8 if fp8 else fa.fa_forward_kvcache_paged)(
             dq, dev(kp), dev(vp), torch.from_numpy(table).cuda(), **kw)
     torch.cuda.synchronize()
@@ -92,20 +84,7 @@ def _run(fa, torch, dq, kc, vc, lens, W, causal, ps=0, seed=0, scale=None, fmt=N
 
 
 def _check(oracle, o, lse, want, want_lse, fmt, what):
-    got = o.float().cpu().numpy().reshape(want.shape)
-    got_lse = lse.cpu().numpy().reshape(want_lse.shape)
-    ma, rl = oracle.max_abs(got, want), oracle.rel_l2(got, want)
-    live = np.isfinite(want_lse)
-    le = float(np.abs(got_lse[live] - want_lse[live]).max()) if live.any() else 0.0
-    print(f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e} lse_abs={le:.3e} (bounds {MAX_ABS:.1e} {REL_L2[fmt]:.1e} {2 * P_EPS[fmt]:.2e})")
-    assert np.isfinite(got).all(), what + ": O is not finite"
-    assert not np.isnan(got_lse).any(), what + ": NaN in lse"
-    assert ma <= MAX_ABS and rl <= REL_L2[fmt], f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
-    # rows without a key: exact zeros and -inf; every other row: a finite lse within the bound
-    assert (got[~live] == 0.0).all(), what + ": a row without a key is not exactly zero"
-    assert (got_lse[~live] == -np.inf).all(), what + ": a row without a key has lse != -inf"
-    assert np.isfinite(got_lse[live]).all(), what
-    assert le <= 2 * P_EPS[fmt], f"{what}: lse off by {le:.3e}"
+    cm.check_decode(oracle, o.float().cpu().numpy().reshape(want.shape), lse.cpu().numpy().reshape(want_lse.shape), want, want_lse, fmt, what)
 
 
 # ---- 1 - 4. oracle parity of the contiguous entry; the paged entry returns its bits ---------------------------------------------------
@@ -120,8 +99,8 @@ def test_oracle_parity_and_paged_bits(fa, oracle, torch_cuda, fmt, d, name, W, c
     B, Hkv, G, Nq, Ncap = _shape(c)
     _, (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, c["seed"])
     want, want_lse = wi.reference(oracle, name, d, fmt, W, causal)
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    kc, vc = wi.poisoned(kb, c["lens"], Nq, W), wi.poisoned(vb, c["lens"], Nq, W)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), c["lens"], Nq, W) for x in (kb, vb))
     o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, causal, fmt=fmt, want_S=c["S"])
     _check(oracle, o, lse, want, want_lse, fmt, f"window {name} W={W} causal={causal} d={d} fmt={fmt}")
     for ps in wi.PAGES:
@@ -168,14 +147,14 @@ def test_fp8_window(fa, oracle, torch_cuda, fmt, d, name, W, causal):
     c = wi.CASES[name]
     B, Hkv, G, Nq, Ncap = _shape(c)
     q, qb, k8, v8, kd, vd, ks, vs = _quantised(fa, oracle, name, d, fmt)
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    pk, pv = wi.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), wi.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    pk, pv = cm.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), cm.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
     # the widened caches: torch's CPU conversion of the poisoned codes (0x7F widens to a NaN), as 16-bit encodings
     wide = [torch.from_numpy(x).view(torch.float8_e4m3fn).to(_tdtype(torch, fmt)).view(torch.int16).numpy().view(np.uint16) for x in (pk, pv)]
     sc = 2.0 ** -7 / np.sqrt(d)
     base, base_lse = _run(fa, torch, dq, wide[0], wide[1], c["lens"], W, causal, scale=sc, fmt=fmt, want_S=c["S"])
     assert torch.isfinite(base).all() and not torch.isnan(base_lse).any()
-    want, want_lse = wi.expected(oracle, q, kd, vd, c["lens"], B, Hkv, G, Nq, causal, W)
+    want, want_lse = cm.expected(oracle, q, kd, vd, c["lens"], B, Hkv, G, Nq, causal, W)
     for ps in (0, 16):
         o, lse = _run(fa, torch, dq, pk, pv, c["lens"], W, causal, ps=ps, seed=ps + d, scale=sc, want_S=c["S"])
         assert torch.equal(o, base) and torch.equal(lse, base_lse), f"fp8 layout {ps}: not the 16-bit windowed entry's bits"
@@ -209,9 +188,9 @@ def test_no_window_and_full_window_are_the_base_entry(fa, oracle, torch_cuda, fm
     c = wi.CASES[name]
     B, Hkv, G, Nq, Ncap = _shape(c)
     _, (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, c["seed"])
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    kc, vc = di.poisoned(kb, c["lens"], B, Hkv), di.poisoned(vb, c["lens"], B, Hkv)
-    dk, dv, dl = _dev16(torch, kc, fmt), _dev16(torch, vc, fmt), _ints(torch, c["lens"])
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), c["lens"]) for x in (kb, vb))
+    dk, dv, dl = cm.dev16(torch, kc, fmt), cm.dev16(torch, vc, fmt), _ints(torch, c["lens"])
     need = fa.kvcache_workspace_bytes(B, Hkv, G, Nq, Ncap, d)
     assert need > 0 and fa.kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, Ncap) == need
     for causal in (False, True):
@@ -234,15 +213,15 @@ def test_window_is_the_base_entry_on_the_shifted_cache(fa, oracle, torch_cuda, f
     s = wi.SHIFT
     B, Hkv, G, Nq, Ncap, W = s["B"], s["Hkv"], s["G"], s["Nq"], s["Ncap"], s["W"]
     _, (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, s["seed"])
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    kc, vc = wi.poisoned(kb, s["lens"], Nq, W), wi.poisoned(vb, s["lens"], Nq, W)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), s["lens"], Nq, W) for x in (kb, vb))
     o, lse = _run(fa, torch, dq, kc, vc, s["lens"], W, False, fmt=fmt, want_S=4)
     small = []
     for src in (kc, vc):
-        x = np.full((B, Hkv, W + 64, d), di.NAN16, np.uint16)
+        x = np.full((B, Hkv, W + 64, d), cm.NAN16, np.uint16)
         for b, L in enumerate(s["lens"]):
             x[b, :, :W] = src[b, :, L - W:L]
-        small.append(_dev16(torch, x, fmt))
+        small.append(cm.dev16(torch, x, fmt))
     need = fa.kvcache_workspace_bytes(B, Hkv, G, Nq, W + 64, d)
     assert need == fa.kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, W) and di.splits_of(need, B * Hkv, 1, d) == 4
     base, base_lse = fa.fa_forward_kvcache(dq, small[0], small[1], _ints(torch, [W] * B), return_lse=True,
@@ -264,12 +243,12 @@ def test_captured_append_then_windowed_decode(fa, oracle, torch_cuda):
     kb4, vb4, qb4 = kb.reshape(B, Hkv, Ncap, d), vb.reshape(B, Hkv, Ncap, d), qb.reshape(B, Hkv * G, steps, d)
     lens = list(g["start"])
     # the cache holds the drawn rows below the start lengths and NaN above; step t appends the drawn row at each sequence's length
-    dk, dv = _dev16(torch, di.poisoned(kb, lens, B, Hkv), fmt), _dev16(torch, di.poisoned(vb, lens, B, Hkv), fmt)
+    dk, dv = (cm.dev16(torch, cm.poisoned(x, lens), fmt) for x in (kb4, vb4))
     dl = _ints(torch, lens)
 
     def new_rows(t):
         rows = [np.stack([src[b, :, lens[b] + t:lens[b] + t + 1] for b in range(B)]) for src in (kb4, vb4)]
-        return _dev16(torch, rows[0], fmt), _dev16(torch, rows[1], fmt), _dev16(torch, qb4[:, :, t:t + 1], fmt)
+        return cm.dev16(torch, rows[0], fmt), cm.dev16(torch, rows[1], fmt), cm.dev16(torch, qb4[:, :, t:t + 1], fmt)
 
     need = fa.kvcache_window_workspace_bytes(B, Hkv, G, 1, Ncap, d, W)
     ws = _nan_workspace(torch, need)
@@ -294,7 +273,7 @@ def test_captured_append_then_windowed_decode(fa, oracle, torch_cuda):
         now = [L + t + 1 for L in lens]
         assert dl.tolist() == now
         qt = np.ascontiguousarray(q.reshape(B * Hkv * G, steps, d)[:, t:t + 1])
-        want, want_lse = wi.expected(oracle, qt, k, v, now, B, Hkv, G, 1, True, W)
+        want, want_lse = cm.expected(oracle, qt, k, v, now, B, Hkv, G, 1, True, W)
         _check(oracle, o, lse, want, want_lse, fmt, f"graph step {t} lengths {now}")
 
 
@@ -308,9 +287,9 @@ def test_scale_zero(fa, oracle, torch_cuda, fmt, d, name, W, causal):
     c = wi.CASES[name]
     B, Hkv, G, Nq, Ncap = _shape(c)
     (_, _, v), (qb, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, d, fmt, c["seed"])
-    want, want_lse = wi.uniform_expected(v, c["lens"], B, Hkv, G, Nq, causal, W)
-    dq = _dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
-    kc, vc = wi.poisoned(kb, c["lens"], Nq, W), wi.poisoned(vb, c["lens"], Nq, W)
+    want, want_lse = cm.uniform_expected(v, c["lens"], B, Hkv, G, Nq, causal, W)
+    dq = cm.dev16(torch, qb, fmt).view(B, Hkv * G, Nq, d)
+    kc, vc = (cm.poisoned(x.reshape(B, Hkv, Ncap, d), c["lens"], Nq, W) for x in (kb, vb))
     for scale in (0.0, -0.0):
         for ps in (0, 16):
             o, lse = _run(fa, torch, dq, kc, vc, c["lens"], W, causal, ps=ps, seed=3, scale=scale, fmt=fmt)

@@ -11,21 +11,11 @@ import os
 import numpy as np
 import pytest
 
+import common_inputs as cm
+
 pytestmark = pytest.mark.gpu
 
-MAX_ABS = 1e-2                       # north-star tolerance
-REL_L2 = {0: 2e-3, 1: 1.2e-2}        # fp16 / bf16 inputs (P is rounded to the input type)
-P_EPS = {0: 2.0 ** -11, 1: 2.0 ** -8}  # largest relative rounding error of one weight in the 16-bit format P is packed to (half an ulp at 1.0)
-
-
-def _peaked_tol(fmt, vmax, kernels=1):
-    """The tolerance model of tools/fuzz_gpu.py, for inputs that make sharply PEAKED rows (large logits, the first
-    rows under the causal mask): the north-star bar plus what the 16-bit format of P itself imposes.  A row whose
-    weight sits on two or three comparable keys moves by at most (relative rounding of one weight, P_EPS) x (the
-    spread of the dominant V rows, <= 2 vmax, of which a convex combination keeps at most vmax).  `kernels` = how many
-    independently rounding kernels the difference is taken between (2 when comparing two of ours with each other)."""
-    return MAX_ABS + kernels * float(vmax) * P_EPS[fmt]
-
+# The bounds of the docstring above -- MAX_ABS, REL_L2, P_EPS and peaked_tol -- are defined in tests/common_inputs.py, for every GPU tier.
 
 @pytest.fixture(scope="module")
 def torch_cuda():
@@ -68,11 +58,11 @@ def _algos_for(d):
                     else ((0, 1, 2, 21, 23, 24, 26, 28) if d == 128 else (0, 1)))
 
 
-def _check(oracle, got, want, fmt, what, out_same=False, max_abs=MAX_ABS, rel_l2=None):
+def _check(oracle, got, want, fmt, what, out_same=False, max_abs=cm.MAX_ABS, rel_l2=None):
     ma = oracle.max_abs(got, want)
     rl = oracle.rel_l2(got, want)
     assert np.isfinite(got).all(), what
-    tol_rl = rel_l2 if rel_l2 is not None else REL_L2[fmt] * (1.5 if out_same else 1.0)
+    tol_rl = rel_l2 if rel_l2 is not None else cm.REL_L2[fmt] * (1.5 if out_same else 1.0)
     assert ma <= max_abs and rl <= tol_rl, f"{what}: max_abs={ma:.3e} rel_l2={rl:.3e}"
 
 
@@ -175,7 +165,7 @@ def test_extreme_logits_stay_finite(fa, oracle, torch_cuda):
     for algo in (0, 1):
         got = _run(fa, torch_cuda, qb, kb, vb, 0, algo)
         assert np.isfinite(got).all()
-        assert oracle.max_abs(got, want) <= _peaked_tol(0, np.abs(v).max())   # near-one-hot rows
+        assert oracle.max_abs(got, want) <= cm.peaked_tol(0, np.abs(v).max())   # near-one-hot rows
 
 
 def test_bit_reproducible_and_head_independent(fa, oracle, torch_cuda):
@@ -313,7 +303,7 @@ def test_optimistic_pass_overflow_fallback(fa, oracle, torch_cuda, fmt):
     # is taken from the unrounded fp32 p: 2^-9 for bf16, |V| <= ~4.5.  The shipped kernels (AUTO, 5, 6)
     # sum the ROUNDED bf16 weights instead and meet the plain bar; the A/B variants do not.
     def tol(algo):
-        return MAX_ABS
+        return cm.MAX_ABS
     for algo in _present((0, 5, 6, 21, 22, 23, 24, 25, 26, 27, 29)):
         got = _run(fa, torch_cuda, qb, kb, vb, fmt, algo)
         _check(oracle, got, want, fmt, f"optimistic/fallback fmt={fmt} algo={algo}", max_abs=tol(algo))
@@ -384,7 +374,7 @@ def test_causal_big(fa, oracle, torch_cuda):
     for b, r0 in ((0, 0), (17, 1000), (127, 4032)):
         want = oracle.forward(q, k, v, causal=True, nthreads=8, bh_range=(b, b + 1), row_range=(r0, r0 + 64))
         ma = np.abs(got[b, r0:r0 + 64] - want[b, r0:r0 + 64]).max()
-        assert ma <= MAX_ABS, (b, r0, ma)
+        assert ma <= cm.MAX_ABS, (b, r0, ma)
 
 
 # ---- second, independent oracle on the GPU box: PyTorch's own attention ----------
@@ -416,9 +406,9 @@ def test_full_size_against_torch_fp32(fa, torch_cuda, fmt, causal):
     want = _sdpa_fp32(torch, q, k, v, causal)
     torch.cuda.synchronize()
     err = (got - want).abs().max().item()
-    assert err <= MAX_ABS and torch.isfinite(got).all(), err
+    assert err <= cm.MAX_ABS and torch.isfinite(got).all(), err
     rel = ((got - want).norm() / want.norm()).item()
-    assert rel <= REL_L2[fmt], rel
+    assert rel <= cm.REL_L2[fmt], rel
 
 
 def test_sdpa_like_matches_torch_sdpa(fa, torch_cuda):
@@ -431,7 +421,7 @@ def test_sdpa_like_matches_torch_sdpa(fa, torch_cuda):
         got = sdpa_like(q, k, v, is_causal=causal)
         want = torch.nn.functional.scaled_dot_product_attention(q.float(), k.float(), v.float(), is_causal=causal)
         assert got.dtype == torch.float16
-        assert (got.float() - want).abs().max().item() <= MAX_ABS
+        assert (got.float() - want).abs().max().item() <= cm.MAX_ABS
 
 
 # ---- Nq != Nk with a split over the keys (not a reference entry point) -----------
@@ -591,7 +581,7 @@ def test_splitkv_grouped_query_heads(fa, oracle, torch_cuda):
 
 # ---------------------------------------------------------------- round 2: configs at their stated shapes, AUTO edges, the folded pass
 
-def _sampled_rows_check(fa, oracle, torch, q, k, v, o, fmt, rows, what, max_abs=MAX_ABS, rel_l2=None):
+def _sampled_rows_check(fa, oracle, torch, q, k, v, o, fmt, rows, what, max_abs=cm.MAX_ABS, rel_l2=None):
     """q,k,v,o: [B,H,N,d] device tensors; rows: list of (b, h, r0, n) row ranges checked against the oracle."""
     for (b, h, r0, n) in rows:
         qs, ks, vs = (t[b, h].float().cpu().numpy()[None] for t in (q, k, v))
@@ -678,7 +668,7 @@ def test_bf16_overflow_window_below_inf(fa, oracle, torch_cuda):
     want = oracle.forward(q, k, v, accum=1, nthreads=8)
     for algo in _present((0, 5, 6, 21, 23, 24, 26, 27)):
         got = _run(fa, torch_cuda, qb, kb, vb, fmt, algo)
-        _check(oracle, got, want, fmt, f"bf16 window algo={algo}", max_abs=4 * MAX_ABS)   # |V| = 4 x the N(0,1) bar
+        _check(oracle, got, want, fmt, f"bf16 window algo={algo}", max_abs=4 * cm.MAX_ABS)   # |V| = 4 x the N(0,1) bar
 
 
 @pytest.mark.parametrize("fmt", [0, 1])
@@ -742,8 +732,8 @@ def test_folded_pass_gates(fa, oracle, torch_cuda, fmt):
             # (case (i): O = 3 (w1 - w2) with w1 ~ w2 -- the row's output nearly cancels, so a relative measure over the tensor says
             # little; the max-abs bar is what holds there)
             _check(oracle, got, want, fmt, f"folded-pass gate: {name} algo={algo} fmt={fmt}",
-                   max_abs=MAX_ABS if fmt == 0 else _peaked_tol(fmt, np.abs(v).max()),
-                   rel_l2=5.0 * REL_L2[fmt] if name.startswith("two dominant") else None)
+                   max_abs=cm.MAX_ABS if fmt == 0 else cm.peaked_tol(fmt, np.abs(v).max()),
+                   rel_l2=5.0 * cm.REL_L2[fmt] if name.startswith("two dominant") else None)
 
 
 def _pass_ids(torch, q, k, v, algo):
@@ -817,9 +807,9 @@ def test_redo_kernel_takes_the_blocks_the_fast_passes_refuse(fa, oracle, torch_c
         assert torch.equal(o, o_exp)
         vmax = float(vv.float().abs().max())
         exact = fa.fa_forward(qq, kk, vv, algo=23)
-        assert float((o - exact).abs().max()) <= _peaked_tol(fmt, vmax, kernels=2) - MAX_ABS + 1e-3
+        assert float((o - exact).abs().max()) <= cm.peaked_tol(fmt, vmax, kernels=2) - cm.MAX_ABS + 1e-3
         _sampled_rows_check(fa, oracle, torch, qq, kk, vv, o, fmt, [(0, 0, 0, 16), (1, 7, 4080, 16), (1, 3, 2047, 8)],
-                            f"redo kernel fmt={fmt}", max_abs=MAX_ABS if fmt == 0 else _peaked_tol(fmt, vmax), rel_l2=None if fmt == 0 else 3e-2)
+                            f"redo kernel fmt={fmt}", max_abs=cm.MAX_ABS if fmt == 0 else cm.peaked_tol(fmt, vmax), rel_l2=None if fmt == 0 else 3e-2)
 
 
 @pytest.mark.parametrize("fmt", [0, 1])
@@ -841,9 +831,9 @@ def test_folded_pass_spread_inputs_all_widths(fa, oracle, torch_cuda, fmt):
                 assert bool(torch.isfinite(o).all()), (d, spread, algo)
                 # two of our kernels against each other: each rounds its weights once (the bar itself does not enter)
                 vmax = float(v.float().abs().max())
-                assert float((o - exact).abs().max()) <= _peaked_tol(fmt, vmax, kernels=2) - MAX_ABS + 1e-3, (d, spread, algo)
+                assert float((o - exact).abs().max()) <= cm.peaked_tol(fmt, vmax, kernels=2) - cm.MAX_ABS + 1e-3, (d, spread, algo)
                 _sampled_rows_check(fa, oracle, torch, q, k, v, o, fmt, [(0, 0, 0, 16), (1, 2, 1136, 16), (1, 1, 500, 8)],
-                                    f"spread {spread} d={d} algo={algo}", max_abs=MAX_ABS if fmt == 0 else _peaked_tol(fmt, vmax),
+                                    f"spread {spread} d={d} algo={algo}", max_abs=cm.MAX_ABS if fmt == 0 else cm.peaked_tol(fmt, vmax),
                                     rel_l2=None if fmt == 0 else 3e-2)
 
 
@@ -924,7 +914,7 @@ def test_causal_large_grid_item_order(fa, oracle, torch_cuda, fmt):
             want = torch.softmax(s, dim=-1) @ v.float()
             err = float((o - want).abs().max())
             # (bf16 under the mask: the first rows have two or three keys -- peaked by construction)
-            assert err <= (MAX_ABS if fmt == 0 else _peaked_tol(fmt, float(v.float().abs().max()))), (bh, n, d, algo, err)
+            assert err <= (cm.MAX_ABS if fmt == 0 else cm.peaked_tol(fmt, float(v.float().abs().max()))), (bh, n, d, algo, err)
             del s, want, o
         del q, k, v
         torch.cuda.empty_cache()

@@ -6,11 +6,10 @@ kernel that merges wrongly.  No GPU."""
 import numpy as np
 import pytest
 
-import decode_inputs as di
-import logit_inputs as li
+import common_inputs as cm
 import merge_inputs as mi
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 CASES = [pytest.param(*c, id=f"Nq{c[0]}-{'causal' if c[1] else 'full'}-{c[2]}") for c in mi.CASES]
 
 
@@ -155,7 +154,7 @@ def test_causal_rows_keep_the_prefix(oracle):
     Hq = Hkv * G
     assert np.abs(want[:Hq] - o_p[:Hq]).max() < 1e-12 and np.abs(want[Hq:2 * Hq, :2] - o_p[Hq:2 * Hq, :2]).max() < 1e-12
     k, v = mi.concatenated(x, c)
-    full, full_lse = li.expected_f64(x["q"], k, v, [P + L for L in c["lens"]], B, Hkv, G, Nq, True, 0)
+    full, full_lse = cm.expected_f64(x["q"], k, v, [P + L for L in c["lens"]], B, Hkv, G, Nq, True, 0)
     assert np.abs(full[2 * Hq:] - want[2 * Hq:]).max() < 1e-12 and np.abs(full_lse[2 * Hq:] - want_lse[2 * Hq:]).max() < 1e-12
     assert np.abs(full[:Hq] - want[:Hq]).max() > 1e-3      # the cut prefix is another result
 
@@ -181,8 +180,8 @@ def test_census_case(oracle, causal):
     rows = G * Nq
     ones = np.ones(B * Hkv * G)
     zero_k = [np.zeros_like(v) for v in z["v"]]
-    o_p, l_p = li.expected_f64(mi.folded_q(z["q"], B, Hkv, G), zero_k[0], z["v"][0], [P], 1, Hkv, B * G, Nq, False, 0)
-    o_s, l_s = li.expected_f64(z["q"], zero_k[1], z["v"][1], c["lens"], B, Hkv, G, Nq, causal, 0)
+    o_p, l_p = cm.expected_f64(mi.folded_q(z["q"], B, Hkv, G), zero_k[0], z["v"][0], [P], 1, Hkv, B * G, Nq, False, 0)
+    o_s, l_s = cm.expected_f64(z["q"], zero_k[1], z["v"][1], c["lens"], B, Hkv, G, Nq, causal, 0)
     parts = ((o_p.reshape(-1, d), l_p.reshape(-1), rows, B * rows), (o_s.reshape(-1, d), l_s.reshape(-1), Hkv * rows, rows))
     got, _ = mi.merge_f64(parts, B, Hkv, rows)
     assert ci.census_check(got.reshape(z["S"].shape), z["S"], z["cnt"], ones) < 1e-9

@@ -6,10 +6,11 @@ kernel."""
 import numpy as np
 import pytest
 
+import common_inputs as cm
 import decode_inputs as di
 import window_inputs as wi
 
-FMT_D = [pytest.param(fmt, d, id=f"{di.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
+FMT_D = [pytest.param(fmt, d, id=f"{cm.FMT_NAME[fmt]}-d{d}") for d in (64, 128) for fmt in (0, 1)]
 LAUNCHES = [pytest.param(name, W, causal, id=f"{name}-W{W}-{'causal' if causal else 'full'}")
             for name, c in wi.CASES.items() for W in c["windows"] for causal in c["causal"]]
 
@@ -17,19 +18,25 @@ LAUNCHES = [pytest.param(name, W, causal, id=f"{name}-W{W}-{'causal' if causal e
 def test_lows_and_limits():
     """lo_i = max(0, L - Nq + 1 + i - W), the same with and without the mask; under the mask a row sees its own position and the
     W - 1 before it; with one row the last W keys; lo < c wherever c >= 1."""
-    assert wi.lows(1000, 1, 64) == [936] and wi.limits(1000, 1, False) == [1000] and wi.limits(1000, 1, True) == [1000]
-    assert wi.lows(1000, 5, 3) == [993, 994, 995, 996, 997] and wi.limits(1000, 5, True) == [996, 997, 998, 999, 1000]
-    assert wi.limits(1000, 5, False) == [1000] * 5
-    assert wi.lows(4, 5, 3) == [0, 0, 0, 0, 1] and wi.limits(4, 5, True) == [0, 1, 2, 3, 4]
-    assert wi.lows(700, 1, 1024) == [0] and wi.lows(0, 3, 7) == [0, 0, 0] and wi.lows(1000, 2, 0) == [0, 0]
+    def lows(L, nq, W):
+        return cm.row_limits(L, nq, nq, False, W)[0].tolist()
+
+    def limits(L, nq, causal):
+        return cm.row_limits(L, nq, nq, causal)[1].tolist()
+    assert lows(1000, 1, 64) == [936] and limits(1000, 1, False) == [1000] and limits(1000, 1, True) == [1000]
+    assert lows(1000, 5, 3) == [993, 994, 995, 996, 997] and limits(1000, 5, True) == [996, 997, 998, 999, 1000]
+    assert limits(1000, 5, False) == [1000] * 5
+    assert lows(4, 5, 3) == [0, 0, 0, 0, 1] and limits(4, 5, True) == [0, 1, 2, 3, 4]
+    assert lows(700, 1, 1024) == [0] and lows(0, 3, 7) == [0, 0, 0] and lows(1000, 2, 0) == [0, 0]
     assert wi.start_of(1500, 1, 1024) == 476 and wi.start_tile(1500, 1, 1024) == 448
     for L in range(0, 200, 7):
         for nq in (1, 2, 5):
             for W in (1, 2, 3, 63, 64, 65, 500):
-                lo = wi.lows(L, nq, W)
+                lo = lows(L, nq, W)
                 assert lo == sorted(lo) and wi.start_of(L, nq, W) == min(lo)
                 for causal in (False, True):
-                    lim = wi.limits(L, nq, causal)
+                    lim = limits(L, nq, causal)
+                    assert cm.row_limits(L, nq, nq, causal, W)[0].tolist() == lo   # the same with and without the mask
                     assert all(l < c for l, c in zip(lo, lim) if c >= 1)
                     if causal:   # flash-attn's window_size = (W - 1, 0): at most W keys, ending at the row's own position
                         assert all(c - l == min(W, c) for l, c in zip(lo, lim))
@@ -109,7 +116,7 @@ def test_cases_cover_every_regime():
 
 @pytest.mark.parametrize("fmt,d", FMT_D)
 def test_references(oracle, fmt, d):
-    """expected() against the plain float64 softmax: O within 1e-5 of the value scale, lse within 1e-9; zeros and -inf exactly on
+    """cm.expected() (the oracle) against cm.expected_f64 (the plain float64 softmax), for every window case: O within 1e-5 of the value scale, lse within 1e-9; zeros and -inf exactly on
     the rows without a key; at scale 0 the mean of the visible V rows and ln(their number)."""
     for name, c in wi.CASES.items():
         B, Hkv, G, Nq, Ncap = (c[x] for x in ("B", "Hkv", "G", "Nq", "Ncap"))
@@ -117,16 +124,16 @@ def test_references(oracle, fmt, d):
         for W in c["windows"]:
             for causal in c["causal"]:
                 out, lse = wi.reference(oracle, name, d, fmt, W, causal)
-                ref, ref_lse = wi.expected_f64(q, k, v, c["lens"], B, Hkv, G, Nq, causal, W)
+                ref, ref_lse = cm.expected_f64(q, k, v, c["lens"], B, Hkv, G, Nq, causal, W)
                 assert np.isfinite(out).all() and not np.isnan(lse).any()
                 assert np.abs(out - ref).max() <= 1e-5 * max(1.0, np.abs(v).max())
-                dead = np.array([[x == 0 for x in wi.limits(L, Nq, causal)] for L in c["lens"]])
+                dead = np.array([cm.row_limits(L, Nq, Nq, causal)[1] == 0 for L in c["lens"]])
                 dead = np.repeat(dead, Hkv * G, axis=0)
                 assert np.array_equal(np.isneginf(lse), dead) and (out[dead] == 0.0).all()
                 assert np.array_equal(np.isneginf(ref_lse), dead) and np.abs(lse[~dead] - ref_lse[~dead]).max() < 1e-9
                 if name == "rows":
-                    uo, ul = wi.uniform_expected(v, c["lens"], B, Hkv, G, Nq, causal, W)
-                    zo, zl = wi.expected(oracle, q, k, v, c["lens"], B, Hkv, G, Nq, causal, W, scale=0.0)
+                    uo, ul = cm.uniform_expected(v, c["lens"], B, Hkv, G, Nq, causal, W)
+                    zo, zl = cm.expected(oracle, q, k, v, c["lens"], B, Hkv, G, Nq, causal, W, scale=0.0)
                     assert np.abs(zo - uo).max() < 1e-6 and np.array_equal(np.isfinite(ul), ~dead)
                     assert np.abs(zl[~dead] - ul[~dead]).max() < 1e-12
     # a window of one key returns that key's V row
@@ -143,21 +150,21 @@ def test_poison_and_scatter(oracle):
         B, Hkv, G, Nq, Ncap = (c[x] for x in ("B", "Hkv", "G", "Nq", "Ncap"))
         _, (_, kb, vb) = wi.inputs(oracle, B, Hkv, G, Nq, Ncap, 64, 0, c["seed"])
         for W in c["windows"]:
-            kc, vc = wi.poisoned(kb, c["lens"], Nq, W), wi.poisoned(vb, c["lens"], Nq, W)
-            k4 = kb.reshape(B, Hkv, Ncap, 64)
+            k4, v4 = kb.reshape(B, Hkv, Ncap, 64), vb.reshape(B, Hkv, Ncap, 64)
+            kc, vc = cm.poisoned(k4, c["lens"], Nq, W), cm.poisoned(v4, c["lens"], Nq, W)
             for ps in wi.PAGES:
-                kp, vp, table = wi.scatter(kc, vc, c["lens"], Nq, W, ps, seed=ps)
+                kp, vp, table = cm.scatter(kc, vc, c["lens"], ps, ps, Nq, W)
                 named = set()
                 for b, L in enumerate(c["lens"]):
                     sb = wi.start_of(L, Nq, W)
-                    assert (kc[b, :, L:] == di.NAN16).all() and (kc[b, :, :sb] == di.NAN16).all()
+                    assert (kc[b, :, L:] == cm.NAN16).all() and (kc[b, :, :sb] == cm.NAN16).all()
                     assert np.array_equal(kc[b, :, sb:L], k4[b, :, sb:L])
                     for pi in range(Ncap // ps):
                         live = pi < di.live_pages(L, ps) and (pi + 1) * ps > sb
-                        assert (table[b, pi] in di.GARBAGE) != live
+                        assert (table[b, pi] in cm.GARBAGE) != live
                         if live:
                             named.add(int(table[b, pi]))
                             assert np.array_equal(kp[table[b, pi]], kc[b, :, pi * ps:(pi + 1) * ps])
                             assert np.array_equal(vp[table[b, pi]], vc[b, :, pi * ps:(pi + 1) * ps])
                 unnamed = sorted(set(range(kp.shape[0])) - named)
-                assert unnamed and (kp[unnamed] == di.NAN16).all() and (vp[unnamed] == di.NAN16).all()
+                assert unnamed and (kp[unnamed] == cm.NAN16).all() and (vp[unnamed] == cm.NAN16).all()
