@@ -53,6 +53,7 @@ SYMBOLS = (
     "fa_kvcache_decode",
     "fa_kvcache_append_ex",
     "fa_merge_states",
+    "fa_forward_varlen",
     "fa_forward_kvcache_paged_workspace_bytes",
     "fa_forward_kvcache_paged",
 )
@@ -115,6 +116,21 @@ class MergeDesc(C.Structure):
             self.parts[i] = p if isinstance(p, StatePart) else StatePart(*p)
         if "size" not in fields:
             self.size = C.sizeof(MergeDesc)
+
+
+class VarlenDesc(C.Structure):
+    """fa_varlen_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p),
+                ("cu_seqlens_q", C.c_void_p), ("cu_seqlens_k", C.c_void_p), ("B", C.c_int), ("Hkv", C.c_int), ("G", C.c_int),
+                ("d", C.c_int), ("total_q", C.c_int), ("total_k", C.c_int), ("q_stride_t", C.c_longlong), ("q_stride_h", C.c_longlong),
+                ("k_stride_t", C.c_longlong), ("k_stride_h", C.c_longlong), ("v_stride_t", C.c_longlong), ("v_stride_h", C.c_longlong),
+                ("o_stride_t", C.c_longlong), ("o_stride_h", C.c_longlong), ("scale", C.c_float), ("causal", C.c_int),
+                ("in_dtype", C.c_int), ("out_dtype", C.c_int), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(VarlenDesc)
 
 
 class FaError(RuntimeError):
@@ -218,6 +234,9 @@ def lib() -> C.CDLL:
         # the merge of attention states over key ranges
         L.fa_merge_states.argtypes = [C.POINTER(MergeDesc)]
         L.fa_merge_states.restype = C.c_int
+        # variable-length packed prefill
+        L.fa_forward_varlen.argtypes = [C.POINTER(VarlenDesc)]
+        L.fa_forward_varlen.restype = C.c_int
         L.fa_mi355_version.argtypes = []
         L.fa_mi355_version.restype = C.c_char_p
         _lib = L

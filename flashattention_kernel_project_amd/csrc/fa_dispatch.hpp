@@ -9,6 +9,7 @@
 #include <type_traits>
 
 struct fa_merge_desc;   // include/fa_mi355.h
+struct fa_varlen_desc;
 
 namespace fa {
 
@@ -190,6 +191,8 @@ hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
 hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
+// fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is
+hipError_t varlen_dispatch(const ::fa_varlen_desc* desc);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

@@ -433,6 +433,87 @@ def fa_merge_states(outs, lses, out_dtype=None, return_lse: bool = True, stream=
     return (out, lse) if return_lse else out
 
 
+def _packed_strides(t, name: str):
+    """(stride_t, stride_h) in elements of a packed (total, H, d) tensor as it lies; the last dimension must be contiguous"""
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        raise ValueError(f"{name} must be contiguous in its last dimension (any token and head strides are taken as they are)")
+    # the stride of a dimension of size 1 addresses nothing and may hold anything
+    return (t.stride(0) if t.shape[0] > 1 else t.shape[2]), (t.stride(1) if t.shape[1] > 1 else 0)
+
+
+def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, scale: float | None = None, out_dtype=None,
+                      return_lse: bool = False, out=None, stream=None, lse=None):
+    """Variable-length packed prefill (fa_forward_varlen): B sequences of different lengths in one launch.
+    q (total_q, Hq, d), k and v (total_k, Hkv, d) fp16/bf16 device tensors, packed along the token axis; d in {64,128};
+    Hq = G * Hkv (grouped-query: query head hq reads K/V head hq // G, no expanded copy).  Any token and head strides are accepted as
+    long as the last dimension is contiguous (strides multiples of 8 elements, 16-byte aligned storage), so a (H, total, d) tensor
+    passed through .transpose(0, 1) is taken as it lies.
+    cu_seqlens_q, cu_seqlens_k: int32 device tensors [B+1], read on the device only; sequence b owns the rows [cu[b], cu[b+1]),
+    clamped into the tensor.  cu_seqlens_k=None means cu_seqlens_q (self-attention).
+    causal: row i of a sequence sees the keys [0, Lk - Lq + 1 + i) -- aligned to the END of the keys, as in fa_forward_kvcache.  A row
+    that sees no key is O = 0 and lse = -inf.
+    -> o (total_q, Hq, d) of out_dtype (torch.float32, the default, or the input dtype), or (o, lse) with return_lse, lse (Hq, total_q)
+    float32 in natural-log units, as fa_merge_states takes it.  Rows that belong to no sequence are NOT written: in a fresh result they
+    are uninitialised; pass `out` (and `lse`, which implies return_lse) to keep what they held.
+    One kernel, no workspace, nothing read on the host: a captured call follows vectors that are rewritten in place."""
+    import torch
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{name} must be a packed tensor (total, H, d)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("q, k, v must all be fp16 or all bf16")
+    total_q, Hq, d = q.shape
+    total_k, Hkv = k.shape[0], k.shape[1]
+    if v.shape != k.shape or k.shape[2] != d:
+        raise ValueError("k and v must both be (total_k, Hkv, d) with q's d")
+    if d not in (64, 128):
+        raise ValueError("d must be 64 or 128")
+    if total_q <= 0 or total_k <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0:
+        raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
+    if cu_seqlens_k is None:
+        cu_seqlens_k = cu_seqlens_q
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor (the kernel reads 32-bit entries)")
+        if cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-d tensor of B+1 entries")
+    if cu_seqlens_k.numel() != cu_seqlens_q.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both have B+1 entries")
+    B = cu_seqlens_q.numel() - 1
+    (qt, qh), (kt, kh), (vt, vh) = (_packed_strides(t, name) for name, t in (("q", q), ("k", k), ("v", v)))
+    for name, t in (("q", q), ("k", k), ("v", v), ("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    if out_dtype not in (torch.float32, q.dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.shape != q.shape or out.dtype != out_dtype:
+        raise ValueError("out must be a device tensor of q's shape and of out_dtype")
+    if lse is not None:
+        if not isinstance(lse, torch.Tensor) or lse.shape != (Hq, total_q):
+            raise ValueError("lse must be a float32 tensor (Hq, total_q)")
+        _dev_ptr(lse, "lse", (torch.float32,))
+        return_lse = True
+    elif return_lse:
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    ot, oh = _packed_strides(out, "out")
+    desc = capi.VarlenDesc(Q=q.data_ptr(), K=k.data_ptr(), V=v.data_ptr(), O=out.data_ptr(), lse=None if lse is None else lse.data_ptr(),
+                           cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(), B=B, Hkv=Hkv, G=Hq // Hkv, d=d,
+                           total_q=total_q, total_k=total_k, q_stride_t=qt, q_stride_h=qh, k_stride_t=kt, k_stride_h=kh, v_stride_t=vt,
+                           v_stride_h=vh, o_stride_t=ot, o_stride_h=oh, scale=float(scale), causal=int(bool(causal)), in_dtype=in_dt,
+                           out_dtype=capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(q, k, v, out, cu_seqlens_q, cu_seqlens_k, lse)):
+        code = capi.lib().fa_forward_varlen(desc)
+    capi.check("fa_forward_varlen", code)
+    return (out, lse) if return_lse else out
+
+
 def fa_forward_kvcache_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len=None, cache_seqlens=None, block_table=None,
                                      k_scale=None, v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None,
                                      return_lse: bool = False, sinks=None, softcap: float = 0.0, stream=None):

@@ -58,6 +58,8 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.merge_states(outs, lses, out_f32)
     o = torch.ops.fa_mi355.decode_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len, cache_seqlens, scale, causal, sinks,
                                                 softcap, out_fp32)
+    # variable-length packed prefill (ops.fa_forward_varlen): q (total_q,Hq,d), k and v (total_k,Hkv,d), lse (Hq,total_q)
+    o, lse = torch.ops.fa_mi355.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32)
 """
 from __future__ import annotations
 
@@ -68,8 +70,8 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window and four _ex forms, the
-    four .append ops and their four _rope forms, the four decode and four append _ragged forms, .merge_states and
-    .decode_shared_prefix (idempotent)."""
+    four .append ops and their four _rope forms, the four decode and four append _ragged forms, .merge_states,
+    .decode_shared_prefix and .forward_varlen (idempotent)."""
     global _registered
     if _registered:
         return
@@ -388,6 +390,20 @@ def register() -> None:
             sinks=opt(sinks), softcap=softcap, stream=stream(q))
 
     decode_shared_prefix.register_fake(decode_fake)
+
+    # Variable-length packed prefill (ops.fa_forward_varlen): q (total_q,Hq,d), k and v (total_k,Hkv,d) as they lie (any token and head
+    # strides), cu_seqlens_k None = cu_seqlens_q; lse (Hq,total_q) is always returned.
+    @torch.library.custom_op("fa_mi355::forward_varlen", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, float scale, bool causal, "
+                                    "bool out_f32) -> (Tensor, Tensor)")
+    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32):
+        return ops.fa_forward_varlen(q, k, v, cu_seqlens_q.contiguous(), opt(cu_seqlens_k), causal=causal, scale=scale,
+                                     out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q))
+
+    @forward_varlen.register_fake
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32):
+        return (q.new_empty(q.shape, dtype=out_dtype(q, out_f32)),
+                q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32))
 
     _registered = True
 

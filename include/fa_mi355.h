@@ -570,6 +570,52 @@ typedef struct fa_merge_desc {
 } fa_merge_desc;
 int fa_merge_states(const fa_merge_desc* desc);
 
+/* Variable-length packed prefill ("varlen"): B sequences of different lengths in ONE call, Q, K and V packed along the token axis
+ * and cut by one cu_seqlens vector each for queries and keys, grouped-query heads without an expanded K/V, a causal mask aligned to
+ * the end of each sequence's keys, and lse out.  d in {64,128}, fp16 / bf16, O fp32 or 16 bit.
+ * Addressing: row (t, h) of a tensor is the d elements at base + t*stride_t + h*stride_h (strides in ELEMENTS, d contiguous), so
+ * [total, H, d] (the usual varlen layout), [H, total, d] and padded forms are all expressible without a copy.  Q and O have Hkv*G
+ * heads, K and V have Hkv; query head hq = hkv*G + g uses K/V head hkv, as everywhere else in the library.
+ * Sequence bounds are clamped, never a fault: for sequence b, s = clamp(cu[b], 0, total) and e = clamp(cu[b+1], s, total), for q
+ * (cu_seqlens_q, total_q) and k (cu_seqlens_k, total_k) separately; Lq_b = e_q - s_q and Lk_b = e_k - s_k.  A non-monotone vector
+ * gives meaningless results but never an address outside [0, total) rows.
+ * Untouched: rows of Q, K and V that belong to no sequence (at or past cu[B]) are never used and may hold NaN patterns; rows of O
+ * and lse that belong to no sequence are not written.
+ * causal = 0: row i of sequence b sees the keys [0, Lk_b) of that sequence.  causal = 1: row i sees [0, c_i) with
+ * c_i = max(0, Lk_b - Lq_b + 1 + i) -- the decode entries' alignment to the END of the keys, so the last query row sees every key
+ * and Lq == Lk is the ordinary triangle.  A row with c_i = 0, or with Lk_b = 0, gets O = 0 exactly and lse = -inf, never NaN.
+ * lse = ln sum_j exp(scale * q.k_j) over the visible keys, in natural-log units, [Hkv*G, total_q] fp32: row i of sequence b and head
+ * hq is lse[hq*total_q + s_q + i], so it feeds fa_merge_states directly (a prompt chunk merged with a decode over a cached prefix).
+ * scale keeps the library-wide rule: a negative scale negates the logits; 0 gives uniform weights, never NaN (the host hands the
+ * kernel +-FLT_MIN).
+ * Nothing on the host reads cu_seqlens_*: the grid depends on (B, Hkv, G, total_q) only -- floor(total_q/128) + B block slots per
+ * query head, which a workgroup maps to (sequence, query block) on the device -- and there is no workspace.  A call captured into a
+ * HIP graph follows vectors that are rewritten in place later, within the same total_*.  total_q and total_k are HOST integers: the
+ * token rows of Q/O resp. K/V, the bound of every address.
+ * hipErrorInvalidValue, before the device is touched: a NULL descriptor or a wrong `size`; a null Q, K, V, O or cu_seqlens_*; B,
+ * Hkv, G, total_q or total_k <= 0; d not in {64,128}; an in_dtype that is no FA_DTYPE_* or an out_dtype that is no FA_OUT_*; a
+ * stride_t below d, a negative stride_h, or any stride that is not a multiple of 8 elements; a base pointer that is not 16-byte
+ * aligned; a tensor whose last addressable byte, ((total-1)*stride_t + (H-1)*stride_h + d) * element bytes, does not fit 32 bits
+ * (the kernel uses 32-bit buffer offsets); B*Hkv*G, or the block-slot count times Hkv*G, beyond 2^31 - 1 (the grid).
+ * Not part of this entry: a window, sinks, a soft-cap, fp8, a paged K/V, rotary, max_seqlen hints, dropout.
+ * NOT a reference entry point. */
+typedef struct fa_varlen_desc {
+    size_t size;                    /* sizeof(fa_varlen_desc); any other value is refused */
+    const void *Q, *K, *V;          /* device, 16-bit of in_dtype */
+    void* O;                        /* device, of out_dtype (FA_OUT_F32 / FA_OUT_SAME) */
+    float* lse;                     /* device, [Hkv*G, total_q] fp32 contiguous, may be NULL */
+    const int* cu_seqlens_q;        /* device, B+1 int32 */
+    const int* cu_seqlens_k;        /* device, B+1 int32; may be the same pointer as cu_seqlens_q */
+    int B, Hkv, G, d;               /* d in {64,128} */
+    int total_q, total_k;           /* HOST: token rows in Q/O resp. K/V; the bound of every address */
+    long long q_stride_t, q_stride_h, k_stride_t, k_stride_h,
+              v_stride_t, v_stride_h, o_stride_t, o_stride_h;   /* in ELEMENTS; d is contiguous */
+    float scale; int causal;
+    int in_dtype, out_dtype;
+    void* stream;
+} fa_varlen_desc;
+int fa_forward_varlen(const fa_varlen_desc* desc);
+
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
  * the same LDS images, fragment loads and accumulator maps as the product kernels.  d in {64,128}.
