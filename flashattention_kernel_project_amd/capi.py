@@ -16,49 +16,6 @@ ALGO_RP, ALGO_RP_FOLD, ALGO_RP16, ALGO_RP16_FOLD = 21, 22, 23, 24
 ALGO_RP16_DMA = 25
 ALGO_RP16_FOLD_HALF, ALGO_RP16_FOLD_QUARTER, ALGO_RP16_FOLD_1W, ALGO_RP16_FOLD_KS2 = 26, 27, 28, 29
 
-# every symbol include/fa_mi355.h declares
-SYMBOLS = (
-    "flashattn_forward_wmma",
-    "fa_forward",
-    "fa_forward_ex",
-    "fa_forward_causal",
-    "fa_forward_splitkv_workspace_bytes",
-    "fa_forward_splitkv",
-    "fa_debug_stage",
-    "flashattn_streaming_16x16_mw",
-    "flashattn_streaming_16x16_mw_kt",
-    "fa_mi355_version",
-    "fa_mi355_has_experiments",
-    "fa_selected_algo",
-    "fa_selected_kernel",
-    "fa_forward_kvcache_workspace_bytes",
-    "fa_forward_kvcache",
-    "fa_forward_kvcache_fp8",
-    "fa_forward_kvcache_paged_fp8",
-    "fa_kvcache_append",
-    "fa_kvcache_append_paged",
-    "fa_kvcache_append_fp8",
-    "fa_kvcache_append_paged_fp8",
-    "fa_kvcache_append_rope",
-    "fa_kvcache_append_paged_rope",
-    "fa_kvcache_append_fp8_rope",
-    "fa_kvcache_append_paged_fp8_rope",
-    "fa_forward_kvcache_window_workspace_bytes",
-    "fa_forward_kvcache_paged_window_workspace_bytes",
-    "fa_forward_kvcache_window",
-    "fa_forward_kvcache_paged_window",
-    "fa_forward_kvcache_fp8_window",
-    "fa_forward_kvcache_paged_fp8_window",
-    "fa_kvcache_decode_workspace_bytes",
-    "fa_kvcache_decode",
-    "fa_kvcache_append_ex",
-    "fa_merge_states",
-    "fa_forward_varlen",
-    "fa_forward_kvcache_paged_workspace_bytes",
-    "fa_forward_kvcache_paged",
-)
-
-
 KV_16BIT, KV_FP8_E4M3 = 0, 1
 
 
@@ -91,6 +48,19 @@ class KvAppendDesc(C.Structure):
         super().__init__(**fields)
         if "size" not in fields:
             self.size = C.sizeof(KvAppendDesc)
+
+
+def new_desc(cls):
+    """A zeroed descriptor with its `size` set, to be filled by fill(desc, field=value, ...).  The pair is the per-call path of
+    ops._decode and ops._append: Structure's own keyword initialiser costs half of what cls(**fields) costs through the Python-level
+    __init__ above, and that difference is what a decode or append call may cost over the flat entries' positional call
+    (profiles/frontend_refactor.txt)."""
+    desc = cls.__new__(cls)
+    desc.size = C.sizeof(cls)
+    return desc
+
+
+fill = C.Structure.__init__
 
 
 MERGE_MAX_PARTS = 16
@@ -131,6 +101,59 @@ class VarlenDesc(C.Structure):
         super().__init__(**fields)
         if "size" not in fields:
             self.size = C.sizeof(VarlenDesc)
+
+
+def _signatures() -> dict:
+    """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
+    vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
+    sig = {
+        "flashattn_forward_wmma": (i, [vp, vp, vp, vp, i, i, i, f, vp]),
+        "fa_forward": (i, [vp, vp, vp, vp, i, i, i, i, f, i, i, vp]),
+        "fa_forward_ex": (i, [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]),
+        "fa_forward_causal": (i, [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]),
+        "fa_forward_splitkv_workspace_bytes": (sz, [i, i, i, i, i]),
+        "fa_forward_splitkv": (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, i, vp, sz, vp]),
+        "fa_debug_stage": (i, [i, vp, vp, vp, i, i, i, f, i, vp]),
+        "flashattn_streaming_16x16_mw": (i, [vp, vp, vp, vp, i, i, f, vp]),
+        "flashattn_streaming_16x16_mw_kt": (i, [vp, vp, vp, vp, i, i, f, vp]),
+        "fa_mi355_version": (s, []),
+        "fa_mi355_has_experiments": (i, []),
+        "fa_selected_algo": (i, [i, i, i, i, i]),
+        "fa_selected_kernel": (s, [i, i, i, i, i, i]),
+        "fa_forward_kvcache_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "fa_forward_kvcache_paged_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        # the windowed sizing functions: the base one's list with `int window` at the end
+        "fa_forward_kvcache_window_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        "fa_forward_kvcache_paged_window_workspace_bytes": (sz, [i, i, i, i, i, i, i, i]),
+        # the descriptor form of the eight decode entries, with sinks, softcap and seqlens_q
+        "fa_kvcache_decode_workspace_bytes": (sz, [C.POINTER(KvDecodeDesc)]),
+        "fa_kvcache_decode": (i, [C.POINTER(KvDecodeDesc)]),
+        # the descriptor form of the eight append entries, with seqlens_new
+        "fa_kvcache_append_ex": (i, [C.POINTER(KvAppendDesc)]),
+        "fa_merge_states": (i, [C.POINTER(MergeDesc)]),
+        "fa_forward_varlen": (i, [C.POINTER(VarlenDesc)]),
+    }
+    for paged in (False, True):
+        for fp8 in (False, True):
+            layout = "_paged" * paged + "_fp8" * fp8
+            geometry = [i] * (3 if paged else 1)   # Ncap, or of a pool: num_pages, page_size, max_pages
+            # the eight decode entries, from one rule: Q, K, V, O, lse, seqlens [, table] [, k_scale, v_scale], B, Hkv, G, Nq, geometry,
+            # d, scale, causal [, window], in_dtype, out_dtype, workspace, workspace_bytes, stream
+            for window in (False, True):
+                sig["fa_forward_kvcache" + layout + "_window" * window] = (
+                    i, [vp] * (6 + paged + 2 * fp8) + [i] * 4 + geometry + [i, f, i] + [i] * window + [i, i, vp, sz, vp])
+            # the eight append entries, from one rule: Knew, Vnew, K, V, seqlens_k, seqlens_out [, table] [, k_scale, v_scale]
+            # [, Q, Qout, rope_cos, rope_sin], B, Hkv, Nnew, geometry, d [, G, rot_dim, max_pos, interleaved], dtype, stream
+            for rope in (False, True):
+                sig["fa_kvcache_append" + layout + "_rope" * rope] = (
+                    i, [vp] * (6 + paged + 2 * fp8 + 4 * rope) + [i] * 3 + geometry + [i] + [i] * (4 * rope) + [i, vp])
+    for name in ("fa_forward_kvcache_paged_workspace_bytes", "fa_forward_kvcache_paged"):
+        sig[name] = sig.pop(name)   # SYMBOLS ends with this pair, as it always has (tests/test_kvcache_paged_host.py)
+    return sig
+
+
+SIGNATURES = _signatures()
+SYMBOLS = tuple(SIGNATURES)   # every symbol include/fa_mi355.h declares
 
 
 class FaError(RuntimeError):
@@ -177,68 +200,9 @@ def lib() -> C.CDLL:
                 "or `make -C flashattention_kernel_project_amd/csrc`")
         _share_torch_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        vp, i, f = C.c_void_p, C.c_int, C.c_float
-        L.flashattn_forward_wmma.argtypes = [vp, vp, vp, vp, i, i, i, f, vp]
-        L.fa_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, i, vp]
-        L.fa_forward_ex.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]
-        L.fa_forward_causal.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, i, i, vp]
-        L.fa_forward_splitkv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, i, i, vp, C.c_size_t, vp]
-        L.fa_forward_splitkv_workspace_bytes.argtypes = [i, i, i, i, i]
-        L.fa_debug_stage.argtypes = [i, vp, vp, vp, i, i, i, f, i, vp]
-        L.flashattn_streaming_16x16_mw.argtypes = [vp, vp, vp, vp, i, i, f, vp]
-        L.flashattn_streaming_16x16_mw_kt.argtypes = [vp, vp, vp, vp, i, i, f, vp]
-        for s in SYMBOLS[:9]:
-            getattr(L, s).restype = C.c_int
-        L.fa_mi355_has_experiments.argtypes = []
-        L.fa_mi355_has_experiments.restype = C.c_int
-        L.fa_selected_algo.argtypes = [i, i, i, i, i]
-        L.fa_selected_algo.restype = C.c_int
-        L.fa_selected_kernel.argtypes = [i, i, i, i, i, i]
-        L.fa_selected_kernel.restype = C.c_char_p
-        L.fa_forward_splitkv_workspace_bytes.restype = C.c_size_t
-        # the eight decode entries, from one rule: Q, K, V, O, lse, seqlens [, table] [, k_scale, v_scale], B, Hkv, G, Nq, Ncap (paged:
-        # num_pages, page_size, max_pages), d, scale, causal [, window], in_dtype, out_dtype, workspace, workspace_bytes, stream
-        for paged in (False, True):
-            for fp8 in (False, True):
-                for window in (False, True):
-                    fn = getattr(L, "fa_forward_kvcache" + "_paged" * paged + "_fp8" * fp8 + "_window" * window)
-                    fn.argtypes = ([vp] * (6 + paged + 2 * fp8) + [i] * (7 if paged else 5) + [i, f, i] + [i] * window
-                                   + [i, i, vp, C.c_size_t, vp])
-                    fn.restype = C.c_int
-        L.fa_forward_kvcache_workspace_bytes.argtypes = [i, i, i, i, i, i]
-        L.fa_forward_kvcache_workspace_bytes.restype = C.c_size_t
-        L.fa_forward_kvcache_paged_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
-        L.fa_forward_kvcache_paged_workspace_bytes.restype = C.c_size_t
-        # the windowed sizing functions: the base one's list with `int window` at the end
-        L.fa_forward_kvcache_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
-        L.fa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
-        L.fa_forward_kvcache_paged_window_workspace_bytes.argtypes = [i, i, i, i, i, i, i, i]
-        L.fa_forward_kvcache_paged_window_workspace_bytes.restype = C.c_size_t
-        # the descriptor form of the eight, with sinks and softcap
-        L.fa_kvcache_decode.argtypes = [C.POINTER(KvDecodeDesc)]
-        L.fa_kvcache_decode.restype = C.c_int
-        L.fa_kvcache_decode_workspace_bytes.argtypes = [C.POINTER(KvDecodeDesc)]
-        L.fa_kvcache_decode_workspace_bytes.restype = C.c_size_t
-        # the eight append entries, from one rule: Knew, Vnew, K, V, seqlens_k, seqlens_out [, table] [, k_scale, v_scale]
-        # [, Q, Qout, rope_cos, rope_sin], B, Hkv, Nnew, Ncap (paged: num_pages, page_size, max_pages), d
-        # [, G, rot_dim, max_pos, interleaved], dtype, stream
-        for paged in (False, True):
-            for fp8 in (False, True):
-                for rope in (False, True):
-                    fn = getattr(L, "fa_kvcache_append" + "_paged" * paged + "_fp8" * fp8 + "_rope" * rope)
-                    fn.argtypes = [vp] * (6 + paged + 2 * fp8 + 4 * rope) + [i] * (6 if paged else 4) + [i] + [i] * (4 * rope) + [i, vp]
-                    fn.restype = C.c_int
-        # the descriptor form of the eight, with seqlens_new
-        L.fa_kvcache_append_ex.argtypes = [C.POINTER(KvAppendDesc)]
-        L.fa_kvcache_append_ex.restype = C.c_int
-        # the merge of attention states over key ranges
-        L.fa_merge_states.argtypes = [C.POINTER(MergeDesc)]
-        L.fa_merge_states.restype = C.c_int
-        # variable-length packed prefill
-        L.fa_forward_varlen.argtypes = [C.POINTER(VarlenDesc)]
-        L.fa_forward_varlen.restype = C.c_int
-        L.fa_mi355_version.argtypes = []
-        L.fa_mi355_version.restype = C.c_char_p
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

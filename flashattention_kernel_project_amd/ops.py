@@ -47,6 +47,24 @@ def _dev_ptr(t, name: str, dtypes):
     return t.data_ptr()
 
 
+def _in_dt(dtype) -> int:
+    """the C ABI's id of a 16-bit input dtype that has been checked"""
+    import torch
+    return capi.F16 if dtype == torch.float16 else capi.BF16
+
+
+def _out_dt(out_dtype, in_dtype) -> int:
+    """the C ABI's id of an output dtype, which is float32 or the input's"""
+    import torch
+    if out_dtype not in (torch.float32, in_dtype):
+        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    return capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME
+
+
+def _scale_or_default(scale, d: int):
+    return 1.0 / math.sqrt(d) if scale is None else scale
+
+
 def flashattn_forward_wmma(Q, K, V, O, BH: int, N: int, D: int, scale: float, stream=None) -> None:
     """(Q,K,V,O,BH,N,D,scale) of flashattn_forward_wmma_kernel
     (FlashAttention/flashattn_forward_wmma/flashattn_forward_wmma.cu:49-58).
@@ -80,21 +98,15 @@ def fa_forward(q, k, v, scale: float | None = None, out_dtype=None, algo: int = 
         raise ValueError("q, k, v must have identical shapes (self-attention, Nq == Nk)")
     if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError("q, k, v must all be fp16 or all bf16")
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    in_dt = _in_dt(q.dtype)
     if out_dtype is None:
         out_dtype = torch.float32 if out is None else out.dtype
-    if out_dtype == torch.float32:
-        out_dt = capi.OUT_F32
-    elif out_dtype == q.dtype:
-        out_dt = capi.OUT_SAME
-    else:
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    out_dt = _out_dt(out_dtype, q.dtype)
     if out is None:
         out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     elif out.shape != q.shape or out.dtype != out_dtype:
         raise ValueError("out has the wrong shape or dtype")
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
+    scale = _scale_or_default(scale, d)
     dts = (torch.float16, torch.bfloat16)
     fn_name = "fa_forward_causal" if causal else "fa_forward_ex"
     with torch.cuda.device(_one_device(q, k, v, out)):   # the launch goes to the CURRENT device: make that the tensors' device
@@ -123,23 +135,19 @@ def fa_forward_splitkv(q, k, v, scale: float | None = None, out_dtype=None, work
     rows = (Hq // H) * Nq   # query rows that share one K/V head
     if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError("q, k, v must all be fp16 or all bf16")
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
+    in_dt = _in_dt(q.dtype)
     out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    out_dt = _out_dt(out_dtype, q.dtype)
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     need = splitkv_workspace_bytes(B, H, rows, Nk, d)   # from the shape alone: the split count reads no device property
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
+    scale = _scale_or_default(scale, d)
     dts = (torch.float16, torch.bfloat16)
     ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k, "k", dts), _dev_ptr(v, "v", dts), _dev_ptr(out, "out", (out_dtype,)))
     with torch.cuda.device(_one_device(q, k, v, out, workspace)):
-        code = capi.lib().fa_forward_splitkv(
-            *ptrs, B, H, rows, Nk, d, float(scale), in_dt, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
-            ws_ptr, ws_len, _stream_ptr(stream))
+        code = capi.lib().fa_forward_splitkv(*ptrs, B, H, rows, Nk, d, float(scale), in_dt, out_dt, ws_ptr, ws_len, _stream_ptr(stream))
     capi.check("fa_forward_splitkv", code)
     return out
 
@@ -151,13 +159,12 @@ def splitkv_workspace_bytes(B: int, H: int, Nq: int, Nk: int, d: int) -> int:
 def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream, window, paged=False,
             block_table=None, scales=None, sinks=None, softcap=0.0, seqlens_q=None):
     """The four decode front ends: k, v (named k_name, v_name in messages) are a cache [B,Hkv,Ncap,d] or, with `paged`, a pool
-    [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one.  The C entry
-    is fa_forward_kvcache + _paged + _fp8 + _window, and each suffix inserts its arguments: the table after the lengths, the two
-    scales after that, the geometry of the pool in the place of Ncap, the window after causal.  With `sinks` (a tensor) or a
-    `softcap` other than 0 or `seqlens_q` (a tensor) the call goes through the descriptor entry fa_kvcache_decode instead, which alone has
-    the three."""
+    [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one.  Every call
+    is fa_kvcache_decode, whose descriptor names each field; without sinks, softcap and seqlens_q that IS the flat entry
+    fa_forward_kvcache + _paged + _fp8 + _window of the same layout (include/fa_mi355.h)."""
     import torch
     fp8 = scales is not None
+    table_ptr = ks_ptr = vs_ptr = None
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[3] != k.shape[3] or (not paged and q.shape[0] != k.shape[0]):
         raise ValueError(f"q must be [B,Hq,Nq,d] and {k_name}, {v_name} " + ("[num_pages,Hkv,page_size,d]" if paged else "[B,Hkv,Ncap,d]"))
     B, Hq, Nq, d = q.shape
@@ -166,7 +173,8 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     if fp8:   # the cache format is judged first, then (paged) the table: before q and before anything that needs a device
         if k.dtype != torch.float8_e4m3fn or v.dtype != torch.float8_e4m3fn:
             raise ValueError(f"{k_name}, {v_name}: {_FP8_CACHE} (got {k.dtype}, {v.dtype})")
-        args = (_table_ptr(block_table, B),) if paged else ()
+        if paged:
+            table_ptr = _table_ptr(block_table, B)
         if q.dtype not in dts:
             raise ValueError("q must be fp16 or bf16")
     if Hq % Hkv != 0:
@@ -175,61 +183,44 @@ def _decode(q, k, v, k_name, v_name, cache_seqlens, causal, scale, out_dtype, re
     if not fp8 and (q.dtype not in dts or k.dtype != q.dtype or v.dtype != q.dtype):
         raise ValueError(f"q, {k_name}, {v_name} must all be fp16 or all bf16")
     out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    out_dt = _out_dt(out_dtype, q.dtype)
     if fp8:
-        args += tuple(_scale_ptrs(scales[0], scales[1], Hkv))
-        cache_dts = (torch.float8_e4m3fn,)
-    else:
-        args = (_table_ptr(block_table, B),) if paged else ()
-        cache_dts = dts
+        ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], Hkv)
+    elif paged:
+        table_ptr = _table_ptr(block_table, B)
+    cache_dts = (torch.float8_e4m3fn,) if fp8 else dts
     len_ptr = None
     if cache_seqlens is not None:
         if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B:
             raise ValueError("cache_seqlens must be an int32 device tensor of shape [B]")
         len_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
-    ptrs = (_dev_ptr(q, "q", dts), _dev_ptr(k, "k cache" if fp8 else k_name, cache_dts),
-            _dev_ptr(v, "v cache" if fp8 else v_name, cache_dts))
+    q_ptr, k_ptr, v_ptr = (_dev_ptr(q, "q", dts), _dev_ptr(k, "k cache" if fp8 else k_name, cache_dts),
+                           _dev_ptr(v, "v cache" if fp8 else v_name, cache_dts))
     out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
     window = _window(window)
     softcap = _softcap(softcap)
     sink_ptr = _sinks_ptr(sinks, Hq, q.device)
     nq_ptr = _counts_ptr(seqlens_q, "seqlens_q", B, q.device)
-    # in the place of Ncap a pool has (num_pages, page_size, max_pages)
-    cap = (k.shape[0], k.shape[2], block_table.shape[1]) if paged else (k.shape[2],)
+    # a cache has Ncap, a pool (num_pages, page_size, max_pages); the fields of the other layout are 0
+    Ncap, num_pages, page_size, max_pages = (0, k.shape[0], k.shape[2], block_table.shape[1]) if paged else (k.shape[2], 0, 0, 0)
     if workspace is None:
         # from the shape and the window alone (the split count reads no device property); the 16-bit entry's for an fp8 cache
-        need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, cap[2], cap[1], d, window) if paged \
-            else kvcache_window_workspace_bytes(B, Hkv, G, Nq, cap[0], d, window)
+        need = kvcache_paged_window_workspace_bytes(B, Hkv, G, Nq, max_pages, page_size, d, window) if paged \
+            else kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, window)
         if need:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
-    if sinks is not None or softcap != 0.0 or seqlens_q is not None:
-        # args: [table] [k_scale, v_scale]; the descriptor names every field, so no suffix rule is needed
-        desc = capi.KvDecodeDesc(
-            Q=ptrs[0], K=ptrs[1], V=ptrs[2], O=out.data_ptr(), lse=lse.data_ptr() if return_lse else None, seqlens_k=len_ptr,
-            block_table=args[0] if paged else None, k_scale=args[-2] if fp8 else None, v_scale=args[-1] if fp8 else None,
-            sinks=sink_ptr, kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, G=G, Nq=Nq, d=d,
-            Ncap=0 if paged else cap[0], num_pages=cap[0] if paged else 0, page_size=cap[1] if paged else 0,
-            max_pages=cap[2] if paged else 0, scale=float(scale), causal=1 if causal else 0, window=window, softcap=softcap,
-            in_dtype=capi.F16 if q.dtype == torch.float16 else capi.BF16,
-            out_dtype=capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, workspace=ws_ptr, workspace_bytes=ws_len,
-            stream=_stream_ptr(stream), seqlens_q=nq_ptr)
-        with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace, sinks, seqlens_q)):
-            code = capi.lib().fa_kvcache_decode(desc)
-        capi.check("fa_kvcache_decode", code)
-        return (out, lse) if return_lse else out
-    fn_name = "fa_forward_kvcache" + ("_paged" if paged else "") + ("_fp8" if fp8 else "") + ("_window" if window else "")
-    args = ptrs + (out.data_ptr(), lse.data_ptr() if return_lse else None, len_ptr) + args + (B, Hkv, G, Nq) + cap \
-        + (d, float(scale), 1 if causal else 0) + ((window,) if window else ()) \
-        + (capi.F16 if q.dtype == torch.float16 else capi.BF16, capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME,
-           ws_ptr, ws_len, _stream_ptr(stream))
-    with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace)):
-        code = getattr(capi.lib(), fn_name)(*args)
-    capi.check(fn_name, code)
+    desc = capi.new_desc(capi.KvDecodeDesc)
+    capi.fill(
+        desc, Q=q_ptr, K=k_ptr, V=v_ptr, O=out.data_ptr(), lse=lse.data_ptr() if return_lse else None, seqlens_k=len_ptr,
+        block_table=table_ptr, k_scale=ks_ptr, v_scale=vs_ptr, sinks=sink_ptr, kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT,
+        B=B, Hkv=Hkv, G=G, Nq=Nq, d=d, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages,
+        scale=float(_scale_or_default(scale, d)), causal=1 if causal else 0, window=window, softcap=softcap, in_dtype=_in_dt(q.dtype),
+        out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len, stream=_stream_ptr(stream), seqlens_q=nq_ptr)
+    with torch.cuda.device(_one_device(q, k, v, block_table, *(scales or ()), cache_seqlens, workspace, sinks, seqlens_q)):
+        code = capi.lib().fa_kvcache_decode(desc)
+    capi.check("fa_kvcache_decode", code)
     return (out, lse) if return_lse else out
 
 
@@ -257,7 +248,8 @@ def fa_forward_kvcache(q, k_cache, v_cache, cache_seqlens=None, causal: bool = F
     n_b = min(max(seqlens_q[b], 0), Nq) live rows per head, rows i < n_b, with n_b in the place of Nq in the causal and window limits.
     Dead rows return O = 0 and lse = -inf exactly and their q rows are never used; n_b = 0 is an idle slot that reads nothing of the
     sequence.  Read on the device only: a captured call follows counts rewritten in place; grid, splits and workspace follow the padded Nq.
-    With any of the three the call is fa_kvcache_decode; workspace sizes are unchanged."""
+    The C call is always the descriptor entry fa_kvcache_decode; without the last three it is, bit for bit, the flat entry named above
+    (fa_forward_kvcache, with a window fa_forward_kvcache_window).  Workspace sizes do not depend on the three."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
                    window, sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
@@ -359,9 +351,9 @@ def fa_forward_kvcache_fp8(q, k_cache, v_cache, k_scale=None, v_scale=None, cach
     is v_scale[h] * softmax.v8, lse is that of the scaled logits.  Scales must be finite and > 0; they are read on the device only,
     like cache_seqlens, so a captured call follows all three when they are rewritten in place.  quantize_kv_fp8() makes a cache
     and its scales from a 16-bit or fp32 tensor.
-    Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (then
-    fa_forward_kvcache_fp8_window and kvcache_window_workspace_bytes), sinks and softcap (the sinks take neither scale), seqlens_q -- is
-    fa_forward_kvcache's."""
+    Everything else -- cache_seqlens, causal, rows without a key, return_lse, the workspace (kvcache_workspace_bytes), window (what
+    fa_forward_kvcache_fp8_window computes, on kvcache_window_workspace_bytes), sinks and softcap (the sinks take neither scale),
+    seqlens_q, the descriptor call -- is fa_forward_kvcache's."""
     return _decode(q, k_cache, v_cache, "k_cache", "v_cache", cache_seqlens, causal, scale, out_dtype, return_lse, workspace, stream,
                    window, scales=(k_scale, v_scale), sinks=sinks, softcap=softcap, seqlens_q=seqlens_q)
 
@@ -484,11 +476,9 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
     for name, t in (("q", q), ("k", k), ("v", v), ("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
-    in_dt = capi.F16 if q.dtype == torch.float16 else capi.BF16
     if out_dtype is None:
         out_dtype = torch.float32 if out is None else out.dtype
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    out_dt = _out_dt(out_dtype, q.dtype)
     if out is None:
         out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
     elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.shape != q.shape or out.dtype != out_dtype:
@@ -500,14 +490,12 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
         return_lse = True
     elif return_lse:
         lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(d)
     ot, oh = _packed_strides(out, "out")
     desc = capi.VarlenDesc(Q=q.data_ptr(), K=k.data_ptr(), V=v.data_ptr(), O=out.data_ptr(), lse=None if lse is None else lse.data_ptr(),
                            cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(), B=B, Hkv=Hkv, G=Hq // Hkv, d=d,
                            total_q=total_q, total_k=total_k, q_stride_t=qt, q_stride_h=qh, k_stride_t=kt, k_stride_h=kh, v_stride_t=vt,
-                           v_stride_h=vh, o_stride_t=ot, o_stride_h=oh, scale=float(scale), causal=int(bool(causal)), in_dtype=in_dt,
-                           out_dtype=capi.OUT_F32 if out_dtype == torch.float32 else capi.OUT_SAME, stream=_stream_ptr(stream))
+                           v_stride_h=vh, o_stride_t=ot, o_stride_h=oh, scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)),
+                           in_dtype=_in_dt(q.dtype), out_dtype=out_dt, stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, k, v, out, cu_seqlens_q, cu_seqlens_k, lse)):
         code = capi.lib().fa_forward_varlen(desc)
     capi.check("fa_forward_varlen", code)
@@ -562,8 +550,7 @@ def fa_forward_kvcache_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, pr
         raise ValueError("prefix_len must be an int32 device tensor of shape [1]")
     _dev_ptr(q, "q", dts)
     out_dtype = out_dtype or torch.float32
-    if out_dtype not in (torch.float32, q.dtype):
-        raise ValueError("out_dtype must be torch.float32 or the input dtype")
+    _out_dt(out_dtype, q.dtype)
     if isinstance(stream, torch.cuda.Stream):
         on_stream = torch.cuda.stream(stream)
     elif stream is None:
@@ -609,26 +596,30 @@ def quantize_kv_fp8(x, scale=None):
     return x8, scale.contiguous()
 
 
-def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, what, rope=(None, None, None, None, False)):
-    """What the four append front ends share once the cache is known to be 4-D: shapes and dtypes of the new rows against the cache
-    ([*, Hkv, rows, d]), the rotary arguments (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), the two length tensors.
-    -> (B, Hkv, Nnew, d, dtype id, source pointers, cache pointers, len_ptr, out_ptr, rotary groups or None)"""
+def _append(k_new, v_new, k_dst, v_dst, what, cache_seqlens, seqlens_out, stream, rope, seqlens_new, paged=False, block_table=None,
+            scales=None):
+    """The four append front ends: k_dst, v_dst (named `what` in messages) are a cache [B,Hkv,Ncap,d] or, with `paged`, a pool
+    [num_pages,Hkv,page_size,d] behind block_table; scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one; rope is
+    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved).  Every call is fa_kvcache_append_ex, whose descriptor names each field;
+    without seqlens_new that IS the flat entry fa_kvcache_append + _paged + _fp8 + _rope of the same layout (include/fa_mi355.h)."""
     import torch
-    if k_new.dim() != 4 or v_new.shape != k_new.shape or k_new.shape[1] != k_dst.shape[1] or k_new.shape[3] != k_dst.shape[3]:
+    fp8 = scales is not None
+    if k_dst.dim() != 4 or v_dst.shape != k_dst.shape or k_new.dim() != 4 or (not paged and k_new.shape[0] != k_dst.shape[0]):
+        raise ValueError(f"k_new, v_new must be [B,Hkv,Nnew,d] and {what} " + ("[num_pages,Hkv,page_size,d]" if paged else "[B,Hkv,Ncap,d]"))
+    if fp8 and (k_dst.dtype != torch.float8_e4m3fn or v_dst.dtype != torch.float8_e4m3fn):   # judged first, as in the decode front end
+        raise ValueError(f"{what}: {_FP8_CACHE} (got {k_dst.dtype}, {v_dst.dtype})")
+    table_ptr = _table_ptr(block_table, k_new.shape[0]) if paged else None
+    ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], k_new.shape[1]) if fp8 else (None, None)
+    if v_new.shape != k_new.shape or k_new.shape[1] != k_dst.shape[1] or k_new.shape[3] != k_dst.shape[3]:
         raise ValueError(f"k_new, v_new must be [B,Hkv,Nnew,d] with the Hkv and d of {what}")
     B, Hkv, Nnew, d = k_new.shape
     dts = (torch.float16, torch.bfloat16)
     if k_new.dtype not in dts or v_new.dtype != k_new.dtype:
         raise ValueError("k_new, v_new must both be fp16 or both bf16")
-    if fp8:
-        if k_dst.dtype != torch.float8_e4m3fn or v_dst.dtype != torch.float8_e4m3fn:
-            raise ValueError(f"{what}: {_FP8_CACHE} (got {k_dst.dtype}, {v_dst.dtype})")
-        cache_dts = (torch.float8_e4m3fn,)
-    else:
-        if k_dst.dtype != k_new.dtype or v_dst.dtype != k_new.dtype:
-            raise ValueError(f"{what} must have the dtype of k_new ({k_new.dtype}; got {k_dst.dtype}, {v_dst.dtype}); an fp8 cache "
-                             "goes through fa_kvcache_append_fp8 / fa_kvcache_append_paged_fp8")
-        cache_dts = dts
+    if not fp8 and (k_dst.dtype != k_new.dtype or v_dst.dtype != k_new.dtype):
+        raise ValueError(f"{what} must have the dtype of k_new ({k_new.dtype}; got {k_dst.dtype}, {v_dst.dtype}); an fp8 cache "
+                         "goes through fa_kvcache_append_fp8 / fa_kvcache_append_paged_fp8")
+    cache_dts = (torch.float8_e4m3fn,) if fp8 else dts
     rot = _rope_shapes(k_new, *rope)
     len_ptrs = []
     for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
@@ -638,14 +629,29 @@ def _append_args(k_new, v_new, k_dst, v_dst, cache_seqlens, seqlens_out, fp8, wh
         if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] != B:
             raise ValueError(f"{name} must be an int32 device tensor of shape [B]")
         len_ptrs.append(_dev_ptr(t, name, (torch.int32,)))
-    src = (_dev_ptr(k_new, "k_new", dts), _dev_ptr(v_new, "v_new", dts))
-    dst = (_dev_ptr(k_dst, "k cache", cache_dts), _dev_ptr(v_dst, "v cache", cache_dts))
+    knew_ptr, vnew_ptr = _dev_ptr(k_new, "k_new", dts), _dev_ptr(v_new, "v_new", dts)
+    k_ptr, v_ptr = _dev_ptr(k_dst, "k cache", cache_dts), _dev_ptr(v_dst, "v cache", cache_dts)
+    rope_fields, rope_tensors = {}, ()   # without rotary_cos the rotary fields stay as new_desc leaves them: 0 and NULL
     if rot is not None:
-        q, q_out, cos, sin, ints = rot
-        ptrs = (None, None) if q is None else (_dev_ptr(q, "q", dts), _dev_ptr(q_out, "q_out", dts))
-        rot = (ptrs + (_dev_ptr(cos, "rotary_cos", (torch.float32,)), _dev_ptr(sin, "rotary_sin", (torch.float32,))), ints,
-               (q, q_out, cos, sin))
-    return B, Hkv, Nnew, d, capi.F16 if k_new.dtype == torch.float16 else capi.BF16, src, dst, len_ptrs[0], len_ptrs[1], rot
+        q, q_out, cos, sin, (G, rot_dim, max_pos, interleaved) = rot
+        q_ptr, qout_ptr = (None, None) if q is None else (_dev_ptr(q, "q", dts), _dev_ptr(q_out, "q_out", dts))
+        rope_fields = dict(Q=q_ptr, Qout=qout_ptr, rope_cos=_dev_ptr(cos, "rotary_cos", (torch.float32,)),
+                           rope_sin=_dev_ptr(sin, "rotary_sin", (torch.float32,)), G=G, rot_dim=rot_dim, max_pos=max_pos,
+                           interleaved=interleaved)
+        rope_tensors = (q, q_out, cos, sin)
+    cnt_ptr = _counts_ptr(seqlens_new, "seqlens_new", B, k_new.device)
+    # a cache has Ncap, a pool (num_pages, page_size, max_pages); the fields of the other layout are 0
+    Ncap, num_pages, page_size, max_pages = (0, k_dst.shape[0], k_dst.shape[2], block_table.shape[1]) if paged else (k_dst.shape[2], 0, 0, 0)
+    desc = capi.new_desc(capi.KvAppendDesc)
+    capi.fill(
+        desc, Knew=knew_ptr, Vnew=vnew_ptr, K=k_ptr, V=v_ptr, seqlens_k=len_ptrs[0], seqlens_out=len_ptrs[1], seqlens_new=cnt_ptr,
+        block_table=table_ptr, k_scale=ks_ptr, v_scale=vs_ptr, kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv,
+        Nnew=Nnew, d=d, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, dtype=_in_dt(k_new.dtype),
+        stream=_stream_ptr(stream), **rope_fields)
+    with torch.cuda.device(_one_device(k_new, v_new, k_dst, v_dst, block_table, *(scales or ()), cache_seqlens, seqlens_out, *rope_tensors,
+                                       seqlens_new)):
+        code = capi.lib().fa_kvcache_append_ex(desc)
+    capi.check("fa_kvcache_append_ex", code)
 
 
 def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
@@ -684,36 +690,6 @@ def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
     return q, q_out, cos, sin, (G, rot_dim, max_pos, 1 if interleaved else 0)
 
 
-def _append_call(base, tensors, head, geometry, d, dt, rot, stream, seqlens_new=None):
-    """The C call of an append front end: `base` + "_rope" with the rotary groups inserted, pointers before B and integers after d.
-    With seqlens_new (a tensor) the call is fa_kvcache_append_ex, whose descriptor names every field."""
-    import torch
-    name = base + ("_rope" if rot else "")
-    ptrs, ints, more = rot if rot else ((), (), ())
-    if seqlens_new is not None:
-        paged, fp8 = "_paged" in base, "_fp8" in base
-        B, Hkv, Nnew = geometry[:3]
-        cnt_ptr = _counts_ptr(seqlens_new, "seqlens_new", B, tensors[0].device)
-        rest = list(head[6:])          # [table] [k_scale, v_scale]
-        table = rest.pop(0) if paged else None
-        ks, vs = rest if fp8 else (None, None)
-        G, rot_dim, max_pos, il = ints if rot else (0, 0, 0, 0)
-        q_ptr, qout_ptr, cos_ptr, sin_ptr = ptrs if rot else (None, None, None, None)
-        desc = capi.KvAppendDesc(
-            Knew=head[0], Vnew=head[1], K=head[2], V=head[3], seqlens_k=head[4], seqlens_out=head[5], seqlens_new=cnt_ptr,
-            block_table=table, k_scale=ks, v_scale=vs, Q=q_ptr, Qout=qout_ptr, rope_cos=cos_ptr, rope_sin=sin_ptr,
-            kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, Nnew=Nnew, d=d, Ncap=0 if paged else geometry[3],
-            num_pages=geometry[3] if paged else 0, page_size=geometry[4] if paged else 0, max_pages=geometry[5] if paged else 0,
-            G=G, rot_dim=rot_dim, max_pos=max_pos, interleaved=il, dtype=dt, stream=_stream_ptr(stream))
-        with torch.cuda.device(_one_device(*tensors, *more, seqlens_new)):
-            code = capi.lib().fa_kvcache_append_ex(desc)
-        capi.check("fa_kvcache_append_ex", code)
-        return
-    with torch.cuda.device(_one_device(*tensors, *more)):
-        code = getattr(capi.lib(), name)(*head, *ptrs, *geometry, d, *ints, dt, _stream_ptr(stream))
-    capi.check(name, code)
-
-
 def _scale_ptrs(k_scale, v_scale, Hkv):
     import torch
     out = []
@@ -746,22 +722,19 @@ def fa_kvcache_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, seqlen
     Lengths are read on the device only: append(seqlens_out=lens) followed by fa_forward_kvcache(lens), captured once into a graph,
     serves every step of a growing cache.
     rotary_cos, rotary_sin: float32 contiguous device tensors [max_pos, rot_dim/2] (rot_dim a multiple of 16 in [16, d]), or None.  With
-    them the call is fa_kvcache_append_rope: K is rotated at its position p = L_b + t (table row min(p, max_pos - 1)) on its way into
+    them the call is what fa_kvcache_append_rope computes: K is rotated at its position p = L_b + t (table row min(p, max_pos - 1)) on its way into
     the cache, elements [rot_dim, d) pass through, V is written as without them.  rotary_interleaved: False pairs (x[i], x[i+rot_dim/2])
     (NeoX / HF), True pairs (x[2i], x[2i+1]) (GPT-J).  The arithmetic is stepwise fp32 without fused multiply-add (include/fa_mi355.h).
     q: [B,Hq,Nnew,d] of k_new's dtype, Hq a multiple of Hkv, or None: rotated by the same positions in the same launch, into q_out
     (same shape and dtype, not overlapping q) or, with q_out=None, in place.  Without rotary_cos, q and q_out must be None.
     seqlens_new: None, or an int32 contiguous device tensor [B] that does not overlap seqlens_out: Nnew is then the PADDED token count,
     sequence b appends its first m_b = min(max(seqlens_new[b], 0), Nnew) tokens and grows by m_b; a token t >= m_b is not written (no
-    table entry is read for it) and its q row reaches q_out unchanged.  Read on the device only.  The call is fa_kvcache_append_ex;
-    fa_forward_kvcache(seqlens_q=the same tensor) is its read half."""
-    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
-        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
-        k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, False, "k_cache, v_cache",
-        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
-    _append_call("fa_kvcache_append", (k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out), (*src, *dst, len_ptr, out_ptr),
-                 (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream, seqlens_new)
+    table entry is read for it) and its q row reaches q_out unchanged.  Read on the device only.
+    fa_forward_kvcache(seqlens_q=the same tensor) is its read half.
+    The C call is always the descriptor entry fa_kvcache_append_ex; without seqlens_new it is, byte for byte, the flat entry of the
+    form (fa_kvcache_append, fa_kvcache_append_rope)."""
+    _append(k_new, v_new, k_cache, v_cache, "k_cache, v_cache", cache_seqlens, seqlens_out, stream,
+            (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), seqlens_new)
 
 
 def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens=None, seqlens_out=None, stream=None, *, q=None,
@@ -773,15 +746,8 @@ def fa_kvcache_append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seq
     between sequences may only be written by the caller's copy-on-write (not checked).
     q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_paged_rope); the q row of a
     dropped token is still rotated.  seqlens_new: as in fa_kvcache_append."""
-    if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
-        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
-    tbl_ptr = _table_ptr(block_table, k_new.shape[0])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
-        k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, False, "k_pool, v_pool",
-        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
-    _append_call("fa_kvcache_append_paged", (k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out),
-                 (*src, *dst, len_ptr, out_ptr, tbl_ptr), (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt,
-                 rot, stream, seqlens_new)
+    _append(k_new, v_new, k_pool, v_pool, "k_pool, v_pool", cache_seqlens, seqlens_out, stream,
+            (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), seqlens_new, paged=True, block_table=block_table)
 
 
 def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=None, cache_seqlens=None, seqlens_out=None,
@@ -792,17 +758,8 @@ def fa_kvcache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale=None, v_scale=
     k_scale, v_scale: float32 contiguous device tensors [Hkv], finite and > 0, or None (1.0); read on the device only.
     q, q_out, rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append (fa_kvcache_append_fp8_rope).  The fp32 rotated K is
     quantised directly, without a 16-bit rounding in between; q stays 16 bit.  seqlens_new: as in fa_kvcache_append."""
-    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_new.dim() != 4 or k_new.shape[0] != k_cache.shape[0]:
-        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_cache, v_cache [B,Hkv,Ncap,d]")
-    import torch
-    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
-        raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_cache.dtype}, {v_cache.dtype})")
-    ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
-        k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, True, "k_cache, v_cache",
-        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
-    _append_call("fa_kvcache_append_fp8", (k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out),
-                 (*src, *dst, len_ptr, out_ptr, ks_ptr, vs_ptr), (B, Hkv, Nnew, k_cache.shape[2]), d, dt, rot, stream, seqlens_new)
+    _append(k_new, v_new, k_cache, v_cache, "k_cache, v_cache", cache_seqlens, seqlens_out, stream,
+            (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), seqlens_new, scales=(k_scale, v_scale))
 
 
 def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale=None, v_scale=None, cache_seqlens=None,
@@ -811,19 +768,8 @@ def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_sca
     """fa_kvcache_append_paged into fp8 pools (fa_kvcache_append_paged_fp8): k_pool/v_pool [num_pages,Hkv,page_size,d]
     torch.float8_e4m3fn, block_table as in fa_kvcache_append_paged, scales and codes as in fa_kvcache_append_fp8; the rotary keywords
     as there (fa_kvcache_append_paged_fp8_rope); seqlens_new as in fa_kvcache_append."""
-    if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or k_new.dim() != 4:
-        raise ValueError("k_new, v_new must be [B,Hkv,Nnew,d] and k_pool, v_pool [num_pages,Hkv,page_size,d]")
-    import torch
-    if k_pool.dtype != torch.float8_e4m3fn or v_pool.dtype != torch.float8_e4m3fn:   # judged first, as in the decode front end
-        raise ValueError(f"k_pool, v_pool: {_FP8_CACHE} (got {k_pool.dtype}, {v_pool.dtype})")
-    tbl_ptr = _table_ptr(block_table, k_new.shape[0])
-    ks_ptr, vs_ptr = _scale_ptrs(k_scale, v_scale, k_new.shape[1])
-    B, Hkv, Nnew, d, dt, src, dst, len_ptr, out_ptr, rot = _append_args(
-        k_new, v_new, k_pool, v_pool, cache_seqlens, seqlens_out, True, "k_pool, v_pool",
-        (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
-    _append_call("fa_kvcache_append_paged_fp8", (k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out),
-                 (*src, *dst, len_ptr, out_ptr, tbl_ptr, ks_ptr, vs_ptr),
-                 (B, Hkv, Nnew, k_pool.shape[0], k_pool.shape[2], block_table.shape[1]), d, dt, rot, stream, seqlens_new)
+    _append(k_new, v_new, k_pool, v_pool, "k_pool, v_pool", cache_seqlens, seqlens_out, stream,
+            (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), seqlens_new, paged=True, block_table=block_table, scales=(k_scale, v_scale))
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

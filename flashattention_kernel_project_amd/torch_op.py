@@ -7,52 +7,26 @@ eager fallback.  Registered on first use:
     from flashattention_kernel_project_amd.torch_op import register
     register()
     o = torch.ops.fa_mi355.forward(q, k, v, scale, causal, out_fp32)
-    o = torch.ops.fa_mi355.decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache
-    o = torch.ops.fa_mi355.decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_paged
-    o = torch.ops.fa_mi355.decode_fp8(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)   # ops.fa_forward_kvcache_fp8
-    o = torch.ops.fa_mi355.decode_paged_fp8(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32)
-    # the same four with a sliding window: `window` (an int >= 0, 0 = none) follows `causal`, as in the C entries
-    o = torch.ops.fa_mi355.decode_window(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32)
-    o = torch.ops.fa_mi355.decode_paged_window(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32)
-    o = torch.ops.fa_mi355.decode_fp8_window(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32)
-    o = torch.ops.fa_mi355.decode_paged_fp8_window(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal,
-                                                   window, out_fp32)
-    # ... and with attention sinks and soft-capped logits: (window, sinks, softcap) follow `causal`; sinks is a float32 [Hq] tensor or None
-    o = torch.ops.fa_mi355.decode_ex(q, k_cache, v_cache, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32)
-    o = torch.ops.fa_mi355.decode_paged_ex(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32)
-    o = torch.ops.fa_mi355.decode_fp8_ex(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap,
-                                         out_fp32)
+    # KV-cache decode: torch.ops.fa_mi355.decode + layout + form, 16 ops.  The layout names the ops function and the leading arguments:
+    #   ""           (q, k_cache, v_cache, ...                                   ops.fa_forward_kvcache
+    #   "_paged"     (q, k_pool, v_pool, block_table, ...                        ops.fa_forward_kvcache_paged
+    #   "_fp8"       (q, k_cache8, v_cache8, k_scale, v_scale, ...               ops.fa_forward_kvcache_fp8
+    #   "_paged_fp8" (q, k_pool8, v_pool8, block_table, k_scale, v_scale, ...    ops.fa_forward_kvcache_paged_fp8
+    # and the form the rest (window: an int >= 0, 0 = none; sinks: a float32 [Hq] tensor or None; seqlens_q: ops' keyword):
+    #   ""        ... cache_seqlens, scale, causal, out_fp32)
+    #   "_window" ... cache_seqlens, scale, causal, window, out_fp32)
+    #   "_ex"     ... cache_seqlens, scale, causal, window, sinks, softcap, out_fp32)
+    #   "_ragged" ... cache_seqlens, seqlens_q, scale, causal, window, sinks, softcap, out_fp32)
     o = torch.ops.fa_mi355.decode_paged_fp8_ex(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window,
                                                sinks, softcap, out_fp32)
-    torch.ops.fa_mi355.append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out)   # ops.fa_kvcache_append; returns nothing
-    torch.ops.fa_mi355.append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out)
-    torch.ops.fa_mi355.append_fp8(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out)
-    torch.ops.fa_mi355.append_paged_fp8(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out)
-    # the same four with rotary embedding: (q, rotary_cos, rotary_sin, interleaved) follow the base op's list; q (or None) is rotated in place
-    torch.ops.fa_mi355.append_rope(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin, interleaved)
+    # KV-cache append: torch.ops.fa_mi355.append + layout + form, 12 ops that return nothing.  The layouts are the decode ops' with
+    # (k_new, v_new, cache or pool, ... in the place of (q, cache or pool, ... (ops.fa_kvcache_append and its _paged, _fp8, _paged_fp8
+    # forms); q (or None) is rotated in place; in "_ragged" the three rotary arguments may be None:
+    #   ""        ... cache_seqlens, seqlens_out)
+    #   "_rope"   ... cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin, interleaved)
+    #   "_ragged" ... cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin, interleaved)
     torch.ops.fa_mi355.append_paged_rope(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
                                          interleaved)
-    torch.ops.fa_mi355.append_fp8_rope(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos,
-                                       rotary_sin, interleaved)
-    torch.ops.fa_mi355.append_paged_fp8_rope(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
-                                             q, rotary_cos, rotary_sin, interleaved)
-    # a count per sequence (ops' seqlens_q / seqlens_new): the _ex schema with `Tensor? seqlens_q` after cache_seqlens, and the _rope schema
-    # with q, rotary_cos, rotary_sin optional and `Tensor? seqlens_new` after seqlens_out
-    o = torch.ops.fa_mi355.decode_ragged(q, k_cache, v_cache, cache_seqlens, seqlens_q, scale, causal, window, sinks, softcap, out_fp32)
-    o = torch.ops.fa_mi355.decode_paged_ragged(q, k_pool, v_pool, block_table, cache_seqlens, seqlens_q, scale, causal, window, sinks,
-                                               softcap, out_fp32)
-    o = torch.ops.fa_mi355.decode_fp8_ragged(q, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_q, scale, causal, window,
-                                             sinks, softcap, out_fp32)
-    o = torch.ops.fa_mi355.decode_paged_fp8_ragged(q, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_q, scale,
-                                                   causal, window, sinks, softcap, out_fp32)
-    torch.ops.fa_mi355.append_ragged(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin,
-                                     interleaved)
-    torch.ops.fa_mi355.append_paged_ragged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, seqlens_new, q,
-                                           rotary_cos, rotary_sin, interleaved)
-    torch.ops.fa_mi355.append_fp8_ragged(k_new, v_new, k_cache8, v_cache8, k_scale, v_scale, cache_seqlens, seqlens_out, seqlens_new, q,
-                                         rotary_cos, rotary_sin, interleaved)
-    torch.ops.fa_mi355.append_paged_fp8_ragged(k_new, v_new, k_pool8, v_pool8, block_table, k_scale, v_scale, cache_seqlens, seqlens_out,
-                                               seqlens_new, q, rotary_cos, rotary_sin, interleaved)
     # the merge of R attention states, stacked [R,B,Hq,Nq,d] and [R,B,Hq,Nq] (ops.fa_merge_states), and shared-prefix decode on a
     # contiguous 16-bit suffix (ops.fa_forward_kvcache_shared_prefix)
     o, lse = torch.ops.fa_mi355.merge_states(outs, lses, out_f32)
@@ -69,9 +43,8 @@ _registered = False
 
 
 def register() -> None:
-    """Define torch.ops.fa_mi355.forward, .decode, .decode_paged, .decode_fp8, .decode_paged_fp8, their four _window and four _ex forms, the
-    four .append ops and their four _rope forms, the four decode and four append _ragged forms, .merge_states,
-    .decode_shared_prefix and .forward_varlen (idempotent)."""
+    """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
+    .merge_states, .decode_shared_prefix and .forward_varlen (idempotent)."""
     global _registered
     if _registered:
         return
@@ -100,271 +73,69 @@ def register() -> None:
     def _(q, k, v, scale, causal, out_fp32):
         return q.new_empty(q.shape, dtype=out_dtype(q, out_fp32))
 
-    @torch.library.custom_op("fa_mi355::decode", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
-                                    "bool out_fp32) -> Tensor")
-    def decode(q, k_cache, v_cache, cache_seqlens, scale, causal, out_fp32):
-        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
-                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q))
+    # The 16 decode and 12 append ops are made from two tables each: the layout gives the leading part of the schema, the ops function
+    # and how each leading argument is passed on; the form gives the schema's tail and the keywords made of the arguments behind the
+    # leading ones.  The op is <family> + layout + form.
+    PASS = {"c": lambda t: t.contiguous(), "o": opt, "-": lambda t: t}
 
-    @torch.library.custom_op("fa_mi355::decode_paged", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
-                                    "bool causal, bool out_fp32) -> Tensor")
-    def decode_paged(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, out_fp32):
-        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                            stream=stream(q))
+    def define(name, schema, mutates, fn, how, kw, fake):
+        def body(*args):   # kw gets the first argument (q, k_new) for the stream and the output type
+            return fn(*(PASS[h](t) for h, t in zip(how, args)), **kw(args[0], *args[len(how):]))
+        torch.library.custom_op("fa_mi355::" + name, mutates_args=mutates, device_types="cuda", schema=schema)(body).register_fake(fake)
 
-    @torch.library.custom_op("fa_mi355::decode_fp8", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
-    def decode_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                          stream=stream(q))
-
-    @torch.library.custom_op("fa_mi355::decode_paged_fp8", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor")
-    def decode_paged_fp8(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, out_fp32):
-        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
-                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q))
-
-    # The sliding-window forms: the schema of the op above each with `int window` after `causal`; the existing ops keep theirs.
-    @torch.library.custom_op("fa_mi355::decode_window", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
-                                    "int window, bool out_fp32) -> Tensor")
-    def decode_window(q, k_cache, v_cache, cache_seqlens, scale, causal, window, out_fp32):
-        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
-                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window)
-
-    @torch.library.custom_op("fa_mi355::decode_paged_window", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
-                                    "bool causal, int window, bool out_fp32) -> Tensor")
-    def decode_paged_window(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, out_fp32):
-        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                            stream=stream(q), window=window)
-
-    @torch.library.custom_op("fa_mi355::decode_fp8_window", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
-    def decode_fp8_window(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                          stream=stream(q), window=window)
-
-    @torch.library.custom_op("fa_mi355::decode_paged_fp8_window", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor")
-    def decode_paged_fp8_window(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, out_fp32):
-        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
-                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window)
-
-    # The forms with attention sinks and a soft-cap: the schema of the windowed op above each with `Tensor? sinks, float softcap`
-    # after `window`.
-    @torch.library.custom_op("fa_mi355::decode_ex", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? cache_seqlens, float scale, bool causal, "
-                                    "int window, Tensor? sinks, float softcap, bool out_fp32) -> Tensor")
-    def decode_ex(q, k_cache, v_cache, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
-        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(cache_seqlens), causal=causal,
-                                      scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window,
-                                      sinks=opt(sinks), softcap=softcap)
-
-    @torch.library.custom_op("fa_mi355::decode_paged_ex", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? cache_seqlens, float scale, "
-                                    "bool causal, int window, Tensor? sinks, float softcap, bool out_fp32) -> Tensor")
-    def decode_paged_ex(q, k_pool, v_pool, block_table, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
-        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                            stream=stream(q), window=window, sinks=opt(sinks), softcap=softcap)
-
-    @torch.library.custom_op("fa_mi355::decode_fp8_ex", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, int window, Tensor? sinks, float softcap, "
-                                    "bool out_fp32) -> Tensor")
-    def decode_fp8_ex(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap, out_fp32):
-        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32),
-                                          stream=stream(q), window=window, sinks=opt(sinks), softcap=softcap)
-
-    @torch.library.custom_op("fa_mi355::decode_paged_fp8_ex", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
-                                    "Tensor? cache_seqlens, float scale, bool causal, int window, Tensor? sinks, float softcap, "
-                                    "bool out_fp32) -> Tensor")
-    def decode_paged_fp8_ex(q, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, scale, causal, window, sinks, softcap,
-                            out_fp32):
-        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                                opt(k_scale), opt(v_scale), opt(cache_seqlens), causal=causal, scale=scale,
-                                                out_dtype=out_dtype(q, out_fp32), stream=stream(q), window=window,
-                                                sinks=opt(sinks), softcap=softcap)
-
-    # The forms with a query count per sequence: the schema of the _ex op above each with `Tensor? seqlens_q` after `cache_seqlens`.
-    RAGGED = "Tensor? cache_seqlens, Tensor? seqlens_q, float scale, bool causal, int window, Tensor? sinks, float softcap, " \
-             "bool out_fp32) -> Tensor"
-
+    # `int window` follows `causal`, `Tensor? sinks, float softcap` follow it, `Tensor? seqlens_q` follows `cache_seqlens`
     def ragged_kw(q, cache_seqlens, seqlens_q, scale, causal, window, sinks, softcap, out_fp32):
         return dict(cache_seqlens=opt(cache_seqlens), causal=causal, scale=scale, out_dtype=out_dtype(q, out_fp32), stream=stream(q),
                     window=window, sinks=opt(sinks), softcap=softcap, seqlens_q=opt(seqlens_q))
 
-    @torch.library.custom_op("fa_mi355::decode_ragged", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, " + RAGGED)
-    def decode_ragged(q, k_cache, v_cache, *rest):
-        return ops.fa_forward_kvcache(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), **ragged_kw(q, *rest))
-
-    @torch.library.custom_op("fa_mi355::decode_paged_ragged", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, " + RAGGED)
-    def decode_paged_ragged(q, k_pool, v_pool, block_table, *rest):
-        return ops.fa_forward_kvcache_paged(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                            **ragged_kw(q, *rest))
-
-    @torch.library.custom_op("fa_mi355::decode_fp8_ragged", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, " + RAGGED)
-    def decode_fp8_ragged(q, k_cache, v_cache, k_scale, v_scale, *rest):
-        return ops.fa_forward_kvcache_fp8(q.contiguous(), k_cache.contiguous(), v_cache.contiguous(), opt(k_scale), opt(v_scale),
-                                          **ragged_kw(q, *rest))
-
-    @torch.library.custom_op("fa_mi355::decode_paged_fp8_ragged", mutates_args=(), device_types="cuda",
-                             schema="(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, "
-                                    + RAGGED)
-    def decode_paged_fp8_ragged(q, k_pool, v_pool, block_table, k_scale, v_scale, *rest):
-        return ops.fa_forward_kvcache_paged_fp8(q.contiguous(), k_pool.contiguous(), v_pool.contiguous(), block_table.contiguous(),
-                                                opt(k_scale), opt(v_scale), **ragged_kw(q, *rest))
-
-    for op in (decode, decode_paged, decode_fp8, decode_paged_fp8, decode_window, decode_paged_window, decode_fp8_window,
-               decode_paged_fp8_window, decode_ex, decode_paged_ex, decode_fp8_ex, decode_paged_fp8_ex, decode_ragged,
-               decode_paged_ragged, decode_fp8_ragged, decode_paged_fp8_ragged):
-        op.register_fake(decode_fake)
+    DECODE_LAYOUTS = (
+        ("", "(Tensor q, Tensor k_cache, Tensor v_cache, ", ops.fa_forward_kvcache, "ccc"),
+        ("_paged", "(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, ", ops.fa_forward_kvcache_paged, "cccc"),
+        ("_fp8", "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? k_scale, Tensor? v_scale, ", ops.fa_forward_kvcache_fp8, "cccoo"),
+        ("_paged_fp8", "(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor? k_scale, Tensor? v_scale, ",
+         ops.fa_forward_kvcache_paged_fp8, "ccccoo"))
+    DECODE_FORMS = (
+        ("", "Tensor? cache_seqlens, float scale, bool causal, bool out_fp32) -> Tensor",
+         lambda q, lens, scale, causal, out_fp32: ragged_kw(q, lens, None, scale, causal, 0, None, 0.0, out_fp32)),
+        ("_window", "Tensor? cache_seqlens, float scale, bool causal, int window, bool out_fp32) -> Tensor",
+         lambda q, lens, scale, causal, window, out_fp32: ragged_kw(q, lens, None, scale, causal, window, None, 0.0, out_fp32)),
+        ("_ex", "Tensor? cache_seqlens, float scale, bool causal, int window, Tensor? sinks, float softcap, bool out_fp32) -> Tensor",
+         lambda q, lens, *rest: ragged_kw(q, lens, None, *rest)),
+        ("_ragged", "Tensor? cache_seqlens, Tensor? seqlens_q, float scale, bool causal, int window, Tensor? sinks, float softcap, "
+                    "bool out_fp32) -> Tensor", ragged_kw))
+    for layout, lead, fn, how in DECODE_LAYOUTS:
+        for form, tail, kw in DECODE_FORMS:
+            define("decode" + layout + form, lead + tail, (), fn, how, kw, decode_fake)
 
     # The appends mutate the caches (and seqlens_out) and return nothing.  The caches are passed as they are: a copy made by
-    # .contiguous() would take the writes, so a cache that is not contiguous is refused by the front end.
-    @torch.library.custom_op("fa_mi355::append", mutates_args=("k_cache", "v_cache", "seqlens_out"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cache_seqlens, "
-                                    "Tensor(c!)? seqlens_out) -> ()")
-    def append(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
-        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out,
-                              stream=stream(k_new))
-
-    @append.register_fake
-    def _(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out):
-        return None
-
-    @torch.library.custom_op("fa_mi355::append_paged", mutates_args=("k_pool", "v_pool", "seqlens_out"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    "Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
-    def append_paged(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
-        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                    opt(cache_seqlens), seqlens_out, stream=stream(k_new))
-
-    @append_paged.register_fake
-    def _(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out):
-        return None
-
-    @torch.library.custom_op("fa_mi355::append_fp8", mutates_args=("k_cache", "v_cache", "seqlens_out"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
-                                    "Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
-    def append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
-        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
-                                  opt(cache_seqlens), seqlens_out, stream=stream(k_new))
-
-    @append_fp8.register_fake
-    def _(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out):
-        return None
-
-    @torch.library.custom_op("fa_mi355::append_paged_fp8", mutates_args=("k_pool", "v_pool", "seqlens_out"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    "Tensor? k_scale, Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()")
-    def append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
-        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream(k_new))
-
-    @append_paged_fp8.register_fake
-    def _(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out):
-        return None
-
-    # The rotary forms: the schema of the op above each plus (q, rotary_cos, rotary_sin, interleaved).  q is rotated in place, so it is
-    # passed as it is, like the caches, and is among the mutated arguments.
-    ROPE = "Tensor(d!)? q, Tensor rotary_cos, Tensor rotary_sin, bool interleaved) -> ()"
-
-    def rope_kw(q, rotary_cos, rotary_sin, interleaved):
-        return dict(q=q, rotary_cos=rotary_cos.contiguous(), rotary_sin=rotary_sin.contiguous(), rotary_interleaved=interleaved)
-
-    @torch.library.custom_op("fa_mi355::append_rope", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cache_seqlens, "
-                                    "Tensor(c!)? seqlens_out, " + ROPE)
-    def append_rope(k_new, v_new, k_cache, v_cache, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin, interleaved):
-        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(cache_seqlens), seqlens_out,
-                              stream=stream(k_new), **rope_kw(q, rotary_cos, rotary_sin, interleaved))
-
-    @torch.library.custom_op("fa_mi355::append_paged_rope", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
-    def append_paged_rope(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
-                          interleaved):
-        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                    opt(cache_seqlens), seqlens_out, stream=stream(k_new),
-                                    **rope_kw(q, rotary_cos, rotary_sin, interleaved))
-
-    @torch.library.custom_op("fa_mi355::append_fp8_rope", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
-                                    "Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
-    def append_fp8_rope(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
-                        interleaved):
-        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
-                                  opt(cache_seqlens), seqlens_out, stream=stream(k_new),
-                                  **rope_kw(q, rotary_cos, rotary_sin, interleaved))
-
-    @torch.library.custom_op("fa_mi355::append_paged_fp8_rope", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"),
-                             device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    "Tensor? k_scale, Tensor? v_scale, Tensor? cache_seqlens, Tensor(c!)? seqlens_out, " + ROPE)
-    def append_paged_fp8_rope(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, cache_seqlens, seqlens_out, q, rotary_cos,
-                              rotary_sin, interleaved):
-        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                        opt(k_scale), opt(v_scale), opt(cache_seqlens), seqlens_out, stream=stream(k_new),
-                                        **rope_kw(q, rotary_cos, rotary_sin, interleaved))
-
-    # The forms with a token count per sequence: the schema of the _rope op above each with `Tensor? seqlens_new` after `seqlens_out` and
-    # the rotary arguments optional (all three None: no rotation).
-    RAGGED_APPEND = "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, Tensor? seqlens_new, Tensor(d!)? q, Tensor? rotary_cos, " \
-                    "Tensor? rotary_sin, bool interleaved) -> ()"
-
+    # .contiguous() would take the writes, so a cache that is not contiguous is refused by the front end.  So is q, which the rotary
+    # forms rotate in place: it is among their mutated arguments.  In the _ragged form the rotary arguments are optional (all three
+    # None: no rotation).
     def ragged_append_kw(k_new, cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin, interleaved):
         return dict(cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, stream=stream(k_new), q=q, rotary_cos=opt(rotary_cos),
                     rotary_sin=opt(rotary_sin), rotary_interleaved=interleaved, seqlens_new=opt(seqlens_new))
 
-    @torch.library.custom_op("fa_mi355::append_ragged", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, " + RAGGED_APPEND)
-    def append_ragged(k_new, v_new, k_cache, v_cache, *rest):
-        ops.fa_kvcache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, **ragged_append_kw(k_new, *rest))
-
-    @torch.library.custom_op("fa_mi355::append_paged_ragged", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    + RAGGED_APPEND)
-    def append_paged_ragged(k_new, v_new, k_pool, v_pool, block_table, *rest):
-        ops.fa_kvcache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                    **ragged_append_kw(k_new, *rest))
-
-    @torch.library.custom_op("fa_mi355::append_fp8_ragged", mutates_args=("k_cache", "v_cache", "seqlens_out", "q"), device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, "
-                                    "Tensor? v_scale, " + RAGGED_APPEND)
-    def append_fp8_ragged(k_new, v_new, k_cache, v_cache, k_scale, v_scale, *rest):
-        ops.fa_kvcache_append_fp8(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache, opt(k_scale), opt(v_scale),
-                                  **ragged_append_kw(k_new, *rest))
-
-    @torch.library.custom_op("fa_mi355::append_paged_fp8_ragged", mutates_args=("k_pool", "v_pool", "seqlens_out", "q"),
-                             device_types="cuda",
-                             schema="(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
-                                    "Tensor? k_scale, Tensor? v_scale, " + RAGGED_APPEND)
-    def append_paged_fp8_ragged(k_new, v_new, k_pool, v_pool, block_table, k_scale, v_scale, *rest):
-        ops.fa_kvcache_append_paged_fp8(k_new.contiguous(), v_new.contiguous(), k_pool, v_pool, block_table.contiguous(),
-                                        opt(k_scale), opt(v_scale), **ragged_append_kw(k_new, *rest))
-
-    for op in (append_rope, append_paged_rope, append_fp8_rope, append_paged_fp8_rope, append_ragged, append_paged_ragged,
-               append_fp8_ragged, append_paged_fp8_ragged):
-        op.register_fake(lambda *args: None)
+    APPEND_LAYOUTS = (
+        ("", "(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, ", ("k_cache", "v_cache"), ops.fa_kvcache_append, "cc--"),
+        ("_paged", "(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, ", ("k_pool", "v_pool"),
+         ops.fa_kvcache_append_paged, "cc--c"),
+        ("_fp8", "(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_scale, Tensor? v_scale, ",
+         ("k_cache", "v_cache"), ops.fa_kvcache_append_fp8, "cc--oo"),
+        ("_paged_fp8", "(Tensor k_new, Tensor v_new, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, Tensor? k_scale, "
+                       "Tensor? v_scale, ", ("k_pool", "v_pool"), ops.fa_kvcache_append_paged_fp8, "cc--coo"))
+    APPEND_FORMS = (
+        ("", "Tensor? cache_seqlens, Tensor(c!)? seqlens_out) -> ()", ("seqlens_out",),
+         lambda k_new, lens, out: dict(cache_seqlens=opt(lens), seqlens_out=out, stream=stream(k_new))),
+        ("_rope", "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, Tensor(d!)? q, Tensor rotary_cos, Tensor rotary_sin, "
+                  "bool interleaved) -> ()", ("seqlens_out", "q"),
+         lambda k_new, lens, out, q, rotary_cos, rotary_sin, interleaved: dict(
+             cache_seqlens=opt(lens), seqlens_out=out, stream=stream(k_new), q=q, rotary_cos=rotary_cos.contiguous(),
+             rotary_sin=rotary_sin.contiguous(), rotary_interleaved=interleaved)),
+        ("_ragged", "Tensor? cache_seqlens, Tensor(c!)? seqlens_out, Tensor? seqlens_new, Tensor(d!)? q, Tensor? rotary_cos, "
+                    "Tensor? rotary_sin, bool interleaved) -> ()", ("seqlens_out", "q"), ragged_append_kw))
+    for layout, lead, caches, fn, how in APPEND_LAYOUTS:
+        for form, tail, more, kw in APPEND_FORMS:
+            define("append" + layout + form, lead + tail, caches + more, fn, how, kw, lambda *args: None)
 
     # The merge of attention states over key ranges (ops.fa_merge_states) on stacked parts, and shared-prefix decode on a contiguous
     # 16-bit suffix (ops.fa_forward_kvcache_shared_prefix; the paged and fp8 forms are the front end's).

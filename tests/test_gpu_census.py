@@ -293,7 +293,7 @@ K_SCALE, V_SCALES = 3.0, (None, 0.5)   # fp8: any k_scale leaves a zero score ze
 def _cache_run(fa, torch, dq, kc, vc, lens, W, causal, fmt, ps=0, seed=0, v_scale=None):
     """kc, vc [B, Hkv, Ncap, d] poisoned for (lens, W): uint16 encodings (16-bit entries) or uint8 codes (fp8 entries, with
     k_scale = K_SCALE and the given v_scale).  ps = 0: the contiguous entry, else the paged one on cm.scatter's pool (W = 0: no
-    start, no dead pages).  W = 0 goes to the base entries, W > 0 to the windowed ones.  -> O, lse"""
+    start, no dead pages).  W = 0 is the base entries' call, W > 0 the windowed ones', both through fa_kvcache_decode.  -> O, lse"""
     B, Hq, Nq, d = dq.shape
     Hkv, Ncap = kc.shape[1], kc.shape[2]
     G = Hq // Hkv

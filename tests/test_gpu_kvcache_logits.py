@@ -17,6 +17,7 @@ import pytest
 
 import common_inputs as cm
 import decode_inputs as di
+import flat_entries as flat
 import fp8_inputs as f8
 import logit_inputs as li
 import window_inputs as wi
@@ -200,7 +201,7 @@ def test_fp8(fa, oracle, torch_cuda, fmt, d, name, W, causal, variant):
 
 # ---- 3. bit ties ------------------------------------------------------------------------------------------------------------------------
 def _raw(fa, torch, dq, dk, dv, dl, W, causal, fmt, need, table=None, scales=None, sinks=None, softcap=0.0):
-    """fa_kvcache_decode called through the C ABI as it is (the Python front end routes sinks=None, softcap=0 to the flat entries)"""
+    """fa_kvcache_decode called through the C ABI as it is: the descriptor filled here, not by the Python front end"""
     B, Hq, Nq, d = dq.shape
     Hkv = dk.shape[1]
     o = torch.full(dq.shape, float("nan"), dtype=torch.float32, device="cuda")
@@ -225,7 +226,8 @@ def _raw(fa, torch, dq, dk, dv, dl, W, causal, fmt, need, table=None, scales=Non
 @pytest.mark.parametrize("fmt,d", FMT_D)
 def test_descriptor_without_options_is_each_of_the_eight_entries(fa, oracle, torch_cuda, fmt, d):
     """sinks = NULL, softcap = 0 through fa_kvcache_decode: O and lse of fa_forward_kvcache and its _paged, _fp8, _paged_fp8 forms,
-    without a window (S = 4) and under one (S = 1), on the rows case under the causal mask"""
+    without a window (S = 4) and under one (S = 1, their _window forms), on the rows case under the causal mask.  The eight flat
+    entries are called through the C ABI (tests/flat_entries.py): the Python front end goes through the descriptor entry alone."""
     torch = torch_cuda
     name = "rows"
     for W in li.case_windows(name):
@@ -233,7 +235,6 @@ def test_descriptor_without_options_is_each_of_the_eight_entries(fa, oracle, tor
         B, Hkv, G, Nq, Ncap = _shape(c)
         need = fa.kvcache_window_workspace_bytes(B, Hkv, G, Nq, Ncap, d, W)
         dl = _ints(torch, c["lens"])
-        kw = dict(cache_seqlens=dl, causal=True, return_lse=True, window=W)
         k8, v8 = (torch.from_numpy(np.array(x).view(np.int16)).view(_tdtype(torch, fmt)).float().clamp(-400, 400).nan_to_num(0.0)
                   .to(torch.float8_e4m3fn).view(torch.uint8).numpy() for x in (kc, vc))
         k8, v8 = cm.poisoned(k8, c["lens"], Nq, W, nan=wi.NAN8), cm.poisoned(v8, c["lens"], Nq, W, nan=wi.NAN8)
@@ -247,10 +248,8 @@ def test_descriptor_without_options_is_each_of_the_eight_entries(fa, oracle, tor
                     kk, vv, table = cm.scatter(kk, vv, c["lens"], 16, 77, Nq, W, nan=wi.NAN8 if fp8 else cm.NAN16)
                     table = torch.from_numpy(table).cuda()
                 dk, dv = dev(kk), dev(vv)
-                fn = getattr(fa, "fa_forward_kvcache" + "_paged" * paged + "_fp8" * fp8)
-                args = (dq, dk, dv) + ((table,) if paged else ()) + (sc if fp8 else ())
-                base, base_lse = fn(*args, workspace=_nan_workspace(torch, need), **kw)
-                torch.cuda.synchronize()
+                base, base_lse = flat.decode(fa, torch, dq, dk, dv, dl, True, fmt, _nan_workspace(torch, need), table=table,
+                                             scales=sc if fp8 else None, window=W or None)
                 assert torch.isfinite(base).all() and not torch.isnan(base_lse).any()
                 o, lse = _raw(fa, torch, dq, dk, dv, dl, W, True, fmt, need, table=table, scales=sc if fp8 else None)
                 assert torch.equal(o, base) and torch.equal(lse, base_lse), f"W={W} paged={paged} fp8={fp8}"

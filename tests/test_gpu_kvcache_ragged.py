@@ -15,6 +15,7 @@ import append_inputs as ai
 import census_inputs as ci
 import common_inputs as cm
 import decode_inputs as di
+import flat_entries as fe
 import fp8_inputs as f8
 import logit_inputs as li
 import ragged_inputs as ri
@@ -49,7 +50,8 @@ def _nan_workspace(torch, need):
 def _run(fa, torch, f, d, fmt, qb, kb, vb, nq, W, causal, ps=0, seed=0, sinks=None, softcap=0.0, fp8=False, k_scale=None, v_scale=None,
          check_S=True):
     """One decode launch of a family: qb [B*Hq, Nq, d] encodings; kb, vb [B*Hkv, Ncap, d] encodings (fp8: codes), poisoned here at and
-    past L_b; ps = 0 the contiguous entry, else the paged one on the scattered cache; nq a list or None (the keyword absent).
+    past L_b; ps = 0 the contiguous entry, else the paged one on the scattered cache; nq a list, or None: the call without counts, which is
+    the flat entry fa_forward_kvcache[_window] through the C ABI (tests/flat_entries.py).
     -> O, lse (device tensors)"""
     B, Hkv, G, Nq, Ncap = ri.shape(f)
     lens = f["lens"]
@@ -66,7 +68,11 @@ def _run(fa, torch, f, d, fmt, qb, kb, vb, nq, W, causal, ps=0, seed=0, sinks=No
         kw.update(k_scale=_floats(torch, k_scale), v_scale=_floats(torch, v_scale))
     nan = f8.NAN_CODES[0] if fp8 else cm.NAN16
     kc, vc = (x.reshape(B, Hkv, Ncap, d) for x in (kb, vb))
-    if ps == 0:
+    if nq is None:
+        assert ps == 0 and not fp8 and sinks is None and softcap == 0.0
+        o, lse = fe.decode(fa, torch, dq, dev(cm.poisoned(kc, lens, nan=nan)), dev(cm.poisoned(vc, lens, nan=nan)), kw["cache_seqlens"],
+                           causal, fmt, kw["workspace"], window=W or None)
+    elif ps == 0:
         o, lse = (fa.fa_forward_kvcache_fp8 if fp8 else fa.fa_forward_kvcache)(dq, dev(cm.poisoned(kc, lens, nan=nan)),
                                                                                dev(cm.poisoned(vc, lens, nan=nan)), **kw)
     else:
@@ -289,8 +295,9 @@ def test_append_bytes(fa, oracle, torch_cuda, fmt, d, paged, fp8, rope):
     fn = getattr(fa, "fa_kvcache_append" + ("_paged" if paged else "") + ("_fp8" if fp8 else ""))
 
     def launch(new_counts, flat=False, table=table, disjoint=False, by_desc=False):
-        """-> K, V, lengths, Qout, Q after one append.  flat: no seqlens_new (the flat entry); by_desc: the same through
-        fa_kvcache_append_ex with seqlens_new = NULL; disjoint: Q goes to a NaN-filled q_out of its own instead of in place"""
+        """-> K, V, lengths, Qout, Q after one append.  flat: no seqlens_new, the flat entry of the form through the C ABI
+        (tests/flat_entries.py); by_desc: the same through fa_kvcache_append_ex with seqlens_new = NULL; neither: the Python front
+        end with seqlens_new = new_counts; disjoint: Q goes to a NaN-filled q_out of its own instead of in place"""
         dev = (lambda x: cm.dev8(torch, x)) if fp8 else (lambda x: cm.dev16(torch, x, fmt))
         dk, dv, dl = dev(kc0), dev(vc0), _ints(torch, lens)
         dkn, dvn = cm.dev16(torch, knb, fmt), cm.dev16(torch, vnb, fmt)
@@ -308,17 +315,18 @@ def test_append_bytes(fa, oracle, torch_cuda, fmt, d, paged, fp8, rope):
                 max_pages=Ncap // ps if paged else 0, G=G if rope else 0, rot_dim=d // 2 if rope else 0, max_pos=cos.shape[0] if rope else 0,
                 interleaved=int(il), dtype=fmt, stream=torch.cuda.current_stream().cuda_stream)
             assert fa.lib().fa_kvcache_append_ex(ctypes.byref(desc)) == 0
+        elif flat:
+            fe.append(fa, torch, dkn, dvn, dk, dv, dl, dl, fmt, table=dt, scales=(dks, dvs) if fp8 else None,
+                      rope=(dq, dqo, dcos, dsin, il) if rope else None)
         else:
             args = [dkn, dvn, dk, dv] + ([dt] if paged else [])
-            kw = dict(cache_seqlens=dl, seqlens_out=dl)
+            kw = dict(cache_seqlens=dl, seqlens_out=dl, seqlens_new=_ints(torch, new_counts))
             if fp8:
                 kw.update(k_scale=dks, v_scale=dvs)
             if rope:
                 kw.update(q=dq, rotary_cos=dcos, rotary_sin=dsin, rotary_interleaved=il)
                 if disjoint:
                     kw.update(q_out=dqo)
-            if not flat:
-                kw["seqlens_new"] = _ints(torch, new_counts)
             fn(*args, **kw)
         torch.cuda.synchronize()
         u = torch.uint8 if fp8 else torch.int16

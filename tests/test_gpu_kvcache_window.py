@@ -10,7 +10,6 @@ Poison: the workspace is filled with NaN bytes; every cache row at or past L_b A
 holds NaN bit patterns; every pool page no table names holds NaN; every table entry past the last live page or wholly below start_b
 holds garbage.  An over-read shows as a non-finite result, not as a fault.
 """
-import ctypes
 import functools
 
 import numpy as np
@@ -18,6 +17,7 @@ import pytest
 
 import common_inputs as cm
 import decode_inputs as di
+import flat_entries as flat
 import fp8_inputs as f8
 import window_inputs as wi
 
@@ -164,20 +164,9 @@ def test_fp8_window(fa, oracle, torch_cuda, fmt, d, name, W, causal):
 
 # ---- 6. exact ties to the existing entries ------------------------------------------------------------------------------------------
 def _raw_window(fa, torch, dq, dk, dv, dl, W, causal, fmt, need):
-    """fa_forward_kvcache_window called through the C ABI as it is (the Python front end routes window = 0 to the base entry)"""
-    B, Hq, Nq, d = dq.shape
-    Hkv, Ncap = dk.shape[1], dk.shape[2]
-    o = torch.full(dq.shape, float("nan"), dtype=torch.float32, device="cuda")
-    lse = torch.full(dq.shape[:3], float("nan"), dtype=torch.float32, device="cuda")
-    ws = _nan_workspace(torch, need)
-    torch.cuda.synchronize()
-    code = fa.lib().fa_forward_kvcache_window(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), o.data_ptr(), lse.data_ptr(), dl.data_ptr(),
-                                              B, Hkv, Hq // Hkv, Nq, Ncap, d, 1.0 / np.sqrt(d), 1 if causal else 0, W, fmt,
-                                              fa.capi.OUT_F32, ws.data_ptr(), ws.numel(),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert code == 0
-    torch.cuda.synchronize()
-    return o, lse
+    """fa_forward_kvcache_window called through the C ABI as it is, window = 0 included (the Python front end goes through
+    fa_kvcache_decode)"""
+    return flat.decode(fa, torch, dq, dk, dv, dl, causal, fmt, _nan_workspace(torch, need), window=W)
 
 
 @pytest.mark.parametrize("name", ["split", "rows"])

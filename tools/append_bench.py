@@ -198,7 +198,8 @@ def rope_main(args):
         paged, fp8 = "paged" in layout, "fp8" in layout
         cdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
         shape = (B * max_pages, H, ps, d) if paged else (B, H, Ncap, d)
-        fn = getattr(fa, "fa_kvcache_append" + ("_paged" if paged else "") + ("_fp8" if fp8 else ""))
+        fn = {(False, False): fa.fa_kvcache_append, (True, False): fa.fa_kvcache_append_paged, (False, True): fa.fa_kvcache_append_fp8,
+              (True, True): fa.fa_kvcache_append_paged_fp8}[paged, fp8]
         extra = ((table,) if paged else ()) + ((k_scale, v_scale) if fp8 else ())
         caches = {name: [torch.zeros(shape, dtype=torch.uint8 if fp8 else cdt, device=dev).view(cdt) for _ in range(2)]
                   for name in ("rope", "torch+entry", "plain")}
