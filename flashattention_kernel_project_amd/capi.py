@@ -103,6 +103,16 @@ class VarlenDesc(C.Structure):
             self.size = C.sizeof(VarlenDesc)
 
 
+class VarlenOpts(C.Structure):
+    """fa_varlen_opts of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("sinks", C.c_void_p), ("window", C.c_int), ("softcap", C.c_float)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(VarlenOpts)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -132,6 +142,8 @@ def _signatures() -> dict:
         "fa_kvcache_append_ex": (i, [C.POINTER(KvAppendDesc)]),
         "fa_merge_states": (i, [C.POINTER(MergeDesc)]),
         "fa_forward_varlen": (i, [C.POINTER(VarlenDesc)]),
+        # the same with a window, a soft-cap and sinks; a null opts is fa_forward_varlen
+        "fa_forward_varlen_ex": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

@@ -310,6 +310,10 @@ FA_EXPORT int fa_kvcache_append_ex(const fa_kvappend_desc* desc)
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 
 FA_EXPORT int fa_forward_varlen(const fa_varlen_desc* desc) { return (int)fa::varlen_dispatch(desc); }
+FA_EXPORT int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_opts* opts)
+{
+    return (int)fa::varlen_logits_dispatch(desc, opts);
+}
 
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)

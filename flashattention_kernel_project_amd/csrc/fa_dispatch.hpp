@@ -10,6 +10,7 @@
 
 struct fa_merge_desc;   // include/fa_mi355.h
 struct fa_varlen_desc;
+struct fa_varlen_opts;
 
 namespace fa {
 
@@ -193,6 +194,8 @@ hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t varlen_dispatch(const ::fa_varlen_desc* desc);
+// fa_forward_varlen_ex (fa_fwd_varlen_logits.hip): the options' checks, then varlen_dispatch (no options, or all off) or the one launch
+hipError_t varlen_logits_dispatch(const ::fa_varlen_desc* desc, const ::fa_varlen_opts* opts);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

@@ -1,397 +1,18 @@
 // fa_fwd_varlen.hip -- fa_forward_varlen: prefill on token-packed Q, K, V (cu_seqlens), grouped-query heads, a causal mask
 // aligned to the END of each sequence's keys, lse out.  The contract is include/fa_mi355.h's; the reasons are DESIGN.md 7.12.
-//
-// The design is the LDS-staged tiled kernel's (fa_fwd_kernel, fa_fwd_kernels.hip): S^T = K.Q^T on v_mfma_f32_32x32x16 with Q^T
-// resident in registers, the packed P directly the B operand of O^T += V^T.P^T, V^T through ds_read_b64_tr_b16, the K/V tile loaded
-// a tile ahead into a double-buffered LDS image (fa_tile.hpp), a lazy running max -- on 128-row workgroups (four waves of 32 rows),
-// so that a short sequence wastes little.  Nothing of that kernel is used here; what is new:
-//   * block -> (K/V head, slot, head of the group) with the G heads of a group, then the slots of a sequence, adjacent in the launch
-//     order; slot -> (sequence, query block) on the device: sequence b owns the slots [first_b, first_{b+1}), first_b =
-//     floor(s_q(b) / 128) + b, found by a binary search over cu_seqlens_q with scalar loads.  The grid is floor(total_q / 128) + B
-//     slots per query head: host integers only;
-//   * one buffer descriptor per (sequence, head) and tensor: base ptr + s * stride_t + h * stride_h, range (L - 1) * stride_t + d
-//     elements (0 when L = 0).  A row at or past L is never addressed: its offset could wrap 32 bits, so it is selected away (a
-//     partial tile's loads) or guarded (the stores), not left to the range check;
-//   * the causal limit c_i = max(0, Lk - Lq + 1 + i); a row that sees no key keeps m_ref = -inf and is selected to O = 0, lse = -inf;
-//   * lse = (m_ref + log2 l) ln 2, written with guarded vector stores.
-#include "../../include/fa_mi355.h"
-#include "fa_tile.hpp"
-#include "fa_dispatch.hpp"
-
-#include <math.h>
+// The kernel template and the checks are fa_fwd_varlen_kernel.hpp's; this unit holds the 16 plain instantiations (T x d x out x
+// causal).  The windowed / soft-capped / sink ones are fa_fwd_varlen_logits.hip's, so that neither set perturbs the other's code.
+#include "fa_fwd_varlen_kernel.hpp"
 
 namespace fa {
 
-constexpr int kVarlenWaves = 4;                    // 32 query rows each
-constexpr int kVarlenRows = 32 * kVarlenWaves;     // BM: query rows per workgroup = rows per slot
-constexpr float kVarlenLn2 = 0.6931471805599453f;
-
-struct VarlenArgs {
-    const uint16_t *Q, *K, *V;
-    void* O;
-    float* lse;
-    const int *cu_q, *cu_k;
-    int B, Hkv, G, total_q, total_k;
-    unsigned nslots;                                // floor(total_q / BM) + B
-    long long q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh;   // elements
-    float scale_log2e;
-};
-
-// [s, e) of sequence b in a tensor of `total` rows: never outside it, never negative in length
-__device__ __forceinline__ void varlen_bounds(const int* __restrict__ cu, unsigned b, int total, int& s, int& e)
-{
-    s = min(max(cu[b], 0), total);
-    e = min(max(cu[b + 1], s), total);
-}
-
-// the (sequence, head) view of a packed tensor: rows [0, L) of stride_t elements, d contiguous; es = bytes per element
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t varlen_rsrc(const void* ptr, int s, int L, unsigned h, long long st, long long sh,
-                                                              int d, unsigned es)
-{
-    const long long first = (long long)s * st + (long long)h * sh;
-    const unsigned bytes = L > 0 ? (unsigned)((unsigned long long)((long long)(L - 1) * st + d) * es) : 0u;
-    return make_rsrc(static_cast<const char*>(ptr) + first * (long long)es, bytes);
-}
-
-template <typename T, int D, bool kOutF32, bool kCausal>
-__global__ __launch_bounds__(64 * kVarlenWaves, 2)
-void fa_fwd_varlen_kernel(VarlenArgs a)
-{
-    using G = TileGeom<D>;
-    constexpr int W = kVarlenWaves;
-    constexpr unsigned BM = kVarlenRows;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    // ---- block -> (K/V head, slot, head of the group): blocks that share K/V sit on one XCD, consecutively ----
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned xq = nwg >> 3, xr = nwg & 7u, xcd = bid & 7u;
-    const unsigned wgid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
-    const unsigned grp = wgid / (unsigned)a.G, g = wgid - grp * (unsigned)a.G;
-    const unsigned hkv = grp / a.nslots, sidx = grp - hkv * a.nslots;
-    const unsigned slot = kCausal ? a.nslots - 1u - sidx : sidx;   // under the mask the last blocks of a sequence are the long ones
-    const unsigned hq = hkv * (unsigned)a.G + g;
-
-    // ---- slot -> (sequence, query block): the largest b with first_b <= slot (wave-uniform: scalar loads) ----
-    const int* __restrict__ cu_q = a.cu_q;
-    const int* __restrict__ cu_k = a.cu_k;
-    unsigned lo = 0, hi = (unsigned)a.B;
-    while (hi - lo > 1u) {
-        const unsigned mid = (lo + hi) >> 1;
-        const unsigned first = (unsigned)min(max(cu_q[mid], 0), a.total_q) / BM + mid;
-        if (first <= slot) lo = mid; else hi = mid;
-    }
-    const unsigned b = lo;
-    int sq, eq, sk, ek;
-    varlen_bounds(cu_q, b, a.total_q, sq, eq);
-    varlen_bounds(cu_k, b, a.total_k, sk, ek);
-    const int Lq = eq - sq, Lk = ek - sk;
-    const unsigned first_b = (unsigned)sq / BM + b;
-    if (slot < first_b) return;                        // slots below the first sequence's
-    const unsigned qb = slot - first_b;
-    if ((unsigned long long)qb * BM >= (unsigned long long)Lq) return;   // a spare slot of the sequence
-
-    const unsigned tid  = threadIdx.x;
-    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lane = tid & 63u;
-    const unsigned r = lane & 31u, h = lane >> 5;
-
-    const __amdgpu_buffer_rsrc_t rq = varlen_rsrc(a.Q, sq, Lq, hq, a.q_st, a.q_sh, D, 2u);
-    const __amdgpu_buffer_rsrc_t rk = varlen_rsrc(a.K, sk, Lk, hkv, a.k_st, a.k_sh, D, 2u);
-    const __amdgpu_buffer_rsrc_t rv = varlen_rsrc(a.V, sk, Lk, hkv, a.v_st, a.v_sh, D, 2u);
-    // byte strides of a token row; every offset of an existing row fits 32 bits (checked on the host)
-    const unsigned q_stb = (unsigned)a.q_st * 2u, k_stb = (unsigned)a.k_st * 2u, v_stb = (unsigned)a.v_st * 2u;
-
-    constexpr int kLoadsW = (kBlockN * G::kChunks) / (64 * W);
-    const unsigned wave_row0 = qb * BM + wave * 32u;   // first query row of this wave, in the sequence
-    const unsigned q_row = wave_row0 + r;
-    const bool row_live = q_row < (unsigned)Lq;
-    const int shift = Lk - Lq;                         // causal: row i sees the keys j <= i + shift
-
-    // ---- Q^T fragments (B operand of S^T = K.Q^T), resident for the whole kernel ---------------
-    // c = |scale|*log2(e) is applied to the fp32 scores; a negative scale flips Q's sign bits so that the row max of c*S is
-    // always c*max(S).  Rows at or past Lq are zeros.
-    const float c = fabsf(a.scale_log2e);
-    const unsigned q_flip = a.scale_log2e < 0.0f ? 0x80008000u : 0u;
-    u32x4 qf[G::kKSteps];
-#pragma unroll
-    for (int s = 0; s < G::kKSteps; ++s) {
-        u32x4 raw = buf_load16(rq, (row_live ? q_row * q_stb : 0u) + (16u * s + 8u * h) * 2u);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) raw[w] = row_live ? raw[w] ^ q_flip : 0u;
-        qf[s] = raw;
-    }
-
-    // ---- staging: each thread moves kLoadsW 16-B chunks of K and of V per tile -----------------
-    unsigned s_row[kLoadsW], s_col[kLoadsW], k_lds[kLoadsW], v_lds[kLoadsW];
-#pragma unroll
-    for (int p = 0; p < kLoadsW; ++p) {
-        const unsigned idx = tid + p * 64u * W;
-        const unsigned row = idx / G::kChunks, ch = idx % G::kChunks;
-        s_row[p] = row;
-        s_col[p] = ch * 16u;
-        k_lds[p] = G::k_off(row, ch);
-        v_lds[p] = G::kTileBytes + G::v_off(row, ch);
-    }
-    u32x4 kst[kLoadsW], vst[kLoadsW];
-    auto stage_load = [&](unsigned kv0) {
-        if (kv0 + (unsigned)kBlockN <= (unsigned)Lk) {          // a whole tile (wave-uniform)
-#pragma unroll
-            for (int p = 0; p < kLoadsW; ++p) {
-                kst[p] = buf_load16(rk, (kv0 + s_row[p]) * k_stb + s_col[p]);
-                vst[p] = buf_load16(rv, (kv0 + s_row[p]) * v_stb + s_col[p]);
-            }
-        } else {                                                // the last one: rows at or past Lk are zeros
-#pragma unroll
-            for (int p = 0; p < kLoadsW; ++p) {
-                const unsigned key = kv0 + s_row[p];
-                const bool ok = key < (unsigned)Lk;
-                const u32x4 kk = buf_load16(rk, (ok ? key * k_stb : 0u) + s_col[p]);
-                const u32x4 vv = buf_load16(rv, (ok ? key * v_stb : 0u) + s_col[p]);
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    kst[p][w] = ok ? kk[w] : 0u;
-                    vst[p][w] = ok ? vv[w] : 0u;
-                }
-            }
-        }
-    };
-    auto stage_write = [&](unsigned buf) {
-#pragma unroll
-        for (int p = 0; p < kLoadsW; ++p) {
-            lds_write16(smem, buf * G::kBufBytes + k_lds[p], kst[p]);
-            lds_write16(smem, buf * G::kBufBytes + v_lds[p], vst[p]);
-        }
-    };
-
-    // ---- per-lane LDS read addresses (fa_tile.hpp's images) ------------------------------------
-    const unsigned k_rd_row = r * G::kRowBytes;
-    const unsigned k_rd_swz = G::k_swz(r);
-    const unsigned i16 = lane & 15u, vq = i16 >> 2, vp = i16 & 3u, vg = (lane >> 4) & 1u;
-    unsigned v_rd[2];   // per parity of the column block (row-slot rotation)
-#pragma unroll
-    for (int par = 0; par < 2; ++par)
-        v_rd[par] = G::kTileBytes + h * G::kDBlocks * 256u + ((vq ^ par) << 6) + vg * 32u + vp * 8u;
-
-    // ---- running state -------------------------------------------------------------------------
-    f32x16 o[G::kDBlocks];
-#pragma unroll
-    for (int db = 0; db < G::kDBlocks; ++db)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[db][i] = 0.0f;
-    f32x16 zero16;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) zero16[i] = 0.0f;
-    float m_ref = -INFINITY;   // reference max of this lane's query row, in log2 units (c*S); -inf: no key seen yet
-    float l_part = 0.0f;       // this half-wave's share of the row sum
-
-    // tiles up to the key limit of the workgroup's last existing row
-    int klim = Lk;
-    if constexpr (kCausal) {
-        const int last_row = (int)min((unsigned)Lq - 1u, qb * BM + BM - 1u);
-        klim = max(0, shift + 1 + last_row);           // <= Lk
-    }
-    const int ntiles = (klim + kBlockN - 1) / kBlockN;
-
-    if (ntiles > 0) {
-        stage_load(0);
-        stage_write(0);
-    }
-    __syncthreads();
-
-    for (int t = 0; t < ntiles; ++t) {
-        const unsigned cur = t & 1u;
-        const char* kbuf = smem + cur * G::kBufBytes;
-        if (t + 1 < ntiles) stage_load((t + 1) * kBlockN);
-        // causal: tiles wholly past the limits of this wave's rows contribute nothing (wave-uniform)
-        if (!kCausal || t * kBlockN <= shift + (int)wave_row0 + 31) {
-
-        // ---- S^T = K.Q^T (raw fp32 scores) ------------------------------------------------
-        f32x16 s[2];
-#pragma unroll
-        for (int ks = 0; ks < G::kKSteps; ++ks) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                const u32x4 kf = lds_read16(kbuf, kb * 32u * G::kRowBytes + k_rd_row +
-                                                      (((2u * ks + h) ^ k_rd_swz) << 4));
-                s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
-            }
-        }
-
-        // ---- keys >= Lk (last tile only): -inf so that p = 0 --------------------------------
-        if ((t + 1) * kBlockN > Lk) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = t * kBlockN + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * (int)h;
-                    if (key >= Lk) s[kb][i] = -INFINITY;
-                }
-        }
-        if constexpr (kCausal) {   // tiles a limit of this wave crosses: keys past the row's limit -> -inf
-            if (t * kBlockN + kBlockN - 1 > shift + (int)wave_row0) {
-                const int lim = shift + (int)q_row;   // the last key the row sees; negative: none
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = t * kBlockN + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * (int)h;
-                        if (key > lim) s[kb][i] = -INFINITY;
-                    }
-            }
-        }
-
-        // ---- tile max vs the reference max; raise the reference only when needed ----------------
-        float tmax = max3(s[0][0], s[0][1], s[0][2]);
-#pragma unroll
-        for (int i = 3; i < 15; i += 2) tmax = max3(tmax, s[0][i], s[0][i + 1]);
-        tmax = max3(tmax, s[0][15], s[1][0]);
-#pragma unroll
-        for (int i = 1; i < 15; i += 2) tmax = max3(tmax, s[1][i], s[1][i + 1]);
-        tmax = fmaxf(tmax, s[1][15]) * c;   // log2 units; -inf: the row sees no key of this tile
-
-        // a row that has seen no key has m_ref = -inf: a first key raises it (inf > kThr), none leaves it (NaN > kThr is false)
-        if (__any(tmax - m_ref > kThr)) {
-            const float mx = fmaxf(tmax, swap_halves(tmax));         // row max, same in both halves
-            const float m_new = fmaxf(mx, m_ref);
-            const float alpha = m_ref == -INFINITY ? 0.0f : fast_exp2(m_ref - m_new);   // never 2^(-inf - -inf)
-            m_ref = m_new;
-#pragma unroll
-            for (int db = 0; db < G::kDBlocks; ++db)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
-            l_part *= alpha;
-        }
-
-        // ---- p = 2^(c*S - m_ref), row-sum share, pack to 16 bit (B operand of PV) -----------
-        u32x4 pk[4];
-        float lsum0 = 0.0f, lsum1 = 0.0f;
-        const float neg_m = m_ref == -INFINITY ? 0.0f : -m_ref;   // every score of such a row is -inf: p = 2^-inf = 0
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s[kb][i] = fast_exp2(__builtin_fmaf(s[kb][i], c, neg_m));
-            if constexpr (!T::kSumRounded) {
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    lsum0 += s[kb][i];
-                    lsum1 += s[kb][i + 1];
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    pk[kb * 2 + s2][w] = T::pack2(s[kb][8 * s2 + 2 * w], s[kb][8 * s2 + 2 * w + 1]);
-                    if constexpr (T::kSumRounded) {
-                        if (w & 1) lsum1 = T::sum2(pk[kb * 2 + s2][w], lsum1);
-                        else lsum0 = T::sum2(pk[kb * 2 + s2][w], lsum0);
-                    }
-                }
-        }
-        l_part += lsum0 + lsum1;
-
-        // ---- O^T += V^T.P^T -------------------------------------------------------------------
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-            for (int db = 0; db < G::kDBlocks; ++db) {
-                u32x4 vf;
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const u32x2 half = lds_read_tr8(
-                        kbuf, v_rd[db & 1] + ((4u * ks + 2u * jj) * G::kDBlocks + db) * 256u);
-                    vf[2 * jj] = half[0];
-                    vf[2 * jj + 1] = half[1];
-                }
-                o[db] = T::mfma32(vf, pk[ks], o[db]);
-            }
-        }
-        }   // wave has work in this tile
-
-        if (t + 1 < ntiles) stage_write(cur ^ 1u);
-        __syncthreads();
-    }
-
-    // ---- normalise and store: lane holds O[q_row][db*32 + 8g + 4h + 0..3] in o[db][4g..4g+3] ---
-    if (!row_live) return;                             // rows at or past Lq are the next sequence's, or nobody's
-    const float l = l_part + swap_halves(l_part);
-    const bool none = m_ref == -INFINITY;              // the row saw no key: O = 0 and lse = -inf, never 0/0
-    const float inv = none ? 0.0f : 1.0f / l;
-    if (a.lse && h == 0)
-        a.lse[(size_t)hq * (size_t)a.total_q + (size_t)sq + q_row] = none ? -INFINITY : (m_ref + __log2f(l)) * kVarlenLn2;
-    constexpr unsigned es = kOutF32 ? 4u : 2u;
-    const __amdgpu_buffer_rsrc_t ro = varlen_rsrc(a.O, sq, Lq, hq, a.o_st, a.o_sh, D, es);
-    const unsigned o_row = q_row * ((unsigned)a.o_st * es);
-#pragma unroll
-    for (int db = 0; db < G::kDBlocks; ++db) {
-#pragma unroll
-        for (int gg = 0; gg < 4; ++gg) {
-            const unsigned col = db * 32u + 8u * gg + 4u * h;
-            const float x0 = none ? 0.0f : o[db][4 * gg] * inv, x1 = none ? 0.0f : o[db][4 * gg + 1] * inv;
-            const float x2 = none ? 0.0f : o[db][4 * gg + 2] * inv, x3 = none ? 0.0f : o[db][4 * gg + 3] * inv;
-            if constexpr (kOutF32) {
-                const f32x4 v = {x0, x1, x2, x3};
-                buf_store16(ro, o_row + col * 4u, __builtin_bit_cast(u32x4, v));
-            } else {
-                const u32x2 v = {T::pack2(x0, x1), T::pack2(x2, x3)};
-                buf_store8(ro, o_row + col * 2u, v);
-            }
-        }
-    }
-}
-
-// ---- host side: the checks and the one launch --------------------------------------------------------------------------------
-
-// the last addressable byte of a packed tensor, ((total-1)*stride_t + (H-1)*stride_h + d) * es, must fit 32 bits
-static bool varlen_tensor_ok(const void* p, int total, int H, int d, long long st, long long sh, unsigned es)
-{
-    if (!p || (reinterpret_cast<uintptr_t>(p) & 15u)) return false;
-    if (st < d || sh < 0 || st % 8 != 0 || sh % 8 != 0) return false;
-    const unsigned __int128 end = ((unsigned __int128)(total - 1) * (unsigned long long)st +
-                                   (unsigned __int128)(H - 1) * (unsigned long long)sh + (unsigned)d) * es;
-    return end <= 0xFFFFFFFFull;
-}
-
 hipError_t varlen_dispatch(const fa_varlen_desc* d)
 {
-    if (!d || d->size != sizeof(fa_varlen_desc)) return hipErrorInvalidValue;
-    if (!d->cu_seqlens_q || !d->cu_seqlens_k) return hipErrorInvalidValue;
-    if (d->B <= 0 || d->Hkv <= 0 || d->G <= 0 || d->total_q <= 0 || d->total_k <= 0) return hipErrorInvalidValue;
-    if (d->d != 64 && d->d != 128) return hipErrorInvalidValue;
-    if (d->in_dtype != FA_DTYPE_F16 && d->in_dtype != FA_DTYPE_BF16) return hipErrorInvalidValue;
-    if (d->out_dtype != FA_OUT_F32 && d->out_dtype != FA_OUT_SAME) return hipErrorInvalidValue;
-    const long long Hq = (long long)d->Hkv * d->G;                                          // < 2^62
-    if (Hq > 0x7FFFFFFFll || (unsigned __int128)Hq * (unsigned)d->B > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const unsigned es = d->out_dtype == FA_OUT_F32 ? 4u : 2u;
-    if (!varlen_tensor_ok(d->Q, d->total_q, (int)Hq, d->d, d->q_stride_t, d->q_stride_h, 2u) ||
-        !varlen_tensor_ok(d->K, d->total_k, d->Hkv, d->d, d->k_stride_t, d->k_stride_h, 2u) ||
-        !varlen_tensor_ok(d->V, d->total_k, d->Hkv, d->d, d->v_stride_t, d->v_stride_h, 2u) ||
-        !varlen_tensor_ok(d->O, d->total_q, (int)Hq, d->d, d->o_stride_t, d->o_stride_h, es))
-        return hipErrorInvalidValue;
-    // block slots: floor(total_q / BM) + B per query head, whatever the vectors hold
-    const long long nslots = (long long)d->total_q / kVarlenRows + d->B;
-    if (nslots * Hq > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    VarlenArgs a = {static_cast<const uint16_t*>(d->Q), static_cast<const uint16_t*>(d->K), static_cast<const uint16_t*>(d->V),
-                    d->O, d->lse, d->cu_seqlens_q, d->cu_seqlens_k, d->B, d->Hkv, d->G, d->total_q, d->total_k, (unsigned)nslots,
-                    d->q_stride_t, d->q_stride_h, d->k_stride_t, d->k_stride_h, d->v_stride_t, d->v_stride_h, d->o_stride_t,
-                    d->o_stride_h, host_scale_log2e(d->scale)};
-    const dim3 grid((unsigned)(nslots * Hq));
-    const bool causal = d->causal != 0;
-    return with_types(d->in_dtype, d->out_dtype, [&](auto t, auto f32) {
-        using T = decltype(t);
-        auto launch = [&](auto kernel, int lds) {
-            const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds);
-            if (attr != hipSuccess) return attr;
-            FA_LAUNCH(kernel, grid, dim3(64 * kVarlenWaves), (size_t)lds, static_cast<hipStream_t>(d->stream), a);
-            return launch_status();
-        };
-        constexpr bool kF32 = decltype(f32)::value;
-        if (d->d == 64)
-            return causal ? launch(fa_fwd_varlen_kernel<T, 64, kF32, true>, TileGeom<64>::kLdsBytes)
-                          : launch(fa_fwd_varlen_kernel<T, 64, kF32, false>, TileGeom<64>::kLdsBytes);
-        return causal ? launch(fa_fwd_varlen_kernel<T, 128, kF32, true>, TileGeom<128>::kLdsBytes)
-                      : launch(fa_fwd_varlen_kernel<T, 128, kF32, false>, TileGeom<128>::kLdsBytes);
-    });
+    VarlenArgs a;
+    dim3 grid;
+    const hipError_t e = varlen_check(d, a, grid);
+    if (e != hipSuccess) return e;
+    return varlen_launch<false>(d, a, grid);
 }
 
 }  // namespace fa

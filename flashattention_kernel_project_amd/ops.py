@@ -434,8 +434,8 @@ def _packed_strides(t, name: str):
 
 
 def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, scale: float | None = None, out_dtype=None,
-                      return_lse: bool = False, out=None, stream=None, lse=None):
-    """Variable-length packed prefill (fa_forward_varlen): B sequences of different lengths in one launch.
+                      return_lse: bool = False, out=None, stream=None, lse=None, window: int = 0, softcap: float = 0.0, sinks=None):
+    """Variable-length packed prefill (fa_forward_varlen, fa_forward_varlen_ex): B sequences of different lengths in one launch.
     q (total_q, Hq, d), k and v (total_k, Hkv, d) fp16/bf16 device tensors, packed along the token axis; d in {64,128};
     Hq = G * Hkv (grouped-query: query head hq reads K/V head hq // G, no expanded copy).  Any token and head strides are accepted as
     long as the last dimension is contiguous (strides multiples of 8 elements, 16-byte aligned storage), so a (H, total, d) tensor
@@ -447,6 +447,14 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
     -> o (total_q, Hq, d) of out_dtype (torch.float32, the default, or the input dtype), or (o, lse) with return_lse, lse (Hq, total_q)
     float32 in natural-log units, as fa_merge_states takes it.  Rows that belong to no sequence are NOT written: in a fresh result they
     are uninitialised; pass `out` (and `lse`, which implies return_lse) to keep what they held.
+    window: 0 (no window), or W >= 1: row i sees only the keys [max(0, Lk - Lq + 1 + i - W), its upper limit) -- with causal its own
+    position and the W - 1 before it, the limits fa_forward_kvcache has.  K/V tiles below a query block's first visible key are not read.
+    softcap: 0 (off), or a finite float > 0: every logit s becomes softcap * tanh(s / softcap) before the masks and the softmax.
+    sinks: None, or a float32 contiguous device tensor of Hq values: head h gets one extra key with the natural-log logit sinks[h]
+    (not scaled, not capped) and a zero V row, which every row of a sequence sees under any mask or window -- lse includes it, and a
+    row without a key is O = 0, lse = sinks[h]; -inf: no sink for that head.  Read on the device only.
+    window and softcap are host values (baked into a captured call).  With all three unset the call is fa_forward_varlen itself;
+    otherwise fa_forward_varlen_ex, whose kernels compute a prompt by the arithmetic fa_forward_kvcache decodes its tokens with.
     One kernel, no workspace, nothing read on the host: a captured call follows vectors that are rewritten in place."""
     import torch
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -462,6 +470,9 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
         raise ValueError("d must be 64 or 128")
     if total_q <= 0 or total_k <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0:
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
+    window = _window(window)
+    softcap = _softcap(softcap)
+    sink_ptr = _sinks_ptr(sinks, Hq, q.device)
     if cu_seqlens_k is None:
         cu_seqlens_k = cu_seqlens_q
     for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
@@ -496,9 +507,13 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
                            total_q=total_q, total_k=total_k, q_stride_t=qt, q_stride_h=qh, k_stride_t=kt, k_stride_h=kh, v_stride_t=vt,
                            v_stride_h=vh, o_stride_t=ot, o_stride_h=oh, scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)),
                            in_dtype=_in_dt(q.dtype), out_dtype=out_dt, stream=_stream_ptr(stream))
-    with torch.cuda.device(_one_device(q, k, v, out, cu_seqlens_q, cu_seqlens_k, lse)):
-        code = capi.lib().fa_forward_varlen(desc)
-    capi.check("fa_forward_varlen", code)
+    plain = window == 0 and softcap == 0.0 and sinks is None   # then the old symbol, as before the options existed
+    with torch.cuda.device(_one_device(q, k, v, out, cu_seqlens_q, cu_seqlens_k, lse, sinks)):
+        if plain:
+            code = capi.lib().fa_forward_varlen(desc)
+        else:
+            code = capi.lib().fa_forward_varlen_ex(desc, capi.VarlenOpts(sinks=sink_ptr, window=window, softcap=softcap))
+    capi.check("fa_forward_varlen" if plain else "fa_forward_varlen_ex", code)
     return (out, lse) if return_lse else out
 
 

@@ -34,6 +34,8 @@ eager fallback.  Registered on first use:
                                                 softcap, out_fp32)
     # variable-length packed prefill (ops.fa_forward_varlen): q (total_q,Hq,d), k and v (total_k,Hkv,d), lse (Hq,total_q)
     o, lse = torch.ops.fa_mi355.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32)
+    # the same with a sliding window, sinks and a soft-cap (the decode _ex form's three arguments, in its order)
+    o, lse = torch.ops.fa_mi355.forward_varlen_ex(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, sinks, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
-    .merge_states, .decode_shared_prefix and .forward_varlen (idempotent)."""
+    .merge_states, .decode_shared_prefix, .forward_varlen and .forward_varlen_ex (idempotent)."""
     global _registered
     if _registered:
         return
@@ -173,6 +175,20 @@ def register() -> None:
 
     @forward_varlen.register_fake
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32):
+        return (q.new_empty(q.shape, dtype=out_dtype(q, out_f32)),
+                q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32))
+
+    # forward_varlen with `int window, Tensor? sinks, float softcap` behind `causal`, as in the decode _ex form
+    @torch.library.custom_op("fa_mi355::forward_varlen_ex", mutates_args=(), device_types="cuda",
+                             schema="(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, float scale, bool causal, "
+                                    "int window, Tensor? sinks, float softcap, bool out_f32) -> (Tensor, Tensor)")
+    def forward_varlen_ex(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, sinks, softcap, out_f32):
+        return ops.fa_forward_varlen(q, k, v, cu_seqlens_q.contiguous(), opt(cu_seqlens_k), causal=causal, scale=scale,
+                                     out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+                                     softcap=softcap, sinks=opt(sinks))
+
+    @forward_varlen_ex.register_fake
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, sinks, softcap, out_f32):
         return (q.new_empty(q.shape, dtype=out_dtype(q, out_f32)),
                 q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32))
 

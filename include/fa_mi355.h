@@ -328,7 +328,8 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  *           splits.  With every n_b >= Nq the bits are those of the call without seqlens_q.
  *           A descriptor whose `size` is offsetof(fa_kvdecode_desc, seqlens_q) -- the structure before this field existed -- is
  *           accepted and means seqlens_q == NULL; every other wrong size is refused.
- * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the prefill entries (fa_forward*), a tanh other than
+ * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the dense prefill entries (fa_forward, fa_forward_ex;
+ * the packed prefill has them: fa_forward_varlen_ex), a tanh other than
  * the one above; token-packed (cu_seqlens) layouts, a split count or a window per sequence, explicit position ids, per-sequence
  * query counts on the prefill entries or on the flat decode entries.  NOT a reference entry point. */
 #define FA_KV_16BIT    0   /* K, V elements are of in_dtype */
@@ -597,8 +598,8 @@ int fa_merge_states(const fa_merge_desc* desc);
  * stride_t below d, a negative stride_h, or any stride that is not a multiple of 8 elements; a base pointer that is not 16-byte
  * aligned; a tensor whose last addressable byte, ((total-1)*stride_t + (H-1)*stride_h + d) * element bytes, does not fit 32 bits
  * (the kernel uses 32-bit buffer offsets); B*Hkv*G, or the block-slot count times Hkv*G, beyond 2^31 - 1 (the grid).
- * Not part of this entry: a window, sinks, a soft-cap, fp8, a paged K/V, rotary, max_seqlen hints, dropout.
- * NOT a reference entry point. */
+ * Not part of this entry: a window, sinks, a soft-cap, fp8, a paged K/V, rotary, max_seqlen hints, dropout.  The first three are
+ * fa_forward_varlen_ex's, below, which takes this descriptor and a small structure of options.  NOT a reference entry point. */
 typedef struct fa_varlen_desc {
     size_t size;                    /* sizeof(fa_varlen_desc); any other value is refused */
     const void *Q, *K, *V;          /* device, 16-bit of in_dtype */
@@ -615,6 +616,49 @@ typedef struct fa_varlen_desc {
     void* stream;
 } fa_varlen_desc;
 int fa_forward_varlen(const fa_varlen_desc* desc);
+
+/* fa_forward_varlen with the three options on the logits that the local-attention model families use and fa_kvcache_decode already
+ * has: a sliding window, soft-capped logits (Gemma-2 style) and one attention sink per query head (gpt-oss style), so that a
+ * prompt is prefilled by the arithmetic its tokens are decoded with.  `desc` means what it means above.  The semantics are the
+ * decode side's, with Lq_b in the place of Nq and Lk_b in the place of L_b.
+ * opts == NULL, or window == 0, softcap == 0 and sinks == NULL: the call IS fa_forward_varlen(desc): same checks, same kernels,
+ * same bits.  `size` must equal sizeof(fa_varlen_opts).
+ * window    a host int, baked into a captured call.  0: none.  W >= 1: row i of sequence b sees the keys [lo_i, c_i) with
+ *           lo_i = max(0, Lk_b - Lq_b + 1 + i - W) and c_i as above (Lk_b without causal, max(0, Lk_b - Lq_b + 1 + i) with it).  The
+ *           lower limit is the same with and without causal: flash-attn's window_size (W-1, 0) with causal = 1 and (W-1, -1) with
+ *           causal = 0, as fa_forward_kvcache_window has it.  lo_i < c_i whenever c_i >= 1.  W >= Lk_b + Lq_b for every b returns the
+ *           bits of the same call with window == 0.  W < 0: hipErrorInvalidValue.  One W for all sequences and heads.
+ *           What is read: the K/V rows of a sequence below the 64-key tile that holds the first visible key of a 128-row query block
+ *           are not read for that block.  A key below a row's lo_i inside a tile that is read is a masked score (weight exactly 0),
+ *           but its K and V rows are used as they are: a NaN there behaves like a NaN in any other key of fa_forward_varlen.
+ * softcap   a host float, baked into a captured call.  0: off.  > 0 and finite: the logit becomes
+ *           t_j = softcap * tanh(s_j / softcap) with s_j = scale * q.k_j, by fa_kvcache_decode's formula (1 - 2 / (1 + e^(2y)) on the
+ *           hardware exponential and reciprocal).  The masks apply AFTER the cap: a key outside [lo_i, c_i) has weight exactly 0.
+ *           scale = 0 keeps its meaning (uniform weights), a negative scale negates the logits (tanh is odd).  Negative, NaN or inf:
+ *           hipErrorInvalidValue.
+ * sinks     a device pointer to Hkv*G fp32 values, or NULL for none.  Head hq has the sink logit a = sinks[hq], in natural-log units
+ *           and final: not multiplied by scale, not soft-capped.  It is one extra key that every row of the head sees, with logit a
+ *           and a zero V row, which no mask or window removes:
+ *             O_i = sum_j exp(t_j) v_j / (exp(a) + sum_j exp(t_j)),   lse_i = ln(exp(a) + sum_j exp(t_j)).
+ *           A row of a sequence that sees no key gets O = 0 exactly and lse = a.  a = -inf is "no sink for this head": the head
+ *           returns the bits it returns with sinks == NULL.  The sink counts ONCE per row.  The vector is read on the device only: a
+ *           captured call follows a vector that is rewritten in place.  Rows of O and lse that belong to no sequence stay unwritten.
+ *           The sink is part of lse: a caller who merges this result with others through fa_merge_states passes `sinks` to one
+ *           of the parts only.
+ * Unchanged: nothing on the host reads device data; the grid depends on (B, Hkv, G, total_q) only; no workspace; one kernel; the
+ * clamps of the sequence bounds; a captured call follows cu_seqlens_* and sinks that are rewritten in place.
+ * hipErrorInvalidValue, before the device is touched: a wrong opts->size, window < 0, a bad softcap, and everything
+ * fa_forward_varlen rejects.
+ * Not part of this entry: a window that crosses into a separately cached prefix (a prompt chunk merged with a decode over a cached
+ * prefix through fa_merge_states cannot carry a window over the boundary), a window per sequence or per head, fp8 or paged K/V,
+ * rotary.  NOT a reference entry point. */
+typedef struct fa_varlen_opts {
+    size_t size;          /* sizeof(fa_varlen_opts); any other value is refused */
+    const float* sinks;   /* device, Hkv*G fp32 natural-log logits, or NULL */
+    int window;           /* 0: none; W >= 1 */
+    float softcap;        /* 0: off; > 0 and finite */
+} fa_varlen_opts;
+int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_opts* opts);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
