@@ -113,6 +113,22 @@ class VarlenOpts(C.Structure):
             self.size = C.sizeof(VarlenOpts)
 
 
+class VarlenKvcacheDesc(C.Structure):
+    """fa_varlen_kvcache_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Q", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p),
+                ("cu_seqlens_q", C.c_void_p), ("seqlens_k", C.c_void_p), ("block_table", C.c_void_p), ("B", C.c_int), ("Hkv", C.c_int),
+                ("G", C.c_int), ("d", C.c_int), ("total_q", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int),
+                ("page_size", C.c_int), ("max_pages", C.c_int), ("q_stride_t", C.c_longlong), ("q_stride_h", C.c_longlong),
+                ("o_stride_t", C.c_longlong), ("o_stride_h", C.c_longlong), ("scale", C.c_float), ("causal", C.c_int),
+                ("in_dtype", C.c_int), ("out_dtype", C.c_int), ("sinks", C.c_void_p), ("window", C.c_int), ("softcap", C.c_float),
+                ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(VarlenKvcacheDesc)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -144,6 +160,8 @@ def _signatures() -> dict:
         "fa_forward_varlen": (i, [C.POINTER(VarlenDesc)]),
         # the same with a window, a soft-cap and sinks; a null opts is fa_forward_varlen
         "fa_forward_varlen_ex": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
+        # the same with K/V in the KV cache, contiguous or paged
+        "fa_forward_varlen_kvcache": (i, [C.POINTER(VarlenKvcacheDesc)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

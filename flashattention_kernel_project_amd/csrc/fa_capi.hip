@@ -314,6 +314,7 @@ FA_EXPORT int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_o
 {
     return (int)fa::varlen_logits_dispatch(desc, opts);
 }
+FA_EXPORT int fa_forward_varlen_kvcache(const fa_varlen_kvcache_desc* desc) { return (int)fa::varlen_cache_dispatch(desc); }
 
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)

@@ -11,6 +11,7 @@
 struct fa_merge_desc;   // include/fa_mi355.h
 struct fa_varlen_desc;
 struct fa_varlen_opts;
+struct fa_varlen_kvcache_desc;
 
 namespace fa {
 
@@ -196,6 +197,10 @@ hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 hipError_t varlen_dispatch(const ::fa_varlen_desc* desc);
 // fa_forward_varlen_ex (fa_fwd_varlen_logits.hip): the options' checks, then varlen_dispatch (no options, or all off) or the one launch
 hipError_t varlen_logits_dispatch(const ::fa_varlen_desc* desc, const ::fa_varlen_opts* opts);
+// fa_forward_varlen_kvcache (fa_fwd_varlen_cache.hip): the checks and the one launch; the descriptor is the public one, as it is
+hipError_t varlen_cache_dispatch(const ::fa_varlen_kvcache_desc* desc);
+// ... what it hands a checked call with an option on to (fa_fwd_varlen_cache_logits.hip); args: the checked VarlenCacheArgs
+hipError_t varlen_cache_logits_launch(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

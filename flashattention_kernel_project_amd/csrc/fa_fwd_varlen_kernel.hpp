@@ -27,6 +27,18 @@
 //   * soft-cap: before the masks every score x = s c (log2 units) becomes cap2 tanh(x / cap2) by the decode side's formula; the
 //     factor the vote and the weights then multiply a score by is 1 (`cs`).  cap2 == 0 skips it by a wave-uniform branch;
 //   * sinks: one extra key per row with the head's logit and a zero V row, joined to (m, l) by sink_join() in the epilogue only.
+// kCache (fa_forward_varlen_kvcache; the argument is then a VarlenCacheArgs): K/V rows come from the KV cache, and
+// only that is new -- everything it adds sits behind `if constexpr (kCache ...)`, and the 32 packed instantiations keep their
+// argument lists and their code (profiles/varlen_cache.txt).  Lk = clamp(seqlens_k[b], 0, Ncap) in the place of the cu_k pair:
+//   * kVarlenContig: one descriptor per (b, hkv) of Lk rows of d elements; the loads are the packed ones;
+//   * kVarlenPaged: the decode side's scheme (fa_fwd_split_kernel.hpp) on this kernel's staging.  With idx = tid + p * 256 the loads
+//     one wave issues for one p cover 8 consecutive rows at d = 64 and 4 at d = 128, aligned to as many, so they lie inside ONE page
+//     of >= 16 keys: the page number is wave-uniform, held in a scalar register per (wave, p), and goes into a descriptor that ends
+//     at the page's last row below Lk (rows past it read 0, as the packed kernel's last tile selects them).  The table entries of
+//     tile t + 1 are fetched while tile t - 1 computes; the entry index is clamped to [page of lo(first row), page of Lk - 1];
+//   * with a window the rows of tile t0 below the lo of the workgroup's first row reach LDS as zeros, and a page wholly below that
+//     lo gets a descriptor of no records: a freed page may hold NaN, and 0 * NaN in the PV MFMA is NaN.
+// Tiles stay at absolute multiples of 64 from key 0, so on finite keys the cache kernels return the packed kernels' bits.
 #pragma once
 #include "../../include/fa_mi355.h"
 #include "fa_tile.hpp"
@@ -61,6 +73,21 @@ struct VarlenLogitArgs : VarlenArgs {
     float cap_rk;         // 2 / softcap
 };
 
+// Where the K/V rows come from (the kernel's kCache)
+constexpr int kVarlenPacked = 0;   // token-packed tensors cut by cu_k
+constexpr int kVarlenContig = 1;   // a cache [B, Hkv, Ncap, D]
+constexpr int kVarlenPaged = 2;    // page pools [num_pages, Hkv, page, D] behind a block table
+
+// What the cache instantiations take, plain and kLogits alike (the plain ones leave the three options unread).  K, V: the cache or
+// the pools; cu_k is null; total_k is the capacity Ncap; k_st = v_st = D and k_sh = v_sh = Ncap * D (the contiguous descriptor's).
+struct VarlenCacheArgs : VarlenLogitArgs {
+    const int* seqlens_k;   // [B] keys of sequence b in the cache, on the device
+    const int* table;       // [B][max_pages] page numbers on the device; null: contiguous
+    int max_pages;          // row pitch of the table; Ncap = max_pages << lg_page
+    int num_pages;          // pages in the pool: a live entry outside [0, num_pages) reads as a page of zeros
+    int lg_page;            // log2 of the page size in keys (>= 4)
+};
+
 // [s, e) of sequence b in a tensor of `total` rows: never outside it, never negative in length
 __device__ __forceinline__ void varlen_bounds(const int* __restrict__ cu, unsigned b, int total, int& s, int& e)
 {
@@ -77,9 +104,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t varlen_rsrc(const void* ptr, i
     return make_rsrc(static_cast<const char*>(ptr) + first * (long long)es, bytes);
 }
 
-template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false>
+template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false, int kCache = kVarlenPacked>
 __global__ __launch_bounds__(64 * kVarlenWaves, 2)
-void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs> a)
+void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCacheArgs, std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs>> a)
 {
     using G = TileGeom<D>;
     constexpr int W = kVarlenWaves;
@@ -107,7 +134,12 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
     const unsigned b = lo;
     int sq, eq, sk, ek;
     varlen_bounds(cu_q, b, a.total_q, sq, eq);
-    varlen_bounds(cu_k, b, a.total_k, sk, ek);
+    if constexpr (kCache != kVarlenPacked) {   // the keys of sequence b are the cache rows [0, Lk)
+        sk = 0;
+        ek = min(max(a.seqlens_k[b], 0), a.total_k);
+    } else {
+        varlen_bounds(cu_k, b, a.total_k, sk, ek);
+    }
     const int Lq = eq - sq, Lk = ek - sk;
     const unsigned first_b = (unsigned)sq / BM + b;
     if (slot < first_b) return;                        // slots below the first sequence's
@@ -120,10 +152,15 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
     const unsigned r = lane & 31u, h = lane >> 5;
 
     const __amdgpu_buffer_rsrc_t rq = varlen_rsrc(a.Q, sq, Lq, hq, a.q_st, a.q_sh, D, 2u);
-    const __amdgpu_buffer_rsrc_t rk = varlen_rsrc(a.K, sk, Lk, hkv, a.k_st, a.k_sh, D, 2u);
-    const __amdgpu_buffer_rsrc_t rv = varlen_rsrc(a.V, sk, Lk, hkv, a.v_st, a.v_sh, D, 2u);
+    // kCache: sequence b's part of the cache starts b * Hkv * Ncap rows in (64 bit); a.k_sh = Ncap * D then selects the head.  Paged:
+    // these two are not used, every (wave, p) makes its own
+    const size_t kv_b = kCache == kVarlenContig ? (size_t)b * (size_t)a.Hkv * (size_t)a.k_sh : 0;
+    const __amdgpu_buffer_rsrc_t rk = varlen_rsrc(a.K + kv_b, sk, Lk, hkv, a.k_st, a.k_sh, D, 2u);
+    const __amdgpu_buffer_rsrc_t rv = varlen_rsrc(a.V + kv_b, sk, Lk, hkv, a.v_st, a.v_sh, D, 2u);
     // byte strides of a token row; every offset of an existing row fits 32 bits (checked on the host)
-    const unsigned q_stb = (unsigned)a.q_st * 2u, k_stb = (unsigned)a.k_st * 2u, v_stb = (unsigned)a.v_st * 2u;
+    const unsigned q_stb = (unsigned)a.q_st * 2u;
+    const unsigned k_stb = kCache != kVarlenPacked ? D * 2u : (unsigned)a.k_st * 2u;
+    const unsigned v_stb = kCache != kVarlenPacked ? D * 2u : (unsigned)a.v_st * 2u;
 
     constexpr int kLoadsW = (kBlockN * G::kChunks) / (64 * W);
     const unsigned wave_row0 = qb * BM + wave * 32u;   // first query row of this wave, in the sequence
@@ -143,11 +180,14 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
     // kLogits: the lower key limits of the workgroup's first row (tile t0 holds it), of this wave's first row (the wave's smallest)
     // and of its last row (its largest); |shift + 1 + row| <= 2^26 and window <= 2^27 by the host's checks, so nothing wraps
     [[maybe_unused]] int t0 = 0, lo_first = 0, lo_last = 0;
+    // kCache: the lo of the workgroup's first row itself (0 without a window): no K/V row and no page below it is used
+    [[maybe_unused]] unsigned lo_wg = 0;
     if constexpr (kLogits) {
         cs = to_sgpr(a.cap2 > 0.0f ? 1.0f : c);
         cap_k1 = to_sgpr(c * a.cap_rk);
         cap_n2 = to_sgpr(-2.0f * a.cap2);
         t0 = max(0, shift + 1 + (int)(qb * BM) - a.window) / kBlockN;
+        if constexpr (kCache != kVarlenPacked) lo_wg = (unsigned)max(0, shift + 1 + (int)(qb * BM) - a.window);
         lo_first = max(0, shift + 1 + (int)wave_row0 - a.window);
         lo_last = max(0, shift + 1 + (int)wave_row0 + 31 - a.window);
     }
@@ -172,6 +212,54 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
         v_lds[p] = G::kTileBytes + G::v_off(row, ch);
     }
     u32x4 kst[kLoadsW], vst[kLoadsW];
+    // kVarlenPaged: the page numbers of the tile that is staged next, one per (wave, p), in scalar registers.  fetch_pages() reads them
+    // for a tile (only called with Lk >= 1); the entry index is clamped to the sequence's last live page, so no entry at or past
+    // ceil(Lk / page) is read -- which also makes a tile index past the last tile harmless.  `first_tile` (tile t0, in the prologue)
+    // under a window: the index is clamped to lo_wg's page too (lo_wg < Lk), so no entry of a page wholly below the window is read,
+    // and such a page gets a descriptor of no records; every later tile starts above lo_wg, so the loop does not carry lo_wg.
+    // A (wave, p) whose rows all lie at or past Lk gets a descriptor of no records whatever the number says.
+    [[maybe_unused]] int pg[kLoadsW];
+    // the pools at this K/V head's block of page 0, and the pool's elements per page
+    [[maybe_unused]] const uint16_t *k_pool = a.K, *v_pool = a.V;
+    if constexpr (kCache == kVarlenPaged) {
+        k_pool += ((size_t)hkv << a.lg_page) * D;
+        v_pool += ((size_t)hkv << a.lg_page) * D;
+    }
+    [[maybe_unused]] auto fetch_pages = [&](unsigned kv0, [[maybe_unused]] auto first_tile) {
+        if constexpr (kCache == kVarlenPaged) {
+            const int* __restrict__ tbl = a.table + (size_t)b * (unsigned)a.max_pages;
+            const unsigned last = ((unsigned)Lk - 1u) >> a.lg_page;
+#pragma unroll
+            for (int p = 0; p < kLoadsW; ++p) {
+                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;   // first row of the tile this wave loads with p
+                unsigned e = min((kv0 + wrow) >> a.lg_page, last);
+                if constexpr (kLogits && decltype(first_tile)::value) e = max(e, lo_wg >> a.lg_page);
+                pg[p] = __builtin_amdgcn_readfirstlane(tbl[e]);
+            }
+        }
+    };
+    [[maybe_unused]] auto stage_load_paged = [&](unsigned kv0, [[maybe_unused]] auto first_tile) {
+        if constexpr (kCache == kVarlenPaged) {
+            const unsigned page = 1u << a.lg_page;
+#pragma unroll
+            for (int p = 0; p < kLoadsW; ++p) {
+                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;
+                const unsigned first = (kv0 + wrow) & ~(page - 1u);            // first key of the page
+                bool ok = (unsigned)pg[p] < (unsigned)a.num_pages && first < (unsigned)Lk;
+                // a page wholly below the window: pg[p] is another page's
+                if constexpr (kLogits && decltype(first_tile)::value) ok = ok && first + page > lo_wg;
+                // the page's rows below Lk; a bad page number or a page outside the live range: no record, every load reads 0
+                const unsigned bytes = ok ? min(page, (unsigned)Lk - first) * (D * 2u) : 0u;
+                // 64-bit: pools beyond 4 GiB are normal; only the offset inside one page-head block is 32 bit
+                const size_t blk = (((size_t)(ok ? pg[p] : 0) * (unsigned)a.Hkv) << a.lg_page) * D;
+                const __amdgpu_buffer_rsrc_t pk = make_rsrc(k_pool + blk, bytes), pv = make_rsrc(v_pool + blk, bytes);
+                // reduced to the page: a product that wraps 32 bits keeps its low bits
+                const unsigned off = ((kv0 + s_row[p]) * (D * 2u) + s_col[p]) & (page * (D * 2u) - 1u);
+                kst[p] = buf_load16(pk, off);
+                vst[p] = buf_load16(pv, off);
+            }
+        }
+    };
     auto stage_load = [&](unsigned kv0) {
         if (kv0 + (unsigned)kBlockN <= (unsigned)Lk) {          // a whole tile (wave-uniform)
 #pragma unroll
@@ -192,6 +280,14 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
                     vst[p][w] = ok ? vv[w] : 0u;
                 }
             }
+        }
+    };
+    // kCache with a window: the rows of the first streamed tile below lo_wg go to LDS as zeros (workgroup-uniform test, tile t0 only)
+    [[maybe_unused]] auto stage_zero_below = [&](unsigned kv0) {
+        if (kv0 < lo_wg) {
+#pragma unroll
+            for (int p = 0; p < kLoadsW; ++p)
+                if (kv0 + s_row[p] < lo_wg) kst[p] = vst[p] = u32x4{0u, 0u, 0u, 0u};
         }
     };
     auto stage_write = [&](unsigned buf) {
@@ -233,7 +329,11 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
 
     // kLogits: the loop starts at tile t0 (t0 < ntiles whenever ntiles > 0: lo < c for a row with c >= 1), in buffer t0 & 1
     if (kLogits ? t0 < ntiles : ntiles > 0) {
-        stage_load(kLogits ? t0 * kBlockN : 0);
+        if constexpr (kCache == kVarlenPaged) fetch_pages(kLogits ? t0 * kBlockN : 0, std::true_type{});
+        if constexpr (kCache == kVarlenPaged) stage_load_paged(kLogits ? t0 * kBlockN : 0, std::true_type{});
+        else stage_load(kLogits ? t0 * kBlockN : 0);
+        if constexpr (kCache == kVarlenPaged) fetch_pages(((kLogits ? t0 : 0) + 1) * kBlockN, std::false_type{});
+        if constexpr (kCache != kVarlenPacked && kLogits) stage_zero_below(t0 * kBlockN);
         stage_write(kLogits ? t0 & 1u : 0);
     }
     __syncthreads();
@@ -241,7 +341,13 @@ void fa_fwd_varlen_kernel(std::conditional_t<kLogits, VarlenLogitArgs, VarlenArg
     for (int t = kLogits ? t0 : 0; t < ntiles; ++t) {
         const unsigned cur = t & 1u;
         const char* kbuf = smem + cur * G::kBufBytes;
-        if (t + 1 < ntiles) stage_load((t + 1) * kBlockN);
+        if constexpr (kCache == kVarlenPaged) {
+            if (t + 1 < ntiles) stage_load_paged((t + 1) * kBlockN, std::false_type{});
+        } else {
+            if (t + 1 < ntiles) stage_load((t + 1) * kBlockN);
+        }
+        // kVarlenPaged: the table read of the tile after next (clamped to the last live page) overlaps this tile's arithmetic
+        if constexpr (kCache == kVarlenPaged) fetch_pages((t + 2) * kBlockN, std::false_type{});
         // causal: tiles wholly past the limits of this wave's rows contribute nothing (wave-uniform)
         // kLogits: nor do tiles wholly below the lower limit of the wave's first row
         if ((!kCausal || t * kBlockN <= shift + (int)wave_row0 + 31) && (!kLogits || t * kBlockN + kBlockN > lo_first)) {
@@ -476,6 +582,33 @@ static inline hipError_t varlen_launch(const fa_varlen_desc* d, const Args& a, d
                           : launch(fa_fwd_varlen_kernel<T, 64, kF32, false, kLogits>, TileGeom<64>::kLdsBytes);
         return causal ? launch(fa_fwd_varlen_kernel<T, 128, kF32, true, kLogits>, TileGeom<128>::kLdsBytes)
                       : launch(fa_fwd_varlen_kernel<T, 128, kF32, false, kLogits>, TileGeom<128>::kLdsBytes);
+    });
+}
+
+// the one launch of fa_forward_varlen_kvcache: the cache instantiation of (types, d, causal, paged) with the unit's kLogits
+template <bool kLogits>
+static inline hipError_t varlen_cache_launch(const fa_varlen_kvcache_desc* d, const VarlenCacheArgs& a, dim3 grid)
+{
+    const bool causal = d->causal != 0, paged = d->block_table != nullptr;
+    return with_types(d->in_dtype, d->out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel, int lds) {
+            const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds);
+            if (attr != hipSuccess) return attr;
+            FA_LAUNCH(kernel, grid, dim3(64 * kVarlenWaves), (size_t)lds, static_cast<hipStream_t>(d->stream), a);
+            return launch_status();
+        };
+        constexpr bool kF32 = decltype(f32)::value;
+        auto by_mask = [&](auto dd, auto pp) {
+            constexpr int D = decltype(dd)::value;
+            constexpr int kCache = decltype(pp)::value ? kVarlenPaged : kVarlenContig;
+            return causal ? launch(fa_fwd_varlen_kernel<T, D, kF32, true, kLogits, kCache>, TileGeom<D>::kLdsBytes)
+                          : launch(fa_fwd_varlen_kernel<T, D, kF32, false, kLogits, kCache>, TileGeom<D>::kLdsBytes);
+        };
+        using D64 = std::integral_constant<int, 64>;
+        using D128 = std::integral_constant<int, 128>;
+        if (d->d == 64) return paged ? by_mask(D64{}, std::true_type{}) : by_mask(D64{}, std::false_type{});
+        return paged ? by_mask(D128{}, std::true_type{}) : by_mask(D128{}, std::false_type{});
     });
 }
 

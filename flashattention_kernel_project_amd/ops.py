@@ -517,6 +517,96 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
     return (out, lse) if return_lse else out
 
 
+def fa_forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, causal: bool = False,
+                              scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None, stream=None, lse=None,
+                              window: int = 0, softcap: float = 0.0, sinks=None):
+    """fa_forward_varlen with the keys taken from the KV cache (fa_forward_varlen_kvcache): chunked prefill, prefix caching and a window
+    across the cache boundary in one launch.  q (total_q, Hq, d) fp16/bf16 packed along the token axis and cut by cu_seqlens_q (int32
+    device [B+1]), exactly as in fa_forward_varlen; d in {64,128}; Hq = G * Hkv.
+    k_cache, v_cache: contiguous device tensors of q's dtype: [B,Hkv,Ncap,d], or with block_table (int32 contiguous device tensor
+    [B, max_pages]) the pools [num_pages,Hkv,page_size,d], page_size a power of two >= 16; key j of sequence b is then row
+    j % page_size of page block_table[b, j // page_size], and the capacity is max_pages * page_size.
+    cache_seqlens: int32 contiguous device tensor [B]: the keys of sequence b in the cache, the chunk's own tokens INCLUDED -- the
+    lengths after fa_kvcache_append* -- clamped to [0, capacity].  With Lk = cache_seqlens[b] and Lq from cu_seqlens_q, row i sees the
+    keys [lo_i, c_i): c_i = Lk, or max(0, Lk - Lq + 1 + i) with causal; lo_i = max(0, Lk - Lq + 1 + i - window) with a window, else 0.
+    So append the chunk, then call this with causal=True: row i sees the cached prefix and the chunk up to itself.
+    scale, out_dtype, return_lse, out, lse, window, softcap, sinks and the result: as in fa_forward_varlen, whose bits the call returns
+    on the same finite keys; the paged form returns the bits of the contiguous form.
+    Table, lengths and sinks are read on the device only: one kernel, no workspace, and a captured call follows all of them when they
+    are rewritten in place.  Table entries past a sequence's last live page are not read; a live entry outside [0, num_pages) reads
+    as a page of zeros; under a window the pages wholly below max(0, Lk - Lq + 1 - window) are not read and may be freed."""
+    import torch
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    if q.dim() != 3:
+        raise ValueError("q must be a packed tensor (total_q, Hq, d)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("q, k_cache, v_cache must all be fp16 or all bf16")
+    total_q, Hq, d = q.shape
+    paged = block_table is not None
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.shape[3] != d:
+        raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with q's d")
+    Hkv = k_cache.shape[1]
+    if d not in (64, 128):
+        raise ValueError("d must be 64 or 128")
+    if total_q <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or k_cache.numel() == 0:
+        raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
+    window = _window(window)
+    softcap = _softcap(softcap)
+    sink_ptr = _sinks_ptr(sinks, Hq, q.device)
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
+        raise ValueError("cu_seqlens_q must be an int32 tensor (the kernel reads 32-bit entries)")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
+        raise ValueError("cu_seqlens_q must be a contiguous 1-d tensor of B+1 entries")
+    B = cu_seqlens_q.numel() - 1
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,):
+        raise ValueError("cache_seqlens must be an int32 device tensor of B entries")
+    qt, qh = _packed_strides(q, "q")
+    if paged:
+        num_pages, page_size, Ncap = k_cache.shape[0], k_cache.shape[2], 0
+        if page_size < 16 or page_size & (page_size - 1):
+            raise ValueError("page_size must be a power of two >= 16")
+        table_ptr = _table_ptr(block_table, B)
+        max_pages = block_table.shape[1]
+        if max_pages <= 0:
+            raise ValueError("block_table must have at least one column")
+    else:
+        table_ptr, num_pages, page_size, max_pages, Ncap = None, 0, 0, 0, k_cache.shape[2]
+        if k_cache.shape[0] != B:
+            raise ValueError(f"k_cache holds {k_cache.shape[0]} sequences, cu_seqlens_q {B}")
+    for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    k_ptr, v_ptr = _dev_ptr(k_cache, "k_cache", (q.dtype,)), _dev_ptr(v_cache, "v_cache", (q.dtype,))
+    lens_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    out_dt = _out_dt(out_dtype, q.dtype)
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.shape != q.shape or out.dtype != out_dtype:
+        raise ValueError("out must be a device tensor of q's shape and of out_dtype")
+    if lse is not None:
+        if not isinstance(lse, torch.Tensor) or lse.shape != (Hq, total_q):
+            raise ValueError("lse must be a float32 tensor (Hq, total_q)")
+        _dev_ptr(lse, "lse", (torch.float32,))
+        return_lse = True
+    elif return_lse:
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device)
+    ot, oh = _packed_strides(out, "out")
+    desc = capi.VarlenKvcacheDesc(Q=q.data_ptr(), O=out.data_ptr(), lse=None if lse is None else lse.data_ptr(), K=k_ptr, V=v_ptr,
+                                  cu_seqlens_q=cu_seqlens_q.data_ptr(), seqlens_k=lens_ptr, block_table=table_ptr, B=B, Hkv=Hkv,
+                                  G=Hq // Hkv, d=d, total_q=total_q, Ncap=Ncap, num_pages=num_pages, page_size=page_size,
+                                  max_pages=max_pages, q_stride_t=qt, q_stride_h=qh, o_stride_t=ot, o_stride_h=oh,
+                                  scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)), in_dtype=_in_dt(q.dtype),
+                                  out_dtype=out_dt, sinks=sink_ptr, window=window, softcap=softcap, stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks)):
+        code = capi.lib().fa_forward_varlen_kvcache(desc)
+    capi.check("fa_forward_varlen_kvcache", code)
+    return (out, lse) if return_lse else out
+
+
 def fa_forward_kvcache_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len=None, cache_seqlens=None, block_table=None,
                                      k_scale=None, v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None,
                                      return_lse: bool = False, sinks=None, softcap: float = 0.0, stream=None):

@@ -36,6 +36,9 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, out_f32)
     # the same with a sliding window, sinks and a soft-cap (the decode _ex form's three arguments, in its order)
     o, lse = torch.ops.fa_mi355.forward_varlen_ex(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, sinks, softcap, out_f32)
+    # the same against the KV cache, contiguous or (with a block table) paged (ops.fa_forward_varlen_kvcache)
+    o, lse = torch.ops.fa_mi355.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, scale, causal, window,
+                                                       sinks, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -46,7 +49,7 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
-    .merge_states, .decode_shared_prefix, .forward_varlen and .forward_varlen_ex (idempotent)."""
+    .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent)."""
     global _registered
     if _registered:
         return
@@ -191,6 +194,19 @@ def register() -> None:
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, sinks, softcap, out_f32):
         return (q.new_empty(q.shape, dtype=out_dtype(q, out_f32)),
                 q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32))
+
+    def varlen_fake(q, *args):   # out_f32 is the schema's last argument
+        return (q.new_empty(q.shape, dtype=out_dtype(q, args[-1])), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32))
+
+    # forward_varlen_ex against the KV cache (ops.fa_forward_varlen_kvcache): `cache_seqlens` and `Tensor? block_table` take the place
+    # of cu_seqlens_k; the caches are [B,Hkv,Ncap,d], or with a block table the pools [num_pages,Hkv,page_size,d]
+    define("forward_varlen_kvcache",
+           "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor? block_table, float scale, "
+           "bool causal, int window, Tensor? sinks, float softcap, bool out_f32) -> (Tensor, Tensor)", (),
+           ops.fa_forward_varlen_kvcache, "-cccco",
+           lambda q, scale, causal, window, sinks, softcap, out_f32: dict(
+               causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+               softcap=softcap, sinks=opt(sinks)), varlen_fake)
 
     _registered = True
 

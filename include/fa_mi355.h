@@ -599,7 +599,8 @@ int fa_merge_states(const fa_merge_desc* desc);
  * aligned; a tensor whose last addressable byte, ((total-1)*stride_t + (H-1)*stride_h + d) * element bytes, does not fit 32 bits
  * (the kernel uses 32-bit buffer offsets); B*Hkv*G, or the block-slot count times Hkv*G, beyond 2^31 - 1 (the grid).
  * Not part of this entry: a window, sinks, a soft-cap, fp8, a paged K/V, rotary, max_seqlen hints, dropout.  The first three are
- * fa_forward_varlen_ex's, below, which takes this descriptor and a small structure of options.  NOT a reference entry point. */
+ * fa_forward_varlen_ex's, below, which takes this descriptor and a small structure of options; K/V in the KV cache, contiguous or
+ * paged, is fa_forward_varlen_kvcache's, further below.  NOT a reference entry point. */
 typedef struct fa_varlen_desc {
     size_t size;                    /* sizeof(fa_varlen_desc); any other value is refused */
     const void *Q, *K, *V;          /* device, 16-bit of in_dtype */
@@ -651,7 +652,8 @@ int fa_forward_varlen(const fa_varlen_desc* desc);
  * fa_forward_varlen rejects.
  * Not part of this entry: a window that crosses into a separately cached prefix (a prompt chunk merged with a decode over a cached
  * prefix through fa_merge_states cannot carry a window over the boundary), a window per sequence or per head, fp8 or paged K/V,
- * rotary.  NOT a reference entry point. */
+ * rotary.  The window across a cached prefix and the 16-bit paged K/V are fa_forward_varlen_kvcache's, below.  NOT a reference
+ * entry point. */
 typedef struct fa_varlen_opts {
     size_t size;          /* sizeof(fa_varlen_opts); any other value is refused */
     const float* sinks;   /* device, Hkv*G fp32 natural-log logits, or NULL */
@@ -659,6 +661,54 @@ typedef struct fa_varlen_opts {
     float softcap;        /* 0: off; > 0 and finite */
 } fa_varlen_opts;
 int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_opts* opts);
+
+/* The varlen prefill against the KV cache: fa_forward_varlen_ex with the K/V rows of sequence b taken from the cache the decode and
+ * append entries use -- a contiguous cache [B,Hkv,Ncap,d], or with `block_table` the page pools [num_pages,Hkv,page_size,d] -- in
+ * the place of packed K/V tensors.  One launch covers chunked prefill (a long prompt fed in pieces, each attending to what is
+ * cached plus itself: fa_kvcache_append* the chunk, then this call with causal = 1), prefix caching (only the uncached suffix of a
+ * prompt is computed, over cached pages) and a window that runs across the boundary between cached and new tokens.
+ * Semantics: exactly fa_forward_varlen_ex's, with one substitution.  Lq_b comes from cu_seqlens_q under the clamps above;
+ * Lk_b = clamp(seqlens_k[b], 0, Ncap), with Ncap = max_pages*page_size when paged, counts the keys of sequence b in the cache, the
+ * chunk's own tokens INCLUDED (the lengths after the append).  Key j of sequence b is cache row j: K[b][hkv][j], or when paged row
+ * j % page_size of page block_table[b*max_pages + j / page_size].  Row i sees [lo_i, c_i): c_i = Lk_b, or max(0, Lk_b - Lq_b + 1 + i)
+ * under causal; lo_i = max(0, Lk_b - Lq_b + 1 + i - W) under a window W, else 0.  So row i of an appended chunk sees the cached prefix
+ * and the chunk up to itself, and a window simply runs across the prefix boundary.  A row without a key returns O = 0 exactly and
+ * lse = -inf; with a sink, lse is the sink logit.  The lse layout, the scale rule, soft-cap before the masks and the sink counting
+ * once per row are fa_forward_varlen_ex's.  sinks, window, softcap: fa_varlen_opts' three, same meaning; NULL / 0 / 0: off, and the
+ * call runs the plain kernels.
+ * Bits: on the same finite keys and the same options the entry returns the bits of fa_forward_varlen / fa_forward_varlen_ex on the
+ * gathered packed K/V, for O and lse (tiles stay at absolute multiples of 64 keys from key 0), and the paged form returns the bits of
+ * the contiguous form.
+ * What is read -- the decode entries' contract: nothing on the host reads device data; the grid comes from (B, Hkv, G, total_q)
+ * only; there is no workspace; it is one kernel.  A captured call follows cu_seqlens_q, seqlens_k, block_table and sinks when they
+ * are rewritten in place.  Table entries at or past ceil(Lk_b / page_size) are never read; rows at or past Lk_b are never used.
+ * Under a window, for a 128-row query block: K/V rows below the lo of its first row are never used -- the rows of the first
+ * streamed 64-key tile that lie below that lo reach the arithmetic as zeros (a freed page may hold NaN, and 0 * NaN is NaN) -- and
+ * the table entry of a page wholly below that lo is not read.  Therefore pages wholly below lo_0 = max(0, Lk_b - Lq_b + 1 - W) may
+ * be freed.  A live table entry outside [0, num_pages) reads as a page of zeros.  Page addresses are 64 bit; only the offset inside
+ * one page-head block is 32 bit.
+ * hipErrorInvalidValue, before the device is touched: everything fa_forward_varlen_ex refuses for Q, O, lse, B, Hkv, G, d, the
+ * dtypes, window and softcap; a wrong `size`; a null K, V or seqlens_k, or a K or V that is not 16-byte aligned; contiguous:
+ * Ncap <= 0; paged: a page_size that is no power of two >= 16, num_pages <= 0, max_pages <= 0, or max_pages*page_size beyond
+ * 2^31 - 1; a capacity whose rows of one (sequence, head), Ncap*d*2 bytes, do not fit 32 bits.  Ncap, num_pages, page_size and
+ * max_pages of the other form are ignored.
+ * Not part of this entry: fp8 caches; split-KV for a short chunk on a very long cache (that stays with fa_kvcache_decode and its
+ * seqlens_q -- see README for the crossover); rotary (fa_kvcache_append_ex rotates on the way into the cache); a window per sequence
+ * or per head.  NOT a reference entry point. */
+typedef struct fa_varlen_kvcache_desc {
+    size_t size;                  /* sizeof(fa_varlen_kvcache_desc); any other value is refused */
+    const void* Q; void* O; float* lse;      /* as in fa_varlen_desc: Q,O packed (total_q, Hkv*G, d); lse [Hkv*G,total_q] or NULL */
+    const void *K, *V;            /* cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d]; 16 bit of in_dtype */
+    const int* cu_seqlens_q;      /* device, B+1 */
+    const int* seqlens_k;         /* device, B: keys of sequence b in the cache, the chunk's own tokens INCLUDED (i.e. after the append) */
+    const int* block_table;       /* device [B,max_pages] int32, or NULL: contiguous cache */
+    int B, Hkv, G, d, total_q, Ncap, num_pages, page_size, max_pages;
+    long long q_stride_t, q_stride_h, o_stride_t, o_stride_h;
+    float scale; int causal; int in_dtype, out_dtype;
+    const float* sinks; int window; float softcap;   /* fa_varlen_opts' three, same meaning; 0/NULL: off */
+    void* stream;
+} fa_varlen_kvcache_desc;
+int fa_forward_varlen_kvcache(const fa_varlen_kvcache_desc* desc);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
