@@ -162,6 +162,8 @@ def _signatures() -> dict:
         "fa_forward_varlen_ex": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
         # the same with K/V in the KV cache, contiguous or paged
         "fa_forward_varlen_kvcache": (i, [C.POINTER(VarlenKvcacheDesc)]),
+        # the same on an e4m3fn cache: the descriptor as it is, then k_scale, v_scale
+        "fa_forward_varlen_kvcache_fp8": (i, [C.POINTER(VarlenKvcacheDesc), vp, vp]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

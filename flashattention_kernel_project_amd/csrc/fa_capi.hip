@@ -315,6 +315,10 @@ FA_EXPORT int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_o
     return (int)fa::varlen_logits_dispatch(desc, opts);
 }
 FA_EXPORT int fa_forward_varlen_kvcache(const fa_varlen_kvcache_desc* desc) { return (int)fa::varlen_cache_dispatch(desc); }
+FA_EXPORT int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale)
+{
+    return (int)fa::varlen_cache_fp8_dispatch(desc, k_scale, v_scale);
+}
 
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)

@@ -201,6 +201,11 @@ hipError_t varlen_logits_dispatch(const ::fa_varlen_desc* desc, const ::fa_varle
 hipError_t varlen_cache_dispatch(const ::fa_varlen_kvcache_desc* desc);
 // ... what it hands a checked call with an option on to (fa_fwd_varlen_cache_logits.hip); args: the checked VarlenCacheArgs
 hipError_t varlen_cache_logits_launch(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid);
+// fa_forward_varlen_kvcache_fp8 (fa_fwd_varlen_cache_fp8.hip): the 16-bit entry's checks and the one launch on an e4m3fn cache;
+// k_scale, v_scale: device pointers to Hkv fp32 each, or null (1.0)
+hipError_t varlen_cache_fp8_dispatch(const ::fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale);
+// ... what it hands a checked call with an option on to (fa_fwd_varlen_cache_fp8_logits.hip); args: the checked VarlenCacheFp8Args
+hipError_t varlen_cache_fp8_logits_launch(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid);
 hipError_t debug_stage_dispatch(int stage, const void* A, const void* B, void* Out, int BH, int N, int D, float scale,
                                 int dtype, hipStream_t stream);
 hipError_t streaming16_dispatch(const void* Q, const void* K, const void* V, float* O,

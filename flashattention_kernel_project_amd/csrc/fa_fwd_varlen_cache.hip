@@ -7,8 +7,10 @@
 
 namespace fa {
 
-// fa_forward_varlen_kvcache's checks; on success the kernel arguments (the three options included) and the grid (host integers only)
-static hipError_t varlen_cache_check(const fa_varlen_kvcache_desc* d, VarlenCacheArgs& a, dim3& grid)
+// fa_forward_varlen_kvcache's checks; on success the kernel arguments (the three options included) and the grid (host integers only).
+// fa_forward_varlen_kvcache_fp8 (fa_fwd_varlen_cache_fp8.hip) runs them as they are: with one-byte elements the capacity bound
+// Ncap * d * 2 <= 2^32 is twice what the byte offsets need, and every limit derived from it holds unchanged
+hipError_t varlen_cache_check(const fa_varlen_kvcache_desc* d, VarlenCacheArgs& a, dim3& grid)
 {
     if (!d || d->size != sizeof(fa_varlen_kvcache_desc)) return hipErrorInvalidValue;
     if (!d->cu_seqlens_q || !d->seqlens_k) return hipErrorInvalidValue;

@@ -39,6 +39,14 @@
 //   * with a window the rows of tile t0 below the lo of the workgroup's first row reach LDS as zeros, and a page wholly below that
 //     lo gets a descriptor of no records: a freed page may hold NaN, and 0 * NaN in the PV MFMA is NaN.
 // Tiles stay at absolute multiples of 64 from key 0, so on finite keys the cache kernels return the packed kernels' bits.
+// kFp8 (fa_forward_varlen_kvcache_fp8; kCache with a VarlenCacheFp8Args): a K/V row is D e4m3fn bytes, and only that
+// is new -- everything it adds sits behind `if constexpr (kFp8)` or a constant that is the 16-bit one without it, and the 96 other
+// instantiations keep their code (profiles/varlen_cache_fp8.txt).  The decode side's scheme (fa_fwd_split_kernel.hpp): one 16-byte
+// load carries the two adjacent LDS chunks 2c and 2c + 1 of a row, so a thread issues half the loads per tile, keeps the raw bytes
+// across the tile's arithmetic and widens them (exactly) in stage_write(): the LDS image, and everything that reads it, is the 16-bit
+// kernels'.  One wave's loads for one p cover 16 rows at d = 64 and 8 at d = 128, aligned to as many -- still inside one page of
+// >= 16 keys.  The rows past Lk and the rows below lo_wg are zeroed as RAW bytes (code 0 is +0.0): a freed page may hold the NaN
+// codes 0x7F / 0xFF.  k_scale[hkv] joins the logit factor, with the FLT_MIN clamp on the product; v_scale[hkv] joins 1 / l.
 #pragma once
 #include "../../include/fa_mi355.h"
 #include "fa_tile.hpp"
@@ -88,6 +96,20 @@ struct VarlenCacheArgs : VarlenLogitArgs {
     int lg_page;            // log2 of the page size in keys (>= 4)
 };
 
+// What the fp8 cache instantiations take: K, V point at one e4m3fn byte per element (the strides stay in elements)
+struct VarlenCacheFp8Args : VarlenCacheArgs {
+    const float *k_scale, *v_scale;   // [Hkv] on the device, or nullptr (1.0)
+};
+
+// `elems` K/V elements past p.  With kFp8 p points at one byte per element; it keeps the type the argument structs give K and V, and
+// is only ever the base of a buffer descriptor.  (Without kFp8 this must stay `p + elems`: written as byte arithmetic for both, the
+// 16-bit cache kernels compile to another order of their scalar multiplies.)
+template <bool kFp8> __device__ __forceinline__ const uint16_t* varlen_kv_at(const uint16_t* p, size_t elems)
+{
+    if constexpr (kFp8) return reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(p) + elems);
+    else return p + elems;
+}
+
 // [s, e) of sequence b in a tensor of `total` rows: never outside it, never negative in length
 __device__ __forceinline__ void varlen_bounds(const int* __restrict__ cu, unsigned b, int total, int& s, int& e)
 {
@@ -104,11 +126,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t varlen_rsrc(const void* ptr, i
     return make_rsrc(static_cast<const char*>(ptr) + first * (long long)es, bytes);
 }
 
-template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false, int kCache = kVarlenPacked>
+template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false, int kCache = kVarlenPacked, bool kFp8 = false>
 __global__ __launch_bounds__(64 * kVarlenWaves, 2)
-void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCacheArgs, std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs>> a)
+void fa_fwd_varlen_kernel(std::conditional_t<kFp8, VarlenCacheFp8Args, std::conditional_t<kCache != kVarlenPacked, VarlenCacheArgs,
+                                             std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs>>> a)
 {
+    static_assert(!kFp8 || kCache != kVarlenPacked, "an fp8 K/V is a cache's");
     using G = TileGeom<D>;
+    constexpr unsigned kKvEs = kFp8 ? 1u : 2u;                          // bytes per K/V element
+    constexpr int kLdChunks = kFp8 ? G::kChunks / 2 : G::kChunks;      // 16-byte loads per K/V row
     constexpr int W = kVarlenWaves;
     constexpr unsigned BM = kVarlenRows;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -155,14 +181,14 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
     // kCache: sequence b's part of the cache starts b * Hkv * Ncap rows in (64 bit); a.k_sh = Ncap * D then selects the head.  Paged:
     // these two are not used, every (wave, p) makes its own
     const size_t kv_b = kCache == kVarlenContig ? (size_t)b * (size_t)a.Hkv * (size_t)a.k_sh : 0;
-    const __amdgpu_buffer_rsrc_t rk = varlen_rsrc(a.K + kv_b, sk, Lk, hkv, a.k_st, a.k_sh, D, 2u);
-    const __amdgpu_buffer_rsrc_t rv = varlen_rsrc(a.V + kv_b, sk, Lk, hkv, a.v_st, a.v_sh, D, 2u);
+    const __amdgpu_buffer_rsrc_t rk = varlen_rsrc(varlen_kv_at<kFp8>(a.K, kv_b), sk, Lk, hkv, a.k_st, a.k_sh, D, kKvEs);
+    const __amdgpu_buffer_rsrc_t rv = varlen_rsrc(varlen_kv_at<kFp8>(a.V, kv_b), sk, Lk, hkv, a.v_st, a.v_sh, D, kKvEs);
     // byte strides of a token row; every offset of an existing row fits 32 bits (checked on the host)
     const unsigned q_stb = (unsigned)a.q_st * 2u;
-    const unsigned k_stb = kCache != kVarlenPacked ? D * 2u : (unsigned)a.k_st * 2u;
-    const unsigned v_stb = kCache != kVarlenPacked ? D * 2u : (unsigned)a.v_st * 2u;
+    const unsigned k_stb = kCache != kVarlenPacked ? D * kKvEs : (unsigned)a.k_st * 2u;
+    const unsigned v_stb = kCache != kVarlenPacked ? D * kKvEs : (unsigned)a.v_st * 2u;
 
-    constexpr int kLoadsW = (kBlockN * G::kChunks) / (64 * W);
+    constexpr int kLoadsW = (kBlockN * kLdChunks) / (64 * W);
     const unsigned wave_row0 = qb * BM + wave * 32u;   // first query row of this wave, in the sequence
     const unsigned q_row = wave_row0 + r;
     const bool row_live = q_row < (unsigned)Lq;
@@ -171,7 +197,16 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
     // ---- Q^T fragments (B operand of S^T = K.Q^T), resident for the whole kernel ---------------
     // c = |scale|*log2(e) is applied to the fp32 scores; a negative scale flips Q's sign bits so that the row max of c*S is
     // always c*max(S).  Rows at or past Lq are zeros.
-    const float c = fabsf(a.scale_log2e);
+    // kFp8: the head's k_scale is part of the factor, and the clamp applies to the product (the host's clamp of scale_log2e alone does
+    // not survive a k_scale below 1: +-FLT_MIN * 0.5 must not meet a masked -inf as 0).  The product is vector arithmetic, so it goes
+    // back into a scalar register; v_scale is used at the end
+    float c = fabsf(a.scale_log2e);
+    [[maybe_unused]] float v_scale = 1.0f;
+    if constexpr (kFp8) {
+        const float k_scale = a.k_scale ? a.k_scale[hkv] : 1.0f;
+        if (a.v_scale) v_scale = a.v_scale[hkv];
+        c = to_sgpr(fmaxf(fabsf(a.scale_log2e * k_scale), 1.17549435e-38f));
+    }
     const unsigned q_flip = a.scale_log2e < 0.0f ? 0x80008000u : 0u;
     // kLogits: what a score is multiplied by on its way into the vote and the exponent (c, or 1 once the soft-cap has made the scores
     // final) and the cap's two constants, in scalar registers: computed from kernel arguments they would live in VGPRs through the
@@ -205,11 +240,13 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
 #pragma unroll
     for (int p = 0; p < kLoadsW; ++p) {
         const unsigned idx = tid + p * 64u * W;
-        const unsigned row = idx / G::kChunks, ch = idx % G::kChunks;
+        const unsigned row = idx / kLdChunks, ch = idx % kLdChunks;
         s_row[p] = row;
         s_col[p] = ch * 16u;
-        k_lds[p] = G::k_off(row, ch);
-        v_lds[p] = G::kTileBytes + G::v_off(row, ch);
+        // kFp8: the load holds the LDS chunks 2 ch and 2 ch + 1; the second one's offset is the first's with bit 4 flipped, in the K
+        // image (the swizzle XORs the chunk index) and in the V image (chunk & 3 is even)
+        k_lds[p] = G::k_off(row, kFp8 ? 2u * ch : ch);
+        v_lds[p] = G::kTileBytes + G::v_off(row, kFp8 ? 2u * ch : ch);
     }
     u32x4 kst[kLoadsW], vst[kLoadsW];
     // kVarlenPaged: the page numbers of the tile that is staged next, one per (wave, p), in scalar registers.  fetch_pages() reads them
@@ -222,8 +259,8 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
     // the pools at this K/V head's block of page 0, and the pool's elements per page
     [[maybe_unused]] const uint16_t *k_pool = a.K, *v_pool = a.V;
     if constexpr (kCache == kVarlenPaged) {
-        k_pool += ((size_t)hkv << a.lg_page) * D;
-        v_pool += ((size_t)hkv << a.lg_page) * D;
+        k_pool = varlen_kv_at<kFp8>(k_pool, ((size_t)hkv << a.lg_page) * D);
+        v_pool = varlen_kv_at<kFp8>(v_pool, ((size_t)hkv << a.lg_page) * D);
     }
     [[maybe_unused]] auto fetch_pages = [&](unsigned kv0, [[maybe_unused]] auto first_tile) {
         if constexpr (kCache == kVarlenPaged) {
@@ -231,7 +268,7 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
             const unsigned last = ((unsigned)Lk - 1u) >> a.lg_page;
 #pragma unroll
             for (int p = 0; p < kLoadsW; ++p) {
-                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;   // first row of the tile this wave loads with p
+                const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;   // first row of the tile this wave loads with p
                 unsigned e = min((kv0 + wrow) >> a.lg_page, last);
                 if constexpr (kLogits && decltype(first_tile)::value) e = max(e, lo_wg >> a.lg_page);
                 pg[p] = __builtin_amdgcn_readfirstlane(tbl[e]);
@@ -243,18 +280,19 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
             const unsigned page = 1u << a.lg_page;
 #pragma unroll
             for (int p = 0; p < kLoadsW; ++p) {
-                const unsigned wrow = (wave * 64u + p * 64u * W) / G::kChunks;
+                const unsigned wrow = (wave * 64u + p * 64u * W) / kLdChunks;
                 const unsigned first = (kv0 + wrow) & ~(page - 1u);            // first key of the page
                 bool ok = (unsigned)pg[p] < (unsigned)a.num_pages && first < (unsigned)Lk;
                 // a page wholly below the window: pg[p] is another page's
                 if constexpr (kLogits && decltype(first_tile)::value) ok = ok && first + page > lo_wg;
                 // the page's rows below Lk; a bad page number or a page outside the live range: no record, every load reads 0
-                const unsigned bytes = ok ? min(page, (unsigned)Lk - first) * (D * 2u) : 0u;
+                const unsigned bytes = ok ? min(page, (unsigned)Lk - first) * (D * kKvEs) : 0u;
                 // 64-bit: pools beyond 4 GiB are normal; only the offset inside one page-head block is 32 bit
                 const size_t blk = (((size_t)(ok ? pg[p] : 0) * (unsigned)a.Hkv) << a.lg_page) * D;
-                const __amdgpu_buffer_rsrc_t pk = make_rsrc(k_pool + blk, bytes), pv = make_rsrc(v_pool + blk, bytes);
+                const __amdgpu_buffer_rsrc_t pk = make_rsrc(varlen_kv_at<kFp8>(k_pool, blk), bytes),
+                                             pv = make_rsrc(varlen_kv_at<kFp8>(v_pool, blk), bytes);
                 // reduced to the page: a product that wraps 32 bits keeps its low bits
-                const unsigned off = ((kv0 + s_row[p]) * (D * 2u) + s_col[p]) & (page * (D * 2u) - 1u);
+                const unsigned off = ((kv0 + s_row[p]) * (D * kKvEs) + s_col[p]) & (page * (D * kKvEs) - 1u);
                 kst[p] = buf_load16(pk, off);
                 vst[p] = buf_load16(pv, off);
             }
@@ -293,6 +331,16 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
     auto stage_write = [&](unsigned buf) {
 #pragma unroll
         for (int p = 0; p < kLoadsW; ++p) {
+            if constexpr (kFp8) {   // the raw bytes become the two chunks of T (fp8x16_widen, exact)
+                u32x4 lo, hi;
+                fp8x16_widen<T>(kst[p], lo, hi);
+                lds_write16(smem, buf * G::kBufBytes + k_lds[p], lo);
+                lds_write16(smem, buf * G::kBufBytes + (k_lds[p] ^ 16u), hi);
+                fp8x16_widen<T>(vst[p], lo, hi);
+                lds_write16(smem, buf * G::kBufBytes + v_lds[p], lo);
+                lds_write16(smem, buf * G::kBufBytes + (v_lds[p] ^ 16u), hi);
+                continue;
+            }
             lds_write16(smem, buf * G::kBufBytes + k_lds[p], kst[p]);
             lds_write16(smem, buf * G::kBufBytes + v_lds[p], vst[p]);
         }
@@ -499,6 +547,7 @@ void fa_fwd_varlen_kernel(std::conditional_t<kCache != kVarlenPacked, VarlenCach
     }
     float inv = none ? 0.0f : 1.0f / l;
     if constexpr (kLogits) inv *= w_keys;
+    if constexpr (kFp8) inv *= v_scale;
     if (a.lse && h == 0)
         a.lse[(size_t)hq * (size_t)a.total_q + (size_t)sq + q_row] =
             (kLogits ? nolse : none) ? -INFINITY : (m_ref + __log2f(l)) * kVarlenLn2;
@@ -563,6 +612,10 @@ static inline hipError_t varlen_check(const fa_varlen_desc* d, VarlenArgs& a, di
     return hipSuccess;
 }
 
+// fa_forward_varlen_kvcache's checks (fa_fwd_varlen_cache.hip), which the fp8 entry runs too; on success the kernel arguments (the
+// three options included) and the grid (host integers only)
+hipError_t varlen_cache_check(const fa_varlen_kvcache_desc* d, VarlenCacheArgs& a, dim3& grid);
+
 // the one launch: the instantiation of (types, d, causal) with the entry's kLogits and argument structure
 template <bool kLogits, typename Args>
 static inline hipError_t varlen_launch(const fa_varlen_desc* d, const Args& a, dim3 grid)
@@ -586,8 +639,9 @@ static inline hipError_t varlen_launch(const fa_varlen_desc* d, const Args& a, d
 }
 
 // the one launch of fa_forward_varlen_kvcache: the cache instantiation of (types, d, causal, paged) with the unit's kLogits
-template <bool kLogits>
-static inline hipError_t varlen_cache_launch(const fa_varlen_kvcache_desc* d, const VarlenCacheArgs& a, dim3 grid)
+// (Args a VarlenCacheFp8Args: of fa_forward_varlen_kvcache_fp8, the fp8 one)
+template <bool kLogits, typename Args>
+static inline hipError_t varlen_cache_launch(const fa_varlen_kvcache_desc* d, const Args& a, dim3 grid)
 {
     const bool causal = d->causal != 0, paged = d->block_table != nullptr;
     return with_types(d->in_dtype, d->out_dtype, [&](auto t, auto f32) {
@@ -602,8 +656,9 @@ static inline hipError_t varlen_cache_launch(const fa_varlen_kvcache_desc* d, co
         auto by_mask = [&](auto dd, auto pp) {
             constexpr int D = decltype(dd)::value;
             constexpr int kCache = decltype(pp)::value ? kVarlenPaged : kVarlenContig;
-            return causal ? launch(fa_fwd_varlen_kernel<T, D, kF32, true, kLogits, kCache>, TileGeom<D>::kLdsBytes)
-                          : launch(fa_fwd_varlen_kernel<T, D, kF32, false, kLogits, kCache>, TileGeom<D>::kLdsBytes);
+            constexpr bool kFp8 = std::is_same_v<Args, VarlenCacheFp8Args>;
+            return causal ? launch(fa_fwd_varlen_kernel<T, D, kF32, true, kLogits, kCache, kFp8>, TileGeom<D>::kLdsBytes)
+                          : launch(fa_fwd_varlen_kernel<T, D, kF32, false, kLogits, kCache, kFp8>, TileGeom<D>::kLdsBytes);
         };
         using D64 = std::integral_constant<int, 64>;
         using D128 = std::integral_constant<int, 128>;

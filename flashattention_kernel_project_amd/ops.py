@@ -534,14 +534,43 @@ def fa_forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, 
     on the same finite keys; the paged form returns the bits of the contiguous form.
     Table, lengths and sinks are read on the device only: one kernel, no workspace, and a captured call follows all of them when they
     are rewritten in place.  Table entries past a sequence's last live page are not read; a live entry outside [0, num_pages) reads
-    as a page of zeros; under a window the pages wholly below max(0, Lk - Lq + 1 - window) are not read and may be freed."""
+    as a page of zeros; under a window the pages wholly below max(0, Lk - Lq + 1 - window) are not read and may be freed.
+    An fp8 cache is fa_forward_varlen_kvcache_fp8's."""
+    return _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out,
+                           stream, lse, window, softcap, sinks)
+
+
+def fa_forward_varlen_kvcache_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, k_scale=None, v_scale=None,
+                                  causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None,
+                                  stream=None, lse=None, window: int = 0, softcap: float = 0.0, sinks=None):
+    """fa_forward_varlen_kvcache against an fp8 cache (fa_forward_varlen_kvcache_fp8): the cache fa_kvcache_append_fp8 / _paged_fp8
+    write and the fp8 decode entries read.  k_cache, v_cache: contiguous torch.float8_e4m3fn device tensors (OCP e4m3fn; fnuz, e5m2
+    and 16-bit caches are refused), [B,Hkv,Ncap,d] or with block_table the pools [num_pages,Hkv,page_size,d].  q stays fp16/bf16: the
+    codes are widened to its type, exactly, on the way into LDS.  k_scale, v_scale: float32 device tensors [Hkv], finite and > 0, or
+    None for 1.0, read on the device only: the logits are scale * k_scale[hkv] * q.k8 and O = v_scale[hkv] * softmax.v8; the sinks take
+    neither scale, and lse is that of the scaled logits.  Everything else -- lengths, limits, options, what is read and what a captured
+    call follows -- as in fa_forward_varlen_kvcache, whose bits the call returns on the widened cache when both scales are None."""
+    return _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out,
+                           stream, lse, window, softcap, sinks, scales=(k_scale, v_scale))
+
+
+def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out, stream,
+                    lse, window, softcap, sinks, scales=None):
+    """The two varlen front ends against the KV cache: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one."""
     import torch
+    fp8 = scales is not None
+    name8 = "fa_forward_varlen_kvcache" + "_fp8" * fp8
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a tensor")
+    if fp8 and (k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn):   # judged first, as in _decode
+        raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_cache.dtype}, {v_cache.dtype})")
     if q.dim() != 3:
         raise ValueError("q must be a packed tensor (total_q, Hq, d)")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    if fp8:
+        if q.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("q must be fp16 or bf16")
+    elif q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("q, k_cache, v_cache must all be fp16 or all bf16")
     total_q, Hq, d = q.shape
     paged = block_table is not None
@@ -555,6 +584,7 @@ def fa_forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, 
     window = _window(window)
     softcap = _softcap(softcap)
     sink_ptr = _sinks_ptr(sinks, Hq, q.device)
+    ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], Hkv) if fp8 else (None, None)
     if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
         raise ValueError("cu_seqlens_q must be an int32 tensor (the kernel reads 32-bit entries)")
     if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
@@ -578,7 +608,8 @@ def fa_forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, 
     for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
-    k_ptr, v_ptr = _dev_ptr(k_cache, "k_cache", (q.dtype,)), _dev_ptr(v_cache, "v_cache", (q.dtype,))
+    cache_dts = (torch.float8_e4m3fn if fp8 else q.dtype,)
+    k_ptr, v_ptr = _dev_ptr(k_cache, "k_cache", cache_dts), _dev_ptr(v_cache, "v_cache", cache_dts)
     lens_ptr = _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
     if out_dtype is None:
         out_dtype = torch.float32 if out is None else out.dtype
@@ -601,9 +632,12 @@ def fa_forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, 
                                   max_pages=max_pages, q_stride_t=qt, q_stride_h=qh, o_stride_t=ot, o_stride_h=oh,
                                   scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)), in_dtype=_in_dt(q.dtype),
                                   out_dtype=out_dt, sinks=sink_ptr, window=window, softcap=softcap, stream=_stream_ptr(stream))
-    with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks)):
-        code = capi.lib().fa_forward_varlen_kvcache(desc)
-    capi.check("fa_forward_varlen_kvcache", code)
+    with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, *(scales or ()))):
+        if fp8:
+            code = capi.lib().fa_forward_varlen_kvcache_fp8(desc, ks_ptr, vs_ptr)
+        else:
+            code = capi.lib().fa_forward_varlen_kvcache(desc)
+    capi.check(name8, code)
     return (out, lse) if return_lse else out
 
 

@@ -39,6 +39,9 @@ eager fallback.  Registered on first use:
     # the same against the KV cache, contiguous or (with a block table) paged (ops.fa_forward_varlen_kvcache)
     o, lse = torch.ops.fa_mi355.forward_varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, scale, causal, window,
                                                        sinks, softcap, out_f32)
+    # ... and against an fp8 (e4m3fn) cache with per-head scales (ops.fa_forward_varlen_kvcache_fp8)
+    o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_fp8(q, k_cache8, v_cache8, cu_seqlens_q, cache_seqlens, block_table, k_scale,
+                                                           v_scale, scale, causal, window, sinks, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -49,7 +52,8 @@ _registered = False
 
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
-    .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent)."""
+    .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
+    .forward_varlen_kvcache_fp8."""
     global _registered
     if _registered:
         return
@@ -204,6 +208,15 @@ def register() -> None:
            "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor? block_table, float scale, "
            "bool causal, int window, Tensor? sinks, float softcap, bool out_f32) -> (Tensor, Tensor)", (),
            ops.fa_forward_varlen_kvcache, "-cccco",
+           lambda q, scale, causal, window, sinks, softcap, out_f32: dict(
+               causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+               softcap=softcap, sinks=opt(sinks)), varlen_fake)
+
+    # the same on an fp8 cache (ops.fa_forward_varlen_kvcache_fp8): `Tensor? k_scale, Tensor? v_scale` follow `block_table`
+    define("forward_varlen_kvcache_fp8",
+           "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor? block_table, Tensor? k_scale, "
+           "Tensor? v_scale, float scale, bool causal, int window, Tensor? sinks, float softcap, bool out_f32) -> (Tensor, Tensor)", (),
+           ops.fa_forward_varlen_kvcache_fp8, "-ccccooo",
            lambda q, scale, causal, window, sinks, softcap, out_f32: dict(
                causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
                softcap=softcap, sinks=opt(sinks)), varlen_fake)

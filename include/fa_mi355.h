@@ -694,7 +694,8 @@ int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_opts* opts)
  * max_pages of the other form are ignored.
  * Not part of this entry: fp8 caches; split-KV for a short chunk on a very long cache (that stays with fa_kvcache_decode and its
  * seqlens_q -- see README for the crossover); rotary (fa_kvcache_append_ex rotates on the way into the cache); a window per sequence
- * or per head.  NOT a reference entry point. */
+ * or per head.  (An fp8 cache has an entry of its own on this descriptor: fa_forward_varlen_kvcache_fp8, below.)  NOT a reference
+ * entry point. */
 typedef struct fa_varlen_kvcache_desc {
     size_t size;                  /* sizeof(fa_varlen_kvcache_desc); any other value is refused */
     const void* Q; void* O; float* lse;      /* as in fa_varlen_desc: Q,O packed (total_q, Hkv*G, d); lse [Hkv*G,total_q] or NULL */
@@ -709,6 +710,31 @@ typedef struct fa_varlen_kvcache_desc {
     void* stream;
 } fa_varlen_kvcache_desc;
 int fa_forward_varlen_kvcache(const fa_varlen_kvcache_desc* desc);
+
+/* fa_forward_varlen_kvcache on an fp8 cache -- the cache fa_kvcache_append_fp8 / _paged_fp8 write and fa_forward_kvcache_fp8 /
+ * _paged_fp8 read -- so that a stack that keeps its cache in fp8 runs chunked prefill and prefix caching without widening it first.
+ * The descriptor is fa_varlen_kvcache_desc as it is, and every field means what it means above, with these differences:
+ *   K, V      one OCP e4m3fn byte per element: [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d].
+ *   in_dtype  remains the type of Q: the codes are widened to it (exactly: every e4m3fn value is a normal fp16 and bf16 number)
+ *             on the way into LDS, and P is packed to it.
+ *   k_scale, v_scale   device pointers to Hkv fp32 each, or NULL for 1.0.  Read on the device only: a captured call follows scales
+ *             that are rewritten in place.  They must be finite and > 0 (the caller's contract, as in the fp8 decode entries).
+ * Semantics: fa_forward_varlen_kvcache's with the decode side's fp8 rule.  The logits are scale * k_scale[hkv] * q.k8; the factor
+ * that goes to the device is clamped to +-FLT_MIN AFTER the product with k_scale, so scale = 0 still gives uniform weights under
+ * every mask.  Soft-cap, masks and sinks follow after that; the sinks take neither scale.  O = v_scale[hkv] * softmax.v8, and lse is
+ * that of the scaled logits (v_scale is no part of it).  With NULL scales the entry returns the bits of fa_forward_varlen_kvcache on
+ * the widened cache, for O and lse, and the paged form returns the bits of the contiguous form.
+ * Unchanged: the lengths include the chunk; the causal and window limits; rows without a key; table entries that are never read;
+ * pages wholly below lo_0 may be freed; a live table entry outside [0, num_pages) reads as a page of zeros; nothing on the host
+ * reads device data; one kernel; no workspace; the grid from (B, Hkv, G, total_q).  A freed page may hold the NaN codes 0x7F / 0xFF:
+ * the rows at or past Lk_b, the rows of the first streamed tile below the lo of a query block's first row, and the pages wholly
+ * below it reach the arithmetic as zeros because their RAW bytes are zeroed (or never loaded) before the widening.
+ * hipErrorInvalidValue, before the device is touched: exactly what fa_forward_varlen_kvcache refuses, K and V that are not 16-byte
+ * aligned included.  The capacity bound stays Ncap*d*2 bytes in 32 bits although a row is d bytes here: every 32-bit limit derived
+ * from it (the byte offsets, |Lk - Lq + 1 + i| <= 2^26, the window clamp total_q + Ncap <= 2^27) then holds unchanged.
+ * Not part of this entry: split-KV for a short chunk on a very long cache (that stays with fa_kvcache_decode and its seqlens_q);
+ * per-token or per-page scales; an fp8 Q or fp8 MFMAs; rotary (the append rotates).  NOT a reference entry point. */
+int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
