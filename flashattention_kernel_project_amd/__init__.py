@@ -25,6 +25,8 @@ from .ops import (  # noqa: F401
     fa_kvcache_append_paged,
     fa_kvcache_append_fp8,
     fa_kvcache_append_paged_fp8,
+    fa_kvcache_append_varlen,
+    fa_kvcache_append_varlen_fp8,
     fa_merge_states,
     fa_forward_kvcache_shared_prefix,
     fa_forward_varlen,
@@ -45,6 +47,7 @@ __all__ = [
     "kvcache_window_workspace_bytes", "kvcache_paged_window_workspace_bytes",
     "fa_forward_kvcache_fp8", "fa_forward_kvcache_paged_fp8", "quantize_kv_fp8",
     "fa_kvcache_append", "fa_kvcache_append_paged", "fa_kvcache_append_fp8", "fa_kvcache_append_paged_fp8",
+    "fa_kvcache_append_varlen", "fa_kvcache_append_varlen_fp8",
     "fa_merge_states", "fa_forward_kvcache_shared_prefix", "fa_forward_varlen", "fa_forward_varlen_kvcache",
     "fa_forward_varlen_kvcache_fp8",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",

@@ -50,6 +50,24 @@ class KvAppendDesc(C.Structure):
             self.size = C.sizeof(KvAppendDesc)
 
 
+class KvAppendVarlenDesc(C.Structure):
+    """fa_kvappend_varlen_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Knew", C.c_void_p), ("Vnew", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p),
+                ("cu_seqlens_new", C.c_void_p), ("seqlens_k", C.c_void_p), ("seqlens_out", C.c_void_p), ("block_table", C.c_void_p),
+                ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("Q", C.c_void_p), ("Qout", C.c_void_p), ("rope_cos", C.c_void_p),
+                ("rope_sin", C.c_void_p), ("kv_dtype", C.c_int), ("B", C.c_int), ("Hkv", C.c_int), ("d", C.c_int), ("total_new", C.c_int),
+                ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int), ("max_pages", C.c_int), ("G", C.c_int),
+                ("rot_dim", C.c_int), ("max_pos", C.c_int), ("interleaved", C.c_int), ("dtype", C.c_int),
+                ("k_stride_t", C.c_longlong), ("k_stride_h", C.c_longlong), ("v_stride_t", C.c_longlong), ("v_stride_h", C.c_longlong),
+                ("q_stride_t", C.c_longlong), ("q_stride_h", C.c_longlong), ("qo_stride_t", C.c_longlong), ("qo_stride_h", C.c_longlong),
+                ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvAppendVarlenDesc)
+
+
 def new_desc(cls):
     """A zeroed descriptor with its `size` set, to be filled by fill(desc, field=value, ...).  The pair is the per-call path of
     ops._decode and ops._append: Structure's own keyword initialiser costs half of what cls(**fields) costs through the Python-level
@@ -156,6 +174,8 @@ def _signatures() -> dict:
         "fa_kvcache_decode": (i, [C.POINTER(KvDecodeDesc)]),
         # the descriptor form of the eight append entries, with seqlens_new
         "fa_kvcache_append_ex": (i, [C.POINTER(KvAppendDesc)]),
+        # the same eight forms on token-packed (cu_seqlens) sources read through their strides
+        "fa_kvcache_append_varlen": (i, [C.POINTER(KvAppendVarlenDesc)]),
         "fa_merge_states": (i, [C.POINTER(MergeDesc)]),
         "fa_forward_varlen": (i, [C.POINTER(VarlenDesc)]),
         # the same with a window, a soft-cap and sinks; a null opts is fa_forward_varlen

@@ -307,6 +307,8 @@ FA_EXPORT int fa_kvcache_append_ex(const fa_kvappend_desc* desc)
                                              rope ? desc->max_pos : 0, rope ? desc->interleaved : 0, rope, desc->seqlens_new});
 }
 
+FA_EXPORT int fa_kvcache_append_varlen(const fa_kvappend_varlen_desc* desc) { return (int)fa::kvcache_append_varlen(desc); }
+
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 
 FA_EXPORT int fa_forward_varlen(const fa_varlen_desc* desc) { return (int)fa::varlen_dispatch(desc); }

@@ -12,6 +12,7 @@ struct fa_merge_desc;   // include/fa_mi355.h
 struct fa_varlen_desc;
 struct fa_varlen_opts;
 struct fa_varlen_kvcache_desc;
+struct fa_kvappend_varlen_desc;
 
 namespace fa {
 
@@ -191,6 +192,8 @@ hipError_t kvcache_append_rope_check(const KvAppendArgs& a, unsigned long long& 
 hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
 // the lengths kernel behind either append kernel (fa_kvcache_append.hip); nothing is launched without a seqlens_out
 hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
+// fa_kvcache_append_varlen (fa_kvcache_append_varlen.hip): the checks and the one or two launches; the descriptor is the public one, as it is
+hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

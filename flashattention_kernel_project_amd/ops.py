@@ -802,17 +802,7 @@ def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
             raise ValueError("q, q_out and rotary_sin are arguments of the rotary append: they need rotary_cos")
         return None
     B, Hkv, Nnew, d = k_new.shape
-    for name, t in (("rotary_cos", cos), ("rotary_sin", sin)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be a float32 device tensor of shape [max_pos, rot_dim/2]")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    if sin.shape != cos.shape:
-        raise ValueError(f"rotary_cos and rotary_sin must have one shape (got {tuple(cos.shape)}, {tuple(sin.shape)})")
-    max_pos, rot_dim = cos.shape[0], 2 * cos.shape[1]
-    if max_pos < 1 or rot_dim % 16 != 0 or not 16 <= rot_dim <= d:
-        raise ValueError(f"rotary_cos must be [max_pos >= 1, rot_dim/2] with rot_dim a multiple of 16 in [16, d = {d}] (got "
-                         f"{tuple(cos.shape)})")
+    max_pos, rot_dim = _rope_tables(cos, sin, d)
     G = 1
     if q is None:
         if q_out is not None:
@@ -827,6 +817,23 @@ def _rope_shapes(k_new, q, q_out, cos, sin, interleaved):
         elif not isinstance(q_out, torch.Tensor) or q_out.shape != q.shape or q_out.dtype != q.dtype:
             raise ValueError("q_out must have q's shape and dtype")
     return q, q_out, cos, sin, (G, rot_dim, max_pos, 1 if interleaved else 0)
+
+
+def _rope_tables(cos, sin, d):
+    """rotary_cos, rotary_sin of an append against rows of d elements, by shape and dtype alone -> (max_pos, rot_dim)"""
+    import torch
+    for name, t in (("rotary_cos", cos), ("rotary_sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 device tensor of shape [max_pos, rot_dim/2]")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if sin.shape != cos.shape:
+        raise ValueError(f"rotary_cos and rotary_sin must have one shape (got {tuple(cos.shape)}, {tuple(sin.shape)})")
+    max_pos, rot_dim = cos.shape[0], 2 * cos.shape[1]
+    if max_pos < 1 or rot_dim % 16 != 0 or not 16 <= rot_dim <= d:
+        raise ValueError(f"rotary_cos must be [max_pos >= 1, rot_dim/2] with rot_dim a multiple of 16 in [16, d = {d}] (got "
+                         f"{tuple(cos.shape)})")
+    return max_pos, rot_dim
 
 
 def _scale_ptrs(k_scale, v_scale, Hkv):
@@ -909,6 +916,135 @@ def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_sca
     as there (fa_kvcache_append_paged_fp8_rope); seqlens_new as in fa_kvcache_append."""
     _append(k_new, v_new, k_pool, v_pool, "k_pool, v_pool", cache_seqlens, seqlens_out, stream,
             (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), seqlens_new, paged=True, block_table=block_table, scales=(k_scale, v_scale))
+
+
+def fa_kvcache_append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None,
+                             stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
+    """The append of a token-packed batch (fa_kvcache_append_varlen): the write half of fa_forward_varlen_kvcache.  k_new, v_new
+    (total_new, Hkv, d) fp16 or bf16 device tensors of ONE dtype, d in {64,128}, taken as they lie: any token and head strides with a
+    contiguous last dimension (strides multiples of 8 elements, 16-byte aligned storage), so the K and V views of a fused
+    (total_new, Hq + 2*Hkv, d) projection buffer go in without a copy.
+    cu_seqlens_new: int32 contiguous device tensor [B+1], read on the device only; sequence b owns the rows [cu[b], cu[b+1]), clamped
+    into the tensor as in fa_forward_varlen.  Rows of no sequence are never used.
+    k_cache, v_cache: [B,Hkv,Ncap,d] of k_new's dtype, or with block_table (int32 [B, max_pages]) the pools
+    [num_pages,Hkv,page_size,d].  Token i of sequence b goes to p = L_b + i, L_b = cache_seqlens[b] clamped to [0, capacity] (None:
+    every sequence EMPTY); the drops at the capacity and at a bad table entry are fa_kvcache_append's.
+    seqlens_out: int32 [B] that receives min(L_b + m_b, capacity), or None; cache_seqlens itself or disjoint from it; it must not
+    overlap cu_seqlens_new.
+    rotary_cos, rotary_sin, rotary_interleaved: as in fa_kvcache_append.  q: packed (total_new, Hq, d) of k_new's dtype with its own
+    strides, rotated at its token's position into q_out (same shape and dtype, its own strides, not overlapping q) or, with q_out=None,
+    in place; q_out rows of no sequence are not written.
+    Every kept byte is what fa_kvcache_append(seqlens_new=m) writes from the padded [B,Hkv,max m,d] copy of the same rows.  Nothing is
+    read on the host and there is no workspace: append_varlen(seqlens_out=lens) then
+    fa_forward_varlen_kvcache(q, ..., cu_seqlens_new, lens), captured once, serves every step of the same total_new."""
+    _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+
+
+def fa_kvcache_append_varlen_fp8(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None,
+                                 k_scale=None, v_scale=None, stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None,
+                                 rotary_interleaved=False) -> None:
+    """fa_kvcache_append_varlen into an fp8 cache: k_cache, v_cache (or the pools) torch.float8_e4m3fn, k_scale, v_scale float32 [Hkv]
+    or None (1.0); codes and scales as in fa_kvcache_append_fp8, everything else as in fa_kvcache_append_varlen."""
+    _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), scales=(k_scale, v_scale))
+
+
+def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream, rope, scales=None):
+    """The two packed append front ends: scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one; rope is
+    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved).  Shapes and dtypes are judged before anything needs a device."""
+    import torch
+    fp8 = scales is not None
+    paged = block_table is not None
+    for name, t in (("k_new", k_new), ("v_new", v_new), ("k_cache", k_dst), ("v_cache", v_dst)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    if fp8 and (k_dst.dtype != torch.float8_e4m3fn or v_dst.dtype != torch.float8_e4m3fn):   # judged first, as in the other front ends
+        raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_dst.dtype}, {v_dst.dtype})")
+    if k_new.dim() != 3 or v_new.shape != k_new.shape:
+        raise ValueError("k_new, v_new must both be packed tensors (total_new, Hkv, d)")
+    total, Hkv, d = k_new.shape
+    dts = (torch.float16, torch.bfloat16)
+    if k_new.dtype not in dts or v_new.dtype != k_new.dtype:
+        raise ValueError("k_new, v_new must both be fp16 or both bf16")
+    if d not in (64, 128) or total <= 0 or Hkv <= 0:
+        raise ValueError("d must be 64 or 128, and k_new must not be empty")
+    if k_dst.dim() != 4 or v_dst.shape != k_dst.shape or k_dst.shape[1] != Hkv or k_dst.shape[3] != d or k_dst.numel() == 0:
+        raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with k_new's "
+                         "Hkv and d")
+    if not fp8 and (k_dst.dtype != k_new.dtype or v_dst.dtype != k_new.dtype):
+        raise ValueError(f"k_cache, v_cache must have the dtype of k_new ({k_new.dtype}; got {k_dst.dtype}, {v_dst.dtype}); an fp8 cache "
+                         "goes through fa_kvcache_append_varlen_fp8")
+    if not isinstance(cu_seqlens_new, torch.Tensor) or cu_seqlens_new.dtype != torch.int32:
+        raise ValueError("cu_seqlens_new must be an int32 tensor (the kernel reads 32-bit entries)")
+    if cu_seqlens_new.dim() != 1 or cu_seqlens_new.numel() < 2 or not cu_seqlens_new.is_contiguous():
+        raise ValueError("cu_seqlens_new must be a contiguous 1-d tensor of B+1 entries")
+    B = cu_seqlens_new.numel() - 1
+    if paged:
+        num_pages, page_size, Ncap = k_dst.shape[0], k_dst.shape[2], 0
+        if page_size < 16 or page_size & (page_size - 1):
+            raise ValueError("page_size must be a power of two >= 16")
+        if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] <= 0:
+            raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
+        max_pages = block_table.shape[1]
+    else:
+        num_pages, page_size, max_pages, Ncap = 0, 0, 0, k_dst.shape[2]
+        if k_dst.shape[0] != B:
+            raise ValueError(f"k_cache holds {k_dst.shape[0]} sequences, cu_seqlens_new {B}")
+    for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.shape != (B,)):
+            raise ValueError(f"{name} must be an int32 device tensor of shape [B] = [{B}]")
+    (kt, kh), (vt, vh) = _packed_strides(k_new, "k_new"), _packed_strides(v_new, "v_new")
+    ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], Hkv) if fp8 else (None, None)
+    q, q_out, cos, sin, interleaved = rope
+    rope_fields, rope_tensors = {}, ()
+    if cos is None:
+        if q is not None or q_out is not None or sin is not None:
+            raise ValueError("q, q_out and rotary_sin are arguments of the rotary append: they need rotary_cos")
+    else:
+        max_pos, rot_dim = _rope_tables(cos, sin, d)
+        interleaved = 1 if interleaved else 0
+        G = 1
+        if q is None:
+            if q_out is not None:
+                raise ValueError("q_out needs q")
+        else:
+            if not isinstance(q, torch.Tensor) or q.dim() != 3 or q.shape[0] != total or q.shape[2] != d or q.shape[1] % Hkv != 0 \
+                    or q.shape[1] == 0 or q.dtype != k_new.dtype:
+                raise ValueError(f"q must be packed (total_new, Hq, d) = ({total}, Hq, {d}) with Hq a multiple of Hkv = {Hkv}, of k_new's "
+                                 "dtype")
+            G = q.shape[1] // Hkv
+            if q_out is None:
+                q_out = q   # in place
+            elif not isinstance(q_out, torch.Tensor) or q_out.shape != q.shape or q_out.dtype != q.dtype:
+                raise ValueError("q_out must have q's shape and dtype")
+            (qt, qh), (qot, qoh) = _packed_strides(q, "q"), _packed_strides(q_out, "q_out")
+            for name, t in (("q", q), ("q_out", q_out)):
+                if not t.is_cuda:
+                    raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+            rope_fields.update(Q=q.data_ptr(), Qout=q_out.data_ptr(), q_stride_t=qt, q_stride_h=qh, qo_stride_t=qot, qo_stride_h=qoh)
+        rope_fields.update(rope_cos=_dev_ptr(cos, "rotary_cos", (torch.float32,)), rope_sin=_dev_ptr(sin, "rotary_sin", (torch.float32,)),
+                           G=G, rot_dim=rot_dim, max_pos=max_pos, interleaved=interleaved)
+        rope_tensors = (q, q_out, cos, sin)
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    cu_ptr = _dev_ptr(cu_seqlens_new, "cu_seqlens_new", (torch.int32,))
+    table_ptr = _table_ptr(block_table, B) if paged else None
+    cache_dts = (torch.float8_e4m3fn,) if fp8 else dts
+    k_ptr, v_ptr = _dev_ptr(k_dst, "k_cache", cache_dts), _dev_ptr(v_dst, "v_cache", cache_dts)
+    len_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    out_ptr = None if seqlens_out is None else _dev_ptr(seqlens_out, "seqlens_out", (torch.int32,))
+    desc = capi.new_desc(capi.KvAppendVarlenDesc)
+    capi.fill(
+        desc, Knew=k_new.data_ptr(), Vnew=v_new.data_ptr(), K=k_ptr, V=v_ptr, cu_seqlens_new=cu_ptr, seqlens_k=len_ptr, seqlens_out=out_ptr,
+        block_table=table_ptr, k_scale=ks_ptr, v_scale=vs_ptr, kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, d=d,
+        total_new=total, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, dtype=_in_dt(k_new.dtype),
+        k_stride_t=kt, k_stride_h=kh, v_stride_t=vt, v_stride_h=vh, stream=_stream_ptr(stream), **rope_fields)
+    with torch.cuda.device(_one_device(k_new, v_new, k_dst, v_dst, cu_seqlens_new, block_table, *(scales or ()), cache_seqlens, seqlens_out,
+                                       *rope_tensors)):
+        code = capi.lib().fa_kvcache_append_varlen(desc)
+    capi.check("fa_kvcache_append_varlen", code)
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

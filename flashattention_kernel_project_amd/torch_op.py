@@ -27,6 +27,11 @@ eager fallback.  Registered on first use:
     #   "_ragged" ... cache_seqlens, seqlens_out, seqlens_new, q, rotary_cos, rotary_sin, interleaved)
     torch.ops.fa_mi355.append_paged_rope(k_new, v_new, k_pool, v_pool, block_table, cache_seqlens, seqlens_out, q, rotary_cos, rotary_sin,
                                          interleaved)
+    # the append of a token-packed batch (ops.fa_kvcache_append_varlen, _fp8): packed sources taken as they lie, q_out None = in place
+    torch.ops.fa_mi355.append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, q, q_out,
+                                     rotary_cos, rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_varlen_fp8(k_new, v_new, k_cache8, v_cache8, cu_seqlens_new, cache_seqlens, seqlens_out, block_table,
+                                         k_scale, v_scale, q, q_out, rotary_cos, rotary_sin, interleaved)
     # the merge of R attention states, stacked [R,B,Hq,Nq,d] and [R,B,Hq,Nq] (ops.fa_merge_states), and shared-prefix decode on a
     # contiguous 16-bit suffix (ops.fa_forward_kvcache_shared_prefix)
     o, lse = torch.ops.fa_mi355.merge_states(outs, lses, out_f32)
@@ -53,7 +58,7 @@ _registered = False
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
-    .forward_varlen_kvcache_fp8."""
+    .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8."""
     global _registered
     if _registered:
         return
@@ -145,6 +150,25 @@ def register() -> None:
     for layout, lead, caches, fn, how in APPEND_LAYOUTS:
         for form, tail, more, kw in APPEND_FORMS:
             define("append" + layout + form, lead + tail, caches + more, fn, how, kw, lambda *args: None)
+
+    # The append of a token-packed batch (ops.fa_kvcache_append_varlen, _fp8): k_new, v_new (total_new,Hkv,d) and q, q_out
+    # (total_new,Hq,d) go in as they lie -- views of a fused projection buffer are the point -- and the caches are [B,Hkv,Ncap,d] or,
+    # with a block table, pools.  q_out None rotates q in place; all of q, q_out and the tables None: no rotation.
+    def varlen_append_kw(k_new, cache_seqlens, seqlens_out, block_table, *rest):
+        *scales, q, q_out, rotary_cos, rotary_sin, interleaved = rest
+        kw = dict(cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), stream=stream(k_new), q=q,
+                  q_out=q_out, rotary_cos=opt(rotary_cos), rotary_sin=opt(rotary_sin), rotary_interleaved=interleaved)
+        if scales:
+            kw.update(k_scale=opt(scales[0]), v_scale=opt(scales[1]))
+        return kw
+
+    VARLEN_APPEND = "(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_new, Tensor? cache_seqlens, " \
+                    "Tensor(c!)? seqlens_out, Tensor? block_table, "
+    VARLEN_APPEND_TAIL = "Tensor(d!)? q, Tensor(e!)? q_out, Tensor? rotary_cos, Tensor? rotary_sin, bool interleaved) -> ()"
+    for name, mid, fn in (("append_varlen", "", ops.fa_kvcache_append_varlen),
+                          ("append_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_append_varlen_fp8)):
+        define(name, VARLEN_APPEND + mid + VARLEN_APPEND_TAIL, ("k_cache", "v_cache", "seqlens_out", "q", "q_out"), fn, "----c",
+               varlen_append_kw, lambda *args: None)
 
     # The merge of attention states over key ranges (ops.fa_merge_states) on stacked parts, and shared-prefix decode on a contiguous
     # 16-bit suffix (ops.fa_forward_kvcache_shared_prefix; the paged and fp8 forms are the front end's).

@@ -330,7 +330,8 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  *           accepted and means seqlens_q == NULL; every other wrong size is refused.
  * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the dense prefill entries (fa_forward, fa_forward_ex;
  * the packed prefill has them: fa_forward_varlen_ex), a tanh other than
- * the one above; token-packed (cu_seqlens) layouts, a split count or a window per sequence, explicit position ids, per-sequence
+ * the one above; token-packed (cu_seqlens) layouts (a packed step is fa_kvcache_append_varlen, then fa_forward_varlen_kvcache),
+ * a split count or a window per sequence, explicit position ids, per-sequence
  * query counts on the prefill entries or on the flat decode entries.  NOT a reference entry point. */
 #define FA_KV_16BIT    0   /* K, V elements are of in_dtype */
 #define FA_KV_FP8_E4M3 1   /* K, V elements are OCP e4m3fn bytes */
@@ -486,8 +487,8 @@ int fa_kvcache_append_paged_fp8_rope(const void* Knew, const void* Vnew, void* K
  *           fa_kvcache_decode with seqlens_q pointing at the same vector then gives row i the causal position L_b + i.
  * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor, a wrong `size`, an unknown kv_dtype, scales on a
  * 16-bit cache, Q, Qout or rope_sin without rope_cos, the overlap above, and everything the flat entry of the descriptor's form rejects.
- * Not part of this entry: token-packed (cu_seqlens) sources, explicit position ids, and what the flat entries exclude.  NOT a
- * reference entry point. */
+ * Not part of this entry: explicit position ids, and what the flat entries exclude.  Token-packed (cu_seqlens) sources are
+ * fa_kvcache_append_varlen's, below.  NOT a reference entry point. */
 typedef struct fa_kvappend_desc {
     size_t size;               /* sizeof(fa_kvappend_desc) */
     const void *Knew, *Vnew;   /* device, [B,Hkv,Nnew,d] of `dtype` */
@@ -511,6 +512,59 @@ typedef struct fa_kvappend_desc {
     void* stream;
 } fa_kvappend_desc;
 int fa_kvcache_append_ex(const fa_kvappend_desc* desc);
+
+/* KV-cache append of a token-packed batch: fa_kvcache_append_ex with the sources as the QKV projection leaves them.  Knew, Vnew are
+ * packed (total_new, Hkv, d) and, with rotary, Q and Qout (total_new, Hkv*G, d): row (t, h) is d contiguous elements of `dtype` at
+ * base + t*stride_t + h*stride_h (strides in ELEMENTS), so views of one fused (total, Hq + 2*Hkv, d) buffer, head-major tensors
+ * (stride_t = d) and padded rows are all taken as they lie.  Which of the eight forms a call is follows from block_table, kv_dtype and
+ * rope_cos exactly as in fa_kvcache_append_ex, and every field of that name means what it means there.
+ * cu_seqlens_new  a device pointer to B+1 int32, read on the device only, clamped as fa_forward_varlen clamps its vectors:
+ *           s_b = clamp(cu[b], 0, total_new), e_b = clamp(cu[b+1], s_b, total_new), m_b = e_b - s_b.  Token row t belongs to sequence b
+ *           iff s_b <= t < e_b, and is its token i = t - s_b.  A vector that does not ascend places tokens without meaning, but never
+ *           forms a source row outside [0, total_new) or a destination outside the cache: i is used only after it was found in [0, m_b).
+ * Token i of sequence b goes to p = L_b + i, L_b = clamp(seqlens_k[b], 0, Ncap), exactly as fa_kvcache_append_ex places token i of
+ * m_b: dropped at p >= Ncap or behind a table entry outside [0, num_pages); table entries are read only for pages that receive a kept
+ * token; page addresses are 64 bit; the fp8 recipe and the pinned rotary arithmetic are those entries'.  Q row (t, hq) is rotated at p
+ * (table row min(p, max_pos - 1)), also when the K token is dropped.  seqlens_out[b] = min(L_b + m_b, Ncap).
+ * THE BYTES ARE A CONTRACT: for every sequence, the cache or pool bytes, the rotated Q rows and seqlens_out are exactly what
+ * fa_kvcache_append_ex writes with seqlens_new[b] = m_b and Nnew = max m_b from the padded head-major copy of the same rows.
+ * Rows of no sequence -- before s_0, at or past e_{B-1}, in gaps -- are never used: their K, V and Q rows may hold NaN patterns, and
+ * their Qout rows are NOT written (fa_forward_varlen's rule for O, not the ragged append's copy-through).  An empty sequence reads no
+ * table entry and writes nothing; its seqlens_out entry is L_b.
+ * total_new is a HOST integer, the token rows of Knew, Vnew, Q and Qout and the bound of every source address.  Nothing on the host
+ * reads device data; the grid follows (total_new, Hkv, G, d, whether there is a Q) only; there is no workspace; the call is one copy
+ * kernel and, with seqlens_out, one tiny lengths kernel.  A captured call follows cu_seqlens_new, the lengths, the table, the scales
+ * and the rotary tables when they are rewritten in place within the same total_new.  fa_forward_varlen_kvcache with Q = Qout,
+ * cu_seqlens_q = cu_seqlens_new and seqlens_k = seqlens_out is the step's read half: two launches on the projection's own buffer.
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor or a wrong `size`; everything
+ * fa_kvcache_append_ex rejects for the cache and pool geometry, kv_dtype, scales on a 16-bit cache, the rotary fields, and Q, Qout or
+ * rope_sin without rope_cos; a NULL cu_seqlens_new; total_new <= 0; a stride_t below d, a negative stride_h, a stride that is not a
+ * multiple of 8 elements or a base that is not 16-byte aligned (fa_varlen_desc's rules); total_new*Hkv*d/8 or total_new*Hkv*G*d/8 of
+ * 2^31 or more; a Qout that is neither Q with equal strides nor disjoint from Q's address extent; cu_seqlens_new overlapping
+ * seqlens_out; a partial overlap of seqlens_out and seqlens_k.
+ * Not part of this entry: explicit position ids or per-sequence position offsets, a token-major page layout, cu_seqlens on the decode
+ * entries, per-token or per-page scales, fp8 sources.  NOT a reference entry point. */
+typedef struct fa_kvappend_varlen_desc {
+    size_t size;                    /* sizeof(fa_kvappend_varlen_desc) */
+    const void *Knew, *Vnew;        /* device, packed: row (t, h) = d elements at base + t*stride_t + h*stride_h */
+    void *K, *V;                    /* the cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d] */
+    const int* cu_seqlens_new;      /* device, B+1 int32 */
+    const int* seqlens_k;           /* device, B int32, may be NULL (= 0 for all: every sequence empty) */
+    int* seqlens_out;               /* device, B int32, may be NULL; == seqlens_k or disjoint from it */
+    const int* block_table;         /* device, [B,max_pages] int32; NULL: a contiguous cache */
+    const float *k_scale, *v_scale; /* device, Hkv fp32 each, may be NULL (= 1.0); fp8 only */
+    const void* Q; void* Qout;      /* rotary only: packed (total_new, Hkv*G, d) through their own strides; both NULL: K only */
+    const float *rope_cos, *rope_sin;   /* device, [max_pos,rot_dim/2] fp32; rope_cos NULL: no rotation */
+    int kv_dtype;                   /* FA_KV_16BIT or FA_KV_FP8_E4M3 */
+    int B, Hkv, d, total_new;       /* total_new: HOST, the token rows of Knew, Vnew, Q and Qout */
+    int Ncap, num_pages, page_size, max_pages;   /* Ncap: contiguous only; the other three: paged only */
+    int G, rot_dim, max_pos, interleaved;        /* rotary only */
+    int dtype;
+    long long k_stride_t, k_stride_h, v_stride_t, v_stride_h,
+              q_stride_t, q_stride_h, qo_stride_t, qo_stride_h;   /* ELEMENTS; d contiguous; the q pairs: with Q only */
+    void* stream;
+} fa_kvappend_varlen_desc;
+int fa_kvcache_append_varlen(const fa_kvappend_varlen_desc* desc);
 
 /* Merge of attention states over disjoint key ranges: the rule the decode entries above promise (fa_forward_kvcache),
  *   lse = ln sum_r exp(lse_r),   O = sum_r O_r exp(lse_r - lse),
