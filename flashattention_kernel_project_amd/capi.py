@@ -147,6 +147,23 @@ class VarlenKvcacheDesc(C.Structure):
             self.size = C.sizeof(VarlenKvcacheDesc)
 
 
+class KvDecodeVarlenDesc(C.Structure):
+    """fa_kvdecode_varlen_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Q", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p),
+                ("cu_seqlens_q", C.c_void_p), ("seqlens_k", C.c_void_p), ("block_table", C.c_void_p), ("k_scale", C.c_void_p),
+                ("v_scale", C.c_void_p), ("sinks", C.c_void_p), ("kv_dtype", C.c_int), ("B", C.c_int), ("Hkv", C.c_int), ("G", C.c_int),
+                ("d", C.c_int), ("total_q", C.c_int), ("max_q", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int),
+                ("page_size", C.c_int), ("max_pages", C.c_int), ("q_stride_t", C.c_longlong), ("q_stride_h", C.c_longlong),
+                ("o_stride_t", C.c_longlong), ("o_stride_h", C.c_longlong), ("scale", C.c_float), ("causal", C.c_int),
+                ("window", C.c_int), ("softcap", C.c_float), ("in_dtype", C.c_int), ("out_dtype", C.c_int), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvDecodeVarlenDesc)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -184,6 +201,9 @@ def _signatures() -> dict:
         "fa_forward_varlen_kvcache": (i, [C.POINTER(VarlenKvcacheDesc)]),
         # the same on an e4m3fn cache: the descriptor as it is, then k_scale, v_scale
         "fa_forward_varlen_kvcache_fp8": (i, [C.POINTER(VarlenKvcacheDesc), vp, vp]),
+        # split-KV decode on token-packed (cu_seqlens) Q, O and lse: the read half of fa_kvcache_append_varlen
+        "fa_kvcache_decode_varlen_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc)]),
+        "fa_kvcache_decode_varlen": (i, [C.POINTER(KvDecodeVarlenDesc)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

@@ -322,6 +322,9 @@ FA_EXPORT int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, 
     return (int)fa::varlen_cache_fp8_dispatch(desc, k_scale, v_scale);
 }
 
+FA_EXPORT size_t fa_kvcache_decode_varlen_workspace_bytes(const fa_kvdecode_varlen_desc* desc) { return fa::kvpacked_workspace_bytes(desc); }
+FA_EXPORT int fa_kvcache_decode_varlen(const fa_kvdecode_varlen_desc* desc) { return (int)fa::kvpacked_dispatch(desc); }
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

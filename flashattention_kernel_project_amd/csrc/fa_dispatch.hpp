@@ -13,6 +13,7 @@ struct fa_varlen_desc;
 struct fa_varlen_opts;
 struct fa_varlen_kvcache_desc;
 struct fa_kvappend_varlen_desc;
+struct fa_kvdecode_varlen_desc;
 
 namespace fa {
 
@@ -78,7 +79,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_fwd_kvragged*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_fwd_kvragged*.hip, fa_fwd_kvpacked*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -114,6 +115,15 @@ struct KvPagedArgs {
 // LogitArgs kernels of fa_fwd_kvlogits*.hip, which exist around the windowed packs only: window 0 runs there as window = Ncap.
 // seqlens_q, also the descriptor's alone: a device pointer to B int32 query counts (null: every sequence has Nq rows).  A call with it
 // runs the RaggedArgs kernels of fa_fwd_kvragged*.hip, which wrap the LogitArgs packs, so window 0 runs there as window = Ncap too.
+// packed, fa_kvcache_decode_varlen's alone and last for the same reason: where the rows of a token-packed call live.  With it p.c.Q
+// and p.c.O are packed (total_q, Hkv*G, d) tensors behind these strides (elements), p.c.lse is [Hkv*G, total_q], p.c.Nq is max_q and
+// seqlens_q is null: the counts come from cu_q on the device.  A call with it runs the PackedArgs kernels of fa_fwd_kvpacked*.hip,
+// which wrap the RaggedArgs packs.
+struct KvPackedRows {
+    const int* cu_q;
+    int total_q;
+    long long q_st, q_sh, o_st, o_sh;
+};
 struct KvDecodeArgs {
     KvPagedArgs p;
     const float *k_scale, *v_scale;
@@ -122,6 +132,7 @@ struct KvDecodeArgs {
     const float* sinks;
     float softcap;
     const int* seqlens_q;
+    const KvPackedRows* packed;
 };
 hipError_t kvdecode_dispatch(const KvDecodeArgs& a);
 // What kvdecode_dispatch hands checked arguments to: one function per translation unit that owns decode kernels -- fa_fwd_kvcache,
@@ -146,6 +157,15 @@ hipError_t kvlogits_combine(const void* ws, void* O, float* lse, const float* si
 // rows per query head
 hipError_t kvragged_combine(const void* ws, void* O, float* lse, const float* sinks, const int* seqlens_q, int BH, int rows, int Hkv,
                             int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
+// fa_kvcache_decode_varlen (fa_fwd_kvpacked.hip): the checks, then the PackedArgs kernels of that unit or, on an fp8 cache, of
+// fa_fwd_kvpacked_fp8.hip; the descriptor is the public one, as it is.  d.packed is set for both hand-overs.
+hipError_t kvpacked_dispatch(const ::fa_kvdecode_varlen_desc* desc);
+size_t kvpacked_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc);
+hipError_t kvpacked_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvpacked_fp8_decode(const KvDecodeArgs& a, int lg_page);
+// ... and the merge behind them (fa_fwd_kvpacked.hip): live rows go to their tokens, nothing else is written; Nq: max_q
+hipError_t kvpacked_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
+                            int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
 // The argument checks alone: the append runs them too, so it accepts exactly the caches the decode accepts.  kvpaged_check fills
 // in the capacity and returns page_log2(page_size): log2 of a page size the kernels take, else -1.
 hipError_t kvcache_check(const KvCacheArgs& a);

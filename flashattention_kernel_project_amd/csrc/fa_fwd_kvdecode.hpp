@@ -1,7 +1,7 @@
 // fa_fwd_kvdecode.hpp -- the host path the eight KV-cache decode entries share: the pack builder, the launcher and the type switch,
-// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>) the kernel takes.  Private
-// to the nine translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow, _kvwindow_fp8,
-// _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8): it instantiates
+// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>, PackedArgs<...>) the kernel
+// takes.  Private to the eleven translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow,
+// _kvwindow_fp8, _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8, _kvpacked, _kvpacked_fp8): it instantiates
 // kernels, so a unit names only its own packs and no other unit's code moves.
 #pragma once
 #include "fa_fwd_split_kernel.hpp"
@@ -34,6 +34,14 @@ static Pack kvdecode_pack(const KvDecodeArgs& d, int lg_page)
         pack.cap_rk = d.softcap > 0.0f ? 2.0f / d.softcap : 0.0f;
     }
     if constexpr (IsRaggedArgs<Pack>::value) pack.seqlens_q = d.seqlens_q;
+    if constexpr (IsPackedArgs<Pack>::value) {   // the counts come from cu_q: seqlens_q stays null
+        pack.cu_q = d.packed->cu_q;
+        pack.total_q = d.packed->total_q;
+        pack.q_st = d.packed->q_st;
+        pack.q_sh = d.packed->q_sh;
+        pack.o_st = d.packed->o_st;
+        pack.o_sh = d.packed->o_sh;
+    }
     return pack;
 }
 
@@ -69,8 +77,12 @@ static hipError_t launch_kvdecode(const KvCacheArgs& a, Pack pack, int span)
                        a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), pack);
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
+    // token-packed rows: the merge stores the live rows to their tokens through O's strides and writes nothing else
+    if constexpr (IsPackedArgs<Pack>::value)
+        return kvpacked_combine(a.ws, a.O, a.lse, pack.sinks, {pack.cu_q, pack.total_q, pack.q_st, pack.q_sh, pack.o_st, pack.o_sh}, BH, rows,
+                                a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // per-sequence query counts: the merge maps padded rows to the packed workspace rows, writes the dead rows and joins the sinks
-    if constexpr (IsRaggedArgs<Pack>::value)
+    else if constexpr (IsRaggedArgs<Pack>::value)
         return kvragged_combine(a.ws, a.O, a.lse, pack.sinks, pack.seqlens_q, BH, rows, a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // the partial kernels leave the sinks alone: the merge joins them, once per row
     else if constexpr (IsLogitArgs<Pack>::value)

@@ -4,7 +4,8 @@
 // pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt); the paged entry passes
 // a PagedArgs in that pack, and everything it adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt); the fp8
 // entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
-// selects (profiles/kvcache_fp8.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
+// selects (profiles/kvcache_fp8.txt); the token-packed entry (fa_kvcache_decode_varlen) wraps the four RaggedArgs packs in a
+// PackedArgs, and what it adds sits behind `if constexpr (kPacked)` (profiles/kvcache_decode_varlen.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
 // behind `if constexpr (kWindow)` (profiles/kvcache_window.txt); the soft-cap / sink entry wraps the four windowed packs in a
 // LogitArgs, and what it adds sits behind `if constexpr (kLogits)` (profiles/kvcache_logits.txt); the per-sequence query count wraps
 // the four LogitArgs packs in a RaggedArgs, and what it adds sits behind `if constexpr (kRagged)` (profiles/kvcache_ragged.txt).
@@ -111,6 +112,51 @@ __device__ __forceinline__ NoRagged ragged_part() { return {}; }
 __device__ __forceinline__ NoRagged ragged_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const RaggedArgs<Base>& ragged_part(const RaggedArgs<Base>& g) { return g; }
 
+// What the token-packed instantiations take (fa_kvcache_decode_varlen): a RaggedArgs pack plus where the rows live.  Q and O are
+// packed (total_q, Hkv*G, d) tensors read and written through their strides, lse is [Hkv*G, total_q], and sequence b owns the tokens
+// [s_b, e_b) that cu_q gives under fa_forward_varlen's clamps; n_b = min(e_b - s_b, Nq1) takes the place of the seqlens_q count (the
+// wrapped pack's seqlens_q is null and never read).  Strides in elements; every byte offset inside one (sequence, K/V head) view --
+// rows [0, n_b) of the G heads of the group -- fits 32 bits (checked on the host).
+template <typename Base> struct PackedArgs : Base {
+    const int* cu_q;        // [B + 1] on the device, not null
+    int total_q;
+    long long q_st, q_sh, o_st, o_sh;
+};
+template <typename A> struct IsPackedArgs : std::false_type {};
+template <typename Base> struct IsPackedArgs<PackedArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<PackedArgs<Base>> : IsFp8Args<Base> {};
+template <typename Base> struct IsWindowArgs<PackedArgs<Base>> : IsWindowArgs<Base> {};
+template <typename Base> struct IsLogitArgs<PackedArgs<Base>> : IsLogitArgs<Base> {};
+template <typename Base> struct IsRaggedArgs<PackedArgs<Base>> : IsRaggedArgs<Base> {};
+struct NoPacked {};
+__device__ __forceinline__ NoPacked packed_part() { return {}; }
+__device__ __forceinline__ NoPacked packed_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const PackedArgs<Base>& packed_part(const PackedArgs<Base>& k) { return k; }
+// what a kPacked kernel keeps about its (sequence, K/V head) view -- all of it wave-uniform but the lane's offsets and (hd, i), which
+// live in the prologue (qoff) or in the epilogue (the rest) only
+struct PackedView {
+    int s;                            // the sequence's first token
+    __amdgpu_buffer_rsrc_t rq, ro;    // the views of Q and O
+    unsigned qend, qoff, ooff;        // Q: the view's size (a dead lane's offset) and the lane's offset; O: the lane's offset
+    unsigned hd, i;                   // the lane's head within the group and its row
+    bool live;
+};
+// [s, s + n) of sequence b among the total_q token rows: fa_forward_varlen's clamps, cut to at most max_q rows (wave-uniform)
+__device__ __forceinline__ void packed_rows(const int* __restrict__ cu, unsigned b, int total, int max_q, int& s, unsigned& n)
+{
+    s = min(max(cu[b], 0), total);
+    n = (unsigned)min(min(max(cu[b + 1], s), total) - s, max_q);
+}
+// the (sequence, K/V head) view of a packed tensor: rows [0, n) of the G heads from `h0` on; `bytes` is what a lane past the live
+// rows uses as its offset (the first one past the view: loads read 0, stores are dropped)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_rsrc(const void* ptr, int s, unsigned n, unsigned h0, unsigned G, long long st,
+                                                              long long sh, int d, unsigned es, unsigned& bytes)
+{
+    const long long first = (long long)s * st + (long long)h0 * sh;
+    bytes = n > 0 ? (unsigned)((unsigned long long)((long long)(n - 1) * st + (long long)(G - 1) * sh + d) * es) : 0u;
+    return make_rsrc(static_cast<const char*>(ptr) + first * (long long)es, bytes);
+}
+
 // A wave-uniform float into a scalar register.  gfx950 has no scalar float arithmetic, so a value computed from kernel arguments
 // lives in a VGPR unless it is read back; the d = 64 kernels sit at their 128 VGPRs and spill for every such value they keep.
 __device__ __forceinline__ float to_sgpr(float x)
@@ -197,6 +243,15 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // takes the register the wrapped kernel keeps for it, and the one-pass epilogue derives the padded row again.
 // The wrapped kernels' own expressions are left textually alone, with the ragged ones beside them: naming "rows per head" once for
 // both changed the schedule of the windowed units (profiles/kvcache_ragged.txt).
+// kPacked (kRagged with a PackedArgs around the pack): the rows of sequence b are the tokens [s_b, s_b + n_b) of packed (total_q,
+// Hkv*G, d) tensors, n_b = min(e_b - s_b, Nq1) from the clamped cu_q pair.  Everything between the Q load and the O store is the
+// ragged kernel's, the lane's packed row -> (head hd, row i) map with its limits for a lane past the live rows included, so the bits
+// are the ragged kernel's on the padded copy of the same rows.  Q and O go through ONE scalar descriptor per (sequence, K/V head):
+// it starts at token s_b of head hkv*G and spans the n_b rows of the G heads, a row's offset is i * stride_t + hd * stride_h, and a
+// lane past the live rows uses the view's size as its offset (loads read 0, stores are dropped).  No dead row is written, by the
+// one-pass kernels or by the merge (PackedLse): a token that is no live row keeps its O row and its lse entries.  lse goes to
+// lse[hq * total_q + s_b + i] by a guarded store.  As under kRagged nothing new lives in a VGPR across the tile loop: the Q offset
+// dies with the Q load, and the epilogue derives (hd, i) and the O offset from the thread id again (profiles/kvcache_decode_varlen.txt).
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -221,6 +276,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto la = logit_part(cache...);
     constexpr bool kRagged = (IsRaggedArgs<Cache>::value || ...);
     [[maybe_unused]] const auto ra = ragged_part(cache...);
+    constexpr bool kPacked = (IsPackedArgs<Cache>::value || ...);
+    [[maybe_unused]] const auto ka = packed_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -245,11 +302,15 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     }
     // kRagged: the sequence's live rows per query head and per K/V head (wave-uniform).  The one-pass kernels write the dead rows
     // of this block's padded share -- two threads per row, half a row each -- and a block without a live packed row ends here.
+    // kPacked: the count comes from the sequence's clamped cu_q pair, whose first token pv.s is where its rows start; no dead row
+    // is written
     [[maybe_unused]] unsigned n_q = 0, live = 0;
+    [[maybe_unused]] std::conditional_t<kPacked, PackedView, NoPacked> pv;
     if constexpr (kRagged) {
-        n_q = (unsigned)min(max(ra.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
+        if constexpr (kPacked) packed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
+        else n_q = (unsigned)min(max(ra.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
         live = ((unsigned)Nq / (unsigned)ca.Nq1) * n_q;
-        if constexpr (!kPartial) {
+        if constexpr (!kPartial && !kPacked) {
             const unsigned pr = qb * (unsigned)kRows + (tid >> 1);
             if (pr < (unsigned)Nq && pr % (unsigned)ca.Nq1 >= n_q) {
                 constexpr unsigned es = kOutF32 ? 4u : 2u, kHalf = (unsigned)D * es / 2u;
@@ -274,7 +335,13 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     }
     const unsigned key0 = (kWindow ? start_t : 0u) + sp * (unsigned)chunk;   // multiple of kBlockN
     const unsigned key1 = min(nkeys, key0 + (unsigned)chunk);         // exclusive
+    // kPacked: Q is the (sequence, K/V head) view of the packed tensor -- the sequence's n_b token rows over the G heads of the group
+    // (rq itself is then unused; it keeps its line so that the wrapped kernels' text stays as it was)
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(Qg + (size_t)bh * Nq * D, (unsigned)((size_t)Nq * D * 2));
+    if constexpr (kPacked) {
+        const unsigned grp = (unsigned)Nq / (unsigned)ca.Nq1;
+        pv.rq = packed_rsrc(Qg, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, ka.q_st, ka.q_sh, D, 2u, pv.qend);
+    }
     // K/V descriptors end at this split's last key: rows beyond it read 0 and are masked below
     // element offset -> address: the fp8 instantiations get byte pointers in Kg / Vg
     [[maybe_unused]] auto kv_at = [](const uint16_t* base, size_t elems) -> const void* {
@@ -291,12 +358,14 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     // descriptor), and its index within its head, which for such a lane is the last live row's -- except with n_b = Nq1, where no
     // row is dead and a lane past Nq keeps the index q_row % Nq1 the wrapped kernel gives it: its votes then fall in the same tiles,
     // which is what makes full counts return the wrapped kernel's bits in every shape.  Else io_row is q_row.
+    // kPacked: the same map; Q is then loaded from row i of head hd of the view, and a lane past the live rows from past its end.
     [[maybe_unused]] unsigned rag_row1 = 0, rag_io = 0;
     if constexpr (kRagged) {
         const unsigned last = n_q == (unsigned)ca.Nq1 ? ~0u : live - 1u;   // wave-uniform
         const unsigned pc = min(q_row, last), hd = pc / n_q;
         rag_row1 = pc - hd * n_q;
         rag_io = q_row < live ? hd * (unsigned)ca.Nq1 + rag_row1 : (unsigned)Nq;
+        if constexpr (kPacked) pv.qoff = q_row < live ? (rag_row1 * (unsigned)ka.q_st + hd * (unsigned)ka.q_sh) * 2u : pv.qend;
     }
     const unsigned io_row = kRagged ? rag_io : q_row;
 
@@ -351,6 +420,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 #pragma unroll
     for (int s = 0; s < G::kKSteps; ++s) {
         u32x4 raw = buf_load16(rq, io_row * G::kRowBytes + (16u * s + 8u * h) * 2u);
+        if constexpr (kPacked) raw = buf_load16(pv.rq, pv.qoff + (16u * s + 8u * h) * 2u);   // the first load is then dead
 #pragma unroll
         for (int w = 0; w < 4; ++w) raw[w] ^= q_flip;
         qf[s] = raw;
@@ -608,6 +678,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         // kRagged: the padded row once more, from the packed one and the two counts taken through an empty asm: kept from the
         // prologue it stays in a VGPR across the tile loop, and so does q_row once the prologue has divided it (the wrapped kernels
         // re-derive q_row from the thread id), which the d = 64 paged kernels spill; the counts themselves are scalar
+        // kPacked: the same derivation also gives the row's head and index in the view, where O and lse go; o_row stays the padded
+        // row, which names the head whose sink the row joins
         [[maybe_unused]] unsigned o_row = io_row;
         if constexpr (kRagged) {
             unsigned nq = n_q, lv = live, t = tid;
@@ -615,6 +687,11 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             const unsigned pk = qb * (unsigned)kRows + (t >> 6) * 32u + (t & 31u);   // q_row, from the thread id again
             const unsigned pc = min(pk, lv - 1u), hd = pc / nq;
             o_row = pk < lv ? hd * (unsigned)ca.Nq1 + (pc - hd * nq) : (unsigned)Nq;
+            if constexpr (kPacked) {
+                pv.hd = hd;
+                pv.i = pc - hd * nq;
+                pv.live = pk < lv;
+            }
         }
         // kLogits: the sink joins here, once per row; rows past Nq read the sink of the head's last row and store nothing
         [[maybe_unused]] float w_keys = 1.0f;
@@ -632,14 +709,26 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
         if constexpr (kLogits) inv *= w_keys;
         if constexpr (kFp8) inv *= v_scale;
-        if constexpr (kCache) {
+        if constexpr (kPacked) {
+            // lse is [Hkv*G, total_q]: the live rows alone store, each to its own token's entry
+            if (ca.lse && h == 0 && pv.live)
+                ca.lse[((size_t)(bh % (unsigned)ca.Hkv) * ((unsigned)Nq / (unsigned)ca.Nq1) + pv.hd) * (size_t)ka.total_q + (size_t)pv.s + pv.i] =
+                    l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2;
+        } else if constexpr (kCache) {
             if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
                 buf_store4(make_rsrc(ca.lse + (size_t)bh * Nq, (unsigned)Nq * 4u), o_row * 4u,
                            __float_as_uint(l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2));
         }
         constexpr unsigned es = kOutF32 ? 4u : 2u;
+        // kPacked: O is the view Q has, through O's strides; a lane past the live rows stores past its end
         const __amdgpu_buffer_rsrc_t ro =
             make_rsrc(reinterpret_cast<char*>(Og) + (size_t)bh * Nq * D * es, (unsigned)((size_t)Nq * D * es));
+        if constexpr (kPacked) {
+            const unsigned grp = (unsigned)Nq / (unsigned)ca.Nq1;
+            unsigned oend;
+            pv.ro = packed_rsrc(Og, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, ka.o_st, ka.o_sh, D, es, oend);
+            pv.ooff = pv.live ? (pv.i * (unsigned)ka.o_st + pv.hd * (unsigned)ka.o_sh) * es : oend;
+        }
 #pragma unroll
         for (int db = 0; db < G::kDBlocks; ++db)
 #pragma unroll
@@ -649,9 +738,11 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 const float cc = o[db][4 * g + 2] * inv, d = o[db][4 * g + 3] * inv;
                 if constexpr (kOutF32) {
                     const f32x4 v = {a, b, cc, d};
-                    buf_store16(ro, (o_row * D + col) * 4u, __builtin_bit_cast(u32x4, v));
+                    if constexpr (kPacked) buf_store16(pv.ro, pv.ooff + col * 4u, __builtin_bit_cast(u32x4, v));
+                    else buf_store16(ro, (o_row * D + col) * 4u, __builtin_bit_cast(u32x4, v));
                 } else {
-                    buf_store8(ro, (o_row * D + col) * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
+                    if constexpr (kPacked) buf_store8(pv.ro, pv.ooff + col * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
+                    else buf_store8(ro, (o_row * D + col) * 2u, u32x2{T::pack2(a, b), T::pack2(cc, d)});
                 }
             }
     }
@@ -692,6 +783,30 @@ __device__ __forceinline__ NoRaggedLse ragged_lse_part() { return {}; }
 __device__ __forceinline__ NoRaggedLse ragged_lse_part(float*) { return {}; }
 __device__ __forceinline__ NoRaggedLse ragged_lse_part(const SinkLse&) { return {}; }
 __device__ __forceinline__ const RaggedLse& ragged_lse_part(const RaggedLse& s) { return s; }
+// PackedLse in the place of the float*: the merge behind the PackedArgs partial kernels.  The grid is RaggedLse's, one wave per padded
+// row; row i = row % Nq1 of head hd = row / Nq1 is live for i < n_b (packed_rows), reads workspace row hd * n_b + i and joins the
+// sink as under RaggedLse; it stores O to token s_b + i of query head hkv*G + hd through the strides and lse into [Hkv*G, total_q].
+// A wave with i >= n_b returns without writing anything.
+struct PackedLse {
+    float* lse;
+    const float* sinks;       // [Hkv * G] on the device, or nullptr
+    const int* cu_q;          // [B + 1] on the device, not null
+    int Hkv, Nq1, total_q;
+    long long o_st, o_sh;     // elements
+};
+__device__ __forceinline__ float* lse_part(const PackedLse& s) { return s.lse; }
+__device__ __forceinline__ NoSink sink_part(const PackedLse&) { return {}; }
+__device__ __forceinline__ NoRaggedLse ragged_lse_part(const PackedLse&) { return {}; }
+struct NoPackedLse {};
+__device__ __forceinline__ NoPackedLse packed_lse_part() { return {}; }
+__device__ __forceinline__ NoPackedLse packed_lse_part(float*) { return {}; }
+__device__ __forceinline__ NoPackedLse packed_lse_part(const SinkLse&) { return {}; }
+__device__ __forceinline__ NoPackedLse packed_lse_part(const RaggedLse&) { return {}; }
+__device__ __forceinline__ const PackedLse& packed_lse_part(const PackedLse& s) { return s; }
+// a live row's token and query head, and the first element of its O row
+struct PackedRow { size_t tok, hq; };
+__device__ __forceinline__ size_t packed_elem(const NoPackedLse&, const NoPackedLse&) { return 0; }
+__device__ __forceinline__ size_t packed_elem(const PackedLse& s, const PackedRow& r) { return r.tok * (size_t)s.o_st + r.hq * (size_t)s.o_sh; }
 template <typename T, bool kOutF32, bool kCache = false, typename... Lse>
 __global__ __launch_bounds__(64)
 void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og, int BH, int Nq, int D, int S, Lse... lse_arg)
@@ -702,6 +817,8 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     [[maybe_unused]] const auto sk = sink_part(lse_arg...);
     constexpr bool kRaggedM = (std::is_same_v<Lse, RaggedLse> || ...);
     [[maybe_unused]] const auto rg = ragged_lse_part(lse_arg...);
+    constexpr bool kPackedM = (std::is_same_v<Lse, PackedLse> || ...);
+    [[maybe_unused]] const auto pg = packed_lse_part(lse_arg...);
     const int cols4 = D / 4;             // 16 or 32
     const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
     const unsigned lane = threadIdx.x;
@@ -729,6 +846,18 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
         }
         ws_row = hd * n_q + i;
     }
+    // kPackedM: the row's token and query head, where O and lse go
+    [[maybe_unused]] std::conditional_t<kPackedM, PackedRow, NoPackedLse> pm;
+    if constexpr (kPackedM) {
+        int s;
+        unsigned n_q;
+        packed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
+        const int hd = row / pg.Nq1, i = row - hd * pg.Nq1;
+        if (i >= (int)n_q) return;   // wave-uniform: no live row, nothing is written
+        ws_row = hd * (int)n_q + i;
+        pm.tok = (size_t)s + (size_t)i;
+        pm.hq = (size_t)(bh % pg.Hkv) * (size_t)(Nq / pg.Nq1) + (size_t)hd;
+    }
     const float* base = ws + (size_t)bh * S * stride_s + (size_t)ws_row * (D + 2);
     // global reference max: every lane takes splits lane, lane+64, ...
     float M = -INFINITY;
@@ -743,6 +872,10 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     }
     if constexpr (kRaggedM) {
         if (rg.sinks) a2 = rg.sinks[(bh % rg.Hkv) * (Nq / rg.Nq1) + row / rg.Nq1] * kLog2e;
+        M = fmaxf(M, a2);
+    }
+    if constexpr (kPackedM) {
+        if (pg.sinks) a2 = pg.sinks[pm.hq] * kLog2e;
         M = fmaxf(M, a2);
     }
     float L = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -765,12 +898,14 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
         for (int i = 0; i < 4; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
     }
     if (sl != 0) return;
-    if constexpr (kSink || kRaggedM) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
+    if constexpr (kSink || kRaggedM || kPackedM) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
     const float inv = (kCache && L == 0.0f) ? 0.0f : 1.0f / L;
-    if constexpr (kCache) {
+    if constexpr (kPackedM) {
+        if (lse && lane == 0) lse[pm.hq * (size_t)pg.total_q + pm.tok] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
+    } else if constexpr (kCache) {
         if (lse && lane == 0) lse[rowi] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
     }
-    const size_t off = ((size_t)bh * Nq + row) * D + 4 * c4;
+    const size_t off = kPackedM ? packed_elem(pg, pm) + 4 * c4 : ((size_t)bh * Nq + row) * D + 4 * c4;
     if constexpr (kOutF32) {
         float* o = static_cast<float*>(Og) + off;
 #pragma unroll

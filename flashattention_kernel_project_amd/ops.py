@@ -641,6 +641,155 @@ def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_tabl
     return (out, lse) if return_lse else out
 
 
+def fa_kvcache_decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, causal: bool = False,
+                             scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None, workspace=None, stream=None,
+                             window=None, softcap: float = 0.0, sinks=None, lse=None):
+    """Split-KV decode on a token-packed batch (fa_kvcache_decode_varlen): the read half of fa_kvcache_append_varlen for a step whose
+    sequences bring few rows each (one token per sequence, speculative tokens, a short chunk beside decode tokens).  It is
+    fa_forward_kvcache(seqlens_q=...) -- the split-KV stream with the G heads of a group folded into the rows -- with q, the result and
+    lse in the packed layout of fa_forward_varlen_kvcache.
+    q: (total_q, Hq, d) fp16/bf16 device tensor, taken as it lies: any token and head strides with a contiguous last dimension (strides
+    multiples of 8 elements, 16-byte aligned storage), so the Q view of a fused (total, Hq + 2*Hkv, d) projection buffer, rotated in
+    place by the append, goes in without a copy.  d in {64,128}; Hq = G * Hkv.
+    cu_seqlens_q: int32 contiguous device tensor [B+1], read on the device only; sequence b owns the tokens [cu[b], cu[b+1]), clamped
+    into the tensor as in fa_forward_varlen.  max_seqlen_q: a host int >= 1, the most rows a sequence may have: sequence b has
+    n_b = min(cu[b+1] - cu[b], max_seqlen_q) rows, its first n_b tokens.  Grid, split count and workspace follow max_seqlen_q, not the
+    vector: size it to the step.
+    k_cache, v_cache: [B,Hkv,Ncap,d] of q's dtype, or with block_table (int32 [B, max_pages]) the pools [num_pages,Hkv,page_size,d].
+    cache_seqlens: int32 [B], the keys of sequence b in the cache, its own new tokens INCLUDED (the lengths after the append), or None
+    (the capacity for all).  With L_b and n_b, row i sees the keys [lo_i, c_i): c_i = L_b, or max(0, L_b - n_b + 1 + i) with causal;
+    lo_i = max(0, L_b - n_b + 1 + i - window) with a window, else 0.
+    window (None or 0: none), softcap, sinks, scale, out_dtype: as in fa_forward_kvcache.
+    -> o (total_q, Hq, d) of out_dtype (torch.float32, the default, or q's dtype), or (o, lse) with return_lse, lse (Hq, total_q)
+    float32.  On the live rows the bits are those of fa_forward_kvcache(seqlens_q=n, Nq=max_seqlen_q) on the padded copy of the same
+    rows.  Tokens that are no live row of any sequence are NOT written: a fresh result holds O = 0 and lse = -inf there ("no key");
+    with `out` (a tensor of q's shape and of out_dtype, any token and head strides) and `lse` (a contiguous float32 (Hq, total_q) tensor,
+    which implies return_lse) they keep what they held.  The fills of a fresh result are torch's, on the current stream.
+    workspace: optional uint8 device tensor of at least kvcache_decode_varlen_workspace_bytes(...).
+    Nothing is read on the host: append_varlen(seqlens_out=lens, q=q) then this call with cu_seqlens_q = cu_seqlens_new and
+    cache_seqlens = lens, captured once, serves every step of the same total_q; the replay follows the vectors, the table and the sinks.
+    An fp8 cache is fa_kvcache_decode_varlen_fp8's."""
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
+                          return_lse, out, workspace, stream, window, softcap, sinks, lse)
+
+
+def fa_kvcache_decode_varlen_fp8(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, k_scale=None,
+                                 v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
+                                 out=None, workspace=None, stream=None, window=None, softcap: float = 0.0, sinks=None, lse=None):
+    """fa_kvcache_decode_varlen against an fp8 cache: k_cache, v_cache (or the pools) contiguous torch.float8_e4m3fn (OCP e4m3fn; fnuz,
+    e5m2 and 16-bit caches are refused), k_scale, v_scale float32 [Hkv] or None (1.0), read on the device only; scales, logits and lse
+    as in fa_forward_kvcache_fp8, everything else as in fa_kvcache_decode_varlen."""
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
+                          return_lse, out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale))
+
+
+def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, d: int, Ncap: int = 0, max_pages: int = 0,
+                                          page_size: int = 0, window: int = 0) -> int:
+    """Workspace of fa_kvcache_decode_varlen and _fp8: a contiguous cache gives Ncap, a paged one max_pages and page_size.  It is what
+    the padded decode entry needs with Nq = max_seqlen_q (kvcache_window_workspace_bytes, kvcache_paged_window_workspace_bytes)."""
+    desc = capi.new_desc(capi.KvDecodeVarlenDesc)
+    capi.fill(desc, block_table=1 if max_pages or page_size else None, B=B, Hkv=Hkv, G=G, d=d, max_q=max_seqlen_q, Ncap=Ncap,
+              max_pages=max_pages, page_size=page_size, window=window)
+    return int(capi.lib().fa_kvcache_decode_varlen_workspace_bytes(desc))
+
+
+def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse,
+                   out, workspace, stream, window, softcap, sinks, lse, scales=None):
+    """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one.  Shapes and
+    dtypes are judged before anything needs a device."""
+    import torch
+    fp8 = scales is not None
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    if fp8 and (k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn):   # judged first, as in _decode
+        raise ValueError(f"k_cache, v_cache: {_FP8_CACHE} (got {k_cache.dtype}, {v_cache.dtype})")
+    if q.dim() != 3:
+        raise ValueError("q must be a packed tensor (total_q, Hq, d)")
+    dts = (torch.float16, torch.bfloat16)
+    if fp8:
+        if q.dtype not in dts:
+            raise ValueError("q must be fp16 or bf16")
+    elif q.dtype not in dts or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("q, k_cache, v_cache must all be fp16 or all bf16")
+    total_q, Hq, d = q.shape
+    paged = block_table is not None
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.shape[3] != d:
+        raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with q's d")
+    Hkv = k_cache.shape[1]
+    if d not in (64, 128):
+        raise ValueError("d must be 64 or 128")
+    if total_q <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or k_cache.numel() == 0:
+        raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1:
+        raise ValueError("max_seqlen_q must be an int >= 1: the most rows a sequence may have")
+    window = _window(0 if window is None else window)
+    softcap = _softcap(softcap)
+    sink_ptr = _sinks_ptr(sinks, Hq, q.device)
+    ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], Hkv) if fp8 else (None, None)
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
+        raise ValueError("cu_seqlens_q must be an int32 tensor (the kernel reads 32-bit entries)")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
+        raise ValueError("cu_seqlens_q must be a contiguous 1-d tensor of B+1 entries")
+    B = cu_seqlens_q.numel() - 1
+    if cache_seqlens is not None and (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32
+                                      or cache_seqlens.shape != (B,)):
+        raise ValueError("cache_seqlens must be an int32 device tensor of B entries")
+    qt, qh = _packed_strides(q, "q")
+    if paged:
+        num_pages, page_size, Ncap = k_cache.shape[0], k_cache.shape[2], 0
+        if page_size < 16 or page_size & (page_size - 1):
+            raise ValueError("page_size must be a power of two >= 16")
+        table_ptr = _table_ptr(block_table, B)
+        max_pages = block_table.shape[1]
+        if max_pages <= 0:
+            raise ValueError("block_table must have at least one column")
+    else:
+        table_ptr, num_pages, page_size, max_pages, Ncap = None, 0, 0, 0, k_cache.shape[2]
+        if k_cache.shape[0] != B:
+            raise ValueError(f"k_cache holds {k_cache.shape[0]} sequences, cu_seqlens_q {B}")
+    for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    cache_dts = (torch.float8_e4m3fn if fp8 else q.dtype,)
+    k_ptr, v_ptr = _dev_ptr(k_cache, "k_cache", cache_dts), _dev_ptr(v_cache, "v_cache", cache_dts)
+    lens_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    out_dt = _out_dt(out_dtype, q.dtype)
+    if out is None:   # tokens of no sequence then read as "no key"
+        out = torch.zeros(q.shape, dtype=out_dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.shape != q.shape or out.dtype != out_dtype:
+        raise ValueError("out must be a device tensor of q's shape and of out_dtype")
+    if lse is not None:
+        if not isinstance(lse, torch.Tensor) or lse.shape != (Hq, total_q):
+            raise ValueError("lse must be a float32 tensor (Hq, total_q)")
+        _dev_ptr(lse, "lse", (torch.float32,))
+        return_lse = True
+    elif return_lse:
+        lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
+    ot, oh = _packed_strides(out, "out")
+    G = Hq // Hkv
+    if workspace is None:
+        need = kvcache_decode_varlen_workspace_bytes(B, Hkv, G, max_seqlen_q, d, Ncap, max_pages, page_size, window)
+        if need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    desc = capi.new_desc(capi.KvDecodeVarlenDesc)
+    capi.fill(
+        desc, Q=q.data_ptr(), O=out.data_ptr(), lse=None if lse is None else lse.data_ptr(), K=k_ptr, V=v_ptr,
+        cu_seqlens_q=cu_seqlens_q.data_ptr(), seqlens_k=lens_ptr, block_table=table_ptr, k_scale=ks_ptr, v_scale=vs_ptr, sinks=sink_ptr,
+        kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, B=B, Hkv=Hkv, G=G, d=d, total_q=total_q, max_q=max_seqlen_q, Ncap=Ncap,
+        num_pages=num_pages, page_size=page_size, max_pages=max_pages, q_stride_t=qt, q_stride_h=qh, o_stride_t=ot, o_stride_h=oh,
+        scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)), window=window, softcap=softcap, in_dtype=_in_dt(q.dtype),
+        out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len, stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, workspace,
+                                       *(scales or ()))):
+        code = capi.lib().fa_kvcache_decode_varlen(desc)
+    capi.check("fa_kvcache_decode_varlen", code)
+    return (out, lse) if return_lse else out
+
+
 def fa_forward_kvcache_shared_prefix(q, k_prefix, v_prefix, k_cache, v_cache, prefix_len=None, cache_seqlens=None, block_table=None,
                                      k_scale=None, v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None,
                                      return_lse: bool = False, sinks=None, softcap: float = 0.0, stream=None):

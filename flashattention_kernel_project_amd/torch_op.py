@@ -245,6 +245,30 @@ def register() -> None:
                causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
                softcap=softcap, sinks=opt(sinks)), varlen_fake)
 
+    # split-KV decode on a token-packed batch (ops.fa_kvcache_decode_varlen, _fp8): q (total_q,Hq,d) as it lies, `int max_seqlen_q`
+    # behind cu_seqlens_q, `Tensor? cache_seqlens`; o and lse come back as from forward_varlen_kvcache, fresh results zero / -inf
+    # where no sequence has a live row
+    def decode_varlen_kw(q, *rest):
+        *scales, scale, causal, window, sinks, softcap, out_f32 = rest
+        kw = dict(causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+                  softcap=softcap, sinks=opt(sinks))
+        if scales:
+            kw.update(k_scale=opt(scales[0]), v_scale=opt(scales[1]))
+        return kw
+
+    def decode_varlen(fn):   # max_seqlen_q is positional in ops, behind cu_seqlens_q; the tensors behind it go by keyword
+        def call(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, **kw):
+            return fn(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=cache_seqlens, block_table=block_table, **kw)
+        return call
+
+    DECODE_VARLEN = "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, int max_seqlen_q, Tensor? cache_seqlens, " \
+                    "Tensor? block_table, "
+    DECODE_VARLEN_TAIL = "float scale, bool causal, int window, Tensor? sinks, float softcap, bool out_f32) -> (Tensor, Tensor)"
+    for name, mid, fn in (("decode_varlen", "", ops.fa_kvcache_decode_varlen),
+                          ("decode_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
+        define(name, DECODE_VARLEN + mid + DECODE_VARLEN_TAIL, (), decode_varlen(fn), "-ccc-oo",
+               decode_varlen_kw, varlen_fake)
+
     _registered = True
 
 

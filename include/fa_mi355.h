@@ -330,7 +330,7 @@ int fa_forward_kvcache_paged_fp8_window(const void* Q, const void* Kpool, const 
  *           accepted and means seqlens_q == NULL; every other wrong size is refused.
  * Not part of this entry: a sink per row or per token, sinks or a soft-cap on the dense prefill entries (fa_forward, fa_forward_ex;
  * the packed prefill has them: fa_forward_varlen_ex), a tanh other than
- * the one above; token-packed (cu_seqlens) layouts (a packed step is fa_kvcache_append_varlen, then fa_forward_varlen_kvcache),
+ * the one above; token-packed (cu_seqlens) layouts (a packed step is fa_kvcache_append_varlen, then fa_kvcache_decode_varlen, below),
  * a split count or a window per sequence, explicit position ids, per-sequence
  * query counts on the prefill entries or on the flat decode entries.  NOT a reference entry point. */
 #define FA_KV_16BIT    0   /* K, V elements are of in_dtype */
@@ -542,8 +542,8 @@ int fa_kvcache_append_ex(const fa_kvappend_desc* desc);
  * multiple of 8 elements or a base that is not 16-byte aligned (fa_varlen_desc's rules); total_new*Hkv*d/8 or total_new*Hkv*G*d/8 of
  * 2^31 or more; a Qout that is neither Q with equal strides nor disjoint from Q's address extent; cu_seqlens_new overlapping
  * seqlens_out; a partial overlap of seqlens_out and seqlens_k.
- * Not part of this entry: explicit position ids or per-sequence position offsets, a token-major page layout, cu_seqlens on the decode
- * entries, per-token or per-page scales, fp8 sources.  NOT a reference entry point. */
+ * Not part of this entry: explicit position ids or per-sequence position offsets, a token-major page layout,
+ * per-token or per-page scales, fp8 sources.  (The decode of a packed step is fa_kvcache_decode_varlen's.)  NOT a reference entry point. */
 typedef struct fa_kvappend_varlen_desc {
     size_t size;                    /* sizeof(fa_kvappend_varlen_desc) */
     const void *Knew, *Vnew;        /* device, packed: row (t, h) = d elements at base + t*stride_t + h*stride_h */
@@ -746,8 +746,8 @@ int fa_forward_varlen_ex(const fa_varlen_desc* desc, const fa_varlen_opts* opts)
  * Ncap <= 0; paged: a page_size that is no power of two >= 16, num_pages <= 0, max_pages <= 0, or max_pages*page_size beyond
  * 2^31 - 1; a capacity whose rows of one (sequence, head), Ncap*d*2 bytes, do not fit 32 bits.  Ncap, num_pages, page_size and
  * max_pages of the other form are ignored.
- * Not part of this entry: fp8 caches; split-KV for a short chunk on a very long cache (that stays with fa_kvcache_decode and its
- * seqlens_q -- see README for the crossover); rotary (fa_kvcache_append_ex rotates on the way into the cache); a window per sequence
+ * Not part of this entry: fp8 caches; split-KV for a short chunk on a very long cache (that is fa_kvcache_decode_varlen on
+ * the same packed Q -- see README for the crossover); rotary (fa_kvcache_append_ex rotates on the way into the cache); a window per sequence
  * or per head.  (An fp8 cache has an entry of its own on this descriptor: fa_forward_varlen_kvcache_fp8, below.)  NOT a reference
  * entry point. */
 typedef struct fa_varlen_kvcache_desc {
@@ -789,6 +789,75 @@ int fa_forward_varlen_kvcache(const fa_varlen_kvcache_desc* desc);
  * Not part of this entry: split-KV for a short chunk on a very long cache (that stays with fa_kvcache_decode and its seqlens_q);
  * per-token or per-page scales; an fp8 Q or fp8 MFMAs; rotary (the append rotates).  NOT a reference entry point. */
 int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale);
+
+/* Token-packed split-KV decode against the KV cache: the read half of fa_kvcache_append_varlen for a step whose sequences bring few
+ * rows each -- a pure decode step (one token per sequence), speculative or multi-token decode, a short chunk beside decode tokens.
+ * It is fa_kvcache_decode with seqlens_q -- the split-KV stream, the G heads of a group folded into the rows, every cache form --
+ * with Q, O and lse in the packed layout of fa_forward_varlen_kvcache, cut by cu_seqlens_q on the device, so that the rotated Q left
+ * in a fused QKV buffer by the append goes in as it lies and O comes out token-major.
+ * The descriptor carries everything fa_kvdecode_desc carries about the cache and the options, with the same meaning (K, V,
+ * seqlens_k, block_table, k_scale, v_scale, sinks, kv_dtype, B, Hkv, G, d, Ncap or num_pages / page_size / max_pages, scale, causal,
+ * window, softcap, in_dtype, out_dtype, workspace, workspace_bytes, stream), and in the place of the padded Q, O, lse, Nq and
+ * seqlens_q the packed fields of fa_varlen_kvcache_desc: Q, O (total_q, Hkv*G, d) through q_stride_t, q_stride_h, o_stride_t,
+ * o_stride_h (elements, d contiguous), lse [Hkv*G, total_q] fp32 or NULL, cu_seqlens_q (device, B+1 int32), total_q -- and one new
+ * host integer, max_q: the most rows any sequence may have, which plays the part Nq plays as the padded count.
+ * Semantics: [s_b, e_b) are fa_forward_varlen's clamps of cu_seqlens_q into [0, total_q] (s_b = clamp(cu[b]), e_b = clamp(cu[b+1])
+ * and never below s_b), n_b = min(e_b - s_b, max_q), and row i < n_b of sequence b is token s_b + i.  On those rows the call IS
+ * fa_kvcache_decode with Nq = max_q and seqlens_q[b] = n_b, run on the padded head-major copy [B,Hkv*G,max_q,d] of the same Q rows:
+ * the same c_i = max(0, L_b - n_b + 1 + i) with causal (L_b without), lo_i = max(0, L_b - n_b + 1 + i - W) and
+ * start_b = max(0, L_b - n_b + 1 - W); the same rules for what is and is not read below the window and past L_b; the sink counted
+ * once per row; the soft-cap before the masks; the fp8 scale rules; a row without a key is O = 0, lse = -inf (the sink logit with
+ * sinks).  It returns that call's BITS for O and lse, for every split count, contiguous and paged, 16-bit and e4m3fn caches, and
+ * with every n_b = max_q.
+ * Tokens that are no live row of any sequence -- before s_0, between or behind sequences, at or past s_b + max_q of a sequence that
+ * is longer than max_q -- are left alone: their Q rows are never loaded and may hold NaN bit patterns, and their O rows and lse
+ * entries are NEVER WRITTEN.  (The padded entry writes zeros and -inf into its dead rows; this one has no dead rows to own, as
+ * fa_forward_varlen has "rows of no sequence".)  n_b = 0 is an idle slot: none of the sequence's K/V rows, pages or table entries are
+ * read.  Sequences should own disjoint token ranges; where two overlap, each writes its result and the last store wins.
+ * Nothing on the host reads device data.  Grid, split count and workspace follow (B, Hkv, G, max_q, capacity or span_cap, d) exactly
+ * as fa_kvcache_decode's do with Nq = max_q, so the split count follows G * max_q: size max_q to the step, not to the longest
+ * prompt.  fa_kvcache_decode_varlen_workspace_bytes returns what fa_kvcache_decode_workspace_bytes returns for that padded
+ * descriptor (0 for a descriptor that is NULL, of the wrong size or of an unknown kv_dtype).  A captured call follows cu_seqlens_q,
+ * seqlens_k, the block table, the scales and the sinks when they are rewritten in place; total_q, max_q, window and softcap are host
+ * values.
+ * hipErrorInvalidValue, before the device is touched: a NULL descriptor; any `size` but sizeof(fa_kvdecode_varlen_desc); an unknown
+ * kv_dtype; scales on a 16-bit cache; everything fa_kvcache_decode of the same form refuses with Nq = max_q (null Q, K, V or O, bad
+ * B, Hkv, G, d, causal, dtypes, window < 0, a bad softcap, a bad capacity or page geometry, G * max_q rows beyond the 32-bit
+ * workspace offsets); fa_forward_varlen's checks on the packed Q and O (16-byte aligned, stride_t >= d, stride_h >= 0, strides
+ * multiples of 8 elements, the last byte of the tensor inside 32 bits); a NULL cu_seqlens_q; total_q <= 0 or max_q <= 0; a
+ * (sequence, K/V head) view -- (min(max_q, total_q) - 1) * stride_t + Hkv*G * stride_h + d elements of Q or of O -- whose bytes
+ * do not fit 32 bits with 512 to spare.
+ * Not part of this entry: a shared prefix (fa_merge_states composes one); a split count per sequence; splitting the keys inside the
+ * prefill kernel; an automatic choice between this entry and fa_forward_varlen_kvcache (README has the measured crossover);
+ * explicit position ids.  NOT a reference entry point. */
+typedef struct fa_kvdecode_varlen_desc {
+    size_t size;               /* sizeof(fa_kvdecode_varlen_desc); any other value is refused */
+    const void* Q; void* O;    /* packed (total_q, Hkv*G, d) through the strides below */
+    float* lse;                /* device, [Hkv*G, total_q] fp32, may be NULL */
+    const void *K, *V;         /* the cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d] */
+    const int* cu_seqlens_q;   /* device, B+1 int32 */
+    const int* seqlens_k;      /* device, B int32, may be NULL (= the capacity for all) */
+    const int* block_table;    /* device, [B,max_pages] int32; NULL: a contiguous cache */
+    const float* k_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const float* v_scale;      /* device, Hkv fp32, may be NULL (= 1.0); fp8 only */
+    const float* sinks;        /* device, Hkv*G fp32 natural-log logits, may be NULL (none) */
+    int kv_dtype;              /* FA_KV_16BIT or FA_KV_FP8_E4M3 */
+    int B, Hkv, G, d;
+    int total_q;               /* token rows of Q and O */
+    int max_q;                 /* the most rows a sequence may have: n_b = min(e_b - s_b, max_q) */
+    int Ncap;                  /* contiguous only */
+    int num_pages, page_size, max_pages;   /* paged only */
+    long long q_stride_t, q_stride_h, o_stride_t, o_stride_h;   /* elements */
+    float scale;
+    int causal, window;
+    float softcap;             /* 0: off */
+    int in_dtype, out_dtype;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} fa_kvdecode_varlen_desc;
+size_t fa_kvcache_decode_varlen_workspace_bytes(const fa_kvdecode_varlen_desc* desc);
+int fa_kvcache_decode_varlen(const fa_kvdecode_varlen_desc* desc);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
