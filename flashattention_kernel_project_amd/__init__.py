@@ -35,6 +35,7 @@ from .ops import (  # noqa: F401
     fa_kvcache_decode_varlen,
     fa_kvcache_decode_varlen_fp8,
     kvcache_decode_varlen_workspace_bytes,
+    tree_from_parents,
     flashattn_forward_wmma,
     flashattn_streaming_16x16_mw,
     flashattn_streaming_16x16_mw_kt,
@@ -53,7 +54,7 @@ __all__ = [
     "fa_kvcache_append_varlen", "fa_kvcache_append_varlen_fp8",
     "fa_merge_states", "fa_forward_kvcache_shared_prefix", "fa_forward_varlen", "fa_forward_varlen_kvcache",
     "fa_forward_varlen_kvcache_fp8",
-    "fa_kvcache_decode_varlen", "fa_kvcache_decode_varlen_fp8", "kvcache_decode_varlen_workspace_bytes",
+    "fa_kvcache_decode_varlen", "fa_kvcache_decode_varlen_fp8", "kvcache_decode_varlen_workspace_bytes", "tree_from_parents",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",
     "attention_flops", "attention_min_bytes", "shard_range",
 ]

@@ -164,6 +164,26 @@ class KvDecodeVarlenDesc(C.Structure):
             self.size = C.sizeof(KvDecodeVarlenDesc)
 
 
+class KvDecodeTreeOpts(C.Structure):
+    """fa_kvdecode_tree_opts of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("tree_mask", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvDecodeTreeOpts)
+
+
+class KvAppendVarlenOpts(C.Structure):
+    """fa_kvappend_varlen_opts of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("positions", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvAppendVarlenOpts)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -204,6 +224,10 @@ def _signatures() -> dict:
         # split-KV decode on token-packed (cu_seqlens) Q, O and lse: the read half of fa_kvcache_append_varlen
         "fa_kvcache_decode_varlen_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc)]),
         "fa_kvcache_decode_varlen": (i, [C.POINTER(KvDecodeVarlenDesc)]),
+        # the same with one 64-bit ancestor word per token row (tree speculation); a null opts is fa_kvcache_decode_varlen
+        "fa_kvcache_decode_varlen_ex": (i, [C.POINTER(KvDecodeVarlenDesc), C.POINTER(KvDecodeTreeOpts)]),
+        # the packed append with explicit rotary positions; a null opts is fa_kvcache_append_varlen
+        "fa_kvcache_append_varlen_ex": (i, [C.POINTER(KvAppendVarlenDesc), C.POINTER(KvAppendVarlenOpts)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

@@ -308,6 +308,10 @@ FA_EXPORT int fa_kvcache_append_ex(const fa_kvappend_desc* desc)
 }
 
 FA_EXPORT int fa_kvcache_append_varlen(const fa_kvappend_varlen_desc* desc) { return (int)fa::kvcache_append_varlen(desc); }
+FA_EXPORT int fa_kvcache_append_varlen_ex(const fa_kvappend_varlen_desc* desc, const fa_kvappend_varlen_opts* opts)
+{
+    return (int)fa::kvcache_append_varlen_ex(desc, opts);
+}
 
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 
@@ -324,6 +328,10 @@ FA_EXPORT int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, 
 
 FA_EXPORT size_t fa_kvcache_decode_varlen_workspace_bytes(const fa_kvdecode_varlen_desc* desc) { return fa::kvpacked_workspace_bytes(desc); }
 FA_EXPORT int fa_kvcache_decode_varlen(const fa_kvdecode_varlen_desc* desc) { return (int)fa::kvpacked_dispatch(desc); }
+FA_EXPORT int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, const fa_kvdecode_tree_opts* opts)
+{
+    return (int)fa::kvtree_dispatch(desc, opts);
+}
 
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)

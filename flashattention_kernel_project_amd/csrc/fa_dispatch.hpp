@@ -14,6 +14,8 @@ struct fa_varlen_opts;
 struct fa_varlen_kvcache_desc;
 struct fa_kvappend_varlen_desc;
 struct fa_kvdecode_varlen_desc;
+struct fa_kvdecode_tree_opts;
+struct fa_kvappend_varlen_opts;
 
 namespace fa {
 
@@ -123,6 +125,9 @@ struct KvPackedRows {
     const int* cu_q;
     int total_q;
     long long q_st, q_sh, o_st, o_sh;
+    // fa_kvcache_decode_varlen_ex alone, last so that the other initialisers leave it null: one 64-bit ancestor word per token row on
+    // the device.  A call with it runs the TreeArgs kernels of fa_fwd_kvtree*.hip, which wrap the PackedArgs packs.
+    const unsigned long long* tree_mask;
 };
 struct KvDecodeArgs {
     KvPagedArgs p;
@@ -159,10 +164,15 @@ hipError_t kvragged_combine(const void* ws, void* O, float* lse, const float* si
                             int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
 // fa_kvcache_decode_varlen (fa_fwd_kvpacked.hip): the checks, then the PackedArgs kernels of that unit or, on an fp8 cache, of
 // fa_fwd_kvpacked_fp8.hip; the descriptor is the public one, as it is.  d.packed is set for both hand-overs.
-hipError_t kvpacked_dispatch(const ::fa_kvdecode_varlen_desc* desc);
+hipError_t kvpacked_dispatch(const ::fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask = nullptr);
 size_t kvpacked_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc);
 hipError_t kvpacked_decode(const KvDecodeArgs& a, int lg_page);
 hipError_t kvpacked_fp8_decode(const KvDecodeArgs& a, int lg_page);
+// fa_kvcache_decode_varlen_ex (fa_fwd_kvtree.hip): the options' checks, then kvpacked_dispatch -- without a mask the plain entry's call,
+// with one its checks and the TreeArgs kernels of fa_fwd_kvtree.hip or, on an fp8 cache, of fa_fwd_kvtree_fp8.hip
+hipError_t kvtree_dispatch(const ::fa_kvdecode_varlen_desc* desc, const ::fa_kvdecode_tree_opts* opts);
+hipError_t kvtree_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvtree_fp8_decode(const KvDecodeArgs& a, int lg_page);
 // ... and the merge behind them (fa_fwd_kvpacked.hip): live rows go to their tokens, nothing else is written; Nq: max_q
 hipError_t kvpacked_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
                             int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
@@ -214,6 +224,9 @@ hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
 hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
 // fa_kvcache_append_varlen (fa_kvcache_append_varlen.hip): the checks and the one or two launches; the descriptor is the public one, as it is
 hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
+// fa_kvcache_append_varlen_ex: the options' checks, then the same; positions (device, total_new int32, or null) are the rotary table
+// rows of the tokens in place of their slots
+hipError_t kvcache_append_varlen_ex(const ::fa_kvappend_varlen_desc* desc, const ::fa_kvappend_varlen_opts* opts);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

@@ -1,7 +1,7 @@
 // fa_fwd_kvdecode.hpp -- the host path the eight KV-cache decode entries share: the pack builder, the launcher and the type switch,
-// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>, PackedArgs<...>) the kernel
-// takes.  Private to the eleven translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow,
-// _kvwindow_fp8, _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8, _kvpacked, _kvpacked_fp8): it instantiates
+// templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>, PackedArgs<...>, TreeArgs<...>) the kernel
+// takes.  Private to the thirteen translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow,
+// _kvwindow_fp8, _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8, _kvpacked, _kvpacked_fp8, _kvtree, _kvtree_fp8): it instantiates
 // kernels, so a unit names only its own packs and no other unit's code moves.
 #pragma once
 #include "fa_fwd_split_kernel.hpp"
@@ -42,6 +42,7 @@ static Pack kvdecode_pack(const KvDecodeArgs& d, int lg_page)
         pack.o_st = d.packed->o_st;
         pack.o_sh = d.packed->o_sh;
     }
+    if constexpr (IsTreeArgs<Pack>::value) pack.tree_mask = d.packed->tree_mask;
     return pack;
 }
 
@@ -79,7 +80,7 @@ static hipError_t launch_kvdecode(const KvCacheArgs& a, Pack pack, int span)
     if (e != hipSuccess) return e;
     // token-packed rows: the merge stores the live rows to their tokens through O's strides and writes nothing else
     if constexpr (IsPackedArgs<Pack>::value)
-        return kvpacked_combine(a.ws, a.O, a.lse, pack.sinks, {pack.cu_q, pack.total_q, pack.q_st, pack.q_sh, pack.o_st, pack.o_sh}, BH, rows,
+        return kvpacked_combine(a.ws, a.O, a.lse, pack.sinks, {pack.cu_q, pack.total_q, pack.q_st, pack.q_sh, pack.o_st, pack.o_sh, nullptr}, BH, rows,
                                 a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // per-sequence query counts: the merge maps padded rows to the packed workspace rows, writes the dead rows and joins the sinks
     else if constexpr (IsRaggedArgs<Pack>::value)

@@ -132,6 +132,23 @@ struct NoPacked {};
 __device__ __forceinline__ NoPacked packed_part() { return {}; }
 __device__ __forceinline__ NoPacked packed_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const PackedArgs<Base>& packed_part(const PackedArgs<Base>& k) { return k; }
+// What the tree-mask instantiations take (fa_kvcache_decode_varlen_ex with a mask): a PackedArgs pack plus one 64-bit word per token
+// row.  Bit j of token s_b + i's word: row i sees the step's own token j, the key at base_b + j with base_b = L_b - n_b; the keys below
+// base_b are visible to every row.  The words take the place of the causal triangle (the host refuses causal != 1 and max_q > 64).
+template <typename Base> struct TreeArgs : Base {
+    const unsigned long long* tree_mask;   // [total_q] on the device, 8-byte aligned, not null
+};
+template <typename A> struct IsTreeArgs : std::false_type {};
+template <typename Base> struct IsTreeArgs<TreeArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<TreeArgs<Base>> : IsFp8Args<Base> {};
+template <typename Base> struct IsWindowArgs<TreeArgs<Base>> : IsWindowArgs<Base> {};
+template <typename Base> struct IsLogitArgs<TreeArgs<Base>> : IsLogitArgs<Base> {};
+template <typename Base> struct IsRaggedArgs<TreeArgs<Base>> : IsRaggedArgs<Base> {};
+template <typename Base> struct IsPackedArgs<TreeArgs<Base>> : IsPackedArgs<Base> {};
+struct NoTree {};
+__device__ __forceinline__ NoTree tree_part() { return {}; }
+__device__ __forceinline__ NoTree tree_part(const CacheArgs&) { return {}; }
+template <typename Base> __device__ __forceinline__ const TreeArgs<Base>& tree_part(const TreeArgs<Base>& t) { return t; }
 // what a kPacked kernel keeps about its (sequence, K/V head) view -- all of it wave-uniform but the lane's offsets and (hd, i), which
 // live in the prologue (qoff) or in the epilogue (the rest) only
 struct PackedView {
@@ -252,6 +269,15 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // one-pass kernels or by the merge (PackedLse): a token that is no live row keeps its O row and its lse entries.  lse goes to
 // lse[hq * total_q + s_b + i] by a guarded store.  As under kRagged nothing new lives in a VGPR across the tile loop: the Q offset
 // dies with the Q load, and the epilogue derives (hd, i) and the O offset from the thread id again (profiles/kvcache_decode_varlen.txt).
+// kTree (kPacked with a TreeArgs around the pack): the causal triangle over the step's own n_b tokens becomes one 64-bit word per
+// row.  With base = L - n_b (may be negative) the keys below base are visible to every row, key base + j to row i iff bit j of
+// m_i = (word & low n_b bits) | 1 << i is set, and the row's lower limit is base + popcount(m_i) - window: its depth in its own
+// branch where the triangle has its index.  Only the masking block of the tile loop differs, and only in the tiles that reach past
+// max(base, 0) -- at most two per sequence, in whichever split they fall -- or start below the last lower limit.  The lane's word is
+// loaded INSIDE that block, through a descriptor over the sequence's n_b words, from the row index that row_end already holds; a
+// lane past the live rows loads nothing (its offset is the descriptor's size) and takes the triangle's word of that index, so it
+// votes where the causal kernel's dead lane votes.  Nothing of the mask lives in a VGPR outside the block.  With
+// the word (2 << i) - 1 every score takes the decision the kPacked causal kernel takes: the bits are that kernel's.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -278,6 +304,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto ra = ragged_part(cache...);
     constexpr bool kPacked = (IsPackedArgs<Cache>::value || ...);
     [[maybe_unused]] const auto ka = packed_part(cache...);
+    constexpr bool kTree = (IsTreeArgs<Cache>::value || ...);
+    [[maybe_unused]] const auto ta = tree_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -569,6 +597,45 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             }
         }
         if constexpr (kWindow) {
+            // kTree: the tiles that hold one of the step's own tokens (keys from max(base, 0) on), the split's end or a row's lower
+            // limit.  The lane's row index comes back from row_end, its word from memory, and both die with the block; the thread id
+            // and row_end go through an empty asm so that "is my row live", the word's offset and the row's bit are derived here and
+            // not kept in registers from the prologue (hoisted, they are five VGPRs across the loop, which the d = 64 kernels spill)
+            if constexpr (kTree) {
+                const int base = (int)nkeys - (int)n_q;   // wave-uniform
+                if (kv0 + kBlockN > min((unsigned)max(base, 0), key1) || kv0 < lo_hi) {
+                    unsigned t = tid;
+                    int re = row_end;   // through the asm too: what follows from the row index is made here, not hoisted out of the loop
+                    asm volatile("" : "+v"(t), "+v"(re));
+                    const unsigned ri = (unsigned)(re - base - 1);   // < n_q for every lane
+                    const bool lv = qb * (unsigned)kRows + (t >> 6) * 32u + (t & 31u) < live;
+                    const u32x2 w = buf_load8(make_rsrc(ta.tree_mask + pv.s, n_q * 8u), lv ? ri * 8u : n_q * 8u);
+                    unsigned long long m = ((unsigned long long)w[1] << 32) | w[0];
+                    m = lv ? ((m & (~0ull >> (64u - n_q))) | (1ull << ri)) : ((2ull << ri) - 1ull);
+                    // The tile's 64 keys as one word per lane, bit o for key kv0 + o, made in place in the two registers of m so that the
+                    // block needs little more than the windowed one's (the d = 64 kernels have no register to spare).  The row's lower
+                    // limit first, the only other per-lane value
+                    const unsigned lo = (unsigned)max(base + (int)__builtin_popcountll(m) - wa.window, 0);
+                    // ... the step's tokens the row sees, all keys below base, none from key1 on: d, and with it every shift and
+                    // constant here, is wave-uniform (key1 > kv0: the tile exists)
+                    const int d = (int)kv0 - base;
+                    const unsigned upto = min(key1 - kv0, 64u);
+                    const unsigned long long ends = upto < 64u ? (1ull << upto) - 1ull : ~0ull;
+                    if (d >= 0) m = d < 64 ? m >> d : 0ull;
+                    else m = d > -64 ? (m << -d) | ((1ull << -d) - 1ull) : ~0ull;
+                    m &= ends;
+                    // ... and none below lo
+                    const unsigned below = lo > kv0 ? min(lo - kv0, 64u) : 0u;
+                    m = below < 64u ? (m >> below) << below : 0ull;
+                    m >>= (t >> 3) & 4u;   // the lane's keys start at kv0 + 4 h; h from t: see above
+                    const unsigned vis2[2] = {(unsigned)m, (unsigned)(m >> 32)};
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                        for (int i = 0; i < 16; ++i)
+                            if (!(vis2[kb] & (1u << ((i & 3) + 8 * (i >> 2))))) s[kb][i] = -INFINITY;
+                }
+            } else
             // keys outside [lo, hi) -> -inf: hi is `lim` above, lo the row's lower limit; one unsigned compare per score
             if (kv0 + kBlockN > lim_lo || kv0 < lo_hi) {
                 const unsigned lo = (unsigned)max(row_end - wa.window, 0);

@@ -59,11 +59,17 @@ __device__ __forceinline__ bool seq_owns(const int* cu, unsigned b, int total, u
 // kRope: 0 no rotation (no Q blocks are launched), 1 half-split pairs, 2 interleaved pairs.  A row that no sequence owns retires
 // before anything is formed from it: nothing is loaded, nothing is written, its Qout row stays as it was.  For an owned row
 // i = t - s_b lies in [0, m_b) whatever the vector holds, and from there on the steps are fa_kvcache_append_ragged_kernel's.
-template <typename T, int D, bool kPaged, bool kFp8, int kRope, bool kHeadMajor>
+// Pos: nothing, or -- fa_kvcache_append_varlen_ex with positions, rotary forms only -- one const int*: the table row of token t is
+// then positions[t] clamped into [0, max_pos), read once the row has an owner, while the destination stays slot p.  A trailing pack
+// and not a flag with an argument of its own, so that the plain instantiations keep their argument list and their code.
+template <typename T, int D, bool kPaged, bool kFp8, int kRope, bool kHeadMajor, typename... Pos>
 __global__ void __launch_bounds__(kAppendThreads)
 fa_kvcache_append_varlen_kernel(const uint16_t* __restrict__ Knew, const uint16_t* __restrict__ Vnew, void* __restrict__ Kdst,
-                                void* __restrict__ Vdst, const uint16_t* Q, uint16_t* Qout, AppendDev a, RopeDev r, PackedDev k)
+                                void* __restrict__ Vdst, const uint16_t* Q, uint16_t* Qout, AppendDev a, RopeDev r, PackedDev k,
+                                Pos... positions)
 {
+    static_assert(sizeof...(Pos) <= 1 && (std::is_same_v<Pos, const int*> && ...), "at most one position vector");
+    static_assert(sizeof...(Pos) == 0 || kRope != 0, "positions belong to the rotary forms");
     constexpr int kLgChunks = D == 64 ? 3 : 4;   // log2 of the 16-byte chunks per row
     const unsigned which = blockIdx.x < r.kv_blocks ? 0u : (blockIdx.x < 2 * r.kv_blocks ? 1u : 2u);   // K, V, Q
     const bool is_q = which == 2, is_v = which == 1;
@@ -119,14 +125,19 @@ fa_kvcache_append_varlen_kernel(const uint16_t* __restrict__ Knew, const uint16_
     }
 
     if constexpr (kRope != 0) {   // K or Q of a rotary form: fa_kvcache_append_rope_kernel's two calls
+        unsigned rp = p;   // the table row: the slot, or the token's entry of the vector (rope_row clamps it at max_pos - 1)
+        if constexpr (sizeof...(Pos) == 1) {
+            const int at = (positions, ...)[t];
+            rp = at < 0 ? 0u : (unsigned)at;
+        }
         if (is_q) {
             const u32x4* src = reinterpret_cast<const u32x4*>(Q) + ((size_t)t * (size_t)k.q_t + (size_t)hh * (size_t)k.q_h + c);
             char* dst = reinterpret_cast<char*>(Qout) + ((size_t)t * (size_t)k.qo_t + (size_t)hh * (size_t)k.qo_h) * 16;
-            rope_row<T, false, kRope == 2, false>(src, dst, c, p, 1.0f, r);
+            rope_row<T, false, kRope == 2, false>(src, dst, c, rp, 1.0f, r);
         } else {
             const float sc = (kFp8 && a.k_scale) ? a.k_scale[h] : 1.0f;
             const u32x4* src = reinterpret_cast<const u32x4*>(Knew) + ((size_t)t * (size_t)k.k_t + (size_t)hh * (size_t)k.k_h + c);
-            rope_row<T, kFp8, kRope == 2, kNt>(src, static_cast<char*>(Kdst) + dst_row * (kFp8 ? D : D * 2), c, p, sc, r);
+            rope_row<T, kFp8, kRope == 2, kNt>(src, static_cast<char*>(Kdst) + dst_row * (kFp8 ? D : D * 2), c, rp, sc, r);
         }
     }
 }
@@ -148,6 +159,7 @@ namespace {
 
 struct VarlenAppendCall {
     const fa_kvappend_varlen_desc* d;
+    const int* positions;   // fa_kvcache_append_varlen_ex, rotary forms only; null: the plain kernels
     AppendDev dev;
     RopeDev r;
     PackedDev k;
@@ -159,6 +171,16 @@ template <typename T, int D, bool kPaged, bool kFp8, int kRope>
 hipError_t launch_varlen(const VarlenAppendCall& c)
 {
     const fa_kvappend_varlen_desc* d = c.d;
+    bool launched = false;
+    if constexpr (kRope != 0) {
+        if (c.positions) {
+            FA_LAUNCH((fa_kvcache_append_varlen_kernel<T, D, kPaged, kFp8, kRope, FA_APPEND_VARLEN_ORDER != 0, const int*>), dim3(c.blocks),
+                      dim3(kAppendThreads), 0, c.stream, static_cast<const uint16_t*>(d->Knew), static_cast<const uint16_t*>(d->Vnew), d->K,
+                      d->V, static_cast<const uint16_t*>(d->Q), static_cast<uint16_t*>(d->Qout), c.dev, c.r, c.k, c.positions);
+            launched = true;
+        }
+    }
+    if (!launched)
     FA_LAUNCH((fa_kvcache_append_varlen_kernel<T, D, kPaged, kFp8, kRope, FA_APPEND_VARLEN_ORDER != 0>), dim3(c.blocks),
               dim3(kAppendThreads), 0, c.stream, static_cast<const uint16_t*>(d->Knew), static_cast<const uint16_t*>(d->Vnew), d->K, d->V,
               static_cast<const uint16_t*>(d->Q), static_cast<uint16_t*>(d->Qout), c.dev, c.r, c.k);
@@ -205,9 +227,11 @@ bool overlap(const void* x, unsigned __int128 xbytes, const void* y, unsigned __
 }  // namespace
 
 // Every check, then the one or two launches.  The grid follows (total_new, Hkv, G, d) and whether there is a Q: host integers only.
-hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* d)
+// positions (fa_kvcache_append_varlen_ex; null: none) selects the position instantiations of the same kernel.
+static hipError_t append_varlen_checked(const ::fa_kvappend_varlen_desc* d, const int* positions)
 {
     if (!d || d->size != sizeof(fa_kvappend_varlen_desc)) return hipErrorInvalidValue;
+    if (positions && (!d->rope_cos || (reinterpret_cast<uintptr_t>(positions) & 3u))) return hipErrorInvalidValue;
     if (d->kv_dtype != FA_KV_16BIT && d->kv_dtype != FA_KV_FP8_E4M3) return hipErrorInvalidValue;
     const bool fp8 = d->kv_dtype == FA_KV_FP8_E4M3, paged = d->block_table != nullptr, rope = d->rope_cos != nullptr;
     if (!fp8 && (d->k_scale || d->v_scale)) return hipErrorInvalidValue;               // a 16-bit cache has no scales
@@ -259,6 +283,7 @@ hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* d)
     const bool has_q = rope && d->Q;
     VarlenAppendCall c;
     c.d = d;
+    c.positions = positions;
     c.stream = static_cast<hipStream_t>(d->stream);
     c.dev = {d->seqlens_k, d->block_table, d->k_scale, d->v_scale, (unsigned)chunks, d->Hkv, d->total_new, Ncap,
              paged ? d->max_pages : 0, paged ? d->num_pages : 0, lg_page};
@@ -273,6 +298,14 @@ hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* d)
     if (d->dtype == 1)
         return d->d == 64 ? varlen_rope_modes<BF16, 64>(c, paged, fp8, mode) : varlen_rope_modes<BF16, 128>(c, paged, fp8, mode);
     return d->d == 64 ? varlen_rope_modes<F16, 64>(c, paged, fp8, mode) : varlen_rope_modes<F16, 128>(c, paged, fp8, mode);
+}
+
+hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* d) { return append_varlen_checked(d, nullptr); }
+
+hipError_t kvcache_append_varlen_ex(const ::fa_kvappend_varlen_desc* d, const ::fa_kvappend_varlen_opts* opts)
+{
+    if (opts && opts->size != sizeof(fa_kvappend_varlen_opts)) return hipErrorInvalidValue;
+    return append_varlen_checked(d, opts ? opts->positions : nullptr);
 }
 
 }  // namespace fa

@@ -643,7 +643,7 @@ def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_tabl
 
 def fa_kvcache_decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, causal: bool = False,
                              scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None, workspace=None, stream=None,
-                             window=None, softcap: float = 0.0, sinks=None, lse=None):
+                             window=None, softcap: float = 0.0, sinks=None, lse=None, tree_mask=None):
     """Split-KV decode on a token-packed batch (fa_kvcache_decode_varlen): the read half of fa_kvcache_append_varlen for a step whose
     sequences bring few rows each (one token per sequence, speculative tokens, a short chunk beside decode tokens).  It is
     fa_forward_kvcache(seqlens_q=...) -- the split-KV stream with the G heads of a group folded into the rows -- with q, the result and
@@ -668,19 +668,25 @@ def fa_kvcache_decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, ca
     workspace: optional uint8 device tensor of at least kvcache_decode_varlen_workspace_bytes(...).
     Nothing is read on the host: append_varlen(seqlens_out=lens, q=q) then this call with cu_seqlens_q = cu_seqlens_new and
     cache_seqlens = lens, captured once, serves every step of the same total_q; the replay follows the vectors, the table and the sinks.
+    tree_mask (fa_kvcache_decode_varlen_ex): None, or an int64 tensor (total_q,) on q's device, one word per token row, for the verify
+    step of tree speculation.  It takes the causal triangle's place (causal must be True, max_seqlen_q <= 64): with base = L_b - n_b,
+    row i sees every key below base and key base + j iff bit j of (tree_mask[s_b + i] & low n_b bits) | 1 << i is set; under a window
+    lo_i = max(0, base + popcount - window).  tree_from_parents() makes the words from parent indices; with (1 << (i + 1)) - 1 the
+    result has the bits of causal=True.  Words of tokens of no sequence are not read; a captured call follows the tensor in place.
     An fp8 cache is fa_kvcache_decode_varlen_fp8's."""
     return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
-                          return_lse, out, workspace, stream, window, softcap, sinks, lse)
+                          return_lse, out, workspace, stream, window, softcap, sinks, lse, tree_mask=tree_mask)
 
 
 def fa_kvcache_decode_varlen_fp8(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, k_scale=None,
                                  v_scale=None, causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
-                                 out=None, workspace=None, stream=None, window=None, softcap: float = 0.0, sinks=None, lse=None):
+                                 out=None, workspace=None, stream=None, window=None, softcap: float = 0.0, sinks=None, lse=None,
+                                 tree_mask=None):
     """fa_kvcache_decode_varlen against an fp8 cache: k_cache, v_cache (or the pools) contiguous torch.float8_e4m3fn (OCP e4m3fn; fnuz,
     e5m2 and 16-bit caches are refused), k_scale, v_scale float32 [Hkv] or None (1.0), read on the device only; scales, logits and lse
-    as in fa_forward_kvcache_fp8, everything else as in fa_kvcache_decode_varlen."""
+    as in fa_forward_kvcache_fp8, everything else as in fa_kvcache_decode_varlen, tree_mask included."""
     return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
-                          return_lse, out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale))
+                          return_lse, out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale), tree_mask=tree_mask)
 
 
 def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, d: int, Ncap: int = 0, max_pages: int = 0,
@@ -694,9 +700,10 @@ def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q
 
 
 def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse,
-                   out, workspace, stream, window, softcap, sinks, lse, scales=None):
-    """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one.  Shapes and
-    dtypes are judged before anything needs a device."""
+                   out, workspace, stream, window, softcap, sinks, lse, scales=None, tree_mask=None):
+    """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one; tree_mask is
+    None (fa_kvcache_decode_varlen) or the words of fa_kvcache_decode_varlen_ex.  Shapes and dtypes are judged before anything needs a
+    device."""
     import torch
     fp8 = scales is not None
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
@@ -723,6 +730,17 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
     if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1:
         raise ValueError("max_seqlen_q must be an int >= 1: the most rows a sequence may have")
+    if tree_mask is not None:
+        if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+            raise ValueError("tree_mask must be an int64 tensor: one 64-bit word per token row")
+        if tree_mask.shape != (total_q,) or not tree_mask.is_contiguous():
+            raise ValueError("tree_mask must be a contiguous tensor (total_q,)")
+        if tree_mask.device != q.device:
+            raise ValueError("tree_mask must live on q's device")
+        if not causal:
+            raise ValueError("tree_mask takes the causal triangle's place: causal must be True")
+        if max_seqlen_q > 64:
+            raise ValueError("tree_mask holds one bit per token of a sequence's step: max_seqlen_q must be <= 64")
     window = _window(0 if window is None else window)
     softcap = _softcap(softcap)
     sink_ptr = _sinks_ptr(sinks, Hq, q.device)
@@ -784,9 +802,14 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
         scale=float(_scale_or_default(scale, d)), causal=int(bool(causal)), window=window, softcap=softcap, in_dtype=_in_dt(q.dtype),
         out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len, stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, workspace,
-                                       *(scales or ()))):
-        code = capi.lib().fa_kvcache_decode_varlen(desc)
-    capi.check("fa_kvcache_decode_varlen", code)
+                                       tree_mask, *(scales or ()))):
+        if tree_mask is None:
+            code = capi.lib().fa_kvcache_decode_varlen(desc)
+        else:
+            opts = capi.new_desc(capi.KvDecodeTreeOpts)
+            opts.tree_mask = tree_mask.data_ptr()
+            code = capi.lib().fa_kvcache_decode_varlen_ex(desc, opts)
+    capi.check("fa_kvcache_decode_varlen" if tree_mask is None else "fa_kvcache_decode_varlen_ex", code)
     return (out, lse) if return_lse else out
 
 
@@ -1068,7 +1091,8 @@ def fa_kvcache_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, k_sca
 
 
 def fa_kvcache_append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None,
-                             stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False) -> None:
+                             stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False,
+                             positions=None) -> None:
     """The append of a token-packed batch (fa_kvcache_append_varlen): the write half of fa_forward_varlen_kvcache.  k_new, v_new
     (total_new, Hkv, d) fp16 or bf16 device tensors of ONE dtype, d in {64,128}, taken as they lie: any token and head strides with a
     contiguous last dimension (strides multiples of 8 elements, 16-byte aligned storage), so the K and V views of a fused
@@ -1085,23 +1109,29 @@ def fa_kvcache_append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cac
     in place; q_out rows of no sequence are not written.
     Every kept byte is what fa_kvcache_append(seqlens_new=m) writes from the padded [B,Hkv,max m,d] copy of the same rows.  Nothing is
     read on the host and there is no workspace: append_varlen(seqlens_out=lens) then
-    fa_forward_varlen_kvcache(q, ..., cu_seqlens_new, lens), captured once, serves every step of the same total_new."""
+    fa_forward_varlen_kvcache(q, ..., cu_seqlens_new, lens), captured once, serves every step of the same total_new.
+    positions (fa_kvcache_append_varlen_ex; rotary only): None, or an int32 contiguous tensor (total_new,) on k_new's device.  Token t
+    is then rotated (its K row and its q rows) at table row clamp(positions[t], 0, max_pos - 1) while it still goes to slot L_b + i:
+    the drafts of a speculation tree sit in consecutive slots and share positions, their depths (tree_from_parents).  Entries of rows
+    of no sequence are not read; positions[s_b + i] = L_b + i gives the bytes of the call without positions."""
     _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
-                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved))
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), positions=positions)
 
 
 def fa_kvcache_append_varlen_fp8(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None,
                                  k_scale=None, v_scale=None, stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None,
-                                 rotary_interleaved=False) -> None:
+                                 rotary_interleaved=False, positions=None) -> None:
     """fa_kvcache_append_varlen into an fp8 cache: k_cache, v_cache (or the pools) torch.float8_e4m3fn, k_scale, v_scale float32 [Hkv]
-    or None (1.0); codes and scales as in fa_kvcache_append_fp8, everything else as in fa_kvcache_append_varlen."""
+    or None (1.0); codes and scales as in fa_kvcache_append_fp8, everything else as in fa_kvcache_append_varlen, positions included."""
     _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
-                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), scales=(k_scale, v_scale))
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), scales=(k_scale, v_scale), positions=positions)
 
 
-def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream, rope, scales=None):
+def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream, rope, scales=None,
+                   positions=None):
     """The two packed append front ends: scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one; rope is
-    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved).  Shapes and dtypes are judged before anything needs a device."""
+    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved); positions is None or the vector of fa_kvcache_append_varlen_ex.  Shapes
+    and dtypes are judged before anything needs a device."""
     import torch
     fp8 = scales is not None
     paged = block_table is not None
@@ -1147,6 +1177,15 @@ def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, se
     ks_ptr, vs_ptr = _scale_ptrs(scales[0], scales[1], Hkv) if fp8 else (None, None)
     q, q_out, cos, sin, interleaved = rope
     rope_fields, rope_tensors = {}, ()
+    if positions is not None:
+        if cos is None:
+            raise ValueError("positions are rotary positions: they need rotary_cos")
+        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32:
+            raise ValueError("positions must be an int32 tensor: one rotary position per token row")
+        if positions.shape != (total,) or not positions.is_contiguous():
+            raise ValueError("positions must be a contiguous tensor (total_new,)")
+        if positions.device != k_new.device:
+            raise ValueError("positions must live on k_new's device")
     if cos is None:
         if q is not None or q_out is not None or sin is not None:
             raise ValueError("q, q_out and rotary_sin are arguments of the rotary append: they need rotary_cos")
@@ -1191,9 +1230,56 @@ def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, se
         total_new=total, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, dtype=_in_dt(k_new.dtype),
         k_stride_t=kt, k_stride_h=kh, v_stride_t=vt, v_stride_h=vh, stream=_stream_ptr(stream), **rope_fields)
     with torch.cuda.device(_one_device(k_new, v_new, k_dst, v_dst, cu_seqlens_new, block_table, *(scales or ()), cache_seqlens, seqlens_out,
-                                       *rope_tensors)):
-        code = capi.lib().fa_kvcache_append_varlen(desc)
-    capi.check("fa_kvcache_append_varlen", code)
+                                       positions, *rope_tensors)):
+        if positions is None:
+            code = capi.lib().fa_kvcache_append_varlen(desc)
+        else:
+            opts = capi.new_desc(capi.KvAppendVarlenOpts)
+            opts.positions = positions.data_ptr()
+            code = capi.lib().fa_kvcache_append_varlen_ex(desc, opts)
+    capi.check("fa_kvcache_append_varlen" if positions is None else "fa_kvcache_append_varlen_ex", code)
+
+
+def tree_from_parents(parents, cu_seqlens):
+    """The tree_mask words and rotary depths of a step's draft trees, from parent indices.  parents: int32 (total,), for each token the
+    index WITHIN ITS SEQUENCE of its parent, -1 for a root; a parent precedes its child.  cu_seqlens: (B+1,) integer tensor; sequence b
+    owns the tokens [cu[b], cu[b+1]).  -> (tree_mask int64 (total,), depth int32 (total,)): bit j of token i's word is set iff token j
+    of its sequence is i itself or one of its ancestors, and depth is the number of ancestors, so that
+    positions = L_before[b] + depth is the rotary position of fa_kvcache_append_varlen(positions=...).  Tokens of no sequence get 0 and 0.
+    Plain torch on the inputs' device (a host-side helper, not a kernel; the bounds are read on the host).  Raises ValueError on a
+    sequence of more than 64 tokens and on a parent that does not precede its child."""
+    import torch
+    if not isinstance(parents, torch.Tensor) or parents.dim() != 1 or parents.dtype != torch.int32:
+        raise ValueError("parents must be an int32 tensor (total,)")
+    if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.is_floating_point():
+        raise ValueError("cu_seqlens must be an integer tensor of B+1 entries")
+    total = parents.numel()
+    cu = [min(max(int(c), 0), total) for c in cu_seqlens.tolist()]
+    mask = torch.zeros(total, dtype=torch.int64, device=parents.device)
+    depth = torch.zeros(total, dtype=torch.int32, device=parents.device)
+    for b in range(len(cu) - 1):
+        s, n = cu[b], max(cu[b + 1] - cu[b], 0)
+        if n == 0:
+            continue
+        if n > 64:
+            raise ValueError(f"sequence {b} has {n} tokens: a tree_mask word holds 64")
+        par = parents[s:s + n].to(torch.int64)
+        idx = torch.arange(n, device=parents.device)
+        if bool(((par < -1) | (par >= idx)).any()):
+            raise ValueError(f"sequence {b}: a parent must be -1 or precede its child")
+        # bit 63 is the sign bit of the word: 1 << 63 wraps to it, which is the pattern the kernel reads
+        m = torch.ones(n, dtype=torch.int64, device=parents.device) << idx
+        dep = torch.zeros(n, dtype=torch.int32, device=parents.device)
+        anc = par.clone()
+        while bool((anc >= 0).any()):   # one level of every token's chain per pass: at most n - 1 passes
+            has = anc >= 0
+            at = anc.clamp(min=0)
+            m = torch.where(has, m | (torch.ones_like(m) << at), m)
+            dep = dep + has.to(torch.int32)
+            anc = torch.where(has, par[at], anc)
+        mask[s:s + n] = m
+        depth[s:s + n] = dep
+    return mask, depth
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

@@ -47,6 +47,12 @@ eager fallback.  Registered on first use:
     # ... and against an fp8 (e4m3fn) cache with per-head scales (ops.fa_forward_varlen_kvcache_fp8)
     o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_fp8(q, k_cache8, v_cache8, cu_seqlens_q, cache_seqlens, block_table, k_scale,
                                                            v_scale, scale, causal, window, sinks, softcap, out_f32)
+    # the tree step (speculative decoding): the packed append with explicit rotary positions (int32, total_new) in front of q, and the
+    # packed split-KV decode with one int64 ancestor word per token row behind block_table; _fp8 forms take k_scale, v_scale as above
+    torch.ops.fa_mi355.append_varlen_pos(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table,
+                                         positions, q, q_out, rotary_cos, rotary_sin, interleaved)
+    o, lse = torch.ops.fa_mi355.decode_varlen_tree(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, tree_mask,
+                                                   scale, causal, window, sinks, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -58,7 +64,8 @@ _registered = False
 def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
-    .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8."""
+    .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
+    .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree and .decode_varlen_tree_fp8."""
     global _registered
     if _registered:
         return
@@ -170,6 +177,18 @@ def register() -> None:
         define(name, VARLEN_APPEND + mid + VARLEN_APPEND_TAIL, ("k_cache", "v_cache", "seqlens_out", "q", "q_out"), fn, "----c",
                varlen_append_kw, lambda *args: None)
 
+    # the same with explicit rotary positions (fa_kvcache_append_varlen_ex): `Tensor positions` (int32, total_new) stands in front of q
+    def varlen_append_pos_kw(k_new, cache_seqlens, seqlens_out, block_table, *rest):
+        *scales, positions, q, q_out, rotary_cos, rotary_sin, interleaved = rest
+        kw = varlen_append_kw(k_new, cache_seqlens, seqlens_out, block_table, *scales, q, q_out, rotary_cos, rotary_sin, interleaved)
+        kw.update(positions=positions.contiguous())
+        return kw
+
+    for name, mid, fn in (("append_varlen_pos", "", ops.fa_kvcache_append_varlen),
+                          ("append_varlen_pos_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_append_varlen_fp8)):
+        define(name, VARLEN_APPEND + mid + "Tensor positions, " + VARLEN_APPEND_TAIL, ("k_cache", "v_cache", "seqlens_out", "q", "q_out"),
+               fn, "----c", varlen_append_pos_kw, lambda *args: None)
+
     # The merge of attention states over key ranges (ops.fa_merge_states) on stacked parts, and shared-prefix decode on a contiguous
     # 16-bit suffix (ops.fa_forward_kvcache_shared_prefix; the paged and fp8 forms are the front end's).
     @torch.library.custom_op("fa_mi355::merge_states", mutates_args=(), device_types="cuda",
@@ -267,6 +286,18 @@ def register() -> None:
     for name, mid, fn in (("decode_varlen", "", ops.fa_kvcache_decode_varlen),
                           ("decode_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
         define(name, DECODE_VARLEN + mid + DECODE_VARLEN_TAIL, (), decode_varlen(fn), "-ccc-oo",
+               decode_varlen_kw, varlen_fake)
+
+    # the same with a tree mask (fa_kvcache_decode_varlen_ex): `Tensor tree_mask` (int64, total_q) follows block_table; causal must be True
+    def decode_varlen_tree(fn):
+        def call(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, tree_mask, **kw):
+            return fn(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=cache_seqlens, block_table=block_table,
+                      tree_mask=tree_mask, **kw)
+        return call
+
+    for name, mid, fn in (("decode_varlen_tree", "", ops.fa_kvcache_decode_varlen),
+                          ("decode_varlen_tree_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
+        define(name, DECODE_VARLEN + "Tensor tree_mask, " + mid + DECODE_VARLEN_TAIL, (), decode_varlen_tree(fn), "-ccc-ooc",
                decode_varlen_kw, varlen_fake)
 
     _registered = True

@@ -566,6 +566,25 @@ typedef struct fa_kvappend_varlen_desc {
 } fa_kvappend_varlen_desc;
 int fa_kvcache_append_varlen(const fa_kvappend_varlen_desc* desc);
 
+/* fa_kvcache_append_varlen with explicit rotary positions, for a step whose tokens do not sit one behind the other: the drafts of a
+ * speculation TREE occupy consecutive cache slots while siblings share a position, their depth.
+ * opts == NULL or opts->positions == NULL: the call IS fa_kvcache_append_varlen(desc), bit for bit.
+ * With positions: token i of sequence b (token row t = s_b + i) still goes to SLOT L_b + i -- the drop rules, the table reads, the fp8
+ * recipe and seqlens_out are the plain entry's -- and its K row and its Q rows (t, hq) are rotated at table row
+ * clamp(positions[t], 0, max_pos - 1) in the place of min(L_b + i, max_pos - 1).  The pinned arithmetic is unchanged, so the bytes are
+ * those of the plain entry's recipe at that table row, and positions[s_b + i] = L_b + i returns the plain call's bytes.  Positions of
+ * rows of no sequence are never read; out-of-range positions clamp and never fault.  positions is read on the device only: a captured
+ * call follows it when it is rewritten in place.
+ * Rejected with hipErrorInvalidValue before the device is touched: an opts->size other than sizeof(fa_kvappend_varlen_opts);
+ * positions without rope_cos; positions that are not 4-byte aligned; everything fa_kvcache_append_varlen rejects.
+ * Not part of this entry: positions on the padded fa_kvcache_append_ex; a per-sequence position offset; compacting an accepted
+ * path's K/V rows to consecutive slots after verification (by copies or by page-table edits).  NOT a reference entry point. */
+typedef struct fa_kvappend_varlen_opts {
+    size_t size;            /* sizeof(fa_kvappend_varlen_opts) */
+    const int* positions;   /* device, [total_new] int32; NULL: position = slot (the plain entry's rule) */
+} fa_kvappend_varlen_opts;
+int fa_kvcache_append_varlen_ex(const fa_kvappend_varlen_desc* desc, const fa_kvappend_varlen_opts* opts);
+
 /* Merge of attention states over disjoint key ranges: the rule the decode entries above promise (fa_forward_kvcache),
  *   lse = ln sum_r exp(lse_r),   O = sum_r O_r exp(lse_r - lse),
  * applied by ONE kernel to R parts, each an (O_r, lse_r) pair as a decode entry returns it with lse.  A part is addressed by rows:
@@ -858,6 +877,36 @@ typedef struct fa_kvdecode_varlen_desc {
 } fa_kvdecode_varlen_desc;
 size_t fa_kvcache_decode_varlen_workspace_bytes(const fa_kvdecode_varlen_desc* desc);
 int fa_kvcache_decode_varlen(const fa_kvdecode_varlen_desc* desc);
+
+/* fa_kvcache_decode_varlen with a tree mask: the verify step of tree speculation (Medusa, EAGLE, SpecInfer), where a token sees the
+ * committed context plus its own ancestors among the step's tokens and not every earlier token of the step.
+ * opts == NULL or opts->tree_mask == NULL: the call IS fa_kvcache_decode_varlen(desc) -- same checks, same kernels, same bits.
+ * With a mask: s_b, n_b, L_b are fa_kvcache_decode_varlen's (L_b includes the step's own tokens) and base_b = L_b - n_b, which may be
+ * negative; token s_b + j is the key at cache position base_b + j.  For row i < n_b
+ *   m_i = (tree_mask[s_b + i] & low n_b bits) | (1 << i):  bits at or above n_b are ignored, a token always sees itself, bits above i
+ *         are legal, and nothing checks that the mask is ancestor-closed;
+ *   row i sees key k iff 0 <= k < L_b, k >= lo_i and (k < base_b -- committed context, always visible -- or bit k - base_b of m_i);
+ *   lo_i = max(0, base_b + popcount(m_i) - W) under a window W (0 without): for an ancestor-closed mask popcount(m_i) - 1 is the
+ *         token's depth, so the window is measured from the token's position in its own branch; start_b = max(0, base_b + 1 - W) as
+ *         in the plain entry, and no row reaches below it.
+ * Everything else is fa_kvcache_decode_varlen's: the soft-cap before the masks, the sink once per row, the fp8 scale rules; a row
+ * without a key (possible with base_b + i < 0) is O = 0, lse = -inf or the sink logit; tokens of no sequence are neither read nor
+ * written, their mask words included; n_b = 0 reads nothing; split count, grid and workspace follow (B, Hkv, G, max_q, span) only, so
+ * fa_kvcache_decode_varlen_workspace_bytes(desc) sizes the workspace of this entry too; nothing on the host reads device data, and a
+ * captured call follows tree_mask when it is rewritten in place.
+ * BITS: with tree_mask[s_b + i] = (1 << (i + 1)) - 1 on every live row the call returns the bits of fa_kvcache_decode_varlen with
+ * causal = 1, for O and lse, for every split count, contiguous and paged, 16-bit and e4m3fn, with and without window, sinks, soft-cap.
+ * hipErrorInvalidValue, before the device is touched: an opts->size other than sizeof(fa_kvdecode_tree_opts); with a mask,
+ * causal != 1 (the tree takes the triangle's place), max_q > 64, or a tree_mask that is not 8-byte aligned; everything
+ * fa_kvcache_decode_varlen refuses.
+ * Not part of this entry: trees of more than 64 tokens per sequence, or a dense or bit-packed [n, n] mask; a mask on the prefill
+ * entries or on the padded fa_kvcache_decode; per-head masks; a shared prefix under a tree; the commit after verification
+ * (compacting the accepted path's K/V rows to consecutive slots, by copies or by page-table edits).  NOT a reference entry point. */
+typedef struct fa_kvdecode_tree_opts {
+    size_t size;                          /* sizeof(fa_kvdecode_tree_opts); any other value is refused */
+    const unsigned long long* tree_mask;  /* device, [total_q] 64-bit words, one per token row; NULL: no tree */
+} fa_kvdecode_tree_opts;
+int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, const fa_kvdecode_tree_opts* opts);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
