@@ -184,6 +184,19 @@ class KvAppendVarlenOpts(C.Structure):
             self.size = C.sizeof(KvAppendVarlenOpts)
 
 
+class KvCommitDesc(C.Structure):
+    """fa_kvcommit_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("K", C.c_void_p), ("V", C.c_void_p), ("seqlens_k", C.c_void_p), ("seqlens_out", C.c_void_p),
+                ("accept_mask", C.c_void_p), ("block_table", C.c_void_p), ("kv_dtype", C.c_int), ("dtype", C.c_int), ("B", C.c_int),
+                ("Hkv", C.c_int), ("d", C.c_int), ("max_new", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int),
+                ("page_size", C.c_int), ("max_pages", C.c_int), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(KvCommitDesc)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -228,6 +241,8 @@ def _signatures() -> dict:
         "fa_kvcache_decode_varlen_ex": (i, [C.POINTER(KvDecodeVarlenDesc), C.POINTER(KvDecodeTreeOpts)]),
         # the packed append with explicit rotary positions; a null opts is fa_kvcache_append_varlen
         "fa_kvcache_append_varlen_ex": (i, [C.POINTER(KvAppendVarlenDesc), C.POINTER(KvAppendVarlenOpts)]),
+        # the commit of a tree step: the accepted path's K/V rows to consecutive slots, one 64-bit word per sequence
+        "fa_kvcache_commit": (i, [C.POINTER(KvCommitDesc)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

@@ -313,6 +313,8 @@ FA_EXPORT int fa_kvcache_append_varlen_ex(const fa_kvappend_varlen_desc* desc, c
     return (int)fa::kvcache_append_varlen_ex(desc, opts);
 }
 
+FA_EXPORT int fa_kvcache_commit(const fa_kvcommit_desc* desc) { return (int)fa::kvcache_commit(desc); }
+
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 
 FA_EXPORT int fa_forward_varlen(const fa_varlen_desc* desc) { return (int)fa::varlen_dispatch(desc); }

@@ -16,6 +16,7 @@ struct fa_kvappend_varlen_desc;
 struct fa_kvdecode_varlen_desc;
 struct fa_kvdecode_tree_opts;
 struct fa_kvappend_varlen_opts;
+struct fa_kvcommit_desc;
 
 namespace fa {
 
@@ -227,6 +228,8 @@ hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
 // fa_kvcache_append_varlen_ex: the options' checks, then the same; positions (device, total_new int32, or null) are the rotary table
 // rows of the tokens in place of their slots
 hipError_t kvcache_append_varlen_ex(const ::fa_kvappend_varlen_desc* desc, const ::fa_kvappend_varlen_opts* opts);
+// fa_kvcache_commit (fa_kvcache_commit.hip): the checks and the one or two launches; the descriptor is the public one, as it is
+hipError_t kvcache_commit(const ::fa_kvcommit_desc* desc);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

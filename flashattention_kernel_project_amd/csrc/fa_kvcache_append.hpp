@@ -2,7 +2,8 @@
 // fa_kvcache_append_rope.hip: the _rope entries; fa_kvcache_append_ragged.hip: fa_kvcache_append_ex with a token count per sequence;
 // fa_kvcache_append_varlen.hip: fa_kvcache_append_varlen on token-packed sources):
 // the kernels' argument pack, the length clamp, the page lookup with its 64-bit destination row, the e4m3fn quantisation, and the
-// rotation of one row chunk.  Private to csrc/.  Everything is in an unnamed namespace: each unit gets its own
+// rotation of one row chunk.  fa_kvcache_commit.hip, which moves rows the appends placed, takes the clamp and the page lookup from here
+// too.  Private to csrc/.  Everything is in an unnamed namespace: each unit gets its own
 // copy, all of it is inlined, and the kernels' symbols stay what they were when the helpers lived in fa_kvcache_append.hip.
 #pragma once
 #include "fa_dispatch.hpp"

@@ -1282,6 +1282,82 @@ def tree_from_parents(parents, cu_seqlens):
     return mask, depth
 
 
+def tree_accept_mask(tree_mask, cu_seqlens, last):
+    """The accept words of fa_kvcache_commit from a step's tree: for each sequence the tree_mask word of its last accepted token,
+    tree_mask[cu_seqlens[b] + last[b]] -- that token's own bit and its ancestors', the path that is kept.  tree_mask: int64 (total,)
+    as tree_from_parents returns it; cu_seqlens: integer (B+1,); last: integer (B,), the index WITHIN ITS SEQUENCE of the last
+    accepted token, -1: nothing accepted (word 0).  -> int64 (B,).  Plain torch on the inputs' device with no host read (an index
+    outside the tensor is clamped into it, never a fault), so it can sit inside a captured step between the tree decode and the
+    commit."""
+    import torch
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dim() != 1 or tree_mask.dtype != torch.int64 or tree_mask.numel() == 0:
+        raise ValueError("tree_mask must be a non-empty int64 tensor (total,)")
+    if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.is_floating_point():
+        raise ValueError("cu_seqlens must be an integer tensor of B+1 entries")
+    if not isinstance(last, torch.Tensor) or last.is_floating_point() or last.shape != (cu_seqlens.numel() - 1,):
+        raise ValueError("last must be an integer tensor (B,)")
+    last = last.to(torch.int64)
+    at = (cu_seqlens[:-1].to(torch.int64) + last).clamp(0, tree_mask.numel() - 1)
+    return torch.where(last >= 0, tree_mask[at], torch.zeros_like(last))
+
+
+def fa_kvcache_commit(k_cache, v_cache, accept_mask, cache_seqlens=None, seqlens_out=None, block_table=None, max_new: int = 64,
+                      stream=None) -> None:
+    """The commit step of tree speculation (fa_kvcache_commit): after fa_kvcache_append_varlen(positions=...) placed a step's tokens at
+    slots L_b, L_b + 1, ... in tree order and the tree decode verified them, the accepted path's K/V rows move to consecutive slots.
+    k_cache, v_cache: [B,Hkv,Ncap,d] fp16, bf16 or torch.float8_e4m3fn device tensors of one dtype, d in {64,128}, or with block_table
+    (int32 [B, max_pages]) the pools [num_pages,Hkv,page_size,d]; written in place.
+    accept_mask: int64 contiguous device tensor (B,), one word per sequence: bit i names the step token at slot L_b + i
+    (tree_accept_mask gives it from the tree_mask words).  Bits at or above max_new (1..64) and bits of tokens the append dropped at the
+    capacity are ignored.
+    cache_seqlens: int32 [B], the lengths BEFORE the step (what the append read), clamped to [0, capacity]; None: 0 for all.
+    With i_0 < i_1 < ... the kept bits, row L_b + i_j goes to row L_b + j in every head of K and of V, every bit kept, as if all
+    sources were read before any destination was written.  A word that is a low-bit prefix moves nothing and reads no table entry.
+    seqlens_out: int32 [B] that receives L_b + popcount, or None; cache_seqlens itself or disjoint from it; it must not overlap
+    accept_mask.  Nothing is read on the host and there is no workspace: append, tree decode, commit, captured once, serve every step."""
+    import torch
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    dts = (torch.float16, torch.bfloat16, torch.float8_e4m3fn)
+    if k_cache.dtype not in dts or v_cache.dtype != k_cache.dtype:
+        raise ValueError(f"k_cache, v_cache must both be fp16, both bf16 or both torch.float8_e4m3fn (got {k_cache.dtype}, {v_cache.dtype})")
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.numel() == 0 or k_cache.shape[3] not in (64, 128):
+        raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], d 64 or 128")
+    Hkv, d = k_cache.shape[1], k_cache.shape[3]
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] <= 0 or block_table.shape[1] <= 0:
+            raise ValueError("block_table must be an int32 device tensor of shape [B, max_pages]")
+        B, max_pages = block_table.shape
+        num_pages, page_size, Ncap = k_cache.shape[0], k_cache.shape[2], 0
+        if page_size < 16 or page_size & (page_size - 1):
+            raise ValueError("page_size must be a power of two >= 16")
+    else:
+        B, Ncap, num_pages, page_size, max_pages = k_cache.shape[0], k_cache.shape[2], 0, 0, 0
+    if not isinstance(accept_mask, torch.Tensor) or accept_mask.dtype != torch.int64:
+        raise ValueError("accept_mask must be an int64 tensor: one 64-bit word per sequence")
+    if accept_mask.shape != (B,) or not accept_mask.is_contiguous():
+        raise ValueError(f"accept_mask must be a contiguous tensor [B] = [{B}]")
+    if isinstance(max_new, bool) or not isinstance(max_new, int) or not 1 <= max_new <= 64:
+        raise ValueError("max_new must be an int in 1..64: a word holds 64 tokens")
+    for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.shape != (B,)):
+            raise ValueError(f"{name} must be an int32 device tensor of shape [B] = [{B}]")
+    k_ptr, v_ptr = _dev_ptr(k_cache, "k_cache", dts), _dev_ptr(v_cache, "v_cache", dts)
+    word_ptr = _dev_ptr(accept_mask, "accept_mask", (torch.int64,))
+    table_ptr = _table_ptr(block_table, B) if block_table is not None else None
+    len_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    out_ptr = None if seqlens_out is None else _dev_ptr(seqlens_out, "seqlens_out", (torch.int32,))
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    desc = capi.new_desc(capi.KvCommitDesc)
+    capi.fill(desc, K=k_ptr, V=v_ptr, seqlens_k=len_ptr, seqlens_out=out_ptr, accept_mask=word_ptr, block_table=table_ptr,
+              kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT, dtype=capi.F16 if fp8 else _in_dt(k_cache.dtype), B=B, Hkv=Hkv, d=d,
+              max_new=max_new, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(k_cache, v_cache, accept_mask, block_table, cache_seqlens, seqlens_out)):
+        code = capi.lib().fa_kvcache_commit(desc)
+    capi.check("fa_kvcache_commit", code)
+
+
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):
     import torch
     if Q.numel() != num_batches * 256 or K.numel() != num_batches * 16 * seq_len \

@@ -53,6 +53,9 @@ eager fallback.  Registered on first use:
                                          positions, q, q_out, rotary_cos, rotary_sin, interleaved)
     o, lse = torch.ops.fa_mi355.decode_varlen_tree(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, tree_mask,
                                                    scale, causal, window, sinks, softcap, out_f32)
+    # ... and its commit (ops.fa_kvcache_commit): the accepted path's K/V rows to consecutive slots, one int64 word per sequence;
+    # any cache dtype, block_table None = contiguous
+    torch.ops.fa_mi355.commit(k_cache, v_cache, accept_mask, cache_seqlens, seqlens_out, block_table, max_new)
 """
 from __future__ import annotations
 
@@ -65,7 +68,7 @@ def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
-    .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree and .decode_varlen_tree_fp8."""
+    .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit."""
     global _registered
     if _registered:
         return
@@ -299,6 +302,14 @@ def register() -> None:
                           ("decode_varlen_tree_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
         define(name, DECODE_VARLEN + "Tensor tree_mask, " + mid + DECODE_VARLEN_TAIL, (), decode_varlen_tree(fn), "-ccc-ooc",
                decode_varlen_kw, varlen_fake)
+
+    # the commit behind the tree decode (ops.fa_kvcache_commit): the caches go in as they are and are written in place, like the appends'
+    define("commit",
+           "(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor accept_mask, Tensor? cache_seqlens, Tensor(c!)? seqlens_out, "
+           "Tensor? block_table, int max_new) -> ()", ("k_cache", "v_cache", "seqlens_out"), ops.fa_kvcache_commit, "--c",
+           lambda k_cache, cache_seqlens, seqlens_out, block_table, max_new: dict(
+               cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), max_new=max_new,
+               stream=stream(k_cache)), lambda *args: None)
 
     _registered = True
 

@@ -577,8 +577,9 @@ int fa_kvcache_append_varlen(const fa_kvappend_varlen_desc* desc);
  * call follows it when it is rewritten in place.
  * Rejected with hipErrorInvalidValue before the device is touched: an opts->size other than sizeof(fa_kvappend_varlen_opts);
  * positions without rope_cos; positions that are not 4-byte aligned; everything fa_kvcache_append_varlen rejects.
- * Not part of this entry: positions on the padded fa_kvcache_append_ex; a per-sequence position offset; compacting an accepted
- * path's K/V rows to consecutive slots after verification (by copies or by page-table edits).  NOT a reference entry point. */
+ * Not part of this entry: positions on the padded fa_kvcache_append_ex; a per-sequence position offset; re-rotating a kept row at
+ * another position (fa_kvcache_commit, below, moves the accepted path's rows as they are: depth positions already are the path's
+ * final positions).  NOT a reference entry point. */
 typedef struct fa_kvappend_varlen_opts {
     size_t size;            /* sizeof(fa_kvappend_varlen_opts) */
     const int* positions;   /* device, [total_new] int32; NULL: position = slot (the plain entry's rule) */
@@ -900,13 +901,59 @@ int fa_kvcache_decode_varlen(const fa_kvdecode_varlen_desc* desc);
  * causal != 1 (the tree takes the triangle's place), max_q > 64, or a tree_mask that is not 8-byte aligned; everything
  * fa_kvcache_decode_varlen refuses.
  * Not part of this entry: trees of more than 64 tokens per sequence, or a dense or bit-packed [n, n] mask; a mask on the prefill
- * entries or on the padded fa_kvcache_decode; per-head masks; a shared prefix under a tree; the commit after verification
- * (compacting the accepted path's K/V rows to consecutive slots, by copies or by page-table edits).  NOT a reference entry point. */
+ * entries or on the padded fa_kvcache_decode; per-head masks; a shared prefix under a tree; a commit after verification by
+ * page-table edits (the commit by copies is fa_kvcache_commit, below).  NOT a reference entry point. */
 typedef struct fa_kvdecode_tree_opts {
     size_t size;                          /* sizeof(fa_kvdecode_tree_opts); any other value is refused */
     const unsigned long long* tree_mask;  /* device, [total_q] 64-bit words, one per token row; NULL: no tree */
 } fa_kvdecode_tree_opts;
 int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, const fa_kvdecode_tree_opts* opts);
+
+/* The commit step of tree speculation: after fa_kvcache_append_varlen_ex placed a step's n_b tokens at slots L_b .. L_b + n_b - 1 in
+ * tree order and fa_kvcache_decode_varlen_ex verified them, one root-to-node path per sequence is kept.  This entry moves that path's
+ * K/V rows to the consecutive slots behind L_b and writes the new lengths, so that every other entry reads the sequence as the dense
+ * range [0, L_b + a_b) again.  append -> tree decode -> commit, captured once, serves every step on all four cache forms.
+ * L_b = clamp(seqlens_k[b], 0, cap), cap = Ncap or, with block_table, max_pages * page_size: the append's clamp, on the lengths
+ *           BEFORE the step (what the append read; NULL: 0 for all).
+ * accept_mask  a device pointer to B 64-bit words, one per SEQUENCE.  Bit i names the step token the append placed at slot L_b + i.
+ *           w_b = the word restricted to the bits i < max_new with L_b + i < cap: bits at or above max_new are ignored, and tokens the
+ *           append dropped at the capacity are ignored and not counted.  a_b = popcount(w_b).  The word of a tree node as
+ *           fa_kvcache_decode_varlen_ex takes it (the node's own bit and its ancestors') is the word that keeps the path to that node.
+ * With i_0 < i_1 < ... the set bits of w_b: for every K/V head, for K and for V, row L_b + i_j is copied to row L_b + j.  A row is d
+ *           elements, 16 bit or one e4m3fn byte: kv_dtype and d matter through the row's size alone, and every bit is kept, NaN
+ *           payloads and NaN codes included.  The copy behaves as if all sources were read before any destination was written: {1,3}
+ *           makes slot L_b + 1 the source of j = 0 and the destination of j = 1.
+ * A move with i_j == j touches nothing.  A word that is a low-bit prefix (0, a fully accepted chain, a step of linear speculation)
+ *           reads and writes no cache byte and no table entry: the call is a pure length update, so one captured graph serves linear
+ *           and tree steps.
+ * Paged: slots map to pages exactly as in the append, addresses are 64 bit.  Table entries are read only for the pages that hold the
+ *           source or the destination of a move with i_j != j.  An entry outside [0, num_pages) skips that move: no address is formed
+ *           from it, the destination keeps its bytes, and the move still counts in a_b.  The pages a sequence moves rows within must
+ *           be owned by that sequence alone (the append's rule).
+ * seqlens_out[b] = L_b + a_b, by a tiny second kernel behind the copy, as in the appends: seqlens_out may be NULL, seqlens_k itself
+ *           or disjoint from it.
+ * Every byte that is not the destination of a move with i_j != j is left as it was: slots at and past L_b + a_b keep whatever the
+ *           step left there.  Nothing is read on the host and there is no workspace; the grid follows (B, Hkv, d, kv_dtype, max_new)
+ *           only; a captured call follows the words, the lengths and the table when they are rewritten in place.
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor or a wrong `size`; a NULL K, V or accept_mask; an
+ * accept_mask that is not 8-byte aligned; max_new outside 1..64; everything fa_kvcache_append_ex rejects for the cache and pool
+ * geometry, d, dtype and kv_dtype; a partial overlap of seqlens_out and seqlens_k; an accept_mask that overlaps seqlens_out.
+ * Not part of this entry: trees above 64 tokens; a commit by page-table edits; moving rows between sequences; compacting the Q or O
+ * rows of the step; re-rotating a moved K row.  NOT a reference entry point. */
+typedef struct fa_kvcommit_desc {
+    size_t size;                            /* sizeof(fa_kvcommit_desc) */
+    void *K, *V;                            /* the cache [B,Hkv,Ncap,d], or with block_table the pools [num_pages,Hkv,page_size,d] */
+    const int* seqlens_k;                   /* device, B int32: the lengths BEFORE the step (what the append read); NULL = 0 for all */
+    int* seqlens_out;                       /* device, B int32; NULL, == seqlens_k, or disjoint from it */
+    const unsigned long long* accept_mask;  /* device, B 64-bit words, one per SEQUENCE */
+    const int* block_table;                 /* device, [B,max_pages] int32; NULL: a contiguous cache */
+    int kv_dtype;                           /* FA_KV_16BIT or FA_KV_FP8_E4M3: only the element size matters */
+    int dtype;                              /* the 16-bit element type, as in fa_kvcache_append_ex */
+    int B, Hkv, d, max_new;                 /* max_new: HOST, 1..64; bits at or above it are ignored */
+    int Ncap, num_pages, page_size, max_pages;   /* Ncap: contiguous only; the other three: paged only */
+    void* stream;
+} fa_kvcommit_desc;
+int fa_kvcache_commit(const fa_kvcommit_desc* desc);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
