@@ -35,6 +35,8 @@ from .ops import (  # noqa: F401
     fa_kvcache_decode_varlen,
     fa_kvcache_decode_varlen_fp8,
     kvcache_decode_varlen_workspace_bytes,
+    fa_kvcache_attend_varlen,
+    fa_kvcache_attend_varlen_fp8,
     tree_from_parents,
     tree_accept_mask,
     fa_kvcache_commit,
@@ -57,7 +59,7 @@ __all__ = [
     "fa_merge_states", "fa_forward_kvcache_shared_prefix", "fa_forward_varlen", "fa_forward_varlen_kvcache",
     "fa_forward_varlen_kvcache_fp8",
     "fa_kvcache_decode_varlen", "fa_kvcache_decode_varlen_fp8", "kvcache_decode_varlen_workspace_bytes", "tree_from_parents",
-    "tree_accept_mask", "fa_kvcache_commit",
+    "tree_accept_mask", "fa_kvcache_commit", "fa_kvcache_attend_varlen", "fa_kvcache_attend_varlen_fp8",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",
     "attention_flops", "attention_min_bytes", "shard_range",
 ]

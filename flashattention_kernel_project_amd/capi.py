@@ -17,6 +17,7 @@ ALGO_RP16_DMA = 25
 ALGO_RP16_FOLD_HALF, ALGO_RP16_FOLD_QUARTER, ALGO_RP16_FOLD_1W, ALGO_RP16_FOLD_KS2 = 26, 27, 28, 29
 
 KV_16BIT, KV_FP8_E4M3 = 0, 1
+ATTEND_SHORT, ATTEND_LONG = 1, 2   # the parts of fa_kvcache_attend_varlen_part
 
 
 class KvDecodeDesc(C.Structure):
@@ -239,6 +240,9 @@ def _signatures() -> dict:
         "fa_kvcache_decode_varlen": (i, [C.POINTER(KvDecodeVarlenDesc)]),
         # the same with one 64-bit ancestor word per token row (tree speculation); a null opts is fa_kvcache_decode_varlen
         "fa_kvcache_decode_varlen_ex": (i, [C.POINTER(KvDecodeVarlenDesc), C.POINTER(KvDecodeTreeOpts)]),
+        # the mixed prefill + decode step on the same descriptor: max_q is the routing threshold; parts: ATTEND_SHORT | ATTEND_LONG
+        "fa_kvcache_attend_varlen": (i, [C.POINTER(KvDecodeVarlenDesc)]),
+        "fa_kvcache_attend_varlen_part": (i, [C.POINTER(KvDecodeVarlenDesc), i]),
         # the packed append with explicit rotary positions; a null opts is fa_kvcache_append_varlen
         "fa_kvcache_append_varlen_ex": (i, [C.POINTER(KvAppendVarlenDesc), C.POINTER(KvAppendVarlenOpts)]),
         # the commit of a tree step: the accepted path's K/V rows to consecutive slots, one 64-bit word per sequence

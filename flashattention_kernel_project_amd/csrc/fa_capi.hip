@@ -335,6 +335,12 @@ FA_EXPORT int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, c
     return (int)fa::kvtree_dispatch(desc, opts);
 }
 
+FA_EXPORT int fa_kvcache_attend_varlen_part(const fa_kvdecode_varlen_desc* desc, int parts) { return (int)fa::kvattend_dispatch(desc, parts); }
+FA_EXPORT int fa_kvcache_attend_varlen(const fa_kvdecode_varlen_desc* desc)
+{
+    return (int)fa::kvattend_dispatch(desc, FA_ATTEND_SHORT | FA_ATTEND_LONG);
+}
+
 FA_EXPORT int fa_debug_stage(int stage, const void* A, const void* B, void* Out, int BH, int N, int d, float scale,
                    int dtype, void* stream)
 {

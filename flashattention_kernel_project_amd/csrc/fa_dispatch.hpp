@@ -177,6 +177,21 @@ hipError_t kvtree_fp8_decode(const KvDecodeArgs& a, int lg_page);
 // ... and the merge behind them (fa_fwd_kvpacked.hip): live rows go to their tokens, nothing else is written; Nq: max_q
 hipError_t kvpacked_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
                             int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
+// fa_kvcache_decode_varlen's checks alone (fa_fwd_kvpacked.hip): on success `d` holds the checked arguments (the capacity filled in,
+// window 0 mapped to the capacity, d.packed pointing at `rows_of`, which the caller keeps alive) and lg_page the paged check's
+hipError_t kvpacked_check(const ::fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask, KvPackedRows& rows_of, KvDecodeArgs& d,
+                          int& lg_page);
+// fa_kvcache_attend_varlen[_part] (fa_fwd_kvrouted.hip): kvpacked_check and varlen_cache_check on the one descriptor, then the parts
+// that were asked for -- FA_ATTEND_SHORT: the RoutedArgs kernels of that unit or, on an fp8 cache, of fa_fwd_kvrouted_fp8.hip, with
+// their merge; FA_ATTEND_LONG: the routed varlen cache kernels of fa_fwd_varlen_cache_routed.hip or _routed_fp8.hip
+hipError_t kvattend_dispatch(const ::fa_kvdecode_varlen_desc* desc, int parts);
+hipError_t kvrouted_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvrouted_fp8_decode(const KvDecodeArgs& a, int lg_page);
+hipError_t kvrouted_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
+                            int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
+// args: the checked VarlenCacheArgs (16-bit) or VarlenCacheFp8Args; min_rows: sequences of at most as many rows are skipped
+hipError_t varlen_cache_routed_launch16(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid, int min_rows);
+hipError_t varlen_cache_routed_launch8(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid, int min_rows);
 // The argument checks alone: the append runs them too, so it accepts exactly the caches the decode accepts.  kvpaged_check fills
 // in the capacity and returns page_log2(page_size): log2 of a page size the kernels take, else -1.
 hipError_t kvcache_check(const KvCacheArgs& a);

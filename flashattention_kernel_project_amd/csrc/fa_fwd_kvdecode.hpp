@@ -1,7 +1,7 @@
 // fa_fwd_kvdecode.hpp -- the host path the eight KV-cache decode entries share: the pack builder, the launcher and the type switch,
 // templates over the pack (CacheArgs, PagedArgs, Fp8Args<...>, WindowArgs<...>, LogitArgs<...>, RaggedArgs<...>, PackedArgs<...>, TreeArgs<...>) the kernel
-// takes.  Private to the thirteen translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow,
-// _kvwindow_fp8, _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8, _kvpacked, _kvpacked_fp8, _kvtree, _kvtree_fp8): it instantiates
+// takes.  Private to the fifteen translation units that each own the kernels of their packs (fa_fwd_kvcache.hip, _kvpaged, _kvfp8, _kvwindow,
+// _kvwindow_fp8, _kvlogits, _kvlogits_fp8, _kvragged, _kvragged_fp8, _kvpacked, _kvpacked_fp8, _kvtree, _kvtree_fp8, _kvrouted, _kvrouted_fp8): it instantiates
 // kernels, so a unit names only its own packs and no other unit's code moves.
 #pragma once
 #include "fa_fwd_split_kernel.hpp"
@@ -78,8 +78,12 @@ static hipError_t launch_kvdecode(const KvCacheArgs& a, Pack pack, int span)
                        a.stream, q, k, v, a.O, static_cast<float*>(a.ws), rows, a.Ncap, nqb, S, 0, host_scale_log2e(a.scale), pack);
     hipError_t e = launch_status();
     if (e != hipSuccess) return e;
+    // routed rows: the packed merge with the routed row count (a sequence above max_q rows has no live row)
+    if constexpr (IsRoutedArgs<Pack>::value)
+        return kvrouted_combine(a.ws, a.O, a.lse, pack.sinks, {pack.cu_q, pack.total_q, pack.q_st, pack.q_sh, pack.o_st, pack.o_sh, nullptr}, BH, rows,
+                                a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // token-packed rows: the merge stores the live rows to their tokens through O's strides and writes nothing else
-    if constexpr (IsPackedArgs<Pack>::value)
+    else if constexpr (IsPackedArgs<Pack>::value)
         return kvpacked_combine(a.ws, a.O, a.lse, pack.sinks, {pack.cu_q, pack.total_q, pack.q_st, pack.q_sh, pack.o_st, pack.o_sh, nullptr}, BH, rows,
                                 a.Hkv, a.Nq, D, S, a.in_dtype, a.out_dtype, a.stream);
     // per-sequence query counts: the merge maps padded rows to the packed workspace rows, writes the dead rows and joins the sinks

@@ -61,7 +61,9 @@ static bool packed_view_ok(int max_q, int total, long long Hq, int d, long long 
 // The checks of kvdecode_dispatch (fa_fwd_kvcache.hip) with Nq = max_q, then the packed tensors', then the hand-over: the PackedArgs
 // kernels wrap the RaggedArgs packs, which exist around the windowed ones only, so window 0 runs as window = the capacity.
 // tree_mask (fa_kvcache_decode_varlen_ex; null: none): the same checks, the mask's own, and the TreeArgs kernels of fa_fwd_kvtree*.hip.
-hipError_t kvpacked_dispatch(const fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask)
+// The checks stand alone (kvpacked_check) because fa_kvcache_attend_varlen runs them too, on the same descriptor.
+hipError_t kvpacked_check(const fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask, KvPackedRows& rows_of, KvDecodeArgs& d,
+                          int& lg_page)
 {
     if (!kvpacked_desc_ok(desc)) return hipErrorInvalidValue;
     // the words take the triangle's place, one bit per token of the step; the kernels load them as 8-byte words
@@ -70,17 +72,16 @@ hipError_t kvpacked_dispatch(const fa_kvdecode_varlen_desc* desc, const unsigned
     if (desc->window < 0) return hipErrorInvalidValue;
     if (!(desc->softcap >= 0.0f) || __builtin_isinf(desc->softcap)) return hipErrorInvalidValue;   // negative, NaN or inf
     const bool paged = desc->block_table != nullptr;
-    const KvPackedRows rows_of = {desc->cu_seqlens_q, desc->total_q, desc->q_stride_t, desc->q_stride_h, desc->o_stride_t,
-                                  desc->o_stride_h, tree_mask};
-    KvDecodeArgs d = {.p = {.c = {desc->Q, desc->K, desc->V, desc->O, desc->lse, desc->seqlens_k, desc->B, desc->Hkv, desc->G, desc->max_q,
-                                  paged ? 0 : desc->Ncap, desc->d, desc->scale, desc->causal, desc->in_dtype, desc->out_dtype,
-                                  desc->workspace, desc->workspace_bytes, static_cast<hipStream_t>(desc->stream)},
-                            .table = desc->block_table, .num_pages = paged ? desc->num_pages : 0,
-                            .page_size = paged ? desc->page_size : 0, .max_pages = paged ? desc->max_pages : 0},
-                      .k_scale = desc->k_scale, .v_scale = desc->v_scale, .window = desc->window, .paged = paged,
-                      .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap, .seqlens_q = nullptr,
-                      .packed = &rows_of};
-    int lg_page = 0;
+    rows_of = {desc->cu_seqlens_q, desc->total_q, desc->q_stride_t, desc->q_stride_h, desc->o_stride_t, desc->o_stride_h, tree_mask};
+    d = {.p = {.c = {desc->Q, desc->K, desc->V, desc->O, desc->lse, desc->seqlens_k, desc->B, desc->Hkv, desc->G, desc->max_q,
+                     paged ? 0 : desc->Ncap, desc->d, desc->scale, desc->causal, desc->in_dtype, desc->out_dtype,
+                     desc->workspace, desc->workspace_bytes, static_cast<hipStream_t>(desc->stream)},
+               .table = desc->block_table, .num_pages = paged ? desc->num_pages : 0,
+               .page_size = paged ? desc->page_size : 0, .max_pages = paged ? desc->max_pages : 0},
+         .k_scale = desc->k_scale, .v_scale = desc->v_scale, .window = desc->window, .paged = paged,
+         .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap, .seqlens_q = nullptr,
+         .packed = &rows_of};
+    lg_page = 0;
     if (!paged) {
         const hipError_t bad = kvcache_check(d.p.c);
         if (bad != hipSuccess) return bad;
@@ -100,6 +101,16 @@ hipError_t kvpacked_dispatch(const fa_kvdecode_varlen_desc* desc, const unsigned
         !packed_view_ok(desc->max_q, desc->total_q, Hq, desc->d, desc->o_stride_t, desc->o_stride_h, es))
         return hipErrorInvalidValue;
     if (d.window == 0) d.window = d.p.c.Ncap;
+    return hipSuccess;
+}
+
+hipError_t kvpacked_dispatch(const fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask)
+{
+    KvPackedRows rows_of;
+    KvDecodeArgs d;
+    int lg_page;
+    const hipError_t bad = kvpacked_check(desc, tree_mask, rows_of, d, lg_page);
+    if (bad != hipSuccess) return bad;
     if (tree_mask) return d.fp8 ? kvtree_fp8_decode(d, lg_page) : kvtree_decode(d, lg_page);
     return d.fp8 ? kvpacked_fp8_decode(d, lg_page) : kvpacked_decode(d, lg_page);
 }

@@ -149,6 +149,17 @@ struct NoTree {};
 __device__ __forceinline__ NoTree tree_part() { return {}; }
 __device__ __forceinline__ NoTree tree_part(const CacheArgs&) { return {}; }
 template <typename Base> __device__ __forceinline__ const TreeArgs<Base>& tree_part(const TreeArgs<Base>& t) { return t; }
+// What the routed instantiations take (the SHORT half of fa_kvcache_attend_varlen): a PackedArgs pack and nothing more -- the type alone
+// says that a sequence with more than Nq1 rows has NO live row here (routed_rows) where the wrapped pack cuts it to its first Nq1: the
+// tiled kernel owns such a sequence.  Its workgroups then take the n_b = 0 path and return before any table entry, K/V or Q row is read.
+template <typename Base> struct RoutedArgs : Base {};
+template <typename A> struct IsRoutedArgs : std::false_type {};
+template <typename Base> struct IsRoutedArgs<RoutedArgs<Base>> : std::true_type {};
+template <typename Base> struct IsFp8Args<RoutedArgs<Base>> : IsFp8Args<Base> {};
+template <typename Base> struct IsWindowArgs<RoutedArgs<Base>> : IsWindowArgs<Base> {};
+template <typename Base> struct IsLogitArgs<RoutedArgs<Base>> : IsLogitArgs<Base> {};
+template <typename Base> struct IsRaggedArgs<RoutedArgs<Base>> : IsRaggedArgs<Base> {};
+template <typename Base> struct IsPackedArgs<RoutedArgs<Base>> : IsPackedArgs<Base> {};
 // what a kPacked kernel keeps about its (sequence, K/V head) view -- all of it wave-uniform but the lane's offsets and (hd, i), which
 // live in the prologue (qoff) or in the epilogue (the rest) only
 struct PackedView {
@@ -163,6 +174,13 @@ __device__ __forceinline__ void packed_rows(const int* __restrict__ cu, unsigned
 {
     s = min(max(cu[b], 0), total);
     n = (unsigned)min(min(max(cu[b + 1], s), total) - s, max_q);
+}
+// ... under RoutedArgs / RoutedLse: all of the sequence's rows if they are at most max_q, else none (wave-uniform)
+__device__ __forceinline__ void routed_rows(const int* __restrict__ cu, unsigned b, int total, int max_q, int& s, unsigned& n)
+{
+    s = min(max(cu[b], 0), total);
+    const int span = min(max(cu[b + 1], s), total) - s;
+    n = span <= max_q ? (unsigned)span : 0u;
 }
 // the (sequence, K/V head) view of a packed tensor: rows [0, n) of the G heads from `h0` on; `bytes` is what a lane past the live
 // rows uses as its offset (the first one past the view: loads read 0, stores are dropped)
@@ -278,6 +296,9 @@ template <typename T> __device__ __forceinline__ void fp8x16_widen(u32x4 raw, u3
 // lane past the live rows loads nothing (its offset is the descriptor's size) and takes the triangle's word of that index, so it
 // votes where the causal kernel's dead lane votes.  Nothing of the mask lives in a VGPR outside the block.  With
 // the word (2 << i) - 1 every score takes the decision the kPacked causal kernel takes: the bits are that kernel's.
+// kRouted (kPacked with a RoutedArgs around the pack): the one difference is the row count -- n_b = e_b - s_b when that
+// is at most Nq1 and 0 otherwise -- taken where the packed kernel takes its own, so a sequence of up to Nq1 rows returns the packed
+// kernel's bits and a longer one is an idle slot.  The decision is wave-uniform and is gone before the Q load.
 // Why a parameter pack for one optional argument, and not a shared __device__ body behind two __global__ kernels: the plain
 // instantiations must keep the parent's code.  Behind a wrapper the d = 128 plain kernels came out with another register
 // allocation (204/205 -> 202/203 VGPRs, another schedule); with the pack their gfx950 assembly is the parent's, instruction for
@@ -304,6 +325,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] const auto ra = ragged_part(cache...);
     constexpr bool kPacked = (IsPackedArgs<Cache>::value || ...);
     [[maybe_unused]] const auto ka = packed_part(cache...);
+    constexpr bool kRouted = (IsRoutedArgs<Cache>::value || ...);
     constexpr bool kTree = (IsTreeArgs<Cache>::value || ...);
     [[maybe_unused]] const auto ta = tree_part(cache...);
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
@@ -315,7 +337,13 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     // block -> (head, query block, split): the splits of one (head, query block) are consecutive
     const unsigned sp = blockIdx.x % (unsigned)S;
     const unsigned rest = blockIdx.x / (unsigned)S;
-    const unsigned bh = rest / (unsigned)nqb, qb = rest % (unsigned)nqb;
+    // kRouted: the query block is the SLOW index.  With Nq1 = T a one-token sequence has live rows in its block 0 alone, and with the
+    // blocks of a head adjacent (bh * nqb + qb) the live workgroups sit at block ids that are multiples of nqb: for nqb = 4 on two of
+    // the eight XCDs (block id % 8), with the other six idle (measured: 812 against 322 us at 256 x 1 tokens, T = 128, d = 64).
+    // Block-major, the live workgroups are the first BH * S ids and spread over all of them.  Which workgroup computes what is
+    // unchanged, and so are the bits.
+    [[maybe_unused]] const unsigned nbh = kRouted ? gridDim.x / ((unsigned)S * (unsigned)nqb) : 1u;
+    const unsigned bh = kRouted ? rest % nbh : rest / (unsigned)nqb, qb = kRouted ? rest / nbh : rest % (unsigned)nqb;
 
     const unsigned tid  = threadIdx.x;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -335,7 +363,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] unsigned n_q = 0, live = 0;
     [[maybe_unused]] std::conditional_t<kPacked, PackedView, NoPacked> pv;
     if constexpr (kRagged) {
-        if constexpr (kPacked) packed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
+        if constexpr (kRouted) routed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
+        else if constexpr (kPacked) packed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
         else n_q = (unsigned)min(max(ra.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
         live = ((unsigned)Nq / (unsigned)ca.Nq1) * n_q;
         if constexpr (!kPartial && !kPacked) {
@@ -864,6 +893,9 @@ struct PackedLse {
 __device__ __forceinline__ float* lse_part(const PackedLse& s) { return s.lse; }
 __device__ __forceinline__ NoSink sink_part(const PackedLse&) { return {}; }
 __device__ __forceinline__ NoRaggedLse ragged_lse_part(const PackedLse&) { return {}; }
+// RoutedLse: PackedLse behind the RoutedArgs partial kernels -- the row count is routed_rows', so the waves of a sequence with more
+// than Nq1 rows return without writing, as those of an idle slot do.
+struct RoutedLse : PackedLse {};
 struct NoPackedLse {};
 __device__ __forceinline__ NoPackedLse packed_lse_part() { return {}; }
 __device__ __forceinline__ NoPackedLse packed_lse_part(float*) { return {}; }
@@ -884,7 +916,8 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     [[maybe_unused]] const auto sk = sink_part(lse_arg...);
     constexpr bool kRaggedM = (std::is_same_v<Lse, RaggedLse> || ...);
     [[maybe_unused]] const auto rg = ragged_lse_part(lse_arg...);
-    constexpr bool kPackedM = (std::is_same_v<Lse, PackedLse> || ...);
+    constexpr bool kRoutedM = (std::is_same_v<Lse, RoutedLse> || ...);
+    constexpr bool kPackedM = (std::is_same_v<Lse, PackedLse> || ...) || kRoutedM;
     [[maybe_unused]] const auto pg = packed_lse_part(lse_arg...);
     const int cols4 = D / 4;             // 16 or 32
     const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
@@ -918,7 +951,8 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     if constexpr (kPackedM) {
         int s;
         unsigned n_q;
-        packed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
+        if constexpr (kRoutedM) routed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
+        else packed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
         const int hd = row / pg.Nq1, i = row - hd * pg.Nq1;
         if (i >= (int)n_q) return;   // wave-uniform: no live row, nothing is written
         ws_row = hd * (int)n_q + i;

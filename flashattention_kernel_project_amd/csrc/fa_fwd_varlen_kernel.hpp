@@ -47,6 +47,9 @@
 // kernels'.  One wave's loads for one p cover 16 rows at d = 64 and 8 at d = 128, aligned to as many -- still inside one page of
 // >= 16 keys.  The rows past Lk and the rows below lo_wg are zeroed as RAW bytes (code 0 is +0.0): a freed page may hold the NaN
 // codes 0x7F / 0xFF.  k_scale[hkv] joins the logit factor, with the FLT_MIN clamp on the product; v_scale[hkv] joins 1 / l.
+// kRouted (fa_kvcache_attend_varlen's LONG half; kCache, causal, with a VarlenRoutedArgs around the arguments): right
+// after Lq is known a workgroup whose sequence has Lq <= min_rows returns -- such a sequence is the split-KV stream's.  The test is
+// scalar and dead before the Q load; every other workgroup runs the unrouted kernel's code and returns its bits.
 #pragma once
 #include "../../include/fa_mi355.h"
 #include "fa_tile.hpp"
@@ -101,6 +104,18 @@ struct VarlenCacheFp8Args : VarlenCacheArgs {
     const float *k_scale, *v_scale;   // [Hkv] on the device, or nullptr (1.0)
 };
 
+// What the routed cache instantiations take (kRouted: the LONG half of fa_kvcache_attend_varlen): the cache arguments as they are plus
+// the threshold, in a derived structure so that VarlenCacheArgs, and with it the argument layout of every other kernel, stays as it is
+template <typename Base> struct VarlenRoutedArgs : Base {
+    int min_rows;   // a sequence with Lq <= min_rows is the split-KV stream's: its workgroups return
+};
+// the argument structure of an instantiation
+template <bool kLogits, int kCache, bool kFp8, bool kRouted> struct VarlenKernelArgs {
+    using plain = std::conditional_t<kFp8, VarlenCacheFp8Args, std::conditional_t<kCache != 0, VarlenCacheArgs,
+                                     std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs>>>;
+    using type = std::conditional_t<kRouted, VarlenRoutedArgs<plain>, plain>;
+};
+
 // `elems` K/V elements past p.  With kFp8 p points at one byte per element; it keeps the type the argument structs give K and V, and
 // is only ever the base of a buffer descriptor.  (Without kFp8 this must stay `p + elems`: written as byte arithmetic for both, the
 // 16-bit cache kernels compile to another order of their scalar multiplies.)
@@ -126,12 +141,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t varlen_rsrc(const void* ptr, i
     return make_rsrc(static_cast<const char*>(ptr) + first * (long long)es, bytes);
 }
 
-template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false, int kCache = kVarlenPacked, bool kFp8 = false>
+template <typename T, int D, bool kOutF32, bool kCausal, bool kLogits = false, int kCache = kVarlenPacked, bool kFp8 = false,
+          bool kRouted = false>
 __global__ __launch_bounds__(64 * kVarlenWaves, 2)
-void fa_fwd_varlen_kernel(std::conditional_t<kFp8, VarlenCacheFp8Args, std::conditional_t<kCache != kVarlenPacked, VarlenCacheArgs,
-                                             std::conditional_t<kLogits, VarlenLogitArgs, VarlenArgs>>> a)
+void fa_fwd_varlen_kernel(typename VarlenKernelArgs<kLogits, kCache, kFp8, kRouted>::type a)
 {
     static_assert(!kFp8 || kCache != kVarlenPacked, "an fp8 K/V is a cache's");
+    static_assert(!kRouted || (kCache != kVarlenPacked && kCausal), "the routed forms are causal cache kernels");
     using G = TileGeom<D>;
     constexpr unsigned kKvEs = kFp8 ? 1u : 2u;                          // bytes per K/V element
     constexpr int kLdChunks = kFp8 ? G::kChunks / 2 : G::kChunks;      // 16-byte loads per K/V row
@@ -167,6 +183,10 @@ void fa_fwd_varlen_kernel(std::conditional_t<kFp8, VarlenCacheFp8Args, std::cond
         varlen_bounds(cu_k, b, a.total_k, sk, ek);
     }
     const int Lq = eq - sq, Lk = ek - sk;
+    // kRouted: a sequence of at most min_rows rows belongs to the other launch; wave-uniform, before anything of it is read
+    if constexpr (kRouted) {
+        if (Lq <= a.min_rows) return;
+    }
     const unsigned first_b = (unsigned)sq / BM + b;
     if (slot < first_b) return;                        // slots below the first sequence's
     const unsigned qb = slot - first_b;
@@ -635,6 +655,33 @@ static inline hipError_t varlen_launch(const fa_varlen_desc* d, const Args& a, d
                           : launch(fa_fwd_varlen_kernel<T, 64, kF32, false, kLogits>, TileGeom<64>::kLdsBytes);
         return causal ? launch(fa_fwd_varlen_kernel<T, 128, kF32, true, kLogits>, TileGeom<128>::kLdsBytes)
                       : launch(fa_fwd_varlen_kernel<T, 128, kF32, false, kLogits>, TileGeom<128>::kLdsBytes);
+    });
+}
+
+// the LONG half of fa_kvcache_attend_varlen: varlen_cache_launch's choice among the kRouted instantiations (causal only), with the
+// threshold behind the checked arguments.  Base: VarlenCacheArgs or VarlenCacheFp8Args
+template <bool kLogits, typename Base>
+static inline hipError_t varlen_cache_routed_launch(const fa_varlen_kvcache_desc* d, const Base& base, dim3 grid, int min_rows)
+{
+    VarlenRoutedArgs<Base> a;
+    static_cast<Base&>(a) = base;
+    a.min_rows = min_rows;
+    const bool paged = d->block_table != nullptr;
+    return with_types(d->in_dtype, d->out_dtype, [&](auto t, auto f32) {
+        using T = decltype(t);
+        constexpr bool kF32 = decltype(f32)::value;
+        constexpr bool kFp8 = std::is_same_v<Base, VarlenCacheFp8Args>;
+        auto launch = [&](auto kernel, int lds) {
+            const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), lds);
+            if (attr != hipSuccess) return attr;
+            FA_LAUNCH(kernel, grid, dim3(64 * kVarlenWaves), (size_t)lds, static_cast<hipStream_t>(d->stream), a);
+            return launch_status();
+        };
+        if (d->d == 64)
+            return paged ? launch(fa_fwd_varlen_kernel<T, 64, kF32, true, kLogits, kVarlenPaged, kFp8, true>, TileGeom<64>::kLdsBytes)
+                         : launch(fa_fwd_varlen_kernel<T, 64, kF32, true, kLogits, kVarlenContig, kFp8, true>, TileGeom<64>::kLdsBytes);
+        return paged ? launch(fa_fwd_varlen_kernel<T, 128, kF32, true, kLogits, kVarlenPaged, kFp8, true>, TileGeom<128>::kLdsBytes)
+                     : launch(fa_fwd_varlen_kernel<T, 128, kF32, true, kLogits, kVarlenContig, kFp8, true>, TileGeom<128>::kLdsBytes);
     });
 }
 

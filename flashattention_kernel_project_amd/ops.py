@@ -689,6 +689,40 @@ def fa_kvcache_decode_varlen_fp8(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
                           return_lse, out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale), tree_mask=tree_mask)
 
 
+def fa_kvcache_attend_varlen(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, split_rows: int = 128,
+                             scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None, workspace=None, window=None,
+                             softcap: float = 0.0, sinks=None, parts: int = 3, stream=None, lse=None):
+    """The mixed prefill + decode step (fa_kvcache_attend_varlen): one causal attention call for a token-packed batch that holds prompt
+    chunks beside one-token decodes, each sequence routed on the device to the kernel that suits its row count.  With span_b the rows
+    cu_seqlens_q gives sequence b (clamped into the tensor as in fa_forward_varlen): 1 <= span_b <= split_rows runs on the split-KV
+    stream and returns the bits of fa_kvcache_decode_varlen(..., max_seqlen_q=split_rows, causal=True); span_b > split_rows runs on the
+    tiled kernel and returns the bits of fa_forward_varlen_kvcache(..., causal=True).  Every token of every sequence is computed --
+    nothing is cut at split_rows -- and row i sees the keys [lo_i, c_i) with c_i = max(0, L_b - span_b + 1 + i),
+    lo_i = max(0, L_b - span_b + 1 + i - window) under a window, else 0: append the step, then call this.
+    q, k_cache, v_cache, cu_seqlens_q, block_table, window, softcap, sinks, scale, out_dtype, out, lse: as in fa_kvcache_decode_varlen.
+    cache_seqlens: int32 [B], required: the keys of sequence b, its new tokens INCLUDED.  split_rows: a host int >= 1 (default 128, the
+    measured crossover of the two entries); the split count, the grid of the split-KV half and the workspace follow it, so
+    kvcache_decode_varlen_workspace_bytes(B, Hkv, G, max_seqlen_q=split_rows, ...) sizes `workspace`.
+    parts: 3 (both halves, the default), 1 (only the sequences of at most split_rows rows are computed and written) or 2 (only the
+    longer ones); the other class keeps its rows in `out` and `lse` and nothing of it is read -- for a caller who runs the
+    bandwidth-bound half and the compute-bound half on two streams.
+    -> o (total_q, Hq, d), or (o, lse) with return_lse; a fresh o holds zeros and a fresh lse -inf where nothing was written.
+    Nothing is read on the host: captured once, the call follows cu_seqlens_q, cache_seqlens, the table and the sinks rewritten in
+    place, sequences that change class included.  An fp8 cache is fa_kvcache_attend_varlen_fp8's."""
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, split_rows, cache_seqlens, block_table, True, scale, out_dtype, return_lse,
+                          out, workspace, stream, window, softcap, sinks, lse, attend=True, parts=parts)
+
+
+def fa_kvcache_attend_varlen_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, k_scale=None, v_scale=None,
+                                 split_rows: int = 128, scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None,
+                                 workspace=None, window=None, softcap: float = 0.0, sinks=None, parts: int = 3, stream=None, lse=None):
+    """fa_kvcache_attend_varlen against an fp8 cache: k_cache, v_cache (or the pools) contiguous torch.float8_e4m3fn, k_scale, v_scale
+    float32 [Hkv] or None (1.0), read on the device only.  The short sequences return the bits of fa_kvcache_decode_varlen_fp8, the long
+    ones those of fa_forward_varlen_kvcache_fp8; everything else as in fa_kvcache_attend_varlen."""
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, split_rows, cache_seqlens, block_table, True, scale, out_dtype, return_lse,
+                          out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale), attend=True, parts=parts)
+
+
 def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, d: int, Ncap: int = 0, max_pages: int = 0,
                                           page_size: int = 0, window: int = 0) -> int:
     """Workspace of fa_kvcache_decode_varlen and _fp8: a contiguous cache gives Ncap, a paged one max_pages and page_size.  It is what
@@ -700,10 +734,10 @@ def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q
 
 
 def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse,
-                   out, workspace, stream, window, softcap, sinks, lse, scales=None, tree_mask=None):
+                   out, workspace, stream, window, softcap, sinks, lse, scales=None, tree_mask=None, attend=False, parts=3):
     """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one; tree_mask is
     None (fa_kvcache_decode_varlen) or the words of fa_kvcache_decode_varlen_ex.  Shapes and dtypes are judged before anything needs a
-    device."""
+    device.  attend: the call is fa_kvcache_attend_varlen_part(desc, parts) on the same descriptor, max_seqlen_q its threshold."""
     import torch
     fp8 = scales is not None
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
@@ -729,7 +763,13 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     if total_q <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or k_cache.numel() == 0:
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
     if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1:
-        raise ValueError("max_seqlen_q must be an int >= 1: the most rows a sequence may have")
+        raise ValueError("split_rows must be an int >= 1: the most rows of a sequence that runs on the split-KV stream"
+                         if attend else "max_seqlen_q must be an int >= 1: the most rows a sequence may have")
+    if attend:
+        if type(parts) is not int or parts not in (1, 2, 3):
+            raise ValueError("parts must be 1 (the split-KV half), 2 (the tiled half) or 3 (both)")
+        if cache_seqlens is None:
+            raise ValueError("cache_seqlens must be an int32 device tensor of B entries (the mixed step has no default lengths)")
     if tree_mask is not None:
         if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
             raise ValueError("tree_mask must be an int64 tensor: one 64-bit word per token row")
@@ -803,13 +843,16 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
         out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len, stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, workspace,
                                        tree_mask, *(scales or ()))):
-        if tree_mask is None:
+        if attend:
+            code = capi.lib().fa_kvcache_attend_varlen_part(desc, parts)
+        elif tree_mask is None:
             code = capi.lib().fa_kvcache_decode_varlen(desc)
         else:
             opts = capi.new_desc(capi.KvDecodeTreeOpts)
             opts.tree_mask = tree_mask.data_ptr()
             code = capi.lib().fa_kvcache_decode_varlen_ex(desc, opts)
-    capi.check("fa_kvcache_decode_varlen" if tree_mask is None else "fa_kvcache_decode_varlen_ex", code)
+    capi.check("fa_kvcache_attend_varlen_part" if attend else
+               "fa_kvcache_decode_varlen" if tree_mask is None else "fa_kvcache_decode_varlen_ex", code)
     return (out, lse) if return_lse else out
 
 

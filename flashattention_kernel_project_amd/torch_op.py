@@ -56,6 +56,10 @@ eager fallback.  Registered on first use:
     # ... and its commit (ops.fa_kvcache_commit): the accepted path's K/V rows to consecutive slots, one int64 word per sequence;
     # any cache dtype, block_table None = contiguous
     torch.ops.fa_mi355.commit(k_cache, v_cache, accept_mask, cache_seqlens, seqlens_out, block_table, max_new)
+    # the mixed prefill + decode step (ops.fa_kvcache_attend_varlen): sequences of up to split_rows rows on the split-KV stream, longer
+    # ones on the tiled kernel, routed on the device; always causal; parts 3 = both halves; _fp8 takes k_scale, v_scale behind block_table
+    o, lse = torch.ops.fa_mi355.attend_varlen(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, split_rows, scale, window,
+                                              sinks, softcap, parts, out_f32)
 """
 from __future__ import annotations
 
@@ -68,7 +72,8 @@ def register() -> None:
     """Define torch.ops.fa_mi355.forward, the 16 .decode and 12 .append ops (layout x form, as the module's docstring lists them),
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
-    .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit."""
+    .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
+    .attend_varlen and .attend_varlen_fp8."""
     global _registered
     if _registered:
         return
@@ -302,6 +307,18 @@ def register() -> None:
                           ("decode_varlen_tree_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
         define(name, DECODE_VARLEN + "Tensor tree_mask, " + mid + DECODE_VARLEN_TAIL, (), decode_varlen_tree(fn), "-ccc-ooc",
                decode_varlen_kw, varlen_fake)
+
+    # the mixed prefill + decode step (ops.fa_kvcache_attend_varlen, _fp8): forward_varlen_kvcache's leading arguments, then
+    # `int split_rows` (the routing threshold) and, before out_f32, `int parts` (3: both halves); always causal
+    def attend_varlen_kw(q, split_rows, scale, window, sinks, softcap, parts, out_f32):
+        return dict(split_rows=split_rows, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+                    softcap=softcap, sinks=opt(sinks), parts=parts)
+
+    ATTEND_VARLEN_TAIL = "int split_rows, float scale, int window, Tensor? sinks, float softcap, int parts, bool out_f32) -> (Tensor, Tensor)"
+    for name, mid, fn, how in (("attend_varlen", "", ops.fa_kvcache_attend_varlen, "-cccco"),
+                               ("attend_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_attend_varlen_fp8, "-ccccooo")):
+        define(name, "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor? block_table, " + mid +
+               ATTEND_VARLEN_TAIL, (), fn, how, attend_varlen_kw, varlen_fake)
 
     # the commit behind the tree decode (ops.fa_kvcache_commit): the caches go in as they are and are written in place, like the appends'
     define("commit",

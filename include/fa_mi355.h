@@ -848,8 +848,8 @@ int fa_forward_varlen_kvcache_fp8(const fa_varlen_kvcache_desc* desc, const floa
  * (sequence, K/V head) view -- (min(max_q, total_q) - 1) * stride_t + Hkv*G * stride_h + d elements of Q or of O -- whose bytes
  * do not fit 32 bits with 512 to spare.
  * Not part of this entry: a shared prefix (fa_merge_states composes one); a split count per sequence; splitting the keys inside the
- * prefill kernel; an automatic choice between this entry and fa_forward_varlen_kvcache (README has the measured crossover);
- * explicit position ids.  NOT a reference entry point. */
+ * prefill kernel; explicit position ids.  (The choice between this entry and fa_forward_varlen_kvcache per sequence, on the device,
+ * is fa_kvcache_attend_varlen, below.)  NOT a reference entry point. */
 typedef struct fa_kvdecode_varlen_desc {
     size_t size;               /* sizeof(fa_kvdecode_varlen_desc); any other value is refused */
     const void* Q; void* O;    /* packed (total_q, Hkv*G, d) through the strides below */
@@ -908,6 +908,46 @@ typedef struct fa_kvdecode_tree_opts {
     const unsigned long long* tree_mask;  /* device, [total_q] 64-bit words, one per token row; NULL: no tree */
 } fa_kvdecode_tree_opts;
 int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, const fa_kvdecode_tree_opts* opts);
+
+/* The mixed step: ONE attention call for the batch a continuous-batching scheduler packs on every iteration -- a few prompt chunks of
+ * some hundred rows beside many one-token decodes -- with each sequence routed ON THE DEVICE to the stream that suits its row count.
+ * fa_kvcache_append_varlen then fa_kvcache_attend_varlen is the two-call step of a serving loop, whatever mix was packed.
+ * The descriptor is fa_kvdecode_varlen_desc as it is, and every field means what it means above, with one difference: max_q is the
+ * routing threshold T.  [s_b, e_b) are the clamps of cu_seqlens_q both existing entries apply, and span_b = e_b - s_b:
+ *   span_b = 0          the sequence has no rows: an idle slot, nothing of it is read;
+ *   1 <= span_b <= T    SHORT: the packed split-KV stream (fa_kvcache_decode_varlen's kernels);
+ *   span_b > T          LONG: the tiled kernel (fa_forward_varlen_kvcache's), one workgroup per (128-row block, query head).
+ * Every token of every sequence is a live row: NOTHING is cut at T.  Row i of sequence b sees the keys [lo_i, c_i) with
+ * c_i = max(0, L_b - span_b + 1 + i) and lo_i = max(0, L_b - span_b + 1 + i - W) under a window W, else 0 -- the one formula both existing entries already share, as they share the soft-cap before the masks, the sink counted once per row, the
+ * fp8 scale rules and "a row without a key is O = 0, lse = -inf (the sink logit with sinks)".
+ * BITS: on the rows of a SHORT sequence the call returns the bits of fa_kvcache_decode_varlen(desc) with the same descriptor, for O
+ * and lse; on the rows of a LONG sequence the bits of fa_forward_varlen_kvcache on the same fields -- for kv_dtype FA_KV_FP8_E4M3
+ * those of fa_forward_varlen_kvcache_fp8 with the descriptor's scales.  window = 0 maps as each entry maps it.
+ * Tokens of no sequence are neither read nor written, as in both entries.
+ * Parts: fa_kvcache_attend_varlen(desc) is fa_kvcache_attend_varlen_part(desc, FA_ATTEND_SHORT | FA_ATTEND_LONG).  FA_ATTEND_SHORT alone
+ * computes and writes the SHORT rows only, FA_ATTEND_LONG alone the LONG rows only: the rows of the other class keep their bytes, and
+ * for the skipped class no Q row, no K/V row and no table entry is read.  This is the form for a caller who puts the bandwidth-bound
+ * half and the compute-bound half on two streams.
+ * Launches, all on desc->stream, the SHORT half first (the halves write disjoint rows, so the order does not show in the result):
+ * the SHORT half is the packed split-KV stream plus its merge when the split count exceeds 1, with grid, split count and workspace
+ * from (B, Hkv, G, T, span) exactly as fa_kvcache_decode_varlen derives them from max_q -- so
+ * fa_kvcache_decode_varlen_workspace_bytes(desc) sizes the workspace of this entry; the workgroups of a LONG sequence return before
+ * any table entry, K/V row or Q row is read, and its merge waves return without writing.  The LONG half is the one launch of the tiled
+ * kernel with its grid from (B, Hkv, G, total_q); a workgroup whose sequence has span_b <= T returns right after the slot search.
+ * With total_q <= T no sequence can be LONG and the LONG half is not launched: a rule on host integers alone.  Nothing on the host
+ * reads device data; a captured call follows cu_seqlens_q, seqlens_k, the block table, the scales and the sinks when they are
+ * rewritten in place, a sequence changing class included; total_q, T, window and softcap are host values.
+ * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_decode_varlen refuses for this descriptor, a missing or
+ * short workspace included, whichever parts are asked for; everything fa_forward_varlen_kvcache[_fp8] refuses for the same fields --
+ * its 32-bit bounds on Q, O and the capacity cover all total_q rows, not T of them; causal != 1 (a mixed step is causal); a NULL
+ * seqlens_k; parts outside {1, 2, 3}.
+ * Not part of this entry: a tree mask (the tree step keeps fa_kvcache_decode_varlen_ex); a threshold per sequence; key splits for
+ * LONG sequences; a shared prefix; concurrency of the two halves managed by the library (the caller has _part for that).  NOT a
+ * reference entry point. */
+#define FA_ATTEND_SHORT 1   /* the split-KV half */
+#define FA_ATTEND_LONG  2   /* the tiled half    */
+int fa_kvcache_attend_varlen(const fa_kvdecode_varlen_desc* desc);            /* == _part(desc, 3) */
+int fa_kvcache_attend_varlen_part(const fa_kvdecode_varlen_desc* desc, int parts);
 
 /* The commit step of tree speculation: after fa_kvcache_append_varlen_ex placed a step's n_b tokens at slots L_b .. L_b + n_b - 1 in
  * tree order and fa_kvcache_decode_varlen_ex verified them, one root-to-node path per sequence is kept.  This entry moves that path's
