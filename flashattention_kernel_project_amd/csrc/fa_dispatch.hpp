@@ -82,7 +82,7 @@ hipError_t rp16_causal_dispatch(const FwdArgs& a, Rp16Family family);   // kFull
 template <int D, int X, bool kDma, bool kCausal, int kWv = 8, int kKeySplit = 1>
 hipError_t rp16_family(const FwdArgs& a, bool fold);
 
-// ---- fa_fwd_split.hip, fa_fwd_kvcache.hip, fa_fwd_kvpaged.hip, fa_fwd_kvfp8.hip, fa_fwd_kvwindow*.hip, fa_fwd_kvlogits*.hip, fa_fwd_kvragged*.hip, fa_fwd_kvpacked*.hip, fa_kvcache_append*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
+// ---- the split-KV stream and what else runs on it or beside it: fa_fwd_split.hip, fa_fwd_kv*.hip, fa_kvcache_*.hip, fa_debug_stages.hip, fa_streaming16.hip ----
 hipError_t split_dispatch(const void* Q, const void* K, const void* V, void* O, void* ws, size_t ws_bytes,
                           int BH, int Nq, int Nk, int D, float scale, int in_dtype, int out_dtype, hipStream_t stream);
 size_t split_workspace_bytes(int BH, int Nq, int Nk, int D);
@@ -108,28 +108,31 @@ struct KvPagedArgs {
     const int* table;
     int num_pages, page_size, max_pages;
 };
-// All eight decode entries (fa_forward_kvcache and its _paged / _fp8 / _window forms): p.c alone for a contiguous cache, all of p
-// with `paged` (Ncap is then filled in by the dispatcher).  With `fp8` K, V point at one-byte e4m3fn elements that are widened to
-// in_dtype on the way into LDS, and k_scale, v_scale are device pointers to Hkv fp32 each, or null (1.0).  window >= 1: row i
-// sees the last `window` keys up to its own position, and the split count, with it grid and workspace, follows from
-// window_span_cap() in place of the capacity; 0: no window; < 0: rejected.
-// fa_kvcache_decode alone sets the last two, at the end so that the eight flat entries' initialisers leave them zero: sinks, a device
-// pointer to Hkv * G fp32 logits (null: none), and softcap (0: off; negative, NaN or inf: rejected).  A call with either runs the
-// LogitArgs kernels of fa_fwd_kvlogits*.hip, which exist around the windowed packs only: window 0 runs there as window = Ncap.
-// seqlens_q, also the descriptor's alone: a device pointer to B int32 query counts (null: every sequence has Nq rows).  A call with it
-// runs the RaggedArgs kernels of fa_fwd_kvragged*.hip, which wrap the LogitArgs packs, so window 0 runs there as window = Ncap too.
-// packed, fa_kvcache_decode_varlen's alone and last for the same reason: where the rows of a token-packed call live.  With it p.c.Q
-// and p.c.O are packed (total_q, Hkv*G, d) tensors behind these strides (elements), p.c.lse is [Hkv*G, total_q], p.c.Nq is max_q and
-// seqlens_q is null: the counts come from cu_q on the device.  A call with it runs the PackedArgs kernels of fa_fwd_kvpacked*.hip,
-// which wrap the RaggedArgs packs.
+// Where the rows of a token-packed call live (fa_kvcache_decode_varlen): Q and O are packed (total_q, Hkv*G, d) tensors behind these
+// strides (elements), lse is [Hkv*G, total_q], and the counts come from cu_q on the device.  tree_mask (fa_kvcache_decode_varlen_ex
+// alone, else null): one 64-bit ancestor word per token row on the device.
 struct KvPackedRows {
     const int* cu_q;
     int total_q;
     long long q_st, q_sh, o_st, o_sh;
-    // fa_kvcache_decode_varlen_ex alone, last so that the other initialisers leave it null: one 64-bit ancestor word per token row on
-    // the device.  A call with it runs the TreeArgs kernels of fa_fwd_kvtree*.hip, which wrap the PackedArgs packs.
     const unsigned long long* tree_mask;
 };
+// The features of the decode stream form a line, each level holding every one below it; kTree and kRouted both stand on kPacked.  A
+// call runs the kernels of the lowest level that has what it asks for.
+enum class KvLevel {
+    kPlain,    // key counts, causal tail, lse
+    kWindow,   // window >= 1
+    kLogits,   // sinks or softcap; from here up window 0 runs as window = capacity
+    kRagged,   // seqlens_q
+    kPacked,   // packed rows (fa_kvcache_decode_varlen)
+    kTree,     // packed rows under a tree mask (fa_kvcache_decode_varlen_ex)
+    kRouted,   // packed rows, sequences above max_q left out (the SHORT half of fa_kvcache_attend_varlen)
+};
+// One decode call, every entry's: p.c alone for a contiguous cache, all of p with `paged` (the checks fill in Ncap).  fp8: K, V hold
+// one-byte e4m3fn elements, and k_scale, v_scale are device pointers to Hkv fp32 each, or null (1.0).  window: 0 none, < 0 rejected.
+// sinks: a device pointer to Hkv * G fp32 logits, or null; softcap: 0 off (negative, NaN or inf: rejected); seqlens_q: a device
+// pointer to B int32 query counts, or null; packed: null but for the token-packed entries, where p.c.Nq is max_q and seqlens_q null.
+// The fields from sinks on come last so that the flat entries' initialisers leave them zero.  level: set by the entry's checker.
 struct KvDecodeArgs {
     KvPagedArgs p;
     const float *k_scale, *v_scale;
@@ -139,56 +142,28 @@ struct KvDecodeArgs {
     float softcap;
     const int* seqlens_q;
     const KvPackedRows* packed;
+    KvLevel level;
 };
+// The kernels of one (level, fp8, paged) cell launched on checked arguments, with the merge behind a split; lg_page: log2 of the page
+// size (paged only).  Defined in fa_fwd_kvdecode.hpp and explicitly instantiated in the fa_fwd_kv*.hip unit that owns the cell.
+template <KvLevel kLevel, bool kFp8, bool kPaged> hipError_t kvdecode_unit(const KvDecodeArgs& a, int lg_page);
+// fa_fwd_kvcache.hip: the flat and descriptor entries' checks (levels kPlain to kRagged); the router every checker hands its checked
+// arguments to; the merge behind a split, for all of them
 hipError_t kvdecode_dispatch(const KvDecodeArgs& a);
-// What kvdecode_dispatch hands checked arguments to: one function per translation unit that owns decode kernels -- fa_fwd_kvcache,
-// _kvpaged, _kvfp8 (contiguous and paged), _kvwindow and _kvwindow_fp8 (window >= 1; contiguous and paged), _kvlogits and
-// _kvlogits_fp8 (sinks or softcap set, window >= 1; contiguous and paged), _kvragged and _kvragged_fp8 (seqlens_q set, window >= 1;
-// contiguous and paged).  lg_page: log2 of the page size (paged only).
-hipError_t kvcache_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvpaged_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvfp8_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvwindow_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvwindow_fp8_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvlogits_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvlogits_fp8_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvragged_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvragged_fp8_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
-                           hipStream_t stream);   // the merge kernel behind a split, for all of them
-// ... and the merge that also joins the heads' sinks (not null), once per row -- fa_fwd_kvlogits.hip; Nq: rows per query head
-hipError_t kvlogits_combine(const void* ws, void* O, float* lse, const float* sinks, int BH, int rows, int Hkv, int Nq, int D, int S,
-                            int in_dtype, int out_dtype, hipStream_t stream);
-// ... and the merge behind the per-sequence query counts (seqlens_q not null; sinks may be null) -- fa_fwd_kvragged.hip; Nq: the padded
-// rows per query head
-hipError_t kvragged_combine(const void* ws, void* O, float* lse, const float* sinks, const int* seqlens_q, int BH, int rows, int Hkv,
-                            int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
-// fa_kvcache_decode_varlen (fa_fwd_kvpacked.hip): the checks, then the PackedArgs kernels of that unit or, on an fp8 cache, of
-// fa_fwd_kvpacked_fp8.hip; the descriptor is the public one, as it is.  d.packed is set for both hand-overs.
+hipError_t kvdecode_route(const KvDecodeArgs& a, int lg_page);
+hipError_t kvdecode_combine(const KvDecodeArgs& a, int S);
+// fa_fwd_kvpacked.hip: fa_kvcache_decode_varlen (tree_mask null) and, through kvtree_dispatch (fa_fwd_kvtree.hip, the options' checks),
+// fa_kvcache_decode_varlen_ex.  kvpacked_check is the checks alone: on success `d` holds the checked arguments (the capacity filled
+// in, the level set, d.packed pointing at `rows_of`, which the caller keeps alive) and lg_page the paged check's
 hipError_t kvpacked_dispatch(const ::fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask = nullptr);
 size_t kvpacked_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc);
-hipError_t kvpacked_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvpacked_fp8_decode(const KvDecodeArgs& a, int lg_page);
-// fa_kvcache_decode_varlen_ex (fa_fwd_kvtree.hip): the options' checks, then kvpacked_dispatch -- without a mask the plain entry's call,
-// with one its checks and the TreeArgs kernels of fa_fwd_kvtree.hip or, on an fp8 cache, of fa_fwd_kvtree_fp8.hip
 hipError_t kvtree_dispatch(const ::fa_kvdecode_varlen_desc* desc, const ::fa_kvdecode_tree_opts* opts);
-hipError_t kvtree_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvtree_fp8_decode(const KvDecodeArgs& a, int lg_page);
-// ... and the merge behind them (fa_fwd_kvpacked.hip): live rows go to their tokens, nothing else is written; Nq: max_q
-hipError_t kvpacked_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
-                            int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
-// fa_kvcache_decode_varlen's checks alone (fa_fwd_kvpacked.hip): on success `d` holds the checked arguments (the capacity filled in,
-// window 0 mapped to the capacity, d.packed pointing at `rows_of`, which the caller keeps alive) and lg_page the paged check's
 hipError_t kvpacked_check(const ::fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask, KvPackedRows& rows_of, KvDecodeArgs& d,
                           int& lg_page);
 // fa_kvcache_attend_varlen[_part] (fa_fwd_kvrouted.hip): kvpacked_check and varlen_cache_check on the one descriptor, then the parts
-// that were asked for -- FA_ATTEND_SHORT: the RoutedArgs kernels of that unit or, on an fp8 cache, of fa_fwd_kvrouted_fp8.hip, with
-// their merge; FA_ATTEND_LONG: the routed varlen cache kernels of fa_fwd_varlen_cache_routed.hip or _routed_fp8.hip
+// that were asked for -- FA_ATTEND_SHORT: level kRouted; FA_ATTEND_LONG: the routed varlen cache kernels of
+// fa_fwd_varlen_cache_routed.hip or _routed_fp8.hip
 hipError_t kvattend_dispatch(const ::fa_kvdecode_varlen_desc* desc, int parts);
-hipError_t kvrouted_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvrouted_fp8_decode(const KvDecodeArgs& a, int lg_page);
-hipError_t kvrouted_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
-                            int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream);
 // args: the checked VarlenCacheArgs (16-bit) or VarlenCacheFp8Args; min_rows: sequences of at most as many rows are skipped
 hipError_t varlen_cache_routed_launch16(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid, int min_rows);
 hipError_t varlen_cache_routed_launch8(const ::fa_varlen_kvcache_desc* desc, const void* args, unsigned grid, int min_rows);

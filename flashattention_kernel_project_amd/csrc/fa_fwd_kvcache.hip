@@ -1,8 +1,7 @@
 // fa_fwd_kvcache.hip -- decode against a pre-allocated KV cache (fa_forward_kvcache): the split-KV stream of fa_fwd_split.hip with
 // the key count of each sequence read on the device, a causal mask aligned to the end of the cache and a log-sum-exp output.
-// DESIGN.md section 7 has the reasoning; the kernels are the CacheArgs instantiations of fa_fwd_split_kernel.hpp, launched through
-// the host path of fa_fwd_kvdecode.hpp like those of the eight units beside this one.  Also here, once for all decode entries:
-// the argument checks, the entry kvdecode_dispatch and the merge kernel.
+// DESIGN.md section 7 has the reasoning.  Owns the plain 16-bit contiguous kernels.  Also here, once for all decode entries: the
+// argument checks, the entry kvdecode_dispatch, the router from a checked call to its kernels and every merge kernel.
 #include "fa_fwd_kvdecode.hpp"
 
 namespace fa {
@@ -31,50 +30,90 @@ hipError_t kvcache_check(const KvCacheArgs& a)
     return hipSuccess;
 }
 
-// The translation unit that owns the kernels of the pack the flags name.  Window 0 is the un-windowed entry itself: it launches
-// the un-windowed kernels.  With sinks or a soft-cap the LogitArgs kernels run, which wrap the windowed packs only: window 0 goes
-// there as window = Ncap, which include/fa_mi355.h guarantees to be the un-windowed result bit for bit, on the same split count.
-// With seqlens_q the RaggedArgs kernels run, which wrap the LogitArgs packs, under the same rule for window 0.
-static hipError_t kvdecode_handover(const KvDecodeArgs& d, int lg_page)
-{
-    if (d.sinks || d.softcap != 0.0f || d.seqlens_q) {
-        KvDecodeArgs w = d;
-        if (w.window == 0) w.window = w.p.c.Ncap;
-        if (w.seqlens_q) return w.fp8 ? kvragged_fp8_decode(w, lg_page) : kvragged_decode(w, lg_page);
-        return w.fp8 ? kvlogits_fp8_decode(w, lg_page) : kvlogits_decode(w, lg_page);
-    }
-    if (d.window == 0) return d.fp8 ? kvfp8_decode(d, lg_page) : d.paged ? kvpaged_decode(d, lg_page) : kvcache_decode(d, lg_page);
-    return d.fp8 ? kvwindow_fp8_decode(d, lg_page) : kvwindow_decode(d, lg_page);
-}
-
-// The one entry behind the eight fa_forward_kvcache* functions: the checks, once, then the hand-over.
+// The one entry behind the eight fa_forward_kvcache* functions and fa_kvcache_decode: the checks, once, then the lowest level that
+// has what the call asks for.
 hipError_t kvdecode_dispatch(const KvDecodeArgs& d)
 {
     if (d.window < 0) return hipErrorInvalidValue;
     if (!(d.softcap >= 0.0f) || __builtin_isinf(d.softcap)) return hipErrorInvalidValue;   // negative, NaN or inf
-    if (!d.paged) {
-        const hipError_t bad = kvcache_check(d.p.c);
-        return bad != hipSuccess ? bad : kvdecode_handover(d, 0);
-    }
-    KvDecodeArgs q = {{}, d.k_scale, d.v_scale, d.window, d.paged, d.fp8, d.sinks, d.softcap, d.seqlens_q};   // q.p: d.p with the capacity, from the check
-    int lg_page;
-    const hipError_t bad = kvpaged_check(d.p, q.p, lg_page);
-    return bad != hipSuccess ? bad : kvdecode_handover(q, lg_page);
+    KvDecodeArgs q = d;   // ... with the capacity, from the paged check
+    int lg_page = 0;
+    const hipError_t bad = d.paged ? kvpaged_check(d.p, q.p, lg_page) : kvcache_check(d.p.c);
+    if (bad != hipSuccess) return bad;
+    q.level = d.seqlens_q                      ? KvLevel::kRagged
+              : d.sinks || d.softcap != 0.0f ? KvLevel::kLogits
+              : d.window != 0                 ? KvLevel::kWindow
+                                              : KvLevel::kPlain;
+    return kvdecode_route(q, lg_page);
 }
 
-hipError_t kvcache_decode(const KvDecodeArgs& d, int lg_page) { return dispatch_kvdecode<CacheArgs>(d, lg_page); }
+// The router below names all 28 cells with kvdecode_unit's definition in sight; each is instantiated in the unit that owns its
+// kernels and nowhere by use, so implicit instantiation is switched off for all of them, and this unit's own cell follows.
+#define FA_KVDECODE_EXTERN(level)                                                                       \
+    extern template hipError_t kvdecode_unit<KvLevel::level, false, false>(const KvDecodeArgs&, int); \
+    extern template hipError_t kvdecode_unit<KvLevel::level, false, true>(const KvDecodeArgs&, int);  \
+    extern template hipError_t kvdecode_unit<KvLevel::level, true, false>(const KvDecodeArgs&, int);  \
+    extern template hipError_t kvdecode_unit<KvLevel::level, true, true>(const KvDecodeArgs&, int);
+FA_KVDECODE_EXTERN(kPlain)
+FA_KVDECODE_EXTERN(kWindow)
+FA_KVDECODE_EXTERN(kLogits)
+FA_KVDECODE_EXTERN(kRagged)
+FA_KVDECODE_EXTERN(kPacked)
+FA_KVDECODE_EXTERN(kTree)
+FA_KVDECODE_EXTERN(kRouted)
+#undef FA_KVDECODE_EXTERN
+template hipError_t kvdecode_unit<KvLevel::kPlain, false, false>(const KvDecodeArgs&, int);
 
-// The merge behind a split, for every decode entry: the kernel is instantiated in this translation unit only.
-hipError_t kvcache_combine(const void* ws, void* O, float* lse, int BH, int rows, int D, int S, int in_dtype, int out_dtype,
-                           hipStream_t stream)
+template <KvLevel kLevel>
+static hipError_t route_cache(const KvDecodeArgs& d, int lg_page)
 {
-    const long long out_rows = (long long)BH * rows;   // one wave per output row
+    if (d.fp8) return d.paged ? kvdecode_unit<kLevel, true, true>(d, lg_page) : kvdecode_unit<kLevel, true, false>(d, lg_page);
+    return d.paged ? kvdecode_unit<kLevel, false, true>(d, lg_page) : kvdecode_unit<kLevel, false, false>(d, lg_page);
+}
+
+// Checked arguments (level, fp8, paged) -> the instantiation: the one list of the 28 packs.  The packs from kLogits up wrap a
+// WindowArgs whatever the call's window, so window 0 runs there as window = Ncap: include/fa_mi355.h guarantees that to be the
+// un-windowed result bit for bit, and kvdecode_span() gives it the same split count.
+hipError_t kvdecode_route(const KvDecodeArgs& checked, int lg_page)
+{
+    KvDecodeArgs d = checked;
+    if (d.level >= KvLevel::kLogits && d.window == 0) d.window = d.p.c.Ncap;
+    switch (d.level) {
+    case KvLevel::kPlain: return route_cache<KvLevel::kPlain>(d, lg_page);
+    case KvLevel::kWindow: return route_cache<KvLevel::kWindow>(d, lg_page);
+    case KvLevel::kLogits: return route_cache<KvLevel::kLogits>(d, lg_page);
+    case KvLevel::kRagged: return route_cache<KvLevel::kRagged>(d, lg_page);
+    case KvLevel::kPacked: return route_cache<KvLevel::kPacked>(d, lg_page);
+    case KvLevel::kTree: return route_cache<KvLevel::kTree>(d, lg_page);
+    case KvLevel::kRouted: return route_cache<KvLevel::kRouted>(d, lg_page);
+    }
+    return hipErrorInvalidValue;
+}
+
+// The merge behind a split, for every level: one wave per output row (the padded rows where the counts are the device's), and the
+// Lse value that tells the kernel what a row is -- float*: rows as they are; SinkLse: a sink joins each row; RaggedLse: seqlens_q says
+// which rows are live, the dead ones are written as zeros; PackedLse: live rows go to their tokens, nothing else is written;
+// RoutedLse: the same with the routed row count.  The merge kernels are instantiated in this translation unit only.
+hipError_t kvdecode_combine(const KvDecodeArgs& d, int S)
+{
+    const KvCacheArgs& a = d.p.c;
+    const int BH = a.B * a.Hkv, rows = a.G * a.Nq;
+    const long long out_rows = (long long)BH * rows;
     if (out_rows > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
-        FA_LAUNCH((fa_split_combine_kernel<decltype(t), decltype(f32)::value, true, float*>), dim3((unsigned)out_rows), dim3(64), 0,
-                  stream, static_cast<const float*>(ws), O, BH, rows, D, S, lse);
-        return launch_status();
-    });
+    auto launch = [&](auto lse) {
+        return with_types(a.in_dtype, a.out_dtype, [&](auto t, auto f32) {
+            FA_LAUNCH((fa_split_combine_kernel<decltype(t), decltype(f32)::value, true, decltype(lse)>), dim3((unsigned)out_rows), dim3(64), 0,
+                      a.stream, static_cast<const float*>(a.ws), a.O, BH, rows, a.D, S, lse);
+            return launch_status();
+        });
+    };
+    if (d.level >= KvLevel::kPacked) {
+        const PackedLse packed = {a.lse, d.sinks, d.packed->cu_q, a.Hkv, a.Nq, d.packed->total_q, d.packed->o_st, d.packed->o_sh};
+        return d.level == KvLevel::kRouted ? launch(RoutedLse{packed}) : launch(packed);
+    }
+    if (d.level == KvLevel::kRagged) return launch(RaggedLse{a.lse, d.sinks, d.seqlens_q, a.Hkv, a.Nq});
+    if (d.level == KvLevel::kLogits && d.sinks) return launch(SinkLse{a.lse, d.sinks, a.Hkv, a.Nq});
+    return launch(a.lse);
 }
 
 }  // namespace fa

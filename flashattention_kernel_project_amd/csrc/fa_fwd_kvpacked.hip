@@ -1,34 +1,15 @@
 // fa_fwd_kvpacked.hip -- token-packed (cu_seqlens) split-KV decode against a 16-bit cache, contiguous and paged
 // (fa_kvcache_decode_varlen): the streams of fa_fwd_kvragged.hip with Q, O and lse in the packed layout of fa_forward_varlen_kvcache
-// and each sequence's rows cut from cu_seqlens_q on the device.  DESIGN.md section 7.17 has the reasoning; the kernels are the
-// PackedArgs<RaggedArgs<LogitArgs<WindowArgs<...>>>> instantiations of fa_fwd_split_kernel.hpp, launched through fa_fwd_kvdecode.hpp.
-// The fp8 forms are in fa_fwd_kvpacked_fp8.hip.  Also here, for both units: the entry's checks and the merge that stores the live
-// rows to their tokens and nothing else.
+// and each sequence's rows cut from cu_seqlens_q on the device.  DESIGN.md section 7.17 has the reasoning.  Owns the 16-bit kernels of level kPacked
+// (DESIGN.md 7.21); the fp8 forms are in fa_fwd_kvpacked_fp8.hip.  Also here, for both units and for levels kTree and kRouted: the
+// entry's checks.
 #include "fa_fwd_kvdecode.hpp"
 #include "fa_fwd_varlen_kernel.hpp"   // varlen_tensor_ok()
 
 namespace fa {
 
-hipError_t kvpacked_decode(const KvDecodeArgs& d, int lg_page)
-{
-    return !d.paged ? dispatch_kvdecode<PackedArgs<RaggedArgs<LogitArgs<WindowArgs<CacheArgs>>>>>(d, lg_page)
-                    : dispatch_kvdecode<PackedArgs<RaggedArgs<LogitArgs<WindowArgs<PagedArgs>>>>>(d, lg_page);
-}
-
-// kvragged_combine with the live rows stored to their tokens: the PackedLse instantiations of the merge kernel.  The grid follows
-// the host shape (one wave per padded row); which rows are live, and where they go, is decided on the device.
-hipError_t kvpacked_combine(const void* ws, void* O, float* lse, const float* sinks, const KvPackedRows& rows_of, int BH, int rows,
-                            int Hkv, int Nq, int D, int S, int in_dtype, int out_dtype, hipStream_t stream)
-{
-    const long long out_rows = (long long)BH * rows;
-    if (out_rows > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
-        FA_LAUNCH((fa_split_combine_kernel<decltype(t), decltype(f32)::value, true, PackedLse>), dim3((unsigned)out_rows), dim3(64), 0,
-                  stream, static_cast<const float*>(ws), O, BH, rows, D, S,
-                  PackedLse{lse, sinks, rows_of.cu_q, Hkv, Nq, rows_of.total_q, rows_of.o_st, rows_of.o_sh});
-        return launch_status();
-    });
-}
+template hipError_t kvdecode_unit<KvLevel::kPacked, false, false>(const KvDecodeArgs&, int);
+template hipError_t kvdecode_unit<KvLevel::kPacked, false, true>(const KvDecodeArgs&, int);
 
 // what the descriptor alone can get wrong (the rule of fa_kvcache_decode's descriptor, with one size only)
 static bool kvpacked_desc_ok(const fa_kvdecode_varlen_desc* desc)
@@ -58,9 +39,8 @@ static bool packed_view_ok(int max_q, int total, long long Hq, int d, long long 
     return end <= 0xFFFFFFFFull;
 }
 
-// The checks of kvdecode_dispatch (fa_fwd_kvcache.hip) with Nq = max_q, then the packed tensors', then the hand-over: the PackedArgs
-// kernels wrap the RaggedArgs packs, which exist around the windowed ones only, so window 0 runs as window = the capacity.
-// tree_mask (fa_kvcache_decode_varlen_ex; null: none): the same checks, the mask's own, and the TreeArgs kernels of fa_fwd_kvtree*.hip.
+// The checks of kvdecode_dispatch (fa_fwd_kvcache.hip) with Nq = max_q, then the packed tensors'; the level is kPacked, or kTree with
+// a tree_mask (fa_kvcache_decode_varlen_ex; null: none), which adds the mask's own checks.
 // The checks stand alone (kvpacked_check) because fa_kvcache_attend_varlen runs them too, on the same descriptor.
 hipError_t kvpacked_check(const fa_kvdecode_varlen_desc* desc, const unsigned long long* tree_mask, KvPackedRows& rows_of, KvDecodeArgs& d,
                           int& lg_page)
@@ -80,7 +60,7 @@ hipError_t kvpacked_check(const fa_kvdecode_varlen_desc* desc, const unsigned lo
                .page_size = paged ? desc->page_size : 0, .max_pages = paged ? desc->max_pages : 0},
          .k_scale = desc->k_scale, .v_scale = desc->v_scale, .window = desc->window, .paged = paged,
          .fp8 = desc->kv_dtype == FA_KV_FP8_E4M3, .sinks = desc->sinks, .softcap = desc->softcap, .seqlens_q = nullptr,
-         .packed = &rows_of};
+         .packed = &rows_of, .level = tree_mask ? KvLevel::kTree : KvLevel::kPacked};
     lg_page = 0;
     if (!paged) {
         const hipError_t bad = kvcache_check(d.p.c);
@@ -100,7 +80,6 @@ hipError_t kvpacked_check(const fa_kvdecode_varlen_desc* desc, const unsigned lo
     if (!packed_view_ok(desc->max_q, desc->total_q, Hq, desc->d, desc->q_stride_t, desc->q_stride_h, 2u) ||
         !packed_view_ok(desc->max_q, desc->total_q, Hq, desc->d, desc->o_stride_t, desc->o_stride_h, es))
         return hipErrorInvalidValue;
-    if (d.window == 0) d.window = d.p.c.Ncap;
     return hipSuccess;
 }
 
@@ -110,9 +89,7 @@ hipError_t kvpacked_dispatch(const fa_kvdecode_varlen_desc* desc, const unsigned
     KvDecodeArgs d;
     int lg_page;
     const hipError_t bad = kvpacked_check(desc, tree_mask, rows_of, d, lg_page);
-    if (bad != hipSuccess) return bad;
-    if (tree_mask) return d.fp8 ? kvtree_fp8_decode(d, lg_page) : kvtree_decode(d, lg_page);
-    return d.fp8 ? kvpacked_fp8_decode(d, lg_page) : kvpacked_decode(d, lg_page);
+    return bad != hipSuccess ? bad : kvdecode_route(d, lg_page);
 }
 
 }  // namespace fa

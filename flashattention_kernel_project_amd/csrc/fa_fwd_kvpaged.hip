@@ -1,7 +1,7 @@
 // fa_fwd_kvpaged.hip -- decode against a paged KV cache (fa_forward_kvcache_paged): the KV-cache stream of fa_fwd_kvcache.hip with
 // every tile's rows taken from pages of a pool through a block table that is read on the device.  DESIGN.md section 7.2 has the
-// reasoning; the kernels are the PagedArgs instantiations of fa_fwd_split_kernel.hpp, launched through fa_fwd_kvdecode.hpp; the
-// merge is fa_fwd_kvcache.hip's.  Also here: the page-geometry checks every paged entry (decode and append) shares.
+// reasoning.  Owns the plain 16-bit paged kernels.  Also here: the page-geometry checks every paged entry (decode
+// and append) shares.
 #include "fa_fwd_kvdecode.hpp"
 
 namespace fa {
@@ -35,6 +35,6 @@ hipError_t kvpaged_check(const KvPagedArgs& p, KvPagedArgs& q, int& lg_page)
     return kvcache_check(q.c);
 }
 
-hipError_t kvpaged_decode(const KvDecodeArgs& d, int lg_page) { return dispatch_kvdecode<PagedArgs>(d, lg_page); }
+template hipError_t kvdecode_unit<KvLevel::kPlain, false, true>(const KvDecodeArgs&, int);
 
 }  // namespace fa

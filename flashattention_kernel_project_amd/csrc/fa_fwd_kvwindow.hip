@@ -1,8 +1,7 @@
 // fa_fwd_kvwindow.hip -- sliding-window decode against a 16-bit KV cache, contiguous (fa_forward_kvcache_window) and paged
 // (fa_forward_kvcache_paged_window): the streams of fa_fwd_kvcache.hip / fa_fwd_kvpaged.hip with a lower key limit per row and a
-// first tile per sequence.  DESIGN.md section 7.6 has the reasoning; the kernels are the WindowArgs instantiations of
-// fa_fwd_split_kernel.hpp, launched through fa_fwd_kvdecode.hpp; the merge is fa_fwd_kvcache.hip's.  The fp8 forms are in
-// fa_fwd_kvwindow_fp8.hip.  Also here: the window's span and the two windowed sizing functions.
+// first tile per sequence.  DESIGN.md section 7.6 has the reasoning.  Owns the 16-bit kernels of level kWindow; the
+// fp8 forms are in fa_fwd_kvwindow_fp8.hip.  Also here: the window's span and the two windowed sizing functions.
 #include "fa_fwd_kvdecode.hpp"
 
 namespace fa {
@@ -32,9 +31,7 @@ size_t kvpaged_window_workspace_bytes(int B, int Hkv, int G, int Nq, int max_pag
 }
 
 // The split count follows from window_span_cap, not from the capacity; grid and workspace follow from it.
-hipError_t kvwindow_decode(const KvDecodeArgs& d, int lg_page)
-{
-    return !d.paged ? dispatch_kvdecode<WindowArgs<CacheArgs>>(d, lg_page) : dispatch_kvdecode<WindowArgs<PagedArgs>>(d, lg_page);
-}
+template hipError_t kvdecode_unit<KvLevel::kWindow, false, false>(const KvDecodeArgs&, int);
+template hipError_t kvdecode_unit<KvLevel::kWindow, false, true>(const KvDecodeArgs&, int);
 
 }  // namespace fa

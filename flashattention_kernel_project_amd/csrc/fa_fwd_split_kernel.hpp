@@ -1,16 +1,22 @@
-// fa_fwd_split_kernel.hpp -- device code of the split-KV stream, shared by fa_fwd_split.hip (fa_forward_splitkv),
-// fa_fwd_kvcache.hip (fa_forward_kvcache), fa_fwd_kvpaged.hip (fa_forward_kvcache_paged) and fa_fwd_kvfp8.hip (the two _fp8
-// entries).  One kernel template serves all of them: what the KV-cache entry adds is a template flag and a trailing parameter
-// pack, so the plain instantiations keep their argument list and their code (profiles/kvcache_decode.txt); the paged entry passes
-// a PagedArgs in that pack, and everything it adds sits behind `if constexpr (kPaged)` (profiles/kvcache_paged.txt); the fp8
-// entries pass an Fp8Args<CacheArgs | PagedArgs>, and what they add sits behind `if constexpr (kFp8)` or a constant that kFp8
-// selects (profiles/kvcache_fp8.txt); the token-packed entry (fa_kvcache_decode_varlen) wraps the four RaggedArgs packs in a
-// PackedArgs, and what it adds sits behind `if constexpr (kPacked)` (profiles/kvcache_decode_varlen.txt); the sliding-window entries wrap any of those three in a WindowArgs, and what they add sits
-// behind `if constexpr (kWindow)` (profiles/kvcache_window.txt); the soft-cap / sink entry wraps the four windowed packs in a
-// LogitArgs, and what it adds sits behind `if constexpr (kLogits)` (profiles/kvcache_logits.txt); the per-sequence query count wraps
-// the four LogitArgs packs in a RaggedArgs, and what it adds sits behind `if constexpr (kRagged)` (profiles/kvcache_ragged.txt).
-// The sets are instantiated in separate translation units so that none perturbs another's register allocation; the host path of the
-// KV-cache sets (pack builder, launcher, type switch) is fa_fwd_kvdecode.hpp.  Design notes: head of fa_fwd_split.hip, DESIGN.md 7.1.
+// fa_fwd_split_kernel.hpp -- device code of the split-KV stream: one kernel template for fa_forward_splitkv (fa_fwd_split.hip) and
+// for every KV-cache decode entry, and the merge kernel behind a split.  The plain instantiations take no trailing argument; a
+// KV-cache instantiation (kCache) takes ONE pack, a CacheArgs inside the wrappers of the parts it has.  A wrapper derives from what
+// it wraps and adds its bit to kParts, and everything a part adds to the kernel sits behind `if constexpr` of its flag:
+//
+//   part (pack type)       what it adds                                             guard      note under profiles/
+//   CacheArgs              key counts read on the device, causal tail, lse          kCache     kvcache_decode.txt
+//   PagedArgs              K/V rows from pages of a pool, through a block table     kPaged     kvcache_paged.txt
+//   Fp8Args<>              one-byte e4m3fn K/V, widened into LDS; per-head scales   kFp8       kvcache_fp8.txt
+//   WindowArgs<>           a lower key limit per row, a first tile per sequence     kWindow    kvcache_window.txt
+//   LogitArgs<>            soft-capped scores, one sink logit per query head        kLogits    kvcache_logits.txt
+//   RaggedArgs<>           a query row count per sequence                           kRagged    kvcache_ragged.txt
+//   PackedArgs<>           token-packed Q, O and lse, row counts from cu_q          kPacked    kvcache_decode_varlen.txt
+//   TreeArgs<>             a 64-bit ancestor word per row for the causal triangle   kTree      kvcache_tree.txt
+//   RoutedArgs<>           a sequence above max_q rows has no live row here         kRouted    kvcache_attend_varlen.txt
+//
+// The wrappers nest in one order -- [Paged] < [Fp8] < Window < Logit < Ragged < Packed < {Tree | Routed} -- and the packs the library
+// instantiates, with the translation unit that owns each, are named in fa_fwd_kvdecode.hpp (PackFor) and DESIGN.md 7.21.  What each
+// part does in the kernel is told above the kernel.  Design notes: head of fa_fwd_split.hip, DESIGN.md 7.1.
 #pragma once
 #include "fa_tile.hpp"
 
@@ -30,8 +36,14 @@ constexpr int kRows = 32 * kW;        // query rows per workgroup
 }  // namespace split
 constexpr float kLn2 = 0.6931471805599453f;
 
+// One bit per part of a pack: a pack's kParts is its base's with its own bit set, and the kernel's k* flags are tests of it.
+namespace kvpart {
+constexpr unsigned kPaged = 1u, kFp8 = 2u, kWindow = 4u, kLogits = 8u, kRagged = 16u, kPacked = 32u, kTree = 64u, kRouted = 128u;
+}
+
 // What the KV-cache instantiations (kCache) take as their trailing argument; the plain split kernels have no such argument.
 struct CacheArgs {
+    static constexpr unsigned kParts = 0u;
     const int* seqlens;   // [B] key counts on the device, or nullptr: every sequence holds Nk keys
     float* lse;           // [BH][Nq] natural-log sum of exponentials, or nullptr
     int Hkv;              // K/V heads per batch entry: bh / Hkv indexes seqlens
@@ -42,75 +54,46 @@ struct CacheArgs {
 // What the paged instantiations take instead: the CacheArgs plus where a key's row lives.  K/V are pools [num_pages, Hkv, page, D];
 // key j of sequence b is row j % page of page table[b * max_pages + j / page].
 struct PagedArgs : CacheArgs {
+    static constexpr unsigned kParts = CacheArgs::kParts | kvpart::kPaged;
     const int* table;     // [B][max_pages] page numbers on the device
     int max_pages;        // row pitch of the table; the capacity Nk is max_pages << lg_page
     int num_pages;        // pages in the pool: a live entry outside [0, num_pages) reads as a page of zeros
     int lg_page;          // log2 of the page size in keys (>= 4)
 };
-struct NoPages {};
-__device__ __forceinline__ NoPages paged_part() { return {}; }
-__device__ __forceinline__ NoPages paged_part(const CacheArgs&) { return {}; }
-__device__ __forceinline__ const PagedArgs& paged_part(const PagedArgs& p) { return p; }
 
 // What the fp8 instantiations take: the CacheArgs or the PagedArgs plus the dequantisation scales.  K/V elements are then ONE byte
 // (OCP e4m3fn) and are widened to T while a tile is written to LDS; the kernel's K/V pointers address bytes.
 template <typename Base> struct Fp8Args : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kFp8;
     const float* k_scale;   // [Hkv] on the device, or nullptr (1.0): the logits are scale * k_scale[hkv] * q.k8
     const float* v_scale;   // [Hkv] on the device, or nullptr (1.0): the output is v_scale[hkv] * softmax.v8
 };
-template <typename A> struct IsFp8Args : std::false_type {};
-template <typename Base> struct IsFp8Args<Fp8Args<Base>> : std::true_type {};
-struct NoScales {};
-__device__ __forceinline__ NoScales fp8_part() { return {}; }
-__device__ __forceinline__ NoScales fp8_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const Fp8Args<Base>& fp8_part(const Fp8Args<Base>& f) { return f; }
 
 // What the sliding-window instantiations take: any of the packs above plus the window.  Row i of a head sees the keys
 // [max(0, L - Nq1 + 1 + i - window), c_i) with c_i the limit of the wrapped pack (L, or the causal one).  The wrapper derives from
-// what it wraps, so the kPaged test and paged_part() / fp8_part() see through it; IsFp8Args needs the line below.
+// what it wraps, so the wrapped pack's fields and parts are its own.
 template <typename Base> struct WindowArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kWindow;
     int window;           // >= 1 (0, "no window", never reaches the kernel: the host calls the wrapped entry)
 };
-template <typename A> struct IsWindowArgs : std::false_type {};
-template <typename Base> struct IsWindowArgs<WindowArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<WindowArgs<Base>> : IsFp8Args<Base> {};
-struct NoWindow {};
-__device__ __forceinline__ NoWindow window_part() { return {}; }
-__device__ __forceinline__ NoWindow window_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const WindowArgs<Base>& window_part(const WindowArgs<Base>& w) { return w; }
 
 // What the soft-cap / attention-sink instantiations take (fa_kvcache_decode): a WindowArgs pack plus the two options on the logits.
 // The cap comes in log2 units, as the scores do once they are multiplied by the folded factor c; the sinks are one natural-log
 // logit per QUERY head and never enter the tile loop (they join in the one-pass epilogue and in the merge, SinkLse below).
 template <typename Base> struct LogitArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kLogits;
     const float* sinks;   // [Hkv * G] on the device, or nullptr: none
     float cap2;           // softcap * log2(e); 0: no cap (the tile loop then runs the wrapped pack's arithmetic)
     float cap_rk;         // 2 / softcap: 2^(x * cap_rk) = e^(2 x / cap2) for a score x in log2 units
 };
-template <typename A> struct IsLogitArgs : std::false_type {};
-template <typename Base> struct IsLogitArgs<LogitArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<LogitArgs<Base>> : IsFp8Args<Base> {};
-template <typename Base> struct IsWindowArgs<LogitArgs<Base>> : IsWindowArgs<Base> {};
-struct NoLogits {};
-__device__ __forceinline__ NoLogits logit_part() { return {}; }
-__device__ __forceinline__ NoLogits logit_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const LogitArgs<Base>& logit_part(const LogitArgs<Base>& l) { return l; }
 
 // What the per-sequence query count instantiations take (fa_kvcache_decode with seqlens_q): a LogitArgs pack plus the counts.  The
 // CacheArgs' Nq1 is then the PADDED row count per query head; sequence b has n_b = min(max(seqlens_q[b], 0), Nq1) live rows per
 // head, and n_b takes the place of Nq1 in every limit.
 template <typename Base> struct RaggedArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kRagged;
     const int* seqlens_q;   // [B] on the device, not null (without it the host runs the wrapped pack's kernels)
 };
-template <typename A> struct IsRaggedArgs : std::false_type {};
-template <typename Base> struct IsRaggedArgs<RaggedArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<RaggedArgs<Base>> : IsFp8Args<Base> {};
-template <typename Base> struct IsWindowArgs<RaggedArgs<Base>> : IsWindowArgs<Base> {};
-template <typename Base> struct IsLogitArgs<RaggedArgs<Base>> : IsLogitArgs<Base> {};
-struct NoRagged {};
-__device__ __forceinline__ NoRagged ragged_part() { return {}; }
-__device__ __forceinline__ NoRagged ragged_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const RaggedArgs<Base>& ragged_part(const RaggedArgs<Base>& g) { return g; }
 
 // What the token-packed instantiations take (fa_kvcache_decode_varlen): a RaggedArgs pack plus where the rows live.  Q and O are
 // packed (total_q, Hkv*G, d) tensors read and written through their strides, lse is [Hkv*G, total_q], and sequence b owns the tokens
@@ -118,48 +101,30 @@ template <typename Base> __device__ __forceinline__ const RaggedArgs<Base>& ragg
 // wrapped pack's seqlens_q is null and never read).  Strides in elements; every byte offset inside one (sequence, K/V head) view --
 // rows [0, n_b) of the G heads of the group -- fits 32 bits (checked on the host).
 template <typename Base> struct PackedArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kPacked;
     const int* cu_q;        // [B + 1] on the device, not null
     int total_q;
     long long q_st, q_sh, o_st, o_sh;
 };
-template <typename A> struct IsPackedArgs : std::false_type {};
-template <typename Base> struct IsPackedArgs<PackedArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<PackedArgs<Base>> : IsFp8Args<Base> {};
-template <typename Base> struct IsWindowArgs<PackedArgs<Base>> : IsWindowArgs<Base> {};
-template <typename Base> struct IsLogitArgs<PackedArgs<Base>> : IsLogitArgs<Base> {};
-template <typename Base> struct IsRaggedArgs<PackedArgs<Base>> : IsRaggedArgs<Base> {};
-struct NoPacked {};
-__device__ __forceinline__ NoPacked packed_part() { return {}; }
-__device__ __forceinline__ NoPacked packed_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const PackedArgs<Base>& packed_part(const PackedArgs<Base>& k) { return k; }
 // What the tree-mask instantiations take (fa_kvcache_decode_varlen_ex with a mask): a PackedArgs pack plus one 64-bit word per token
 // row.  Bit j of token s_b + i's word: row i sees the step's own token j, the key at base_b + j with base_b = L_b - n_b; the keys below
 // base_b are visible to every row.  The words take the place of the causal triangle (the host refuses causal != 1 and max_q > 64).
 template <typename Base> struct TreeArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kTree;
     const unsigned long long* tree_mask;   // [total_q] on the device, 8-byte aligned, not null
 };
-template <typename A> struct IsTreeArgs : std::false_type {};
-template <typename Base> struct IsTreeArgs<TreeArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<TreeArgs<Base>> : IsFp8Args<Base> {};
-template <typename Base> struct IsWindowArgs<TreeArgs<Base>> : IsWindowArgs<Base> {};
-template <typename Base> struct IsLogitArgs<TreeArgs<Base>> : IsLogitArgs<Base> {};
-template <typename Base> struct IsRaggedArgs<TreeArgs<Base>> : IsRaggedArgs<Base> {};
-template <typename Base> struct IsPackedArgs<TreeArgs<Base>> : IsPackedArgs<Base> {};
-struct NoTree {};
-__device__ __forceinline__ NoTree tree_part() { return {}; }
-__device__ __forceinline__ NoTree tree_part(const CacheArgs&) { return {}; }
-template <typename Base> __device__ __forceinline__ const TreeArgs<Base>& tree_part(const TreeArgs<Base>& t) { return t; }
 // What the routed instantiations take (the SHORT half of fa_kvcache_attend_varlen): a PackedArgs pack and nothing more -- the type alone
 // says that a sequence with more than Nq1 rows has NO live row here (routed_rows) where the wrapped pack cuts it to its first Nq1: the
 // tiled kernel owns such a sequence.  Its workgroups then take the n_b = 0 path and return before any table entry, K/V or Q row is read.
-template <typename Base> struct RoutedArgs : Base {};
-template <typename A> struct IsRoutedArgs : std::false_type {};
-template <typename Base> struct IsRoutedArgs<RoutedArgs<Base>> : std::true_type {};
-template <typename Base> struct IsFp8Args<RoutedArgs<Base>> : IsFp8Args<Base> {};
-template <typename Base> struct IsWindowArgs<RoutedArgs<Base>> : IsWindowArgs<Base> {};
-template <typename Base> struct IsLogitArgs<RoutedArgs<Base>> : IsLogitArgs<Base> {};
-template <typename Base> struct IsRaggedArgs<RoutedArgs<Base>> : IsRaggedArgs<Base> {};
-template <typename Base> struct IsPackedArgs<RoutedArgs<Base>> : IsPackedArgs<Base> {};
+template <typename Base> struct RoutedArgs : Base {
+    static constexpr unsigned kParts = Base::kParts | kvpart::kRouted;
+};
+// The kernel's one view of its trailing argument: the pack itself, or an empty struct for the plain instantiations.  Every field is
+// read inside an `if constexpr` of its part's flag, so a pack without the part (and the empty struct) is never asked for it.  The merge
+// kernel reads its Lse argument the same way.
+struct NoPack {};
+__device__ __forceinline__ NoPack pack_of() { return {}; }
+template <typename A> __device__ __forceinline__ const A& pack_of(const A& a) { return a; }
 // what a kPacked kernel keeps about its (sequence, K/V head) view -- all of it wave-uniform but the lane's offsets and (hd, i), which
 // live in the prologue (qoff) or in the epilogue (the rest) only
 struct PackedView {
@@ -313,21 +278,11 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     static_assert(sizeof...(Cache) == (kCache ? 1 : 0), "the KV-cache instantiations take one CacheArgs or PagedArgs, the plain ones nothing");
     using G = TileGeom<D>;
     [[maybe_unused]] const CacheArgs ca = {cache...};
-    constexpr bool kPaged = (std::is_base_of_v<PagedArgs, Cache> || ...);
-    [[maybe_unused]] const auto pa = paged_part(cache...);
-    constexpr bool kFp8 = (IsFp8Args<Cache>::value || ...);
-    [[maybe_unused]] const auto fa8 = fp8_part(cache...);
-    constexpr bool kWindow = (IsWindowArgs<Cache>::value || ...);
-    [[maybe_unused]] const auto wa = window_part(cache...);
-    constexpr bool kLogits = (IsLogitArgs<Cache>::value || ...);
-    [[maybe_unused]] const auto la = logit_part(cache...);
-    constexpr bool kRagged = (IsRaggedArgs<Cache>::value || ...);
-    [[maybe_unused]] const auto ra = ragged_part(cache...);
-    constexpr bool kPacked = (IsPackedArgs<Cache>::value || ...);
-    [[maybe_unused]] const auto ka = packed_part(cache...);
-    constexpr bool kRouted = (IsRoutedArgs<Cache>::value || ...);
-    constexpr bool kTree = (IsTreeArgs<Cache>::value || ...);
-    [[maybe_unused]] const auto ta = tree_part(cache...);
+    [[maybe_unused]] const auto pa = pack_of(cache...);   // the whole pack; a part's fields are read under its flag only
+    constexpr unsigned kParts = (0u | ... | Cache::kParts);
+    constexpr bool kPaged = (kParts & kvpart::kPaged) != 0, kFp8 = (kParts & kvpart::kFp8) != 0, kWindow = (kParts & kvpart::kWindow) != 0;
+    constexpr bool kLogits = (kParts & kvpart::kLogits) != 0, kRagged = (kParts & kvpart::kRagged) != 0;
+    constexpr bool kPacked = (kParts & kvpart::kPacked) != 0, kTree = (kParts & kvpart::kTree) != 0, kRouted = (kParts & kvpart::kRouted) != 0;
     constexpr unsigned kKvRowBytes = kFp8 ? D : G::kRowBytes;      // bytes of one K or V row in memory
     constexpr unsigned kLdChunks = kFp8 ? D / 16 : G::kChunks;     // 16-byte loads per row
     using namespace split;
@@ -361,11 +316,11 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     // kPacked: the count comes from the sequence's clamped cu_q pair, whose first token pv.s is where its rows start; no dead row
     // is written
     [[maybe_unused]] unsigned n_q = 0, live = 0;
-    [[maybe_unused]] std::conditional_t<kPacked, PackedView, NoPacked> pv;
+    [[maybe_unused]] std::conditional_t<kPacked, PackedView, NoPack> pv;
     if constexpr (kRagged) {
-        if constexpr (kRouted) routed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
-        else if constexpr (kPacked) packed_rows(ka.cu_q, bh / (unsigned)ca.Hkv, ka.total_q, ca.Nq1, pv.s, n_q);
-        else n_q = (unsigned)min(max(ra.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
+        if constexpr (kRouted) routed_rows(pa.cu_q, bh / (unsigned)ca.Hkv, pa.total_q, ca.Nq1, pv.s, n_q);
+        else if constexpr (kPacked) packed_rows(pa.cu_q, bh / (unsigned)ca.Hkv, pa.total_q, ca.Nq1, pv.s, n_q);
+        else n_q = (unsigned)min(max(pa.seqlens_q[bh / (unsigned)ca.Hkv], 0), ca.Nq1);
         live = ((unsigned)Nq / (unsigned)ca.Nq1) * n_q;
         if constexpr (!kPartial && !kPacked) {
             const unsigned pr = qb * (unsigned)kRows + (tid >> 1);
@@ -385,8 +340,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     // kWindow: the first key any row of the sequence sees, the tile it lies in, and the tiles from there dealt out to the splits
     [[maybe_unused]] unsigned start_b = 0, start_t = 0;
     if constexpr (kWindow) {
-        if constexpr (kRagged) start_b = (unsigned)max((int)nkeys - (int)n_q + 1 - wa.window, 0);
-        else start_b = (unsigned)max((int)nkeys - ca.Nq1 + 1 - wa.window, 0);
+        if constexpr (kRagged) start_b = (unsigned)max((int)nkeys - (int)n_q + 1 - pa.window, 0);
+        else start_b = (unsigned)max((int)nkeys - ca.Nq1 + 1 - pa.window, 0);
         start_t = start_b & ~(unsigned)(kBlockN - 1);
         chunk = (int)(((nkeys - start_t + kBlockN - 1) / kBlockN + (unsigned)S - 1) / (unsigned)S) * kBlockN;
     }
@@ -397,7 +352,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(Qg + (size_t)bh * Nq * D, (unsigned)((size_t)Nq * D * 2));
     if constexpr (kPacked) {
         const unsigned grp = (unsigned)Nq / (unsigned)ca.Nq1;
-        pv.rq = packed_rsrc(Qg, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, ka.q_st, ka.q_sh, D, 2u, pv.qend);
+        pv.rq = packed_rsrc(Qg, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, pa.q_st, pa.q_sh, D, 2u, pv.qend);
     }
     // K/V descriptors end at this split's last key: rows beyond it read 0 and are masked below
     // element offset -> address: the fp8 instantiations get byte pointers in Kg / Vg
@@ -422,7 +377,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         const unsigned pc = min(q_row, last), hd = pc / n_q;
         rag_row1 = pc - hd * n_q;
         rag_io = q_row < live ? hd * (unsigned)ca.Nq1 + rag_row1 : (unsigned)Nq;
-        if constexpr (kPacked) pv.qoff = q_row < live ? (rag_row1 * (unsigned)ka.q_st + hd * (unsigned)ka.q_sh) * 2u : pv.qend;
+        if constexpr (kPacked) pv.qoff = q_row < live ? (rag_row1 * (unsigned)pa.q_st + hd * (unsigned)pa.q_sh) * 2u : pv.qend;
     }
     const unsigned io_row = kRagged ? rag_io : q_row;
 
@@ -449,7 +404,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     if constexpr (kWindow) {
         if constexpr (kRagged) row_end = (int)nkeys - (int)n_q + 1 + (int)rag_row1;
         else row_end = (int)nkeys - ca.Nq1 + 1 + (int)(q_row % (unsigned)ca.Nq1);
-        lo_hi = (unsigned)max((int)nkeys - wa.window, 0);
+        lo_hi = (unsigned)max((int)nkeys - pa.window, 0);
     }
 
     // kCache: a scale of 0 must not turn a masked -inf into 0 * -inf.  Redundant behind host_scale_log2e() (fa_dispatch.hpp), which
@@ -458,8 +413,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     [[maybe_unused]] float k_scale = 1.0f, v_scale = 1.0f;
     if constexpr (kFp8) {
         const unsigned hkv = bh % (unsigned)ca.Hkv;
-        if (fa8.k_scale) k_scale = fa8.k_scale[hkv];
-        if (fa8.v_scale) v_scale = fa8.v_scale[hkv];
+        if (pa.k_scale) k_scale = pa.k_scale[hkv];
+        if (pa.v_scale) v_scale = pa.v_scale[hkv];
     }
     const float c = kFp8 ? fmaxf(fabsf(scale_log2e * k_scale), 1.17549435e-38f)
                          : kCache ? fmaxf(fabsf(scale_log2e), 1.17549435e-38f) : fabsf(scale_log2e);
@@ -469,9 +424,9 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
     // the tile loop than the windowed one: c itself is then dead after this point
     [[maybe_unused]] float cs = c, cap_k1 = 0.0f, cap_n2 = 0.0f;
     if constexpr (kLogits) {
-        cs = to_sgpr(la.cap2 > 0.0f ? 1.0f : c);
-        cap_k1 = to_sgpr(c * la.cap_rk);
-        cap_n2 = to_sgpr(-2.0f * la.cap2);
+        cs = to_sgpr(pa.cap2 > 0.0f ? 1.0f : c);
+        cap_k1 = to_sgpr(c * pa.cap_rk);
+        cap_n2 = to_sgpr(-2.0f * pa.cap2);
     }
     u32x4 qf[G::kKSteps];
 #pragma unroll
@@ -617,12 +572,12 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                 s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
             }
         if constexpr (kLogits) {
-            if (la.cap2 > 0.0f) {   // wave-uniform; before the masks, so a masked key stays at -inf
+            if (pa.cap2 > 0.0f) {   // wave-uniform; before the masks, so a masked key stays at -inf
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        s[kb][i] = __builtin_fmaf(cap_n2, __builtin_amdgcn_rcpf(1.0f + fast_exp2(s[kb][i] * cap_k1)), la.cap2);
+                        s[kb][i] = __builtin_fmaf(cap_n2, __builtin_amdgcn_rcpf(1.0f + fast_exp2(s[kb][i] * cap_k1)), pa.cap2);
             }
         }
         if constexpr (kWindow) {
@@ -638,13 +593,13 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
                     asm volatile("" : "+v"(t), "+v"(re));
                     const unsigned ri = (unsigned)(re - base - 1);   // < n_q for every lane
                     const bool lv = qb * (unsigned)kRows + (t >> 6) * 32u + (t & 31u) < live;
-                    const u32x2 w = buf_load8(make_rsrc(ta.tree_mask + pv.s, n_q * 8u), lv ? ri * 8u : n_q * 8u);
+                    const u32x2 w = buf_load8(make_rsrc(pa.tree_mask + pv.s, n_q * 8u), lv ? ri * 8u : n_q * 8u);
                     unsigned long long m = ((unsigned long long)w[1] << 32) | w[0];
                     m = lv ? ((m & (~0ull >> (64u - n_q))) | (1ull << ri)) : ((2ull << ri) - 1ull);
                     // The tile's 64 keys as one word per lane, bit o for key kv0 + o, made in place in the two registers of m so that the
                     // block needs little more than the windowed one's (the d = 64 kernels have no register to spare).  The row's lower
                     // limit first, the only other per-lane value
-                    const unsigned lo = (unsigned)max(base + (int)__builtin_popcountll(m) - wa.window, 0);
+                    const unsigned lo = (unsigned)max(base + (int)__builtin_popcountll(m) - pa.window, 0);
                     // ... the step's tokens the row sees, all keys below base, none from key1 on: d, and with it every shift and
                     // constant here, is wave-uniform (key1 > kv0: the tile exists)
                     const int d = (int)kv0 - base;
@@ -667,7 +622,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
             } else
             // keys outside [lo, hi) -> -inf: hi is `lim` above, lo the row's lower limit; one unsigned compare per score
             if (kv0 + kBlockN > lim_lo || kv0 < lo_hi) {
-                const unsigned lo = (unsigned)max(row_end - wa.window, 0);
+                const unsigned lo = (unsigned)max(row_end - pa.window, 0);
                 const unsigned hi = ca.causal ? min((unsigned)max(row_end, 0), key1) : key1;
                 const unsigned seen = hi > lo ? hi - lo : 0u;   // a split that ends below lo: nothing
 #pragma unroll
@@ -792,14 +747,14 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         // kLogits: the sink joins here, once per row; rows past Nq read the sink of the head's last row and store nothing
         [[maybe_unused]] float w_keys = 1.0f;
         if constexpr (kLogits) {
-            if (la.sinks) {
+            if (pa.sinks) {
                 // the two divisors go through an empty asm so that these divisions share nothing with `bh % ca.Hkv` and `q_row %
                 // ca.Nq1` of the prologue: shared, two reciprocals stay in VGPRs across the tile loop, which the d = 64 kernels
                 // spill (profiles/kvcache_logits.txt); recomputed here they cost a few instructions once per workgroup
                 unsigned nq1 = (unsigned)ca.Nq1, nhkv = (unsigned)ca.Hkv;
                 asm volatile("" : "+s"(nq1), "+s"(nhkv));
                 const unsigned hq = (bh % nhkv) * ((unsigned)Nq / nq1) + min(o_row, (unsigned)Nq - 1u) / nq1;
-                w_keys = sink_join(la.sinks[hq] * kLog2e, m_ref, l);
+                w_keys = sink_join(pa.sinks[hq] * kLog2e, m_ref, l);
             }
         }
         float inv = (kCache && l == 0.0f) ? 0.0f : 1.0f / l;   // a row without a key: O = 0
@@ -808,7 +763,7 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if constexpr (kPacked) {
             // lse is [Hkv*G, total_q]: the live rows alone store, each to its own token's entry
             if (ca.lse && h == 0 && pv.live)
-                ca.lse[((size_t)(bh % (unsigned)ca.Hkv) * ((unsigned)Nq / (unsigned)ca.Nq1) + pv.hd) * (size_t)ka.total_q + (size_t)pv.s + pv.i] =
+                ca.lse[((size_t)(bh % (unsigned)ca.Hkv) * ((unsigned)Nq / (unsigned)ca.Nq1) + pv.hd) * (size_t)pa.total_q + (size_t)pv.s + pv.i] =
                     l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2;
         } else if constexpr (kCache) {
             if (ca.lse && h == 0)   // m_ref is in log2 units; rows past Nq fall outside the descriptor
@@ -822,8 +777,8 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
         if constexpr (kPacked) {
             const unsigned grp = (unsigned)Nq / (unsigned)ca.Nq1;
             unsigned oend;
-            pv.ro = packed_rsrc(Og, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, ka.o_st, ka.o_sh, D, es, oend);
-            pv.ooff = pv.live ? (pv.i * (unsigned)ka.o_st + pv.hd * (unsigned)ka.o_sh) * es : oend;
+            pv.ro = packed_rsrc(Og, pv.s, n_q, (bh % (unsigned)ca.Hkv) * grp, grp, pa.o_st, pa.o_sh, D, es, oend);
+            pv.ooff = pv.live ? (pv.i * (unsigned)pa.o_st + pv.hd * (unsigned)pa.o_sh) * es : oend;
         }
 #pragma unroll
         for (int db = 0; db < G::kDBlocks; ++db)
@@ -849,19 +804,13 @@ void fa_fwd_split_kernel(const uint16_t* __restrict__ Qg, const uint16_t* __rest
 // of one lane walking them (a serial walk costs ~0.25 us per partial: 64 us at S = 128).
 // kCache: a partial with m = -inf is neutral (weight 0, not 2^(-inf + inf)), a row of neutral partials gives O = 0, and the
 // trailing float* argument (may be nullptr) receives ln(sum of exponentials) = (M + log2 L) ln 2.
-// SinkLse in the place of the float*: the row's head has an attention sink, which joins (M, L) here, once per row.
+// Four structs can take the float*'s place (the kernel reads the one it got through pack_of(), and its lse pointer through lse_of()).
+// SinkLse: the row's head has an attention sink, which joins (M, L) here, once per row.
 struct SinkLse {
     float* lse;           // as the float* of the kCache instantiations
     const float* sinks;   // [Hkv * G] on the device, not null
     int Hkv, Nq1;         // K/V heads per batch entry and rows per query head: row `row` of K/V head bh belongs to query head
 };                        // (bh % Hkv) * (Nq / Nq1) + row / Nq1
-__device__ __forceinline__ float* lse_part() { return nullptr; }
-__device__ __forceinline__ float* lse_part(float* p) { return p; }
-__device__ __forceinline__ float* lse_part(const SinkLse& s) { return s.lse; }
-struct NoSink {};
-__device__ __forceinline__ NoSink sink_part() { return {}; }
-__device__ __forceinline__ NoSink sink_part(float*) { return {}; }
-__device__ __forceinline__ const SinkLse& sink_part(const SinkLse& s) { return s; }
 // RaggedLse in the place of the float*: the merge behind the RaggedArgs partial kernels.  Output row `row` (padded) of K/V head bh is
 // row i = row % Nq1 of its query head; with n_b = min(max(seqlens_q[bh / Hkv], 0), Nq1) it is dead for i >= n_b -- the wave writes
 // zeros and -inf and reads no partial -- and else its partials are workspace row (row / Nq1) * n_b + i.  Sinks (may be null here)
@@ -872,13 +821,6 @@ struct RaggedLse {
     const int* seqlens_q;     // [B] on the device, not null
     int Hkv, Nq1;
 };
-__device__ __forceinline__ float* lse_part(const RaggedLse& s) { return s.lse; }
-__device__ __forceinline__ NoSink sink_part(const RaggedLse&) { return {}; }
-struct NoRaggedLse {};
-__device__ __forceinline__ NoRaggedLse ragged_lse_part() { return {}; }
-__device__ __forceinline__ NoRaggedLse ragged_lse_part(float*) { return {}; }
-__device__ __forceinline__ NoRaggedLse ragged_lse_part(const SinkLse&) { return {}; }
-__device__ __forceinline__ const RaggedLse& ragged_lse_part(const RaggedLse& s) { return s; }
 // PackedLse in the place of the float*: the merge behind the PackedArgs partial kernels.  The grid is RaggedLse's, one wave per padded
 // row; row i = row % Nq1 of head hd = row / Nq1 is live for i < n_b (packed_rows), reads workspace row hd * n_b + i and joins the
 // sink as under RaggedLse; it stores O to token s_b + i of query head hkv*G + hd through the strides and lse into [Hkv*G, total_q].
@@ -890,35 +832,29 @@ struct PackedLse {
     int Hkv, Nq1, total_q;
     long long o_st, o_sh;     // elements
 };
-__device__ __forceinline__ float* lse_part(const PackedLse& s) { return s.lse; }
-__device__ __forceinline__ NoSink sink_part(const PackedLse&) { return {}; }
-__device__ __forceinline__ NoRaggedLse ragged_lse_part(const PackedLse&) { return {}; }
 // RoutedLse: PackedLse behind the RoutedArgs partial kernels -- the row count is routed_rows', so the waves of a sequence with more
 // than Nq1 rows return without writing, as those of an idle slot do.
 struct RoutedLse : PackedLse {};
-struct NoPackedLse {};
-__device__ __forceinline__ NoPackedLse packed_lse_part() { return {}; }
-__device__ __forceinline__ NoPackedLse packed_lse_part(float*) { return {}; }
-__device__ __forceinline__ NoPackedLse packed_lse_part(const SinkLse&) { return {}; }
-__device__ __forceinline__ NoPackedLse packed_lse_part(const RaggedLse&) { return {}; }
-__device__ __forceinline__ const PackedLse& packed_lse_part(const PackedLse& s) { return s; }
-// a live row's token and query head, and the first element of its O row
+// the lse pointer of whatever came in the float*'s place (the plain instantiations: none)
+__device__ __forceinline__ float* lse_of() { return nullptr; }
+__device__ __forceinline__ float* lse_of(float* p) { return p; }
+template <typename L> __device__ __forceinline__ float* lse_of(const L& s) { return s.lse; }
+// a live row's token and query head, and the first element of its O row (the overload for the other Lse types is never run: it
+// stands in the dead arm of a ?: on a constant)
 struct PackedRow { size_t tok, hq; };
-__device__ __forceinline__ size_t packed_elem(const NoPackedLse&, const NoPackedLse&) { return 0; }
+template <typename L> __device__ __forceinline__ size_t packed_elem(const L&, const NoPack&) { return 0; }
 __device__ __forceinline__ size_t packed_elem(const PackedLse& s, const PackedRow& r) { return r.tok * (size_t)s.o_st + r.hq * (size_t)s.o_sh; }
 template <typename T, bool kOutF32, bool kCache = false, typename... Lse>
 __global__ __launch_bounds__(64)
 void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og, int BH, int Nq, int D, int S, Lse... lse_arg)
 {
     static_assert(sizeof...(Lse) == (kCache ? 1 : 0), "the KV-cache instantiations take the lse pointer, the plain ones nothing");
-    [[maybe_unused]] float* const lse = lse_part(lse_arg...);
+    [[maybe_unused]] float* const lse = lse_of(lse_arg...);
+    [[maybe_unused]] const auto la = pack_of(lse_arg...);   // the Lse value; a type's fields are read under its flag only
     constexpr bool kSink = (std::is_same_v<Lse, SinkLse> || ...);
-    [[maybe_unused]] const auto sk = sink_part(lse_arg...);
     constexpr bool kRaggedM = (std::is_same_v<Lse, RaggedLse> || ...);
-    [[maybe_unused]] const auto rg = ragged_lse_part(lse_arg...);
     constexpr bool kRoutedM = (std::is_same_v<Lse, RoutedLse> || ...);
     constexpr bool kPackedM = (std::is_same_v<Lse, PackedLse> || ...) || kRoutedM;
-    [[maybe_unused]] const auto pg = packed_lse_part(lse_arg...);
     const int cols4 = D / 4;             // 16 or 32
     const int nsl = 64 / cols4;          // 4 or 2 slices of the split axis
     const unsigned lane = threadIdx.x;
@@ -929,7 +865,7 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     const size_t stride_s = (size_t)Nq * (D + 2);
     int ws_row = row;                    // the row's partials in the workspace
     if constexpr (kRaggedM) {
-        const int n_q = min(max(rg.seqlens_q[bh / rg.Hkv], 0), rg.Nq1), hd = row / rg.Nq1, i = row - hd * rg.Nq1;
+        const int n_q = min(max(la.seqlens_q[bh / la.Hkv], 0), la.Nq1), hd = row / la.Nq1, i = row - hd * la.Nq1;
         if (i >= n_q) {   // wave-uniform: a dead row
             if (sl != 0) return;
             if (lse && lane == 0) lse[rowi] = -INFINITY;
@@ -947,17 +883,17 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
         ws_row = hd * n_q + i;
     }
     // kPackedM: the row's token and query head, where O and lse go
-    [[maybe_unused]] std::conditional_t<kPackedM, PackedRow, NoPackedLse> pm;
+    [[maybe_unused]] std::conditional_t<kPackedM, PackedRow, NoPack> pm;
     if constexpr (kPackedM) {
         int s;
         unsigned n_q;
-        if constexpr (kRoutedM) routed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
-        else packed_rows(pg.cu_q, (unsigned)(bh / pg.Hkv), pg.total_q, pg.Nq1, s, n_q);
-        const int hd = row / pg.Nq1, i = row - hd * pg.Nq1;
+        if constexpr (kRoutedM) routed_rows(la.cu_q, (unsigned)(bh / la.Hkv), la.total_q, la.Nq1, s, n_q);
+        else packed_rows(la.cu_q, (unsigned)(bh / la.Hkv), la.total_q, la.Nq1, s, n_q);
+        const int hd = row / la.Nq1, i = row - hd * la.Nq1;
         if (i >= (int)n_q) return;   // wave-uniform: no live row, nothing is written
         ws_row = hd * (int)n_q + i;
         pm.tok = (size_t)s + (size_t)i;
-        pm.hq = (size_t)(bh % pg.Hkv) * (size_t)(Nq / pg.Nq1) + (size_t)hd;
+        pm.hq = (size_t)(bh % la.Hkv) * (size_t)(Nq / la.Nq1) + (size_t)hd;
     }
     const float* base = ws + (size_t)bh * S * stride_s + (size_t)ws_row * (D + 2);
     // global reference max: every lane takes splits lane, lane+64, ...
@@ -968,15 +904,15 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     // kSink: the sink takes part in the reference maximum (a sink far above the keys' logits must not overflow the sum)
     [[maybe_unused]] float a2 = -INFINITY;
     if constexpr (kSink) {
-        a2 = sk.sinks[(bh % sk.Hkv) * (Nq / sk.Nq1) + row / sk.Nq1] * kLog2e;
+        a2 = la.sinks[(bh % la.Hkv) * (Nq / la.Nq1) + row / la.Nq1] * kLog2e;
         M = fmaxf(M, a2);
     }
     if constexpr (kRaggedM) {
-        if (rg.sinks) a2 = rg.sinks[(bh % rg.Hkv) * (Nq / rg.Nq1) + row / rg.Nq1] * kLog2e;
+        if (la.sinks) a2 = la.sinks[(bh % la.Hkv) * (Nq / la.Nq1) + row / la.Nq1] * kLog2e;
         M = fmaxf(M, a2);
     }
     if constexpr (kPackedM) {
-        if (pg.sinks) a2 = pg.sinks[pm.hq] * kLog2e;
+        if (la.sinks) a2 = la.sinks[pm.hq] * kLog2e;
         M = fmaxf(M, a2);
     }
     float L = 0.0f, acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1002,11 +938,11 @@ void fa_split_combine_kernel(const float* __restrict__ ws, void* __restrict__ Og
     if constexpr (kSink || kRaggedM || kPackedM) L += a2 == -INFINITY ? 0.0f : fast_exp2(a2 - M);   // after the slices are summed: once per row
     const float inv = (kCache && L == 0.0f) ? 0.0f : 1.0f / L;
     if constexpr (kPackedM) {
-        if (lse && lane == 0) lse[pm.hq * (size_t)pg.total_q + pm.tok] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
+        if (lse && lane == 0) lse[pm.hq * (size_t)la.total_q + pm.tok] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
     } else if constexpr (kCache) {
         if (lse && lane == 0) lse[rowi] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
     }
-    const size_t off = kPackedM ? packed_elem(pg, pm) + 4 * c4 : ((size_t)bh * Nq + row) * D + 4 * c4;
+    const size_t off = kPackedM ? packed_elem(la, pm) + 4 * c4 : ((size_t)bh * Nq + row) * D + 4 * c4;
     if constexpr (kOutF32) {
         float* o = static_cast<float*>(Og) + off;
 #pragma unroll
