@@ -17,6 +17,7 @@ ALGO_RP16_DMA = 25
 ALGO_RP16_FOLD_HALF, ALGO_RP16_FOLD_QUARTER, ALGO_RP16_FOLD_1W, ALGO_RP16_FOLD_KS2 = 26, 27, 28, 29
 
 KV_16BIT, KV_FP8_E4M3 = 0, 1
+MLA_DC, MLA_DR, MLA_DQK = 512, 64, 576   # FA_MLA_*: a latent row's compressed and rotary parts, and its width
 ATTEND_SHORT, ATTEND_LONG = 1, 2   # the parts of fa_kvcache_attend_varlen_part
 
 
@@ -198,6 +199,34 @@ class KvCommitDesc(C.Structure):
             self.size = C.sizeof(KvCommitDesc)
 
 
+class MlaDecodeDesc(C.Structure):
+    """fa_mla_decode_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Q", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p), ("C", C.c_void_p),
+                ("cu_seqlens_q", C.c_void_p), ("seqlens_k", C.c_void_p), ("block_table", C.c_void_p), ("B", C.c_int), ("Hq", C.c_int),
+                ("total_q", C.c_int), ("max_q", C.c_int), ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int),
+                ("max_pages", C.c_int), ("q_stride_t", C.c_longlong), ("q_stride_h", C.c_longlong), ("o_stride_t", C.c_longlong),
+                ("o_stride_h", C.c_longlong), ("scale", C.c_float), ("causal", C.c_int), ("num_splits", C.c_int), ("in_dtype", C.c_int),
+                ("out_dtype", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(MlaDecodeDesc)
+
+
+class MlaAppendDesc(C.Structure):
+    """fa_mla_append_desc of include/fa_mi355.h, field for field; `size` is filled in."""
+    _fields_ = [("size", C.c_size_t), ("Cnew", C.c_void_p), ("C", C.c_void_p), ("cu_seqlens_new", C.c_void_p), ("seqlens_k", C.c_void_p),
+                ("seqlens_out", C.c_void_p), ("block_table", C.c_void_p), ("B", C.c_int), ("total_new", C.c_int),
+                ("new_stride_t", C.c_longlong), ("Ncap", C.c_int), ("num_pages", C.c_int), ("page_size", C.c_int), ("max_pages", C.c_int),
+                ("dtype", C.c_int), ("stream", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        if "size" not in fields:
+            self.size = C.sizeof(MlaAppendDesc)
+
+
 def _signatures() -> dict:
     """{symbol: (restype, argtypes)} of every function include/fa_mi355.h declares."""
     vp, i, f, sz, s = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
@@ -247,6 +276,10 @@ def _signatures() -> dict:
         "fa_kvcache_append_varlen_ex": (i, [C.POINTER(KvAppendVarlenDesc), C.POINTER(KvAppendVarlenOpts)]),
         # the commit of a tree step: the accepted path's K/V rows to consecutive slots, one 64-bit word per sequence
         "fa_kvcache_commit": (i, [C.POINTER(KvCommitDesc)]),
+        # MLA: absorbed-query decode over a latent cache [.., 576] (O from its first 512 elements) and the copy that fills the cache
+        "fa_mla_decode_workspace_bytes": (sz, [C.POINTER(MlaDecodeDesc)]),
+        "fa_mla_decode": (i, [C.POINTER(MlaDecodeDesc)]),
+        "fa_mla_append": (i, [C.POINTER(MlaAppendDesc)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

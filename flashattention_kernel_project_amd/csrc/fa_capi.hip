@@ -315,6 +315,10 @@ FA_EXPORT int fa_kvcache_append_varlen_ex(const fa_kvappend_varlen_desc* desc, c
 
 FA_EXPORT int fa_kvcache_commit(const fa_kvcommit_desc* desc) { return (int)fa::kvcache_commit(desc); }
 
+FA_EXPORT size_t fa_mla_decode_workspace_bytes(const fa_mla_decode_desc* desc) { return fa::mla_decode_workspace_bytes(desc); }
+FA_EXPORT int fa_mla_decode(const fa_mla_decode_desc* desc) { return (int)fa::mla_decode_dispatch(desc); }
+FA_EXPORT int fa_mla_append(const fa_mla_append_desc* desc) { return (int)fa::mla_append_dispatch(desc); }
+
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 
 FA_EXPORT int fa_forward_varlen(const fa_varlen_desc* desc) { return (int)fa::varlen_dispatch(desc); }

@@ -17,6 +17,8 @@ struct fa_kvdecode_varlen_desc;
 struct fa_kvdecode_tree_opts;
 struct fa_kvappend_varlen_opts;
 struct fa_kvcommit_desc;
+struct fa_mla_decode_desc;
+struct fa_mla_append_desc;
 
 namespace fa {
 
@@ -220,6 +222,12 @@ hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
 hipError_t kvcache_append_varlen_ex(const ::fa_kvappend_varlen_desc* desc, const ::fa_kvappend_varlen_opts* opts);
 // fa_kvcache_commit (fa_kvcache_commit.hip): the checks and the one or two launches; the descriptor is the public one, as it is
 hipError_t kvcache_commit(const ::fa_kvcommit_desc* desc);
+// fa_mla_decode (fa_mla_decode.hip) and fa_mla_append (fa_mla_append.hip): the checks and the launches on the public descriptors;
+// mla_geometry is the capacity and page check the two share (cap: Ncap or max_pages * page_size; lg_page: 0 when contiguous)
+hipError_t mla_decode_dispatch(const ::fa_mla_decode_desc* desc);
+size_t mla_decode_workspace_bytes(const ::fa_mla_decode_desc* desc);
+hipError_t mla_append_dispatch(const ::fa_mla_append_desc* desc);
+bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

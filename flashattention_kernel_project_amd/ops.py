@@ -1401,6 +1401,172 @@ def fa_kvcache_commit(k_cache, v_cache, accept_mask, cache_seqlens=None, seqlens
     capi.check("fa_kvcache_commit", code)
 
 
+def _mla_cache(c_cache, block_table, B, dtype, name="c_cache"):
+    """(Ncap, num_pages, page_size, max_pages, table pointer) of a latent cache [B,Ncap,576] or, with block_table, a pool
+    [num_pages,page_size,576]; shapes and dtypes are judged before anything needs a device"""
+    import torch
+    if not isinstance(c_cache, torch.Tensor) or c_cache.dim() != 3 or c_cache.shape[2] != capi.MLA_DQK or c_cache.numel() == 0:
+        raise ValueError(f"{name} must be a latent cache [B,Ncap,{capi.MLA_DQK}] or, with block_table, a pool [num_pages,page_size,{capi.MLA_DQK}]")
+    if c_cache.dtype != dtype:
+        raise ValueError(f"{name} has dtype {c_cache.dtype}, expected {dtype} (an fp8 latent cache is not part of the MLA entries)")
+    if block_table is None:
+        if c_cache.shape[0] != B:
+            raise ValueError(f"{name} holds {c_cache.shape[0]} sequences, the cu_seqlens vector {B}")
+        return c_cache.shape[1], 0, 0, 0, None
+    page_size = c_cache.shape[1]
+    if page_size < 16 or page_size & (page_size - 1):
+        raise ValueError("page_size must be a power of two >= 16")
+    table_ptr = _table_ptr(block_table, B)
+    if block_table.shape[1] <= 0:
+        raise ValueError("block_table must have at least one column")
+    return 0, c_cache.shape[0], page_size, block_table.shape[1], table_ptr
+
+
+def _cu_vector(cu, name: str) -> int:
+    """B of a checked cu_seqlens vector"""
+    import torch
+    if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32:
+        raise ValueError(f"{name} must be an int32 tensor (the kernel reads 32-bit entries)")
+    if cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 1-d tensor of B+1 entries")
+    return cu.numel() - 1
+
+
+def mla_decode_workspace_bytes(B: int, Hq: int, max_seqlen_q: int, Ncap: int = 0, max_pages: int = 0, page_size: int = 0,
+                               num_splits: int = 0) -> int:
+    """Workspace of fa_mla_decode (fa_mla_decode_workspace_bytes): a contiguous cache gives Ncap, a paged one max_pages and page_size;
+    num_splits as in the call (0: the library's choice).  From host integers alone; 0 when one split is chosen, and 0 for a shape
+    the call refuses."""
+    desc = capi.new_desc(capi.MlaDecodeDesc)
+    paged = bool(max_pages or page_size)
+    # the pointers and strides are stand-ins that pass the checks: the size reads none of them
+    capi.fill(desc, Q=16, O=16, C=16, cu_seqlens_q=16, block_table=16 if paged else None, B=B, Hq=Hq, total_q=max(B, 1) * max(max_seqlen_q, 1),
+              max_q=max_seqlen_q, Ncap=0 if paged else Ncap, num_pages=1 if paged else 0, page_size=page_size, max_pages=max_pages,
+              q_stride_t=capi.MLA_DQK, q_stride_h=0, o_stride_t=capi.MLA_DC, o_stride_h=0, causal=1, num_splits=num_splits,
+              in_dtype=capi.F16, out_dtype=capi.OUT_F32)
+    return int(capi.lib().fa_mla_decode_workspace_bytes(desc))
+
+
+def fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, scale: float | None = None,
+                  causal: bool = True, num_splits: int = 0, return_lse: bool = False, out=None, workspace=None, out_dtype=None,
+                  stream=None, lse=None):
+    """Multi-head latent attention decode (fa_mla_decode): absorbed queries against a latent KV cache that holds ONE row of 576
+    elements per token for all heads -- 512 compressed-KV elements, then 64 rotary ones.  The logits run over all 576 elements, the
+    output is the softmax-weighted sum of the rows' first 512: o (total_q, Hq, 512).
+    q: (total_q, Hq, 576) fp16/bf16 device tensor, the absorbed queries [q_nope . W_UK | q_rope], taken as it lies: any token and head
+    strides with a contiguous last dimension (multiples of 8 elements, 16-byte aligned storage), so a slice of a fused projection
+    buffer goes in without a copy.  1 <= Hq <= 128.  The absorption and the up-projection of o by W_UV stay the caller's GEMMs.
+    c_cache: [B, Ncap, 576] of q's dtype, contiguous, or with block_table (int32 [B, max_pages]) a pool [num_pages, page_size, 576],
+    page_size a power of two >= 16; key j of sequence b is then row j % page_size of page block_table[b, j // page_size].
+    cu_seqlens_q: int32 [B+1] on the device; sequence b owns the tokens [cu[b], cu[b+1]), clamped into the tensor, and has
+    n_b = min(cu[b+1] - cu[b], max_seqlen_q) rows, its first n_b tokens.  max_seqlen_q: a host int >= 1; grid, split count and workspace
+    follow it, not the vector.
+    cache_seqlens: int32 [B], the keys of sequence b, its new tokens INCLUDED (the lengths after fa_mla_append), or None (the capacity).
+    With L_b and n_b, row i sees the keys [0, c_i): c_i = max(0, L_b - n_b + 1 + i) with causal (the default), else L_b.  A row
+    without a key is O = 0, lse = -inf.  Rows at or past L_b are never used and may hold anything; table entries past the last live
+    page are not read, a live entry outside the pool reads as a page of zeros.
+    scale: None is 576 ** -0.5; MODELS PASS THEIR OWN -- DeepSeek's softmax scale is that of the un-absorbed head dimension
+    (128 + 64) ** -0.5, times the rope-scaling factor where one applies.
+    num_splits: 0 (the library chooses from the shape), or the number of key splits, 1 .. ceil(capacity / 64); 1 needs no workspace.
+    -> o (total_q, Hq, 512) of out_dtype (torch.float32, the default, or q's dtype), or (o, lse) with return_lse, lse (Hq, total_q)
+    float32 in natural-log units.  Tokens that are no live row of any sequence are NOT written: a fresh result holds O = 0 and
+    lse = -inf there; with `out` (any token and head strides) and `lse` (contiguous; implies return_lse) they keep what they held.
+    workspace: optional uint8 device tensor of at least mla_decode_workspace_bytes(...).
+    Nothing is read on the host: fa_mla_append(seqlens_out=lens) then this call, captured once, serves every step of the same total_q.
+    Not here: an fp8 latent cache, window, soft-cap, sinks, a tree mask, other latent widths."""
+    import torch
+    if not isinstance(q, torch.Tensor) or q.dim() != 3 or q.shape[2] != capi.MLA_DQK:
+        raise ValueError(f"q must be a packed tensor (total_q, Hq, {capi.MLA_DQK}): the absorbed queries")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("q must be fp16 or bf16")
+    total_q, Hq = q.shape[0], q.shape[1]
+    if total_q <= 0 or not 1 <= Hq <= 128:
+        raise ValueError("q must hold at least one token and 1 .. 128 heads")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1:
+        raise ValueError("max_seqlen_q must be an int >= 1: the most rows a sequence may have")
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+        raise ValueError("num_splits must be an int >= 0 (0: chosen by the library)")
+    B = _cu_vector(cu_seqlens_q, "cu_seqlens_q")
+    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, q.dtype)
+    if cache_seqlens is not None and (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32
+                                      or cache_seqlens.shape != (B,)):
+        raise ValueError("cache_seqlens must be an int32 device tensor of B entries")
+    qt, qh = _packed_strides(q, "q")
+    for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    c_ptr = _dev_ptr(c_cache, "c_cache", (q.dtype,))
+    lens_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    out_dt = _out_dt(out_dtype, q.dtype)
+    o_shape = (total_q, Hq, capi.MLA_DC)
+    if out is None:   # tokens of no sequence then read as "no key"
+        out = torch.zeros(o_shape, dtype=out_dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or tuple(out.shape) != o_shape or out.dtype != out_dtype:
+        raise ValueError(f"out must be a device tensor (total_q, Hq, {capi.MLA_DC}) of out_dtype")
+    if lse is not None:
+        if not isinstance(lse, torch.Tensor) or lse.shape != (Hq, total_q):
+            raise ValueError("lse must be a float32 tensor (Hq, total_q)")
+        _dev_ptr(lse, "lse", (torch.float32,))
+        return_lse = True
+    elif return_lse:
+        lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
+    ot, oh = _packed_strides(out, "out")
+    if workspace is None:
+        need = mla_decode_workspace_bytes(B, Hq, max_seqlen_q, Ncap, max_pages, page_size, num_splits)
+        if need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    desc = capi.new_desc(capi.MlaDecodeDesc)
+    capi.fill(desc, Q=q.data_ptr(), O=out.data_ptr(), lse=None if lse is None else lse.data_ptr(), C=c_ptr,
+              cu_seqlens_q=cu_seqlens_q.data_ptr(), seqlens_k=lens_ptr, block_table=table_ptr, B=B, Hq=Hq, total_q=total_q,
+              max_q=max_seqlen_q, Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, q_stride_t=qt, q_stride_h=qh,
+              o_stride_t=ot, o_stride_h=oh, scale=float(capi.MLA_DQK ** -0.5 if scale is None else scale), causal=int(bool(causal)),
+              num_splits=num_splits, in_dtype=_in_dt(q.dtype), out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len,
+              stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(q, c_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, workspace)):
+        code = capi.lib().fa_mla_decode(desc)
+    capi.check("fa_mla_decode", code)
+    return (out, lse) if return_lse else out
+
+
+def fa_mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None, stream=None) -> None:
+    """The write half of fa_mla_decode (fa_mla_append): c_new (total_new, 576) fp16/bf16, the step's latent rows [compressed KV |
+    rotated k_rope], taken as it lies (any token stride that is a multiple of 8 elements, contiguous rows), cut into sequences by
+    cu_seqlens_new (int32 [B+1], device, clamped into the tensor).  Token i of sequence b is copied bit for bit to slot L_b + i of
+    c_cache ([B,Ncap,576], or with block_table the pool [num_pages,page_size,576]), L_b = cache_seqlens[b] clamped to the capacity
+    (None: 0 for all).  A token at or past the capacity is dropped; a table entry outside the pool skips the write.  No rotary here.
+    seqlens_out: None, cache_seqlens itself, or a disjoint int32 [B] tensor: min(L_b + m_b, capacity), by a second kernel behind the
+    copy.  Nothing is read on the host."""
+    import torch
+    if not isinstance(c_new, torch.Tensor) or c_new.dim() != 2 or c_new.shape[1] != capi.MLA_DQK or c_new.shape[0] <= 0:
+        raise ValueError(f"c_new must be a packed tensor (total_new, {capi.MLA_DQK})")
+    if c_new.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("c_new must be fp16 or bf16")
+    if c_new.stride(1) != 1:
+        raise ValueError("c_new must be contiguous in its last dimension (any token stride is taken as it is)")
+    B = _cu_vector(cu_seqlens_new, "cu_seqlens_new")
+    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, c_new.dtype)
+    for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.shape != (B,)):
+            raise ValueError(f"{name} must be an int32 device tensor of shape [B] = [{B}]")
+    for name, t in (("c_new", c_new), ("cu_seqlens_new", cu_seqlens_new)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    c_ptr = _dev_ptr(c_cache, "c_cache", (c_new.dtype,))
+    len_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
+    out_ptr = None if seqlens_out is None else _dev_ptr(seqlens_out, "seqlens_out", (torch.int32,))
+    desc = capi.new_desc(capi.MlaAppendDesc)
+    capi.fill(desc, Cnew=c_new.data_ptr(), C=c_ptr, cu_seqlens_new=cu_seqlens_new.data_ptr(), seqlens_k=len_ptr, seqlens_out=out_ptr,
+              block_table=table_ptr, B=B, total_new=c_new.shape[0], new_stride_t=c_new.stride(0) if c_new.shape[0] > 1 else capi.MLA_DQK,
+              Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, dtype=_in_dt(c_new.dtype),
+              stream=_stream_ptr(stream))
+    with torch.cuda.device(_one_device(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table)):
+        code = capi.lib().fa_mla_append(desc)
+    capi.check("fa_mla_append", code)
+
+
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):
     import torch
     if Q.numel() != num_batches * 256 or K.numel() != num_batches * 16 * seq_len \

@@ -60,6 +60,11 @@ eager fallback.  Registered on first use:
     # ones on the tiled kernel, routed on the device; always causal; parts 3 = both halves; _fp8 takes k_scale, v_scale behind block_table
     o, lse = torch.ops.fa_mi355.attend_varlen(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, split_rows, scale, window,
                                               sinks, softcap, parts, out_f32)
+    # multi-head latent attention (ops.fa_mla_decode, ops.fa_mla_append): absorbed q (total_q,Hq,576) against a latent cache
+    # [B,Ncap,576] or, with a block table, a pool [num_pages,page_size,576]; o is (total_q,Hq,512); num_splits 0 = the library's choice
+    o, lse = torch.ops.fa_mi355.mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits,
+                                           out_f32)
+    torch.ops.fa_mi355.mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table)
 """
 from __future__ import annotations
 
@@ -73,7 +78,7 @@ def register() -> None:
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
-    .attend_varlen and .attend_varlen_fp8."""
+    .attend_varlen and .attend_varlen_fp8, and .mla_decode and .mla_append."""
     global _registered
     if _registered:
         return
@@ -327,6 +332,27 @@ def register() -> None:
            lambda k_cache, cache_seqlens, seqlens_out, block_table, max_new: dict(
                cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), max_new=max_new,
                stream=stream(k_cache)), lambda *args: None)
+
+    # MLA (ops.fa_mla_decode, ops.fa_mla_append): q (total_q,Hq,576) as it lies, the latent cache [B,Ncap,576] or with a block table
+    # the pool [num_pages,page_size,576]; o (total_q,Hq,512) and lse (Hq,total_q) come back as from decode_varlen
+    def mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, **kw):
+        return ops.fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=cache_seqlens, block_table=block_table, **kw)
+
+    define("mla_decode",
+           "(Tensor q, Tensor c_cache, Tensor cu_seqlens_q, int max_seqlen_q, Tensor? cache_seqlens, Tensor? block_table, float scale, "
+           "bool causal, int num_splits, bool out_f32) -> (Tensor, Tensor)", (), mla_decode, "-cc-oo",
+           lambda q, scale, causal, num_splits, out_f32: dict(scale=scale, causal=causal, num_splits=num_splits,
+                                                              out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q)),
+           lambda q, *args: (q.new_empty((q.shape[0], q.shape[1], 512), dtype=out_dtype(q, args[-1])),
+                             q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)))
+
+    # the cache goes in as it is and is written in place, like the other appends'
+    define("mla_append",
+           "(Tensor c_new, Tensor(a!) c_cache, Tensor cu_seqlens_new, Tensor? cache_seqlens, Tensor(b!)? seqlens_out, "
+           "Tensor? block_table) -> ()", ("c_cache", "seqlens_out"), ops.fa_mla_append, "--c",
+           lambda c_new, cache_seqlens, seqlens_out, block_table: dict(
+               cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), stream=stream(c_new)),
+           lambda *args: None)
 
     _registered = True
 

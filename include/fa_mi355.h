@@ -995,6 +995,102 @@ typedef struct fa_kvcommit_desc {
 } fa_kvcommit_desc;
 int fa_kvcache_commit(const fa_kvcommit_desc* desc);
 
+/* Multi-head latent attention (MLA) decode, as DeepSeek-V2/V3/R1 and Kimi K2 serve it: the cache holds ONE row per token, shared by
+ * all query heads -- FA_MLA_DC = 512 compressed-KV elements followed by FA_MLA_DR = 64 rotary elements (they arrive rotated) -- and a
+ * step attends with "absorbed" queries of width FA_MLA_DQK = 576 (q_nope . W_UK next to q_rope).  The logits run over all 576
+ * elements of a row, the output is the softmax-weighted sum of its FIRST 512: V is a prefix of K and is never stored or staged apart.
+ * A kernel of its own on the split-KV stream's plan (Hkv = 1, G = Hq): the Hq heads of a token are rows of one workgroup, so a latent
+ * row is read from memory once and written to LDS once for both products.  DESIGN.md 7.22, profiles/mla_decode.txt.
+ * Rows.     [s_b, e_b) are fa_forward_varlen's clamps of cu_seqlens_q: s_b = clamp(cu[b], 0, total_q), e_b = clamp(cu[b+1], s_b,
+ *           total_q).  n_b = min(e_b - s_b, max_q); row i < n_b of sequence b is token s_b + i; a sequence that owns more than max_q
+ *           tokens has its first max_q served.  L_b = clamp(seqlens_k[b], 0, capacity) (NULL: capacity), capacity = Ncap or, with
+ *           block_table, max_pages * page_size.
+ * Arithmetic, for every head h of token s_b + i, with C_b the latent rows of sequence b (row j of a paged sequence is row
+ *           j % page_size of page block_table[b, j / page_size]):
+ *             s_j = scale * sum_{e < 576} Q[s_b + i, h, e] * C_b[j, e]
+ *             the row sees the keys [0, c_i): c_i = max(0, L_b - n_b + 1 + i) with causal, else L_b
+ *             O[s_b + i, h, :] = sum_{j < c_i} softmax(s)_j * C_b[j, 0:512]        lse[h, s_b + i] = ln sum_{j < c_i} exp(s_j)
+ *           Elements 512..575 never reach O.  Products in the 16-bit type's matrix instructions with fp32 accumulation, softmax in
+ *           fp32, the weights rounded to the input type for the second product, as in every decode entry here.
+ * Edges.    A row without a key (c_i = 0) returns O = 0 and lse = -inf exactly.  n_b = 0 is an idle slot: nothing of the sequence is
+ *           read, its table row and cache rows included.  scale = 0 gives uniform weights and never NaN.
+ * Never read or written: tokens that are no live row of any sequence (their Q rows may hold NaN; their O rows and lse entries keep
+ *           what they held).  Cache rows at or past L_b are never used and may hold NaN bit patterns: they reach LDS as zeros, they
+ *           are not merely masked in the score.  Table entries past a sequence's last live page are not read.  A live table entry
+ *           outside [0, num_pages) reads as a page of zeros; no address is formed from it.
+ * Host.     Nothing on the host reads device data.  Grid, split count and workspace follow (B, Hq, max_q, capacity, num_splits)
+ *           only, so a captured call follows cu_seqlens_q, seqlens_k and the block table when they are rewritten in place.
+ * Splits.   num_splits = 1 is one kernel and needs no workspace.  With S > 1 the 64-key tiles of EACH sequence's L_b keys are dealt
+ *           to S partial workgroups, which write unnormalised fp32 (O, m, l) per (row, split) to the workspace, and a private merge
+ *           kernel finishes; it writes no token of no sequence.  num_splits = 0 lets the library choose from (B, Hq, max_q,
+ *           capacity) alone.  fa_mla_decode_workspace_bytes(desc) is the size the call needs (0 with one split, and 0 for a
+ *           descriptor the call would refuse); it reads the fields named above, B, Hq, max_q, the capacity fields and num_splits.
+ * Bits.     A paged and a contiguous cache holding the same keys return the same bits under the same num_splits, and a sequence's
+ *           rows have the same bits whatever the other sequences of the batch hold.
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor or a wrong `size`; a NULL Q, O, C or
+ * cu_seqlens_q; B, total_q or max_q <= 0; Hq outside [1, 128]; in_dtype outside FA_DTYPE_F16 / FA_DTYPE_BF16, out_dtype outside
+ * FA_OUT_F32 / FA_OUT_SAME; causal outside {0, 1}; contiguous: Ncap outside [1, 2^30]; paged: num_pages <= 0, max_pages <= 0, a
+ * page_size that is no power of two >= 16, max_pages * page_size > 2^30; num_splits outside [0, ceil(capacity / 64)]; Q, O or C not
+ * 16-byte aligned; a stride that is no multiple of 8 elements, a negative head stride, q_stride_t < 576 or o_stride_t < 512; a
+ * sequence's view of Q or O -- max_q tokens over the Hq heads -- beyond 2^32 - 1 bytes; with more than one split a NULL workspace or
+ * one below fa_mla_decode_workspace_bytes(desc).
+ * Not part of this entry: an fp8 latent cache; a sliding window, soft-cap, sinks or a tree mask; latent widths other than 512 + 64;
+ * the absorption and up-projection GEMMs (W_UK into q, W_UV out of O), which stay the caller's; a d = 512 form of
+ * fa_merge_states -- the entry merges its own splits.  NOT a reference entry point. */
+#define FA_MLA_DC  512   /* compressed-KV elements of a latent row: what O is made of */
+#define FA_MLA_DR  64    /* rotary elements behind them: in the logits only */
+#define FA_MLA_DQK 576   /* the width of a latent row and of an absorbed query */
+typedef struct fa_mla_decode_desc {
+    size_t size;                /* sizeof(fa_mla_decode_desc) */
+    const void* Q;              /* packed (total_q, Hq, 576), d contiguous, through q_stride_t / q_stride_h (elements) */
+    void* O;                    /* packed (total_q, Hq, 512) through o_stride_t / o_stride_h */
+    float* lse;                 /* [Hq, total_q] fp32 natural log, may be NULL */
+    const void* C;              /* latent cache [B, Ncap, 576] of in_dtype; with block_table a pool [num_pages, page_size, 576] */
+    const int* cu_seqlens_q;    /* device, B+1 */
+    const int* seqlens_k;       /* device, B; may be NULL (= capacity) */
+    const int* block_table;     /* device, [B, max_pages]; NULL: contiguous */
+    int B, Hq, total_q, max_q;
+    int Ncap;                               /* contiguous only */
+    int num_pages, page_size, max_pages;    /* paged only; page_size a power of two >= 16 */
+    long long q_stride_t, q_stride_h, o_stride_t, o_stride_h;
+    float scale;
+    int causal;
+    int num_splits;             /* 0: chosen by the library; else forced, 1 .. ceil(capacity/64) */
+    int in_dtype, out_dtype;    /* FA_DTYPE_*; FA_OUT_F32 | FA_OUT_SAME */
+    void* workspace; size_t workspace_bytes; void* stream;
+} fa_mla_decode_desc;
+size_t fa_mla_decode_workspace_bytes(const fa_mla_decode_desc* desc);
+int    fa_mla_decode(const fa_mla_decode_desc* desc);
+
+/* The write half of fa_mla_decode: a token-packed batch of latent rows goes into the latent cache.  Token i of sequence b -- row
+ * s_b + i of Cnew, 576 elements read through new_stride_t, [s_b, e_b) the clamps of cu_seqlens_new as above, m_b = e_b - s_b -- is
+ * copied bit for bit (NaN payloads included) to slot L_b + i, L_b = clamp(seqlens_k[b], 0, capacity) (NULL: 0 for all, a fresh
+ * cache).  No rotary here: the 64 rotary elements arrive rotated.  A token whose slot is at or past the capacity is dropped; paged, a
+ * table entry outside [0, num_pages) skips the write and no address is formed from it.  Rows of no sequence are not read.
+ * seqlens_out[b] = min(L_b + m_b, capacity), by a tiny second kernel behind the copy on the same stream: seqlens_out may be NULL,
+ * seqlens_k itself, or disjoint from it.  Nothing is read on the host; the grid follows total_new alone; a captured call follows
+ * cu_seqlens_new, seqlens_k and the table when they are rewritten in place.
+ * Rejected with hipErrorInvalidValue before the device is touched: a NULL descriptor or a wrong `size`; a NULL Cnew, C or
+ * cu_seqlens_new; B or total_new <= 0; total_new above 2^24; a dtype outside FA_DTYPE_F16 / FA_DTYPE_BF16 (the copy does not look at
+ * the elements, the field names the cache's type); the capacity and page geometry fa_mla_decode refuses; Cnew or C not 16-byte
+ * aligned; new_stride_t < 576 or no multiple of 8; a partial overlap of seqlens_out and seqlens_k; a cu_seqlens_new that overlaps
+ * seqlens_out.  NOT a reference entry point. */
+typedef struct fa_mla_append_desc {
+    size_t size;                /* sizeof(fa_mla_append_desc) */
+    const void* Cnew;           /* packed (total_new, 576) through new_stride_t (elements) */
+    void* C;                    /* the latent cache [B, Ncap, 576], or with block_table the pool [num_pages, page_size, 576] */
+    const int* cu_seqlens_new;  /* device, B+1 */
+    const int* seqlens_k;       /* device, B: the lengths BEFORE the append; NULL = 0 for all */
+    int* seqlens_out;           /* device, B; NULL, == seqlens_k, or disjoint from it */
+    const int* block_table;     /* device, [B, max_pages]; NULL: contiguous */
+    int B, total_new;
+    long long new_stride_t;
+    int Ncap, num_pages, page_size, max_pages;   /* as in fa_mla_decode_desc */
+    int dtype;                  /* FA_DTYPE_F16 or FA_DTYPE_BF16 */
+    void* stream;
+} fa_mla_append_desc;
+int fa_mla_append(const fa_mla_append_desc* desc);
+
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
  * the same LDS images, fragment loads and accumulator maps as the product kernels.  d in {64,128}.
