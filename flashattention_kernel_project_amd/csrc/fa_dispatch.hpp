@@ -194,7 +194,7 @@ struct KvAppendArgs {
     int num_pages, page_size, max_pages;
     bool paged, fp8;
     hipStream_t stream;
-    // the _rope entries (fa_kvcache_append_rope.hip), at the end so that the plain entries' initialisers leave them zero: K is rotated
+    // the _rope entries (fa_kvcache_append_padded.hip), at the end so that the plain entries' initialisers leave them zero: K is rotated
     // at its position on the way into the cache, and Q [B, Hkv*G, Nnew, D] of `dtype` into Qout (the same buffer, a disjoint one, or
     // both null: K only).  rope_cos, rope_sin: device fp32 [max_pos, rot_dim / 2].
     const void* Q;
@@ -202,19 +202,29 @@ struct KvAppendArgs {
     const float *rope_cos, *rope_sin;
     int G, rot_dim, max_pos, interleaved;
     bool rope;
-    // fa_kvcache_append_ex alone (fa_kvcache_append_ragged.hip): a device pointer to B int32 token counts, m_b = min(max(., 0), Nnew);
+    // fa_kvcache_append_ex alone (fa_kvcache_append_padded.hip): a device pointer to B int32 token counts, m_b = min(max(., 0), Nnew);
     // null: every sequence appends Nnew tokens, and the call is the flat entry's
     const int* seqlens_new;
 };
 hipError_t kvcache_append_dispatch(const KvAppendArgs& a);
-// what kvcache_append_dispatch hands a checked `rope` call to; Ncap: the checked capacity, lg_page: log2 of the page size (paged only)
-hipError_t kvcache_append_rope(const KvAppendArgs& a, int Ncap, int lg_page);
-// the rotary arguments' checks alone (fa_kvcache_append_rope.hip); qchunks: the 16-byte chunks of Q (counted whether or not there is a Q)
-hipError_t kvcache_append_rope_check(const KvAppendArgs& a, unsigned long long& qchunks);
-// what kvcache_append_dispatch hands a checked call with seqlens_new to, rotary or not (fa_kvcache_append_ragged.hip)
-hipError_t kvcache_append_ragged(const KvAppendArgs& a, int Ncap, int lg_page);
-// the lengths kernel behind either append kernel (fa_kvcache_append.hip); nothing is launched without a seqlens_out
-hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap);
+// what kvcache_append_dispatch hands a checked call with `rope` or seqlens_new to (fa_kvcache_append_padded.hip); Ncap: the checked
+// capacity, lg_page: log2 of the page size (paged only)
+hipError_t kvcache_append_padded(const KvAppendArgs& a, int Ncap, int lg_page);
+// What the write side shares on the host (fa_kvcache_append.hip).  The cache of an append, append_varlen or commit call with the rows
+// that go into it (commit: the caches themselves): kvwrite_check runs the decode entries' checks on it (kvcache_check, kvpaged_check),
+// the rows standing in for Q and O, and returns the checked capacity and log2 of the page size (0: contiguous).
+struct KvWriteCache {
+    const void *src_k, *src_v, *K, *V;
+    const int *seqlens, *table;
+    int B, Hkv, Ncap, D, dtype, num_pages, page_size, max_pages;
+    bool paged;
+};
+hipError_t kvwrite_check(const KvWriteCache& w, int& Ncap, int& lg_page);
+// the rotary arguments' checks, short of what Q and Qout add; heads: B * Hkv
+hipError_t kvappend_rope_check(const float* cos, const float* sin, int rot_dim, int D, int max_pos, int G, int interleaved, long long heads);
+// The lengths kernel behind every append's copy, out[i] = min(clamp(in[i], 0, cap) + m_i, cap): m_i is the clamped cu[i + 1] - cu[i]
+// with a cu (n: the total), else cnt[i] clamped into [0, n], else n.  Nothing is launched without an `out`.
+hipError_t kvappend_lens(const int* in, const int* cnt, const int* cu, int* out, int B, int n, int cap, hipStream_t stream);
 // fa_kvcache_append_varlen (fa_kvcache_append_varlen.hip): the checks and the one or two launches; the descriptor is the public one, as it is
 hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
 // fa_kvcache_append_varlen_ex: the options' checks, then the same; positions (device, total_new int32, or null) are the rotary table

@@ -1,9 +1,11 @@
 // fa_kvcache_append.hip -- the write half of a decode step (fa_kvcache_append, _paged, _fp8, _paged_fp8): Nnew new K and V rows per
 // sequence are copied behind the sequence's current length, into a contiguous cache or through a block table into a page pool, as
 // they are or quantised to e4m3fn with the head's scale.  Lengths, table and scales are read on the device, so a captured
-// append -> decode pair follows a growing cache.  DESIGN.md section 7.5 has the reasoning.  The device helpers are shared with the
-// _rope entries' unit through fa_kvcache_append.hpp.
+// append -> decode pair follows a growing cache.  DESIGN.md section 7.5 has the reasoning.  Also here, for the whole write side
+// (DESIGN.md 7.23): the lengths kernel behind every append's copy, the cache check and the rotary-argument check.
 #include "fa_kvcache_append.hpp"
+
+#include <limits.h>
 
 namespace fa {
 
@@ -11,7 +13,9 @@ namespace fa {
 // [B, Hkv, Nnew, D], so thread g of a tensor reads bytes [16 g, 16 g + 16): the loads of a wave are 1 KiB in a row.  Length, page
 // number and scale are the same for the D / 8 threads of a row: each is fetched once by the row (one address per row, broadcast
 // by the memory pipeline), never per element.  A token at or past the capacity, or in a page whose table entry is outside
-// [0, num_pages), is dropped before any address is formed from it.
+// [0, num_pages), is dropped before any address is formed from it.  The body is written out, not put together from append_len,
+// append_page, append_dst_row and append_chunk of the header as every other copy kernel is: through any of them the fp8 kernels
+// of this unit come out in another instruction order, and the flat append is the one the decode step's time was measured with.
 template <typename T, int D, bool kPaged, bool kFp8>
 __global__ void __launch_bounds__(kAppendThreads)
 fa_kvcache_append_kernel(const uint16_t* __restrict__ Knew, const uint16_t* __restrict__ Vnew, void* __restrict__ Kdst,
@@ -53,77 +57,82 @@ fa_kvcache_append_kernel(const uint16_t* __restrict__ Knew, const uint16_t* __re
     }
 }
 
-// The lengths after the append, min(L_b + Nnew, Ncap).  A kernel of its own behind the copy on the same stream: every read of
-// seqlens by the copy has retired before this one starts, so `out` may be `in` itself.
+// The lengths after an append, min(L_i + m_i, cap), for all four append kernels: m_i from the clamped bounds of `cu` (n: the total),
+// else the clamped count, else n.  A kernel of its own behind the copy on the same stream: every read of the lengths by the copy
+// has retired before this one starts, so `out` may be `in` itself; `cnt` and `cu` never overlap `out` (checked on the host).
 __global__ void __launch_bounds__(kAppendThreads)
-fa_kvcache_append_lens_kernel(const int* in, int* out, int B, int Nnew, int Ncap)
+fa_kvcache_append_lens_kernel(const int* in, const int* __restrict__ cnt, const int* __restrict__ cu, int* out, int B, int n, int cap)
 {
     const unsigned i = blockIdx.x * (unsigned)kAppendThreads + threadIdx.x;
     if (i >= (unsigned)B) return;
-    int L = 0;
-    if (in) {
-        const int raw = in[i];
-        L = raw < 0 ? 0 : (raw > Ncap ? Ncap : raw);
+    const unsigned L = append_len(in, cap, i);
+    unsigned m = (unsigned)n;
+    if (cu) {
+        const unsigned s = cu_at(cu, i, n), e = cu_at(cu, i + 1, n);
+        m = e > s ? e - s : 0u;
+    } else if (cnt) {
+        const int raw = cnt[i];
+        m = (unsigned)(raw < 0 ? 0 : (raw > n ? n : raw));
     }
-    const long long n = (long long)L + Nnew;
-    out[i] = n < Ncap ? (int)n : Ncap;
+    const long long sum = (long long)L + m;
+    out[i] = sum < cap ? (int)sum : cap;
 }
 
-// the launch of the kernel above, for both append units; Ncap: the checked capacity
-hipError_t kvcache_append_lens(const KvAppendArgs& a, int Ncap)
+hipError_t kvappend_lens(const int* in, const int* cnt, const int* cu, int* out, int B, int n, int cap, hipStream_t stream)
 {
-    if (!a.seqlens_out) return hipSuccess;
-    FA_LAUNCH(fa_kvcache_append_lens_kernel, dim3(((unsigned)a.B + kAppendThreads - 1) / kAppendThreads), dim3(kAppendThreads), 0,
-              a.stream, a.seqlens, a.seqlens_out, a.B, a.Nnew, Ncap);
+    if (!out) return hipSuccess;
+    FA_LAUNCH(fa_kvcache_append_lens_kernel, dim3(((unsigned)B + kAppendThreads - 1) / kAppendThreads), dim3(kAppendThreads), 0, stream, in,
+              cnt, cu, out, B, n, cap);
     return launch_status();
 }
 
-template <typename T, int D, bool kPaged, bool kFp8>
-static hipError_t launch_append(const KvAppendArgs& a, const AppendDev& dev)
+hipError_t kvwrite_check(const KvWriteCache& w, int& Ncap, int& lg_page)
 {
-    const unsigned blocks = (dev.chunks + kAppendThreads - 1) / kAppendThreads;   // from (B, Hkv, Nnew, D) alone
-    FA_LAUNCH((fa_kvcache_append_kernel<T, D, kPaged, kFp8>), dim3(blocks, 2), dim3(kAppendThreads), 0, a.stream,
-              static_cast<const uint16_t*>(a.Knew), static_cast<const uint16_t*>(a.Vnew), a.K, a.V, dev);
-    const hipError_t e = launch_status();
-    return e != hipSuccess ? e : kvcache_append_lens(a, dev.Ncap);
+    // null pointers, B, Hkv, the capacity and its bound, d, dtype; the page geometry
+    const KvPagedArgs chk = {.c = {.Q = w.src_k, .K = w.K, .V = w.V, .O = const_cast<void*>(w.src_v), .seqlens = w.seqlens, .B = w.B,
+                                   .Hkv = w.Hkv, .G = 1, .Nq = 1, .Ncap = w.paged ? 0 : w.Ncap, .D = w.D, .scale = 1.0f, .in_dtype = w.dtype},
+                             .table = w.table, .num_pages = w.paged ? w.num_pages : 0, .page_size = w.paged ? w.page_size : 0,
+                             .max_pages = w.paged ? w.max_pages : 0};
+    KvPagedArgs with_cap = chk;
+    lg_page = 0;
+    const hipError_t bad = w.paged ? kvpaged_check(chk, with_cap, lg_page) : kvcache_check(chk.c);
+    Ncap = with_cap.c.Ncap;
+    return bad;
 }
 
-template <bool kPaged, bool kFp8>
-static hipError_t append_types(const KvAppendArgs& a, const AppendDev& dev)
+hipError_t kvappend_rope_check(const float* cos, const float* sin, int rot_dim, int D, int max_pos, int G, int interleaved, long long heads)
 {
-    // a 16-bit cache takes the source bits as they are: one instantiation serves fp16 and bf16
-    if constexpr (kFp8)
-        if (a.dtype == 1)
-            return a.D == 64 ? launch_append<BF16, 64, kPaged, kFp8>(a, dev) : launch_append<BF16, 128, kPaged, kFp8>(a, dev);
-    return a.D == 64 ? launch_append<F16, 64, kPaged, kFp8>(a, dev) : launch_append<F16, 128, kPaged, kFp8>(a, dev);
+    if (!cos || !sin) return hipErrorInvalidValue;
+    if (rot_dim < 16 || rot_dim > D || rot_dim % 16 != 0) return hipErrorInvalidValue;
+    if (max_pos <= 0 || G <= 0 || (interleaved != 0 && interleaved != 1)) return hipErrorInvalidValue;
+    return heads * G > (long long)INT_MAX ? hipErrorInvalidValue : hipSuccess;   // heads fits an int (kvcache_check): no wrap
 }
 
 hipError_t kvcache_append_dispatch(const KvAppendArgs& a)
 {
     if (a.Nnew <= 0) return hipErrorInvalidValue;
-    // the decode entries' checks on the cache this append feeds (null pointers, B, Hkv, Ncap, d, dtype, the bound on Ncap; the page
-    // geometry), with the new rows in the place of Q and O
-    KvPagedArgs chk = {{a.Knew, a.K, a.V, const_cast<void*>(a.Vnew), nullptr, a.seqlens, a.B, a.Hkv, 1, 1, a.Ncap, a.D, 1.0f, 0, a.dtype, 0,
-                        nullptr, 0, a.stream}, a.table, a.num_pages, a.page_size, a.max_pages};
-    int lg_page = 0;
-    KvPagedArgs with_cap = chk;
-    const hipError_t bad = a.paged ? kvpaged_check(chk, with_cap, lg_page) : kvcache_check(chk.c);
+    int Ncap = 0, lg_page = 0;
+    const hipError_t bad = kvwrite_check({.src_k = a.Knew, .src_v = a.Vnew, .K = a.K, .V = a.V, .seqlens = a.seqlens, .table = a.table,
+                                          .B = a.B, .Hkv = a.Hkv, .Ncap = a.Ncap, .D = a.D, .dtype = a.dtype, .num_pages = a.num_pages,
+                                          .page_size = a.page_size, .max_pages = a.max_pages, .paged = a.paged}, Ncap, lg_page);
     if (bad != hipSuccess) return bad;
-    const int Ncap = with_cap.c.Ncap;
     // a thread's chunk number is 32 bit (so is the grid): sources of 2^31 chunks (32 GiB) and more per tensor are refused
     const unsigned long long chunks = (unsigned long long)a.B * a.Hkv * (unsigned long long)a.Nnew * (unsigned)(a.D / 8);
     if (chunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (a.seqlens_out && a.seqlens && a.seqlens_out != a.seqlens) {   // the same buffer or disjoint ones; never a partial overlap
-        const uintptr_t in = reinterpret_cast<uintptr_t>(a.seqlens), out = reinterpret_cast<uintptr_t>(a.seqlens_out);
-        const uintptr_t bytes = (uintptr_t)a.B * sizeof(int);
-        if (in < out + bytes && out < in + bytes) return hipErrorInvalidValue;
-    }
-    // a token count per sequence: its own checks and kernels, rotary or not (fa_kvcache_append_ragged.hip)
-    if (a.seqlens_new) return kvcache_append_ragged(a, Ncap, lg_page);
-    if (a.rope) return kvcache_append_rope(a, Ncap, lg_page);   // its own checks, then its own kernels (fa_kvcache_append_rope.hip)
+    if (!lens_out_ok(a.seqlens, a.seqlens_out, a.B, a.seqlens_new, (size_t)a.B * sizeof(int))) return hipErrorInvalidValue;
+    // a rotation or a token count per sequence: their own checks and kernels (fa_kvcache_append_padded.hip)
+    if (a.seqlens_new || a.rope) return kvcache_append_padded(a, Ncap, lg_page);
     const AppendDev dev = {a.seqlens, a.table, a.k_scale, a.v_scale, (unsigned)chunks, a.Hkv, a.Nnew, Ncap, a.max_pages, a.num_pages, lg_page};
-    if (a.paged) return a.fp8 ? append_types<true, true>(a, dev) : append_types<true, false>(a, dev);
-    return a.fp8 ? append_types<false, true>(a, dev) : append_types<false, false>(a, dev);
+    return append_form(a.dtype, a.D, a.paged, a.fp8, [&](auto form) {
+        using F = decltype(form);
+        // a 16-bit cache takes the source bits as they are: the F16 instantiation serves fp16 and bf16
+        using T = std::conditional_t<F::kFp8, typename F::T, F16>;
+        const unsigned blocks = (dev.chunks + kAppendThreads - 1) / kAppendThreads;   // from (B, Hkv, Nnew, D) alone
+        FA_LAUNCH((fa_kvcache_append_kernel<T, F::D, F::kPaged, F::kFp8>), dim3(blocks, 2), dim3(kAppendThreads), 0, a.stream,
+                  static_cast<const uint16_t*>(a.Knew), static_cast<const uint16_t*>(a.Vnew), a.K, a.V, dev);
+        const hipError_t e = launch_status();
+        return e != hipSuccess ? e : kvappend_lens(a.seqlens, nullptr, nullptr, a.seqlens_out, a.B, a.Nnew, Ncap, a.stream);
+    });
 }
 
 }  // namespace fa

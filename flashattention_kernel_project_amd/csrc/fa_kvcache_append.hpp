@@ -1,10 +1,10 @@
-// fa_kvcache_append.hpp -- the device side the four append translation units share (fa_kvcache_append.hip: the plain entries;
-// fa_kvcache_append_rope.hip: the _rope entries; fa_kvcache_append_ragged.hip: fa_kvcache_append_ex with a token count per sequence;
-// fa_kvcache_append_varlen.hip: fa_kvcache_append_varlen on token-packed sources):
-// the kernels' argument pack, the length clamp, the page lookup with its 64-bit destination row, the e4m3fn quantisation, and the
-// rotation of one row chunk.  fa_kvcache_commit.hip, which moves rows the appends placed, takes the clamp and the page lookup from here
-// too.  Private to csrc/.  Everything is in an unnamed namespace: each unit gets its own
-// copy, all of it is inlined, and the kernels' symbols stay what they were when the helpers lived in fa_kvcache_append.hip.
+// fa_kvcache_append.hpp -- what the write side of the KV cache shares.  Three append translation units (fa_kvcache_append.hip: the
+// plain entries, the lengths kernel and the host checks of all; fa_kvcache_append_padded.hip: the padded entries that rotate or
+// take a token count per sequence; fa_kvcache_append_varlen.hip: token-packed sources), fa_mla_append.hip and fa_kvcache_commit.hip
+// take from here, on the device: the kernels' argument pack, the length clamp, the page lookup with its 64-bit destination row, the
+// search of cu_seqlens_new, the e4m3fn quantisation, the store of one chunk and the rotation of one; on the host: the form switch
+// and the interval test.  Private to csrc/.  Everything is in an unnamed namespace: each unit gets its own copy and all of it is
+// inlined.  DESIGN.md section 7.23 has the map.
 #pragma once
 #include "fa_dispatch.hpp"
 
@@ -63,9 +63,9 @@ __device__ __forceinline__ unsigned quant4f(float x0, float x1, float x2, float 
     return quant_codes(x0 / s, x1 / s, x2 / s, x3 / s);
 }
 
-// The position helpers of the _rope kernel.  fa_kvcache_append_kernel keeps the same three steps written out in its body: called
-// through these (by reference or by value) its fp8 kernels come out with another instruction order, and that unit's device code
-// is to stay as measured (profiles/kvcache_append_rope.txt has the diff).
+// The position helpers of every kernel but fa_kvcache_append_kernel, which keeps the same three steps written out in its body:
+// called through these (by reference or by value) its fp8 kernels come out with another instruction order, and that unit's device
+// code is to stay as measured (profiles/kvcache_append_rope.txt has the diff).
 
 // L_b = min(max(seqlens[b], 0), Ncap); no lengths: 0
 __device__ __forceinline__ unsigned append_len(const int* seqlens, int Ncap, unsigned b)
@@ -93,7 +93,53 @@ __device__ __forceinline__ size_t append_dst_row(int page, int Hkv, int lg_page,
     return (size_t)bh * (unsigned)Ncap + p;
 }
 
-// ---- the rotary part: shared by fa_kvcache_append_rope.hip and fa_kvcache_append_ragged.hip ----
+// One 16-byte chunk of a row that is not rotated: `src` is the chunk's source address, `dst` the tensor's base, `scale` the tensor's
+// [Hkv] scales or null (1.0).  The copy, or the quantisation by the head's scale.  fa_kvcache_append_kernel keeps these lines
+// written out as well: through this call its code changes (profiles/append_write_refactor.txt).
+template <typename T, int D, bool kFp8>
+__device__ __forceinline__ void append_chunk(const u32x4* src, char* dst, size_t dst_row, unsigned c, const float* scale, unsigned h)
+{
+    constexpr bool kNt = FA_APPEND_NT_LOAD >= (kFp8 ? 2 : 1);
+    const u32x4 v = kNt ? __builtin_nontemporal_load(src) : *src;
+    if constexpr (kFp8) {
+        const float s = scale ? scale[h] : 1.0f;
+        const u32x2 o = {quant4<T>(v[0], v[1], s), quant4<T>(v[2], v[3], s)};
+        *reinterpret_cast<u32x2*>(dst + dst_row * D + c * 8) = o;
+    } else {
+        *reinterpret_cast<u32x4*>(dst + dst_row * (D * 2) + c * 16) = v;
+    }
+}
+
+// ---- token-packed sources (fa_kvcache_append_varlen.hip, fa_mla_append.hip): the sequence of a row, from cu_seqlens_new ----
+
+// cu[j] clamped into [0, total]
+__device__ __forceinline__ unsigned cu_at(const int* cu, unsigned j, int total)
+{
+    const int raw = cu[j];
+    return (unsigned)(raw < 0 ? 0 : (raw > total ? total : raw));
+}
+
+// The largest b in [0, B) whose clamped start is <= t (0 when none is): log2(B) reads of cu, every index inside [0, B).  Among
+// sequences that start at one row -- empty ones and the one behind them -- this is the last, the only one that can own the row.
+__device__ __forceinline__ unsigned seq_search(const int* cu, unsigned B, int total, unsigned t)
+{
+    unsigned lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (cu_at(cu, mid, total) <= t) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Does sequence b own row t?  s_b = clamp(cu[b], 0, total), e_b = clamp(cu[b+1], s_b, total): on true, s <= t < e <= total.
+__device__ __forceinline__ bool seq_owns(const int* cu, unsigned b, int total, unsigned t, unsigned& s)
+{
+    s = cu_at(cu, b, total);
+    const unsigned e = cu_at(cu, b + 1, total);   // e < s (a non-monotone vector) owns nothing: t >= s excludes t < e
+    return s <= t && t < e;
+}
+
+// ---- the rotary part: fa_kvcache_append_padded.hip and fa_kvcache_append_varlen.hip ----
 
 struct RopeDev {
     const float* cos;      // [max_pos][half] fp32 on the device
@@ -188,6 +234,57 @@ __device__ __forceinline__ void rope_row(const u32x4* src, char* dst_row, unsign
         store8<T, kCodes>(dst_row + c * kOut, y, s);
         store8<T, kCodes>(dst_row + (c + half_chunks) * kOut, y2, s);
     }
+}
+
+// ---- the host side ----
+
+// Do [x, x + xbytes) and [y, y + ybytes) share a byte?  Each caller states its own rule around it: identity allowed, or not.
+inline bool ranges_overlap(const void* x, size_t xbytes, const void* y, size_t ybytes)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+    return a < b + ybytes && b < a + xbytes;
+}
+
+// The rule of every lengths kernel's buffers: what it reads besides `in` -- counts, bounds, accept words; null: nothing -- shares no
+// byte with `out`, identity included, and `in` is `out` itself or shares no byte with it.  No `out`: nothing is written.
+inline bool lens_out_ok(const int* in, const int* out, int B, const void* also, size_t also_bytes)
+{
+    const size_t bytes = (size_t)B * sizeof(int);
+    if (!out) return true;
+    if (also && ranges_overlap(also, also_bytes, out, bytes)) return false;
+    return !in || in == out || !ranges_overlap(in, bytes, out, bytes);
+}
+
+// The KvWriteCache of a descriptor (fa_kvappend_varlen_desc, fa_kvcommit_desc: one set of field names); a block table makes it paged.
+template <typename Desc> KvWriteCache write_cache_of(const Desc& d, const void* src_k, const void* src_v)
+{
+    return {src_k, src_v, d.K, d.V, d.seqlens_k, d.block_table, d.B, d.Hkv, d.Ncap, d.d, d.dtype, d.num_pages, d.page_size, d.max_pages,
+            d.block_table != nullptr};
+}
+
+// The form of a copy kernel as compile-time tags: the source's element type, the row length, the cache's addressing and element.
+template <typename T_, int D_, bool kPaged_, bool kFp8_> struct AppendForm {
+    using T = T_;
+    static constexpr int D = D_;
+    static constexpr bool kPaged = kPaged_, kFp8 = kFp8_;
+};
+template <typename F> hipError_t on_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+// (dtype, D, paged, fp8) of a checked call -> f(AppendForm<...>{}): the one switch of the three append units
+template <typename F> hipError_t append_form(int dtype, int D, bool paged, bool fp8, F&& f)
+{
+    return on_flag(dtype == 1, [&](auto bf) {
+        return on_flag(D == 64, [&](auto d64) {
+            return on_flag(paged, [&](auto pg) {
+                return on_flag(fp8, [&](auto q) { return f(AppendForm<std::conditional_t<bf(), BF16, F16>, d64() ? 64 : 128, pg(), q()>{}); });
+            });
+        });
+    });
+}
+// the rotary mode of a call -> f(integral constant): 0 no rotation, 1 half-split pairs, 2 interleaved pairs
+template <typename F> hipError_t append_rope_mode(bool rope, bool interleaved, F&& f)
+{
+    if (!rope) return f(std::integral_constant<int, 0>{});
+    return interleaved ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 1>{});
 }
 
 }  // namespace

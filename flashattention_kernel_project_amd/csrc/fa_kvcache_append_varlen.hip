@@ -2,11 +2,12 @@
 // rotary, Q (total_new, Hkv*G, d) are read through their own token and head strides, as views of the projection's buffer lie, and cut
 // into sequences by cu_seqlens_new on the device.  One kernel template serves all eight forms (contiguous or paged, 16 bit or e4m3fn,
 // plain or rotary) on the helpers of fa_kvcache_append.hpp, so every kept token's bytes are those fa_kvcache_append_ex writes from the
-// padded head-major copy of the same rows.  The other append units keep their device code.  DESIGN.md section 7.16.
+// padded head-major copy of the same rows.  The search of cu_seqlens_new, the lengths kernel and the host checks are the write
+// side's shared ones.  DESIGN.md section 7.16.
 #include "../../include/fa_mi355.h"
 #include "fa_kvcache_append.hpp"
 
-// the rotary arithmetic is a contract of bytes: no fused multiply-add anywhere in this unit (fa_kvcache_append_rope.hip)
+// the rotary arithmetic is a contract of bytes: no fused multiply-add anywhere in this unit (fa_kvcache_append_padded.hip)
 #pragma clang fp contract(off)
 
 // The thread order over (token, head, chunk) inside a tensor: 0 = token-major (a wave reads the heads of a token in a row, as the
@@ -27,38 +28,11 @@ struct PackedDev {
     long long k_t, k_h, v_t, v_h, q_t, q_h, qo_t, qo_h;
 };
 
-// cu[j] clamped into [0, total]
-__device__ __forceinline__ unsigned cu_at(const int* cu, unsigned j, int total)
-{
-    const int raw = cu[j];
-    return (unsigned)(raw < 0 ? 0 : (raw > total ? total : raw));
-}
-
-// The largest b in [0, B) whose clamped start is <= t (0 when none is): log2(B) reads of cu, every index inside [0, B).  Among
-// sequences that start at one row -- empty ones and the one behind them -- this is the last, the only one that can own the row.
-__device__ __forceinline__ unsigned seq_search(const int* cu, unsigned B, int total, unsigned t)
-{
-    unsigned lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (cu_at(cu, mid, total) <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Does sequence b own row t?  s_b = clamp(cu[b], 0, total), e_b = clamp(cu[b+1], s_b, total): on true, s <= t < e <= total.
-__device__ __forceinline__ bool seq_owns(const int* cu, unsigned b, int total, unsigned t, unsigned& s)
-{
-    s = cu_at(cu, b, total);
-    const unsigned e = cu_at(cu, b + 1, total);   // e < s (a non-monotone vector) owns nothing: t >= s excludes t < e
-    return s <= t && t < e;
-}
-
 }  // namespace
 
 // kRope: 0 no rotation (no Q blocks are launched), 1 half-split pairs, 2 interleaved pairs.  A row that no sequence owns retires
 // before anything is formed from it: nothing is loaded, nothing is written, its Qout row stays as it was.  For an owned row
-// i = t - s_b lies in [0, m_b) whatever the vector holds, and from there on the steps are fa_kvcache_append_ragged_kernel's.
+// i = t - s_b lies in [0, m_b) whatever the vector holds, and from there on the steps are fa_kvcache_append_padded_kernel's.
 // Pos: nothing, or -- fa_kvcache_append_varlen_ex with positions, rotary forms only -- one const int*: the table row of token t is
 // then positions[t] clamped into [0, max_pos), read once the row has an owner, while the destination stays slot p.  A trailing pack
 // and not a flag with an argument of its own, so that the plain instantiations keep their argument list and their code.
@@ -107,24 +81,15 @@ fa_kvcache_append_varlen_kernel(const uint16_t* __restrict__ Knew, const uint16_
         dst_row = append_dst_row<kPaged>(page, a.Hkv, a.lg_page, a.Ncap, h, b * (unsigned)a.Hkv + h, p);
     }
 
-    constexpr bool kNt = FA_APPEND_NT_LOAD >= (kFp8 ? 2 : 1);
-    if (is_v || kRope == 0) {   // fa_kvcache_append_kernel's body: the copy, or the quantisation by the head's scale
+    if (is_v || kRope == 0) {
         const u32x4* src = reinterpret_cast<const u32x4*>(is_v ? Vnew : Knew) +
                            ((size_t)t * (size_t)(is_v ? k.v_t : k.k_t) + (size_t)hh * (size_t)(is_v ? k.v_h : k.k_h) + c);
-        const u32x4 v = kNt ? __builtin_nontemporal_load(src) : *src;
-        char* dst = static_cast<char*>(is_v ? Vdst : Kdst);
-        if constexpr (kFp8) {
-            const float* sp = is_v ? a.v_scale : a.k_scale;
-            const float sc = sp ? sp[h] : 1.0f;
-            const u32x2 o = {quant4<T>(v[0], v[1], sc), quant4<T>(v[2], v[3], sc)};
-            *reinterpret_cast<u32x2*>(dst + dst_row * D + c * 8) = o;
-        } else {
-            *reinterpret_cast<u32x4*>(dst + dst_row * (D * 2) + c * 16) = v;
-        }
+        append_chunk<T, D, kFp8>(src, static_cast<char*>(is_v ? Vdst : Kdst), dst_row, c, is_v ? a.v_scale : a.k_scale, h);
         return;
     }
 
-    if constexpr (kRope != 0) {   // K or Q of a rotary form: fa_kvcache_append_rope_kernel's two calls
+    if constexpr (kRope != 0) {   // K or Q of a rotary form: fa_kvcache_append_padded_kernel's two calls
+        constexpr bool kNt = FA_APPEND_NT_LOAD >= (kFp8 ? 2 : 1);
         unsigned rp = p;   // the table row: the slot, or the token's entry of the vector (rope_row clamps it at max_pos - 1)
         if constexpr (sizeof...(Pos) == 1) {
             const int at = (positions, ...)[t];
@@ -142,67 +107,27 @@ fa_kvcache_append_varlen_kernel(const uint16_t* __restrict__ Knew, const uint16_
     }
 }
 
-// The lengths after the append, min(L_b + m_b, Ncap), with m_b from the clamped bounds.  Behind the copy on the same stream, so
-// `out` may be `in` itself; `cu` never overlaps `out` (checked on the host).
-__global__ void __launch_bounds__(kAppendThreads)
-fa_kvcache_append_varlen_lens_kernel(const int* in, const int* __restrict__ cu, int* out, int B, int total, int Ncap)
-{
-    const unsigned i = blockIdx.x * (unsigned)kAppendThreads + threadIdx.x;
-    if (i >= (unsigned)B) return;
-    const int L = (int)append_len(in, Ncap, i);
-    const unsigned s = cu_at(cu, i, total), e = cu_at(cu, i + 1, total);
-    const long long n = (long long)L + (e > s ? e - s : 0u);
-    out[i] = n < Ncap ? (int)n : Ncap;
-}
-
 namespace {
 
 struct VarlenAppendCall {
     const fa_kvappend_varlen_desc* d;
-    const int* positions;   // fa_kvcache_append_varlen_ex, rotary forms only; null: the plain kernels
     AppendDev dev;
     RopeDev r;
     PackedDev k;
     unsigned blocks;
-    hipStream_t stream;
 };
 
-template <typename T, int D, bool kPaged, bool kFp8, int kRope>
-hipError_t launch_varlen(const VarlenAppendCall& c)
+// Pos: nothing, or the position vector (rotary forms only)
+template <typename F, int kRope, typename... Pos>
+hipError_t launch_varlen(const VarlenAppendCall& c, Pos... positions)
 {
     const fa_kvappend_varlen_desc* d = c.d;
-    bool launched = false;
-    if constexpr (kRope != 0) {
-        if (c.positions) {
-            FA_LAUNCH((fa_kvcache_append_varlen_kernel<T, D, kPaged, kFp8, kRope, FA_APPEND_VARLEN_ORDER != 0, const int*>), dim3(c.blocks),
-                      dim3(kAppendThreads), 0, c.stream, static_cast<const uint16_t*>(d->Knew), static_cast<const uint16_t*>(d->Vnew), d->K,
-                      d->V, static_cast<const uint16_t*>(d->Q), static_cast<uint16_t*>(d->Qout), c.dev, c.r, c.k, c.positions);
-            launched = true;
-        }
-    }
-    if (!launched)
-    FA_LAUNCH((fa_kvcache_append_varlen_kernel<T, D, kPaged, kFp8, kRope, FA_APPEND_VARLEN_ORDER != 0>), dim3(c.blocks),
-              dim3(kAppendThreads), 0, c.stream, static_cast<const uint16_t*>(d->Knew), static_cast<const uint16_t*>(d->Vnew), d->K, d->V,
-              static_cast<const uint16_t*>(d->Q), static_cast<uint16_t*>(d->Qout), c.dev, c.r, c.k);
-    hipError_t e = launch_status();
-    if (e != hipSuccess || !d->seqlens_out) return e;
-    FA_LAUNCH(fa_kvcache_append_varlen_lens_kernel, dim3(((unsigned)d->B + kAppendThreads - 1) / kAppendThreads), dim3(kAppendThreads), 0,
-              c.stream, d->seqlens_k, d->cu_seqlens_new, d->seqlens_out, d->B, d->total_new, c.dev.Ncap);
-    return launch_status();
-}
-
-template <typename T, int D, int kRope>
-hipError_t varlen_forms(const VarlenAppendCall& c, bool paged, bool fp8)
-{
-    if (paged) return fp8 ? launch_varlen<T, D, true, true, kRope>(c) : launch_varlen<T, D, true, false, kRope>(c);
-    return fp8 ? launch_varlen<T, D, false, true, kRope>(c) : launch_varlen<T, D, false, false, kRope>(c);
-}
-
-template <typename T, int D>
-hipError_t varlen_rope_modes(const VarlenAppendCall& c, bool paged, bool fp8, int mode)
-{
-    if (mode == 0) return varlen_forms<T, D, 0>(c, paged, fp8);
-    return mode == 2 ? varlen_forms<T, D, 2>(c, paged, fp8) : varlen_forms<T, D, 1>(c, paged, fp8);
+    hipStream_t stream = static_cast<hipStream_t>(d->stream);
+    FA_LAUNCH((fa_kvcache_append_varlen_kernel<typename F::T, F::D, F::kPaged, F::kFp8, kRope, FA_APPEND_VARLEN_ORDER != 0, Pos...>),
+              dim3(c.blocks), dim3(kAppendThreads), 0, stream, static_cast<const uint16_t*>(d->Knew), static_cast<const uint16_t*>(d->Vnew),
+              d->K, d->V, static_cast<const uint16_t*>(d->Q), static_cast<uint16_t*>(d->Qout), c.dev, c.r, c.k, positions...);
+    const hipError_t e = launch_status();
+    return e != hipSuccess ? e : kvappend_lens(d->seqlens_k, nullptr, d->cu_seqlens_new, d->seqlens_out, d->B, d->total_new, c.dev.Ncap, stream);
 }
 
 // fa_varlen_desc's rules for a packed tensor (total, H, d) of 16-bit elements, without its 32-bit bound: the addresses here are 64 bit
@@ -218,7 +143,8 @@ unsigned __int128 packed_extent(int total, long long H, int d, long long st, lon
     return ((unsigned __int128)(total - 1) * (unsigned long long)st + (unsigned __int128)(H - 1) * (unsigned long long)sh + (unsigned)d) * 2u;
 }
 
-bool overlap(const void* x, unsigned __int128 xbytes, const void* y, unsigned __int128 ybytes)
+// ranges_overlap for extents that strides of 2^63 elements can reach
+bool ranges_overlap(const void* x, unsigned __int128 xbytes, const void* y, unsigned __int128 ybytes)
 {
     const unsigned __int128 a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
     return a < b + ybytes && b < a + xbytes;
@@ -237,36 +163,21 @@ static hipError_t append_varlen_checked(const ::fa_kvappend_varlen_desc* d, cons
     if (!fp8 && (d->k_scale || d->v_scale)) return hipErrorInvalidValue;               // a 16-bit cache has no scales
     if (!rope && (d->Q || d->Qout || d->rope_sin)) return hipErrorInvalidValue;        // arguments of the rotary forms
     if (!d->cu_seqlens_new || d->total_new <= 0) return hipErrorInvalidValue;
-    // the decode entries' checks on the cache this append feeds, as in kvcache_append_dispatch
-    KvPagedArgs chk = {{d->Knew, d->K, d->V, const_cast<void*>(d->Vnew), nullptr, d->seqlens_k, d->B, d->Hkv, 1, 1, paged ? 0 : d->Ncap, d->d,
-                        1.0f, 0, d->dtype, 0, nullptr, 0, static_cast<hipStream_t>(d->stream)},
-                       d->block_table, paged ? d->num_pages : 0, paged ? d->page_size : 0, paged ? d->max_pages : 0};
-    int lg_page = 0;
-    KvPagedArgs with_cap = chk;
-    const hipError_t bad = paged ? kvpaged_check(chk, with_cap, lg_page) : kvcache_check(chk.c);
+    int Ncap = 0, lg_page = 0;
+    const hipError_t bad = kvwrite_check(write_cache_of(*d, d->Knew, d->Vnew), Ncap, lg_page);
     if (bad != hipSuccess) return bad;
-    const int Ncap = with_cap.c.Ncap;
     if (!packed_ok(d->Knew, d->d, d->k_stride_t, d->k_stride_h) || !packed_ok(d->Vnew, d->d, d->v_stride_t, d->v_stride_h))
         return hipErrorInvalidValue;
     // a thread's chunk number is 32 bit (so is the grid)
     const unsigned long long chunks = (unsigned long long)d->total_new * (unsigned)d->Hkv * (unsigned)(d->d / 8);
     if (chunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const uintptr_t cu = reinterpret_cast<uintptr_t>(d->cu_seqlens_new), cu_bytes = ((uintptr_t)d->B + 1) * sizeof(int);
-    const uintptr_t len_bytes = (uintptr_t)d->B * sizeof(int);
-    if (d->seqlens_out) {
-        const uintptr_t out = reinterpret_cast<uintptr_t>(d->seqlens_out), in = reinterpret_cast<uintptr_t>(d->seqlens_k);
-        if (cu < out + len_bytes && out < cu + cu_bytes) return hipErrorInvalidValue;   // read by the lengths kernel while it writes
-        if (d->seqlens_k && in != out && in < out + len_bytes && out < in + len_bytes) return hipErrorInvalidValue;
-    }
+    if (!lens_out_ok(d->seqlens_k, d->seqlens_out, d->B, d->cu_seqlens_new, ((size_t)d->B + 1) * sizeof(int))) return hipErrorInvalidValue;
     unsigned long long qchunks = 0;
-    int G = 1;
+    const int G = rope ? d->G : 1;
     if (rope) {
-        if (!d->rope_sin) return hipErrorInvalidValue;
-        if (d->rot_dim < 16 || d->rot_dim > d->d || d->rot_dim % 16 != 0) return hipErrorInvalidValue;
-        if (d->max_pos <= 0 || d->G <= 0 || (d->interleaved != 0 && d->interleaved != 1)) return hipErrorInvalidValue;
-        G = d->G;
-        const unsigned long long heads = (unsigned long long)d->B * (unsigned)d->Hkv * (unsigned long long)G;   // B * Hkv fits an int
-        if (heads > (unsigned long long)INT_MAX) return hipErrorInvalidValue;
+        const hipError_t bad_rope = kvappend_rope_check(d->rope_cos, d->rope_sin, d->rot_dim, d->d, d->max_pos, G, d->interleaved,
+                                                        (long long)d->B * d->Hkv);
+        if (bad_rope != hipSuccess) return bad_rope;
         qchunks = (unsigned long long)d->total_new * (unsigned)d->Hkv * (unsigned long long)G * (unsigned)(d->d / 8);
         if (qchunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
         if ((d->Q == nullptr) != (d->Qout == nullptr)) return hipErrorInvalidValue;
@@ -275,29 +186,31 @@ static hipError_t append_varlen_checked(const ::fa_kvappend_varlen_desc* d, cons
                 return hipErrorInvalidValue;
             const bool in_place = d->Q == d->Qout && d->q_stride_t == d->qo_stride_t && d->q_stride_h == d->qo_stride_h;
             const long long Hq = (long long)d->Hkv * G;
-            if (!in_place && overlap(d->Q, packed_extent(d->total_new, Hq, d->d, d->q_stride_t, d->q_stride_h), d->Qout,
-                                     packed_extent(d->total_new, Hq, d->d, d->qo_stride_t, d->qo_stride_h)))
+            if (!in_place && ranges_overlap(d->Q, packed_extent(d->total_new, Hq, d->d, d->q_stride_t, d->q_stride_h), d->Qout,
+                                            packed_extent(d->total_new, Hq, d->d, d->qo_stride_t, d->qo_stride_h)))
                 return hipErrorInvalidValue;
         }
     }
     const bool has_q = rope && d->Q;
-    VarlenAppendCall c;
-    c.d = d;
-    c.positions = positions;
-    c.stream = static_cast<hipStream_t>(d->stream);
-    c.dev = {d->seqlens_k, d->block_table, d->k_scale, d->v_scale, (unsigned)chunks, d->Hkv, d->total_new, Ncap,
-             paged ? d->max_pages : 0, paged ? d->num_pages : 0, lg_page};
     const unsigned kv_blocks = ((unsigned)chunks + kAppendThreads - 1) / kAppendThreads;
     const unsigned q_blocks = has_q ? (unsigned)((qchunks + kAppendThreads - 1) / kAppendThreads) : 0u;
-    c.r = {d->rope_cos, d->rope_sin, has_q ? (unsigned)qchunks : 0u, kv_blocks, G, rope ? d->max_pos : 0, rope ? d->rot_dim / 2 : 0,
-           rope ? d->rot_dim / 8 : 0};
-    c.k = {d->cu_seqlens_new, d->B, d->total_new, d->k_stride_t / 8, d->k_stride_h / 8, d->v_stride_t / 8, d->v_stride_h / 8,
-           has_q ? d->q_stride_t / 8 : 0, has_q ? d->q_stride_h / 8 : 0, has_q ? d->qo_stride_t / 8 : 0, has_q ? d->qo_stride_h / 8 : 0};
-    c.blocks = 2 * kv_blocks + q_blocks;   // at most 3 * 2^23
-    const int mode = !rope ? 0 : (d->interleaved ? 2 : 1);
-    if (d->dtype == 1)
-        return d->d == 64 ? varlen_rope_modes<BF16, 64>(c, paged, fp8, mode) : varlen_rope_modes<BF16, 128>(c, paged, fp8, mode);
-    return d->d == 64 ? varlen_rope_modes<F16, 64>(c, paged, fp8, mode) : varlen_rope_modes<F16, 128>(c, paged, fp8, mode);
+    const VarlenAppendCall c = {
+        d,
+        {d->seqlens_k, d->block_table, d->k_scale, d->v_scale, (unsigned)chunks, d->Hkv, d->total_new, Ncap, paged ? d->max_pages : 0,
+         paged ? d->num_pages : 0, lg_page},
+        {d->rope_cos, d->rope_sin, has_q ? (unsigned)qchunks : 0u, kv_blocks, G, rope ? d->max_pos : 0, rope ? d->rot_dim / 2 : 0,
+         rope ? d->rot_dim / 8 : 0},
+        {d->cu_seqlens_new, d->B, d->total_new, d->k_stride_t / 8, d->k_stride_h / 8, d->v_stride_t / 8, d->v_stride_h / 8,
+         has_q ? d->q_stride_t / 8 : 0, has_q ? d->q_stride_h / 8 : 0, has_q ? d->qo_stride_t / 8 : 0, has_q ? d->qo_stride_h / 8 : 0},
+        2 * kv_blocks + q_blocks};   // at most 3 * 2^23 blocks
+    return append_form(d->dtype, d->d, paged, fp8, [&](auto form) {
+        return append_rope_mode(rope, d->interleaved != 0, [&](auto mode) {
+            using F = decltype(form);
+            if constexpr (mode() != 0)   // the position instantiations exist for the rotary forms only
+                if (positions) return launch_varlen<F, mode()>(c, positions);
+            return launch_varlen<F, mode()>(c);
+        });
+    });
 }
 
 hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* d) { return append_varlen_checked(d, nullptr); }

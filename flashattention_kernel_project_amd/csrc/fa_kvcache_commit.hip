@@ -132,22 +132,12 @@ hipError_t kvcache_commit(const ::fa_kvcommit_desc* d)
     if (d->max_new < 1 || d->max_new > kCommitRows) return hipErrorInvalidValue;
     if (d->kv_dtype != FA_KV_16BIT && d->kv_dtype != FA_KV_FP8_E4M3) return hipErrorInvalidValue;
     const bool fp8 = d->kv_dtype == FA_KV_FP8_E4M3, paged = d->block_table != nullptr;
-    // the decode entries' checks on the cache, as in kvcache_append_dispatch (no Q and no O here: the caches stand in)
-    KvPagedArgs chk = {{d->K, d->K, d->V, d->V, nullptr, d->seqlens_k, d->B, d->Hkv, 1, 1, paged ? 0 : d->Ncap, d->d, 1.0f, 0, d->dtype, 0,
-                        nullptr, 0, static_cast<hipStream_t>(d->stream)},
-                       d->block_table, paged ? d->num_pages : 0, paged ? d->page_size : 0, paged ? d->max_pages : 0};
-    int lg_page = 0;
-    KvPagedArgs with_cap = chk;
-    const hipError_t bad = paged ? kvpaged_check(chk, with_cap, lg_page) : kvcache_check(chk.c);
+    // no new rows here: the caches stand in for them
+    int Ncap = 0, lg_page = 0;
+    const hipError_t bad = kvwrite_check(write_cache_of(*d, d->K, d->V), Ncap, lg_page);
     if (bad != hipSuccess) return bad;
-    const uintptr_t len_bytes = (uintptr_t)d->B * sizeof(int), word_bytes = (uintptr_t)d->B * sizeof(unsigned long long);
-    if (d->seqlens_out) {
-        const uintptr_t out = reinterpret_cast<uintptr_t>(d->seqlens_out), in = reinterpret_cast<uintptr_t>(d->seqlens_k);
-        const uintptr_t words = reinterpret_cast<uintptr_t>(d->accept_mask);
-        if (words < out + len_bytes && out < words + word_bytes) return hipErrorInvalidValue;   // read by the lengths kernel while it writes
-        if (d->seqlens_k && in != out && in < out + len_bytes && out < in + len_bytes) return hipErrorInvalidValue;
-    }
-    const CommitDev dev = {d->seqlens_k, d->accept_mask, d->block_table, d->Hkv, with_cap.c.Ncap, d->max_new,
+    if (!lens_out_ok(d->seqlens_k, d->seqlens_out, d->B, d->accept_mask, (size_t)d->B * sizeof(unsigned long long))) return hipErrorInvalidValue;
+    const CommitDev dev = {d->seqlens_k, d->accept_mask, d->block_table, d->Hkv, Ncap, d->max_new,
                            paged ? d->max_pages : 0, paged ? d->num_pages : 0, lg_page};
     const int row_bytes = fp8 ? d->d : d->d * 2;   // 64, 128 or 256
     if (row_bytes == 64) return launch_commit<2>(d, dev, paged);

@@ -1,10 +1,11 @@
 // fa_mla_append.hip -- fa_mla_append: the write half of fa_mla_decode.  A token-packed batch of latent rows (total_new, 576), read
 // through its token stride and cut into sequences by cu_seqlens_new on the device, is copied bit for bit behind each sequence's keys
-// in the latent cache, contiguous or paged.  A copy kernel on the model of fa_kvcache_append_varlen.hip (whose kernels it leaves
-// alone): one thread per 16-byte chunk, the row's sequence found by a search of cu_seqlens_new, and a lengths kernel behind the copy.
-// No rotary and no heads: a latent row is one row for all heads and arrives rotated.  DESIGN.md section 7.22.
+// in the latent cache, contiguous or paged.  A copy kernel on the model of fa_kvcache_append_varlen.hip, on the same helpers of
+// fa_kvcache_append.hpp: one thread per 16-byte chunk, the row's sequence found by a search of cu_seqlens_new, and the appends'
+// lengths kernel behind the copy.  No rotary and no heads: a latent row is one row for all heads and arrives rotated.  DESIGN.md
+// section 7.22.
 #include "../../include/fa_mi355.h"
-#include "fa_dispatch.hpp"
+#include "fa_kvcache_append.hpp"
 
 namespace fa {
 
@@ -23,33 +24,6 @@ struct MlaAppendDev {
     unsigned chunks;       // total * 72
 };
 
-// cu[j] clamped into [0, total]
-__device__ __forceinline__ unsigned mla_cu_at(const int* cu, unsigned j, int total)
-{
-    const int raw = cu[j];
-    return (unsigned)(raw < 0 ? 0 : (raw > total ? total : raw));
-}
-
-// the largest b in [0, B) whose clamped start is <= t (0 when none is): among sequences that start at one row the last, the only
-// one that can own it
-__device__ __forceinline__ unsigned mla_seq_search(const int* cu, unsigned B, int total, unsigned t)
-{
-    unsigned lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (mla_cu_at(cu, mid, total) <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// L_b: the keys the sequence holds before the append (a null vector: none)
-__device__ __forceinline__ unsigned mla_len(const int* seqlens, int cap, unsigned b)
-{
-    if (!seqlens) return 0u;
-    const int raw = seqlens[b];
-    return (unsigned)(raw < 0 ? 0 : (raw > cap ? cap : raw));
-}
-
 }  // namespace
 
 // A row that no sequence owns retires before anything is loaded; so does a token at or past the capacity, and one whose page number
@@ -61,14 +35,14 @@ fa_mla_append_kernel(MlaAppendDev a)
     const unsigned g = blockIdx.x * (unsigned)kMlaAppendThreads + threadIdx.x;
     if (g >= a.chunks) return;
     const unsigned t = g / kMlaChunks, c = g - t * kMlaChunks;
-    const unsigned b = mla_seq_search(a.cu, (unsigned)a.B, a.total, t);
-    const unsigned s = mla_cu_at(a.cu, b, a.total), e = mla_cu_at(a.cu, b + 1, a.total);
+    const unsigned b = seq_search(a.cu, (unsigned)a.B, a.total, t);
+    const unsigned s = cu_at(a.cu, b, a.total), e = cu_at(a.cu, b + 1, a.total);
     if (!(s <= t && t < e)) return;                             // a row of no sequence (e < s owns nothing)
-    const unsigned p = mla_len(a.seqlens, a.cap, b) + (t - s);  // L <= cap <= 2^30 and t - s < 2^24: no wrap
+    const unsigned p = append_len(a.seqlens, a.cap, b) + (t - s);  // L <= cap <= 2^30 and t - s < 2^24: no wrap
     if (p >= (unsigned)a.cap) return;                           // dropped
     size_t row;
     if constexpr (kPaged) {
-        const int page = a.table[(size_t)b * (unsigned)a.max_pages + (p >> a.lg_page)];
+        const int page = append_page(a.table, a.max_pages, a.lg_page, b, p);
         if ((unsigned)page >= (unsigned)a.num_pages) return;
         row = ((size_t)(unsigned)page << a.lg_page) + (p & ((1u << a.lg_page) - 1u));
     } else {
@@ -76,18 +50,6 @@ fa_mla_append_kernel(MlaAppendDev a)
     }
     const u32x4 v = __builtin_nontemporal_load(a.src + ((size_t)t * (size_t)a.st + c));
     *reinterpret_cast<u32x4*>(a.dst + (row * kMlaChunks + c) * 16u) = v;
-}
-
-// The lengths after the append, min(L_b + m_b, capacity).  Behind the copy on the same stream, so `out` may be `in` itself; `cu`
-// never overlaps `out` (checked on the host).
-__global__ void __launch_bounds__(kMlaAppendThreads)
-fa_mla_append_lens_kernel(const int* in, const int* __restrict__ cu, int* out, int B, int total, int cap)
-{
-    const unsigned i = blockIdx.x * (unsigned)kMlaAppendThreads + threadIdx.x;
-    if (i >= (unsigned)B) return;
-    const unsigned s = mla_cu_at(cu, i, total), e = mla_cu_at(cu, i + 1, total);
-    const long long n = (long long)mla_len(in, cap, i) + (e > s ? e - s : 0u);
-    out[i] = n < cap ? (int)n : cap;
 }
 
 hipError_t mla_append_dispatch(const ::fa_mla_append_desc* d)
@@ -100,14 +62,9 @@ hipError_t mla_append_dispatch(const ::fa_mla_append_desc* d)
     if (!mla_geometry(d->block_table, d->Ncap, d->num_pages, d->page_size, d->max_pages, cap, lg_page)) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(d->Cnew) | reinterpret_cast<uintptr_t>(d->C)) & 15u) return hipErrorInvalidValue;
     if (d->new_stride_t < FA_MLA_DQK || d->new_stride_t % 8) return hipErrorInvalidValue;
-    const uintptr_t cu = reinterpret_cast<uintptr_t>(d->cu_seqlens_new), cu_bytes = ((uintptr_t)d->B + 1) * sizeof(int);
-    const uintptr_t len_bytes = (uintptr_t)d->B * sizeof(int);
-    if ((cu | reinterpret_cast<uintptr_t>(d->seqlens_k) | reinterpret_cast<uintptr_t>(d->seqlens_out)) & 3u) return hipErrorInvalidValue;
-    if (d->seqlens_out) {
-        const uintptr_t out = reinterpret_cast<uintptr_t>(d->seqlens_out), in = reinterpret_cast<uintptr_t>(d->seqlens_k);
-        if (cu < out + len_bytes && out < cu + cu_bytes) return hipErrorInvalidValue;   // read by the lengths kernel while it writes
-        if (d->seqlens_k && in != out && in < out + len_bytes && out < in + len_bytes) return hipErrorInvalidValue;
-    }
+    if ((reinterpret_cast<uintptr_t>(d->cu_seqlens_new) | reinterpret_cast<uintptr_t>(d->seqlens_k) | reinterpret_cast<uintptr_t>(d->seqlens_out)) & 3u)
+        return hipErrorInvalidValue;
+    if (!lens_out_ok(d->seqlens_k, d->seqlens_out, d->B, d->cu_seqlens_new, ((size_t)d->B + 1) * sizeof(int))) return hipErrorInvalidValue;
     const bool paged = d->block_table != nullptr;
     const unsigned chunks = (unsigned)d->total_new * kMlaChunks;
     const MlaAppendDev a = {static_cast<const u32x4*>(d->Cnew), static_cast<char*>(d->C), d->cu_seqlens_new, d->seqlens_k, d->block_table,
@@ -117,11 +74,8 @@ hipError_t mla_append_dispatch(const ::fa_mla_append_desc* d)
     const dim3 grid((chunks + kMlaAppendThreads - 1) / kMlaAppendThreads), block(kMlaAppendThreads);
     if (paged) FA_LAUNCH(fa_mla_append_kernel<true>, grid, block, 0, stream, a);
     else FA_LAUNCH(fa_mla_append_kernel<false>, grid, block, 0, stream, a);
-    hipError_t e = launch_status();
-    if (e != hipSuccess || !d->seqlens_out) return e;
-    FA_LAUNCH(fa_mla_append_lens_kernel, dim3(((unsigned)d->B + kMlaAppendThreads - 1) / kMlaAppendThreads), block, 0, stream, d->seqlens_k,
-              d->cu_seqlens_new, d->seqlens_out, d->B, d->total_new, cap);
-    return launch_status();
+    const hipError_t e = launch_status();
+    return e != hipSuccess ? e : kvappend_lens(d->seqlens_k, nullptr, d->cu_seqlens_new, d->seqlens_out, d->B, d->total_new, cap, stream);
 }
 
 }  // namespace fa

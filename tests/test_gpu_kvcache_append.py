@@ -356,3 +356,61 @@ def test_page_addresses_are_64_bit(fa, torch_cuda):
         for page in (target - 1, target + 1, alias, 3, 0, num_pages - 1):
             assert int(torch.count_nonzero(raw[page])) == 0, page
         assert int(torch.count_nonzero(pool.view(torch.int64))) == d // 4   # the whole pool: nothing else anywhere
+
+
+# ---- 7. the one lengths kernel, past one block ------------------------------------------------------------------------------------
+LENS_B, LENS_CAP, LENS_NNEW, LENS_D = 257, 8, 2, 64
+LENS_IN = np.array([(-3, 0, 5, 7, 8, 100)[b % 6] for b in range(LENS_B)], dtype=np.int64)
+LENS_CNT = np.array([(-1, 0, 1, 2, 9)[b % 5] for b in range(LENS_B)], dtype=np.int64)
+
+
+@pytest.mark.parametrize("entry", ["flat", "seqlens_new", "varlen", "mla"])
+def test_lengths_past_one_block(fa, torch_cuda, entry):
+    """B = 257: the lengths kernel that serves the flat append, the append with seqlens_new, fa_kvcache_append_varlen and fa_mla_append
+    runs a second 256-thread block with one live thread.  Lengths (-3, 0, 5, 7, 8, 100) and counts (-1, 0, 1, 2, 9) cycle with
+    coprime periods, capacity 8, Nnew 2: the lengths out EQUAL minimum(clip(L, 0, 8) + m, 8), into a separate buffer and in place, and
+    the whole cache -- sequence 256 named -- is the source rows at their slots and untouched elsewhere, bit for bit."""
+    torch = torch_cuda
+    Bn, cap, nnew, d = LENS_B, LENS_CAP, LENS_NNEW, LENS_D
+    width = 576 if entry == "mla" else d
+    start = np.clip(LENS_IN, 0, cap)
+    m = np.full(Bn, nnew) if entry == "flat" else np.clip(LENS_CNT, 0, nnew)
+    want_lens = np.minimum(start + m, cap)
+    assert want_lens[256] == cap and len(set(want_lens.tolist())) >= 3   # several lengths, and the last one at the capacity
+    cu = np.concatenate([[0], np.cumsum(np.clip(LENS_CNT, 0, nnew))])
+    packed = entry in ("varlen", "mla")
+    k0, v0 = ai.random_bytes((Bn, 1, cap, width), 2, 71), ai.random_bytes((Bn, 1, cap, width), 2, 72)
+    src_shape = (int(cu[-1]), 1, width) if packed else (Bn, 1, nnew, width)
+    k_new, v_new = ai.random_bytes(src_shape, 2, 73), ai.random_bytes(src_shape, 2, 74)
+    want_k, want_v = k0.copy(), v0.copy()
+    for b in range(Bn):
+        for i in range(int(m[b])):
+            p = int(start[b]) + i
+            if p < cap:
+                want_k[b, 0, p] = k_new[cu[b] + i, 0] if packed else k_new[b, 0, i]
+                want_v[b, 0, p] = v_new[cu[b] + i, 0] if packed else v_new[b, 0, i]
+    assert not np.array_equal(want_k, k0) and np.array_equal(want_k[256], k0[256])   # sequence 256 is full: 256 % 6 == 4, L = 8
+    dk_new, dv_new = cm.dev16(torch, k_new, 0), cm.dev16(torch, v_new, 0)
+    dcu, dcnt = _ints(torch, cu), _ints(torch, LENS_CNT)
+    for mode in ("separate", "in place"):
+        dk, dv = cm.dev16(torch, k0, 0), cm.dev16(torch, v0, 0)
+        dlens = _ints(torch, LENS_IN)
+        out = torch.full((Bn,), -7, dtype=torch.int32, device="cuda") if mode == "separate" else dlens
+        if entry == "flat":
+            fa.fa_kvcache_append(dk_new, dv_new, dk, dv, cache_seqlens=dlens, seqlens_out=out)
+        elif entry == "seqlens_new":
+            fa.fa_kvcache_append(dk_new, dv_new, dk, dv, cache_seqlens=dlens, seqlens_out=out, seqlens_new=dcnt)
+        elif entry == "varlen":
+            fa.fa_kvcache_append_varlen(dk_new, dv_new, dk, dv, dcu, cache_seqlens=dlens, seqlens_out=out)
+        else:
+            fa.fa_mla_append(dk_new[:, 0], dk[:, 0], dcu, cache_seqlens=dlens, seqlens_out=out)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        print(f"{entry} {mode}: lengths differing {int((got != want_lens).sum())} of {Bn}; last {int(got[256])} want {int(want_lens[256])}")
+        assert np.array_equal(got, want_lens), (entry, mode, np.nonzero(got != want_lens)[0].tolist())
+        assert mode == "in place" or dlens.tolist() == LENS_IN.tolist()
+        assert _bytes_equal(torch, dk[256], want_k[256]), f"{entry} {mode}: sequence 256 of K differs"
+        assert _bytes_equal(torch, dk, want_k), f"{entry} {mode}: K differs"
+        if entry != "mla":
+            assert _bytes_equal(torch, dv[256], want_v[256]), f"{entry} {mode}: sequence 256 of V differs"
+            assert _bytes_equal(torch, dv, want_v), f"{entry} {mode}: V differs"
