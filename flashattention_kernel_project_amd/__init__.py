@@ -43,6 +43,9 @@ from .ops import (  # noqa: F401
     fa_mla_decode,
     mla_decode_workspace_bytes,
     fa_mla_append,
+    fa_mla_decode_fp8,
+    fa_mla_append_fp8,
+    quantize_mla_fp8,
     flashattn_forward_wmma,
     flashattn_streaming_16x16_mw,
     flashattn_streaming_16x16_mw_kt,
@@ -63,7 +66,7 @@ __all__ = [
     "fa_forward_varlen_kvcache_fp8",
     "fa_kvcache_decode_varlen", "fa_kvcache_decode_varlen_fp8", "kvcache_decode_varlen_workspace_bytes", "tree_from_parents",
     "tree_accept_mask", "fa_kvcache_commit", "fa_kvcache_attend_varlen", "fa_kvcache_attend_varlen_fp8",
-    "fa_mla_decode", "mla_decode_workspace_bytes", "fa_mla_append",
+    "fa_mla_decode", "mla_decode_workspace_bytes", "fa_mla_append", "fa_mla_decode_fp8", "fa_mla_append_fp8", "quantize_mla_fp8",
     "flashattn_streaming_16x16_mw", "flashattn_streaming_16x16_mw_kt",
     "attention_flops", "attention_min_bytes", "shard_range",
 ]

@@ -280,6 +280,10 @@ def _signatures() -> dict:
         "fa_mla_decode_workspace_bytes": (sz, [C.POINTER(MlaDecodeDesc)]),
         "fa_mla_decode": (i, [C.POINTER(MlaDecodeDesc)]),
         "fa_mla_append": (i, [C.POINTER(MlaAppendDesc)]),
+        # the same on a latent cache of e4m3fn codes [.., 576 bytes]: the descriptor as it is, then c_scale (one float on the device)
+        "fa_mla_decode_fp8_workspace_bytes": (sz, [C.POINTER(MlaDecodeDesc)]),
+        "fa_mla_decode_fp8": (i, [C.POINTER(MlaDecodeDesc), vp]),
+        "fa_mla_append_fp8": (i, [C.POINTER(MlaAppendDesc), vp]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

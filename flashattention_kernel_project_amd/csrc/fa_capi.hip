@@ -318,6 +318,15 @@ FA_EXPORT int fa_kvcache_commit(const fa_kvcommit_desc* desc) { return (int)fa::
 FA_EXPORT size_t fa_mla_decode_workspace_bytes(const fa_mla_decode_desc* desc) { return fa::mla_decode_workspace_bytes(desc); }
 FA_EXPORT int fa_mla_decode(const fa_mla_decode_desc* desc) { return (int)fa::mla_decode_dispatch(desc); }
 FA_EXPORT int fa_mla_append(const fa_mla_append_desc* desc) { return (int)fa::mla_append_dispatch(desc); }
+FA_EXPORT size_t fa_mla_decode_fp8_workspace_bytes(const fa_mla_decode_desc* desc) { return fa::mla_decode_workspace_bytes(desc); }
+FA_EXPORT int fa_mla_decode_fp8(const fa_mla_decode_desc* desc, const float* c_scale)
+{
+    return (int)fa::mla_decode_fp8_dispatch(desc, c_scale);
+}
+FA_EXPORT int fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale)
+{
+    return (int)fa::mla_append_fp8_dispatch(desc, c_scale);
+}
 
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 

@@ -237,6 +237,11 @@ hipError_t kvcache_commit(const ::fa_kvcommit_desc* desc);
 hipError_t mla_decode_dispatch(const ::fa_mla_decode_desc* desc);
 size_t mla_decode_workspace_bytes(const ::fa_mla_decode_desc* desc);
 hipError_t mla_append_dispatch(const ::fa_mla_append_desc* desc);
+// fa_mla_decode_fp8 and fa_mla_append_fp8: the same checks on the same descriptors, C then addresses rows of 576 e4m3fn codes;
+// c_scale is the cache's one fp32 scale on the device (4-byte aligned), or null (1.0).  The fp8 decode kernels live in
+// fa_mla_decode_fp8.hip, the fp8 append kernels beside the copy in fa_mla_append.hip.
+hipError_t mla_decode_fp8_dispatch(const ::fa_mla_decode_desc* desc, const float* c_scale);
+hipError_t mla_append_fp8_dispatch(const ::fa_mla_append_desc* desc, const float* c_scale);
 bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);

@@ -1,361 +1,11 @@
 // fa_mla_decode.hip -- fa_mla_decode: absorbed-query attention over a latent KV cache (multi-head latent attention).  One row of 576
-// 16-bit elements per token serves all Hq heads: the logits run over the whole row, the output over its first 512 elements.  A kernel
-// of its own on the plan of the split-KV stream (fa_fwd_split_kernel.hpp), which it does not touch: the Hq heads of a sequence's
-// tokens are folded into the rows of a workgroup, lengths, cu_seqlens and the block table are read on the device, the 64-key tiles of
-// a sequence are dealt to S splits, and a private merge kernel finishes behind a split.  What is new is the tile: ONE row-major LDS
-// image of [keys][576] is read by rows for S^T = C Q^T and through ds_read_b64_tr_b16 on its first 512 columns for O^T += V^T P^T.
-// DESIGN.md section 7.22, profiles/mla_decode.txt.
-#include "../../include/fa_mi355.h"
-#include "fa_dispatch.hpp"
-#include "fa_tile.hpp"
+// 16-bit elements per token serves all Hq heads: the logits run over the whole row, the output over its first 512 elements.  The
+// kernel template, the merge kernel and the launcher are in fa_mla_decode_kernel.hpp; this unit owns the host checks and the plan of
+// both MLA decode entries and instantiates the 16-bit kernels.  fa_mla_decode_fp8 (rows of 576 e4m3fn codes) passes the same checks
+// here and launches what fa_mla_decode_fp8.hip instantiates.  DESIGN.md sections 7.22 and 7.24, profiles/mla_decode.txt.
+#include "fa_mla_decode_kernel.hpp"
 
 namespace fa {
-
-namespace mla {
-constexpr int kDqk = FA_MLA_DQK, kDv = FA_MLA_DC;
-constexpr int kW = 4;                    // waves per workgroup
-constexpr int kRowBytes = kDqk * 2;      // 1152: one latent row, in memory and in LDS
-constexpr int kChunks = kDqk / 8;        // 72 16-byte chunks per row
-constexpr int kKSteps = kDqk / 16;       // 36 steps of the 32x32x16 instruction over the reduction dimension of S^T
-constexpr int kSplitTile = 64;           // the unit the splits deal out, whatever the LDS tile is
-constexpr int kWsRow = kDv + 4;          // floats per workspace row: O^T, m, l and two of padding (rows stay 16-byte aligned)
-#ifndef FA_MLA_ROW_BLOCKS
-#define FA_MLA_ROW_BLOCKS 2              // 32-row blocks per workgroup; the other 4 / FA_MLA_ROW_BLOCKS waves of a block split the 512 columns
-#endif
-#ifndef FA_MLA_TILE
-#define FA_MLA_TILE 32                   // keys per LDS tile: 32 (two buffers of 36 KiB), or 64 (72 KiB each; spills)
-#endif
-constexpr int kRB = FA_MLA_ROW_BLOCKS, kDS = kW / kRB;
-constexpr int kRows = 32 * kRB;          // query rows per workgroup
-constexpr int kTile = FA_MLA_TILE;
-constexpr int kDBlocks = kDv / 32 / kDS; // 32-column blocks of O^T per wave
-constexpr int kGroups = kTile / 8 / kW;  // 8-row groups of a tile each wave stages
-constexpr int kGroupLoads = 8 * kChunks / 64;   // 9 16-byte loads per lane and group
-constexpr int kTileBytes = kTile * kRowBytes;
-constexpr int kLdsBytes = 2 * kTileBytes;
-static_assert(kRB * kDS == kW && kGroups >= 1 && kSplitTile % kTile == 0, "geometry");
-
-// The LDS image: row-major rows of 1152 bytes; inside every aligned group of eight 16-byte chunks the chunk index is XORed with a
-// value of the row.  1152 = 4 * 256 + 128, so consecutive rows start half a bank row apart: with x(row) below, the 16 rows one lane
-// group of a ds_read_b128 row read takes (same chunk) fall into 16 different slots, and so do the 4 rows x 4 chunks a 32-lane half
-// of a ds_read_b64_tr_b16 takes (rows 4n .. 4n+3: the row pairs differ in x's bit 2, the rows of a pair in the half bank row).
-__device__ __forceinline__ unsigned swz(unsigned row) { return (((row >> 1) & 1u) << 2) | ((row >> 2) & 3u); }
-__device__ __forceinline__ unsigned img_off(unsigned row, unsigned chunk)
-{
-    return row * kRowBytes + (((chunk & ~7u) | ((chunk & 7u) ^ swz(row))) << 4);
-}
-
-struct Dev {
-    const uint16_t* Q;
-    void* O;
-    float* lse;
-    const char* C;
-    float* ws;
-    const int *cu_q, *seqlens, *table;
-    int B, Hq, total_q, max_q, cap;
-    int max_pages, num_pages, lg_page;   // paged only
-    long long q_st, q_sh, o_st, o_sh;    // elements
-    float scale_log2e;
-    int causal, S, nqb;
-};
-}  // namespace mla
-
-constexpr float kMlaLn2 = 0.6931471805599453f;
-
-// Rows: the live rows of sequence b are (token i, head hd), i < n_b, folded as p = i * Hq + hd into row blocks of kRows; workgroup
-// (b, qb, sp) owns block qb and split sp.  A wave owns 32 rows (lane & 31) and, with kDS = 2, one half of the 512 output columns: the
-// two waves of a row block compute the same S^T and the same (m, l) from the same LDS bytes and differ in the V columns they take.
-// A lane past the live rows loads Q from past the view (zeros), takes the limit of the last live row, so that it votes for a new
-// reference maximum only where a live row votes, and stores nothing.
-// Keys: the tile's rows come through one buffer descriptor per (wave, 8-row group), 64-bit base, ending at the split's last key: rows
-// at or past it read as zeros whatever memory holds.  Eight aligned rows lie inside one page (>= 16 keys), so the page number is
-// wave-uniform; the numbers of the tile after next are fetched while the current one computes, with the entry index clamped to the
-// split's last live page.  Contiguous and paged kernels differ in that base alone: the bits are the same.
-template <typename T, bool kOutF32, bool kPartial, bool kPaged>
-__global__ __launch_bounds__(64 * mla::kW, 1)
-void fa_mla_decode_kernel(mla::Dev a)
-{
-    using namespace mla;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned sp = blockIdx.x % (unsigned)a.S, rest = blockIdx.x / (unsigned)a.S;
-    const unsigned qb = rest % (unsigned)a.nqb, b = rest / (unsigned)a.nqb;
-    const unsigned tid = threadIdx.x;
-    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lane = tid & 63u, r = lane & 31u, h = lane >> 5;
-    const unsigned rb = wave / (unsigned)kDS, dh = wave % (unsigned)kDS;
-
-    // the sequence's rows (wave-uniform): fa_forward_varlen's clamps, cut to max_q
-    const int s_tok = min(max(a.cu_q[b], 0), a.total_q);
-    const unsigned n_q = (unsigned)min(min(max(a.cu_q[b + 1], s_tok), a.total_q) - s_tok, a.max_q);
-    const unsigned live = n_q * (unsigned)a.Hq;
-    if (qb * (unsigned)kRows >= live) return;   // workgroup-uniform: no live row here (n_b = 0: the whole sequence); nothing was read
-    const unsigned nkeys = a.seqlens ? (unsigned)min(max(a.seqlens[b], 0), a.cap) : (unsigned)a.cap;
-    const unsigned chunk = (((nkeys + kSplitTile - 1) / kSplitTile + (unsigned)a.S - 1) / (unsigned)a.S) * kSplitTile;
-    const unsigned key0 = sp * chunk, key1 = min(nkeys, key0 + chunk);
-
-    // the lane's row: token i, head hd of the sequence's view of Q
-    const unsigned p_row = qb * (unsigned)kRows + rb * 32u + r;
-    const bool has_rows = qb * (unsigned)kRows + rb * 32u < live;   // wave-uniform
-    const unsigned pc = min(p_row, live - 1u), row_i = pc / (unsigned)a.Hq, row_hd = pc - row_i * (unsigned)a.Hq;
-    const unsigned qend = (unsigned)((unsigned long long)((long long)(n_q - 1) * a.q_st + (long long)(a.Hq - 1) * a.q_sh + kDqk) * 2u);
-    const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.Q + (long long)s_tok * a.q_st, qend);
-    const unsigned qoff = p_row < live ? (row_i * (unsigned)a.q_st + row_hd * (unsigned)a.q_sh) * 2u : qend;
-
-    // first key the row does NOT see, and the smallest such limit of any row of the sequence
-    unsigned lim = key1, lim_lo = key1;
-    if (a.causal) {
-        const int first = (int)nkeys - (int)n_q + 1;
-        lim = min((unsigned)max(first + (int)row_i, 0), key1);
-        lim_lo = min((unsigned)max(first, 0), key1);
-    }
-    const float c = fmaxf(fabsf(a.scale_log2e), 1.17549435e-38f);   // a scale of 0 must not meet a masked -inf as 0 * -inf
-    const unsigned q_flip = a.scale_log2e < 0.0f ? 0x80008000u : 0u;
-    u32x4 qf[kKSteps];
-#pragma unroll
-    for (int s = 0; s < kKSteps; ++s) {
-        u32x4 raw = buf_load16(rq, qoff + (16u * s + 8u * h) * 2u);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) raw[w] ^= q_flip;
-        qf[s] = raw;
-    }
-
-    // staging: group g of the tile's 8-row groups that this wave loads is group g * kW + wave; lane idx = lane + 64 p of a group is
-    // chunk idx % 72 of row idx / 72, which in memory is byte idx * 16 of the group
-    unsigned l_off[kGroupLoads];
-#pragma unroll
-    for (int p = 0; p < kGroupLoads; ++p) {
-        const unsigned idx = lane + 64u * p;
-        l_off[p] = img_off(wave * 8u + idx / (unsigned)kChunks, idx % (unsigned)kChunks);   // swz repeats every 16 rows: g adds 32 rows
-    }
-    const char* cbase = a.C;
-    if constexpr (!kPaged) cbase += (size_t)b * (unsigned)a.cap * kRowBytes;
-    u32x4 st[kGroups][kGroupLoads];
-    [[maybe_unused]] int pg[kGroups];
-    [[maybe_unused]] auto fetch_pages = [&](unsigned kv0) {
-        if constexpr (kPaged) {
-            const int* tbl = a.table + (size_t)b * (unsigned)a.max_pages;
-            const unsigned last = (key1 - 1u) >> a.lg_page;   // only called with key1 > key0
-#pragma unroll
-            for (int g = 0; g < kGroups; ++g)
-                pg[g] = __builtin_amdgcn_readfirstlane(tbl[min((kv0 + (g * kW + wave) * 8u) >> a.lg_page, last)]);
-        }
-    };
-    auto stage_load = [&](unsigned kv0) {
-#pragma unroll
-        for (int g = 0; g < kGroups; ++g) {
-            const unsigned kg = kv0 + (g * kW + wave) * 8u;               // the group's first key
-            unsigned rows = kg < key1 ? min(8u, key1 - kg) : 0u;          // its rows below the split's end
-            size_t first = kg;                                            // the row of `cbase` the group starts at
-            if constexpr (kPaged) {
-                if ((unsigned)pg[g] >= (unsigned)a.num_pages) rows = 0u;  // a bad page number: no record, every load reads 0
-                first = rows ? ((size_t)(unsigned)pg[g] << a.lg_page) + (kg & ((1u << a.lg_page) - 1u)) : 0;
-            }
-            const __amdgpu_buffer_rsrc_t rc = make_rsrc(cbase + (rows ? first : 0) * kRowBytes, rows * kRowBytes);
-#pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) st[g][p] = buf_load16_nt(rc, (lane + 64u * p) * 16u);
-        }
-    };
-    auto stage_write = [&](unsigned buf) {
-#pragma unroll
-        for (int g = 0; g < kGroups; ++g)
-#pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) lds_write16(smem, buf * kTileBytes + g * (kW * 8 * kRowBytes) + l_off[p], st[g][p]);
-    };
-
-    // row reads of S^T = C Q^T: lane (r, h) takes chunk 2 ks + h of key kb * 32 + r; the XOR touches the chunk's low three bits
-    unsigned k_rd[4];
-#pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) k_rd[k4] = r * kRowBytes + (((2u * k4 + h) ^ swz(r)) << 4);
-    // transposed reads of O^T += V^T P^T: lane 4 vq + vp of a 16-lane group supplies row vq, columns 4 vp .. 4 vp + 3 of the block of
-    // keys 16 q4 + 8 jj + 4 h .. + 3 and columns 32 db + 16 vg .. + 15; the block's two chunks are looked up one by one, since the XOR
-    // may swap them
-    const unsigned i16 = lane & 15u, vq = i16 >> 2, vp = i16 & 3u, vg = (lane >> 4) & 1u;
-    unsigned v_rd[2][2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            const unsigned row = 8u * jj + 4u * h + vq;
-            v_rd[jj][par] = row * kRowBytes + (((4u * par + 2u * vg + (vp >> 1)) ^ swz(row)) << 4) + (vp & 1u) * 8u +
-                            dh * (unsigned)(kDBlocks * 64);
-        }
-
-    f32x16 o[kDBlocks];
-    f32x16 zero16;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) zero16[i] = 0.0f;
-#pragma unroll
-    for (int db = 0; db < kDBlocks; ++db) o[db] = zero16;
-    float m_ref = -INFINITY, l_part = 0.0f;
-
-    // 0 for a split that lies past the sequence's last key: it touches no table entry and no cache row
-    const int ntiles = key0 >= nkeys ? 0 : (int)((key1 - key0 + kTile - 1) / kTile);
-    if (ntiles > 0) {   // workgroup-uniform
-        fetch_pages(key0);
-        stage_load(key0);
-        fetch_pages(key0 + (unsigned)min(1, ntiles - 1) * kTile);
-        stage_write(0);
-        __syncthreads();
-    }
-    for (int t = 0; t < ntiles; ++t) {
-        const unsigned cur = t & 1u;
-        const char* kbuf = smem + cur * kTileBytes;
-        const unsigned kv0 = key0 + (unsigned)t * kTile;
-        if (t + 1 < ntiles) stage_load(kv0 + kTile);
-        fetch_pages(key0 + (unsigned)min(t + 2, ntiles - 1) * kTile);   // a last tile re-reads its own entries
-
-        if (has_rows) {   // a wave without a live row only stages
-            constexpr int kKB = kTile / 32;
-            f32x16 s[kKB];
-#pragma unroll
-            for (int ks = 0; ks < kKSteps; ++ks)
-#pragma unroll
-                for (int kb = 0; kb < kKB; ++kb) {
-                    const u32x4 kf = lds_read16(kbuf, kb * 32u * kRowBytes + (unsigned)(ks >> 2) * 128u + k_rd[ks & 3]);
-                    s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
-                }
-            if (kv0 + kTile > lim_lo) {   // keys past the row's limit (without causal: past the split's end) -> -inf
-#pragma unroll
-                for (int kb = 0; kb < kKB; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const unsigned key = kv0 + (unsigned)(kb * 32 + (i & 3) + 8 * (i >> 2)) + 4u * h;
-                        if (key >= lim) s[kb][i] = -INFINITY;
-                    }
-            }
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kb = 0; kb < kKB; ++kb)
-#pragma unroll
-                for (int e = 0; e < 16; e += 2) tmax = max3(tmax, s[kb][e], s[kb][e + 1]);
-            tmax *= c;
-            // the lazy reference maximum of the split stream: m_ref stays at -inf until the row meets a key, moves only when some
-            // row's tile maximum exceeds it by more than kThr (P <= 2^8 fits fp16), and a row at -inf takes alpha = 0
-            if (__any(tmax > m_ref + kThr)) {
-                const float mx = fmaxf(tmax, swap_halves(tmax));
-                const float m_new = fmaxf(mx, m_ref);
-                const float alpha = m_ref == -INFINITY ? 0.0f : fast_exp2(m_ref - m_new);
-                m_ref = m_new;
-#pragma unroll
-                for (int db = 0; db < kDBlocks; ++db)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
-                l_part *= alpha;
-            }
-            u32x4 pk[2 * kKB];
-            float ls0 = 0.0f, ls1 = 0.0f;
-            const float neg_m = m_ref == -INFINITY ? 0.0f : -m_ref;   // every s of such a row is -inf: p = 2^(-inf + 0) = 0
-#pragma unroll
-            for (int q4 = 0; q4 < 2 * kKB; ++q4) {
-                const int kb = q4 >> 1, b8 = (q4 & 1) * 8;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const float p0 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w], c, neg_m));
-                    const float p1 = fast_exp2(__builtin_fmaf(s[kb][b8 + 2 * w + 1], c, neg_m));
-                    pk[q4][w] = T::pack2(p0, p1);
-                    if (w & 1) ls1 = T::sum2(pk[q4][w], ls1);   // sums of the ROUNDED weights (fa_common.hpp)
-                    else ls0 = T::sum2(pk[q4][w], ls0);
-                }
-            }
-            l_part += ls0 + ls1;
-#pragma unroll
-            for (int q4 = 0; q4 < 2 * kKB; ++q4)
-#pragma unroll
-                for (int db = 0; db < kDBlocks; ++db) {
-                    u32x4 vf;
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const u32x2 half = lds_read_tr8(kbuf, q4 * 16u * kRowBytes + (unsigned)(db >> 1) * 128u + v_rd[jj][db & 1]);
-                        vf[2 * jj] = half[0];
-                        vf[2 * jj + 1] = half[1];
-                    }
-                    o[db] = T::mfma32(vf, pk[q4], o[db]);
-                }
-        }
-        if (t + 1 < ntiles) stage_write(cur ^ 1u);
-        __syncthreads();
-    }
-
-    const float l = l_part + swap_halves(l_part);
-    if constexpr (kPartial) {
-        // workspace row ((b, sp), p): 512 floats of O^T (unnormalised), then m (log2 units), then l; dead rows of the block are
-        // written too (the workspace holds nqb * kRows rows per (b, sp)) and never read
-        float* row = a.ws + (((size_t)b * (unsigned)a.S + sp) * ((size_t)a.nqb * kRows) + p_row) * kWsRow;
-        if (has_rows) {
-#pragma unroll
-            for (int db = 0; db < kDBlocks; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const unsigned col = (dh * kDBlocks + db) * 32u + 8u * g + 4u * h;
-                    const f32x4 v = {o[db][4 * g], o[db][4 * g + 1], o[db][4 * g + 2], o[db][4 * g + 3]};
-                    *reinterpret_cast<f32x4*>(row + col) = v;
-                }
-            if (h == 0 && dh == 0) *reinterpret_cast<f32x2*>(row + kDv) = f32x2{m_ref, l};
-        }
-    } else {
-        const float inv = l == 0.0f ? 0.0f : 1.0f / l;   // a row without a key: O = 0
-        const bool row_live = p_row < live;
-        if (a.lse && h == 0 && dh == 0 && row_live)
-            a.lse[(size_t)row_hd * (size_t)a.total_q + (size_t)s_tok + row_i] = l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kMlaLn2;
-        constexpr unsigned es = kOutF32 ? 4u : 2u;
-        const unsigned oend = (unsigned)((unsigned long long)((long long)(n_q - 1) * a.o_st + (long long)(a.Hq - 1) * a.o_sh + kDv) * es);
-        const __amdgpu_buffer_rsrc_t ro = make_rsrc(static_cast<char*>(a.O) + (long long)s_tok * a.o_st * (long long)es, oend);
-        const unsigned ooff = row_live ? (row_i * (unsigned)a.o_st + row_hd * (unsigned)a.o_sh) * es : oend;
-#pragma unroll
-        for (int db = 0; db < kDBlocks; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const unsigned col = (dh * kDBlocks + db) * 32u + 8u * g + 4u * h;
-                const float x0 = o[db][4 * g] * inv, x1 = o[db][4 * g + 1] * inv, x2 = o[db][4 * g + 2] * inv, x3 = o[db][4 * g + 3] * inv;
-                if constexpr (kOutF32) {
-                    const f32x4 v = {x0, x1, x2, x3};
-                    buf_store16(ro, ooff + col * 4u, __builtin_bit_cast(u32x4, v));
-                } else {
-                    buf_store8(ro, ooff + col * 2u, u32x2{T::pack2(x0, x1), T::pack2(x2, x3)});
-                }
-            }
-    }
-}
-
-// The merge behind a split: one workgroup of 128 threads per padded row (b, token i < max_q, head hd), a thread per 4 output columns.
-// A row with i >= n_b returns without writing: no token of no sequence is written.  A partial with m = -inf (a split without a
-// visible key) takes the weight 0; a row of such partials is O = 0, lse = -inf.
-template <typename T, bool kOutF32>
-__global__ __launch_bounds__(128)
-void fa_mla_merge_kernel(mla::Dev a)
-{
-    using namespace mla;
-    const unsigned per_seq = (unsigned)a.max_q * (unsigned)a.Hq;
-    const unsigned b = blockIdx.x / per_seq, p = blockIdx.x % per_seq;
-    const unsigned i = p / (unsigned)a.Hq, hd = p - i * (unsigned)a.Hq;
-    const int s_tok = min(max(a.cu_q[b], 0), a.total_q);
-    const unsigned n_q = (unsigned)min(min(max(a.cu_q[b + 1], s_tok), a.total_q) - s_tok, a.max_q);
-    if (i >= n_q) return;
-    const size_t stride_s = (size_t)a.nqb * kRows * kWsRow;
-    const float* base = a.ws + (size_t)b * (unsigned)a.S * stride_s + (size_t)p * kWsRow;
-    float M = -INFINITY;
-    for (int s = 0; s < a.S; ++s) M = fmaxf(M, base[(size_t)s * stride_s + kDv]);
-    float L = 0.0f;
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    const unsigned c4 = threadIdx.x * 4u;
-#pragma unroll 4
-    for (int s = 0; s < a.S; ++s) {
-        const float* row = base + (size_t)s * stride_s;
-        const float m = row[kDv];
-        const float w = m == -INFINITY ? 0.0f : fast_exp2(m - M);
-        L += row[kDv + 1] * w;
-        acc += *reinterpret_cast<const f32x4*>(row + c4) * w;
-    }
-    const float inv = L == 0.0f ? 0.0f : 1.0f / L;
-    const size_t tok = (size_t)s_tok + i;
-    if (a.lse && threadIdx.x == 0) a.lse[(size_t)hd * (size_t)a.total_q + tok] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kMlaLn2;
-    const size_t off = tok * (size_t)a.o_st + (size_t)hd * (size_t)a.o_sh + c4;
-    if constexpr (kOutF32) {
-        *reinterpret_cast<f32x4*>(static_cast<float*>(a.O) + off) = acc * inv;
-    } else {
-        *reinterpret_cast<u32x2*>(static_cast<uint16_t*>(a.O) + off) = u32x2{T::pack2(acc[0] * inv, acc[1] * inv), T::pack2(acc[2] * inv, acc[3] * inv)};
-    }
-}
 
 // capacity and page geometry of a latent cache, shared with fa_mla_append: false for what both entries refuse
 bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page)
@@ -437,20 +87,22 @@ size_t mla_ws_bytes(const ::fa_mla_decode_desc* d, const MlaPlan& p)
     return p.S <= 1 ? 0 : (size_t)d->B * p.S * p.nqb * mla::kRows * mla::kWsRow * sizeof(float);
 }
 
-template <typename T, bool kOutF32>
-hipError_t mla_launch(const mla::Dev& a, bool paged, hipStream_t stream)
+// both entries: the checks, then the kernels of the cache's element (c_scale is looked at with fp8 only)
+hipError_t mla_decode_any(const ::fa_mla_decode_desc* d, bool fp8, const float* c_scale)
 {
-    const dim3 grid((unsigned)a.B * (unsigned)a.nqb * (unsigned)a.S), block(64 * mla::kW);
-    void (*kernel)(mla::Dev);
-    if (a.S > 1) kernel = paged ? fa_mla_decode_kernel<T, kOutF32, true, true> : fa_mla_decode_kernel<T, kOutF32, true, false>;
-    else kernel = paged ? fa_mla_decode_kernel<T, kOutF32, false, true> : fa_mla_decode_kernel<T, kOutF32, false, false>;
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), mla::kLdsBytes);
-    if (e != hipSuccess) return e;
-    FA_LAUNCH(kernel, grid, block, (size_t)mla::kLdsBytes, stream, a);
-    e = launch_status();
-    if (e != hipSuccess || a.S <= 1) return e;
-    FA_LAUNCH((fa_mla_merge_kernel<T, kOutF32>), dim3((unsigned)a.B * (unsigned)a.max_q * (unsigned)a.Hq), dim3(128), 0, stream, a);
-    return launch_status();
+    MlaPlan p;
+    if (!mla_plan(d, p)) return hipErrorInvalidValue;
+    if (fp8 && (reinterpret_cast<uintptr_t>(c_scale) & 3u)) return hipErrorInvalidValue;
+    const size_t need = mla_ws_bytes(d, p);
+    if (need && (!d->workspace || d->workspace_bytes < need || (reinterpret_cast<uintptr_t>(d->workspace) & 15u)))
+        return hipErrorInvalidValue;
+    const mla::Dev a = {static_cast<const uint16_t*>(d->Q), d->O, d->lse, static_cast<const char*>(d->C), static_cast<float*>(d->workspace),
+                        d->cu_seqlens_q, d->seqlens_k, d->block_table, d->B, d->Hq, d->total_q, d->max_q, p.cap,
+                        p.paged ? d->max_pages : 0, p.paged ? d->num_pages : 0, p.lg_page, d->q_stride_t, d->q_stride_h, d->o_stride_t,
+                        d->o_stride_h, host_scale_log2e(d->scale), d->causal, p.S, p.nqb, fp8 ? c_scale : nullptr};
+    hipStream_t stream = static_cast<hipStream_t>(d->stream);
+    const bool bf16 = d->in_dtype == FA_DTYPE_BF16, f32 = d->out_dtype == FA_OUT_F32;
+    return fp8 ? mla_launch_fp8(a, bf16, f32, p.paged, stream) : mla_launch_typed<false>(a, bf16, f32, p.paged, stream);
 }
 
 }  // namespace
@@ -461,21 +113,8 @@ size_t mla_decode_workspace_bytes(const ::fa_mla_decode_desc* d)
     return mla_plan(d, p) ? mla_ws_bytes(d, p) : 0;
 }
 
-hipError_t mla_decode_dispatch(const ::fa_mla_decode_desc* d)
-{
-    MlaPlan p;
-    if (!mla_plan(d, p)) return hipErrorInvalidValue;
-    const size_t need = mla_ws_bytes(d, p);
-    if (need && (!d->workspace || d->workspace_bytes < need || (reinterpret_cast<uintptr_t>(d->workspace) & 15u)))
-        return hipErrorInvalidValue;
-    const mla::Dev a = {static_cast<const uint16_t*>(d->Q), d->O, d->lse, static_cast<const char*>(d->C), static_cast<float*>(d->workspace),
-                        d->cu_seqlens_q, d->seqlens_k, d->block_table, d->B, d->Hq, d->total_q, d->max_q, p.cap,
-                        p.paged ? d->max_pages : 0, p.paged ? d->num_pages : 0, p.lg_page, d->q_stride_t, d->q_stride_h, d->o_stride_t,
-                        d->o_stride_h, host_scale_log2e(d->scale), d->causal, p.S, p.nqb};
-    hipStream_t stream = static_cast<hipStream_t>(d->stream);
-    const bool f32 = d->out_dtype == FA_OUT_F32;
-    if (d->in_dtype == FA_DTYPE_BF16) return f32 ? mla_launch<BF16, true>(a, p.paged, stream) : mla_launch<BF16, false>(a, p.paged, stream);
-    return f32 ? mla_launch<F16, true>(a, p.paged, stream) : mla_launch<F16, false>(a, p.paged, stream);
-}
+hipError_t mla_decode_dispatch(const ::fa_mla_decode_desc* d) { return mla_decode_any(d, false, nullptr); }
+
+hipError_t mla_decode_fp8_dispatch(const ::fa_mla_decode_desc* d, const float* c_scale) { return mla_decode_any(d, true, c_scale); }
 
 }  // namespace fa

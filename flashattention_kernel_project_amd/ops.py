@@ -1403,12 +1403,13 @@ def fa_kvcache_commit(k_cache, v_cache, accept_mask, cache_seqlens=None, seqlens
 
 def _mla_cache(c_cache, block_table, B, dtype, name="c_cache"):
     """(Ncap, num_pages, page_size, max_pages, table pointer) of a latent cache [B,Ncap,576] or, with block_table, a pool
-    [num_pages,page_size,576]; shapes and dtypes are judged before anything needs a device"""
+    [num_pages,page_size,576]; shapes and dtypes are judged before anything needs a device.  The _fp8 entries judge their cache's
+    dtype first (_mla_fp8_cache) and pass dtype = torch.float8_e4m3fn."""
     import torch
     if not isinstance(c_cache, torch.Tensor) or c_cache.dim() != 3 or c_cache.shape[2] != capi.MLA_DQK or c_cache.numel() == 0:
         raise ValueError(f"{name} must be a latent cache [B,Ncap,{capi.MLA_DQK}] or, with block_table, a pool [num_pages,page_size,{capi.MLA_DQK}]")
     if c_cache.dtype != dtype:
-        raise ValueError(f"{name} has dtype {c_cache.dtype}, expected {dtype} (an fp8 latent cache is not part of the MLA entries)")
+        raise ValueError(f"{name} has dtype {c_cache.dtype}, expected {dtype} (an fp8 latent cache goes to fa_mla_decode_fp8 / fa_mla_append_fp8)")
     if block_table is None:
         if c_cache.shape[0] != B:
             raise ValueError(f"{name} holds {c_cache.shape[0]} sequences, the cu_seqlens vector {B}")
@@ -1420,6 +1421,20 @@ def _mla_cache(c_cache, block_table, B, dtype, name="c_cache"):
     if block_table.shape[1] <= 0:
         raise ValueError("block_table must have at least one column")
     return 0, c_cache.shape[0], page_size, block_table.shape[1], table_ptr
+
+
+def _mla_fp8_cache(c_cache, name="c_cache"):
+    """the first judgement of the _fp8 MLA entries: the cache's element type"""
+    import torch
+    if not isinstance(c_cache, torch.Tensor) or c_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{name}: {_FP8_CACHE} (got {getattr(c_cache, 'dtype', type(c_cache).__name__)})")
+
+
+def _mla_scale_check(c_scale):
+    """c_scale of an fp8 latent cache: float32 [1], or None (1.0); judged with the cache, before anything needs a device"""
+    import torch
+    if c_scale is not None and (not isinstance(c_scale, torch.Tensor) or c_scale.dtype != torch.float32 or tuple(c_scale.shape) != (1,)):
+        raise ValueError("c_scale must be a float32 device tensor of shape [1]: the cache's one scale")
 
 
 def _cu_vector(cu, name: str) -> int:
@@ -1434,7 +1449,7 @@ def _cu_vector(cu, name: str) -> int:
 
 def mla_decode_workspace_bytes(B: int, Hq: int, max_seqlen_q: int, Ncap: int = 0, max_pages: int = 0, page_size: int = 0,
                                num_splits: int = 0) -> int:
-    """Workspace of fa_mla_decode (fa_mla_decode_workspace_bytes): a contiguous cache gives Ncap, a paged one max_pages and page_size;
+    """Workspace of fa_mla_decode and of fa_mla_decode_fp8, which are equal (fa_mla_decode_workspace_bytes): a contiguous cache gives Ncap, a paged one max_pages and page_size;
     num_splits as in the call (0: the library's choice).  From host integers alone; 0 when one split is chosen, and 0 for a shape
     the call refuses."""
     desc = capi.new_desc(capi.MlaDecodeDesc)
@@ -1473,7 +1488,32 @@ def fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, bl
     lse = -inf there; with `out` (any token and head strides) and `lse` (contiguous; implies return_lse) they keep what they held.
     workspace: optional uint8 device tensor of at least mla_decode_workspace_bytes(...).
     Nothing is read on the host: fa_mla_append(seqlens_out=lens) then this call, captured once, serves every step of the same total_q.
-    Not here: an fp8 latent cache, window, soft-cap, sinks, a tree mask, other latent widths."""
+    An fp8 latent cache: fa_mla_decode_fp8.  Not here: window, soft-cap, sinks, a tree mask, other latent widths."""
+    return _mla_decode("fa_mla_decode", None, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits,
+                       return_lse, out, workspace, out_dtype, stream, lse)
+
+
+def fa_mla_decode_fp8(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, c_scale=None,
+                      scale: float | None = None, causal: bool = True, num_splits: int = 0, return_lse: bool = False, out=None,
+                      workspace=None, out_dtype=None, stream=None, lse=None):
+    """fa_mla_decode against an fp8 latent cache (fa_mla_decode_fp8): c_cache is torch.float8_e4m3fn, [B, Ncap, 576] or with
+    block_table a pool [num_pages, page_size, 576] -- one row of 576 BYTES per token, 512 compressed-KV codes then 64 rotary codes --
+    and c_scale is the cache's ONE scale, float32 [1] on the device (read there: a captured call follows it), or None (1.0); an
+    element is code * c_scale, c_scale finite and > 0 (quantize_mla_fp8 makes both).  q names the arithmetic's type: the codes are
+    widened exactly to it on their way into LDS, and everything else -- rows, clamps, masks, splits (the same num_splits = 0 choice
+    and workspace), keywords and results -- is fa_mla_decode's: s = (scale * c_scale) * q . code, o = c_scale * softmax(s) . code[:512].
+    Rows at or past a sequence's length and pages no key lies in may hold NaN codes.  With c_scale None the result has the bits of
+    fa_mla_decode on the widened cache.
+    Not here: per-token or per-128-element scales, a 16-bit rotary tail (656-byte rows), an fp8 q, fp8 matrix instructions."""
+    _mla_fp8_cache(c_cache)
+    _mla_scale_check(c_scale)
+    return _mla_decode("fa_mla_decode_fp8", (c_scale,), q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
+                       num_splits, return_lse, out, workspace, out_dtype, stream, lse)
+
+
+def _mla_decode(entry, fp8, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits, return_lse, out,
+                workspace, out_dtype, stream, lse):
+    """Both MLA decode front ends: fp8 is None (a cache of q's dtype) or (c_scale,) of a cache of e4m3fn codes."""
     import torch
     if not isinstance(q, torch.Tensor) or q.dim() != 3 or q.shape[2] != capi.MLA_DQK:
         raise ValueError(f"q must be a packed tensor (total_q, Hq, {capi.MLA_DQK}): the absorbed queries")
@@ -1487,7 +1527,8 @@ def fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, bl
     if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
         raise ValueError("num_splits must be an int >= 0 (0: chosen by the library)")
     B = _cu_vector(cu_seqlens_q, "cu_seqlens_q")
-    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, q.dtype)
+    c_dtype = q.dtype if fp8 is None else torch.float8_e4m3fn
+    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, c_dtype)
     if cache_seqlens is not None and (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32
                                       or cache_seqlens.shape != (B,)):
         raise ValueError("cache_seqlens must be an int32 device tensor of B entries")
@@ -1495,7 +1536,8 @@ def fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, bl
     for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
-    c_ptr = _dev_ptr(c_cache, "c_cache", (q.dtype,))
+    c_ptr = _dev_ptr(c_cache, "c_cache", (c_dtype,))
+    scale_ptr = None if fp8 is None or fp8[0] is None else _dev_ptr(fp8[0], "c_scale", (torch.float32,))
     lens_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
     if out_dtype is None:
         out_dtype = torch.float32 if out is None else out.dtype
@@ -1525,9 +1567,10 @@ def fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, bl
               o_stride_t=ot, o_stride_h=oh, scale=float(capi.MLA_DQK ** -0.5 if scale is None else scale), causal=int(bool(causal)),
               num_splits=num_splits, in_dtype=_in_dt(q.dtype), out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len,
               stream=_stream_ptr(stream))
-    with torch.cuda.device(_one_device(q, c_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, workspace)):
-        code = capi.lib().fa_mla_decode(desc)
-    capi.check("fa_mla_decode", code)
+    with torch.cuda.device(_one_device(q, c_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, workspace,
+                                       None if fp8 is None else fp8[0])):
+        code = capi.lib().fa_mla_decode(desc) if fp8 is None else capi.lib().fa_mla_decode_fp8(desc, scale_ptr)
+    capi.check(entry, code)
     return (out, lse) if return_lse else out
 
 
@@ -1539,6 +1582,43 @@ def fa_mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens=None, seqlens_ou
     (None: 0 for all).  A token at or past the capacity is dropped; a table entry outside the pool skips the write.  No rotary here.
     seqlens_out: None, cache_seqlens itself, or a disjoint int32 [B] tensor: min(L_b + m_b, capacity), by a second kernel behind the
     copy.  Nothing is read on the host."""
+    _mla_append("fa_mla_append", None, c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream)
+
+
+def fa_mla_append_fp8(c_new, c_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None, c_scale=None,
+                      stream=None) -> None:
+    """fa_mla_append into an fp8 latent cache (fa_mla_append_fp8): c_cache is torch.float8_e4m3fn ([B,Ncap,576] or the pool behind
+    block_table), c_scale its one scale, float32 [1] on the device, or None (1.0).  Token i of sequence b is written to slot L_b + i
+    as the 576 codes of c_new / c_scale: exact widening to fp32, IEEE division, clamp to +-448, round to nearest even, NaN -> 0x7F --
+    the codes quantize_mla_fp8(c_new, c_scale) gives.  Everything else is fa_mla_append's."""
+    _mla_fp8_cache(c_cache)
+    _mla_scale_check(c_scale)
+    _mla_append("fa_mla_append_fp8", (c_scale,), c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream)
+
+
+def quantize_mla_fp8(c, scale=None):
+    """c [..., 576] (a latent cache, a pool or a step's rows), any float type, CPU or GPU -> (c8 torch.float8_e4m3fn of c's shape,
+    scale float32 [1]) with c ~= c8 * scale: the cache's ONE scale, amax / 448 (1.0 for zeros), or the given `scale` (float32 [1] on
+    c's device, finite and > 0), returned as it is.  The quotient is clamped to +-448 before the conversion (torch's does not
+    saturate) and a NaN becomes the code 0x7F: the codes are those fa_mla_append_fp8 writes for the same scale."""
+    import torch
+    if not isinstance(c, torch.Tensor) or c.dim() < 1 or c.shape[-1] != capi.MLA_DQK or not c.is_floating_point():
+        raise ValueError(f"c must be a float tensor [..., {capi.MLA_DQK}]")
+    cf = c.float()
+    if scale is None:
+        amax = cf.abs().amax().reshape(1) if cf.numel() else cf.new_zeros(1)
+        scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    elif not isinstance(scale, torch.Tensor) or tuple(scale.shape) != (1,) or scale.dtype != torch.float32 or scale.device != c.device:
+        raise ValueError("scale must be a float32 tensor of shape [1] on c's device")
+    q = cf / scale
+    nan = q != q
+    codes = torch.where(nan, torch.zeros_like(q), q).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    codes = torch.where(nan, torch.full_like(codes, 0x7F), codes)
+    return codes.view(torch.float8_e4m3fn), scale.contiguous()
+
+
+def _mla_append(entry, fp8, c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream):
+    """Both MLA append front ends: fp8 is None (a cache of c_new's dtype) or (c_scale,) of a cache of e4m3fn codes."""
     import torch
     if not isinstance(c_new, torch.Tensor) or c_new.dim() != 2 or c_new.shape[1] != capi.MLA_DQK or c_new.shape[0] <= 0:
         raise ValueError(f"c_new must be a packed tensor (total_new, {capi.MLA_DQK})")
@@ -1547,14 +1627,16 @@ def fa_mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens=None, seqlens_ou
     if c_new.stride(1) != 1:
         raise ValueError("c_new must be contiguous in its last dimension (any token stride is taken as it is)")
     B = _cu_vector(cu_seqlens_new, "cu_seqlens_new")
-    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, c_new.dtype)
+    c_dtype = c_new.dtype if fp8 is None else torch.float8_e4m3fn
+    Ncap, num_pages, page_size, max_pages, table_ptr = _mla_cache(c_cache, block_table, B, c_dtype)
     for name, t in (("cache_seqlens", cache_seqlens), ("seqlens_out", seqlens_out)):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.shape != (B,)):
             raise ValueError(f"{name} must be an int32 device tensor of shape [B] = [{B}]")
     for name, t in (("c_new", c_new), ("cu_seqlens_new", cu_seqlens_new)):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
-    c_ptr = _dev_ptr(c_cache, "c_cache", (c_new.dtype,))
+    c_ptr = _dev_ptr(c_cache, "c_cache", (c_dtype,))
+    scale_ptr = None if fp8 is None or fp8[0] is None else _dev_ptr(fp8[0], "c_scale", (torch.float32,))
     len_ptr = None if cache_seqlens is None else _dev_ptr(cache_seqlens, "cache_seqlens", (torch.int32,))
     out_ptr = None if seqlens_out is None else _dev_ptr(seqlens_out, "seqlens_out", (torch.int32,))
     desc = capi.new_desc(capi.MlaAppendDesc)
@@ -1562,9 +1644,10 @@ def fa_mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens=None, seqlens_ou
               block_table=table_ptr, B=B, total_new=c_new.shape[0], new_stride_t=c_new.stride(0) if c_new.shape[0] > 1 else capi.MLA_DQK,
               Ncap=Ncap, num_pages=num_pages, page_size=page_size, max_pages=max_pages, dtype=_in_dt(c_new.dtype),
               stream=_stream_ptr(stream))
-    with torch.cuda.device(_one_device(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table)):
-        code = capi.lib().fa_mla_append(desc)
-    capi.check("fa_mla_append", code)
+    with torch.cuda.device(_one_device(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table,
+                                       None if fp8 is None else fp8[0])):
+        code = capi.lib().fa_mla_append(desc) if fp8 is None else capi.lib().fa_mla_append_fp8(desc, scale_ptr)
+    capi.check(entry, code)
 
 
 def _streaming(fn_name: str, Q, K, V, O, num_batches: int, seq_len: int, scale: float, stream):

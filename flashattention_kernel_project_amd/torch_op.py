@@ -65,6 +65,11 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits,
                                            out_f32)
     torch.ops.fa_mi355.mla_append(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table)
+    # the same against a latent cache of e4m3fn codes (ops.fa_mla_decode_fp8, ops.fa_mla_append_fp8): c_scale, float32 [1] or None,
+    # follows block_table
+    o, lse = torch.ops.fa_mi355.mla_decode_fp8(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, c_scale, scale, causal,
+                                               num_splits, out_f32)
+    torch.ops.fa_mi355.mla_append_fp8(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, c_scale)
 """
 from __future__ import annotations
 
@@ -78,7 +83,7 @@ def register() -> None:
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
-    .attend_varlen and .attend_varlen_fp8, and .mla_decode and .mla_append."""
+    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8."""
     global _registered
     if _registered:
         return
@@ -333,26 +338,35 @@ def register() -> None:
                cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), max_new=max_new,
                stream=stream(k_cache)), lambda *args: None)
 
-    # MLA (ops.fa_mla_decode, ops.fa_mla_append): q (total_q,Hq,576) as it lies, the latent cache [B,Ncap,576] or with a block table
-    # the pool [num_pages,page_size,576]; o (total_q,Hq,512) and lse (Hq,total_q) come back as from decode_varlen
-    def mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, **kw):
-        return ops.fa_mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=cache_seqlens, block_table=block_table, **kw)
+    # MLA (ops.fa_mla_decode, ops.fa_mla_append and their _fp8 forms): q (total_q,Hq,576) as it lies, the latent cache [B,Ncap,576] or
+    # with a block table the pool [num_pages,page_size,576]; o (total_q,Hq,512) and lse (Hq,total_q) come back as from decode_varlen.
+    # One table: (suffix, what follows block_table in the schema, the front ends, the keywords made of it)
+    MLA = (("", "", ops.fa_mla_decode, ops.fa_mla_append, lambda: {}),
+           ("_fp8", "Tensor? c_scale, ", ops.fa_mla_decode_fp8, ops.fa_mla_append_fp8, lambda c_scale: dict(c_scale=opt(c_scale))))
+    for suffix, mid, decode_fn, append_fn, scale_kw in MLA:
+        def mla_decode(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, decode_fn=decode_fn, **kw):
+            return decode_fn(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=cache_seqlens, block_table=block_table, **kw)
 
-    define("mla_decode",
-           "(Tensor q, Tensor c_cache, Tensor cu_seqlens_q, int max_seqlen_q, Tensor? cache_seqlens, Tensor? block_table, float scale, "
-           "bool causal, int num_splits, bool out_f32) -> (Tensor, Tensor)", (), mla_decode, "-cc-oo",
-           lambda q, scale, causal, num_splits, out_f32: dict(scale=scale, causal=causal, num_splits=num_splits,
-                                                              out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q)),
-           lambda q, *args: (q.new_empty((q.shape[0], q.shape[1], 512), dtype=out_dtype(q, args[-1])),
-                             q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)))
+        def mla_decode_kw(q, *rest, scale_kw=scale_kw):
+            *scales, scale, causal, num_splits, out_f32 = rest
+            return dict(scale=scale, causal=causal, num_splits=num_splits, out_dtype=out_dtype(q, out_f32), return_lse=True,
+                        stream=stream(q), **scale_kw(*scales))
 
-    # the cache goes in as it is and is written in place, like the other appends'
-    define("mla_append",
-           "(Tensor c_new, Tensor(a!) c_cache, Tensor cu_seqlens_new, Tensor? cache_seqlens, Tensor(b!)? seqlens_out, "
-           "Tensor? block_table) -> ()", ("c_cache", "seqlens_out"), ops.fa_mla_append, "--c",
-           lambda c_new, cache_seqlens, seqlens_out, block_table: dict(
-               cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), stream=stream(c_new)),
-           lambda *args: None)
+        define("mla_decode" + suffix,
+               "(Tensor q, Tensor c_cache, Tensor cu_seqlens_q, int max_seqlen_q, Tensor? cache_seqlens, Tensor? block_table, " + mid +
+               "float scale, bool causal, int num_splits, bool out_f32) -> (Tensor, Tensor)", (), mla_decode, "-cc-oo", mla_decode_kw,
+               lambda q, *args: (q.new_empty((q.shape[0], q.shape[1], 512), dtype=out_dtype(q, args[-1])),
+                                 q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)))
+
+        def mla_append_kw(c_new, cache_seqlens, seqlens_out, block_table, *scales, scale_kw=scale_kw):
+            return dict(cache_seqlens=opt(cache_seqlens), seqlens_out=seqlens_out, block_table=opt(block_table), stream=stream(c_new),
+                        **scale_kw(*scales))
+
+        # the cache goes in as it is and is written in place, like the other appends'
+        define("mla_append" + suffix,
+               "(Tensor c_new, Tensor(a!) c_cache, Tensor cu_seqlens_new, Tensor? cache_seqlens, Tensor(b!)? seqlens_out, "
+               "Tensor? block_table" + (", " + mid[:-2] if mid else "") + ") -> ()", ("c_cache", "seqlens_out"), append_fn, "--c",
+               mla_append_kw, lambda *args: None)
 
     _registered = True
 

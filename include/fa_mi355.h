@@ -1034,7 +1034,7 @@ int fa_kvcache_commit(const fa_kvcommit_desc* desc);
  * 16-byte aligned; a stride that is no multiple of 8 elements, a negative head stride, q_stride_t < 576 or o_stride_t < 512; a
  * sequence's view of Q or O -- max_q tokens over the Hq heads -- beyond 2^32 - 1 bytes; with more than one split a NULL workspace or
  * one below fa_mla_decode_workspace_bytes(desc).
- * Not part of this entry: an fp8 latent cache; a sliding window, soft-cap, sinks or a tree mask; latent widths other than 512 + 64;
+ * An fp8 latent cache: fa_mla_decode_fp8 below.  Not part of this entry: a sliding window, soft-cap, sinks or a tree mask; latent widths other than 512 + 64;
  * the absorption and up-projection GEMMs (W_UK into q, W_UV out of O), which stay the caller's; a d = 512 form of
  * fa_merge_states -- the entry merges its own splits.  NOT a reference entry point. */
 #define FA_MLA_DC  512   /* compressed-KV elements of a latent row: what O is made of */
@@ -1090,6 +1090,30 @@ typedef struct fa_mla_append_desc {
     void* stream;
 } fa_mla_append_desc;
 int fa_mla_append(const fa_mla_append_desc* desc);
+
+/* The fp8 latent cache of the two MLA entries.  A cache row is 576 BYTES: one OCP e4m3fn code per element, 512 compressed-KV codes
+ * followed by 64 rotary codes; C is [B, Ncap, 576] or a pool [num_pages, page_size, 576] of bytes behind the same block table, 16-byte
+ * aligned (576 = 36 * 16 keeps every row so).  ONE fp32 scale serves the whole cache: c_scale points to one float on the device,
+ * 4-byte aligned, read on the device so that a captured call follows it; NULL is 1.0.  An element's value is decode(code) * c_scale.
+ * The caller's contract is a finite c_scale > 0 (quantize_kv_fp8's); another value gives a meaningless result and never a fault.
+ * The descriptors are the 16-bit entries': in_dtype (decode) names Q's type, dtype (append) names Cnew's.
+ * fa_mla_decode_fp8: every rule of fa_mla_decode holds word for word -- rows, clamps, the causal mask, rows without a key, tokens of
+ *   no sequence, the splits and the merge, num_splits = 0 (the SAME S as fa_mla_decode for the same descriptor; the workspace sizes are
+ *   equal), a bad live page reads as zeros, paged and contiguous results are bit-equal.  The codes are widened EXACTLY to Q's type on
+ *   their way into LDS (every e4m3fn value is a normal fp16 and bf16 number) and everything behind that is fa_mla_decode's arithmetic:
+ *     s_j = (scale * c_scale) * sum_e Q[.., e] * code_j[e]          O = c_scale * sum_j softmax(s)_j * code_j[0:512]
+ *   with lse the log-sum-exp of the s_j.  The factor is clamped after the product, so scale = 0 still gives uniform weights.  Rows at or
+ *   past L_b, and pages no key lies in, may hold the NaN codes 0x7F / 0xFF: they lie outside the buffer descriptor's range and reach
+ *   LDS as the code 0 (+0).  With c_scale NULL or 1.0 the result has the bits of fa_mla_decode on the widened cache.
+ * fa_mla_append_fp8: fa_mla_append with the store changed -- the 8 elements of a 16-byte source chunk become 8 codes of x / c_scale:
+ *   exact widening to fp32, IEEE division, clamp to +-448, round to nearest even, a NaN becomes 0x7F (the write side's quantisation,
+ *   fa_kvcache_append's).  Drops, bad table entries, rows of no sequence and seqlens_out are fa_mla_append's.
+ * Rejected: everything the 16-bit entries reject, and a c_scale that is not 4-byte aligned.
+ * Not part of these entries: per-token scales; per-128-element scales; a 16-bit rotary tail (the 656-byte row some stacks use); an
+ * fp8 Q; fp8 matrix instructions.  NOT reference entry points. */
+int    fa_mla_decode_fp8(const fa_mla_decode_desc* desc, const float* c_scale);
+size_t fa_mla_decode_fp8_workspace_bytes(const fa_mla_decode_desc* desc);   /* equals fa_mla_decode_workspace_bytes(desc) */
+int    fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
