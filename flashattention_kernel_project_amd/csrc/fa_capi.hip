@@ -348,6 +348,12 @@ FA_EXPORT int fa_kvcache_decode_varlen_ex(const fa_kvdecode_varlen_desc* desc, c
     return (int)fa::kvtree_dispatch(desc, opts);
 }
 
+FA_EXPORT size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits)
+{
+    return fa::kv256_workspace_bytes(desc, num_splits);
+}
+FA_EXPORT int fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits) { return (int)fa::kv256_dispatch(desc, num_splits); }
+
 FA_EXPORT int fa_kvcache_attend_varlen_part(const fa_kvdecode_varlen_desc* desc, int parts) { return (int)fa::kvattend_dispatch(desc, parts); }
 FA_EXPORT int fa_kvcache_attend_varlen(const fa_kvdecode_varlen_desc* desc)
 {

@@ -243,6 +243,10 @@ hipError_t mla_append_dispatch(const ::fa_mla_append_desc* desc);
 hipError_t mla_decode_fp8_dispatch(const ::fa_mla_decode_desc* desc, const float* c_scale);
 hipError_t mla_append_fp8_dispatch(const ::fa_mla_append_desc* desc, const float* c_scale);
 bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page);
+// fa_kvcache_decode_d256 (fa_fwd_kv256.hip): the checks and the one or two launches on fa_kvcache_decode_varlen's descriptor, which
+// must name d = 256; num_splits: 0 chooses, >= 1 forces
+hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
+size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

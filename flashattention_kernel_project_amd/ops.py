@@ -723,6 +723,33 @@ def fa_kvcache_attend_varlen_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqlen
                           out, workspace, stream, window, softcap, sinks, lse, scales=(k_scale, v_scale), attend=True, parts=parts)
 
 
+def fa_kvcache_decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, causal: bool = False,
+                           scale: float | None = None, window=None, softcap: float = 0.0, return_lse: bool = False, out=None,
+                           workspace=None, num_splits: int = 0, out_dtype=None, stream=None, lse=None):
+    """fa_kvcache_decode_varlen at head dimension 256 (fa_kvcache_decode_d256; the Gemma-2 / Gemma-3 head): q (total_q, Hq, 256), the
+    caches [B,Hkv,Ncap,256] or with block_table the pools [num_pages,Hkv,page_size,256], 16-bit and of q's dtype.  Every argument,
+    rule and result is fa_kvcache_decode_varlen's -- rows from cu_seqlens_q cut to max_seqlen_q, lengths read on the device, causal,
+    window (None or 0: none), softcap, tokens of no sequence never written, nothing read on the host, capture-safe -- on a kernel of its
+    own; there are no sinks, no fp8 cache and no tree mask here.  num_splits: 0 = the library's choice, >= 1 forces the split count
+    (at most the number of 64-key tiles of the capacity).  workspace: optional uint8 device tensor of at least
+    kvcache_decode_d256_workspace_bytes(...) for the same num_splits."""
+    if type(num_splits) is not int or num_splits < 0:
+        raise ValueError("num_splits must be an int >= 0 (0: the library's choice)")
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
+                          return_lse, out, workspace, stream, window, softcap, None, lse, d256=num_splits)
+
+
+def kvcache_decode_d256_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, Ncap: int = 0, max_pages: int = 0,
+                                        page_size: int = 0, window: int = 0, num_splits: int = 0) -> int:
+    """Workspace of fa_kvcache_decode_d256: a contiguous cache gives Ncap, a paged one max_pages and page_size; 0 for one split.  The
+    C function judges the whole descriptor, so the tensors it never looks at stand in as a packed (max_seqlen_q, Hkv*G, 256) pair."""
+    desc = capi.new_desc(capi.KvDecodeVarlenDesc)
+    capi.fill(desc, Q=16, O=16, K=16, V=16, cu_seqlens_q=16, block_table=16 if max_pages or page_size else None, B=B, Hkv=Hkv, G=G, d=256,
+              total_q=max(max_seqlen_q, 1), max_q=max_seqlen_q, Ncap=Ncap, max_pages=max_pages, page_size=page_size, num_pages=1,
+              q_stride_t=Hkv * G * 256, q_stride_h=256, o_stride_t=Hkv * G * 256, o_stride_h=256, window=window)
+    return int(capi.lib().fa_kvcache_decode_d256_workspace_bytes(desc, num_splits))
+
+
 def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, d: int, Ncap: int = 0, max_pages: int = 0,
                                           page_size: int = 0, window: int = 0) -> int:
     """Workspace of fa_kvcache_decode_varlen and _fp8: a contiguous cache gives Ncap, a paged one max_pages and page_size.  It is what
@@ -734,10 +761,11 @@ def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q
 
 
 def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse,
-                   out, workspace, stream, window, softcap, sinks, lse, scales=None, tree_mask=None, attend=False, parts=3):
+                   out, workspace, stream, window, softcap, sinks, lse, scales=None, tree_mask=None, attend=False, parts=3, d256=None):
     """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one; tree_mask is
     None (fa_kvcache_decode_varlen) or the words of fa_kvcache_decode_varlen_ex.  Shapes and dtypes are judged before anything needs a
-    device.  attend: the call is fa_kvcache_attend_varlen_part(desc, parts) on the same descriptor, max_seqlen_q its threshold."""
+    device.  attend: the call is fa_kvcache_attend_varlen_part(desc, parts) on the same descriptor, max_seqlen_q its threshold.
+    d256: None, or the num_splits of fa_kvcache_decode_d256, which runs on the same descriptor with d = 256."""
     import torch
     fp8 = scales is not None
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
@@ -758,7 +786,9 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.shape[3] != d:
         raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with q's d")
     Hkv = k_cache.shape[1]
-    if d not in (64, 128):
+    if d256 is not None and d != 256:
+        raise ValueError("d must be 256 (d in {64,128} is fa_kvcache_decode_varlen's)")
+    if d256 is None and d not in (64, 128):
         raise ValueError("d must be 64 or 128")
     if total_q <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or k_cache.numel() == 0:
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
@@ -829,7 +859,10 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     ot, oh = _packed_strides(out, "out")
     G = Hq // Hkv
     if workspace is None:
-        need = kvcache_decode_varlen_workspace_bytes(B, Hkv, G, max_seqlen_q, d, Ncap, max_pages, page_size, window)
+        if d256 is None:
+            need = kvcache_decode_varlen_workspace_bytes(B, Hkv, G, max_seqlen_q, d, Ncap, max_pages, page_size, window)
+        else:
+            need = kvcache_decode_d256_workspace_bytes(B, Hkv, G, max_seqlen_q, Ncap, max_pages, page_size, window, d256)
         if need:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
@@ -843,7 +876,9 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
         out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len, stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, workspace,
                                        tree_mask, *(scales or ()))):
-        if attend:
+        if d256 is not None:
+            code = capi.lib().fa_kvcache_decode_d256(desc, d256)
+        elif attend:
             code = capi.lib().fa_kvcache_attend_varlen_part(desc, parts)
         elif tree_mask is None:
             code = capi.lib().fa_kvcache_decode_varlen(desc)
@@ -851,7 +886,7 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
             opts = capi.new_desc(capi.KvDecodeTreeOpts)
             opts.tree_mask = tree_mask.data_ptr()
             code = capi.lib().fa_kvcache_decode_varlen_ex(desc, opts)
-    capi.check("fa_kvcache_attend_varlen_part" if attend else
+    capi.check("fa_kvcache_decode_d256" if d256 is not None else "fa_kvcache_attend_varlen_part" if attend else
                "fa_kvcache_decode_varlen" if tree_mask is None else "fa_kvcache_decode_varlen_ex", code)
     return (out, lse) if return_lse else out
 

@@ -70,6 +70,9 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.mla_decode_fp8(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, c_scale, scale, causal,
                                                num_splits, out_f32)
     torch.ops.fa_mi355.mla_append_fp8(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, c_scale)
+    # decode_varlen at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks; num_splits 0 = the library's choice
+    o, lse = torch.ops.fa_mi355.decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
+                                            window, softcap, num_splits, out_f32)
 """
 from __future__ import annotations
 
@@ -83,7 +86,7 @@ def register() -> None:
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
-    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8."""
+    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256."""
     global _registered
     if _registered:
         return
@@ -305,6 +308,13 @@ def register() -> None:
                           ("decode_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_varlen_fp8)):
         define(name, DECODE_VARLEN + mid + DECODE_VARLEN_TAIL, (), decode_varlen(fn), "-ccc-oo",
                decode_varlen_kw, varlen_fake)
+
+    # the same at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks, and `int num_splits` in front of out_f32
+    define("decode_d256", DECODE_VARLEN + "float scale, bool causal, int window, float softcap, int num_splits, bool out_f32) -> "
+           "(Tensor, Tensor)", (), decode_varlen(ops.fa_kvcache_decode_d256), "-ccc-oo",
+           lambda q, scale, causal, window, softcap, num_splits, out_f32: dict(
+               causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+               softcap=softcap, num_splits=num_splits), varlen_fake)
 
     # the same with a tree mask (fa_kvcache_decode_varlen_ex): `Tensor tree_mask` (int64, total_q) follows block_table; causal must be True
     def decode_varlen_tree(fn):

@@ -1115,6 +1115,32 @@ int    fa_mla_decode_fp8(const fa_mla_decode_desc* desc, const float* c_scale);
 size_t fa_mla_decode_fp8_workspace_bytes(const fa_mla_decode_desc* desc);   /* equals fa_mla_decode_workspace_bytes(desc) */
 int    fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale);
 
+/* fa_kvcache_decode_varlen at head dimension 256 (the Gemma-2 / Gemma-3 head): token-packed split-KV decode against a 16-bit KV
+ * cache, contiguous [B,Hkv,Ncap,256] or pools [num_pages,Hkv,page_size,256] behind a block table, with the causal tail, the sliding
+ * window and the soft-cap.  The descriptor is fa_kvdecode_varlen_desc as it is, with d = 256, and every field means what it means
+ * for fa_kvcache_decode_varlen: s_b, e_b, n_b = min(e_b - s_b, max_q) from cu_seqlens_q under the same clamps, L_b from seqlens_k
+ * clamped to the capacity, c_i = max(0, L_b - n_b + 1 + i) with causal (L_b without), lo_i = max(0, L_b - n_b + 1 + i - window)
+ * with a window (0: none), the soft-cap before the masks, lse [Hkv*G, total_q], out_dtype fp32 or the input type.  The same rules
+ * hold word for word: nothing on the host reads device data; tokens that are no live row of any sequence are neither read nor
+ * written; n_b = 0 reads no K/V row, no page and no table entry; a live row without a key is O = 0, lse = -inf; rows at or past
+ * L_b, rows below start_b = lo_0 and pages no visible key lies in reach the arithmetic as zeros or not at all (they may hold NaN);
+ * table entries past the last live page or wholly below the window are not read; a live table entry outside [0, num_pages) reads
+ * as a page of zeros; paged and contiguous calls return the same bits on the same keys; a captured call follows cu_seqlens_q,
+ * seqlens_k and the table rewritten in place.  The entries are new because fa_kvcache_decode_varlen keeps refusing d = 256: the
+ * kernel is one of its own (32-row blocks, the 256 columns of V split over the four waves of a workgroup), not the d <= 128 stream.
+ * num_splits: 0 = chosen from (B, Hkv, G, max_q) and the capacity -- under a window from the longest range a sequence can stream --
+ * for a 256-CU device; >= 1 forces the count, which must not exceed the number of 64-key tiles of the capacity.  The tiles of each
+ * sequence from start_b's on are dealt to the splits on the device; a merge kernel finishes behind S > 1.
+ * fa_kvcache_decode_d256_workspace_bytes returns the bytes the call needs for that num_splits: 0 for one split, and 0 for a
+ * descriptor the call would refuse; the workspace must be 16-byte aligned.
+ * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_decode_varlen refuses for this descriptor, with
+ * "d in {64,128}" replaced by d != 256; kv_dtype != FA_KV_16BIT; a non-null k_scale, v_scale or sinks; num_splits < 0 or above the
+ * tile count; with S > 1 a workspace that is NULL, too small or misaligned.
+ * Not part of these entries: an fp8 cache, sinks, a tree mask, the routed / mixed step, a shared prefix, fa_merge_states at d = 256,
+ * an append at d = 256 (the append entries keep refusing it), a tiled prefill at d = 256.  NOT reference entry points. */
+size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits);
+int    fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits);
+
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
  * the same LDS images, fragment loads and accumulator maps as the product kernels.  d in {64,128}.
