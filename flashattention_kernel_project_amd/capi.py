@@ -287,6 +287,9 @@ def _signatures() -> dict:
         # fa_kvcache_decode_varlen's descriptor with d = 256, on a kernel of its own; then num_splits (0: the library's choice)
         "fa_kvcache_decode_d256_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc), i]),
         "fa_kvcache_decode_d256": (i, [C.POINTER(KvDecodeVarlenDesc), i]),
+        # the varlen prefill at head dimension 256, packed and against the cache: the descriptors above with d = 256, no sinks
+        "fa_forward_varlen_d256": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
+        "fa_forward_varlen_kvcache_d256": (i, [C.POINTER(VarlenKvcacheDesc)]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

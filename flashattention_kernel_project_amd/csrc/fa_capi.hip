@@ -354,6 +354,9 @@ FA_EXPORT size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen
 }
 FA_EXPORT int fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits) { return (int)fa::kv256_dispatch(desc, num_splits); }
 
+FA_EXPORT int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts) { return (int)fa::varlen256_dispatch(desc, opts); }
+FA_EXPORT int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc) { return (int)fa::varlen256_cache_dispatch(desc); }
+
 FA_EXPORT int fa_kvcache_attend_varlen_part(const fa_kvdecode_varlen_desc* desc, int parts) { return (int)fa::kvattend_dispatch(desc, parts); }
 FA_EXPORT int fa_kvcache_attend_varlen(const fa_kvdecode_varlen_desc* desc)
 {

@@ -247,6 +247,10 @@ bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size
 // must name d = 256; num_splits: 0 chooses, >= 1 forces
 hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
 size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
+// fa_forward_varlen_d256 and fa_forward_varlen_kvcache_d256 (fa_fwd_varlen256.hip): the checks and the one launch on the descriptors
+// of fa_forward_varlen_ex and fa_forward_varlen_kvcache, which must name d = 256 and no sinks; opts may be null
+hipError_t varlen256_dispatch(const ::fa_varlen_desc* desc, const ::fa_varlen_opts* opts);
+hipError_t varlen256_cache_dispatch(const ::fa_varlen_kvcache_desc* desc);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

@@ -456,6 +456,22 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
     window and softcap are host values (baked into a captured call).  With all three unset the call is fa_forward_varlen itself;
     otherwise fa_forward_varlen_ex, whose kernels compute a prompt by the arithmetic fa_forward_kvcache decodes its tokens with.
     One kernel, no workspace, nothing read on the host: a captured call follows vectors that are rewritten in place."""
+    return _varlen_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, scale, out_dtype, return_lse, out, stream, lse, window, softcap, sinks)
+
+
+def fa_forward_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, scale: float | None = None, out_dtype=None,
+                           return_lse: bool = False, out=None, stream=None, lse=None, window: int = 0, softcap: float = 0.0):
+    """fa_forward_varlen at head dimension 256 (fa_forward_varlen_d256; the Gemma-2 / Gemma-3 head): q (total_q, Hq, 256), k and v
+    (total_k, Hkv, 256).  Every argument, rule and result is fa_forward_varlen's -- strided packed tensors, cu_seqlens read on the device
+    and clamped, causal aligned to the end of the keys, window, softcap, lse, rows without a key, tokens of no sequence never written,
+    one kernel, no workspace, capture-safe -- on a kernel of its own; there are no sinks here."""
+    return _varlen_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, scale, out_dtype, return_lse, out, stream, lse, window, softcap, None,
+                          d256=True)
+
+
+def _varlen_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, scale, out_dtype, return_lse, out, stream, lse, window, softcap, sinks,
+                   d256=False):
+    """The two packed varlen front ends: d256 selects fa_forward_varlen_d256, which takes d = 256 alone and no sinks."""
     import torch
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor) or t.dim() != 3:
@@ -466,7 +482,9 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
     total_k, Hkv = k.shape[0], k.shape[1]
     if v.shape != k.shape or k.shape[2] != d:
         raise ValueError("k and v must both be (total_k, Hkv, d) with q's d")
-    if d not in (64, 128):
+    if d256 and d != 256:
+        raise ValueError("d must be 256 (d in {64,128} is fa_forward_varlen's)")
+    if not d256 and d not in (64, 128):
         raise ValueError("d must be 64 or 128")
     if total_q <= 0 or total_k <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0:
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
@@ -509,11 +527,13 @@ def fa_forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = F
                            in_dtype=_in_dt(q.dtype), out_dtype=out_dt, stream=_stream_ptr(stream))
     plain = window == 0 and softcap == 0.0 and sinks is None   # then the old symbol, as before the options existed
     with torch.cuda.device(_one_device(q, k, v, out, cu_seqlens_q, cu_seqlens_k, lse, sinks)):
-        if plain:
+        if d256:
+            code = capi.lib().fa_forward_varlen_d256(desc, capi.VarlenOpts(sinks=None, window=window, softcap=softcap))
+        elif plain:
             code = capi.lib().fa_forward_varlen(desc)
         else:
             code = capi.lib().fa_forward_varlen_ex(desc, capi.VarlenOpts(sinks=sink_ptr, window=window, softcap=softcap))
-    capi.check("fa_forward_varlen" if plain else "fa_forward_varlen_ex", code)
+    capi.check("fa_forward_varlen_d256" if d256 else "fa_forward_varlen" if plain else "fa_forward_varlen_ex", code)
     return (out, lse) if return_lse else out
 
 
@@ -554,12 +574,26 @@ def fa_forward_varlen_kvcache_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqle
                            stream, lse, window, softcap, sinks, scales=(k_scale, v_scale))
 
 
+def fa_forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, causal: bool = False,
+                                   scale: float | None = None, out_dtype=None, return_lse: bool = False, out=None, stream=None, lse=None,
+                                   window: int = 0, softcap: float = 0.0):
+    """fa_forward_varlen_kvcache at head dimension 256 (fa_forward_varlen_kvcache_d256): q (total_q, Hq, 256), the caches
+    [B,Hkv,Ncap,256] or with block_table the pools [num_pages,Hkv,page_size,256], 16-bit and of q's dtype -- the cache
+    fa_kvcache_decode_d256 decodes from.  Every argument, rule and result is fa_forward_varlen_kvcache's -- lengths that include the
+    chunk, the causal and window limits, table entries that are never read, pages below lo_0 that may be freed, a bad live page read as
+    zeros, nothing read on the host, capture-safe -- on a kernel of its own; there are no sinks and no fp8 cache here.  On the same
+    finite keys the paged form, the contiguous form and fa_forward_varlen_d256 on the gathered K/V return the same bits."""
+    return _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out,
+                           stream, lse, window, softcap, None, d256=True)
+
+
 def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out, stream,
-                    lse, window, softcap, sinks, scales=None):
-    """The two varlen front ends against the KV cache: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one."""
+                    lse, window, softcap, sinks, scales=None, d256=False):
+    """The varlen front ends against the KV cache: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one;
+    d256 selects fa_forward_varlen_kvcache_d256, which takes d = 256 alone and no sinks."""
     import torch
     fp8 = scales is not None
-    name8 = "fa_forward_varlen_kvcache" + "_fp8" * fp8
+    name8 = "fa_forward_varlen_kvcache" + "_fp8" * fp8 + "_d256" * d256
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a tensor")
@@ -577,7 +611,9 @@ def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_tabl
     if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.shape[3] != d:
         raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with q's d")
     Hkv = k_cache.shape[1]
-    if d not in (64, 128):
+    if d256 and d != 256:
+        raise ValueError("d must be 256 (d in {64,128} is fa_forward_varlen_kvcache's)")
+    if not d256 and d not in (64, 128):
         raise ValueError("d must be 64 or 128")
     if total_q <= 0 or Hkv <= 0 or Hq <= 0 or Hq % Hkv != 0 or k_cache.numel() == 0:
         raise ValueError("the number of query heads must be a positive multiple of the number of K/V heads, and no tensor empty")
@@ -635,6 +671,8 @@ def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_tabl
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, *(scales or ()))):
         if fp8:
             code = capi.lib().fa_forward_varlen_kvcache_fp8(desc, ks_ptr, vs_ptr)
+        elif d256:
+            code = capi.lib().fa_forward_varlen_kvcache_d256(desc)
         else:
             code = capi.lib().fa_forward_varlen_kvcache(desc)
     capi.check(name8, code)

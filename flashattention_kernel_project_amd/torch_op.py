@@ -73,6 +73,10 @@ eager fallback.  Registered on first use:
     # decode_varlen at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks; num_splits 0 = the library's choice
     o, lse = torch.ops.fa_mi355.decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
                                             window, softcap, num_splits, out_f32)
+    # the varlen prefill at head dimension 256 (ops.fa_forward_varlen_d256, ops.fa_forward_varlen_kvcache_d256): no sinks
+    o, lse = torch.ops.fa_mi355.forward_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, softcap, out_f32)
+    o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, scale, causal,
+                                                            window, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -86,7 +90,8 @@ def register() -> None:
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
-    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256."""
+    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256,
+    .forward_varlen_d256 and .forward_varlen_kvcache_d256."""
     global _registered
     if _registered:
         return
@@ -315,6 +320,18 @@ def register() -> None:
            lambda q, scale, causal, window, softcap, num_splits, out_f32: dict(
                causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
                softcap=softcap, num_splits=num_splits), varlen_fake)
+
+    # the varlen prefill at head dimension 256 (ops.fa_forward_varlen_d256, ops.fa_forward_varlen_kvcache_d256): forward_varlen_ex and
+    # forward_varlen_kvcache without `Tensor? sinks`
+    def varlen_d256_kw(q, scale, causal, window, softcap, out_f32):
+        return dict(causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+                    softcap=softcap)
+
+    VARLEN_D256_TAIL = "float scale, bool causal, int window, float softcap, bool out_f32) -> (Tensor, Tensor)"
+    define("forward_varlen_d256", "(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, " + VARLEN_D256_TAIL, (),
+           ops.fa_forward_varlen_d256, "---co", varlen_d256_kw, varlen_fake)
+    define("forward_varlen_kvcache_d256", "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, "
+           "Tensor? block_table, " + VARLEN_D256_TAIL, (), ops.fa_forward_varlen_kvcache_d256, "-cccco", varlen_d256_kw, varlen_fake)
 
     # the same with a tree mask (fa_kvcache_decode_varlen_ex): `Tensor tree_mask` (int64, total_q) follows block_table; causal must be True
     def decode_varlen_tree(fn):

@@ -1137,9 +1137,37 @@ int    fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale);
  * "d in {64,128}" replaced by d != 256; kv_dtype != FA_KV_16BIT; a non-null k_scale, v_scale or sinks; num_splits < 0 or above the
  * tile count; with S > 1 a workspace that is NULL, too small or misaligned.
  * Not part of these entries: an fp8 cache, sinks, a tree mask, the routed / mixed step, a shared prefix, fa_merge_states at d = 256,
- * an append at d = 256 (the append entries keep refusing it), a tiled prefill at d = 256.  NOT reference entry points. */
+ * an append at d = 256 (the append entries keep refusing it).  The tiled prefill at d = 256 is fa_forward_varlen_d256's and
+ * fa_forward_varlen_kvcache_d256's, below.  NOT reference entry points. */
 size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits);
 int    fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits);
+
+/* The variable-length prefill at head dimension 256: fa_forward_varlen_ex and fa_forward_varlen_kvcache for the head
+ * fa_kvcache_decode_d256 decodes, so that a d = 256 cache filled by any means is prefilled (prompts, chunked prefill, prefix
+ * caching) and decoded by the same arithmetic, in the same captured graph.  Both descriptors are used as they are, with d = 256;
+ * opts may be NULL (no window, no cap).
+ * Semantics: word for word those of fa_forward_varlen_ex and fa_forward_varlen_kvcache.  Q and O are token-packed and read through
+ * their strides; cu_seqlens_*, seqlens_k and block_table are read on the device only and clamped; Hq = G*Hkv without expanded K/V;
+ * c_i = max(0, Lk - Lq + 1 + i) under causal (Lk without); lo_i = max(0, Lk - Lq + 1 + i - W) under a window, with and without
+ * causal; the soft-cap is applied before the masks, by the decode side's formula; lse is [Hkv*G, total_q] in natural-log units; a
+ * row without a key returns O = 0 exactly and lse = -inf; rows of no sequence are never read or written; a negative scale flips
+ * the logits and 0 gives uniform weights.  The grid comes from (B, Hkv, G, total_q) alone; no workspace; one kernel; a captured call
+ * follows the vectors and the table rewritten in place.
+ * Cache form: the contiguous cache [B,Hkv,Ncap,256], or the pools [num_pages,Hkv,page_size,256] behind the table, page_size a power
+ * of two >= 16.  Table entries at or past the last live page are never read; pages wholly below lo_0 = max(0, Lk - Lq + 1 - W) may
+ * be freed; a live entry outside [0, num_pages) reads as a page of zeros; rows at or past Lk, and rows of the first streamed 64-key
+ * tile below the lo of a 128-row query block's first row, reach the arithmetic as zeros.  (The packed entry uses the K/V rows of a
+ * sequence as they are, like fa_forward_varlen_ex.)
+ * Bits: tiles stay at absolute multiples of 64 keys from key 0; on the same finite keys the paged form, the contiguous form and the
+ * packed entry on the gathered K/V return the same bits for O and lse.
+ * There are NO SINKS at d = 256, here as in fa_kvcache_decode_d256: a non-null opts->sinks or desc->sinks is refused.
+ * hipErrorInvalidValue, before the device is touched: everything fa_forward_varlen_ex resp. fa_forward_varlen_kvcache refuse, with
+ * "d not in {64,128}" replaced by d != 256; non-null sinks; and for the cache form the capacity bound of fa_kvcache_decode_d256,
+ * (capacity + 64) * 512 >= 2^32.  fa_forward_varlen, _ex, _kvcache and _kvcache_fp8 keep refusing d = 256.
+ * Not part of these entries: the append at d = 256, fp8 caches, sinks, the routed mixed step, a tree mask, key splits,
+ * fa_merge_states at d = 256.  NOT reference entry points. */
+int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts);   /* opts may be NULL */
+int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through
