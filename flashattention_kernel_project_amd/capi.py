@@ -287,6 +287,11 @@ def _signatures() -> dict:
         # fa_kvcache_decode_varlen's descriptor with d = 256, on a kernel of its own; then num_splits (0: the library's choice)
         "fa_kvcache_decode_d256_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc), i]),
         "fa_kvcache_decode_d256": (i, [C.POINTER(KvDecodeVarlenDesc), i]),
+        # the same on an e4m3fn cache (kv_dtype KV_FP8_E4M3, the descriptor's own k_scale, v_scale)
+        "fa_kvcache_decode_d256_fp8_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc), i]),
+        "fa_kvcache_decode_d256_fp8": (i, [C.POINTER(KvDecodeVarlenDesc), i]),
+        # the packed append at d = 256, 16-bit and e4m3fn caches, all eight forms; opts (positions) may be null
+        "fa_kvcache_append_varlen_d256": (i, [C.POINTER(KvAppendVarlenDesc), C.POINTER(KvAppendVarlenOpts)]),
         # the varlen prefill at head dimension 256, packed and against the cache: the descriptors above with d = 256, no sinks
         "fa_forward_varlen_d256": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
         "fa_forward_varlen_kvcache_d256": (i, [C.POINTER(VarlenKvcacheDesc)]),

@@ -353,6 +353,18 @@ FA_EXPORT size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen
     return fa::kv256_workspace_bytes(desc, num_splits);
 }
 FA_EXPORT int fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits) { return (int)fa::kv256_dispatch(desc, num_splits); }
+FA_EXPORT size_t fa_kvcache_decode_d256_fp8_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits)
+{
+    return fa::kv256_workspace_bytes(desc, num_splits, true);
+}
+FA_EXPORT int fa_kvcache_decode_d256_fp8(const fa_kvdecode_varlen_desc* desc, int num_splits)
+{
+    return (int)fa::kv256_dispatch(desc, num_splits, true);
+}
+FA_EXPORT int fa_kvcache_append_varlen_d256(const fa_kvappend_varlen_desc* desc, const fa_kvappend_varlen_opts* opts)
+{
+    return (int)fa::kvcache_append_varlen_d256(desc, opts);
+}
 
 FA_EXPORT int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts) { return (int)fa::varlen256_dispatch(desc, opts); }
 FA_EXPORT int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc) { return (int)fa::varlen256_cache_dispatch(desc); }

@@ -230,6 +230,9 @@ hipError_t kvcache_append_varlen(const ::fa_kvappend_varlen_desc* desc);
 // fa_kvcache_append_varlen_ex: the options' checks, then the same; positions (device, total_new int32, or null) are the rotary table
 // rows of the tokens in place of their slots
 hipError_t kvcache_append_varlen_ex(const ::fa_kvappend_varlen_desc* desc, const ::fa_kvappend_varlen_opts* opts);
+// fa_kvcache_append_varlen_d256 (fa_kvcache_append_varlen256.hip): the same kernel template at 512-byte rows behind the same checks,
+// with "d in {64,128}" replaced by d == 256 and the capacity bound of fa_kvcache_decode_d256; opts may be null
+hipError_t kvcache_append_varlen_d256(const ::fa_kvappend_varlen_desc* desc, const ::fa_kvappend_varlen_opts* opts);
 // fa_kvcache_commit (fa_kvcache_commit.hip): the checks and the one or two launches; the descriptor is the public one, as it is
 hipError_t kvcache_commit(const ::fa_kvcommit_desc* desc);
 // fa_mla_decode (fa_mla_decode.hip) and fa_mla_append (fa_mla_append.hip): the checks and the launches on the public descriptors;
@@ -244,9 +247,10 @@ hipError_t mla_decode_fp8_dispatch(const ::fa_mla_decode_desc* desc, const float
 hipError_t mla_append_fp8_dispatch(const ::fa_mla_append_desc* desc, const float* c_scale);
 bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page);
 // fa_kvcache_decode_d256 (fa_fwd_kv256.hip): the checks and the one or two launches on fa_kvcache_decode_varlen's descriptor, which
-// must name d = 256; num_splits: 0 chooses, >= 1 forces
-hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
-size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc, int num_splits);
+// must name d = 256; num_splits: 0 chooses, >= 1 forces.  fp8: fa_kvcache_decode_d256_fp8, the same checks and the same plan on an
+// e4m3fn cache (kv_dtype FA_KV_FP8_E4M3, the descriptor's scales null or 4-byte aligned), the kernels of fa_fwd_kv256_fp8.hip
+hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* desc, int num_splits, bool fp8 = false);
+size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc, int num_splits, bool fp8 = false);
 // fa_forward_varlen_d256 and fa_forward_varlen_kvcache_d256 (fa_fwd_varlen256.hip): the checks and the one launch on the descriptors
 // of fa_forward_varlen_ex and fa_forward_varlen_kvcache, which must name d = 256 and no sinks; opts may be null
 hipError_t varlen256_dispatch(const ::fa_varlen_desc* desc, const ::fa_varlen_opts* opts);

@@ -2,7 +2,8 @@
 // Gemma-2 / Gemma-3 head), contiguous and paged, with the causal tail, the sliding window and the soft-cap.  The descriptor is
 // fa_kvcache_decode_varlen's as it is; the entries are new because that one keeps refusing d = 256.  The kernel template, the merge
 // kernel and the launcher are in fa_fwd_kv256_kernel.hpp; this unit owns the host checks and the plan and instantiates the kernels.
-// DESIGN.md section 7.25, profiles/kv256_decode.txt.
+// fa_kvcache_decode_d256_fp8 runs the same checks and the same plan here; its kernels are fa_fwd_kv256_fp8.hip's.
+// DESIGN.md sections 7.25 and 7.27, profiles/kv256_decode.txt.
 #include "fa_fwd_kv256_kernel.hpp"
 #include "fa_fwd_varlen_kernel.hpp"   // varlen_tensor_ok()
 
@@ -39,12 +40,16 @@ bool kv256_view_ok(int max_q, int total, long long Hq, long long st, long long s
     return end <= 0xFFFFFFFFull;
 }
 
-// every check that needs no workspace: fa_kvcache_decode_varlen's, with d == 256, a 16-bit cache and neither scales nor sinks; on
-// success the plan is filled in
-bool kv256_plan(const ::fa_kvdecode_varlen_desc* d, int num_splits, Kv256Plan& p)
+// every check that needs no workspace: fa_kvcache_decode_varlen's, with d == 256, no sinks and, for the 16-bit entry, a 16-bit cache
+// without scales, for the fp8 entry an e4m3fn cache whose scales are null or 4-byte aligned; on success the plan is filled in.
+// Nothing of the plan depends on `fp8`: the capacity bound stays that of 512-byte rows, and so do the splits and the workspace.
+bool kv256_plan(const ::fa_kvdecode_varlen_desc* d, int num_splits, bool fp8, Kv256Plan& p)
 {
     if (!d || d->size != sizeof(fa_kvdecode_varlen_desc)) return false;
-    if (d->kv_dtype != FA_KV_16BIT || d->k_scale || d->v_scale || d->sinks) return false;
+    if (d->sinks) return false;
+    if (!fp8 && (d->kv_dtype != FA_KV_16BIT || d->k_scale || d->v_scale)) return false;
+    if (fp8 && (d->kv_dtype != FA_KV_FP8_E4M3 || ((reinterpret_cast<uintptr_t>(d->k_scale) | reinterpret_cast<uintptr_t>(d->v_scale)) & 3u)))
+        return false;
     if (d->d != kv256::kD) return false;
     if (!d->Q || !d->K || !d->V || !d->O || !d->cu_seqlens_q) return false;
     if (d->B <= 0 || d->Hkv <= 0 || d->G <= 0 || d->total_q <= 0 || d->max_q <= 0) return false;
@@ -93,16 +98,16 @@ size_t kv256_ws_bytes(const ::fa_kvdecode_varlen_desc* d, const Kv256Plan& p)
 
 }  // namespace
 
-size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* d, int num_splits)
+size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* d, int num_splits, bool fp8)
 {
     Kv256Plan p;
-    return kv256_plan(d, num_splits, p) ? kv256_ws_bytes(d, p) : 0;
+    return kv256_plan(d, num_splits, fp8, p) ? kv256_ws_bytes(d, p) : 0;
 }
 
-hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* d, int num_splits)
+hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* d, int num_splits, bool fp8)
 {
     Kv256Plan p;
-    if (!kv256_plan(d, num_splits, p)) return hipErrorInvalidValue;
+    if (!kv256_plan(d, num_splits, fp8, p)) return hipErrorInvalidValue;
     const size_t need = kv256_ws_bytes(d, p);
     if (need && (!d->workspace || d->workspace_bytes < need || (reinterpret_cast<uintptr_t>(d->workspace) & 15u)))
         return hipErrorInvalidValue;
@@ -110,10 +115,11 @@ hipError_t kv256_dispatch(const ::fa_kvdecode_varlen_desc* d, int num_splits)
                           static_cast<float*>(d->workspace), d->cu_seqlens_q, d->seqlens_k, d->block_table, d->B, d->Hkv, d->G, d->total_q,
                           d->max_q, p.cap, p.paged ? d->max_pages : 0, p.paged ? d->num_pages : 0, p.lg_page, d->q_stride_t, d->q_stride_h,
                           d->o_stride_t, d->o_stride_h, host_scale_log2e(d->scale), d->softcap * kLog2e,
-                          d->softcap > 0.0f ? 2.0f / d->softcap : 0.0f, d->causal, p.window, p.S, p.nqb};
+                          d->softcap > 0.0f ? 2.0f / d->softcap : 0.0f, d->causal, p.window, p.S, p.nqb, d->k_scale, d->v_scale};
     hipStream_t stream = static_cast<hipStream_t>(d->stream);
+    if (fp8) return kv256_launch_fp8(a, d->in_dtype == FA_DTYPE_BF16, d->out_dtype == FA_OUT_F32, p.paged, stream);
     return with_types(d->in_dtype, d->out_dtype,
-                      [&](auto t, auto f32) { return kv256_launch<decltype(t), decltype(f32)::value>(a, p.paged, stream); });
+                      [&](auto t, auto f32) { return kv256_launch<decltype(t), decltype(f32)::value, false>(a, p.paged, stream); });
 }
 
 }  // namespace fa

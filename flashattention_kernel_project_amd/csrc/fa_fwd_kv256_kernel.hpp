@@ -1,4 +1,5 @@
-// fa_fwd_kv256_kernel.hpp -- device code of fa_kvcache_decode_d256 (fa_fwd_kv256.hip): token-packed split-KV decode against a 16-bit
+// fa_fwd_kv256_kernel.hpp -- device code of fa_kvcache_decode_d256 (fa_fwd_kv256.hip) and, with kFp8, of fa_kvcache_decode_d256_fp8
+// (fa_fwd_kv256_fp8.hip: rows of 256 e4m3fn codes, widened on their way into LDS): token-packed split-KV decode against a
 // KV cache at head dimension 256, contiguous and paged, with the causal tail, the sliding window and the soft-cap.  A kernel of its
 // own on the plan of the split-KV stream (fa_fwd_split_kernel.hpp, whose TileGeom<64|128> sits at its register limits): the G * n_b
 // rows of a (sequence, K/V head) are folded into 32-row blocks, lengths, cu_seqlens and the block table are read on the device, the
@@ -6,7 +7,7 @@
 // is the tile at 512-byte rows: ALL FOUR waves of a workgroup own the SAME 32 rows, every wave computes the whole S^T = K Q^T of the
 // tile (so all four hold the same (m, l) and the same packed P, bit for bit, from the same LDS bytes), and the 256 columns of V are
 // split over the waves: a wave keeps O^T for 64 columns in 32 accumulator registers and reads only its quarter of the V image.
-// Private to csrc/.  DESIGN.md section 7.25, profiles/kv256_decode.txt.
+// Private to csrc/.  DESIGN.md sections 7.25 and 7.27, profiles/kv256_decode.txt, profiles/kv256_fp8.txt.
 #pragma once
 #include "../../include/fa_mi355.h"
 #include "fa_dispatch.hpp"
@@ -28,6 +29,8 @@ constexpr int kDBlocks = kD / 32 / kW;         // 2 32-column blocks of O^T per 
 constexpr int kGroups = kTile / 8 / kW;        // 2 eight-row groups of a tile each wave stages, for K and for V
 constexpr int kGroupLoads = 8 * kChunks / 64;  // 4 16-byte loads per lane and group
 constexpr int kWsRow = kD + 4;                 // floats per workspace row: O^T, m, l and two of padding (rows stay 16-byte aligned)
+constexpr int kRowBytes8 = kD;                 // an e4m3fn cache row: 256 bytes, 16 loads of 16 bytes
+constexpr int kGroupLoads8 = 8 * kRowBytes8 / 16 / 64;   // 2 16-byte loads per lane and group of an e4m3fn cache
 
 // The LDS images, K and V alike: row-major rows of 512 bytes, the low four bits of the 16-byte chunk index XORed with x(row).
 // A row is two bank rows (64 banks x 4 bytes = 16 slots of 16 bytes), so without the XOR chunk c of EVERY row lies in slot c % 16.
@@ -59,7 +62,20 @@ struct Dev {
     float cap2, cap_rk;                  // softcap * log2(e) and 2 / softcap; 0: no cap
     int causal, window;                  // window >= 1: "none" comes in as the capacity
     int S, nqb;
+    const float *k_scale, *v_scale;      // kFp8 only: [Hkv] on the device, or nullptr (1.0).  Last, so that no other field moves
 };
+
+// The staging of an e4m3fn cache (kFp8).  An 8-row group is 2 KiB, two 16-byte loads per lane; load p of lane (a = lane >> 4,
+// b = lane >> 3 & 1, j = lane & 7) is the 16 codes c = j + 8 p of row 4 b + a of the group: the 16 lanes of a quarter wave read half
+// a row of row a and the same half of row a + 4, 128 contiguous bytes each.  Widened, the 16 codes are the LDS chunks 2 c and 2 c + 1
+// of the row, written by two ds_write_b128 (first every lane's chunk 2 c, then every lane's 2 c + 1).  Slots: were the 16 lanes one
+// row, chunks 2 c, c = 0 .. 15, would have only the 8 even values of (chunk & 15) -- 2 c and 2 c + 16 share their low four bits --
+// and the XOR with x(row) permutes slots without separating them: each round 2-way conflicted.  With two rows R and R + 4 to a
+// quarter wave, the lanes of one row cover the 8 values 2 j ^ x(R), all of one parity, and x(R + 4) = x(R) ^ 1 (bit 2 of the row is
+// bit 0 of x), so the other row's 8 slots are those of the other parity: 16 lanes, 16 slots, in the round of the even chunks and, by
+// the same argument with 2 j + 1, in the round of the odd ones.  p adds 16 chunks (256 bytes) and g 32 rows: immediates.
+__device__ __forceinline__ unsigned fp8_row(unsigned lane) { return ((lane >> 3) & 1u) * 4u + (lane >> 4); }
+__device__ __forceinline__ unsigned fp8_ld_off(unsigned lane) { return fp8_row(lane) * kRowBytes8 + (lane & 7u) * 16u; }   // + 128 p
 }  // namespace kv256
 
 // Rows: the live rows of (sequence b, K/V head hkv) are (head hd < G of the group, token i < n_b), folded as p = hd * n_b + i into
@@ -81,7 +97,12 @@ struct Dev {
 // Soft-cap: the stream's arithmetic.  Before the masks every score x = s c (log2 units) becomes cap2 tanh(x / cap2), with tanh(y) =
 // 1 - 2 / (1 + e^(2y)) on v_exp_f32 and v_rcp_f32; the scores are then final and the factor of the vote and of the weights is 1.
 // cap2 == 0 skips it by a wave-uniform branch.
-template <typename T, bool kOutF32, bool kPartial, bool kPaged>
+// kFp8: K and V address one e4m3fn byte per element.  Only the staging differs (above): the descriptors cover rows x 256 bytes, so
+// what lies outside them reads as the code 0 (+0) whatever NaN codes memory holds; the raw bytes wait in 32 registers through the
+// tile's arithmetic and are widened exactly to T (fp8x16_widen) in stage_write.  k_scale[hkv] joins the logit factor -- the clamp
+// comes after the product, and under the soft-cap the product is what the cap sees -- and v_scale[hkv] joins 1 / l here and in
+// the merge.  With both null every factor keeps its bits: the result is the 16-bit kernel's on the widened cache.
+template <typename T, bool kOutF32, bool kPartial, bool kPaged, bool kFp8>
 __global__ __launch_bounds__(64 * kv256::kW, 2)
 void fa_kv256_decode_kernel(kv256::Dev a)
 {
@@ -119,7 +140,11 @@ void fa_kv256_decode_kernel(kv256::Dev a)
     const unsigned lim_lo = a.causal ? min((unsigned)max(first, 0), key1) : key1;
     const unsigned lo_hi = (unsigned)max((int)nkeys - a.window, 0);
 
-    const float c = fmaxf(fabsf(a.scale_log2e), 1.17549435e-38f);   // a scale of 0 must not meet a masked -inf as 0 * -inf
+    float sl2 = a.scale_log2e;
+    if constexpr (kFp8) {
+        if (a.k_scale) sl2 *= a.k_scale[hkv];
+    }
+    const float c = fmaxf(fabsf(sl2), 1.17549435e-38f);   // a scale of 0 must not meet a masked -inf as 0 * -inf
     const unsigned q_flip = a.scale_log2e < 0.0f ? 0x80008000u : 0u;
     // what a score is multiplied by on its way into the vote and the exponent (1 once the cap has made the scores final), and the
     // cap's two constants, in scalar registers
@@ -136,15 +161,22 @@ void fa_kv256_decode_kernel(kv256::Dev a)
 
     // staging: group g of the tile's 8-row groups that this wave loads is group g * kW + wave; lane idx = lane + 64 p of a group is
     // chunk idx % 32 of row idx / 32, which in memory is byte idx * 16 of the group
-    unsigned l_off[kGroupLoads];
+    constexpr int kLoads = kFp8 ? kGroupLoads8 : kGroupLoads;
+    constexpr unsigned kSrcRow = kFp8 ? kRowBytes8 : kRowBytes;   // bytes of a cache row
+    unsigned l_off[kLoads];   // kFp8: [0] is chunk 2 j of the lane's row in the image (chunk 2 j + 1 lies at [0] ^ 16), [1] its load offset
+    if constexpr (kFp8) {
+        l_off[0] = img_off(wave * 8u + fp8_row(lane), 2u * (lane & 7u));
+        l_off[1] = fp8_ld_off(lane);
+    } else {
 #pragma unroll
-    for (int p = 0; p < kGroupLoads; ++p) l_off[p] = img_off(wave * 8u + 2u * p + h, r);   // swz has period 16: g adds 32 rows
+        for (int p = 0; p < kGroupLoads; ++p) l_off[p] = img_off(wave * 8u + 2u * p + h, r);   // swz has period 16: g adds 32 rows
+    }
     const char *kbase = a.K, *vbase = a.V;
     if constexpr (!kPaged) {
-        kbase += (size_t)bh * (unsigned)a.cap * kRowBytes;
-        vbase += (size_t)bh * (unsigned)a.cap * kRowBytes;
+        kbase += (size_t)bh * (unsigned)a.cap * kSrcRow;
+        vbase += (size_t)bh * (unsigned)a.cap * kSrcRow;
     }
-    u32x4 kst[kGroups][kGroupLoads], vst[kGroups][kGroupLoads];
+    u32x4 kst[kGroups][kLoads], vst[kGroups][kLoads];
     [[maybe_unused]] int pg[kGroups];
     [[maybe_unused]] auto fetch_pages = [&](unsigned kv0) {
         if constexpr (kPaged) {
@@ -168,12 +200,13 @@ void fa_kv256_decode_kernel(kv256::Dev a)
                 if ((unsigned)pg[g] >= (unsigned)a.num_pages) rows = 0u;  // a bad page number: no record, every load reads 0
                 row0 = rows ? ((((size_t)(unsigned)pg[g] * (unsigned)a.Hkv + hkv) << a.lg_page) + (kg & ((1u << a.lg_page) - 1u))) : 0;
             }
-            const size_t byte0 = (rows ? row0 : 0) * kRowBytes;
-            const __amdgpu_buffer_rsrc_t rk = make_rsrc(kbase + byte0, rows * kRowBytes), rv = make_rsrc(vbase + byte0, rows * kRowBytes);
+            const size_t byte0 = (rows ? row0 : 0) * kSrcRow;
+            const __amdgpu_buffer_rsrc_t rk = make_rsrc(kbase + byte0, rows * kSrcRow), rv = make_rsrc(vbase + byte0, rows * kSrcRow);
 #pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) {
-                kst[g][p] = buf_load16_nt(rk, (lane + 64u * p) * 16u);
-                vst[g][p] = buf_load16_nt(rv, (lane + 64u * p) * 16u);
+            for (int p = 0; p < kLoads; ++p) {
+                const unsigned off = kFp8 ? l_off[1] + 128u * p : (lane + 64u * p) * 16u;
+                kst[g][p] = buf_load16_nt(rk, off);
+                vst[g][p] = buf_load16_nt(rv, off);
             }
         }
     };
@@ -183,15 +216,31 @@ void fa_kv256_decode_kernel(kv256::Dev a)
 #pragma unroll
             for (int g = 0; g < kGroups; ++g)
 #pragma unroll
-                for (int p = 0; p < kGroupLoads; ++p)
-                    if (kv0 + (g * kW + wave) * 8u + 2u * p + h < start_b) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                for (int p = 0; p < kLoads; ++p) {
+                    if constexpr (kFp8) {   // the raw bytes: the code 0 is +0
+                        if (kv0 + (g * kW + wave) * 8u + fp8_row(lane) < start_b) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                    } else {
+                        if (kv0 + (g * kW + wave) * 8u + 2u * p + h < start_b) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                    }
+                }
         }
 #pragma unroll
         for (int g = 0; g < kGroups; ++g)
 #pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) {
-                lds_write16(smem, g * (kW * 8 * kRowBytes) + l_off[p], kst[g][p]);
-                lds_write16(smem, kImgBytes + g * (kW * 8 * kRowBytes) + l_off[p], vst[g][p]);
+            for (int p = 0; p < kLoads; ++p) {
+                if constexpr (kFp8) {   // one load is the row's chunks 2 c and 2 c + 1, c = j + 8 p: the even round, then the odd one
+                    const unsigned at = g * (kW * 8 * kRowBytes) + p * 256u;
+                    u32x4 klo, khi, vlo, vhi;
+                    fp8x16_widen<T>(kst[g][p], klo, khi);
+                    fp8x16_widen<T>(vst[g][p], vlo, vhi);
+                    lds_write16(smem, at + l_off[0], klo);
+                    lds_write16(smem, at + (l_off[0] ^ 16u), khi);   // `at` is a multiple of 256
+                    lds_write16(smem, kImgBytes + at + l_off[0], vlo);
+                    lds_write16(smem, kImgBytes + at + (l_off[0] ^ 16u), vhi);
+                } else {
+                    lds_write16(smem, g * (kW * 8 * kRowBytes) + l_off[p], kst[g][p]);
+                    lds_write16(smem, kImgBytes + g * (kW * 8 * kRowBytes) + l_off[p], vst[g][p]);
+                }
             }
     };
 
@@ -238,6 +287,18 @@ void fa_kv256_decode_kernel(kv256::Dev a)
                 const u32x4 kf = lds_read16(smem, (k_rd ^ ((unsigned)(ks & 7) << 5)) + (unsigned)(ks >> 3) * 256u + kb * 32u * kRowBytes);
                 s[kb] = T::mfma32(kf, qf[ks], ks == 0 ? zero16 : s[kb]);
             }
+        if constexpr (kFp8) {
+            // The order of the 32 row reads and their MFMAs, pinned: four reads ahead, then one read per MFMA.  Left to itself the
+            // scheduler spends the 32 freed staging registers on 16 reads in flight in the partial kernels and spills a Q fragment
+            // for it (4 VGPRs of scratch); the direct kernels come out read-by-read either way.  0x100: DS read, 0x008: MFMA.
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+            for (int i = 0; i < 2 * kKSteps - 4; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        }
         if (a.cap2 > 0.0f) {   // wave-uniform; before the masks, so a masked key stays at -inf
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -331,7 +392,10 @@ void fa_kv256_decode_kernel(kv256::Dev a)
             if (h == 0 && wave == 0) *reinterpret_cast<f32x2*>(row + kD) = f32x2{m_ref, l};
         }
     } else {
-        const float inv = l == 0.0f ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        float inv = l == 0.0f ? 0.0f : 1.0f / l;   // a row without a key: O = 0
+        if constexpr (kFp8) {
+            if (a.v_scale) inv *= a.v_scale[hkv];
+        }
         if (a.lse && h == 0 && wave == 0 && row_live)
             a.lse[((size_t)hkv * (unsigned)a.G + row_hd) * (size_t)a.total_q + (size_t)s_tok + row_i] =
                 l == 0.0f ? -INFINITY : (m_ref + __log2f(l)) * kLn2;
@@ -357,8 +421,8 @@ void fa_kv256_decode_kernel(kv256::Dev a)
 
 // The merge behind a split: one wave per padded row (b, hkv, head hd of the group, token i < max_q), a lane per 4 output columns.
 // A row with i >= n_b returns without writing: no token of no sequence is written.  A partial with m = -inf (a split without a
-// visible key) takes the weight 0; a row of such partials is O = 0, lse = -inf.
-template <typename T, bool kOutF32>
+// visible key) takes the weight 0; a row of such partials is O = 0, lse = -inf.  kFp8: v_scale[hkv] joins the final division.
+template <typename T, bool kOutF32, bool kFp8>
 __global__ __launch_bounds__(64)
 void fa_kv256_merge_kernel(kv256::Dev a)
 {
@@ -386,7 +450,10 @@ void fa_kv256_merge_kernel(kv256::Dev a)
         L += row[kD + 1] * w;
         acc += *reinterpret_cast<const f32x4*>(row + c4) * w;
     }
-    const float inv = L == 0.0f ? 0.0f : 1.0f / L;
+    float inv = L == 0.0f ? 0.0f : 1.0f / L;
+    if constexpr (kFp8) {
+        if (a.v_scale) inv *= a.v_scale[hkv];
+    }
     const size_t tok = (size_t)s_tok + i, hq = (size_t)hkv * (unsigned)a.G + hd;
     if (a.lse && threadIdx.x == 0) a.lse[hq * (size_t)a.total_q + tok] = L == 0.0f ? -INFINITY : (M + __log2f(L)) * kLn2;
     const size_t off = tok * (size_t)a.o_st + hq * (size_t)a.o_sh + c4;
@@ -398,19 +465,21 @@ void fa_kv256_merge_kernel(kv256::Dev a)
 }
 
 // The one or two launches of a checked call.
-template <typename T, bool kOutF32>
+template <typename T, bool kOutF32, bool kFp8>
 hipError_t kv256_launch(const kv256::Dev& a, bool paged, hipStream_t stream)
 {
     const dim3 grid((unsigned)a.B * (unsigned)a.Hkv * (unsigned)a.nqb * (unsigned)a.S), block(64 * kv256::kW);
     void (*kernel)(kv256::Dev);
-    if (a.S > 1) kernel = paged ? fa_kv256_decode_kernel<T, kOutF32, true, true> : fa_kv256_decode_kernel<T, kOutF32, true, false>;
-    else kernel = paged ? fa_kv256_decode_kernel<T, kOutF32, false, true> : fa_kv256_decode_kernel<T, kOutF32, false, false>;
+    if (a.S > 1) kernel = paged ? fa_kv256_decode_kernel<T, kOutF32, true, true, kFp8> : fa_kv256_decode_kernel<T, kOutF32, true, false, kFp8>;
+    else kernel = paged ? fa_kv256_decode_kernel<T, kOutF32, false, true, kFp8> : fa_kv256_decode_kernel<T, kOutF32, false, false, kFp8>;
     FA_LAUNCH(kernel, grid, block, (size_t)kv256::kLdsBytes, stream, a);   // 64 KiB: the default limit of dynamic LDS
     const hipError_t e = launch_status();
     if (e != hipSuccess || a.S <= 1) return e;
-    FA_LAUNCH((fa_kv256_merge_kernel<T, kOutF32>), dim3((unsigned)a.B * (unsigned)a.Hkv * (unsigned)a.G * (unsigned)a.max_q), dim3(64), 0,
+    FA_LAUNCH((fa_kv256_merge_kernel<T, kOutF32, kFp8>), dim3((unsigned)a.B * (unsigned)a.Hkv * (unsigned)a.G * (unsigned)a.max_q), dim3(64), 0,
               stream, a);
     return launch_status();
 }
+// fa_fwd_kv256_fp8.hip: kv256_launch<., ., true>, the fp8 unit's instantiations behind the checks and the plan of fa_fwd_kv256.hip
+hipError_t kv256_launch_fp8(const kv256::Dev& a, bool bf16, bool f32, bool paged, hipStream_t stream);
 
 }  // namespace fa

@@ -777,15 +777,39 @@ def fa_kvcache_decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cach
                           return_lse, out, workspace, stream, window, softcap, None, lse, d256=num_splits)
 
 
+def fa_kvcache_decode_d256_fp8(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None, k_scale=None,
+                               v_scale=None, causal: bool = False, scale: float | None = None, window=None, softcap: float = 0.0,
+                               return_lse: bool = False, out=None, workspace=None, num_splits: int = 0, out_dtype=None, stream=None,
+                               lse=None):
+    """fa_kvcache_decode_d256 against an fp8 cache (fa_kvcache_decode_d256_fp8): k_cache, v_cache (or the pools) contiguous
+    torch.float8_e4m3fn with d = 256, k_scale, v_scale float32 [Hkv] or None (1.0), read on the device only; an element is
+    decode(code) * scale[h].  Scales, logits and lse as in fa_kvcache_decode_varlen_fp8; rows, masks, splits, workspace and every
+    other argument as in fa_kvcache_decode_d256, whose bits the call returns on the widened cache when both scales are None.
+    The write half is fa_kvcache_append_varlen_d256_fp8.  workspace: at least kvcache_decode_d256_fp8_workspace_bytes(...)."""
+    if type(num_splits) is not int or num_splits < 0:
+        raise ValueError("num_splits must be an int >= 0 (0: the library's choice)")
+    return _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, out_dtype,
+                          return_lse, out, workspace, stream, window, softcap, None, lse, scales=(k_scale, v_scale), d256=num_splits)
+
+
 def kvcache_decode_d256_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, Ncap: int = 0, max_pages: int = 0,
-                                        page_size: int = 0, window: int = 0, num_splits: int = 0) -> int:
-    """Workspace of fa_kvcache_decode_d256: a contiguous cache gives Ncap, a paged one max_pages and page_size; 0 for one split.  The
-    C function judges the whole descriptor, so the tensors it never looks at stand in as a packed (max_seqlen_q, Hkv*G, 256) pair."""
+                                        page_size: int = 0, window: int = 0, num_splits: int = 0, fp8: bool = False) -> int:
+    """Workspace of fa_kvcache_decode_d256 (fp8: of fa_kvcache_decode_d256_fp8, the same number): a contiguous cache gives Ncap, a
+    paged one max_pages and page_size; 0 for one split.  The C function judges the whole descriptor, so the tensors it never looks at
+    stand in as a packed (max_seqlen_q, Hkv*G, 256) pair."""
     desc = capi.new_desc(capi.KvDecodeVarlenDesc)
     capi.fill(desc, Q=16, O=16, K=16, V=16, cu_seqlens_q=16, block_table=16 if max_pages or page_size else None, B=B, Hkv=Hkv, G=G, d=256,
               total_q=max(max_seqlen_q, 1), max_q=max_seqlen_q, Ncap=Ncap, max_pages=max_pages, page_size=page_size, num_pages=1,
-              q_stride_t=Hkv * G * 256, q_stride_h=256, o_stride_t=Hkv * G * 256, o_stride_h=256, window=window)
-    return int(capi.lib().fa_kvcache_decode_d256_workspace_bytes(desc, num_splits))
+              q_stride_t=Hkv * G * 256, q_stride_h=256, o_stride_t=Hkv * G * 256, o_stride_h=256, window=window,
+              kv_dtype=capi.KV_FP8_E4M3 if fp8 else capi.KV_16BIT)
+    fn = capi.lib().fa_kvcache_decode_d256_fp8_workspace_bytes if fp8 else capi.lib().fa_kvcache_decode_d256_workspace_bytes
+    return int(fn(desc, num_splits))
+
+
+def kvcache_decode_d256_fp8_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, Ncap: int = 0, max_pages: int = 0,
+                                            page_size: int = 0, window: int = 0, num_splits: int = 0) -> int:
+    """Workspace of fa_kvcache_decode_d256_fp8: kvcache_decode_d256_workspace_bytes of the same arguments."""
+    return kvcache_decode_d256_workspace_bytes(B, Hkv, G, max_seqlen_q, Ncap, max_pages, page_size, window, num_splits, fp8=True)
 
 
 def kvcache_decode_varlen_workspace_bytes(B: int, Hkv: int, G: int, max_seqlen_q: int, d: int, Ncap: int = 0, max_pages: int = 0,
@@ -803,7 +827,8 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     """The two packed decode front ends: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one; tree_mask is
     None (fa_kvcache_decode_varlen) or the words of fa_kvcache_decode_varlen_ex.  Shapes and dtypes are judged before anything needs a
     device.  attend: the call is fa_kvcache_attend_varlen_part(desc, parts) on the same descriptor, max_seqlen_q its threshold.
-    d256: None, or the num_splits of fa_kvcache_decode_d256, which runs on the same descriptor with d = 256."""
+    d256: None, or the num_splits of fa_kvcache_decode_d256 (with scales: of fa_kvcache_decode_d256_fp8), which runs on the same
+    descriptor with d = 256."""
     import torch
     fp8 = scales is not None
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
@@ -900,7 +925,7 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
         if d256 is None:
             need = kvcache_decode_varlen_workspace_bytes(B, Hkv, G, max_seqlen_q, d, Ncap, max_pages, page_size, window)
         else:
-            need = kvcache_decode_d256_workspace_bytes(B, Hkv, G, max_seqlen_q, Ncap, max_pages, page_size, window, d256)
+            need = kvcache_decode_d256_workspace_bytes(B, Hkv, G, max_seqlen_q, Ncap, max_pages, page_size, window, d256, fp8)
         if need:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
@@ -915,7 +940,7 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, workspace,
                                        tree_mask, *(scales or ()))):
         if d256 is not None:
-            code = capi.lib().fa_kvcache_decode_d256(desc, d256)
+            code = (capi.lib().fa_kvcache_decode_d256_fp8 if fp8 else capi.lib().fa_kvcache_decode_d256)(desc, d256)
         elif attend:
             code = capi.lib().fa_kvcache_attend_varlen_part(desc, parts)
         elif tree_mask is None:
@@ -924,7 +949,7 @@ def _decode_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
             opts = capi.new_desc(capi.KvDecodeTreeOpts)
             opts.tree_mask = tree_mask.data_ptr()
             code = capi.lib().fa_kvcache_decode_varlen_ex(desc, opts)
-    capi.check("fa_kvcache_decode_d256" if d256 is not None else "fa_kvcache_attend_varlen_part" if attend else
+    capi.check("fa_kvcache_decode_d256" + "_fp8" * fp8 if d256 is not None else "fa_kvcache_attend_varlen_part" if attend else
                "fa_kvcache_decode_varlen" if tree_mask is None else "fa_kvcache_decode_varlen_ex", code)
     return (out, lse) if return_lse else out
 
@@ -1243,11 +1268,30 @@ def fa_kvcache_append_varlen_fp8(k_new, v_new, k_cache, v_cache, cu_seqlens_new,
                    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), scales=(k_scale, v_scale), positions=positions)
 
 
+def fa_kvcache_append_varlen_d256(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None, block_table=None,
+                                  stream=None, *, q=None, q_out=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False,
+                                  positions=None) -> None:
+    """fa_kvcache_append_varlen at head dimension 256 (fa_kvcache_append_varlen_d256): the write half of fa_kvcache_decode_d256.
+    k_new, v_new (total_new, Hkv, 256), the caches [B,Hkv,Ncap,256] or the pools [num_pages,Hkv,page_size,256]; rot_dim any multiple of
+    16 up to 256.  Every argument, rule and byte is fa_kvcache_append_varlen's, positions included."""
+    _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), positions=positions, d256=True)
+
+
+def fa_kvcache_append_varlen_d256_fp8(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens=None, seqlens_out=None,
+                                      block_table=None, k_scale=None, v_scale=None, stream=None, *, q=None, q_out=None, rotary_cos=None,
+                                      rotary_sin=None, rotary_interleaved=False, positions=None) -> None:
+    """fa_kvcache_append_varlen_d256 into an fp8 cache, the write half of fa_kvcache_decode_d256_fp8: k_cache, v_cache (or the pools)
+    torch.float8_e4m3fn, k_scale, v_scale float32 [Hkv] or None (1.0); codes and scales as in fa_kvcache_append_varlen_fp8."""
+    _append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream,
+                   (q, q_out, rotary_cos, rotary_sin, rotary_interleaved), scales=(k_scale, v_scale), positions=positions, d256=True)
+
+
 def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, stream, rope, scales=None,
-                   positions=None):
-    """The two packed append front ends: scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one; rope is
-    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved); positions is None or the vector of fa_kvcache_append_varlen_ex.  Shapes
-    and dtypes are judged before anything needs a device."""
+                   positions=None, d256=False):
+    """The packed append front ends: scales is None (a 16-bit cache) or (k_scale, v_scale) of an fp8 one; rope is
+    (q, q_out, rotary_cos, rotary_sin, rotary_interleaved); positions is None or the vector of fa_kvcache_append_varlen_ex; d256
+    selects fa_kvcache_append_varlen_d256, which takes d = 256 alone.  Shapes and dtypes are judged before anything needs a device."""
     import torch
     fp8 = scales is not None
     paged = block_table is not None
@@ -1262,7 +1306,9 @@ def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, se
     dts = (torch.float16, torch.bfloat16)
     if k_new.dtype not in dts or v_new.dtype != k_new.dtype:
         raise ValueError("k_new, v_new must both be fp16 or both bf16")
-    if d not in (64, 128) or total <= 0 or Hkv <= 0:
+    if d256 and d != 256:
+        raise ValueError("d must be 256 (d in {64,128} is fa_kvcache_append_varlen's)")
+    if (not d256 and d not in (64, 128)) or total <= 0 or Hkv <= 0:
         raise ValueError("d must be 64 or 128, and k_new must not be empty")
     if k_dst.dim() != 4 or v_dst.shape != k_dst.shape or k_dst.shape[1] != Hkv or k_dst.shape[3] != d or k_dst.numel() == 0:
         raise ValueError("k_cache and v_cache must both be [B,Hkv,Ncap,d], or with block_table [num_pages,Hkv,page_size,d], with k_new's "
@@ -1347,13 +1393,18 @@ def _append_varlen(k_new, v_new, k_dst, v_dst, cu_seqlens_new, cache_seqlens, se
         k_stride_t=kt, k_stride_h=kh, v_stride_t=vt, v_stride_h=vh, stream=_stream_ptr(stream), **rope_fields)
     with torch.cuda.device(_one_device(k_new, v_new, k_dst, v_dst, cu_seqlens_new, block_table, *(scales or ()), cache_seqlens, seqlens_out,
                                        positions, *rope_tensors)):
-        if positions is None:
-            code = capi.lib().fa_kvcache_append_varlen(desc)
-        else:
+        opts = None
+        if positions is not None:
             opts = capi.new_desc(capi.KvAppendVarlenOpts)
             opts.positions = positions.data_ptr()
+        if d256:
+            code = capi.lib().fa_kvcache_append_varlen_d256(desc, opts)
+        elif positions is None:
+            code = capi.lib().fa_kvcache_append_varlen(desc)
+        else:
             code = capi.lib().fa_kvcache_append_varlen_ex(desc, opts)
-    capi.check("fa_kvcache_append_varlen" if positions is None else "fa_kvcache_append_varlen_ex", code)
+    capi.check("fa_kvcache_append_varlen_d256" if d256 else "fa_kvcache_append_varlen" if positions is None else
+               "fa_kvcache_append_varlen_ex", code)
 
 
 def tree_from_parents(parents, cu_seqlens):

@@ -73,6 +73,14 @@ eager fallback.  Registered on first use:
     # decode_varlen at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks; num_splits 0 = the library's choice
     o, lse = torch.ops.fa_mi355.decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
                                             window, softcap, num_splits, out_f32)
+    # ... against an fp8 (e4m3fn) cache (ops.fa_kvcache_decode_d256_fp8): k_scale, v_scale follow block_table
+    o, lse = torch.ops.fa_mi355.decode_d256_fp8(q, k_cache8, v_cache8, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_scale,
+                                                v_scale, scale, causal, window, softcap, num_splits, out_f32)
+    # ... and its write half (ops.fa_kvcache_append_varlen_d256, _fp8): append_varlen's and append_varlen_fp8's lists, d = 256
+    torch.ops.fa_mi355.append_varlen_d256(k_new, v_new, k_cache, v_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, q,
+                                          q_out, rotary_cos, rotary_sin, interleaved)
+    torch.ops.fa_mi355.append_varlen_d256_fp8(k_new, v_new, k_cache8, v_cache8, cu_seqlens_new, cache_seqlens, seqlens_out, block_table,
+                                              k_scale, v_scale, q, q_out, rotary_cos, rotary_sin, interleaved)
     # the varlen prefill at head dimension 256 (ops.fa_forward_varlen_d256, ops.fa_forward_varlen_kvcache_d256): no sinks
     o, lse = torch.ops.fa_mi355.forward_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, softcap, out_f32)
     o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, scale, causal,
@@ -91,7 +99,7 @@ def register() -> None:
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
     .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256,
-    .forward_varlen_d256 and .forward_varlen_kvcache_d256."""
+    .decode_d256_fp8, .append_varlen_d256, .append_varlen_d256_fp8, .forward_varlen_d256 and .forward_varlen_kvcache_d256."""
     global _registered
     if _registered:
         return
@@ -199,7 +207,9 @@ def register() -> None:
                     "Tensor(c!)? seqlens_out, Tensor? block_table, "
     VARLEN_APPEND_TAIL = "Tensor(d!)? q, Tensor(e!)? q_out, Tensor? rotary_cos, Tensor? rotary_sin, bool interleaved) -> ()"
     for name, mid, fn in (("append_varlen", "", ops.fa_kvcache_append_varlen),
-                          ("append_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_append_varlen_fp8)):
+                          ("append_varlen_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_append_varlen_fp8),
+                          ("append_varlen_d256", "", ops.fa_kvcache_append_varlen_d256),
+                          ("append_varlen_d256_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_append_varlen_d256_fp8)):
         define(name, VARLEN_APPEND + mid + VARLEN_APPEND_TAIL, ("k_cache", "v_cache", "seqlens_out", "q", "q_out"), fn, "----c",
                varlen_append_kw, lambda *args: None)
 
@@ -315,11 +325,19 @@ def register() -> None:
                decode_varlen_kw, varlen_fake)
 
     # the same at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks, and `int num_splits` in front of out_f32
-    define("decode_d256", DECODE_VARLEN + "float scale, bool causal, int window, float softcap, int num_splits, bool out_f32) -> "
-           "(Tensor, Tensor)", (), decode_varlen(ops.fa_kvcache_decode_d256), "-ccc-oo",
-           lambda q, scale, causal, window, softcap, num_splits, out_f32: dict(
-               causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
-               softcap=softcap, num_splits=num_splits), varlen_fake)
+    # ... and against an fp8 cache (ops.fa_kvcache_decode_d256_fp8): `Tensor? k_scale, Tensor? v_scale` behind block_table
+    def decode_d256_kw(q, *rest):
+        *scales, scale, causal, window, softcap, num_splits, out_f32 = rest
+        kw = dict(causal=causal, scale=scale, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q), window=window,
+                  softcap=softcap, num_splits=num_splits)
+        if scales:
+            kw.update(k_scale=opt(scales[0]), v_scale=opt(scales[1]))
+        return kw
+
+    for name, mid, fn in (("decode_d256", "", ops.fa_kvcache_decode_d256),
+                          ("decode_d256_fp8", "Tensor? k_scale, Tensor? v_scale, ", ops.fa_kvcache_decode_d256_fp8)):
+        define(name, DECODE_VARLEN + mid + "float scale, bool causal, int window, float softcap, int num_splits, bool out_f32) -> "
+               "(Tensor, Tensor)", (), decode_varlen(fn), "-ccc-oo", decode_d256_kw, varlen_fake)
 
     # the varlen prefill at head dimension 256 (ops.fa_forward_varlen_d256, ops.fa_forward_varlen_kvcache_d256): forward_varlen_ex and
     # forward_varlen_kvcache without `Tensor? sinks`

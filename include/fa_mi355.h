@@ -1136,11 +1136,50 @@ int    fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale);
  * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_decode_varlen refuses for this descriptor, with
  * "d in {64,128}" replaced by d != 256; kv_dtype != FA_KV_16BIT; a non-null k_scale, v_scale or sinks; num_splits < 0 or above the
  * tile count; with S > 1 a workspace that is NULL, too small or misaligned.
- * Not part of these entries: an fp8 cache, sinks, a tree mask, the routed / mixed step, a shared prefix, fa_merge_states at d = 256,
- * an append at d = 256 (the append entries keep refusing it).  The tiled prefill at d = 256 is fa_forward_varlen_d256's and
- * fa_forward_varlen_kvcache_d256's, below.  NOT reference entry points. */
+ * Not part of these entries: sinks, a tree mask, the routed / mixed step, a shared prefix, fa_merge_states at d = 256.  An fp8 cache
+ * is fa_kvcache_decode_d256_fp8's and the append at d = 256 fa_kvcache_append_varlen_d256's, both below (the d <= 128 append entries
+ * keep refusing d = 256).  The tiled prefill at d = 256 is fa_forward_varlen_d256's and fa_forward_varlen_kvcache_d256's, below.
+ * NOT reference entry points. */
 size_t fa_kvcache_decode_d256_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits);
 int    fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_splits);
+
+/* fa_kvcache_decode_d256 on an fp8 cache.  The descriptor is fa_kvdecode_varlen_desc as it is, with d = 256 and kv_dtype =
+ * FA_KV_FP8_E4M3: K, V address one OCP e4m3fn byte per element, [B,Hkv,Ncap,256] or pools [num_pages,Hkv,page_size,256] behind
+ * block_table; k_scale, v_scale are device pointers to Hkv fp32 each, 4-byte aligned, or NULL (= 1.0), read on the device so that a
+ * captured call follows them; an element's value is decode(code) * scale[h].  The caller's contract is finite scales > 0.
+ * Every rule of fa_kvcache_decode_d256 holds word for word: packed Q / O / lse cut by cu_seqlens_q on the device, lengths and table
+ * read on the device, the causal tail, the window, the soft-cap before the masks, tokens of no sequence never touched, n_b = 0 reads
+ * nothing, a live row without a key is O = 0 and lse = -inf, a bad live page reads as zeros, paged and contiguous calls are bit-equal,
+ * nothing is read on the host.  Rows at or past L_b, rows below start_b and pages no visible key lies in may hold the NaN codes
+ * 0x7F / 0xFF: they lie outside the buffer descriptors or are zeroed as raw bytes, and reach LDS as the code 0 (+0).
+ * The codes are widened EXACTLY to Q's type on their way into LDS and everything behind that is fa_kvcache_decode_d256's arithmetic:
+ *   s_j = (scale * k_scale[h]) * q . code_j      O = v_scale[h] * sum_j softmax(s)_j * code_j
+ * The factor is clamped after the product (scale = 0 still gives uniform weights); under the soft-cap k_scale multiplies the score
+ * before the cap; v_scale joins 1 / l, in the merge's final division behind a split.  With both scales NULL the result has the bits
+ * of fa_kvcache_decode_d256 on the widened cache, for every split count.
+ * The split rule, the grid and the workspace are the 16-bit entry's for the same descriptor: fa_kvcache_decode_d256_fp8_workspace_bytes
+ * equals fa_kvcache_decode_d256_workspace_bytes on the descriptor with kv_dtype = FA_KV_16BIT and null scales (the capacity bound
+ * stays (capacity + 64) * 512 < 2^32).
+ * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_decode_d256 refuses, with "kv_dtype != FA_KV_16BIT,
+ * non-null scales" replaced by kv_dtype != FA_KV_FP8_E4M3; a scale pointer that is not 4-byte aligned; sinks.
+ * Not part of this entry: per-token scales, an fp8 Q, fp8 matrix instructions, fa_forward_varlen_kvcache_d256 on an fp8 cache (a
+ * prompt is prefilled with fa_forward_varlen_d256 on the packed 16-bit K/V and written by the fp8 append).  NOT reference entry points. */
+size_t fa_kvcache_decode_d256_fp8_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits);
+int    fa_kvcache_decode_d256_fp8(const fa_kvdecode_varlen_desc* desc, int num_splits);
+
+/* fa_kvcache_append_varlen_ex at head dimension 256: the write half of fa_kvcache_decode_d256 and fa_kvcache_decode_d256_fp8, so that
+ * append -> decode at d = 256 is one captured two-launch step.  fa_kvappend_varlen_desc and fa_kvappend_varlen_opts as they are, with
+ * d = 256; opts may be NULL.  All eight forms are taken -- contiguous or paged, FA_KV_16BIT (rows of 512 bytes) or FA_KV_FP8_E4M3
+ * (rows of 256 codes), plain or rotary in both pair conventions, rot_dim any multiple of 16 up to 256 -- and positions.  Every rule
+ * and every byte of fa_kvcache_append_varlen_ex holds: cu_seqlens_new clamped and searched on the device, token i of sequence b to
+ * slot L_b + i, the drops at the capacity and behind a bad table entry, 64-bit page addresses, the fp8 recipe, the pinned rotary
+ * arithmetic, Q rotated through its own strides, seqlens_out, rows of no sequence never read and their Qout never written.
+ * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_append_varlen[_ex] refuse, with "d not in {64,128}"
+ * replaced by d != 256, and a capacity with (capacity + 64) * 512 >= 2^32 (the d = 256 decode's bound: the append takes exactly the
+ * caches that decode takes).  fa_kvcache_append_varlen, _ex and the padded append entries keep refusing d = 256.
+ * Not part of this entry: the padded fa_kvcache_append_ex, fa_kvcache_commit and fa_merge_states at d = 256.  NOT a reference entry
+ * point. */
+int fa_kvcache_append_varlen_d256(const fa_kvappend_varlen_desc* desc, const fa_kvappend_varlen_opts* opts);
 
 /* The variable-length prefill at head dimension 256: fa_forward_varlen_ex and fa_forward_varlen_kvcache for the head
  * fa_kvcache_decode_d256 decodes, so that a d = 256 cache filled by any means is prefilled (prompts, chunked prefill, prefix
@@ -1164,7 +1203,7 @@ int    fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_split
  * hipErrorInvalidValue, before the device is touched: everything fa_forward_varlen_ex resp. fa_forward_varlen_kvcache refuse, with
  * "d not in {64,128}" replaced by d != 256; non-null sinks; and for the cache form the capacity bound of fa_kvcache_decode_d256,
  * (capacity + 64) * 512 >= 2^32.  fa_forward_varlen, _ex, _kvcache and _kvcache_fp8 keep refusing d = 256.
- * Not part of these entries: the append at d = 256, fp8 caches, sinks, the routed mixed step, a tree mask, key splits,
+ * Not part of these entries: fp8 caches (the append and the decode at d = 256 take them, above; the cache form here does not yet), sinks, the routed mixed step, a tree mask, key splits,
  * fa_merge_states at d = 256.  NOT reference entry points. */
 int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts);   /* opts may be NULL */
 int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc);
