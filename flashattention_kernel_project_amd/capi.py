@@ -295,6 +295,7 @@ def _signatures() -> dict:
         # the varlen prefill at head dimension 256, packed and against the cache: the descriptors above with d = 256, no sinks
         "fa_forward_varlen_d256": (i, [C.POINTER(VarlenDesc), C.POINTER(VarlenOpts)]),
         "fa_forward_varlen_kvcache_d256": (i, [C.POINTER(VarlenKvcacheDesc)]),
+        "fa_forward_varlen_kvcache_d256_fp8": (i, [C.POINTER(VarlenKvcacheDesc), C.c_void_p, C.c_void_p]),
     }
     for paged in (False, True):
         for fp8 in (False, True):

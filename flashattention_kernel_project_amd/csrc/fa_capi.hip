@@ -368,6 +368,10 @@ FA_EXPORT int fa_kvcache_append_varlen_d256(const fa_kvappend_varlen_desc* desc,
 
 FA_EXPORT int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts) { return (int)fa::varlen256_dispatch(desc, opts); }
 FA_EXPORT int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc) { return (int)fa::varlen256_cache_dispatch(desc); }
+FA_EXPORT int fa_forward_varlen_kvcache_d256_fp8(const fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale)
+{
+    return (int)fa::varlen256_cache_dispatch_fp8(desc, k_scale, v_scale);
+}
 
 FA_EXPORT int fa_kvcache_attend_varlen_part(const fa_kvdecode_varlen_desc* desc, int parts) { return (int)fa::kvattend_dispatch(desc, parts); }
 FA_EXPORT int fa_kvcache_attend_varlen(const fa_kvdecode_varlen_desc* desc)

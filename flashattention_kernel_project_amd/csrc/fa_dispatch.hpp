@@ -255,6 +255,9 @@ size_t kv256_workspace_bytes(const ::fa_kvdecode_varlen_desc* desc, int num_spli
 // of fa_forward_varlen_ex and fa_forward_varlen_kvcache, which must name d = 256 and no sinks; opts may be null
 hipError_t varlen256_dispatch(const ::fa_varlen_desc* desc, const ::fa_varlen_opts* opts);
 hipError_t varlen256_cache_dispatch(const ::fa_varlen_kvcache_desc* desc);
+// fa_forward_varlen_kvcache_d256_fp8: the same checks (K and V at one byte per element) and the one launch on an e4m3fn cache, the
+// kernels of fa_fwd_varlen256_fp8.hip; k_scale, v_scale: device pointers to Hkv fp32 each, 4-byte aligned, or null (1.0)
+hipError_t varlen256_cache_dispatch_fp8(const ::fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale);
 // fa_merge_states (fa_merge_states.hip): the checks and the one launch; the descriptor is the public one, as it is
 hipError_t merge_states_dispatch(const ::fa_merge_desc* desc);
 // fa_forward_varlen (fa_fwd_varlen.hip): the checks and the one launch; the descriptor is the public one, as it is

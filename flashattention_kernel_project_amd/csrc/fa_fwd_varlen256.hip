@@ -1,4 +1,5 @@
-// fa_fwd_varlen256.hip -- fa_forward_varlen_d256 and fa_forward_varlen_kvcache_d256: the variable-length prefill at head dimension
+// fa_fwd_varlen256.hip -- fa_forward_varlen_d256, fa_forward_varlen_kvcache_d256 and the checks of
+// fa_forward_varlen_kvcache_d256_fp8 (its kernels: fa_fwd_varlen256_fp8.hip): the variable-length prefill at head dimension
 // 256 (the Gemma-2 / Gemma-3 head), K/V token-packed or in the KV cache, contiguous or paged, with the causal mask, the sliding
 // window and the soft-cap.  The descriptors are fa_forward_varlen_ex's and fa_forward_varlen_kvcache's as they are; the entries are
 // new because those keep refusing d = 256.  The kernel template is fa_fwd_varlen256_kernel.hpp's; this unit owns the host checks and
@@ -54,15 +55,43 @@ bool varlen256_options(int window, float softcap, varlen256::Dev& a)
     return true;
 }
 
-template <int kForm> hipError_t varlen256_launch(const varlen256::Dev& a, dim3 grid, int in_dtype, int out_dtype, void* stream)
+// The cache entries' one body.  fp8: K and V address one e4m3fn byte per element (the tensor checks take an element size of 1; the
+// capacity bound stays the 16-bit one, so both entries accept the same descriptors) and the scales are device pointers, null or
+// 4-byte aligned.
+hipError_t varlen256_cache_run(const ::fa_varlen_kvcache_desc* d, bool fp8, const float* k_scale, const float* v_scale)
 {
-    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
-        auto kernel = fa_fwd_varlen256_kernel<decltype(t), decltype(f32)::value, kForm>;
-        const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), varlen256::kLdsBytes);
-        if (attr != hipSuccess) return attr;
-        FA_LAUNCH(kernel, grid, dim3(64 * kVarlenWaves), (size_t)varlen256::kLdsBytes, static_cast<hipStream_t>(stream), a);
-        return launch_status();
-    });
+    if (!d || d->size != sizeof(fa_varlen_kvcache_desc)) return hipErrorInvalidValue;
+    if (d->sinks) return hipErrorInvalidValue;   // no sinks at d = 256
+    if (!d->cu_seqlens_q || !d->seqlens_k) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3u) return hipErrorInvalidValue;
+    varlen256::Dev a;
+    dim3 grid;
+    if (!varlen256_common(d, a, grid)) return hipErrorInvalidValue;
+    // the capacity: the paged decode entries' conditions on the page geometry, or a positive Ncap
+    int Ncap = d->Ncap;
+    if (d->block_table) {
+        a.lg_page = page_log2(d->page_size);
+        if (a.lg_page < 0 || d->num_pages <= 0 || d->max_pages <= 0) return hipErrorInvalidValue;
+        if ((long long)d->max_pages * d->page_size > 0x7FFFFFFFll) return hipErrorInvalidValue;   // the capacity is an int
+        Ncap = d->max_pages * d->page_size;
+        a.max_pages = d->max_pages;
+        a.num_pages = d->num_pages;
+    }
+    if (Ncap <= 0) return hipErrorInvalidValue;
+    // the d = 256 decode's bound on a head's bytes; it keeps every key index and limit of the kernel far inside an int
+    if (((unsigned long long)Ncap + varlen256::kTile) * varlen256::kRowBytes >= (1ull << 32)) return hipErrorInvalidValue;
+    const unsigned es = fp8 ? 1u : 2u;
+    if (!varlen_tensor_ok(d->K, Ncap, 1, d->d, d->d, 0, es) || !varlen_tensor_ok(d->V, Ncap, 1, d->d, d->d, 0, es))
+        return hipErrorInvalidValue;
+    a.seqlens = d->seqlens_k;
+    a.table = d->block_table;
+    a.total_k = Ncap;
+    a.k_scale = k_scale;
+    a.v_scale = v_scale;
+    if (!varlen256_options(d->window, d->softcap, a)) return hipErrorInvalidValue;
+    if (fp8) return varlen256_launch_fp8(a, grid, d->in_dtype, d->out_dtype, d->block_table != nullptr, d->stream);
+    return d->block_table ? varlen256_launch<varlen256::kPaged, false>(a, grid, d->in_dtype, d->out_dtype, d->stream)
+                          : varlen256_launch<varlen256::kContig, false>(a, grid, d->in_dtype, d->out_dtype, d->stream);
 }
 
 }  // namespace
@@ -82,38 +111,14 @@ hipError_t varlen256_dispatch(const ::fa_varlen_desc* d, const ::fa_varlen_opts*
     a.total_k = d->total_k;
     a.k_st = d->k_stride_t, a.k_sh = d->k_stride_h, a.v_st = d->v_stride_t, a.v_sh = d->v_stride_h;
     if (!varlen256_options(o ? o->window : 0, o ? o->softcap : 0.0f, a)) return hipErrorInvalidValue;
-    return varlen256_launch<varlen256::kPacked>(a, grid, d->in_dtype, d->out_dtype, d->stream);
+    return varlen256_launch<varlen256::kPacked, false>(a, grid, d->in_dtype, d->out_dtype, d->stream);
 }
 
-hipError_t varlen256_cache_dispatch(const ::fa_varlen_kvcache_desc* d)
+hipError_t varlen256_cache_dispatch(const ::fa_varlen_kvcache_desc* d) { return varlen256_cache_run(d, false, nullptr, nullptr); }
+
+hipError_t varlen256_cache_dispatch_fp8(const ::fa_varlen_kvcache_desc* d, const float* k_scale, const float* v_scale)
 {
-    if (!d || d->size != sizeof(fa_varlen_kvcache_desc)) return hipErrorInvalidValue;
-    if (d->sinks) return hipErrorInvalidValue;   // no sinks at d = 256
-    if (!d->cu_seqlens_q || !d->seqlens_k) return hipErrorInvalidValue;
-    varlen256::Dev a;
-    dim3 grid;
-    if (!varlen256_common(d, a, grid)) return hipErrorInvalidValue;
-    // the capacity: the paged decode entries' conditions on the page geometry, or a positive Ncap
-    int Ncap = d->Ncap;
-    if (d->block_table) {
-        a.lg_page = page_log2(d->page_size);
-        if (a.lg_page < 0 || d->num_pages <= 0 || d->max_pages <= 0) return hipErrorInvalidValue;
-        if ((long long)d->max_pages * d->page_size > 0x7FFFFFFFll) return hipErrorInvalidValue;   // the capacity is an int
-        Ncap = d->max_pages * d->page_size;
-        a.max_pages = d->max_pages;
-        a.num_pages = d->num_pages;
-    }
-    if (Ncap <= 0) return hipErrorInvalidValue;
-    // the d = 256 decode's bound on a head's bytes; it keeps every key index and limit of the kernel far inside an int
-    if (((unsigned long long)Ncap + varlen256::kTile) * varlen256::kRowBytes >= (1ull << 32)) return hipErrorInvalidValue;
-    if (!varlen_tensor_ok(d->K, Ncap, 1, d->d, d->d, 0, 2u) || !varlen_tensor_ok(d->V, Ncap, 1, d->d, d->d, 0, 2u))
-        return hipErrorInvalidValue;
-    a.seqlens = d->seqlens_k;
-    a.table = d->block_table;
-    a.total_k = Ncap;
-    if (!varlen256_options(d->window, d->softcap, a)) return hipErrorInvalidValue;
-    return d->block_table ? varlen256_launch<varlen256::kPaged>(a, grid, d->in_dtype, d->out_dtype, d->stream)
-                          : varlen256_launch<varlen256::kContig>(a, grid, d->in_dtype, d->out_dtype, d->stream);
+    return varlen256_cache_run(d, true, k_scale, v_scale);
 }
 
 }  // namespace fa

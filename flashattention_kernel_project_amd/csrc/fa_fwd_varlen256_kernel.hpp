@@ -27,7 +27,15 @@
 //   * causal, window and soft-cap are runtime and wave-uniform (kernel arguments, scalar registers): 12 instantiations, type x output
 //     x {packed, contiguous, paged}.  "No window" is a W that masks nothing (the host's clamp); cap2 == 0 skips the cap by a branch.
 // Tiles stay at absolute multiples of 64 keys from key 0 and the three forms differ in where a row comes from alone, so on the same
-// finite keys they return the same bits.  Private to csrc/.
+// finite keys they return the same bits.
+// kFp8 (fa_forward_varlen_kvcache_d256_fp8, the 8 cache instantiations of fa_fwd_varlen256_fp8.hip): K and V address
+// one e4m3fn byte per element.  Only the staging differs: an 8-row group is 2 KiB, two 16-byte loads per lane by kv256's e4m3fn lane
+// map (fp8_row, fp8_ld_off: two rows to a quarter wave, so every ds_write_b128 round keeps 16 slots), the descriptors cover
+// (rows - 1) * 256 + 256 bytes, so what lies outside them reads as the code 0 (+0) whatever NaN codes memory holds, the rows of the
+// first tile below lo_wg are zeroed as raw bytes, and the raw bytes wait in 32 registers through the tile's arithmetic and are
+// widened exactly to T (fp8x16_widen) in stage_write, into the same images.  k_scale[hkv] joins the logit factor before the clamp and
+// the cap's constant, v_scale[hkv] joins 1 / l.  With both null every factor keeps its bits: the 16-bit kernel's result on the widened
+// cache.  Private to csrc/.
 #pragma once
 #include "fa_fwd_kv256_kernel.hpp"    // kv256::img_off, swz and the image constants
 #include "fa_fwd_varlen_kernel.hpp"   // varlen_bounds, varlen_rsrc, the slot constants
@@ -61,16 +69,18 @@ struct Dev {
     float scale_log2e;
     float cap2, cap_rk;                  // softcap * log2(e) and 2 / softcap; 0: no cap
     int causal, window;                  // window >= 1: "none" comes in as total_q + total_k
+    const float *k_scale, *v_scale;      // kFp8 only: [Hkv] on the device, or nullptr (1.0).  Last, so that no other field moves
 };
 }  // namespace varlen256
 
-template <typename T, bool kOutF32, int kForm>
+template <typename T, bool kOutF32, int kForm, bool kFp8 = false>
 __global__ __launch_bounds__(64 * kVarlenWaves, 1)
 void fa_fwd_varlen256_kernel(varlen256::Dev a)
 {
     using namespace varlen256;
     using kv256::img_off;
     using kv256::swz;
+    static_assert(!kFp8 || kForm != kPacked, "an e4m3fn source is a cache");
     constexpr unsigned W = kVarlenWaves, BM = kVarlenRows;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const bool causal = a.causal != 0;
@@ -125,7 +135,11 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
     const unsigned seen = hi_row > lo_row ? hi_row - lo_row : 0u;
 
     // ---- Q^T fragments (B operand of S^T = K.Q^T), resident for the whole kernel; rows at or past Lq are zeros ----
-    const float c = fmaxf(fabsf(a.scale_log2e), 1.17549435e-38f);   // a scale of 0 must not meet a masked -inf as 0 * -inf
+    float sl2 = a.scale_log2e;
+    if constexpr (kFp8) {
+        if (a.k_scale) sl2 *= a.k_scale[hkv];   // before the clamp, and under a cap what the cap sees
+    }
+    const float c = fmaxf(fabsf(sl2), 1.17549435e-38f);   // a scale of 0 must not meet a masked -inf as 0 * -inf
     const unsigned q_flip = a.scale_log2e < 0.0f ? 0x80008000u : 0u;
     // what a score is multiplied by on its way into the vote and the exponent (1 once the cap has made the scores final), and the
     // cap's two constants, in scalar registers
@@ -143,17 +157,25 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
 
     // ---- staging: group g of the tile's 8-row groups that this wave loads is group g * W + wave; lane idx = lane + 64 p of a group is
     // chunk idx % 32 = r of row idx / 32 = 2 p + h, which in a cache is byte idx * 16 of the group ----
-    unsigned l_off[kGroupLoads];
+    // kFp8: kv256's e4m3fn lane map -- load p of a lane is the 16 codes j + 8 p of row fp8_row(lane) of the group, which widened are
+    // the chunks 2 (j + 8 p) and the one after it of that row: l_off[0] is chunk 2 j in the image, the odd chunk lies at l_off[0] ^ 16
+    constexpr int kLoads = kFp8 ? kv256::kGroupLoads8 : kGroupLoads;   // 2 or 4 16-byte loads per lane, group and tensor
+    constexpr unsigned kSrcRow = kFp8 ? kv256::kRowBytes8 : kRowBytes;  // bytes of a cache row
+    unsigned l_off[kFp8 ? 1 : kGroupLoads];
+    if constexpr (kFp8) {
+        l_off[0] = img_off(wave * 8u + kv256::fp8_row(lane), 2u * (lane & 7u));
+    } else {
 #pragma unroll
-    for (int p = 0; p < kGroupLoads; ++p) l_off[p] = img_off(wave * 8u + 2u * p + h, r);   // swz has period 16: g adds 32 rows
+        for (int p = 0; p < kGroupLoads; ++p) l_off[p] = img_off(wave * 8u + 2u * p + h, r);   // swz has period 16: g adds 32 rows
+    }
     const char *kbase = a.K, *vbase = a.V;
     if constexpr (kForm == kContig) {
-        kbase += ((size_t)b * (unsigned)a.Hkv + hkv) * (unsigned)a.total_k * kRowBytes;
-        vbase += ((size_t)b * (unsigned)a.Hkv + hkv) * (unsigned)a.total_k * kRowBytes;
+        kbase += ((size_t)b * (unsigned)a.Hkv + hkv) * (unsigned)a.total_k * kSrcRow;
+        vbase += ((size_t)b * (unsigned)a.Hkv + hkv) * (unsigned)a.total_k * kSrcRow;
     }
     // packed: the (sequence, head) view starts (sk * stride_t + hkv * stride_h) elements in, and a token row is stride_t elements
-    // (every offset of an existing row fits 32 bits: checked on the host); a cache row is 512 bytes
-    unsigned k_stb = kRowBytes, v_stb = kRowBytes;
+    // (every offset of an existing row fits 32 bits: checked on the host); a cache row is 512 bytes, or 256 codes
+    unsigned k_stb = kSrcRow, v_stb = kSrcRow;
     if constexpr (kForm == kPacked) {
         k_stb = (unsigned)a.k_st * 2u;
         v_stb = (unsigned)a.v_st * 2u;
@@ -161,13 +183,17 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
         vbase += ((long long)sk * a.v_st + (long long)hkv * a.v_sh) * 2;
     }
     // the lane's byte offset inside a group, per tensor (the same register for both in a cache)
-    unsigned k_off[kGroupLoads], v_off[kGroupLoads];
+    unsigned k_off[kLoads], v_off[kLoads];
 #pragma unroll
-    for (int p = 0; p < kGroupLoads; ++p) {
-        k_off[p] = (2u * p + h) * k_stb + r * 16u;
-        v_off[p] = (2u * p + h) * v_stb + r * 16u;
+    for (int p = 0; p < kLoads; ++p) {
+        if constexpr (kFp8) {
+            k_off[p] = v_off[p] = kv256::fp8_ld_off(lane) + 128u * p;
+        } else {
+            k_off[p] = (2u * p + h) * k_stb + r * 16u;
+            v_off[p] = (2u * p + h) * v_stb + r * 16u;
+        }
     }
-    u32x4 kst[kGroups][kGroupLoads], vst[kGroups][kGroupLoads];
+    u32x4 kst[kGroups][kLoads], vst[kGroups][kLoads];   // kFp8: the raw codes, 32 registers where the 16-bit tile takes 64
     // paged: the page numbers of the tile that is staged next, one per (wave, group), in scalar registers.  Only called with Lk >= 1;
     // the entry index is clamped to [page of lo_wg, last live page] (lo_wg < Lk whenever a tile is streamed), so no entry at or past
     // ceil(Lk / page) and no entry of a page wholly below the window is read, and a tile index past the last tile is harmless
@@ -185,7 +211,7 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
     };
     // One descriptor per (wave, group) and tensor: it starts at the group's first row and ends with its last row below Lk, so the
     // loads of the rows past it read 0 whatever memory holds: offset j * stride + 16 r of row j >= rows lies at or past the
-    // (rows - 1) * stride + 512 bytes of the range.  (Packed, with a token stride beyond 2^29 bytes such an offset may wrap 32 bits
+    // (rows - 1) * stride + 512 bytes of the range (kFp8: offset j * 256 + ... at or past rows * 256; what is not read is the code 0).  (Packed, with a token stride beyond 2^29 bytes such an offset may wrap 32 bits
     // into the range: it then reads a live row of the same sequence, whose score is masked.)
     auto stage_load = [&](unsigned kv0) {
 #pragma unroll
@@ -201,32 +227,49 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
                 row0 = (((size_t)(unsigned)pg[g] * (unsigned)a.Hkv + hkv) << a.lg_page) + (kg & ((1u << a.lg_page) - 1u));
             }
             if (!rows) row0 = 0;
-            const __amdgpu_buffer_rsrc_t rk = make_rsrc(kbase + row0 * k_stb, rows ? (rows - 1u) * k_stb + kRowBytes : 0u),
-                                         rv = make_rsrc(vbase + row0 * v_stb, rows ? (rows - 1u) * v_stb + kRowBytes : 0u);
+            const __amdgpu_buffer_rsrc_t rk = make_rsrc(kbase + row0 * k_stb, rows ? (rows - 1u) * k_stb + kSrcRow : 0u),
+                                         rv = make_rsrc(vbase + row0 * v_stb, rows ? (rows - 1u) * v_stb + kSrcRow : 0u);
 #pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) {
+            for (int p = 0; p < kLoads; ++p) {
                 kst[g][p] = buf_load16(rk, k_off[p]);
                 vst[g][p] = buf_load16(rv, v_off[p]);
             }
         }
     };
-    // a cache under a window: the rows of the first streamed tile below lo_wg go to LDS as zeros (workgroup-uniform, tile t0 only)
+    // a cache under a window: the rows of the first streamed tile below lo_wg go to LDS as zeros (workgroup-uniform, tile t0 only).
+    // kFp8: the raw bytes are zeroed -- the code 0 is +0 -- by the e4m3fn lane-to-row map, which does not depend on p
     [[maybe_unused]] auto stage_zero_below = [&](unsigned kv0) {
         if (kv0 < lo_wg) {
 #pragma unroll
             for (int g = 0; g < kGroups; ++g)
 #pragma unroll
-                for (int p = 0; p < kGroupLoads; ++p)
-                    if (kv0 + (g * W + wave) * 8u + 2u * p + h < lo_wg) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                for (int p = 0; p < kLoads; ++p) {
+                    if constexpr (kFp8) {
+                        if (kv0 + (g * W + wave) * 8u + kv256::fp8_row(lane) < lo_wg) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                    } else {
+                        if (kv0 + (g * W + wave) * 8u + 2u * p + h < lo_wg) kst[g][p] = vst[g][p] = u32x4{0u, 0u, 0u, 0u};
+                    }
+                }
         }
     };
     auto stage_write = [&](unsigned buf) {
 #pragma unroll
         for (int g = 0; g < kGroups; ++g)
 #pragma unroll
-            for (int p = 0; p < kGroupLoads; ++p) {
-                lds_write16(smem, buf * kBufBytes + g * (W * 8 * kRowBytes) + l_off[p], kst[g][p]);
-                lds_write16(smem, buf * kBufBytes + kImgBytes + g * (W * 8 * kRowBytes) + l_off[p], vst[g][p]);
+            for (int p = 0; p < kLoads; ++p) {
+                if constexpr (kFp8) {   // one load is the row's chunks 2 c and 2 c + 1, c = j + 8 p: the even round, then the odd one
+                    const unsigned at = buf * kBufBytes + g * (W * 8 * kRowBytes) + p * 256u;   // a multiple of 256
+                    u32x4 klo, khi, vlo, vhi;
+                    fp8x16_widen<T>(kst[g][p], klo, khi);
+                    fp8x16_widen<T>(vst[g][p], vlo, vhi);
+                    lds_write16(smem, at + l_off[0], klo);
+                    lds_write16(smem, at + (l_off[0] ^ 16u), khi);
+                    lds_write16(smem, kImgBytes + at + l_off[0], vlo);
+                    lds_write16(smem, kImgBytes + at + (l_off[0] ^ 16u), vhi);
+                } else {
+                    lds_write16(smem, buf * kBufBytes + g * (W * 8 * kRowBytes) + l_off[p], kst[g][p]);
+                    lds_write16(smem, buf * kBufBytes + kImgBytes + g * (W * 8 * kRowBytes) + l_off[p], vst[g][p]);
+                }
             }
     };
 
@@ -361,7 +404,10 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
     if (!row_live) return;                             // rows at or past Lq are the next sequence's, or nobody's
     const float l = l_part + swap_halves(l_part);
     const bool none = m_ref == -INFINITY;              // the row saw no key: O = 0 and lse = -inf, never 0/0
-    const float inv = none ? 0.0f : 1.0f / l;
+    float inv = none ? 0.0f : 1.0f / l;
+    if constexpr (kFp8) {
+        if (a.v_scale) inv *= a.v_scale[hkv];
+    }
     if (a.lse && h == 0)
         a.lse[(size_t)hq * (size_t)a.total_q + (size_t)sq + q_row] = none ? -INFINITY : (m_ref + __log2f(l)) * kLn2;
     constexpr unsigned es = kOutF32 ? 4u : 2u;
@@ -382,5 +428,21 @@ void fa_fwd_varlen256_kernel(varlen256::Dev a)
             }
         }
 }
+
+// The one launch of a checked call: the instantiation of (types, form, element size).
+template <int kForm, bool kFp8>
+hipError_t varlen256_launch(const varlen256::Dev& a, dim3 grid, int in_dtype, int out_dtype, void* stream)
+{
+    return with_types(in_dtype, out_dtype, [&](auto t, auto f32) {
+        auto kernel = fa_fwd_varlen256_kernel<decltype(t), decltype(f32)::value, kForm, kFp8>;
+        const hipError_t attr = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), varlen256::kLdsBytes);
+        if (attr != hipSuccess) return attr;
+        FA_LAUNCH(kernel, grid, dim3(64 * kVarlenWaves), (size_t)varlen256::kLdsBytes, static_cast<hipStream_t>(stream), a);
+        return launch_status();
+    });
+}
+// fa_fwd_varlen256_fp8.hip: varlen256_launch<kContig | kPaged, true>, the fp8 unit's instantiations behind the checks of
+// fa_fwd_varlen256.hip
+hipError_t varlen256_launch_fp8(const varlen256::Dev& a, dim3 grid, int in_dtype, int out_dtype, bool paged, void* stream);
 
 }  // namespace fa

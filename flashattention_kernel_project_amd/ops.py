@@ -581,19 +581,38 @@ def fa_forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, cache_seql
     [B,Hkv,Ncap,256] or with block_table the pools [num_pages,Hkv,page_size,256], 16-bit and of q's dtype -- the cache
     fa_kvcache_decode_d256 decodes from.  Every argument, rule and result is fa_forward_varlen_kvcache's -- lengths that include the
     chunk, the causal and window limits, table entries that are never read, pages below lo_0 that may be freed, a bad live page read as
-    zeros, nothing read on the host, capture-safe -- on a kernel of its own; there are no sinks and no fp8 cache here.  On the same
-    finite keys the paged form, the contiguous form and fa_forward_varlen_d256 on the gathered K/V return the same bits."""
+    zeros, nothing read on the host, capture-safe -- on a kernel of its own; there are no sinks here, and an fp8 cache is
+    fa_forward_varlen_kvcache_d256_fp8's.  On the same finite keys the paged form, the contiguous form and fa_forward_varlen_d256 on
+    the gathered K/V return the same bits."""
     return _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out,
                            stream, lse, window, softcap, None, d256=True)
+
+
+def fa_forward_varlen_kvcache_d256_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, k_scale=None, v_scale=None,
+                                       causal: bool = False, scale: float | None = None, out_dtype=None, return_lse: bool = False,
+                                       out=None, stream=None, lse=None, window: int = 0, softcap: float = 0.0):
+    """fa_forward_varlen_kvcache_d256 against an fp8 cache (fa_forward_varlen_kvcache_d256_fp8): the cache
+    fa_kvcache_append_varlen_d256_fp8 writes and fa_kvcache_decode_d256_fp8 decodes from, so that chunked prefill and prefix caching run
+    on the codes.  k_cache, v_cache: contiguous torch.float8_e4m3fn device tensors (OCP e4m3fn; fnuz, e5m2 and 16-bit caches are
+    refused), [B,Hkv,Ncap,256] or with block_table the pools [num_pages,Hkv,page_size,256].  q stays fp16/bf16: the codes are widened
+    to its type, exactly, on the way into LDS.  k_scale, v_scale: float32 device tensors [Hkv], finite and > 0, or None for 1.0, read
+    on the device only: the logits are scale * k_scale[hkv] * q.k8 (under a soft-cap the cap sees that product) and O = v_scale[hkv] *
+    softmax.v8; lse is that of the scaled logits.  Rows at or past a sequence's length, rows below a query block's first visible key
+    and pages no visible key lies in may hold NaN codes.  Everything else -- lengths, limits, options, what is read and what a captured
+    call follows -- as in fa_forward_varlen_kvcache_d256, whose bits the call returns on the widened cache when both scales are None;
+    the paged form returns the contiguous form's bits.  No sinks."""
+    return _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out,
+                           stream, lse, window, softcap, None, scales=(k_scale, v_scale), d256=True)
 
 
 def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, causal, scale, out_dtype, return_lse, out, stream,
                     lse, window, softcap, sinks, scales=None, d256=False):
     """The varlen front ends against the KV cache: scales is None (a 16-bit cache of q's type) or (k_scale, v_scale) of an fp8 one;
-    d256 selects fa_forward_varlen_kvcache_d256, which takes d = 256 alone and no sinks."""
+    d256 selects fa_forward_varlen_kvcache_d256 (with scales: fa_forward_varlen_kvcache_d256_fp8), which takes d = 256 alone and no
+    sinks."""
     import torch
     fp8 = scales is not None
-    name8 = "fa_forward_varlen_kvcache" + "_fp8" * fp8 + "_d256" * d256
+    name8 = "fa_forward_varlen_kvcache" + "_d256" * d256 + "_fp8" * fp8
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a tensor")
@@ -670,7 +689,7 @@ def _varlen_kvcache(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_tabl
                                   out_dtype=out_dt, sinks=sink_ptr, window=window, softcap=softcap, stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, k_cache, v_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, sinks, *(scales or ()))):
         if fp8:
-            code = capi.lib().fa_forward_varlen_kvcache_fp8(desc, ks_ptr, vs_ptr)
+            code = (capi.lib().fa_forward_varlen_kvcache_d256_fp8 if d256 else capi.lib().fa_forward_varlen_kvcache_fp8)(desc, ks_ptr, vs_ptr)
         elif d256:
             code = capi.lib().fa_forward_varlen_kvcache_d256(desc)
         else:

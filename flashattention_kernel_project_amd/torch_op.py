@@ -85,6 +85,9 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.forward_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, scale, causal, window, softcap, out_f32)
     o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_d256(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, scale, causal,
                                                             window, softcap, out_f32)
+    # ... against an fp8 (e4m3fn) cache (ops.fa_forward_varlen_kvcache_d256_fp8): k_scale, v_scale follow block_table
+    o, lse = torch.ops.fa_mi355.forward_varlen_kvcache_d256_fp8(q, k_cache8, v_cache8, cu_seqlens_q, cache_seqlens, block_table, k_scale,
+                                                                v_scale, scale, causal, window, softcap, out_f32)
 """
 from __future__ import annotations
 
@@ -99,7 +102,8 @@ def register() -> None:
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
     .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256,
-    .decode_d256_fp8, .append_varlen_d256, .append_varlen_d256_fp8, .forward_varlen_d256 and .forward_varlen_kvcache_d256."""
+    .decode_d256_fp8, .append_varlen_d256, .append_varlen_d256_fp8, .forward_varlen_d256, .forward_varlen_kvcache_d256 and
+    .forward_varlen_kvcache_d256_fp8."""
     global _registered
     if _registered:
         return
@@ -350,6 +354,10 @@ def register() -> None:
            ops.fa_forward_varlen_d256, "---co", varlen_d256_kw, varlen_fake)
     define("forward_varlen_kvcache_d256", "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, "
            "Tensor? block_table, " + VARLEN_D256_TAIL, (), ops.fa_forward_varlen_kvcache_d256, "-cccco", varlen_d256_kw, varlen_fake)
+    # ... and against an fp8 cache (ops.fa_forward_varlen_kvcache_d256_fp8): `Tensor? k_scale, Tensor? v_scale` behind block_table
+    define("forward_varlen_kvcache_d256_fp8", "(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, Tensor cache_seqlens, "
+           "Tensor? block_table, Tensor? k_scale, Tensor? v_scale, " + VARLEN_D256_TAIL, (), ops.fa_forward_varlen_kvcache_d256_fp8,
+           "-ccccooo", varlen_d256_kw, varlen_fake)
 
     # the same with a tree mask (fa_kvcache_decode_varlen_ex): `Tensor tree_mask` (int64, total_q) follows block_table; causal must be True
     def decode_varlen_tree(fn):

@@ -1162,8 +1162,8 @@ int    fa_kvcache_decode_d256(const fa_kvdecode_varlen_desc* desc, int num_split
  * stays (capacity + 64) * 512 < 2^32).
  * hipErrorInvalidValue, before the device is touched: everything fa_kvcache_decode_d256 refuses, with "kv_dtype != FA_KV_16BIT,
  * non-null scales" replaced by kv_dtype != FA_KV_FP8_E4M3; a scale pointer that is not 4-byte aligned; sinks.
- * Not part of this entry: per-token scales, an fp8 Q, fp8 matrix instructions, fa_forward_varlen_kvcache_d256 on an fp8 cache (a
- * prompt is prefilled with fa_forward_varlen_d256 on the packed 16-bit K/V and written by the fp8 append).  NOT reference entry points. */
+ * Not part of this entry: per-token scales, an fp8 Q, fp8 matrix instructions.  The prefill on the same cache is
+ * fa_forward_varlen_kvcache_d256_fp8's, below.  NOT reference entry points. */
 size_t fa_kvcache_decode_d256_fp8_workspace_bytes(const fa_kvdecode_varlen_desc* desc, int num_splits);
 int    fa_kvcache_decode_d256_fp8(const fa_kvdecode_varlen_desc* desc, int num_splits);
 
@@ -1203,10 +1203,35 @@ int fa_kvcache_append_varlen_d256(const fa_kvappend_varlen_desc* desc, const fa_
  * hipErrorInvalidValue, before the device is touched: everything fa_forward_varlen_ex resp. fa_forward_varlen_kvcache refuse, with
  * "d not in {64,128}" replaced by d != 256; non-null sinks; and for the cache form the capacity bound of fa_kvcache_decode_d256,
  * (capacity + 64) * 512 >= 2^32.  fa_forward_varlen, _ex, _kvcache and _kvcache_fp8 keep refusing d = 256.
- * Not part of these entries: fp8 caches (the append and the decode at d = 256 take them, above; the cache form here does not yet), sinks, the routed mixed step, a tree mask, key splits,
- * fa_merge_states at d = 256.  NOT reference entry points. */
+ * Not part of these entries: an fp8 cache (fa_forward_varlen_kvcache_d256_fp8's, below), sinks, the routed mixed step, a tree mask,
+ * key splits, fa_merge_states at d = 256.  NOT reference entry points. */
 int fa_forward_varlen_d256(const fa_varlen_desc* desc, const fa_varlen_opts* opts);   /* opts may be NULL */
 int fa_forward_varlen_kvcache_d256(const fa_varlen_kvcache_desc* desc);
+
+/* fa_forward_varlen_kvcache_d256 on an fp8 cache: chunked prefill and prefix caching on the cache fa_kvcache_append_varlen_d256
+ * (FA_KV_FP8_E4M3) writes and fa_kvcache_decode_d256_fp8 decodes from, so that append -> prefill -> decode is one serving loop on
+ * one e4m3fn cache.  The descriptor is fa_varlen_kvcache_desc as fa_forward_varlen_kvcache_d256 takes it (d = 256), K and V
+ * addressing one OCP e4m3fn byte per element: [B,Hkv,Ncap,256], or the pools [num_pages,Hkv,page_size,256] behind block_table.
+ * k_scale, v_scale: device pointers to Hkv fp32 each, 4-byte aligned, or NULL (= 1.0), read on the device so that a captured call
+ * follows them; an element's value is decode(code) * scale[h].  The caller's contract is finite scales > 0.
+ * Every rule of fa_forward_varlen_kvcache_d256 holds word for word: token-packed strided Q and O, cu_seqlens_q, seqlens_k and the
+ * table read on the device and clamped, GQA without expanded K/V, the causal mask aligned to the end of the keys, the window with
+ * and without causal, the soft-cap before the masks, lse [Hkv*G, total_q], a row without a key O = 0 and lse = -inf, tokens of no
+ * sequence never touched, pages wholly below lo_0 freeable, a bad live page read as zeros, one kernel, no workspace, nothing read on
+ * the host, paged and contiguous results bit-equal on the same finite keys.  Rows at or past Lk, rows of bad pages and rows below
+ * the lo of a 128-row query block's first row may hold the NaN codes 0x7F / 0xFF: they lie outside the buffer descriptors or are
+ * zeroed as raw bytes, and reach LDS as the code 0 (+0).
+ * The codes are widened EXACTLY to Q's type on their way into LDS and everything behind that is the 16-bit entry's arithmetic:
+ *   s_j = (scale * k_scale[h]) * q . code_j      O = v_scale[h] * sum_j softmax(s)_j * code_j
+ * The factor is clamped after the product (scale = 0 still gives uniform weights); under the soft-cap k_scale multiplies the score
+ * before the cap; v_scale joins 1 / l.  With both scales NULL the result has the bits of fa_forward_varlen_kvcache_d256 on the
+ * widened cache.
+ * hipErrorInvalidValue, before the device is touched: everything fa_forward_varlen_kvcache_d256 refuses -- the capacity bound stays
+ * (capacity + 64) * 512 >= 2^32, so both entries take the same descriptors; K and V are judged at one byte per element -- and a
+ * scale pointer that is not 4-byte aligned.  fa_forward_varlen_kvcache_fp8 keeps refusing d = 256.
+ * Not part of this entry: per-token or per-page scales, an fp8 Q, fp8 matrix instructions, a packed fp8 source, sinks, the routed
+ * mixed step, a tree mask, key splits.  NOT a reference entry point. */
+int fa_forward_varlen_kvcache_d256_fp8(const fa_varlen_kvcache_desc* desc, const float* k_scale, const float* v_scale);
 
 /* Stage-level debug entry (cf. the reference's single-stage experiments
  * FlashAttention/t16/ *debug*.cu): one stage of the tiled forward with its result in memory, through

@@ -8,8 +8,14 @@ does falls on all alike:
            softmax(mask(cap(scale * q K^T))) V as two 16-bit matmuls over the G heads of a group; the mask is made outside the timing
   d128     (b) a yardstick, not a contender: this library's d = 128 varlen entry on the same bytes seen as 2 * Hkv K/V heads and
            2 * Hq query heads of 128 -- the same matrix FLOPs, twice the exponentials
+With --fp8 (profiles/varlen_d256_fp8.txt) the cache shapes are timed on an e4m3fn cache instead (quantize_kv_fp8 of the 16-bit
+one, per-head scales):
+  fp8      fa_forward_varlen_kvcache_d256_fp8 on the codes
+  fp8'     the same call once more: the A/A pair
+  d256     fa_forward_varlen_kvcache_d256 on the 16-bit cache of the same keys
+  widen    the only route before the entry: cache.to(dtype) of K and V, then that call
     python tools/varlen256_bench.py [--G 2 4] [--types f16 bf16] [--shapes packed chunk0 chunk4096 chunk32768 gemma]
-                                    [--forms contig paged] [--rounds 5 --iters 3] [--out FILE]
+                                    [--forms contig paged] [--rounds 5 --iters 3] [--fp8] [--out FILE]
 Shapes: Hkv 8, 16 sequences; "packed" is 16 x 2048 self-attention; "chunkP" is a 512-row chunk per sequence over P cached keys, as a
 contiguous cache and on pages of 16; "gemma" is chunk32768 with W = 4096 and softcap 50.  One line per contender: the median over the
 rounds of the time per call (device events around `iters` calls), the spread of the rounds, and TFLOP/s over the visible (row, key)
@@ -34,6 +40,7 @@ def main():
     ap.add_argument("--forms", nargs="+", default=["contig", "paged"])
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--fp8", action="store_true", help="the e4m3fn cache section: the cache shapes alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -72,7 +79,7 @@ def main():
             say(f"  {name:6s} {med:11.1f} us/call ({min(t):.1f} .. {max(t):.1f})  x{med / statistics.median(base):.3f} of {variants[0][0]} "
                 f"(per round {min(ratios):.3f} .. {max(ratios):.3f})  {flops / med * 1e-6:7.1f} TFLOP/s")
 
-    say(f"varlen prefill at d = 256, Hkv={HKV}, {B} sequences, causal, rounds={args.rounds} iters={args.iters} page={PAGE} ({fa.version()})")
+    say(f"varlen prefill at d = 256{' on an e4m3fn cache' * args.fp8}, Hkv={HKV}, {B} sequences, causal, rounds={args.rounds} iters={args.iters} page={PAGE} ({fa.version()})")
     for typ in args.types:
         tdt = torch.float16 if typ == "f16" else torch.bfloat16
         for shape in args.shapes:
@@ -87,6 +94,8 @@ def main():
             pairs = int(seen.sum())
             first = max(0, P + 1 - W) if W else 0
             mask = torch.zeros((Lq, L - first), device="cuda", dtype=tdt).masked_fill_(~seen[:, first:], float("-inf"))
+            if args.fp8 and shape == "packed":
+                continue   # there is no packed e4m3fn source
             for form in (["packed"] if shape == "packed" else args.forms):
                 k, v = (torch.randn(B, HKV, L, D, device="cuda", dtype=tdt) for _ in range(2))
                 # the same bytes as 2 * Hkv heads of 128: every row of 256 is two rows of 128 of two heads
@@ -102,6 +111,8 @@ def main():
                     k128, v128 = as128(k), as128(v)
                 else:
                     k128, v128 = as128(k), as128(v)
+                if args.fp8:
+                    (k8, ks), (v8, vs) = fa.quantize_kv_fp8(k), fa.quantize_kv_fp8(v)
                 for G in args.G:
                     Hq = HKV * G
                     q = torch.randn(B * Lq, Hq, D, device="cuda", dtype=tdt)
@@ -136,9 +147,23 @@ def main():
                             res.append(torch.matmul(torch.softmax(s + mask, dim=-1), vv[:, None]))
                         return res
 
-                    run(f"{typ} {shape} {form} G{G}: {B} x {Lq} rows over {P} cached keys, W={W} softcap={cap}",
+                    def fp8(q=q, out=out):
+                        return fa.fa_forward_varlen_kvcache_d256_fp8(q, k8, v8, cu, lens, block_table=table, k_scale=ks, v_scale=vs,
+                                                                     causal=True, window=W, softcap=cap, out=out)
+
+                    def widen(q=q, out=out):
+                        return fa.fa_forward_varlen_kvcache_d256(q, k8.to(tdt), v8.to(tdt), cu, lens, block_table=table, causal=True,
+                                                                 window=W, softcap=cap, out=out)
+
+                    title = f"{typ} {shape} {form} G{G}: {B} x {Lq} rows over {P} cached keys, W={W} softcap={cap}"
+                    if args.fp8:
+                        run(title, [("fp8", fp8), ("fp8'", fp8), ("d256", d256), ("widen", widen)], 4.0 * D * pairs * B * Hq)
+                        continue
+                    run(title,
                         [("d256", d256), ("d256'", d256), ("torch", torch_route), ("d128", d128)], 4.0 * D * pairs * B * Hq)
                 del k, v, k128, v128
+                if args.fp8:
+                    del k8, v8
                 torch.cuda.empty_cache()
     if sink:
         sink.close()
