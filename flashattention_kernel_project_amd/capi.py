@@ -284,6 +284,9 @@ def _signatures() -> dict:
         "fa_mla_decode_fp8_workspace_bytes": (sz, [C.POINTER(MlaDecodeDesc)]),
         "fa_mla_decode_fp8": (i, [C.POINTER(MlaDecodeDesc), vp]),
         "fa_mla_append_fp8": (i, [C.POINTER(MlaAppendDesc), vp]),
+        # fa_mla_decode with per-token key index lists: the descriptor as it is, then indices (device int32), topk, idx_stride_t
+        "fa_mla_decode_sparse_workspace_bytes": (sz, [C.POINTER(MlaDecodeDesc), i]),
+        "fa_mla_decode_sparse": (i, [C.POINTER(MlaDecodeDesc), vp, i, C.c_longlong]),
         # fa_kvcache_decode_varlen's descriptor with d = 256, on a kernel of its own; then num_splits (0: the library's choice)
         "fa_kvcache_decode_d256_workspace_bytes": (sz, [C.POINTER(KvDecodeVarlenDesc), i]),
         "fa_kvcache_decode_d256": (i, [C.POINTER(KvDecodeVarlenDesc), i]),

@@ -327,6 +327,14 @@ FA_EXPORT int fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_s
 {
     return (int)fa::mla_append_fp8_dispatch(desc, c_scale);
 }
+FA_EXPORT size_t fa_mla_decode_sparse_workspace_bytes(const fa_mla_decode_desc* desc, int topk)
+{
+    return fa::mla_sparse_workspace_bytes(desc, topk);
+}
+FA_EXPORT int fa_mla_decode_sparse(const fa_mla_decode_desc* desc, const int* indices, int topk, long long idx_stride_t)
+{
+    return (int)fa::mla_sparse_dispatch(desc, indices, topk, idx_stride_t);
+}
 
 FA_EXPORT int fa_merge_states(const fa_merge_desc* desc) { return (int)fa::merge_states_dispatch(desc); }
 

@@ -246,6 +246,12 @@ hipError_t mla_append_dispatch(const ::fa_mla_append_desc* desc);
 hipError_t mla_decode_fp8_dispatch(const ::fa_mla_decode_desc* desc, const float* c_scale);
 hipError_t mla_append_fp8_dispatch(const ::fa_mla_append_desc* desc, const float* c_scale);
 bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size, int max_pages, int& cap, int& lg_page);
+// fa_mla_decode_sparse (fa_mla_sparse.hip): per-token key index lists over the 16-bit latent cache.  It passes fa_mla_decode's checks
+// that know neither the split count nor the grid (mla_desc_checks) and applies its split rule (mla_split_count) to its own grid.
+bool mla_desc_checks(const ::fa_mla_decode_desc* desc, int& cap, int& lg_page);
+int mla_split_count(long long base, int cap);
+hipError_t mla_sparse_dispatch(const ::fa_mla_decode_desc* desc, const int* indices, int topk, long long idx_stride_t);
+size_t mla_sparse_workspace_bytes(const ::fa_mla_decode_desc* desc, int topk);
 // fa_kvcache_decode_d256 (fa_fwd_kv256.hip): the checks and the one or two launches on fa_kvcache_decode_varlen's descriptor, which
 // must name d = 256; num_splits: 0 chooses, >= 1 forces.  fp8: fa_kvcache_decode_d256_fp8, the same checks and the same plan on an
 // e4m3fn cache (kv_dtype FA_KV_FP8_E4M3, the descriptor's scales null or 4-byte aligned), the kernels of fa_fwd_kv256_fp8.hip

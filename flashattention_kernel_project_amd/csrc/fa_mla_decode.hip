@@ -25,16 +25,9 @@ bool mla_geometry(const int* block_table, int Ncap, int num_pages, int page_size
     return true;
 }
 
-namespace {
-
-// What the checks leave behind: the capacity, the split count and the grid, from host integers alone.
-struct MlaPlan {
-    int cap, lg_page, S, nqb;
-    bool paged;
-};
-
 // The number of splits for a shape: enough workgroups for two per CU of a 256-CU device -- one workgroup is resident per CU at
 // 144 KiB of LDS -- but at least four 64-key tiles per split.  The split stream's rule (split_count) on this kernel's figures.
+// fa_mla_decode_sparse (fa_mla_sparse.hip) applies it to its own grid with topk in the capacity's place.
 int mla_split_count(long long base, int cap)
 {
     const int tiles = (cap + mla::kSplitTile - 1) / mla::kSplitTile;
@@ -46,8 +39,8 @@ int mla_split_count(long long base, int cap)
     return (tiles + chunk_tiles - 1) / chunk_tiles;
 }
 
-// every check that needs no workspace; on success the plan is filled in
-bool mla_plan(const ::fa_mla_decode_desc* d, MlaPlan& p)
+// every check of the descriptor that knows neither the split count nor the grid: shared with fa_mla_decode_sparse
+bool mla_desc_checks(const ::fa_mla_decode_desc* d, int& cap, int& lg_page)
 {
     if (!d || d->size != sizeof(fa_mla_decode_desc)) return false;
     if (!d->Q || !d->O || !d->C || !d->cu_seqlens_q) return false;
@@ -55,10 +48,7 @@ bool mla_plan(const ::fa_mla_decode_desc* d, MlaPlan& p)
     if (d->in_dtype != FA_DTYPE_F16 && d->in_dtype != FA_DTYPE_BF16) return false;
     if (d->out_dtype != FA_OUT_F32 && d->out_dtype != FA_OUT_SAME) return false;
     if (d->causal != 0 && d->causal != 1) return false;
-    p.paged = d->block_table != nullptr;
-    if (!mla_geometry(d->block_table, d->Ncap, d->num_pages, d->page_size, d->max_pages, p.cap, p.lg_page)) return false;
-    const int tiles = (p.cap + mla::kSplitTile - 1) / mla::kSplitTile;
-    if (d->num_splits < 0 || d->num_splits > tiles) return false;
+    if (!mla_geometry(d->block_table, d->Ncap, d->num_pages, d->page_size, d->max_pages, cap, lg_page)) return false;
     const uintptr_t align = reinterpret_cast<uintptr_t>(d->Q) | reinterpret_cast<uintptr_t>(d->O) | reinterpret_cast<uintptr_t>(d->C);
     if (align & 15u) return false;
     if ((reinterpret_cast<uintptr_t>(d->cu_seqlens_q) | reinterpret_cast<uintptr_t>(d->seqlens_k) | reinterpret_cast<uintptr_t>(d->lse)) & 3u)
@@ -72,7 +62,24 @@ bool mla_plan(const ::fa_mla_decode_desc* d, MlaPlan& p)
                                   (unsigned __int128)(d->Hq - 1) * (unsigned long long)d->q_stride_h + mla::kDqk) * 2u;
     const unsigned __int128 ov = ((unsigned __int128)(rows - 1) * (unsigned long long)d->o_stride_t +
                                   (unsigned __int128)(d->Hq - 1) * (unsigned long long)d->o_stride_h + mla::kDv) * es;
-    if (qv > 0xFFFFFFFFull || ov > 0xFFFFFFFFull) return false;
+    return qv <= 0xFFFFFFFFull && ov <= 0xFFFFFFFFull;
+}
+
+namespace {
+
+// What the checks leave behind: the capacity, the split count and the grid, from host integers alone.
+struct MlaPlan {
+    int cap, lg_page, S, nqb;
+    bool paged;
+};
+
+// every check that needs no workspace; on success the plan is filled in
+bool mla_plan(const ::fa_mla_decode_desc* d, MlaPlan& p)
+{
+    if (!mla_desc_checks(d, p.cap, p.lg_page)) return false;
+    p.paged = d->block_table != nullptr;
+    const int tiles = (p.cap + mla::kSplitTile - 1) / mla::kSplitTile;
+    if (d->num_splits < 0 || d->num_splits > tiles) return false;
     const long long rows_seq = (long long)d->max_q * d->Hq;
     const long long nqb = (rows_seq + mla::kRows - 1) / mla::kRows;
     const long long base = (long long)d->B * nqb;
@@ -111,6 +118,17 @@ size_t mla_decode_workspace_bytes(const ::fa_mla_decode_desc* d)
 {
     MlaPlan p;
     return mla_plan(d, p) ? mla_ws_bytes(d, p) : 0;
+}
+
+// the 16-bit merge kernels alone, for fa_mla_decode_sparse: its partials use this workspace layout (a.nqb, a.S, a.max_q, a.Hq)
+hipError_t mla_merge_launch(const mla::Dev& a, bool bf16, bool f32, hipStream_t stream)
+{
+    const dim3 grid((unsigned)a.B * (unsigned)a.max_q * (unsigned)a.Hq), block(128);
+    if (bf16 && f32) FA_LAUNCH((fa_mla_merge_kernel<BF16, true, false>), grid, block, 0, stream, a);
+    else if (bf16) FA_LAUNCH((fa_mla_merge_kernel<BF16, false, false>), grid, block, 0, stream, a);
+    else if (f32) FA_LAUNCH((fa_mla_merge_kernel<F16, true, false>), grid, block, 0, stream, a);
+    else FA_LAUNCH((fa_mla_merge_kernel<F16, false, false>), grid, block, 0, stream, a);
+    return launch_status();
 }
 
 hipError_t mla_decode_dispatch(const ::fa_mla_decode_desc* d) { return mla_decode_any(d, false, nullptr); }

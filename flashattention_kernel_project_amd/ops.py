@@ -1654,9 +1654,48 @@ def fa_mla_decode_fp8(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens=None
                        num_splits, return_lse, out, workspace, out_dtype, stream, lse)
 
 
+def mla_decode_sparse_workspace_bytes(B: int, Hq: int, max_seqlen_q: int, topk: int, Ncap: int = 0, max_pages: int = 0,
+                                      page_size: int = 0, num_splits: int = 0) -> int:
+    """Workspace of fa_mla_decode_sparse (fa_mla_decode_sparse_workspace_bytes): mla_decode_workspace_bytes' arguments and the length
+    of a token's list.  From host integers alone -- (B, Hq, max_seqlen_q, topk, num_splits); the capacity only has to be one the call
+    accepts.  0 when one split is chosen, and 0 for a shape the call refuses."""
+    desc = capi.new_desc(capi.MlaDecodeDesc)
+    paged = bool(max_pages or page_size)
+    capi.fill(desc, Q=16, O=16, C=16, cu_seqlens_q=16, block_table=16 if paged else None, B=B, Hq=Hq, total_q=max(B, 1) * max(max_seqlen_q, 1),
+              max_q=max_seqlen_q, Ncap=0 if paged else Ncap, num_pages=1 if paged else 0, page_size=page_size, max_pages=max_pages,
+              q_stride_t=capi.MLA_DQK, q_stride_h=0, o_stride_t=capi.MLA_DC, o_stride_h=0, causal=1, num_splits=num_splits,
+              in_dtype=capi.F16, out_dtype=capi.OUT_F32)
+    return int(capi.lib().fa_mla_decode_sparse_workspace_bytes(desc, topk))
+
+
+def fa_mla_decode_sparse(q, c_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens=None, block_table=None,
+                         scale: float | None = None, causal: bool = True, num_splits: int = 0, return_lse: bool = False, out=None,
+                         workspace=None, out_dtype=None, stream=None, lse=None):
+    """fa_mla_decode where every token names its keys (fa_mla_decode_sparse): token-level sparse attention over the 16-bit latent
+    cache.  indices: int32 device tensor (total_q, topk), contiguous in its last dimension (its row stride is passed through, so a
+    slice of a wider top-k buffer goes in as it lies), 1 <= topk <= 2^20; row t is the list of token t, every head of the token
+    attends to exactly those rows.  An entry is a LOGICAL key position of the token's sequence -- what an indexer's top-k over the
+    sequence's keys returns -- not a pool slot: with block_table it goes through the table as in fa_mla_decode.
+    With L_b, n_b and c_i as in fa_mla_decode (c_i = max(0, L_b - n_b + 1 + i) with causal, else L_b), entry j is visible iff
+    0 <= j < c_i; every other value -- -1 padding, any negative number, a key the causal mask hides, INT_MAX -- is masked: nothing is
+    read for it.  The softmax runs over the visible ENTRIES: order does not matter, a key listed twice counts twice, a token with
+    no visible entry is O = 0, lse = -inf.  Cache rows no visible entry names are never read and may hold NaN.
+    num_splits: 0 (the library chooses from B, Hq, max_seqlen_q and topk), or 1 .. ceil(topk / 64) splits of the list; 1 needs no
+    workspace (mla_decode_sparse_workspace_bytes).  Everything else -- q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, scale,
+    out, lse, out_dtype and the results -- is fa_mla_decode's.  Nothing is read on the host: a captured call follows indices,
+    cu_seqlens_q, cache_seqlens and block_table when they are rewritten in place.
+    Not here: an fp8 latent cache, pool-slot indices, a per-token entry count, per-head lists, the top-k selection, window, sinks,
+    soft-cap."""
+    if indices is None:
+        raise ValueError("indices must be an int32 device tensor (total_q, topk): a call without lists is fa_mla_decode")
+    return _mla_decode("fa_mla_decode_sparse", None, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
+                       num_splits, return_lse, out, workspace, out_dtype, stream, lse, indices=indices)
+
+
 def _mla_decode(entry, fp8, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits, return_lse, out,
-                workspace, out_dtype, stream, lse):
-    """Both MLA decode front ends: fp8 is None (a cache of q's dtype) or (c_scale,) of a cache of e4m3fn codes."""
+                workspace, out_dtype, stream, lse, indices=None):
+    """The MLA decode front ends: fp8 is None (a cache of q's dtype) or (c_scale,) of a cache of e4m3fn codes; `indices` is None or
+    the (total_q, topk) lists of fa_mla_decode_sparse."""
     import torch
     if not isinstance(q, torch.Tensor) or q.dim() != 3 or q.shape[2] != capi.MLA_DQK:
         raise ValueError(f"q must be a packed tensor (total_q, Hq, {capi.MLA_DQK}): the absorbed queries")
@@ -1675,8 +1714,11 @@ def _mla_decode(entry, fp8, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     if cache_seqlens is not None and (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32
                                       or cache_seqlens.shape != (B,)):
         raise ValueError("cache_seqlens must be an int32 device tensor of B entries")
+    if indices is not None and (not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.dim() != 2
+                                or indices.shape[0] != total_q or indices.shape[1] < 1 or (indices.shape[1] > 1 and indices.stride(1) != 1)):
+        raise ValueError("indices must be an int32 device tensor (total_q, topk) with a contiguous last dimension")
     qt, qh = _packed_strides(q, "q")
-    for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)):
+    for name, t in (("q", q), ("cu_seqlens_q", cu_seqlens_q)) + ((("indices", indices),) if indices is not None else ()):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
     c_ptr = _dev_ptr(c_cache, "c_cache", (c_dtype,))
@@ -1698,8 +1740,10 @@ def _mla_decode(entry, fp8, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
     elif return_lse:
         lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
     ot, oh = _packed_strides(out, "out")
+    topk = 0 if indices is None else indices.shape[1]
     if workspace is None:
-        need = mla_decode_workspace_bytes(B, Hq, max_seqlen_q, Ncap, max_pages, page_size, num_splits)
+        need = (mla_decode_workspace_bytes(B, Hq, max_seqlen_q, Ncap, max_pages, page_size, num_splits) if indices is None else
+                mla_decode_sparse_workspace_bytes(B, Hq, max_seqlen_q, topk, Ncap, max_pages, page_size, num_splits))
         if need:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     ws_ptr, ws_len = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
@@ -1711,8 +1755,11 @@ def _mla_decode(entry, fp8, q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlen
               num_splits=num_splits, in_dtype=_in_dt(q.dtype), out_dtype=out_dt, workspace=ws_ptr, workspace_bytes=ws_len,
               stream=_stream_ptr(stream))
     with torch.cuda.device(_one_device(q, c_cache, out, cu_seqlens_q, cache_seqlens, block_table, lse, workspace,
-                                       None if fp8 is None else fp8[0])):
-        code = capi.lib().fa_mla_decode(desc) if fp8 is None else capi.lib().fa_mla_decode_fp8(desc, scale_ptr)
+                                       None if fp8 is None else fp8[0], indices)):
+        if indices is not None:   # the row stride of a one-token list addresses nothing
+            code = capi.lib().fa_mla_decode_sparse(desc, indices.data_ptr(), topk, indices.stride(0) if total_q > 1 else topk)
+        else:
+            code = capi.lib().fa_mla_decode(desc) if fp8 is None else capi.lib().fa_mla_decode_fp8(desc, scale_ptr)
     capi.check(entry, code)
     return (out, lse) if return_lse else out
 

@@ -70,6 +70,9 @@ eager fallback.  Registered on first use:
     o, lse = torch.ops.fa_mi355.mla_decode_fp8(q, c_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, c_scale, scale, causal,
                                                num_splits, out_f32)
     torch.ops.fa_mi355.mla_append_fp8(c_new, c_cache, cu_seqlens_new, cache_seqlens, seqlens_out, block_table, c_scale)
+    # mla_decode with per-token key index lists (ops.fa_mla_decode_sparse): indices int32 (total_q, topk), logical key positions
+    o, lse = torch.ops.fa_mi355.mla_decode_sparse(q, c_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale,
+                                                  causal, num_splits, out_f32)
     # decode_varlen at head dimension 256 (ops.fa_kvcache_decode_d256): no sinks; num_splits 0 = the library's choice
     o, lse = torch.ops.fa_mi355.decode_d256(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, scale, causal,
                                             window, softcap, num_splits, out_f32)
@@ -101,7 +104,7 @@ def register() -> None:
     .merge_states, .decode_shared_prefix, .forward_varlen, .forward_varlen_ex and .forward_varlen_kvcache (idempotent), and
     .forward_varlen_kvcache_fp8, .append_varlen and .append_varlen_fp8, .decode_varlen and .decode_varlen_fp8, and the tree step's
     .append_varlen_pos, .append_varlen_pos_fp8, .decode_varlen_tree, .decode_varlen_tree_fp8 and .commit, and the mixed step's
-    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8 and .mla_append_fp8, and .decode_d256,
+    .attend_varlen and .attend_varlen_fp8, and .mla_decode, .mla_append, .mla_decode_fp8, .mla_append_fp8 and .mla_decode_sparse, and .decode_d256,
     .decode_d256_fp8, .append_varlen_d256, .append_varlen_d256_fp8, .forward_varlen_d256, .forward_varlen_kvcache_d256 and
     .forward_varlen_kvcache_d256_fp8."""
     global _registered
@@ -420,6 +423,18 @@ def register() -> None:
                "(Tensor c_new, Tensor(a!) c_cache, Tensor cu_seqlens_new, Tensor? cache_seqlens, Tensor(b!)? seqlens_out, "
                "Tensor? block_table" + (", " + mid[:-2] if mid else "") + ") -> ()", ("c_cache", "seqlens_out"), append_fn, "--c",
                mla_append_kw, lambda *args: None)
+
+    # the same with per-token key index lists (ops.fa_mla_decode_sparse): indices int32 (total_q, topk) of logical key positions
+    def mla_decode_sparse_kw(q, max_seqlen_q, cache_seqlens, block_table, scale, causal, num_splits, out_f32):
+        return dict(max_seqlen_q=max_seqlen_q, cache_seqlens=opt(cache_seqlens), block_table=opt(block_table), scale=scale, causal=causal,
+                    num_splits=num_splits, out_dtype=out_dtype(q, out_f32), return_lse=True, stream=stream(q))
+
+    define("mla_decode_sparse",
+           "(Tensor q, Tensor c_cache, Tensor indices, Tensor cu_seqlens_q, int max_seqlen_q, Tensor? cache_seqlens, Tensor? block_table, "
+           "float scale, bool causal, int num_splits, bool out_f32) -> (Tensor, Tensor)", (), ops.fa_mla_decode_sparse, "-c-c",
+           mla_decode_sparse_kw,
+           lambda q, *args: (q.new_empty((q.shape[0], q.shape[1], 512), dtype=out_dtype(q, args[-1])),
+                             q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)))
 
     _registered = True
 

@@ -1115,6 +1115,42 @@ int    fa_mla_decode_fp8(const fa_mla_decode_desc* desc, const float* c_scale);
 size_t fa_mla_decode_fp8_workspace_bytes(const fa_mla_decode_desc* desc);   /* equals fa_mla_decode_workspace_bytes(desc) */
 int    fa_mla_append_fp8(const fa_mla_append_desc* desc, const float* c_scale);
 
+/* Sparse MLA decode: fa_mla_decode on a 16-bit latent cache where every token names its keys.  An indexer picks topk keys per query
+ * token and every head of that token attends to exactly those latent rows, read where they lie -- no gathered copy of the rows.
+ * The descriptor is fa_mla_decode_desc as it is.  `indices` is a device int32 array with one row per token of the packed Q: entry e
+ * of token t is indices[t * idx_stride_t + e], e < topk.  DESIGN.md 7.29, profiles/mla_sparse.txt.
+ * Rows.     s_b, e_b, n_b, L_b and c_i are fa_mla_decode's, word for word: the clamps of cu_seqlens_q, max_q, seqlens_k clamped to
+ *           the capacity, c_i = max(0, L_b - n_b + 1 + i) with causal, else L_b.
+ * Entries.  j_e = indices[(s_b + i) * idx_stride_t + e] is a LOGICAL key position of sequence b, not a pool slot: paged, it goes
+ *           through the block table as in fa_mla_decode (row j % page_size of page block_table[b, j / page_size]).  Entry e is
+ *           visible iff 0 <= j_e < c_i; every other value is masked: -1, any negative value, >= c_i, >= L_b, INT_MAX.  No address
+ *           and no table lookup is formed from a masked entry; its row reaches LDS as zeros and its logit is -inf.
+ * Arithmetic, for token s_b + i and every head h, over the visible ENTRIES (not over distinct keys):
+ *             s_e = scale * sum_{x < 576} Q[s_b + i, h, x] * C_b[j_e, x]
+ *             O[s_b + i, h, :] = sum_e softmax(s)_e * C_b[j_e, 0:512]            lse[h, s_b + i] = ln sum_e exp(s_e)
+ *           The order of a list does not matter beyond rounding.  A KEY LISTED TWICE COUNTS TWICE.  Precision is fa_mla_decode's:
+ *           16-bit matrix instructions with fp32 accumulation, fp32 softmax with the lazy reference maximum, the weights rounded to
+ *           the input type and summed rounded.  With indices[t] = 0, 1, .. L - 1, one token per sequence and one split the result
+ *           has fa_mla_decode's bits.
+ * Edges.    A token with no visible entry returns O = 0 and lse = -inf exactly.  A visible entry whose live table entry lies outside
+ *           [0, num_pages) is a key of zeros with logit 0 (fa_mla_decode's rule); no address is formed from it.
+ * Never read: index rows, Q rows and cache rows of tokens that are no live row of any sequence; cache rows no visible entry names
+ *           (they may hold NaN); table entries no visible entry maps to.  Never written: O and lse of tokens of no sequence.
+ * Host.     Nothing on the host reads device data.  Grid, split count and workspace follow (B, Hq, max_q, topk, num_splits) only, so
+ *           a captured call follows indices, cu_seqlens_q, seqlens_k and the block table when they are rewritten in place.
+ * Splits.   The list's 64-entry tiles are dealt to S splits of ceil(ceil(topk / 64) / S) * 64 entries; partials and the merge are
+ *           fa_mla_decode's.  num_splits = 1 needs no workspace; num_splits = 0 applies fa_mla_decode's rule to this entry's grid,
+ *           B * max_q * ceil(Hq / 64) workgroups, with topk in the capacity's place.  fa_mla_decode_sparse_workspace_bytes(desc,
+ *           topk) is the size the call needs: 0 with one split and 0 for anything the call would refuse.
+ * Rejected with hipErrorInvalidValue before the device is touched: everything fa_mla_decode refuses, except that num_splits is
+ * judged against [0, ceil(topk / 64)]; a NULL indices or one that is not 4-byte aligned; topk outside [1, 2^20]; idx_stride_t < topk;
+ * with more than one split a NULL, short or misaligned workspace.
+ * Not part of this entry: the fp8 latent cache (the natural follow-up; the gather is where it differs); pool-slot (physical)
+ * indices; a per-token entry count; per-head lists; the top-k selection itself; window, sinks, soft-cap.  NOT a reference entry
+ * point. */
+size_t fa_mla_decode_sparse_workspace_bytes(const fa_mla_decode_desc* desc, int topk);
+int    fa_mla_decode_sparse(const fa_mla_decode_desc* desc, const int* indices, int topk, long long idx_stride_t);
+
 /* fa_kvcache_decode_varlen at head dimension 256 (the Gemma-2 / Gemma-3 head): token-packed split-KV decode against a 16-bit KV
  * cache, contiguous [B,Hkv,Ncap,256] or pools [num_pages,Hkv,page_size,256] behind a block table, with the causal tail, the sliding
  * window and the soft-cap.  The descriptor is fa_kvdecode_varlen_desc as it is, with d = 256, and every field means what it means
